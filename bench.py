@@ -14,8 +14,10 @@ Resident before the timed region: the witness as 64-bit integer columns and hot 
     python bench.py --gpus N                # hypercube sharded over N GPUs (weak): re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N    # the same under the caller's launcher
 
-Prints ONE JSON line (rank 0) with `roofline` (bind kernel, HIP-event timed live) and `cpu_baseline` (the oracle's
-OpenMP port of the same member mix, bounded sample).  The oracle is used only for that baseline leg.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the line; --full adds what takes runs of
+its own: the per-leg split, `value_with_upload`, `roofline` (bind kernel, HIP-event timed live), `roofline_sumcheck`, `roofline_msm`, both
+round exchanges (N > 1) and `cpu_baseline` (the oracle's OpenMP port of the same member mix, bounded sample; the only use of the oracle here).
+--dump-outputs DIR writes the proof of the last timed step as DIR/<name>.npy (dump_outputs), to compare two builds output for output.
 """
 import argparse
 import json
@@ -34,7 +36,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="number of timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scale", type=int, default=22, help="log2 of the per-GPU trace length T")
     ap.add_argument("--no-msm", action="store_true", help="sumcheck legs only (BASELINE configs[1]); default: commit + open inside the step")
@@ -60,8 +62,15 @@ def parse():
     ap.add_argument("--cpu-scale", type=int, default=0, help="log2 T of the CPU baseline sample (0 = sized to ~10-30 s of CPU work)")
     ap.add_argument("--round-exchange", choices=["rccl", "shm", "both"], default="both",
                     help="N > 1: how the per-round partial sums are exchanged.  `value` is timed with RCCL (the collective north_star names) unless "
-                         "'shm' is given; 'both' (default) times the other exchange in the same run as well and prints the pair in config.round_exchange_ab")
-    return ap.parse_args()
+                         "'shm' is given; 'both' (default) with --full times the other exchange in the same run as well and prints the pair in config.round_exchange_ab")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline figure: the per-leg split, the PCIe-inclusive rate, the rooflines, the other round exchange (N > 1) and the CPU "
+                         "baseline (the --no-* switches above turn single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the proof of the last timed step as DIR/<name>.npy (float64, bit-exact: see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -307,6 +316,45 @@ def cpu_baseline(log_t, srs_dev, with_pcs, with_ext=False, gpu_scale=0):
             "published_reference": PUBLISHED_REFERENCE}
 
 
+G1_OUTPUTS = {("commit", "dense"), ("commit", "onehot"), ("open", "com"), ("open", "w")}  # the step's outputs that are G1 points, (..., 12) uint64 projective
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, ffi):
+    """What the timed step returns to its caller -- round polynomials, challenges and claims of every stage and operator, the commitments and the opening -- as
+    DIR/<key path>.npy in float64, every value exactly: integer arrays (field elements as Montgomery limbs, indices) as their 32-bit words, G1 points as the 32 bytes
+    of their compressed affine encoding (projective coordinates are not unique: equal points from two builds may differ in them), floats as they are."""
+    arrays = {}
+
+    def walk(path, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(path + (str(k),), x)
+        elif isinstance(v, (list, tuple)):
+            for k, x in enumerate(v):
+                walk(path + (str(k),), x)
+        elif isinstance(v, (np.ndarray, np.generic, int, float)):
+            a = np.asarray(v)
+            if path[-2:] in G1_OUTPUTS:
+                pts = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 12)
+                a = np.stack([np.frombuffer(ffi.host_g1_serialize_compressed(p), dtype=np.uint8) for p in pts]).reshape(a.shape[:-1] + (32,))
+            elif a.dtype.kind in "iu" and a.dtype.itemsize == 8:
+                a = np.ascontiguousarray(a).view(np.uint32)
+            elif a.dtype.kind not in "iufb":
+                raise TypeError(f"{'.'.join(path)}: no float form for dtype {a.dtype}")
+            arrays[".".join(path)] = a.astype(np.float64)
+        # anything else the step hands back (device handles, None) is not a value
+
+    walk((), out)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return len(arrays), total
+
+
 def baseline_config(world, scale, with_pcs):
     """which entry of BASELINE.json `configs` a line stands for (the driver's ladder is N = 1, 2, 4, 8 at the default --scale 22: weak scaling, 2^22 cycles per GPU)"""
     total = world << scale
@@ -403,15 +451,17 @@ def main():
             from jolt_amd.stages_sharded import ShardedExtended
             ext = ShardedExtended(ctx, args.scale, rank, world, wl.coll, tail_log=wl.tail_log, round_exchange=wl.round_exchange)
 
-        def step(label=0):  # the same legs as the N = 1 step (DeviceWorkload.step): prepare, commit, extended operators, prove, open
+        def step(label=0):  # the same legs and outputs as the N = 1 step (DeviceWorkload.step): prepare, commit, extended operators, prove, open
             wl.prepare()
+            out = {}
             if pcs_sharded is not None:
-                pcs_sharded.commit()
+                out["commit"] = pcs_sharded.commit()
             if ext is not None:
-                ext.prove(label)
-            wl.prove(label=label)
+                out["extended"] = ext.prove(label)
+            out["stages"] = wl.prove(label=label)
             if pcs_sharded is not None:
-                pcs_sharded.open(label)
+                out["open"] = pcs_sharded.open(label)
+            return out
     else:
         wl = DeviceWorkload(ctx, args.scale, pcs=pcs, extended=(args.stages == "all"), ram_addresses=args.ram_addresses, witness_upload={"resident": False, "upload": True, "upload-pinned": "pinned", "upload-overlapped": "overlapped"}[args.witness])
         if os.environ.get("JOLT_FLIP_UPLOAD") == "1":  # diagnostic: a RESIDENT-built workload switched to the overlapped upload before the timed loop (what the value_with_upload leg does)
@@ -427,7 +477,7 @@ def main():
             ctx.synchronize()
 
     def timed(steps, warmup, base):
-        """`warmup` untimed steps, then exactly `steps` steps between barrier + synchronize on both sides; max over the ranks."""
+        """`warmup` untimed steps, then exactly `steps` steps between barrier + synchronize on both sides; max over the ranks.  -> (seconds, the last step's outputs)"""
         for i in range(warmup):
             step(label=TR | (base + 1000 + i))
         barrier()
@@ -436,7 +486,7 @@ def main():
                 _D.TIMINGS[k] = 0.0
         t0 = time.perf_counter()
         for i in range(steps):
-            step(label=TR | (base + 2000 + i))
+            last = step(label=TR | (base + 2000 + i))
         barrier()
         dt = time.perf_counter() - t0
         if dist is not None:
@@ -444,27 +494,31 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if share_gpu else "cuda")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        return dt
+        return dt, last
 
     exchange_ab = None
     if sharded:
         from jolt_amd import distributed as _D
         shm = wl.round_exchange  # None when the ranks could not agree on a shared-memory segment (or JOLT_ROUND_EXCHANGE says otherwise)
         primary = "shm" if (args.round_exchange == "shm" and shm is not None) else "rccl"
-        if args.round_exchange == "both" and shm is not None and world > 1:  # the exchange that is NOT reported as `value`, timed first
+        if args.full and args.round_exchange == "both" and shm is not None and world > 1:  # the exchange that is NOT reported as `value`, timed first
             other = "shm" if primary == "rccl" else "rccl"
             wl.round_exchange = shm if other == "shm" else None
             if ext is not None:
                 ext.round_exchange = wl.round_exchange
-            exchange_ab = {other: round(timed(args.steps, args.warmup, 50000) / args.steps * 1e3, 3)}
+            exchange_ab = {other: round(timed(args.steps, args.warmup, 50000)[0] / args.steps * 1e3, 3)}
         wl.round_exchange = shm if primary == "shm" else None
         if ext is not None:
             ext.round_exchange = wl.round_exchange
     total_cycles_for_upload = 1 << args.scale
-    dt = timed(args.steps, args.warmup, 0)
+    dt, last_out = timed(args.steps, args.warmup, 0)
     if exchange_ab is not None:
         exchange_ab[primary] = round(dt / args.steps * 1e3, 3)
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        n_dumped, bytes_dumped = dump_outputs(last_out, args.dump_outputs, ffi)
+        print(f"[bench] --dump-outputs: {n_dumped} arrays, {bytes_dumped} bytes in {args.dump_outputs}", file=sys.stderr)
+    del last_out
     # where the step time goes: two more steps (outside the timed region) with a synchronisation after each leg
     split = None
     if os.environ.get("JOLT_FLIP_UPLOAD") == "after" and not sharded:  # diagnostic: the legs of a step AFTER a resident timed loop, with the overlapped upload switched on
@@ -472,7 +526,7 @@ def main():
         args.witness = "upload-overlapped"
         for i in range(3):
             step(label=TR | (90000 + i))
-    if not sharded and not args.no_split:
+    if args.full and not sharded and not args.no_split:
         ext_legs = []
         if wl.ext is not None:
             e, dd = wl.ext, wl.ext.d
@@ -505,15 +559,15 @@ def main():
     # The PCIe-inclusive rate beside the contract's `value` (never instead of it): the same K steps with every proof starting from packed rows in page-locked HOST memory,
     # the next proof's copy in flight under the current proof's kernels (jolt_rows_upload_begin; a tracer one trace ahead of the prover).  N = 1, resident default run only.
     with_upload = None
-    if pcs and not sharded and args.witness == "resident" and not args.no_upload_rate:
+    if args.full and pcs and not sharded and args.witness == "resident" and not args.no_upload_rate:
         try:
             wl.witness_upload, wl.witness_pinned, wl.witness_overlapped = True, True, True
-            dt_up = timed(args.steps, max(3, args.warmup), 70000)  # (the first proof has no copy ahead of it, the second meets a cold pool)
+            dt_up = timed(args.steps, max(3, args.warmup), 70000)[0]  # (the first proof has no copy ahead of it, the second meets a cold pool)
             bpc = wl.witness_bytes_per_cycle()
             # the resident step once more, right behind it: by now the part has run ~30 steps back to back and clocks lower than in the first timed loop, so the upload's
             # cost is the difference to THIS figure, not to `ms_per_step`
             wl.witness_upload = wl.witness_overlapped = False
-            dt_res = timed(args.steps, 1, 80000)
+            dt_res = timed(args.steps, 1, 80000)[0]
             with_upload = {"value": round(total_cycles_for_upload / (dt_up / args.steps), 1), "unit": "cycles/s", "ms_per_step": round(dt_up / args.steps * 1e3, 3),
                            "resident_ms_per_step_right_after": round(dt_res / args.steps * 1e3, 3),
                            "bytes_per_cycle": bpc, "bytes_per_step": bpc << args.scale,
@@ -617,7 +671,7 @@ def main():
                                     if pcs_sharded.block else
                                     f"term-range sharded MSMs, partial points through {type(wl.coll).__name__}; fixed-base window tables {'on' if world <= 2 else 'off (memory)'}")
         out["config"]["ms_per_step_split"] = {k: round(v / args.steps * 1e3, 3) for k, v in _D.TIMINGS.items()}
-    if rank == 0:
+    if rank == 0 and args.full:
         out["roofline"] = bind_roofline(ctx, ffi, args.roofline_scale, args.roofline_reps)
         out["roofline"]["note"] = ("measured on a 2^%d-entry table (beyond L2 + the 256 MiB Infinity Cache): an HBM figure; the binds inside the step run on 2^%d-entry "
                                    "tables (%d MiB each) and are served in part from the Infinity Cache" % (args.roofline_scale, args.scale, (32 << args.scale) >> 20))
@@ -662,6 +716,7 @@ def main():
                                                             "ratio_to_cpu": round(((1 << args.scale) / (ms * 1e-3)) / out["cpu_baseline"]["value"], 1) if out["cpu_baseline"].get("value") else None}
             except Exception as e:  # the oracle is optional infrastructure: never fail the bench on it
                 out["cpu_baseline"] = {"value": None, "unit": "cycles/s", "cores": None, "kind": "port", "sample": f"unavailable: {e}", "published_reference": PUBLISHED_REFERENCE}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -229,3 +229,37 @@ def test_concurrent_stages_prove_what_the_serial_order_proves(n_vars, contexts, 
         same(out["extended"][name], want_ext[name], f"serial {name}")
     serial.close()
     ctx.close()
+
+
+def test_plain_bench_run_is_lean_and_dumps_the_same_proof_twice(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: exactly K timed steps, the headline fields and none of what --full measures, and the last timed
+    step's proof written as float64 .npy files -- the same files, value for value, from two runs with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "12", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-1000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "cycles/s" and line["higher_is_better"] is True and line["dtype"]
+        assert line["value"] == pytest.approx((1 << 12) / (line["ms_per_step"] * 1e-3), rel=1e-3)
+        assert not {"roofline", "roofline_sumcheck", "roofline_msm", "cpu_baseline", "value_with_upload"} & set(line), sorted(line)
+        assert "ms_per_step_split" not in line["config"]
+        files = sorted(os.listdir(d))
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        for need in ("commit.dense.npy", "commit.onehot.npy", "open.com.npy", "open.w.npy", "open.v.npy"):
+            assert need in arrays, files
+        assert any(f.startswith("stages.") and f.endswith(".polys.npy") for f in files) and any(f.startswith("extended.") for f in files), files
+        assert arrays["commit.dense.npy"].shape == (2, 32)  # two dense columns, compressed affine points
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name

@@ -56,14 +56,3 @@ def test_reference_known_answers(case, impl):
             assert np.array_equal(evaluate(coeffs, m([x])[0]), m([y])[0]), case["source"]
     else:
         raise AssertionError(kind)
-
-
-def test_fixture_still_matches_the_reference_checkout():
-    """where the reference checkout exists (the build container), the committed fixture is what the extraction script produces now"""
-    if not os.path.isdir("/root/reference/crates"):
-        pytest.skip("no reference checkout on this box")
-    import subprocess
-    import sys
-    before = open(os.path.join(HERE, "golden", "reference_kats.json")).read()
-    assert subprocess.run([sys.executable, os.path.join(HERE, "golden", "extract_reference_kats.py")], capture_output=True).returncode == 0
-    assert open(os.path.join(HERE, "golden", "reference_kats.json")).read() == before

@@ -16,11 +16,11 @@ if [ "${2:-}" != "notests" ]; then
 fi
 ( timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 ) | tee "$OUT/smoke.txt"
 # the driver's command (default flags: all stages), the round-2 step for comparison, and the sumcheck legs alone (BASELINE configs[1] shape)
-timeout 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cut -c1-200 "$OUT/bench.json"
-timeout 300 python bench.py --stages 2-6b --no-cpu-baseline --no-msm-roofline --no-upload-rate --steps 10 --warmup 3 > "$OUT/bench_stages_2-6b.json" 2>/dev/null
-timeout 300 python bench.py --no-msm --stages 2-6b --scale 22 --no-cpu-baseline --steps 10 --warmup 3 > "$OUT/bench_nomsm_22.json" 2>/dev/null
-timeout 300 python bench.py --no-msm --stages 2-6b --scale 20 --no-cpu-baseline --steps 10 --warmup 3 > "$OUT/bench_nomsm_20.json" 2>/dev/null
+timeout 300 python bench.py --full --stages 2-6b --no-cpu-baseline --no-msm-roofline --no-upload-rate --steps 10 --warmup 3 > "$OUT/bench_stages_2-6b.json" 2>/dev/null
+timeout 300 python bench.py --full --no-msm --stages 2-6b --scale 22 --no-cpu-baseline --steps 10 --warmup 3 > "$OUT/bench_nomsm_22.json" 2>/dev/null
+timeout 300 python bench.py --full --no-msm --stages 2-6b --scale 20 --no-cpu-baseline --steps 10 --warmup 3 > "$OUT/bench_nomsm_20.json" 2>/dev/null
 for f in bench bench_stages_2-6b bench_nomsm_22 bench_nomsm_20; do python -c "import json,sys; d=json.loads(open('$OUT/$f.json').read().strip().splitlines()[-1]); print('$f', d['ms_per_step'], d['config'].get('ms_per_step_split'))"; done
 # kernel trace of the same step (four MSM lanes: durations overlap) and the kernel sums of one step with ONE lane (true kernel times)
 bash tools/prof_step.sh "$TAG/step" > /dev/null 2>&1
@@ -46,10 +46,10 @@ for k, v in sorted(acc.items(), key=lambda kv: -kv[1]):
 PY
 head -16 "$OUT/seq_kernel_sums.txt"
 # the witness path: every step from packed rows in page-locked host memory (PCIe-inclusive; never `value`)
-timeout 300 python bench.py --witness upload-pinned --no-cpu-baseline --no-msm-roofline --steps 10 --warmup 3 > "$OUT/bench_witness_upload.json" 2>/dev/null
+timeout 300 python bench.py --full --witness upload-pinned --no-cpu-baseline --no-msm-roofline --steps 10 --warmup 3 > "$OUT/bench_witness_upload.json" 2>/dev/null
 python -c "import json; d=json.loads(open('$OUT/bench_witness_upload.json').read().strip().splitlines()[-1]); print('witness upload', d['ms_per_step'], d['config'].get('witness'))"
 # ... and with the next proof's rows copied under the current proof (round 5)
-timeout 300 python bench.py --witness upload-overlapped --no-cpu-baseline --no-msm-roofline --steps 10 --warmup 3 > "$OUT/bench_witness_upload_overlapped.json" 2>/dev/null
+timeout 300 python bench.py --full --witness upload-overlapped --no-cpu-baseline --no-msm-roofline --steps 10 --warmup 3 > "$OUT/bench_witness_upload_overlapped.json" 2>/dev/null
 python -c "import json; d=json.loads(open('$OUT/bench_witness_upload_overlapped.json').read().strip().splitlines()[-1]); print('witness upload overlapped', d['ms_per_step'], d['config'].get('witness'))"
 # the step's own opening: what runs while no bucket sum does (profiles/open_exposed.py), min of 3 wall times
 ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/p_os && timeout 500 rocprofv3 --kernel-trace -d /tmp/p_os -o o -- python "$ROOT/tools/open_step.py" 22 1 > "$OUT/open_step.txt" 2>&1; \
@@ -67,7 +67,7 @@ bash tools/prof_extended.sh 22 70 > "$OUT/extended_kernel_stats.txt" 2>&1
 bash tools/prof_sumcheck.sh 22 "$TAG/sumcheck" > "$OUT/sumcheck.log" 2>&1
 # sharded paths with every rank on this GPU (code-path / memory checks, not measurements): bench.py --gpus 2 launching itself, the two-rank
 # 2^23-coefficient subtree opening against the oracle
-JOLT_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus 2 --scale 18 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_gpus2_share_gpu.json" 2> "$OUT/bench_gpus2.err"
+JOLT_BENCH_SHARE_GPU=1 timeout 900 python bench.py --full --gpus 2 --scale 18 --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_gpus2_share_gpu.json" 2> "$OUT/bench_gpus2.err"
 grep "^{" "$OUT/bench_gpus2_share_gpu.json" > "$OUT/bench_gpus2.tmp"; mv "$OUT/bench_gpus2.tmp" "$OUT/bench_gpus2_share_gpu.json"  # the launcher's [Gloo] chatter is not part of the line
 grep "^{" "$OUT/bench_gpus2_share_gpu.json" | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('gpus 2 (one GPU shared):', d['n_gpus'], d['ms_per_step'], d['config'].get('round_exchange_ab'), d['config']['communicator'][:80])"
 timeout 900 python tools/check_subtree_scale.py 18 > "$OUT/subtree_scale.txt" 2>&1

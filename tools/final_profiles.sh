@@ -2,9 +2,9 @@
 set -u
 OUT=/root/repo/gpurun_out/final; mkdir -p $OUT
 cd /root/repo
-timeout 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout 300 python bench.py --scale 22 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_T22.json 2>> $OUT/bench.err
-timeout 300 python bench.py --scale 24 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_T24.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --full --scale 22 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_T22.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --scale 24 --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_T24.json 2>> $OUT/bench.err
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace -d /tmp/p1 -o b -- python /root/repo/bench.py --no-cpu-baseline --steps 5 --warmup 2 > $OUT/bench_under_rocprof.json 2>/dev/null
 f=$(find /tmp/p1 -name "*.db" | head -1); [ -n "$f" ] && timeout 60 python /root/repo/profiles/summarize_rocprof.py "$f" > $OUT/bench_kernel_stats.txt
