@@ -10,7 +10,6 @@
 #include "member.hpp"
 #include "poly_kernels.hip.h"
 #include "small_round.hip.h"
-#include "engine_kernel.hip.h"
 #include "onehot_kernels.hip.h"
 
 using namespace jolt;
@@ -74,17 +73,6 @@ extern "C" int32_t jolt_ctx_create(int32_t device_id, void* stream, jolt_ctx** o
     if (const char* ml = std::getenv("JOLT_MSM_LDS_SORT")) ctx->msm_lds_sort = std::atoi(ml) != 0;
     if (const char* pe = std::getenv("JOLT_POOL")) ctx->pool_enabled = std::atoi(pe) != 0;
     if (const char* la = std::getenv("JOLT_MSM_LANES")) ctx->msm_lanes = std::max(1, std::min(4, std::atoi(la)));
-    if (const char* mb = std::getenv("JOLT_MSM_BATCH")) ctx->msm_batch = std::atoi(mb) != 0;
-    if (const char* po = std::getenv("JOLT_MSM_PAIR_OVERLAP")) ctx->msm_pair_overlap = std::atoi(po) != 0;
-    if (const char* fx = std::getenv("JOLT_MSM_FIXED")) ctx->msm_fixed = std::atoi(fx) != 0;
-    if (const char* sg = std::getenv("JOLT_MSM_STAGGER")) ctx->msm_stagger = std::atoi(sg) != 0;
-    if (const char* gr = std::getenv("JOLT_FX_REDUCE")) ctx->msm_fx_grid_reduce = std::atoi(gr) != 0;
-    if (const char* so = std::getenv("JOLT_FX_SOA")) ctx->msm_fx_soa = std::atoi(so) != 0;
-    if (const char* cs = std::getenv("JOLT_MSM_CU_SPLIT")) ctx->msm_cu_split = std::max(0, std::min(7, std::atoi(cs)));
-    if (const char* rd = std::getenv("JOLT_FX_REDUCE_DIV")) ctx->msm_fx_reduce_div = std::max(1, std::atoi(rd));
-    if (const char* fl = std::getenv("JOLT_FX_LFORM")) ctx->msm_fx_lform = std::atoi(fl) != 0;
-    if (const char* fs = std::getenv("JOLT_FX_STAGE")) ctx->msm_fx_stage = std::atoi(fs) != 0;
-    if (const char* fp = std::getenv("JOLT_FX_PARTITION")) ctx->msm_fx_partition = std::atoi(fp) == 1 ? 1 : 2;
     if (stream) {
         ctx->stream = (hipStream_t)stream;
     } else {
@@ -92,8 +80,6 @@ extern "C" int32_t jolt_ctx_create(int32_t device_id, void* stream, jolt_ctx** o
         ctx->own_stream = true;
     }
     if (hipEventCreate(&ctx->ev_begin) != hipSuccess || hipEventCreate(&ctx->ev_end) != hipSuccess) { delete ctx; return JOLT_ERR_HIP; }
-    for (hipEvent_t& e : ctx->ev_sort)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { delete ctx; return JOLT_ERR_HIP; }
     int32_t s = jolt_internal_ensure_scratch(ctx, 4096 * 8, 1024);
     if (s == JOLT_OK) {
         ctx->round_cap = 1024;
@@ -105,37 +91,8 @@ extern "C" int32_t jolt_ctx_create(int32_t device_id, void* stream, jolt_ctx** o
             s = JOLT_ERR_HIP;
         else
             *ctx->h_flag = 0;
-        // JOLT_SIDE_PRIORITY=1: the side streams above the main stream in priority -- short, latency-bound chains queued there (the dense commitments of
-        // jolt_msm_g1_tables_begin) then get their workgroups in ahead of a long kernel on the main stream instead of behind it
-        int prio_least = 0, prio_greatest = 0;
-        const char* sp = std::getenv("JOLT_SIDE_PRIORITY");
-        const bool side_high = sp && std::atoi(sp) != 0 && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) == hipSuccess && prio_greatest != prio_least;
-        (void)hipGetLastError();
-        for (int k = 0; k < 3 && s == JOLT_OK; ++k) {
-            const hipError_t ce = side_high ? hipStreamCreateWithPriority(&ctx->side[k], hipStreamNonBlocking, prio_greatest) : hipStreamCreateWithFlags(&ctx->side[k], hipStreamNonBlocking);
-            if (ce != hipSuccess) s = JOLT_ERR_HIP;
-        }
-        if (s == JOLT_OK && ctx->msm_cu_split > 0) {
-            // bit n of the mask <-> compute unit n; the split is taken inside every group of 8 consecutive bits (bits n with n mod 8 < k), which gives k of 8
-            // CUs on every XCD whether the runtime numbers the CUs XCD-major or round-robin over the XCDs.  (Round 3 tested ((n / 8) mod 8) < k, which hands out WHOLE
-            // groups of 8: under XCD-major numbering with k <= 4 the odd XCDs got no sort CUs -- profiles/r03_cu_split_ab.txt measured that partition.)
-            const int words = (ctx->num_cus + 31) / 32;
-            std::vector<uint32_t> mask_sort(words, 0u), mask_bucket(words, 0u);
-            for (int n = 0; n < ctx->num_cus; ++n) {
-                const bool sort_cu = (n % 8) < ctx->msm_cu_split;
-                (sort_cu ? mask_sort : mask_bucket)[n / 32] |= 1u << (n % 32);
-            }
-            for (int k = 0; k < 4 && s == JOLT_OK; ++k) {
-                if (hipExtStreamCreateWithCUMask(&ctx->sort_stream[k], (uint32_t)words, mask_sort.data()) != hipSuccess ||
-                    hipExtStreamCreateWithCUMask(&ctx->bucket_stream[k], (uint32_t)words, mask_bucket.data()) != hipSuccess) {
-                    (void)hipGetLastError();
-                    ctx->msm_cu_split = 0;  // the runtime refuses CU masks: keep the single-stream lanes
-                    break;
-                }
-                for (int j = 0; j < 4; ++j)
-                    if (hipEventCreateWithFlags(&ctx->ev_phase[k][j], hipEventDisableTiming) != hipSuccess) s = JOLT_ERR_HIP;
-            }
-        }
+        for (int k = 0; k < 3 && s == JOLT_OK; ++k)
+            if (hipStreamCreateWithFlags(&ctx->side[k], hipStreamNonBlocking) != hipSuccess) s = JOLT_ERR_HIP;
         if (s == JOLT_OK && hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess) s = JOLT_ERR_HIP;
         for (int k = 0; k < 3 && s == JOLT_OK; ++k)
             if (hipEventCreateWithFlags(&ctx->ev_join[k], hipEventDisableTiming) != hipSuccess) s = JOLT_ERR_HIP;
@@ -145,20 +102,13 @@ extern "C" int32_t jolt_ctx_create(int32_t device_id, void* stream, jolt_ctx** o
     return JOLT_OK;
 }
 
-void jolt_internal_engine_free(jolt_ctx* ctx);
 
 extern "C" int32_t jolt_ctx_destroy(jolt_ctx* ctx) {
     if (!ctx) return JOLT_OK;
     (void)hipSetDevice(ctx->device);
-    (void)jolt_internal_engine_quiesce(ctx);
-    jolt_internal_engine_free(ctx);
+    (void)jolt_internal_join_side_writers(ctx);
     (void)hipStreamSynchronize(ctx->stream);
     for (int k = 0; k < 3; ++k) if (ctx->side[k]) { (void)hipStreamSynchronize(ctx->side[k]); (void)hipStreamDestroy(ctx->side[k]); }
-    for (int k = 0; k < 4; ++k) {
-        if (ctx->sort_stream[k]) { (void)hipStreamSynchronize(ctx->sort_stream[k]); (void)hipStreamDestroy(ctx->sort_stream[k]); }
-        if (ctx->bucket_stream[k]) { (void)hipStreamSynchronize(ctx->bucket_stream[k]); (void)hipStreamDestroy(ctx->bucket_stream[k]); }
-        for (int j = 0; j < 4; ++j) if (ctx->ev_phase[k][j]) (void)hipEventDestroy(ctx->ev_phase[k][j]);
-    }
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     for (int k = 0; k < 3; ++k) if (ctx->ev_join[k]) (void)hipEventDestroy(ctx->ev_join[k]);
     (void)jolt_internal_pool_trim(ctx);
@@ -187,7 +137,6 @@ extern "C" int32_t jolt_ctx_destroy(jolt_ctx* ctx) {
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
     if (ctx->ev_copy_fork) (void)hipEventDestroy(ctx->ev_copy_fork);
     if (ctx->ev_end) (void)hipEventDestroy(ctx->ev_end);
-    for (hipEvent_t e : ctx->ev_sort) if (e) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return JOLT_OK;
@@ -195,7 +144,7 @@ extern "C" int32_t jolt_ctx_destroy(jolt_ctx* ctx) {
 
 extern "C" int32_t jolt_ctx_synchronize(jolt_ctx* ctx) {
     if (!ctx) return JOLT_ERR_INVALID_ARG;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     for (int k = 0; k < 3; ++k) if (ctx->side[k]) JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->side[k]));
     if (ctx->hint_stream) JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->hint_stream));
     JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -212,7 +161,7 @@ extern "C" int32_t jolt_ctx_bind_thread(jolt_ctx* ctx) {
 
 extern "C" int32_t jolt_ctx_synchronize_foreground(jolt_ctx* ctx) {
     if (!ctx) return JOLT_ERR_INVALID_ARG;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     for (int k = 0; k < 3; ++k) if (ctx->side[k]) JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->side[k]));
     JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return JOLT_OK;
@@ -336,10 +285,6 @@ int32_t jolt_internal_ensure_scratch(jolt_ctx* ctx, size_t partials, size_t resu
     return JOLT_OK;
 }
 
-static bool bool_lds_on() {
-    static const bool on = !(std::getenv("JOLT_BOOL_LDS") && std::atoi(std::getenv("JOLT_BOOL_LDS")) == 0);
-    return on;
-}
 // LDS bytes of one product group's branch tables (k_split_eq_uniform_lazy_lds): F polynomials x width x (K + 1) entries
 constexpr size_t kLazyLdsMax = 48 * 1024;
 static inline size_t lazy_lds_bytes(const jolt_member* m) {
@@ -373,7 +318,7 @@ static int32_t reduce_into_results(jolt_ctx* ctx, int nblocks, int ne, size_t sl
 }
 // copy results[0..count) to the host and wait (the protocol's per-round sync point)
 static int32_t fetch_results(jolt_ctx* ctx, size_t count, jolt_fr_t* out) {
-    (void)jolt_internal_engine_quiesce(ctx);
+    (void)jolt_internal_join_side_writers(ctx);
     JOLT_HIP_TRY(ctx, hipMemcpyAsync(ctx->h_results, ctx->d_results, count * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream));
     JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(out, ctx->h_results, count * sizeof(Fr));
@@ -468,7 +413,7 @@ extern "C" int32_t jolt_table_from_i64(jolt_ctx* ctx, const int64_t* host, size_
     return table_from_small(ctx, host, len, out, k_from_i64);
 }
 extern "C" int32_t jolt_table_download(jolt_ctx* ctx, const jolt_table* t, size_t offset, size_t len, jolt_fr_t* host) {
-    (void)jolt_internal_engine_quiesce(ctx);
+    (void)jolt_internal_join_side_writers(ctx);
     if (!ctx || !t || (!host && len)) return JOLT_ERR_INVALID_ARG;
     if (len > t->len || offset > t->len - len) return JOLT_ERR_SIZE_MISMATCH;
     if (len) {
@@ -488,7 +433,7 @@ extern "C" int32_t jolt_table_device_ptr(const jolt_table* t, void** p) {
     return JOLT_OK;
 }
 extern "C" int32_t jolt_table_free(jolt_ctx* ctx, jolt_table* t) {
-    (void)jolt_internal_engine_quiesce(ctx ? ctx : (t ? t->ctx : nullptr));
+    (void)jolt_internal_join_side_writers(ctx ? ctx : (t ? t->ctx : nullptr));
     if (!t) return JOLT_OK;
     jolt_ctx* c = t->ctx ? t->ctx : ctx;
     // no synchronisation: the blocks go back to the context's pool and are reused in stream order (ctx.hpp)
@@ -512,7 +457,7 @@ extern "C" int32_t jolt_table_slice(jolt_ctx* ctx, const jolt_table* parent, siz
     return JOLT_OK;
 }
 extern "C" int32_t jolt_table_write(jolt_ctx* ctx, jolt_table* t, size_t offset, const jolt_fr_t* host, size_t len) {
-    (void)jolt_internal_engine_quiesce(ctx);
+    (void)jolt_internal_join_side_writers(ctx);
     if (!ctx || !t || (!host && len)) return JOLT_ERR_INVALID_ARG;
     if (len > t->len || offset > t->len - len) return JOLT_ERR_SIZE_MISMATCH;
     if (len) {
@@ -559,7 +504,7 @@ static int32_t bind_ints_to_field(jolt_ctx* ctx, jolt_table* const* tables, size
 
 int32_t jolt_internal_bind(jolt_ctx* ctx, jolt_table* const* tables, size_t k, const Fr& r, int32_t order) {
     if (k == 0) return JOLT_OK;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     bool any_ints = false;
     for (size_t i = 0; i < k; ++i) {
         if (!tables[i]) return JOLT_ERR_INVALID_ARG;
@@ -1364,7 +1309,7 @@ extern "C" int32_t jolt_member_create_split_eq_product_sharded(jolt_ctx* ctx, jo
 
 // rewind a member that borrows its tables to round 0 (no device work): re-prove with fresh challenges
 extern "C" int32_t jolt_member_reset(jolt_member* m) {
-    (void)jolt_internal_engine_quiesce(m ? m->ctx : nullptr);
+    (void)jolt_internal_join_side_writers(m ? m->ctx : nullptr);
     if (!m) return JOLT_ERR_INVALID_ARG;
     if (m->onehot) {  // lazily bound member: back to the index-encoded state with the unbound scale tables
         const size_t N = m->onehot->n_polys, K = m->onehot->k;
@@ -1437,7 +1382,7 @@ static int32_t lazy_bind_enqueue(jolt_member* m, const Fr& c);
 static int32_t member_bind(jolt_member* m, const Fr& c) {
     JOLT_TRY(member_note_bind(m, c));
     if (m->lazy_width) {
-        JOLT_TRY(jolt_internal_engine_quiesce(m->ctx));
+        JOLT_TRY(jolt_internal_join_side_writers(m->ctx));
         return lazy_bind_enqueue(m, c);
     }
     return jolt_internal_bind(m->ctx, m->tables.data(), m->tables.size(), c, m->order);
@@ -1485,6 +1430,7 @@ static void launch_round_small(int ne, dim3 grid, hipStream_t s, const RoundGrou
 // publishes its sums into host-mapped memory (finish_member).
 // The main stream waits for the side streams that ran table-writing kernels in the previous batch round.
 int32_t jolt_internal_join_side_writers(jolt_ctx* ctx) {
+    if (!ctx) return JOLT_OK;  // entry points call this before they validate their handles
     for (int k = 0; k < 3; ++k) {
         if (!ctx->join_pending[k]) continue;
         JOLT_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join[k], 0));
@@ -1502,7 +1448,7 @@ static int32_t group_enqueue(jolt_ctx* ctx, jolt_member* const* members, size_t 
     if (etrace) e0 = eclk::now();
     const size_t kTailPairs = ctx->tail_pairs;
     const size_t kUniformRowsMajorPairs = ctx->uniform_rows_pairs;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));  // also joins the side streams that wrote tables last round
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));  // the side streams that wrote tables last round
     if (n > (size_t)kGroupTicket) { ctx->last_error = "batch round has too many members"; return JOLT_ERR_UNSUPPORTED; }
     {   // validate BEFORE anything is bound: an error below must leave every member exactly as it was (a caller may fall back)
         size_t sums = 0;
@@ -1683,9 +1629,9 @@ static int32_t group_enqueue(jolt_ctx* ctx, jolt_member* const* members, size_t 
             items[i].lds_blocks = (uint32_t)std::max<size_t>(1, (size_t)round_grid(ctx, (members[i]->len / 2) * members[i]->uni_V) / members[i]->uni_V);
             items[i].grid = (int)(items[i].lds_blocks * members[i]->uni_V);
         }
-        // the booleanity member's index-encoded rounds: column groups with their branch tables in LDS (k_split_eq_booleanity_lds; JOLT_BOOL_LDS=0: global gathers)
+        // the booleanity member's index-encoded rounds: column groups with their branch tables in LDS (k_split_eq_booleanity_lds)
         if (members[i]->kind == jolt_member::kSplitEqBooleanity && members[i]->lazy_width >= 1 && members[i]->lazy_width <= 8 && members[i]->onehot && !members[i]->onehot->wide &&
-            ctx->lazy_lds && bool_lds_on()) {
+            ctx->lazy_lds) {
             const size_t per_col = (size_t)members[i]->lazy_width * ((size_t)members[i]->onehot->k + 1) * sizeof(Fr), n_cols = members[i]->tables.size();
             const size_t cpg = std::min(n_cols, kLazyLdsMax / per_col);
             if (cpg >= 1) {
@@ -1915,7 +1861,7 @@ static void member_aux(const jolt_member* m, jolt_fr_t* aux) {
 }
 
 extern "C" int32_t jolt_member_prove_round(jolt_member* m, const jolt_fr_t* bind, jolt_fr_t* evals_out, size_t n_evals, jolt_fr_t* aux_out) {
-    (void)jolt_internal_engine_quiesce(m ? m->ctx : nullptr);
+    (void)jolt_internal_join_side_writers(m ? m->ctx : nullptr);
     if (!m || !evals_out) return JOLT_ERR_INVALID_ARG;
     jolt_ctx* ctx = m->ctx;
     if (n_evals != jolt_internal_member_n_evals(m)) return JOLT_ERR_SIZE_MISMATCH;
@@ -1929,309 +1875,6 @@ extern "C" int32_t jolt_member_prove_round(jolt_member* m, const jolt_fr_t* bind
     JOLT_TRY(group_enqueue(ctx, &m, 1, &bp));
     member_aux(m, aux_out);
     return round_wait(ctx, n_evals, evals_out);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Persistent round engine (engine_kernel.hip.h): host side
-// ------------------------------------------------------------------------------------------------------------------
-struct jolt_engine {
-    bool active = false;
-    std::vector<jolt_member*> members;
-    int n_rounds = 0, round = 0;
-    uint32_t binds_posted = 0;
-    size_t total = 0;  // round sums per round
-    uint64_t seq0 = 0;
-    EngDesc* h_desc = nullptr;  // pinned staging
-    EngDesc* d_desc = nullptr;
-    EngCtl* h_ctl = nullptr;    // pinned, device-mapped
-    EngSync* d_sync = nullptr;
-    Fr* d_partials = nullptr;
-    // policy (environment: JOLT_ENGINE=1 enables, JOLT_ENGINE_PAIRS=<n> sets the size at which a batch switches over).
-    // Off by default: measured within +-1 % of the per-round kernels at T = 2^20 -- the late rounds
-    // are bound by the serial multiply chain and the host<->device handshake, not by launch overhead.
-    bool enabled = false, trace = false;
-    size_t max_pairs = 1024;
-    uint32_t task_blocks = 32, max_blocks = kEngMaxBlocks;
-    // JOLT_ENGINE_TRACE: host-side split per round (ns): posted -> sums seen (device + PCIe), sums seen -> next post (host)
-    std::vector<long long> t_device, t_host;
-    long long t_last_seen = 0;
-};
-
-static jolt_engine* engine_get(jolt_ctx* ctx) {
-    if (ctx->engine) return ctx->engine;
-    jolt_engine* e = new (std::nothrow) jolt_engine();
-    if (!e) return nullptr;
-    const char* en = std::getenv("JOLT_ENGINE");
-    e->enabled = en && en[0] == '1';
-    const char* mp = std::getenv("JOLT_ENGINE_PAIRS");
-    if (mp && std::atoll(mp) > 0) e->max_pairs = (size_t)std::atoll(mp);
-    const char* tb = std::getenv("JOLT_ENGINE_TASK_BLOCKS");
-    if (tb && std::atoi(tb) > 0) e->task_blocks = (uint32_t)std::min(64, std::atoi(tb));
-    const char* mb = std::getenv("JOLT_ENGINE_MAX_BLOCKS");
-    if (mb && std::atoi(mb) > 0) e->max_blocks = (uint32_t)std::min(kEngMaxBlocks, std::atoi(mb));
-    const char* tr = std::getenv("JOLT_ENGINE_TRACE");
-    e->trace = tr && tr[0] == '1';
-    bool ok = hipHostMalloc((void**)&e->h_desc, sizeof(EngDesc), hipHostMallocDefault) == hipSuccess &&
-              hipMalloc((void**)&e->d_desc, sizeof(EngDesc)) == hipSuccess &&
-              hipHostMalloc((void**)&e->h_ctl, sizeof(EngCtl), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
-              hipMalloc((void**)&e->d_sync, sizeof(EngSync)) == hipSuccess &&
-              hipMalloc((void**)&e->d_partials, (size_t)kEngMaxSlots * kEngMaxBlocks * sizeof(Fr)) == hipSuccess;
-    if (!ok) e->enabled = false;  // the per-round kernels still work
-    ctx->engine = e;
-    return e;
-}
-
-void jolt_internal_engine_free(jolt_ctx* ctx) {
-    jolt_engine* e = ctx->engine;
-    if (!e) return;
-    if (e->h_desc) (void)hipHostFree(e->h_desc);
-    if (e->d_desc) (void)hipFree(e->d_desc);
-    if (e->h_ctl) (void)hipHostFree(e->h_ctl);
-    if (e->d_sync) (void)hipFree(e->d_sync);
-    if (e->d_partials) (void)hipFree(e->d_partials);
-    delete e;
-    ctx->engine = nullptr;
-}
-
-int32_t jolt_internal_engine_quiesce(jolt_ctx* ctx) {
-    if (ctx) JOLT_TRY(jolt_internal_join_side_writers(ctx));  // every entry point that touches tables passes through here
-    jolt_engine* e = ctx ? ctx->engine : nullptr;
-    if (!e || !e->active) return JOLT_OK;
-    __atomic_store_n(&e->h_ctl->abort, (uint64_t)1, __ATOMIC_RELEASE);
-    e->active = false;
-    JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return JOLT_OK;
-}
-
-// Post bind number `binds_posted` into its mailbox: challenge first, then both sequence copies.
-static void engine_post(jolt_engine* e, const Fr& c) {
-    EngMail& mb = e->h_ctl->mail[e->binds_posted];
-    for (int k = 0; k < 8; ++k) mb.challenge[k] = c.l[k];
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    const uint64_t seq = (uint64_t)e->binds_posted + 1;
-    __atomic_store_n(&mb.seq_b, seq, __ATOMIC_RELEASE);
-    __atomic_store_n(&mb.seq_a, seq, __ATOMIC_RELEASE);
-    e->binds_posted += 1;
-}
-
-// How many rounds the engine could take over from here (0 = not eligible).
-static int engine_eligible(jolt_ctx* ctx, jolt_engine* e, jolt_member* const* members, size_t n, const Fr* const* binds) {
-    if (!e || !e->enabled || n == 0 || n > (size_t)kEngMaxMembers) return 0;
-    const bool has_bind = binds && binds[0];
-    size_t tables = 0, slots = 0, tasks = 0;
-    int rounds = -1;
-    for (size_t i = 0; i < n; ++i) {
-        const jolt_member* m = members[i];
-        if (m->order != JOLT_ORDER_LOW_TO_HIGH || m->lazy_width || m->kind == jolt_member::kSplitEqBooleanity || m->eq_weighted) return 0;
-        if ((binds && binds[i] != nullptr) != has_bind) return 0;
-        if (has_bind && !(*binds[i] == *binds[0])) return 0;
-        size_t len = has_bind ? m->len / 2 : m->len;
-        if (len < 2 || len / 2 > e->max_pairs) return 0;
-        int r = 0;
-        while (((size_t)1 << r) < len) ++r;
-        if (((size_t)1 << r) != len) return 0;
-        if ((size_t)r != m->rounds - m->bound - (has_bind ? 1 : 0)) return 0;  // the member must run to its end
-        if (rounds < 0) rounds = r;
-        if (r != rounds) return 0;
-        for (const jolt_table* t : m->tables) if (t->len != m->len || t->ints) return 0;
-        size_t ne = jolt_internal_member_n_evals(m);
-        tables += m->tables.size();
-        slots += ne;
-        tasks += m->kind == jolt_member::kExpr ? ne : 1;
-        if (m->kind == jolt_member::kSplitEqUniform && (m->uni_F < 2 || m->uni_F > 4 || m->uni_V > (uint32_t)kMaxGroups)) return 0;
-        if (m->kind == jolt_member::kExpr && (ne > 8 || !m->all_tables_used)) return 0;  // the fused bind writes through the summand's table references
-    }
-    if (rounds < 3 || rounds > kEngMaxRounds) return 0;  // not worth a launch for one or two rounds
-    if (tables > (size_t)kEngMaxTables || slots > (size_t)kEngMaxSlots || tasks > (size_t)kEngMaxTasks || slots > ctx->round_cap) return 0;
-    return rounds;
-}
-
-static int32_t engine_start(jolt_ctx* ctx, jolt_engine* e, jolt_member* const* members, size_t n, const Fr* const* binds, int rounds) {
-    const bool has_bind = binds && binds[0];
-    EngDesc& D = *e->h_desc;
-    std::memset(&D, 0, sizeof(D));
-    D.n_members = (int32_t)n;
-    D.n_rounds = rounds;
-    D.first_has_bind = has_bind ? 1 : 0;
-    uint32_t tab = 0, slot = 0, task = 0;
-    std::vector<size_t> work;
-    for (size_t i = 0; i < n; ++i) {
-        jolt_member* m = members[i];
-        EngMember& M = D.m[i];
-        M.kind = m->kind;
-        M.n_tables = (uint32_t)m->tables.size();
-        M.tab_off = tab;
-        M.ne = (uint32_t)jolt_internal_member_n_evals(m);
-        M.slot = slot;
-        M.skip_one = m->skip_one ? 1u : 0u;
-        M.desc = m->d_desc;
-        for (jolt_table* t : m->tables) {
-            EngTable& T = D.t[tab++];
-            // capacities for the ping-pong: the first bind writes len/2 entries into the alternate buffer, the second
-            // len/4 into the other one (which a borrowed view does not own yet)
-            JOLT_TRY(jolt_internal_table_ensure_alt(t, t->len / 2));
-            const int first = t->cur < 0 ? 0 : 1 - t->cur;
-            const int second = 1 - first;
-            if (t->cap[second] < std::max<size_t>(t->len / 4, 1)) {
-                if (t->cur == second) { ctx->last_error = "round engine: table buffer smaller than its contents"; return JOLT_ERR_INVALID_ARG; }
-                if (t->buf[second]) { jolt_internal_dev_free(ctx, t->buf[second]); t->buf[second] = nullptr; t->cap[second] = 0; }
-                JOLT_TRY(jolt_internal_dev_alloc(ctx, std::max<size_t>(t->len / 4, 1) * sizeof(Fr), (void**)&t->buf[second]));
-                t->cap[second] = std::max<size_t>(t->len / 4, 1);
-            }
-            T.src = t->data();
-            T.buf[0] = t->buf[0];
-            T.buf[1] = t->buf[1];
-            T.first_out = (uint32_t)first;
-            T.len0 = (uint32_t)t->len;
-        }
-        const size_t pairs0 = (has_bind ? m->len / 2 : m->len) / 2;
-        if (m->kind == jolt_member::kExpr) {
-            for (uint32_t t = 0; t < M.ne; ++t) {
-                D.task[task] = EngTask{(uint32_t)i, t, 0, 0, slot + t, 1, (uint32_t)(pairs0 * std::max<uint32_t>(1, m->desc.n_groups))};
-                D.slot_task[slot + t] = task;
-                work.push_back(pairs0 * std::max<uint32_t>(1, m->desc.n_groups));
-                task++;
-            }
-        } else {
-            M.V = m->kind == jolt_member::kSplitEqUniform ? m->uni_V : 1;
-            M.F = m->kind == jolt_member::kSplitEqUniform ? m->uni_F : 2;
-            for (uint32_t v = 0; v < M.V && m->kind == jolt_member::kSplitEqUniform; ++v) {
-                M.coeff[v] = m->uni_prescaled ? Fr::one() : m->uni_coeff[v];
-                M.coeff_one[v] = (m->uni_prescaled || m->uni_coeff[v] == Fr::one()) ? 1u : 0u;
-            }
-            // E_out / E_in schedule (member_note_bind's bookkeeping, replayed ahead of time)
-            size_t bound = m->bound, in_bits = m->e_in_bits, out_bits = m->e_out_bits;
-            auto step = [&]() {
-                size_t ci = m->rounds - bound - 1;
-                if (m->rounds / 2 < ci && in_bits > 0) in_bits -= 1;
-                else if (0 < ci && out_bits > 0) out_bits -= 1;
-                bound += 1;
-            };
-            if (has_bind) step();
-            for (int k = 0; k < rounds; ++k) {
-                if (out_bits >= m->e_out_cache.size() || in_bits >= m->e_in_cache.size()) { ctx->last_error = "round engine: split-eq cache"; return JOLT_ERR_INVALID_ARG; }
-                M.e_out[k] = m->e_out_cache[out_bits]->data();
-                M.e_in[k] = m->e_in_cache[in_bits]->data();
-                M.in_bits[k] = (int32_t)in_bits;
-                step();
-            }
-            for (uint32_t a = 0; a < M.ne; ++a) D.slot_task[slot + a] = task;
-            D.task[task] = EngTask{(uint32_t)i, 0, 0, 0, slot, M.ne, (uint32_t)(pairs0 * M.V)};
-            work.push_back(pairs0 * M.V);
-            task++;
-        }
-        slot += M.ne;
-    }
-    D.n_tables = (int32_t)tab;
-    D.n_tasks = (int32_t)task;
-    D.n_slots = (int32_t)slot;
-    // workgroups per task: ~2 items per thread in the first engine round, 1..32 each, kEngMaxBlocks in total
-    std::vector<uint32_t> nb(task);
-    uint32_t total_blocks = 0;
-    for (uint32_t k = 0; k < task; ++k) {
-        nb[k] = eng_active_chunks((uint32_t)work[k], e->task_blocks, 0);
-        total_blocks += nb[k];
-    }
-    while (total_blocks > e->max_blocks && total_blocks > task) {
-        total_blocks = 0;
-        for (uint32_t k = 0; k < task; ++k) { nb[k] = std::max<uint32_t>(1, nb[k] / 2); total_blocks += nb[k]; }
-    }
-    uint32_t fb = 0;
-    for (uint32_t k = 0; k < task; ++k) { D.task[k].first_block = fb; D.task[k].n_blocks = nb[k]; fb += nb[k]; }
-    // control block: clear the mailboxes; the pending challenge (if any) is posted before the launch
-    std::memset(e->h_ctl, 0, sizeof(EngCtl));
-    e->binds_posted = 0;
-    if (has_bind) engine_post(e, *binds[0]);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    void* d_ctl = nullptr;
-    void *d_round = nullptr, *d_flag = nullptr;
-    JOLT_HIP_TRY(ctx, hipHostGetDevicePointer(&d_ctl, e->h_ctl, 0));
-    JOLT_HIP_TRY(ctx, hipHostGetDevicePointer(&d_round, ctx->h_round, 0));
-    JOLT_HIP_TRY(ctx, hipHostGetDevicePointer(&d_flag, ctx->h_flag, 0));
-    JOLT_HIP_TRY(ctx, hipMemcpyAsync(e->d_desc, e->h_desc, sizeof(EngDesc), hipMemcpyHostToDevice, ctx->stream));
-    JOLT_HIP_TRY(ctx, hipMemsetAsync(e->d_sync, 0, sizeof(EngSync), ctx->stream));
-    if (e->trace) {
-        const uint32_t one = 1;
-        JOLT_HIP_TRY(ctx, hipMemcpyAsync(&e->d_sync->trace, &one, sizeof(one), hipMemcpyHostToDevice, ctx->stream));
-    }
-    e->seq0 = ctx->seq + 1;
-    hipLaunchKernelGGL(k_round_engine, dim3(total_blocks), dim3(kBlock), 0, ctx->stream, (const EngDesc*)e->d_desc, (const EngCtl*)d_ctl, e->d_sync, e->d_partials,
-                       (Fr*)d_round, (uint64_t*)d_flag, e->seq0);
-    JOLT_HIP_TRY(ctx, hipGetLastError());
-    e->members.assign(members, members + n);
-    e->n_rounds = rounds;
-    e->round = 0;
-    e->total = slot;
-    e->active = true;
-    return JOLT_OK;
-}
-
-// One engine round.  Returns JOLT_OK with the sums, or `*gone = true` when the engine is no longer running (it gave up
-// waiting, or was never started): the caller then runs the round through the per-round kernels -- nothing of this round
-// has been applied to the host-side state yet.
-static int32_t engine_round(jolt_ctx* ctx, jolt_engine* e, const Fr* const* binds, jolt_fr_t* out, bool* gone, const std::function<void()>* overlap) {
-    *gone = false;
-    const bool has_bind = binds && binds[0];
-    auto now_ns = []() { return (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const long long t_post = e->trace ? now_ns() : 0;
-    if (e->trace && e->round > 0) e->t_host.push_back(t_post - e->t_last_seen);
-    if (e->round > 0) engine_post(e, *binds[0]);  // the challenge of the previous round
-    if (overlap && *overlap) (*overlap)();        // host work that does not need the sums
-    const uint64_t want = e->seq0 + (uint64_t)e->round;
-    volatile uint64_t* flag = ctx->h_flag;
-    uint64_t spins = 0;
-    while (*flag != want) {
-        if (++spins > (1ull << 20)) {
-            spins = 0;
-            hipError_t q = hipStreamQuery(ctx->stream);
-            if (q == hipSuccess) {
-                if (*flag == want) break;
-                e->active = false;  // the engine left (spin limit): not an error, the per-round kernels take over
-                *gone = true;
-                return JOLT_OK;
-            }
-            if (q != hipErrorNotReady) { e->active = false; ctx->last_error = std::string("round engine: ") + hipGetErrorString(q); return JOLT_ERR_HIP; }
-        }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    if (e->trace) { e->t_last_seen = now_ns(); e->t_device.push_back(e->t_last_seen - t_post); }
-    std::memcpy(out, ctx->h_round, e->total * sizeof(Fr));
-    ctx->d_round_count = 0;  // the engine publishes to the host only
-    ctx->seq = want;
-    // host-side bookkeeping of the bind the engine applied at the start of this round
-    if (has_bind) {
-        for (jolt_member* m : e->members) {
-            JOLT_TRY(member_note_bind(m, *binds[0]));
-            for (jolt_table* t : m->tables) {
-                t->cur = t->cur < 0 ? 0 : 1 - t->cur;
-                t->len /= 2;
-            }
-        }
-    }
-    e->round += 1;
-    if (e->round == e->n_rounds) {
-        e->active = false;  // the kernel returns by itself after its last round
-        if (e->trace) {     // per-round phase timestamps of block 0 / the publishing block, in shader cycles
-            static EngSync snap;
-            JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            JOLT_HIP_TRY(ctx, hipMemcpy(&snap, e->d_sync, sizeof(EngSync), hipMemcpyDeviceToHost));
-            std::fprintf(stderr, "[engine] host view (us): posted->seen");
-            for (long long v : e->t_device) std::fprintf(stderr, " %.1f", v / 1e3);
-            std::fprintf(stderr, " | seen->next post");
-            for (long long v : e->t_host) std::fprintf(stderr, " %.1f", v / 1e3);
-            std::fprintf(stderr, "\n");
-            e->t_device.clear();
-            e->t_host.clear();
-            for (int r = 0; r < e->n_rounds; ++r) {
-                const uint64_t* st = snap.stamps[r];
-                const uint64_t prev = r ? snap.stamps[r - 1][5] : st[0];
-                std::fprintf(stderr, "[engine] round %2d  wait %6lld  setup %6lld  task %6lld  ticket %6lld  (other block) %6lld  reduce+publish %6lld  (cycles)\n", r,
-                             (long long)(st[0] - prev), (long long)(st[1] - st[0]), (long long)(st[2] - st[1]), (long long)(st[3] - st[2]),
-                             (long long)(st[4] - st[3]), (long long)(st[5] - st[4]));
-            }
-        }
-    }
-    return JOLT_OK;
 }
 
 extern "C" int32_t jolt_round_group_prove(jolt_ctx* ctx, jolt_member* const* members, size_t n, const jolt_fr_t* const* binds, jolt_fr_t* evals_out,
@@ -2256,22 +1899,6 @@ int32_t jolt_internal_round_group_prove(jolt_ctx* ctx, jolt_member* const* membe
             JOLT_REQUIRE(ctx, fr_is_canonical(bstore[i]), "bind challenge is not a canonical Fr");
             bptr[i] = &bstore[i];
         }
-    }
-    // late rounds: the persistent round engine (no launches per round)
-    jolt_engine* eng = engine_get(ctx);
-    if (eng && eng->active) {
-        bool same = eng->members.size() == n && bptr[0] != nullptr;
-        for (size_t i = 0; same && i < n; ++i) same = eng->members[i] == members[i] && bptr[i] && *bptr[i] == *bptr[0];
-        if (!same) JOLT_TRY(jolt_internal_engine_quiesce(ctx));
-    } else if (eng) {
-        int r = engine_eligible(ctx, eng, members, n, bptr.data());
-        if (r > 0) JOLT_TRY(engine_start(ctx, eng, members, n, bptr.data(), r));
-    }
-    if (eng && eng->active) {
-        bool gone = false;
-        JOLT_TRY(engine_round(ctx, eng, bptr.data(), evals_out, &gone, overlap));
-        if (!gone) return JOLT_OK;
-        overlap = nullptr;  // already ran
     }
     if (!ctx->round_trace) {
         JOLT_TRY(group_enqueue(ctx, members, n, bptr.data()));
@@ -2316,7 +1943,7 @@ extern "C" int32_t jolt_round_group_finish(jolt_ctx* ctx, jolt_member* const* me
         while (j < n && members[j] && binds[j] && fr_from_abi(binds[j]) == b && members[j]->order == members[i]->order) {
             JOLT_TRY(member_note_bind(members[j], b));
             if (members[j]->lazy_width) {
-                JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+                JOLT_TRY(jolt_internal_join_side_writers(ctx));
                 JOLT_TRY(lazy_bind_enqueue(members[j], b));
             } else {
                 tabs.insert(tabs.end(), members[j]->tables.begin(), members[j]->tables.end());
@@ -2394,7 +2021,7 @@ static int32_t member_tables_as_fr(jolt_ctx* ctx, const jolt_member* m, TablePtr
 }
 
 extern "C" int32_t jolt_member_input_claim(jolt_member* m, jolt_fr_t* out) {
-    (void)jolt_internal_engine_quiesce(m ? m->ctx : nullptr);
+    (void)jolt_internal_join_side_writers(m ? m->ctx : nullptr);
     if (!m || !out) return JOLT_ERR_INVALID_ARG;
     jolt_ctx* ctx = m->ctx;
     int grid = sweep_grid(ctx, m->len);
@@ -2524,7 +2151,7 @@ extern "C" int32_t jolt_member_input_claim(jolt_member* m, jolt_fr_t* out) {
 }
 
 extern "C" int32_t jolt_member_destroy(jolt_member* m) {
-    (void)jolt_internal_engine_quiesce(m ? m->ctx : nullptr);
+    (void)jolt_internal_join_side_writers(m ? m->ctx : nullptr);
     if (!m) return JOLT_OK;
     jolt_ctx* ctx = m->ctx;
     // no synchronisation: everything the member owns goes back to the context's pool and is reused in stream order

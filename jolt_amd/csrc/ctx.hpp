@@ -60,13 +60,11 @@ struct jolt_ctx {
     size_t msm_batch_ws_cap = 0;
     void* msm_batch_host = nullptr;
     size_t msm_batch_host_cap = 0;
-    bool msm_batch = true;  // JOLT_MSM_BATCH=0: every short MSM on its own (A/B)
     // a pair of fixed-base MSMs over one sort (msm_fixed.hip): the first result's reduction runs here, under the second pass's bucket sums
     hipStream_t msm_aux_stream = nullptr;
     hipEvent_t ev_aux[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
     bool msm_tables_pending = false;  // between jolt_msm_g1_tables_begin and _finish: the side lanes hold MSMs in flight
     void* msm_pending_one = nullptr;  // an MSM begun by jolt_internal_msm_one_begin and not yet collected (msm.hip)
-    bool msm_pair_overlap = true;  // JOLT_MSM_PAIR_OVERLAP=0: reduction between the two passes (A/B)
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     // jolt_msm_profile_buckets: HIP events around the fixed-base MSM's dominant kernel (k_fx_buckets_ordered) ON THE STREAM IT IS LAUNCHED ON, and where the launch's
     // count of non-zero digits (= mixed additions) lives on the device -- the `roofline_msm` object of bench.py
@@ -76,15 +74,6 @@ struct jolt_ctx {
     hipEvent_t ev_fx[2] = {nullptr, nullptr};
     const uint32_t* fx_profile_info = nullptr;  // device: info[1] = non-zero digits of the profiled launch
     bool fx_profile_valid = false;
-    // Sort token (JOLT_MSM_STAGGER): the partition / sort phase of a fixed-base MSM is HBM-bound and its bucket sums are bound by
-    // integer multiply-adds, so concurrent lanes only gain when one lane's sort runs under ANOTHER lane's bucket sums.  Equal MSMs
-    // enqueued together (the three witness MSMs of an opening) would run their sorts at the same time; each sort phase therefore
-    // waits for the previous MSM's sort phase (whatever its lane) and records the next event of this ring when it is done.
-    hipEvent_t ev_sort[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned sort_seq = 0;        // sort phases recorded so far
-    int sort_last_lane = -1;      // lane of the last recorded sort phase (no wait needed on the same stream)
-    // persistent round engine for the late rounds of a batch (engine_kernel.hip.h); owned by capi.hip
-    struct jolt_engine* engine = nullptr;
     // uniform split-eq members switch from (product, pair) work items to one item per pair at this many pairs
     // (JOLT_UNIFORM_ROWS_PAIRS overrides; tests lower it to run the row-major kernels at small sizes)
     size_t uniform_rows_pairs = (size_t)1 << 16;
@@ -98,24 +87,12 @@ struct jolt_ctx {
     bool grid_hint_attr_set = false;  // k_grid_onehot_sum's dynamic-LDS limit raised on this device (pcs.hip: background class sums reserve LDS to stay at one wave per SIMD)
     bool rows_many_attr_set = false;  // k_rows_to_ints_many's dynamic-LDS limit raised on this device (onehot.hip)
     int msm_lanes = 4;            // MSM lanes used by jolt_internal_msm_many (JOLT_MSM_LANES=1: every MSM on the main stream, for standalone kernel durations)
-    int msm_fx_partition = 2;     // JOLT_FX_PARTITION=1: one-pass segment scatter (A/B of the two coalesced passes in msm_fixed.hip)
+    int msm_fx_partition = 2;     // fixed-base MSM: the two coalesced partition passes; 1 (one-pass segment scatter) once the runtime refused their LDS attribute (msm_fixed.hip)
     bool msm_uniform_scalars = false;     // set around MSMs whose scalars are UNIFORM field elements (quotients of a random linear combination, the witness polynomials of an opening): the digit sort
                                           // may then size its regions from the digit model (capacity sort, msm_fixed.hip 2d).  Level commitments do not set it: the folds of a sparse or
                                           // few-valued polynomial overflow the regions and would pay the capacity passes AND the exact sort
     bool msm_full_width_scalars = false;  // set by a caller around MSMs whose scalars are uniform field elements (the level commitments of an opening): lets mid-length ones use the mid table set
-    bool msm_fx_soa = true;          // fixed-base MSM: no key array, split entries in the partition / segment sort (JOLT_FX_SOA=0: 8-byte entries, for an A/B)
-    bool msm_fx_grid_reduce = true;  // fixed-base MSM: bucket reduction by rows and columns (JOLT_FX_REDUCE=0: running sums, for an A/B)
-    // JOLT_MSM_CU_SPLIT=k (experiment, off by default): the fixed-base MSM's HBM-bound phases (digits .. bucket order) and its bucket reduction run on
-    // streams confined to k compute units of every group of 8, its bucket sums on streams confined to the other 8 - k, so that one MSM's
-    // sort runs UNDER another MSM's bucket sums (the bucket kernel fills the VGPR file of every CU it can reach: nothing co-resides with it)
-    int msm_cu_split = 0;
-    hipStream_t sort_stream[4] = {nullptr, nullptr, nullptr, nullptr}, bucket_stream[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_phase[4][4] = {};
-    bool msm_stagger = false;     // JOLT_MSM_STAGGER=1: serialise the sort phases of concurrent fixed-base MSMs (see ev_sort)
-    int msm_fx_reduce_div = 24;   // buckets per thread of the fixed-base bucket reduction (JOLT_FX_REDUCE_DIV)
-    bool msm_fx_lform = true;     // JOLT_FX_LFORM=0: window tables in standard form, word-form XYZZ accumulators (A/B of fq_limb.hip.h)
-    bool msm_fx_stage = true;     // JOLT_FX_STAGE=0: segment sort scatters straight to global memory (A/B of the LDS-staged segment)
-    bool msm_fixed = true;        // JOLT_MSM_FIXED=0: ignore window-precomputed bases (A/B of msm_fixed.hip)
+    bool msm_fx_soa = true;          // fixed-base MSM: no key array, split entries in the partition / segment sort; false (8-byte entries) once the runtime refused their LDS attribute
     bool msm_lds_sort = true;     // MSM counting sort with per-workgroup LDS histograms (JOLT_MSM_LDS_SORT=0: global atomics per key)
     bool round_trace = false;     // JOLT_ROUND_TRACE=1: print where the host time of a batch round goes
     bool serial_streams = false;  // JOLT_SERIAL_STREAMS=1: a round's kernels on one stream (standalone kernel durations under rocprof)
@@ -131,8 +108,7 @@ struct jolt_ctx {
     size_t pool_cached_bytes = 0, pool_live_bytes = 0, pool_peak_bytes = 0;
 };
 
-// Stop a running round engine (if any) so that other work may use the stream / the members' tables.
-int32_t jolt_internal_engine_quiesce(jolt_ctx* ctx);
+// Make the main stream wait for side streams that ran a table-writing kernel (ev_join); a null context is accepted.
 int32_t jolt_internal_join_side_writers(jolt_ctx* ctx);
 
 struct jolt_table {

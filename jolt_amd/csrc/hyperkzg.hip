@@ -155,12 +155,9 @@ static __global__ __launch_bounds__(kBlock) void k_rlc(RlcArgs a, const Fr* __re
     st_fr(out + i, acc);
 }
 
-// elements per thread of the blocked suffix scan (a power of two; JOLT_SCAN_CHUNK overrides).  8 / 16 / 32 / 64 measure the same
-// (141 ms of suffix + Horner kernel time over three 2^26-coefficient openings each): the scans are not bound by their access pattern
-static int scan_chunk_log() {
-    static int v = [] { const char* e = std::getenv("JOLT_SCAN_CHUNK"); int c = e ? std::atoi(e) : 64; int lg = 0; while ((1 << (lg + 1)) <= c) ++lg; return std::max(1, std::min(8, lg)); }();
-    return v;
-}
+// log2 of the elements per thread of the blocked suffix scan: 64.  8 / 16 / 32 / 64 measure the same (141 ms of suffix + Horner kernel time over three
+// 2^26-coefficient openings each): the scans are not bound by their access pattern
+constexpr int kScanChunkLog = 6;
 // LANES interleaved chains: s[k] = a[k] + mu s[k + LANES].  LANES = 1 is the suffix Horner of a witness polynomial (kzg.rs:39-44); LANES = 2 runs the even and the odd
 // coefficients as two chains, which divides by (X^2 - mu) in ONE pass -- the pair of witness polynomials at r and -r of an opening share that quotient
 // (hyperkzg_open_impl).  A chunk is kScanChunk positions of EVERY chain (kScanChunk * LANES consecutive coefficients); heads / S hold LANES values per chunk.
@@ -212,7 +209,7 @@ int32_t suffix_scan(jolt_ctx* ctx, const Fr* a, size_t m, const Fr& mu, Fr* out,
     // a non-zero carry enters the chunk-level recurrence with the weight mu^chunk: the last chunk must be full (segments of a sharded
     // polynomial are powers of two long)
     if (!(carry == Fr::zero()) && (m & (m - 1)) != 0) return JOLT_ERR_UNSUPPORTED;
-    const int chunk_log = scan_chunk_log();
+    const int chunk_log = kScanChunkLog;
     const size_t kScanChunk = (size_t)1 << chunk_log;
     size_t nchunks = (positions + kScanChunk - 1) / kScanChunk;
     unsigned grid = (unsigned)((nchunks + kBlock - 1) / kBlock);
@@ -273,24 +270,21 @@ extern "C" int32_t jolt_hyperkzg_fold(jolt_ctx* ctx, const jolt_table* evals, co
 
 extern "C" int32_t jolt_hyperkzg_eval3(jolt_ctx* ctx, jolt_table* const* levels, size_t ell, const jolt_fr_t u[3], jolt_fr_t* v_out) {
     if (!ctx || !levels || !u || !v_out || ell == 0 || ell > 40) return JOLT_ERR_INVALID_ARG;
-    Fr3 uu, u16, u256, u4096;
+    Fr3 uu, u256, u4096;
     for (int t = 0; t < 3; ++t) {
         uu.v[t] = fr_from_abi(&u[t]);
         JOLT_REQUIRE(ctx, fr_is_canonical(uu.v[t]), "evaluation point is not a canonical Fr");
         Fr p = uu.v[t];
-        for (int i = 0; i < 4; ++i) p = sqr(p);
-        u16.v[t] = p;
-        for (int i = 0; i < 4; ++i) p = sqr(p);
+        for (int i = 0; i < 8; ++i) p = sqr(p);
         u256.v[t] = p;
         for (int i = 0; i < 4; ++i) p = sqr(p);
         u4096.v[t] = p;
     }
-    static const bool strided = !(std::getenv("JOLT_HORNER_STRIDED") && std::atoi(std::getenv("JOLT_HORNER_STRIDED")) == 0);
     const bool plus_minus = uu.v[1] == neg(uu.v[0]);
     JOLT_TRY(jolt_internal_ensure_scratch(ctx, 1, 3 * ell + 8));
     Fr* chunk_weights = nullptr;
     JOLT_TRY(jolt_internal_dev_alloc(ctx, 3 * kBlock * sizeof(Fr), (void**)&chunk_weights));
-    hipLaunchKernelGGL(k_power_table3, dim3(1), dim3(kBlock), 0, ctx->stream, strided ? uu : u16, chunk_weights);  // u^tid for the strided kernel, (u^16)^tid for the chunked one
+    hipLaunchKernelGGL(k_power_table3, dim3(1), dim3(kBlock), 0, ctx->stream, uu, chunk_weights);  // u^tid
     struct FreeWeights { jolt_ctx* c; Fr* p; ~FreeWeights() { jolt_internal_dev_free(c, p); } } free_weights{ctx, chunk_weights};  // stream-ordered: safe right after the last launch
     for (size_t j = 0; j < ell; ++j) {
         const jolt_table* t = levels[j];
@@ -298,12 +292,10 @@ extern "C" int32_t jolt_hyperkzg_eval3(jolt_ctx* ctx, jolt_table* const* levels,
         size_t per_block = (size_t)kBlock * kHornerChunk;
         int grid = (int)std::max<size_t>(1, (t->len + per_block - 1) / per_block);
         JOLT_TRY(jolt_internal_ensure_scratch(ctx, (size_t)grid * 3, 3 * ell + 8));
-        if (strided && plus_minus)
+        if (plus_minus)
             hipLaunchKernelGGL(k_horner3_strided<true>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const Fr*)t->data(), t->len, u256, (const Fr*)chunk_weights, u4096, ctx->d_partials);
-        else if (strided)
-            hipLaunchKernelGGL(k_horner3_strided<false>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const Fr*)t->data(), t->len, u256, (const Fr*)chunk_weights, u4096, ctx->d_partials);
         else
-            hipLaunchKernelGGL(k_horner3<false>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const Fr*)t->data(), t->len, uu, (const Fr*)chunk_weights, u4096, ctx->d_partials, TermMap{});
+            hipLaunchKernelGGL(k_horner3_strided<false>, dim3(grid), dim3(kBlock), 0, ctx->stream, (const Fr*)t->data(), t->len, u256, (const Fr*)chunk_weights, u4096, ctx->d_partials);
         JOLT_HIP_TRY(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kBlock), 0, ctx->stream, (const Fr*)ctx->d_partials, grid, 3, ctx->d_results + 3 * j);
         JOLT_HIP_TRY(ctx, hipGetLastError());
@@ -605,8 +597,7 @@ static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt
     if (s != JOLT_OK) { cleanup(); return s; }
     G1Jac ws[3];
     bool paired = false;
-    static const bool pair_enabled = !(std::getenv("JOLT_KZG_PAIR") && std::atoi(std::getenv("JOLT_KZG_PAIR")) == 0);
-    if (world == 1 && pair_enabled && b_poly->len >= 4) {
+    if (world == 1 && b_poly->len >= 4) {
         // The witness commitments at r and -r from ONE sorted scalar vector.  B = q (X^2 - r^2) + alpha X + beta gives h_r = (B - B(r)) / (X - r) = q (X + r) + alpha
         // and h_(-r) = q (X - r) + alpha, so with Cq = commit(q) and Cxq = commit(X q) (the same scalars against the bases shifted by one):
         //   w[0] = Cxq + r Cq + alpha G_0,   w[1] = Cxq - r Cq + alpha G_0
@@ -615,19 +606,17 @@ static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt
         // q in ONE pass over B when its length is even (every opening of >= 2 variables): q[k] = B[k + 2] + r^2 q[k + 2], two interleaved chains (suffix_scan<2>), and
         // alpha = B[1] + r^2 q[1] (the X^1 coefficient of B = q (X^2 - r^2) + alpha X + beta); otherwise two divisions, by (X - r) and then by (X + r)
         jolt_table *h0 = nullptr, *qp = nullptr, *h2 = nullptr;
-        static const bool one_pass = !(std::getenv("JOLT_KZG_QUOTIENT2") && std::atoi(std::getenv("JOLT_KZG_QUOTIENT2")) == 0);
-        static const bool early_one = !(std::getenv("JOLT_KZG_EARLY") && std::atoi(std::getenv("JOLT_KZG_EARLY")) == 0);
         bool direct = false, begun = false;
         // h at r^2 FIRST, and its MSM enqueued on the second lane at once: its digit sort (HBM bound) runs under the scan that produces q (bound by its multiplications)
         s = jolt_hyperkzg_witness_poly(ctx, b_poly, &u_abi[2], &h2);
-        if (s == JOLT_OK && early_one) {
+        if (s == JOLT_OK) {
             ctx->msm_full_width_scalars = ctx->msm_uniform_scalars = true;  // quotients of the random linear combination: uniform field elements (lets the sort use capacity regions, msm_fixed.hip 2d)
             const int32_t bs = jolt_internal_msm_one_begin(ctx, srs, b_poly->len - 2, 1, h2->data(), h2->len);
             ctx->msm_full_width_scalars = ctx->msm_uniform_scalars = false;
             if (bs == JOLT_OK) begun = true;
             else if (bs != JOLT_ERR_UNSUPPORTED) s = bs;
         }
-        if (s == JOLT_OK && one_pass && b_poly->len % 2 == 0) {
+        if (s == JOLT_OK && b_poly->len % 2 == 0) {
             s = jolt_internal_table_new(ctx, b_poly->len - 2, &qp);
             if (s == JOLT_OK) {
                 const int32_t qs = suffix_scan<2>(ctx, b_poly->data(), b_poly->len, u[2], qp->data(), 2, Fr::zero());

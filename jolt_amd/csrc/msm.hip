@@ -216,7 +216,7 @@ int32_t jolt_internal_msm_enqueue(jolt_ctx* ctx, const jolt_srs* srs, const Fr* 
     // mid-length MSMs of FULL-WIDTH scalars: the mid table set (srs.hpp).  The caller says so (hyperkzg.hip around the level commitments): 64-bit witness scalars would leave
     // its 20-bit windows a 4-bit top window whose n digits pile onto 16 buckets (measured: the commit leg 21.9 -> 29.5 ms)
     const jolt_srs* tables = (srs->mid_tables && ctx->msm_full_width_scalars && n <= srs->mid_tables->n && n >= srs->mid_tables->pre_min_n) ? srs->mid_tables : srs;
-    if (tables->pre && ctx->msm_fixed && n >= tables->pre_min_n) {  // window-precomputed bases: one bucket set for all windows (msm_fixed.hip)
+    if (tables->pre && n >= tables->pre_min_n) {  // window-precomputed bases: one bucket set for all windows (msm_fixed.hip)
         int32_t fs = jolt_internal_msm_fixed_enqueue(ctx, tables, d_scalars, n, lane, job);
         if (fs != JOLT_ERR_UNSUPPORTED) return fs;  // skewed scalars fall through to the per-window method and its heavy-bucket kernels
     }
@@ -333,7 +333,7 @@ int32_t jolt_internal_msm_enqueue_pair(jolt_ctx* ctx, const jolt_srs* srs, const
     if (shift > srs->n || n > srs->n - shift) return JOLT_ERR_SRS_TOO_SMALL;
     if (n == 0) return JOLT_OK;
     if (n >= ((size_t)1 << 31)) return JOLT_ERR_UNSUPPORTED;
-    if (!(srs->pre && ctx->msm_fixed && n >= srs->pre_min_n)) return JOLT_ERR_UNSUPPORTED;
+    if (!(srs->pre && n >= srs->pre_min_n)) return JOLT_ERR_UNSUPPORTED;
     return jolt_internal_msm_fixed_enqueue(ctx, srs, d_scalars, n, lane, job, shift);
 }
 
@@ -526,7 +526,7 @@ int32_t jolt_internal_msm_many(jolt_ctx* ctx, const jolt_srs* srs, const Fr* con
     std::vector<size_t> rest;
     for (size_t i = 0; i < count; ++i) {
         const bool prefix = !base_offsets || base_offsets[i] == 0;
-        if (ctx->msm_batch && prefix && n[i] >= 2 && n[i] <= kBatchMaxLen && n[i] <= srs->n && n_members < kBatchMax) members[n_members++] = (int)i;
+        if (prefix && n[i] >= 2 && n[i] <= kBatchMaxLen && n[i] <= srs->n && n_members < kBatchMax) members[n_members++] = (int)i;
         else rest.push_back(i);
     }
     if (n_members < 2) {  // nothing to share
@@ -559,7 +559,7 @@ int32_t jolt_internal_msm_many(jolt_ctx* ctx, const jolt_srs* srs, const Fr* con
 // JOLT_ERR_UNSUPPORTED, with nothing enqueued, when the pair cannot take the fixed-base method.
 int32_t jolt_internal_msm_pair_and_one(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_a, size_t n_a, size_t shift, const Fr* d_b, size_t n_b, G1Jac* out) {
     if (shift > srs->n || n_a > srs->n - shift) return JOLT_ERR_SRS_TOO_SMALL;
-    if (n_a == 0 || !(srs->pre && ctx->msm_fixed && n_a >= srs->pre_min_n) || ctx->msm_tables_pending) return JOLT_ERR_UNSUPPORTED;
+    if (n_a == 0 || !(srs->pre && n_a >= srs->pre_min_n) || ctx->msm_tables_pending) return JOLT_ERR_UNSUPPORTED;
     JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
     for (int k = 0; k < 3; ++k) JOLT_HIP_TRY(ctx, hipStreamWaitEvent(ctx->side[k], ctx->ev_fork, 0));
     MsmJob pair, one;
@@ -584,7 +584,7 @@ struct MsmPendingOne {
 };
 int32_t jolt_internal_msm_one_begin(jolt_ctx* ctx, const jolt_srs* srs, size_t n_a, size_t shift, const Fr* d_b, size_t n_b) {
     if (shift > srs->n || n_a > srs->n - shift) return JOLT_ERR_SRS_TOO_SMALL;
-    if (n_a == 0 || !(srs->pre && ctx->msm_fixed && n_a >= srs->pre_min_n) || ctx->msm_lanes < 2 || ctx->msm_pending_one || ctx->msm_tables_pending) return JOLT_ERR_UNSUPPORTED;
+    if (n_a == 0 || !(srs->pre && n_a >= srs->pre_min_n) || ctx->msm_lanes < 2 || ctx->msm_pending_one || ctx->msm_tables_pending) return JOLT_ERR_UNSUPPORTED;
     if ((size_t)srs->pre_W * n_a >= ((size_t)1 << 32)) return JOLT_ERR_UNSUPPORTED;  // what jolt_internal_msm_fixed_enqueue would refuse for the pair
     MsmPendingOne* p = new (std::nothrow) MsmPendingOne();
     if (!p) return JOLT_ERR_OOM;
@@ -640,7 +640,7 @@ extern "C" int32_t jolt_msm_g1_tables_begin(jolt_ctx* ctx, const jolt_srs* srs, 
         if (n[i] > scalars[i]->len) return JOLT_ERR_SIZE_MISMATCH;
         if (n[i] > srs->n) return JOLT_ERR_SRS_TOO_SMALL;
     }
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     jolt_msm_pending* p = new (std::nothrow) jolt_msm_pending();
     if (!p) return JOLT_ERR_OOM;
     int32_t status = JOLT_OK;

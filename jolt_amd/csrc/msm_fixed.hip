@@ -11,16 +11,16 @@
 //
 // Pipeline (integer VALU work, no MFMA; DESIGN.md 3.5c has the measurements):
 //   1. histogram: k_fx_hist_scalars -- the W signed c-bit digits of every scalar (scalars above r/2 negated, unsigned top window) recomputed from the scalar
-//                 itself and counted per SEGMENT of 256 buckets in per-workgroup LDS histograms; no key array (the 8-byte-entry path behind JOLT_FX_SOA=0
-//                 keeps k_fx_digits / k_fx_hist)
+//                 itself and counted per SEGMENT of 256 buckets in per-workgroup LDS histograms; no key array (the 8-byte-entry path, for segments
+//                 other than 8 bits or a refused LDS attribute, keeps k_fx_digits / k_fx_hist)
 //   2. partition: two coalesced passes -- groups of 128 segments straight from the scalars (k_fx_partition_groups_scalars), then the segments of each group
 //                 (k_fx_partition_segments_soa): a workgroup ranks a tile by bin with LDS atomics, lays it out bin-major in LDS and copies it out; entries travel
 //                 as 4-byte base index | sign plus one byte of bucket-in-segment
 //   3. segments : ONE workgroup per segment sorts it by bucket INSIDE the LDS of its CU and copies the sorted base indices out coalesced
 //                 (k_fx_segment_sort_staged), emitting the bucket table, the heavy list and the length classes
 //   4. order    : buckets handed out in order of decreasing list length (k_fx_order): a wavefront's lanes sum lists of equal length
-//   5. buckets  : one lane per bucket, XYZZ accumulator in limb form over the L-form tables (k_fx_buckets_ordered); over-full buckets (repeated scalars, the
-//                 carry window of 64-bit witness scalars) as segments of 128 entries, one lane each, folded per bucket (k_fx_heavy_segments / _combine)
+//   5. buckets  : one lane per bucket, XYZZ accumulator in limb form over the L-form tables (k_fx_buckets_ordered_staged); over-full buckets (repeated scalars, the
+//                 carry window of 64-bit witness scalars) as segments of 128 entries, one lane each, folded per bucket (k_fx_heavy_segments_staged / k_fx_heavy_combine)
 //   6. reduce   : sum_b b * B_b by rows and columns of the bucket matrix (k_fx_red_cols / _rows / _fold) and two small running-sum reductions
 // With pair_shift the phases 5-6 run twice over the same sorted lists, the second time against the tables moved by pair_shift points (two MSMs over one set of
 // scalars: the witness commitments at r and -r of a HyperKZG opening).
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(kSortBlock) void k_fx_scatter(const uint32_t* __res
     }
 }
 
-// ---- 2b. the same partition in two coalesced passes (JOLT_FX_PARTITION=2, the default) ---------------------------------------
+// ---- 2b. the same partition in two coalesced passes (the default; the one-pass scatter stays for a refused LDS attribute) ---------------------------------------
 // k_fx_scatter writes each 8-byte entry to one of 16385 open segments: with (slices x segments) write fronts nothing merges in L2 and
 // the 5.4 GB of entries go out as isolated 8-byte stores (14.6 ms at 2^26 terms, c = 26).  Here a workgroup takes a tile of 8192
 // entries, ranks them by bin with LDS atomics, lays the tile out bin-major in LDS and copies it out so that adjacent lanes write
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(kPartThreads) void k_fx_partition_segments(const ui
 }
 
 
-// ---- 2c. the same two passes WITHOUT a key array and with split entries (JOLT_FX_SOA, the default for 8-bit segments) --------------
+// ---- 2c. the same two passes WITHOUT a key array and with split entries (the default for 8-bit segments) --------------
 // The digit / histogram / partition / segment-sort phases move ~49 GB per 2^26-term MSM in the form above (4-byte keys written once and read
 // twice, 8-byte entries written twice and read up to five times) and run at the HBM rate.  Here the digits are recomputed from the scalars
 // where they are needed (one Montgomery multiply per scalar: free next to 32 bytes of traffic), the histogram is fused into the digit
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(kPartThreads) void k_fx_partition_segments_soa(cons
     }
 }
 
-// ---- 2d. the same sort WITHOUT the histogram pass, for scalars the caller knows to be uniform field elements (round 5; JOLT_FX_CAPACITY=0 switches it off) ----------
+// ---- 2d. the same sort WITHOUT the histogram pass, for scalars the caller knows to be uniform field elements (round 5) ----------
 // The histogram pass exists to give every segment its exact place; for uniform scalars the digit counts are predictable -- a bucket below 2^(c-1) collects the signed
 // digits of W - 1 windows (2 (W - 1) n / 2^c on average) and, up to top_max, the unsigned top window (n / top_max) -- so every segment gets a REGION of its expected size
 // plus 8 standard deviations and 64 entries, the two partition passes run straight from the cursors of those regions, the counts fall out of the cursors afterwards, and
@@ -846,19 +846,7 @@ __global__ __launch_bounds__(kBlock) void k_fx_order(const uint32_t* __restrict_
 }
 
 // ---- 4. light buckets in that order (the heavy ones keep k_msm_buckets_heavy / _heavy_combine) ---------------------------
-template <bool LFORM>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(JOLT_BUCKET_WAVES, JOLT_BUCKET_WAVES))) void k_fx_buckets_ordered(
-    const uint32_t* __restrict__ order, uint32_t n_buckets, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ sorted,
-    const G1Affine* __restrict__ bases, uint32_t heavy_threshold, G1Jac* __restrict__ buckets, LformConsts lc) {
-    const uint32_t gt = blockIdx.x * kBlock + threadIdx.x;
-    if (gt >= n_buckets) return;
-    const uint32_t slot = order[gt];
-    const uint32_t cnt = hist[slot];
-    if (cnt == 0 || cnt > heavy_threshold) return;  // empty: the memset identity stands; heavy: the segmented kernels own it
-    buckets[slot] = LFORM ? sum_bucket_points_lform(sorted + offsets[slot], bases, 0u, cnt, 1u, lc) : sum_bucket_points<true>(sorted + offsets[slot], bases, 0u, cnt, 1u);
-}
-// ... with the base indices staged through LDS (msm_kernels.hip.h: sum_bucket_points_lform_staged) -- the default for L-form tables; JOLT_FX_STAGE_IDX=0 keeps the
-// kernel above for an A/B.  kFxIdxChunk indices per lane and refill: 32 = one 128-byte line; 3 workgroups of 256 lanes per CU hold 96 KB of the CU's 160 KB.
+// The base indices are staged through LDS (msm_kernels.hip.h: sum_bucket_points_lform_staged).  kFxIdxChunk indices per lane and refill: 32 = one 128-byte line; 3 workgroups of 256 lanes per CU hold 96 KB of the CU's 160 KB.
 constexpr int kFxIdxChunk = 32;
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(JOLT_BUCKET_WAVES, JOLT_BUCKET_WAVES))) void k_fx_buckets_ordered_staged(
     const uint32_t* __restrict__ order, uint32_t n_buckets, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ sorted,
@@ -884,18 +872,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(JOLT_BUC
 }
 
 // ---- 4b. heavy buckets: one lane per kFxHeavySeg-entry segment, then one wavefront per bucket over its segment sums -------------
-template <bool LFORM>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(JOLT_BUCKET_WAVES, JOLT_BUCKET_WAVES))) void k_fx_heavy_segments(
-    const uint32_t* __restrict__ heavy_list, const uint32_t* __restrict__ heavy_count, uint32_t heavy_cap, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ offsets,
-    const uint32_t* __restrict__ sorted, const G1Affine* __restrict__ bases, G1Jac* __restrict__ seg_sums, LformConsts lc) {
-    const uint32_t total = min(*heavy_count, heavy_cap);
-    for (uint32_t h = blockIdx.x * kBlock + threadIdx.x; h < total; h += gridDim.x * kBlock) {
-        const uint32_t slot = heavy_list[2 * h], sgi = heavy_list[2 * h + 1];
-        const uint32_t cnt = hist[slot], lo = sgi * kFxHeavySeg, len = min(kFxHeavySeg, cnt - lo);
-        const uint32_t* src = sorted + offsets[slot] + lo;
-        seg_sums[h] = LFORM ? sum_bucket_points_lform(src, bases, 0u, len, 1u, lc) : sum_bucket_points<true>(src, bases, 0u, len, 1u);
-    }
-}
 __global__ __launch_bounds__(kBlock) void k_fx_heavy_combine(const uint32_t* __restrict__ heavy_list, const uint32_t* __restrict__ heavy_count, uint32_t heavy_cap,
                                                             const uint32_t* __restrict__ hist, const G1Jac* __restrict__ seg_sums, G1Jac* __restrict__ buckets) {
     const uint32_t lane = threadIdx.x & 63, wave = (blockIdx.x * kBlock + threadIdx.x) >> 6, n_waves = gridDim.x * (kBlock / 64);
@@ -979,8 +955,7 @@ extern "C" int32_t jolt_srs_precompute_windows(jolt_ctx* ctx, jolt_srs* srs, uin
     JOLT_TRY(fx_precompute_into(ctx, srs, window_bits, min_terms));
     // the mid table set (srs.hpp): only next to a main set with the wide default windows over >= 2^25 points, whose own crossover lies above the mid set's
     constexpr size_t kMidN = (size_t)1 << 23, kMidMin = (size_t)1 << 19;
-    const char* mid = std::getenv("JOLT_MSM_MID");
-    if (window_bits == 0 && srs->n >= 4 * kMidN && srs->pre_c >= 23 && srs->pre_min_n > kMidMin && !(mid && std::atoi(mid) == 0) && !srs->mid_tables) {
+    if (window_bits == 0 && srs->n >= 4 * kMidN && srs->pre_c >= 23 && srs->pre_min_n > kMidMin && !srs->mid_tables) {
         jolt_srs* mt = new (std::nothrow) jolt_srs();
         if (!mt) return JOLT_ERR_OOM;
         mt->ctx = ctx;
@@ -1023,8 +998,7 @@ static int32_t fx_precompute_into(jolt_ctx* ctx, jolt_srs* srs, uint32_t window_
         hipLaunchKernelGGL(k_fx_next_window, dim3(grid), dim3(kBlock), 0, ctx->stream, (const G1Affine*)(pre + (size_t)(w - 1) * srs->n), pre + (size_t)w * srs->n, srs->n, c);
         e = hipGetLastError();
     }
-    const bool lform = ctx->msm_fx_lform;
-    if (e == hipSuccess && lform) {  // the tables are only ever read by the limb-form bucket sums: store them in L-form
+    if (e == hipSuccess) {  // the tables are only ever read by the limb-form bucket sums: store them in L-form
         Fq thirty_two = Fq::zero();
         thirty_two.l[0] = 32;
         const size_t count = (size_t)W * srs->n;
@@ -1034,7 +1008,6 @@ static int32_t fx_precompute_into(jolt_ctx* ctx, jolt_srs* srs, uint32_t window_
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { (void)hipFree(pre); ctx->last_error = std::string("precompute windows: ") + hipGetErrorString(e); return JOLT_ERR_HIP; }
     srs->pre = pre;
-    srs->pre_lform = lform;
     srs->pre_c = c;
     srs->pre_W = W;
     srs->pre_B = n_bucket_max;
@@ -1090,11 +1063,11 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
     // reduction: sum_b b * B_b over buckets 1..B with up to 262144 threads, G buckets each (a serial chain of 2G additions per thread, then one
     // multiplication by the range's offset; B / 96 threads measured faster at 2^26 terms (99.2 -> 96.7 ms) but slower on the short prefix
     // MSMs (2^22: 9.3 -> 10.5 ms): the chains are latency bound at one wavefront per SIMD)
-    const uint32_t threads = (uint32_t)std::min<size_t>(std::max<size_t>(B / (size_t)ctx->msm_fx_reduce_div, std::min<size_t>(B, 4096)), 262144);
+    const uint32_t threads = (uint32_t)std::min<size_t>(std::max<size_t>(B / (size_t)24, std::min<size_t>(B, 4096)), 262144);
     const uint32_t nb = (threads + kBlock - 1) / kBlock;
     const uint32_t G = (B + nb * kBlock - 1) / (nb * kBlock);
-    // large bucket sets: the row / column reduction (k_fx_red_*); JOLT_FX_REDUCE=0 keeps the running sums for an A/B
-    const bool grid_reduce = B >= (1u << 16) && ctx->msm_fx_grid_reduce;
+    // large bucket sets: the row / column reduction (k_fx_red_*); small ones keep the running sums
+    const bool grid_reduce = B >= (1u << 16);
     const uint32_t red_H = (B >> kRedS) + 1, red_chunks = (red_H + kRedRC - 1) / kRedRC, red_per_row = kRedCols / kRedCW;
     const size_t red_points = grid_reduce ? (size_t)red_chunks * kRedCols + (size_t)red_H * red_per_row + kRedCols + red_H + 64 : 0;
     // a bucket holding more than max(kLaneCap, 4x the average) points is summed per 1024-point segment by whole wavefronts: the
@@ -1105,16 +1078,14 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
     const uint32_t heavy_threshold = (uint32_t)std::min<size_t>(std::max<size_t>(2 * kLaneCap, 4 * avg), kClasses - 2);
     const uint32_t heavy_cap = (uint32_t)(total / kFxHeavySeg + total / heavy_threshold + 16);
     // split entries and no key array (section 2c): 8-bit segments, the two-pass partition, W <= 12
-    static const bool wide_soa = !(std::getenv("JOLT_FX_SOA13") && std::atoi(std::getenv("JOLT_FX_SOA13")) == 0);
     const bool wide = W > kPartPerS;  // 13 windows: the second instantiation of the scalar-fed passes
-    const bool soa = ctx->msm_fx_soa && lo_bits == 8 && ctx->msm_fx_partition == 2 && (W <= kPartPerS || (W <= kPartPerWide && wide_soa)) &&
+    const bool soa = ctx->msm_fx_soa && lo_bits == 8 && ctx->msm_fx_partition == 2 && W <= kPartPerWide &&
                      ((nb1 + kGroupBins - 1) >> kGroupBits) <= (uint32_t)kPartBins &&
                      (wide ? sizeof(PartSharedN<kPartPerWide, kPartThreadsS>) : sizeof(PartSharedN<kPartPerS, kPartThreadsS>)) + 2048 <= ctx->max_lds_per_block;
     // capacity regions instead of a histogram pass (section 2d): scalars the caller marked as uniform field elements, the split-entry path, long enough to matter
-    static const bool capacity_on = !(std::getenv("JOLT_FX_CAPACITY") && std::atoi(std::getenv("JOLT_FX_CAPACITY")) == 0);
     FxCapModel cap_model;
     size_t cap_total = 0;
-    bool capacity = capacity_on && soa && ctx->msm_uniform_scalars && n >= ((size_t)1 << 16);
+    bool capacity = soa && ctx->msm_uniform_scalars && n >= ((size_t)1 << 16);
     if (capacity) {
         capacity = fx_capacity_model(n, c, W, &cap_model);
         const uint64_t top_max = cap_model.top_max;
@@ -1138,31 +1109,26 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     // Split-entry path: the key array is first WRITTEN by the segment sort (its output: the per-segment sorted base indices), when the grouped entries (6 B each, read for the
     // last time by the segment partition that precedes the sort on the same stream) are dead -- the 4-byte keys live in the grouped buffer instead of beside it
-    // (2.75 GiB less per 2^26-term lane; JOLT_FX_ALIAS_KEYS=0 keeps them apart, for an A/B).
-    static const bool alias_on = !(std::getenv("JOLT_FX_ALIAS_KEYS") && std::atoi(std::getenv("JOLT_FX_ALIAS_KEYS")) == 0);
-    const bool alias_keys = soa && alias_on;
-    size_t o_keys = alias_keys ? 0 : take(span * 4);
+    // (2.75 GiB less per 2^26-term lane: profiles/r06b_fx_alias_keys_ab.txt).  The 8-byte-entry path keeps a key array of its own.
+    size_t o_keys = soa ? 0 : take(span * 4);
     const size_t o_entries = take(soa ? span * 5 + 512 : total * 8), o_hist = take((size_t)nb1 * 4), o_offs = take((size_t)nb1 * 4), o_cur = take((size_t)nb1 * 4),
                  o_info = take(256), o_buckets = take(n_buckets * sizeof(G1Jac)), o_part = take((size_t)nb * sizeof(G1Jac)), o_wsum = take(2 * sizeof(G1Jac)),
                  o_red = take(std::max<size_t>(red_points, 1) * sizeof(G1Jac)),
                  o_bhist = take(n_buckets * 4), o_boffs = take(n_buckets * 4), o_heavy = take((size_t)heavy_cap * 8), o_hcnt = take(256),
                  o_seg = take((size_t)heavy_cap * sizeof(G1Jac)), o_cls = take(kClasses * 4 * 2), o_order = take(n_buckets * 4),
                  o_grouped = take(soa ? span * 6 + 512 : (ctx->msm_fx_partition == 2 ? total * 8 : 256)), o_gcur = take(kPartBins * 4), o_glim = take(kPartBins * 4);
-    if (alias_keys) o_keys = o_grouped;
+    if (soa) o_keys = o_grouped;
     // a pair's second pass sums into its OWN bucket set and reduces through its own scratch, so that the first pass's reduction (latency bound: chains of additions on
     // a few thousand threads) runs on the auxiliary stream under the second pass's bucket sums instead of between the two
-    const bool overlap_reduction = pair_shift != 0 && grid_reduce && ctx->msm_pair_overlap;
+    const bool overlap_reduction = pair_shift != 0 && grid_reduce;
     const size_t o_buckets2 = take(overlap_reduction ? n_buckets * sizeof(G1Jac) : 256), o_red2 = take(overlap_reduction ? red_points * sizeof(G1Jac) : 256),
                  o_wsum2 = take(2 * sizeof(G1Jac));
     hipStream_t st = lane == 0 ? ctx->stream : ctx->side[lane - 1];
-    // phases: sort (HBM bound) -> bucket sums (multiply-add bound) -> reduction (latency bound).  One stream by default; with JOLT_MSM_CU_SPLIT the
-    // sort and the reduction run on the lane's CU-masked "sort" stream and the bucket sums on its "bucket" stream (ctx.hpp), chained by events
-    const bool split = ctx->msm_cu_split > 0 && ctx->sort_stream[lane] && ctx->bucket_stream[lane];
-    hipStream_t sst = split ? ctx->sort_stream[lane] : st, bst = split ? ctx->bucket_stream[lane] : st;
+    // phases: sort (HBM bound) -> bucket sums (multiply-add bound) -> reduction (latency bound), all on the lane's stream (confining the sort and the bucket sums
+    // to disjoint sets of compute units measured 1.6-2.1x slower: profiles/r03_cu_split_ab.txt)
     if (off > ctx->msm_ws_cap[lane]) {
         if (ctx->msm_ws[lane]) {
             JOLT_HIP_TRY(ctx, hipStreamSynchronize(st));
-            if (split) { JOLT_HIP_TRY(ctx, hipStreamSynchronize(sst)); JOLT_HIP_TRY(ctx, hipStreamSynchronize(bst)); }
             JOLT_HIP_TRY(ctx, hipFree(ctx->msm_ws[lane]));
             ctx->msm_ws[lane] = nullptr;
             ctx->msm_ws_cap[lane] = 0;
@@ -1198,7 +1164,6 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
         hipError_t q1 = hipFuncSetAttribute((const void*)k_fx_hist_scalars<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->max_lds_per_block);
         hipError_t q2 = hipFuncSetAttribute((const void*)k_fx_partition_groups_scalars<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PartSharedN<kPartPerS, kPartThreadsS>));
         (void)hipFuncSetAttribute((const void*)k_fx_hist_scalars<8, kPartPerWide>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->max_lds_per_block);
-        (void)hipFuncSetAttribute((const void*)k_fx_hist_scalars<8, kPartPerS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->max_lds_per_block);
         (void)hipFuncSetAttribute((const void*)k_fx_partition_groups_scalars<8, kPartPerWide>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PartSharedN<kPartPerWide, kPartThreadsS>));
         (void)hipGetLastError();
         hipError_t q3 = hipFuncSetAttribute((const void*)k_fx_partition_segments_soa<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(PartSharedN<kPartPer>));
@@ -1215,40 +1180,30 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
         }
         ctx->msm_fx_attr_set = true;
     }
-    // sort token (ctx.hpp ev_sort): this MSM's HBM-bound phase starts when the previous MSM's has finished, so that it runs under
-    // that MSM's bucket sums instead of beside its sort
-    if (ctx->msm_stagger && ctx->sort_seq > 0 && ctx->sort_last_lane != lane)
-        JOLT_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_sort[(ctx->sort_seq - 1) % 8], 0));
-    if (split) {  // the sort starts after whatever the lane's stream holds (the scalars' producers, the lane's previous MSM)
-        JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_phase[lane][0], st));
-        JOLT_HIP_TRY(ctx, hipStreamWaitEvent(sst, ctx->ev_phase[lane][0], 0));
-    }
     const unsigned gn = (unsigned)((n + kBlock - 1) / kBlock);
     const unsigned slices = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)ctx->num_cus * 2, total / 16384));
     const unsigned hist_grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)ctx->num_cus * 2, n / 4096));
-    static const bool plain_hist = !(std::getenv("JOLT_FX_HIST_PLAIN") && std::atoi(std::getenv("JOLT_FX_HIST_PLAIN")) == 0);
     // the exact histogram from the scalars (run_if != nullptr: the fallback behind a capacity sort, a no-op while that sort's overflow flag is clear)
     auto hist_from_scalars = [&](const uint32_t* run_if) {
-        if (wide) hipLaunchKernelGGL((k_fx_hist_scalars<8, kPartPerWide>), dim3(hist_grid), dim3(kSortBlock), lds_bytes, sst, d_scalars, n, c, W, nb1, hist1, run_if);
-        else if (plain_hist) hipLaunchKernelGGL(k_fx_hist_scalars<8>, dim3(hist_grid), dim3(kSortBlock), lds_bytes, sst, d_scalars, n, c, W, nb1, hist1, run_if);
-        else hipLaunchKernelGGL((k_fx_hist_scalars<8, kPartPerS, false>), dim3(hist_grid), dim3(kSortBlock), lds_bytes, sst, d_scalars, n, c, W, nb1, hist1, run_if);
+        if (wide) hipLaunchKernelGGL((k_fx_hist_scalars<8, kPartPerWide>), dim3(hist_grid), dim3(kSortBlock), lds_bytes, st, d_scalars, n, c, W, nb1, hist1, run_if);
+        else hipLaunchKernelGGL(k_fx_hist_scalars<8>, dim3(hist_grid), dim3(kSortBlock), lds_bytes, st, d_scalars, n, c, W, nb1, hist1, run_if);
     };
     if (capacity) {  // region sizes take the histogram's place; k_fx_scan below turns them into offsets and cursors like counts
-        hipLaunchKernelGGL(k_fx_capacity_regions, dim3((nb1 + kBlock - 1) / kBlock), dim3(kBlock), 0, sst, cap_model, nb1, kSegBuckets, hist1, info);
+        hipLaunchKernelGGL(k_fx_capacity_regions, dim3((nb1 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, cap_model, nb1, kSegBuckets, hist1, info);
     } else if (soa) {  // digits straight into the segment histogram: no key array
-        JOLT_HIP_TRY(ctx, hipMemsetAsync(hist1, 0, (size_t)nb1 * 4, sst));
+        JOLT_HIP_TRY(ctx, hipMemsetAsync(hist1, 0, (size_t)nb1 * 4, st));
         hist_from_scalars(nullptr);
     } else {
-        JOLT_HIP_TRY(ctx, hipMemsetAsync(hist1, 0, (size_t)nb1 * 4, sst));
-        hipLaunchKernelGGL(k_fx_digits, dim3(gn), dim3(kBlock), 0, sst, d_scalars, n, c, W, keys);
-        if (lo_bits == 8) hipLaunchKernelGGL(k_fx_hist<8>, dim3(slices), dim3(kSortBlock), lds_bytes, sst, (const uint32_t*)keys, total, nb1, hist1);
-        else hipLaunchKernelGGL(k_fx_hist<11>, dim3(slices), dim3(kSortBlock), lds_bytes, sst, (const uint32_t*)keys, total, nb1, hist1);
+        JOLT_HIP_TRY(ctx, hipMemsetAsync(hist1, 0, (size_t)nb1 * 4, st));
+        hipLaunchKernelGGL(k_fx_digits, dim3(gn), dim3(kBlock), 0, st, d_scalars, n, c, W, keys);
+        if (lo_bits == 8) hipLaunchKernelGGL(k_fx_hist<8>, dim3(slices), dim3(kSortBlock), lds_bytes, st, (const uint32_t*)keys, total, nb1, hist1);
+        else hipLaunchKernelGGL(k_fx_hist<11>, dim3(slices), dim3(kSortBlock), lds_bytes, st, (const uint32_t*)keys, total, nb1, hist1);
     }
-    hipLaunchKernelGGL(k_fx_scan, dim3(1), dim3(kSortBlock), 0, sst, (const uint32_t*)hist1, nb1, offs1, cur1, info);
+    hipLaunchKernelGGL(k_fx_scan, dim3(1), dim3(kSortBlock), 0, st, (const uint32_t*)hist1, nb1, offs1, cur1, info);
     JOLT_HIP_TRY(ctx, hipGetLastError());
-    JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets, 0, n_buckets * sizeof(G1Jac), sst));  // z = 0: identity
-    JOLT_HIP_TRY(ctx, hipMemsetAsync(hcnt, 0, 256, sst));
-    JOLT_HIP_TRY(ctx, hipMemsetAsync(class_hist, 0, kClasses * 4, sst));
+    JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets, 0, n_buckets * sizeof(G1Jac), st));  // z = 0: identity
+    JOLT_HIP_TRY(ctx, hipMemsetAsync(hcnt, 0, 256, st));
+    JOLT_HIP_TRY(ctx, hipMemsetAsync(class_hist, 0, kClasses * 4, st));
     const bool two_pass = ctx->msm_fx_partition == 2 && n_groups <= (uint32_t)kPartBins && sizeof(PartShared) + 2048 <= ctx->max_lds_per_block;
     const unsigned part_grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)ctx->num_cus * 2, (total + kPartTile - 1) / kPartTile));
     // split-entry arrays of the SoA path inside the two entry buffers
@@ -1263,77 +1218,68 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
             const uint32_t* glim = regions ? group_limit : nullptr;
             uint32_t* flag = regions ? info + 2 : nullptr;
             if (wide)
-                hipLaunchKernelGGL((k_fx_partition_groups_scalars<8, kPartPerWide>), dim3(grid_s), dim3(kPartThreadsS), sizeof(PartSharedN<kPartPerWide, kPartThreadsS>), sst, d_scalars, n, c, W,
+                hipLaunchKernelGGL((k_fx_partition_groups_scalars<8, kPartPerWide>), dim3(grid_s), dim3(kPartThreadsS), sizeof(PartSharedN<kPartPerWide, kPartThreadsS>), st, d_scalars, n, c, W,
                                    srs->pre_stride, n_groups, group_cursor, g_val, g_low, glim, flag, run_if);
             else
-                hipLaunchKernelGGL(k_fx_partition_groups_scalars<8>, dim3(grid_s), dim3(kPartThreadsS), sizeof(PartSharedN<kPartPerS, kPartThreadsS>), sst, d_scalars, n, c, W, srs->pre_stride,
+                hipLaunchKernelGGL(k_fx_partition_groups_scalars<8>, dim3(grid_s), dim3(kPartThreadsS), sizeof(PartSharedN<kPartPerS, kPartThreadsS>), st, d_scalars, n, c, W, srs->pre_stride,
                                    n_groups, group_cursor, g_val, g_low, glim, flag, run_if);
-            hipLaunchKernelGGL(k_fx_partition_segments_soa<8>, dim3(part_grid), dim3(kPartThreads), sizeof(PartSharedN<kPartPer>), sst, (const uint32_t*)g_val, (const uint16_t*)g_low,
+            hipLaunchKernelGGL(k_fx_partition_segments_soa<8>, dim3(part_grid), dim3(kPartThreads), sizeof(PartSharedN<kPartPer>), st, (const uint32_t*)g_val, (const uint16_t*)g_low,
                                (const uint32_t*)offs1, nb1, (const uint32_t*)info, cur1, s_val, s_low, regions ? (const uint32_t*)group_cursor : nullptr, glim,
                                regions ? (const uint32_t*)hist1 : nullptr, flag, run_if);
         };
         if (capacity) {
-            hipLaunchKernelGGL(k_fx_group_regions, dim3(1), dim3(kPartBins), 0, sst, (const uint32_t*)offs1, (const uint32_t*)hist1, nb1, n_groups, group_cursor, group_limit);
+            hipLaunchKernelGGL(k_fx_group_regions, dim3(1), dim3(kPartBins), 0, st, (const uint32_t*)offs1, (const uint32_t*)hist1, nb1, n_groups, group_cursor, group_limit);
             partition_passes(true, nullptr);
-            hipLaunchKernelGGL(k_fx_counts_from_cursors, dim3((nb1 + kBlock - 1) / kBlock), dim3(kBlock), 0, sst, (const uint32_t*)offs1, (const uint32_t*)cur1, nb1, hist1, info);
+            hipLaunchKernelGGL(k_fx_counts_from_cursors, dim3((nb1 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, (const uint32_t*)offs1, (const uint32_t*)cur1, nb1, hist1, info);
             // the exact sort, enqueued behind it: every kernel returns at its first instruction unless a region overflowed
             const uint32_t* flag = info + 2;
-            hipLaunchKernelGGL(k_fx_clear_if, dim3((nb1 + kBlock - 1) / kBlock), dim3(kBlock), 0, sst, hist1, nb1, flag);
+            hipLaunchKernelGGL(k_fx_clear_if, dim3((nb1 + kBlock - 1) / kBlock), dim3(kBlock), 0, st, hist1, nb1, flag);
             hist_from_scalars(flag);
-            hipLaunchKernelGGL(k_fx_scan, dim3(1), dim3(kSortBlock), 0, sst, (const uint32_t*)hist1, nb1, offs1, cur1, info, flag);
-            hipLaunchKernelGGL(k_fx_group_cursors, dim3(1), dim3(kPartBins), 0, sst, (const uint32_t*)offs1, n_groups, group_cursor, flag);
+            hipLaunchKernelGGL(k_fx_scan, dim3(1), dim3(kSortBlock), 0, st, (const uint32_t*)hist1, nb1, offs1, cur1, info, flag);
+            hipLaunchKernelGGL(k_fx_group_cursors, dim3(1), dim3(kPartBins), 0, st, (const uint32_t*)offs1, n_groups, group_cursor, flag);
             partition_passes(false, flag);
         } else {
-            hipLaunchKernelGGL(k_fx_group_cursors, dim3(1), dim3(kPartBins), 0, sst, (const uint32_t*)offs1, n_groups, group_cursor);
+            hipLaunchKernelGGL(k_fx_group_cursors, dim3(1), dim3(kPartBins), 0, st, (const uint32_t*)offs1, n_groups, group_cursor);
             partition_passes(false, nullptr);
         }
     } else if (two_pass) {
-        hipLaunchKernelGGL(k_fx_group_cursors, dim3(1), dim3(kPartBins), 0, sst, (const uint32_t*)offs1, n_groups, group_cursor);
+        hipLaunchKernelGGL(k_fx_group_cursors, dim3(1), dim3(kPartBins), 0, st, (const uint32_t*)offs1, n_groups, group_cursor);
         if (lo_bits == 8) {
-            hipLaunchKernelGGL(k_fx_partition_groups<8>, dim3(part_grid), dim3(kPartThreads), sizeof(PartShared), sst, (const uint32_t*)keys, total, n, srs->pre_stride, n_groups,
+            hipLaunchKernelGGL(k_fx_partition_groups<8>, dim3(part_grid), dim3(kPartThreads), sizeof(PartShared), st, (const uint32_t*)keys, total, n, srs->pre_stride, n_groups,
                                group_cursor, grouped);
-            hipLaunchKernelGGL(k_fx_partition_segments<8>, dim3(part_grid), dim3(kPartThreads), sizeof(PartShared), sst, (const uint64_t*)grouped, (const uint32_t*)offs1, nb1,
+            hipLaunchKernelGGL(k_fx_partition_segments<8>, dim3(part_grid), dim3(kPartThreads), sizeof(PartShared), st, (const uint64_t*)grouped, (const uint32_t*)offs1, nb1,
                                (const uint32_t*)info, cur1, entries);
         } else {
-            hipLaunchKernelGGL(k_fx_partition_groups<11>, dim3(part_grid), dim3(kPartThreads), sizeof(PartShared), sst, (const uint32_t*)keys, total, n, srs->pre_stride, n_groups,
+            hipLaunchKernelGGL(k_fx_partition_groups<11>, dim3(part_grid), dim3(kPartThreads), sizeof(PartShared), st, (const uint32_t*)keys, total, n, srs->pre_stride, n_groups,
                                group_cursor, grouped);
-            hipLaunchKernelGGL(k_fx_partition_segments<11>, dim3(part_grid), dim3(kPartThreads), sizeof(PartShared), sst, (const uint64_t*)grouped, (const uint32_t*)offs1, nb1,
+            hipLaunchKernelGGL(k_fx_partition_segments<11>, dim3(part_grid), dim3(kPartThreads), sizeof(PartShared), st, (const uint64_t*)grouped, (const uint32_t*)offs1, nb1,
                                (const uint32_t*)info, cur1, entries);
         }
     } else if (lo_bits == 8) {
-        hipLaunchKernelGGL(k_fx_scatter<8>, dim3(slices), dim3(kSortBlock), lds_bytes, sst, (const uint32_t*)keys, total, n, srs->pre_stride, nb1, cur1, entries);
+        hipLaunchKernelGGL(k_fx_scatter<8>, dim3(slices), dim3(kSortBlock), lds_bytes, st, (const uint32_t*)keys, total, n, srs->pre_stride, nb1, cur1, entries);
     } else {
-        hipLaunchKernelGGL(k_fx_scatter<11>, dim3(slices), dim3(kSortBlock), lds_bytes, sst, (const uint32_t*)keys, total, n, srs->pre_stride, nb1, cur1, entries);
+        hipLaunchKernelGGL(k_fx_scatter<11>, dim3(slices), dim3(kSortBlock), lds_bytes, st, (const uint32_t*)keys, total, n, srs->pre_stride, nb1, cur1, entries);
     }
     if (lo_bits == 8) {
         // LDS for the staged segment: twice the average segment (uniform digits spread by ~1 %), at most what a CU has
         const size_t lds_max = ctx->max_lds_per_block > 12288 ? ctx->max_lds_per_block - 12288 : 0;  // cnt / cur / cls / wave sums live next to it
         const size_t want = (2 * (total / nb1) + 2048) * 4;
-        const size_t stage_bytes = ctx->msm_fx_stage ? std::min(lds_max, want) : 0;
+        const size_t stage_bytes = std::min(lds_max, want);
         if (soa)
-            hipLaunchKernelGGL((k_fx_segment_sort_staged<8, true>), dim3(nb1), dim3(kSegThreads), stage_bytes, sst, (const uint32_t*)hist1, (const uint32_t*)offs1, (const uint64_t*)nullptr,
+            hipLaunchKernelGGL((k_fx_segment_sort_staged<8, true>), dim3(nb1), dim3(kSegThreads), stage_bytes, st, (const uint32_t*)hist1, (const uint32_t*)offs1, (const uint64_t*)nullptr,
                                (const uint32_t*)s_val, (const uint8_t*)s_low, keys, hist, offs, heavy_threshold, heavy, hcnt, heavy_cap, class_hist, (uint32_t)(stage_bytes / 4));
         else
-            hipLaunchKernelGGL((k_fx_segment_sort_staged<8, false>), dim3(nb1), dim3(kSegThreads), stage_bytes, sst, (const uint32_t*)hist1, (const uint32_t*)offs1, (const uint64_t*)entries,
+            hipLaunchKernelGGL((k_fx_segment_sort_staged<8, false>), dim3(nb1), dim3(kSegThreads), stage_bytes, st, (const uint32_t*)hist1, (const uint32_t*)offs1, (const uint64_t*)entries,
                                (const uint32_t*)nullptr, (const uint8_t*)nullptr, keys, hist, offs, heavy_threshold, heavy, hcnt, heavy_cap, class_hist, (uint32_t)(stage_bytes / 4));
     }
     else
-        hipLaunchKernelGGL(k_fx_segment_sort<11>, dim3(nb1), dim3(kBlock), 0, sst, (const uint32_t*)hist1, (const uint32_t*)offs1, (const uint64_t*)entries, keys, hist, offs,
+        hipLaunchKernelGGL(k_fx_segment_sort<11>, dim3(nb1), dim3(kBlock), 0, st, (const uint32_t*)hist1, (const uint32_t*)offs1, (const uint64_t*)entries, keys, hist, offs,
                            heavy_threshold, heavy, hcnt, heavy_cap, class_hist);
     // bucket sums: the kernels of the per-window method with ONE window of B buckets (bases = the window tables)
     const unsigned gh = std::min<uint32_t>((heavy_cap + kBlock - 1) / kBlock, (uint32_t)ctx->num_cus * 64);  // grid-stride over the heavy list (its length lives on the device)
-    hipLaunchKernelGGL(k_fx_order_scan, dim3(1), dim3(kClasses), 0, sst, (const uint32_t*)class_hist, class_cursor);
-    hipLaunchKernelGGL(k_fx_order, dim3((unsigned)((n_buckets + kBlock * kOrderPer - 1) / (kBlock * kOrderPer))), dim3(kBlock), 0, sst, (const uint32_t*)hist, (uint32_t)n_buckets,
+    hipLaunchKernelGGL(k_fx_order_scan, dim3(1), dim3(kClasses), 0, st, (const uint32_t*)class_hist, class_cursor);
+    hipLaunchKernelGGL(k_fx_order, dim3((unsigned)((n_buckets + kBlock * kOrderPer - 1) / (kBlock * kOrderPer))), dim3(kBlock), 0, st, (const uint32_t*)hist, (uint32_t)n_buckets,
                        heavy_threshold, class_cursor, order);
-    if (ctx->msm_stagger) {
-        JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_sort[ctx->sort_seq % 8], sst));
-        ctx->sort_seq++;
-        ctx->sort_last_lane = lane;
-    }
-    if (split) {
-        JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_phase[lane][1], sst));
-        JOLT_HIP_TRY(ctx, hipStreamWaitEvent(bst, ctx->ev_phase[lane][1], 0));
-    }
     LformConsts lc;
     {
         Fq thirty_two = Fq::zero();
@@ -1344,92 +1290,75 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
     const unsigned bucket_grid = (unsigned)((n_buckets + kBlock - 1) / kBlock);
     const int per_result = grid_reduce ? 2 : 1;  // partial sums a result leaves in msm_host for the collect step's Horner
     if ((size_t)per_result * (pair_shift ? 2 : 1) > kMsmHostEntries) return JOLT_ERR_UNSUPPORTED;
-    // bucket sums over the sorted lists against the tables at `bases` into `buckets` (on the bucket stream) ...
+    // bucket sums over the sorted lists against the tables at `bases` into `buckets` ...
     auto bucket_sums = [&](const G1Affine* bases, G1Jac* buckets) -> int32_t {
         const bool profile = ctx->fx_profile && ctx->ev_fx[0] && ctx->ev_fx[1];
-        if (profile) JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_fx[0], bst));
-        static const bool stage_idx = !(std::getenv("JOLT_FX_STAGE_IDX") && std::atoi(std::getenv("JOLT_FX_STAGE_IDX")) == 0);
-        if (srs->pre_lform) {
-            if (stage_idx)
-                hipLaunchKernelGGL(k_fx_buckets_ordered_staged, dim3(bucket_grid), dim3(kBlock), 0, bst, (const uint32_t*)order, (uint32_t)n_buckets, (const uint32_t*)hist,
-                                   (const uint32_t*)offs, (const uint32_t*)keys, bases, heavy_threshold, buckets, lc);
-            else
-                hipLaunchKernelGGL(k_fx_buckets_ordered<true>, dim3(bucket_grid), dim3(kBlock), 0, bst, (const uint32_t*)order, (uint32_t)n_buckets, (const uint32_t*)hist,
-                                   (const uint32_t*)offs, (const uint32_t*)keys, bases, heavy_threshold, buckets, lc);
-            if (profile) {  // the LAST profiled launch is the one reported
-                JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_fx[1], bst));
-                ctx->fx_profile_info = info;
-                ctx->fx_profile_valid = true;
-            }
-            if (stage_idx)
-                hipLaunchKernelGGL(k_fx_heavy_segments_staged, dim3(gh), dim3(kBlock), 0, bst, (const uint32_t*)heavy, (const uint32_t*)hcnt, heavy_cap, (const uint32_t*)hist,
-                                   (const uint32_t*)offs, (const uint32_t*)keys, bases, seg, lc);
-            else
-                hipLaunchKernelGGL(k_fx_heavy_segments<true>, dim3(gh), dim3(kBlock), 0, bst, (const uint32_t*)heavy, (const uint32_t*)hcnt, heavy_cap, (const uint32_t*)hist,
-                                   (const uint32_t*)offs, (const uint32_t*)keys, bases, seg, lc);
-        } else {
-            hipLaunchKernelGGL(k_fx_buckets_ordered<false>, dim3(bucket_grid), dim3(kBlock), 0, bst, (const uint32_t*)order, (uint32_t)n_buckets, (const uint32_t*)hist,
-                               (const uint32_t*)offs, (const uint32_t*)keys, bases, heavy_threshold, buckets, lc);
-            hipLaunchKernelGGL(k_fx_heavy_segments<false>, dim3(gh), dim3(kBlock), 0, bst, (const uint32_t*)heavy, (const uint32_t*)hcnt, heavy_cap, (const uint32_t*)hist, (const uint32_t*)offs,
-                               (const uint32_t*)keys, bases, seg, lc);
+        if (profile) JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_fx[0], st));
+        hipLaunchKernelGGL(k_fx_buckets_ordered_staged, dim3(bucket_grid), dim3(kBlock), 0, st, (const uint32_t*)order, (uint32_t)n_buckets, (const uint32_t*)hist,
+                           (const uint32_t*)offs, (const uint32_t*)keys, bases, heavy_threshold, buckets, lc);
+        if (profile) {  // the LAST profiled launch is the one reported
+            JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_fx[1], st));
+            ctx->fx_profile_info = info;
+            ctx->fx_profile_valid = true;
         }
-        hipLaunchKernelGGL(k_fx_heavy_combine, dim3(std::min<uint32_t>(gh, 2048)), dim3(kBlock), 0, bst, (const uint32_t*)heavy, (const uint32_t*)hcnt, heavy_cap, (const uint32_t*)hist,
+        hipLaunchKernelGGL(k_fx_heavy_segments_staged, dim3(gh), dim3(kBlock), 0, st, (const uint32_t*)heavy, (const uint32_t*)hcnt, heavy_cap, (const uint32_t*)hist,
+                           (const uint32_t*)offs, (const uint32_t*)keys, bases, seg, lc);
+        hipLaunchKernelGGL(k_fx_heavy_combine, dim3(std::min<uint32_t>(gh, 2048)), dim3(kBlock), 0, st, (const uint32_t*)heavy, (const uint32_t*)hcnt, heavy_cap, (const uint32_t*)hist,
                            (const G1Jac*)seg, buckets);
         JOLT_HIP_TRY(ctx, hipGetLastError());
         return JOLT_OK;
     };
-    // ... and their reduction on `bst` (any stream ordered behind the sums), through the scratch at o_red / wsum; the result's partial sums go to msm_host[lane][slot ..]
-    auto reduction = [&](const G1Jac* buckets, size_t o_red, G1Jac* wsum, int slot, hipStream_t bst) -> int32_t {
+    // ... and their reduction on `rs` (any stream ordered behind the sums), through the scratch at o_red / wsum; the result's partial sums go to msm_host[lane][slot ..]
+    auto reduction = [&](const G1Jac* buckets, size_t o_red, G1Jac* wsum, int slot, hipStream_t rs) -> int32_t {
         if (grid_reduce) {
             G1Jac* colpart = (G1Jac*)(ws + o_red);
             G1Jac* rowpart = colpart + (size_t)red_chunks * kRedCols;
             G1Jac* cols = rowpart + (size_t)red_H * red_per_row;  // C_l, l < 2^S
             G1Jac* rows = cols + kRedCols;                         // R_h, h < H
             G1Jac* small_part = rows + red_H;                      // block partials of the two small reductions
-            hipLaunchKernelGGL(k_fx_red_cols, dim3(kRedCols / kBlock, red_chunks), dim3(kBlock), 0, bst, (const G1Jac*)buckets, B, red_H, colpart);
-            hipLaunchKernelGGL(k_fx_red_rows, dim3((red_H * red_per_row + kBlock - 1) / kBlock), dim3(kBlock), 0, bst, (const G1Jac*)buckets, B, red_H, rowpart);
-            hipLaunchKernelGGL(k_fx_red_fold, dim3(kRedCols * 64 / kBlock), dim3(kBlock), 0, bst, (const G1Jac*)colpart, kRedCols, red_chunks, (size_t)kRedCols, (size_t)1, cols);
-            hipLaunchKernelGGL(k_fx_red_fold, dim3((red_H * 64 + kBlock - 1) / kBlock), dim3(kBlock), 0, bst, (const G1Jac*)rowpart, red_H, red_per_row, (size_t)1, (size_t)red_per_row, rows);
+            hipLaunchKernelGGL(k_fx_red_cols, dim3(kRedCols / kBlock, red_chunks), dim3(kBlock), 0, rs, (const G1Jac*)buckets, B, red_H, colpart);
+            hipLaunchKernelGGL(k_fx_red_rows, dim3((red_H * red_per_row + kBlock - 1) / kBlock), dim3(kBlock), 0, rs, (const G1Jac*)buckets, B, red_H, rowpart);
+            hipLaunchKernelGGL(k_fx_red_fold, dim3(kRedCols * 64 / kBlock), dim3(kBlock), 0, rs, (const G1Jac*)colpart, kRedCols, red_chunks, (size_t)kRedCols, (size_t)1, cols);
+            hipLaunchKernelGGL(k_fx_red_fold, dim3((red_H * 64 + kBlock - 1) / kBlock), dim3(kBlock), 0, rs, (const G1Jac*)rowpart, red_H, red_per_row, (size_t)1, (size_t)red_per_row, rows);
             // sum_l l C_l (weights 1 .. 2^S - 1) and sum_h h R_h (weights 1 .. H - 1): index = weight, entry 0 unused -- the layout k_msm_window_reduce reads
             const uint32_t g_small = 8, nb_c = (kRedCols / g_small + kBlock - 1) / kBlock, nb_r = (red_H / g_small + kBlock) / kBlock;
-            hipLaunchKernelGGL(k_msm_window_reduce, dim3(nb_c, 1), dim3(kBlock), 0, bst, (const G1Jac*)cols, kRedCols - 1, g_small, small_part);
-            hipLaunchKernelGGL(k_msm_window_combine, dim3(1), dim3(64), 0, bst, (const G1Jac*)small_part, nb_c, wsum);
+            hipLaunchKernelGGL(k_msm_window_reduce, dim3(nb_c, 1), dim3(kBlock), 0, rs, (const G1Jac*)cols, kRedCols - 1, g_small, small_part);
+            hipLaunchKernelGGL(k_msm_window_combine, dim3(1), dim3(64), 0, rs, (const G1Jac*)small_part, nb_c, wsum);
             if (red_H > 1) {
-                hipLaunchKernelGGL(k_msm_window_reduce, dim3(nb_r, 1), dim3(kBlock), 0, bst, (const G1Jac*)rows, red_H - 1, g_small, small_part + 32);
-                hipLaunchKernelGGL(k_msm_window_combine, dim3(1), dim3(64), 0, bst, (const G1Jac*)(small_part + 32), nb_r, wsum + 1);
+                hipLaunchKernelGGL(k_msm_window_reduce, dim3(nb_r, 1), dim3(kBlock), 0, rs, (const G1Jac*)rows, red_H - 1, g_small, small_part + 32);
+                hipLaunchKernelGGL(k_msm_window_combine, dim3(1), dim3(64), 0, rs, (const G1Jac*)(small_part + 32), nb_r, wsum + 1);
             } else {
-                JOLT_HIP_TRY(ctx, hipMemsetAsync(wsum + 1, 0, sizeof(G1Jac), bst));
+                JOLT_HIP_TRY(ctx, hipMemsetAsync(wsum + 1, 0, sizeof(G1Jac), rs));
             }
         } else {
-            hipLaunchKernelGGL(k_msm_window_reduce, dim3(nb, 1), dim3(kBlock), 0, bst, (const G1Jac*)buckets, B, G, part);
-            hipLaunchKernelGGL(k_msm_window_combine, dim3(1), dim3(64), 0, bst, (const G1Jac*)part, nb, wsum);
+            hipLaunchKernelGGL(k_msm_window_reduce, dim3(nb, 1), dim3(kBlock), 0, rs, (const G1Jac*)buckets, B, G, part);
+            hipLaunchKernelGGL(k_msm_window_combine, dim3(1), dim3(64), 0, rs, (const G1Jac*)part, nb, wsum);
         }
         JOLT_HIP_TRY(ctx, hipGetLastError());
-        JOLT_HIP_TRY(ctx, hipMemcpyAsync((G1Jac*)ctx->msm_host[lane] + slot, wsum, (size_t)per_result * sizeof(G1Jac), hipMemcpyDeviceToHost, bst));
+        JOLT_HIP_TRY(ctx, hipMemcpyAsync((G1Jac*)ctx->msm_host[lane] + slot, wsum, (size_t)per_result * sizeof(G1Jac), hipMemcpyDeviceToHost, rs));
         return JOLT_OK;
     };
     JOLT_TRY(bucket_sums((const G1Affine*)srs->pre, buckets));
     if (!pair_shift) {
-        JOLT_TRY(reduction(buckets, o_red, wsum, 0, bst));
+        JOLT_TRY(reduction(buckets, o_red, wsum, 0, st));
     } else if (overlap_reduction) {
         if (!ctx->msm_aux_stream) JOLT_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->msm_aux_stream, hipStreamNonBlocking));
         if (!ctx->ev_aux[lane][0]) for (hipEvent_t& ev : ctx->ev_aux[lane]) JOLT_HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         G1Jac* buckets2 = (G1Jac*)(ws + o_buckets2);
-        JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[lane][0], bst));  // the first pass's buckets are complete
+        JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[lane][0], st));  // the first pass's buckets are complete
         JOLT_HIP_TRY(ctx, hipStreamWaitEvent(ctx->msm_aux_stream, ctx->ev_aux[lane][0], 0));
         JOLT_TRY(reduction(buckets, o_red, wsum, 0, ctx->msm_aux_stream));
         JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[lane][1], ctx->msm_aux_stream));
-        JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets2, 0, n_buckets * sizeof(G1Jac), bst));
+        JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets2, 0, n_buckets * sizeof(G1Jac), st));
         JOLT_TRY(bucket_sums((const G1Affine*)srs->pre + pair_shift, buckets2));
-        JOLT_TRY(reduction(buckets2, o_red2, (G1Jac*)(ws + o_wsum2), per_result, bst));
-        JOLT_HIP_TRY(ctx, hipStreamWaitEvent(bst, ctx->ev_aux[lane][1], 0));  // the lane's stream covers both results (jolt_internal_msm_collect waits for it alone)
+        JOLT_TRY(reduction(buckets2, o_red2, (G1Jac*)(ws + o_wsum2), per_result, st));
+        JOLT_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[lane][1], 0));  // the lane's stream covers both results (jolt_internal_msm_collect waits for it alone)
     } else {
-        JOLT_TRY(reduction(buckets, o_red, wsum, 0, bst));
-        JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets, 0, n_buckets * sizeof(G1Jac), bst));  // empty buckets rely on the identity the first pass overwrote nowhere; light / heavy ones are rewritten
+        JOLT_TRY(reduction(buckets, o_red, wsum, 0, st));
+        JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets, 0, n_buckets * sizeof(G1Jac), st));  // empty buckets rely on the identity the first pass overwrote nowhere; light / heavy ones are rewritten
         JOLT_TRY(bucket_sums((const G1Affine*)srs->pre + pair_shift, buckets));
-        JOLT_TRY(reduction(buckets, o_red, wsum, per_result, bst));
+        JOLT_TRY(reduction(buckets, o_red, wsum, per_result, st));
     }
-    if (split) { JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_phase[lane][3], bst)); JOLT_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_phase[lane][3], 0)); }
     job->n = n;
     job->lane = lane;
     job->c = grid_reduce ? kRedS : 0;  // the collect step's Horner: 2^S * (row-weighted sum) + (column-weighted sum); or a single "window"
@@ -1458,7 +1387,7 @@ extern "C" int32_t jolt_host_fx_digits(const jolt_fr_t* scalar, uint32_t window_
 
 
 // ---- profile of the dominant kernel (bench.py roofline_msm) ------------------------------------------------------------------------------------------------
-// enable: every later fixed-base MSM of the context brackets its k_fx_buckets_ordered launch with HIP events on the launch's own stream.  _last: duration of the last
+// enable: every later fixed-base MSM of the context brackets its k_fx_buckets_ordered_staged launch with HIP events on the launch's own stream.  _last: duration of the last
 // bracketed launch and the mixed additions it performed (the non-zero signed digits of its scalars: light and heavy buckets together; heavy lists are a few
 // thousandths for uniform scalars).  Call after the MSM was collected (the events must have completed).
 extern "C" int32_t jolt_msm_profile_buckets(jolt_ctx* ctx, int32_t enable) {
@@ -1506,7 +1435,7 @@ __global__ __launch_bounds__(256) void k_mad_peak(uint64_t* out, uint32_t a0, ui
 }  // namespace
 extern "C" int32_t jolt_ctx_measure_mad_peak(jolt_ctx* ctx, float target_ms, double* mads_per_s, float* timed_ms, uint32_t* launches) {
     if (!ctx || !mads_per_s || !(target_ms > 0.f) || target_ms > 5000.f) return JOLT_ERR_INVALID_ARG;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     const int blocks = (int)ctx->num_cus * 8, iters = 4096;
     uint64_t* out = nullptr;
     JOLT_TRY(jolt_internal_dev_alloc(ctx, (size_t)blocks * 256 * sizeof(uint64_t), (void**)&out));

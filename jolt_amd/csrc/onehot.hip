@@ -67,7 +67,7 @@ extern "C" int32_t jolt_onehot_upload16(jolt_ctx* ctx, const uint16_t* indices, 
 extern "C" int32_t jolt_onehot_free(jolt_ctx* ctx, jolt_onehot* s) {
     if (!s) return JOLT_OK;
     jolt_ctx* c = s->ctx ? s->ctx : ctx;
-    if (c) (void)jolt_internal_engine_quiesce(c);
+    if (c) (void)jolt_internal_join_side_writers(c);
     const bool pooled = c && s->idx && c->pool_live.count(s->idx);  // jolt_onehot_from_rows: back to the pool, reused in stream order; uploads: the runtime's block
     if (c && !pooled) (void)hipStreamSynchronize(c->stream);
     if (s->idx) { if (c) jolt_internal_dev_free(c, s->idx); else (void)hipFree(s->idx); }
@@ -80,7 +80,7 @@ extern "C" int32_t jolt_onehot_materialize(jolt_ctx* ctx, const jolt_onehot* s, 
     if (!ctx || !s || !scale_table || !out) return JOLT_ERR_INVALID_ARG;
     if (poly >= s->n_polys) return JOLT_ERR_INVALID_ARG;
     if (scale_table->len != s->k) return JOLT_ERR_SIZE_MISMATCH;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     jolt_table* t = nullptr;
     JOLT_TRY(jolt_internal_table_new(ctx, s->cycles, &t));
     OneHotDense o;
@@ -97,7 +97,7 @@ extern "C" int32_t jolt_onehot_materialize(jolt_ctx* ctx, const jolt_onehot* s, 
 extern "C" int32_t jolt_onehot_pushforward(jolt_ctx* ctx, const jolt_onehot* s, const jolt_table* weights, jolt_table** out) {
     if (!ctx || !s || !weights || !out) return JOLT_ERR_INVALID_ARG;
     if (weights->len != s->cycles) return JOLT_ERR_SIZE_MISMATCH;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     const bool lanes = s->k <= 32 && !s->wide;  // per-lane buckets in LDS (K * 2 KiB per wavefront): every column the reference folds this way has K = 16
     size_t per_block = 4096;        // cycles per wavefront: 64 per lane
     while ((s->cycles + per_block - 1) / per_block > 1024) per_block *= 2;
@@ -369,7 +369,7 @@ extern "C" int32_t jolt_rows_free(jolt_ctx* ctx, jolt_rows* r) {
     if (!r) return JOLT_OK;
     if (ctx && r->ctx && ctx != r->ctx) return JOLT_ERR_INVALID_ARG;  // the block belongs to the pool of the context that uploaded it
     jolt_ctx* c = r->ctx ? r->ctx : ctx;
-    if (c) { (void)jolt_internal_engine_quiesce(c); (void)hipStreamSynchronize(c->stream); }
+    if (c) { (void)jolt_internal_join_side_writers(c); (void)hipStreamSynchronize(c->stream); }
     if (r->pending && c && c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);  // a copy that was begun and never waited for still writes the block
     if (r->data) { if (c) jolt_internal_dev_free(c, r->data); else (void)hipFree(r->data); }
     delete r;
@@ -380,7 +380,7 @@ extern "C" int32_t jolt_table_from_rows(jolt_ctx* ctx, const jolt_rows* rows, si
     if (!ctx || !rows || !out) return JOLT_ERR_INVALID_ARG;
     JOLT_TRY(rows_ready(ctx, rows));
     if (!(width == 1 || width == 2 || width == 4 || width == 8) || width > rows->row_bytes || offset > rows->row_bytes - width) return JOLT_ERR_INVALID_ARG;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     jolt_table* t = nullptr;
     JOLT_TRY(jolt_internal_table_new(ctx, rows->n_rows, &t));
     hipLaunchKernelGGL(k_rows_to_fr, dim3((unsigned)((rows->n_rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, (const uint8_t*)rows->data, rows->n_rows,
@@ -406,7 +406,7 @@ extern "C" int32_t jolt_ints_from_rows(jolt_ctx* ctx, const jolt_rows* rows, siz
     if (!ctx || !rows || !out) return JOLT_ERR_INVALID_ARG;
     JOLT_TRY(rows_ready(ctx, rows));
     if (!(width == 1 || width == 2 || width == 4 || width == 8) || width > rows->row_bytes || offset > rows->row_bytes - width) return JOLT_ERR_INVALID_ARG;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     jolt_ints* v = new (std::nothrow) jolt_ints();
     if (!v) return JOLT_ERR_OOM;
     v->ctx = ctx;
@@ -452,7 +452,7 @@ extern "C" int32_t jolt_ints_from_rows_many(jolt_ctx* ctx, const jolt_rows* rows
         }
         return JOLT_OK;
     }
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     auto release = [&](size_t upto) { for (size_t q = 0; q < upto; ++q) { jolt_ints_free(ctx, out[q]); out[q] = nullptr; } };
     for (size_t k = 0; k < n_fields; ++k) {
         jolt_ints* v = new (std::nothrow) jolt_ints();
@@ -509,7 +509,7 @@ extern "C" int32_t jolt_onehot_from_rows(jolt_ctx* ctx, const jolt_rows* rows, s
         sh.shift[p] = p < n_polys ? shifts[p] : 0;
         if (p < n_polys && shifts[p] + log_k > width * 8) return JOLT_ERR_INVALID_ARG;
     }
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     jolt_onehot* s = new (std::nothrow) jolt_onehot();
     if (!s) return JOLT_ERR_OOM;
     s->ctx = ctx;
@@ -543,7 +543,7 @@ extern "C" int32_t jolt_table_from_rows_window(jolt_ctx* ctx, const jolt_rows* r
     JOLT_TRY(rows_ready(ctx, rows));
     if (!(width == 1 || width == 2 || width == 4 || width == 8) || width > rows->row_bytes || offset > rows->row_bytes - width || (lookahead != 0 && lookahead != 1)) return JOLT_ERR_INVALID_ARG;
     if (rows->n_rows > cycles) return JOLT_ERR_SIZE_MISMATCH;  // rows.rs:44-53: the physical trace must fit the cycle domain
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     jolt_table* t = nullptr;
     JOLT_TRY(jolt_internal_table_new(ctx, cycles, &t));
     if (cycles) {
@@ -567,7 +567,7 @@ extern "C" int32_t jolt_onehot_from_rows_sentinel(jolt_ctx* ctx, const jolt_rows
         sh.shift[p] = p < n_polys ? shifts[p] : 0;
         if (p < n_polys && shifts[p] + log_k > width * 8) return JOLT_ERR_INVALID_ARG;
     }
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     jolt_onehot* s = new (std::nothrow) jolt_onehot();
     if (!s) return JOLT_ERR_OOM;
     s->ctx = ctx;
@@ -598,7 +598,7 @@ extern "C" int32_t jolt_onehot_from_rows_sentinel(jolt_ctx* ctx, const jolt_rows
 // the hot indices back on the host (tests, debugging)
 extern "C" int32_t jolt_onehot_download(jolt_ctx* ctx, const jolt_onehot* s, uint8_t* out) {
     if (!ctx || !s || !out) return JOLT_ERR_INVALID_ARG;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     if (s->wide) { ctx->last_error = "16-bit source: use jolt_onehot_download16"; return JOLT_ERR_INVALID_ARG; }
     JOLT_HIP_TRY(ctx, hipMemcpyAsync(out, s->idx, s->n_polys * s->cycles, hipMemcpyDeviceToHost, ctx->stream));
     JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -608,7 +608,7 @@ extern "C" int32_t jolt_onehot_download(jolt_ctx* ctx, const jolt_onehot* s, uin
 extern "C" int32_t jolt_onehot_download16(jolt_ctx* ctx, const jolt_onehot* s, uint16_t* out) {
     if (!ctx || !s || !out) return JOLT_ERR_INVALID_ARG;
     if (!s->wide) { ctx->last_error = "8-bit source: use jolt_onehot_download"; return JOLT_ERR_INVALID_ARG; }
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     JOLT_HIP_TRY(ctx, hipMemcpyAsync(out, s->idx, s->n_polys * s->cycles * 2, hipMemcpyDeviceToHost, ctx->stream));
     JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return JOLT_OK;

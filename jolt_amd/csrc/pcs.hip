@@ -295,7 +295,7 @@ static int32_t grid_commit_onehot_impl(jolt_ctx* ctx, const jolt_srs* srs, const
         lc.r256 = Fq::one();
     }
     // window 0 of the fixed-base tables IS the SRS in L-form (msm_fixed.hip): the sums then run on the limb-form accumulator
-    if (srs->pre && srs->pre_lform && srs->pre_stride >= (size_t)source->k * T)
+    if (srs->pre && srs->pre_stride >= (size_t)source->k * T)
         hipLaunchKernelGGL(k_grid_onehot_sum<true>, dim3(blocks, (unsigned)N, (unsigned)classes), dim3(kBlock), 0, ctx->stream, (const uint8_t*)source->idx, source->wide, T, cycle_lo,
                            cycle_hi, (const G1Affine*)srs->pre, partial, lc, shift);
     else
@@ -350,7 +350,7 @@ extern "C" int32_t jolt_grid_hint_begin(jolt_ctx* ctx, const jolt_srs* srs, cons
     }
     if (T == 0 || (T & (T - 1)) != 0 || T < ((size_t)1 << levels)) return JOLT_ERR_UNSUPPORTED;  // a power-of-two grid at least 2^levels wide
     if ((size_t)sources[0]->k * T > srs->n) return JOLT_ERR_SRS_TOO_SMALL;
-    JOLT_TRY(jolt_internal_engine_quiesce(ctx));
+    JOLT_TRY(jolt_internal_join_side_writers(ctx));
     jolt_grid_hint* h = new (std::nothrow) jolt_grid_hint();
     if (!h) return JOLT_ERR_OOM;
     h->ctx = ctx;
@@ -399,7 +399,7 @@ extern "C" int32_t jolt_grid_hint_begin(jolt_ctx* ctx, const jolt_srs* srs, cons
             const size_t by_work = (span + (size_t)kBlock * 128 - 1) / ((size_t)kBlock * 128), fill = ((size_t)ctx->num_cus * 8 + N - 1) / std::max<size_t>(N, 1);
             const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>({(span + kBlock - 1) / kBlock, std::max(by_work, fill), blocks_max}));
             const uint32_t per_col = blocks * (kBlock / 64);
-            if (srs->pre && srs->pre_lform && srs->pre_stride >= (size_t)src->k * T)
+            if (srs->pre && srs->pre_stride >= (size_t)src->k * T)
                 hipLaunchKernelGGL(k_grid_onehot_sum<true>, dim3(blocks, (unsigned)N, (unsigned)classes), dim3(kBlock), lds, h->stream, (const uint8_t*)src->idx, src->wide, T, (size_t)0, T,
                                    (const G1Affine*)srs->pre, h->partial, lc, s_);
             else
@@ -538,9 +538,8 @@ static int32_t grid_joint_impl(jolt_ctx* ctx, const jolt_onehot* const* sources,
     int32_t st = JOLT_OK;
     if (total) st = jolt_table_upload(ctx, onehot_scalars, total, &ds);  // synchronises: the caller's array may be short-lived
     if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
-    static const bool by_rows = !(std::getenv("JOLT_JOINT_ROWS") && std::atoi(std::getenv("JOLT_JOINT_ROWS")) == 0);
     const size_t rows_lds = (size_t)K * kJointThreads * sizeof(Fr);
-    if (map.kind == kTermsAll && by_rows && rows_lds <= 64 * 1024)
+    if (map.kind == kTermsAll && rows_lds <= 64 * 1024)
         hipLaunchKernelGGL(k_grid_joint_rows, dim3((unsigned)((T + kJointThreads - 1) / kJointThreads)), dim3(kJointThreads), rows_lds, ctx->stream, a,
                            ds ? (const Fr*)ds->data() : (const Fr*)nullptr, T, K, r->data());
     else if (map.kind == kTermsAll)

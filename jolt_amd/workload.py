@@ -288,15 +288,14 @@ class DeviceWorkload:
         # Compact-scalar witness columns (the optimized tier's Polynomial<u64>: round 0 off the integers, bind_to_field on the first bind,
         # crates/jolt-poly/src/dense.rs:129-142): u64 columns that only feed descriptor-driven members are never promoted -- the members read the resident
         # integers (jolt_member_create_lc_small).  Not: the two committed increment columns (commit and the joint polynomial need them as field tables) and the
-        # split-eq product member's columns.  JOLT_SMALL_ROUND0=0: promote everything (the round-3 path), for an A/B.
-        import os
+        # split-eq product member's columns.
         int_capable = lambda ms: ms.uniform is None and ms.fused is None and ms.split_eq is None
         small = {t for ms in self.members_spec if int_capable(ms) for t in (ms.tables[1:] if ms.eq_inner is not None else ms.tables)
                  if self.tables_spec[t].kind == "u64"}
         small -= {t for ms in self.members_spec if not int_capable(ms) for t in ms.tables}
         small -= {"s6.ram_inc", "s6.rd_inc"}
-        self._small = small if os.environ.get("JOLT_SMALL_ROUND0", "1") != "0" else set()
-        skip |= self._small
+        self._small = small
+        skip |= small
         self._skip = skip
         # ---- resident inputs
         self.ints = {}
@@ -573,9 +572,9 @@ class DeviceWorkload:
         one-hot columns = sums of selected bases."""
         ctx, T = self.ctx, 1 << self.n_vars
         # the dense columns' MSMs go in flight on the side lanes (short: bound by the latency of their sort and reduction chains) and are collected after the one-hot
-        # sums of bases have run on the main stream (bound by multiplications); JOLT_COMMIT_OVERLAP=0 or a context that cannot: one after the other
+        # sums of bases have run on the main stream (bound by multiplications); a context that cannot hold them in flight: one after the other
         pending = None
-        if self.committed_dense and os.environ.get("JOLT_COMMIT_OVERLAP", "1") != "0":
+        if self.committed_dense:
             try:
                 pending = ctx.msm_tables_begin(self.srs, [self.tables[name] for name in self.committed_dense], [T] * len(self.committed_dense))
             except self.ffi.JoltError as e:
@@ -590,10 +589,10 @@ class DeviceWorkload:
         # the opening hint (CommitmentScheme::commit returns (Commitment, OpeningHint), schemes.rs:60-72): the class sums behind the opening's first level commitments are a
         # function of the witness and the SRS alone -- enqueued now in the background, they run under the latency-bound stage operators and sumcheck legs
         levels = self.linear_levels()
-        if levels and os.environ.get("JOLT_HINT_AT_COMMIT", "1") != "0":
+        if levels:
             if self.hint is not None:
                 self.hint.free()
-            self.hint = ctx.grid_hint(self.srs, [self.sources[i] for i in sorted(self.sources)], levels, background=os.environ.get("JOLT_HINT_BACKGROUND", "1") != "0")
+            self.hint = ctx.grid_hint(self.srs, [self.sources[i] for i in sorted(self.sources)], levels, background=True)
         return dict(dense=np.stack(dense), onehot=np.concatenate(onehot))
 
     def joint_polynomial(self):
@@ -601,9 +600,8 @@ class DeviceWorkload:
                                               [self.tables[name] for name in self.committed_dense], self.rlc_dense, self.log_k)
 
     def linear_levels(self):
-        """how many of the opening's first level commitments come by linearity from the commit-time hint (JOLT_OPEN_LINEAR_LEVELS, default 2; 0: every level by MSM)"""
-        levels = 0 if os.environ.get("JOLT_OPEN_LEVEL1", "1") == "0" else int(os.environ.get("JOLT_OPEN_LINEAR_LEVELS", "2"))
-        return max(0, min(levels, 4, self.grid_vars - 1, self.n_vars - 1))
+        """how many of the opening's first level commitments come by linearity from the commit-time hint: 2 (three cost +13 ms, profiles/r04_open_linear_levels_ab.txt), fewer on small grids"""
+        return max(0, min(2, self.grid_vars - 1, self.n_vars - 1))
 
     def open(self, label=0):
         """Stage 8: joint polynomial of the homomorphic batch, one HyperKZG opening at the unified point; the first level commitments by linearity from the opening hint
