@@ -344,6 +344,7 @@ int32_t jolt_host_mul_limbs29(int32_t field, const jolt_fr_t *a, const jolt_fr_t
  * affine points in STANDARD Montgomery form.  op: 0 a*b, 1 a^2, 2 a*b + c*d, 3 (a - b)*c, 4 (a - b - 2c)*d. */
 int32_t jolt_host_fq_limb_op(int32_t op, const jolt_fr_t *a, const jolt_fr_t *b, const jolt_fr_t *c, const jolt_fr_t *d, jolt_fr_t *out);
 int32_t jolt_host_g1_sum_limb_form(const uint64_t *points, const uint8_t *negate, size_t count, jolt_g1_t *out);
+int32_t jolt_host_g1xl_add_paths(const uint32_t *acc, const uint32_t *q, int32_t negate, uint32_t *common, uint32_t *full, uint32_t *step, int32_t *suspect, uint32_t *canon);
 /* The signed-digit recoding of the fixed-base MSM for one scalar (negation above r / 2, c-bit signed windows, unsigned top window), built for
  * the host: keys_out[w] = |digit_w| | sign << 31 for w < ceil(253 / c); *buckets_out = the bucket count of a table set with this c. */
 int32_t jolt_host_fx_digits(const jolt_fr_t *scalar, uint32_t window_bits, uint32_t *keys_out, uint32_t *n_windows_out, uint32_t *buckets_out);

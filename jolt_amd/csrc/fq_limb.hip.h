@@ -14,6 +14,7 @@
 // (jolt_host_fq_limb_* / jolt_host_g1_sum_limb_form in host_mirror.hip), where the CPU suite pins it against the oracle.
 #pragma once
 #include "field.hip.h"
+#include "g1.hip.h"
 
 namespace jolt {
 
@@ -44,12 +45,44 @@ constexpr uint32_t PM(int m, int k) {
     }
     return (uint32_t)v;
 }
+// limb k of (m p + sum_j 2^(29 j)) / 2 for odd m (the sum is then even); fql_diff_signed builds its two constants from it
+constexpr uint32_t PM1(int m, int k) {
+    uint64_t carry = 0, v = 0;
+    for (int i = 0; i <= k; ++i) {
+        v = (uint64_t)m * P(i) + 1 + carry;
+        carry = v >> 29;
+        if (i < 8) v &= kMask29;
+    }
+    return (uint32_t)v;
+}
+constexpr uint32_t PM1H(int m, int k) { return (PM1(m, k) >> 1) | (k < 8 ? (PM1(m, k + 1) & 1u) << 28 : 0u); }
+static_assert((PM1(3, 0) & 1u) == 0 && (PM1(11, 0) & 1u) == 0, "m p + ones must be even");
 }  // namespace fql
 #define JOLT_FQL_MP(m) {fql::PM(m, 0), fql::PM(m, 1), fql::PM(m, 2), fql::PM(m, 3), fql::PM(m, 4), fql::PM(m, 5), fql::PM(m, 6), fql::PM(m, 7), fql::PM(m, 8)}
 // function-local constexpr tables (indexed by unrolled constants: folded into immediates)
 #define JOLT_FQL_P {fql::P(0), fql::P(1), fql::P(2), fql::P(3), fql::P(4), fql::P(5), fql::P(6), fql::P(7), fql::P(8)}
 #define JOLT_FQL_2P {fql::P2(0), fql::P2(1), fql::P2(2), fql::P2(3), fql::P2(4), fql::P2(5), fql::P2(6), fql::P2(7), fql::P2(8)}
 
+// acc += a * b, the column accumulator's step.  Left to itself the compiler breaks a column's sum into two mad chains and joins them with a 64-bit add (16
+// v_lshl_add_u64 per product, ~144 per mixed addition); on the device this keeps ONE dependent chain: the accumulator is the multiply-add's own addend
+// (docs/kernels.md 3.1 has the measured issue costs that decide it).  `b` may be a compile-time constant: the scalar operand of the instruction.
+#ifndef JOLT_FQL_ONE_CHAIN
+#define JOLT_FQL_ONE_CHAIN 1
+#endif
+JOLT_HD void fql_mac(uint64_t& acc, uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__) && JOLT_FQL_ONE_CHAIN
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "vcc");
+#else
+    acc += (uint64_t)a * b;
+#endif
+}
+JOLT_HD void fql_mac_const(uint64_t& acc, uint32_t a, uint32_t c) {  // c: a limb of p
+#if defined(__HIP_DEVICE_COMPILE__) && JOLT_FQL_ONE_CHAIN
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(a), "s"(c) : "vcc");
+#else
+    acc += (uint64_t)a * c;
+#endif
+}
 JOLT_HD FqL fql_from_words(const Fq& a) {  // the words already hold the value's L-form (or any value < 2^256 to be taken as is)
     FqL r;
     to_limbs29<0>(a.l, r.l);
@@ -128,19 +161,19 @@ JOLT_HD FqL fql_mul(const FqL& a, const FqL& b) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
 #pragma unroll
-        for (int i = 0; i <= k; ++i) acc += (uint64_t)a.l[i] * b.l[k - i];
+        for (int i = 0; i <= k; ++i) fql_mac(acc, a.l[i], b.l[k - i]);
 #pragma unroll
-        for (int i = 0; i < k; ++i) acc += (uint64_t)M[i] * PL[k - i];
+        for (int i = 0; i < k; ++i) fql_mac_const(acc, M[i], PL[k - i]);
         M[k] = ((uint32_t)acc * fql::NINV) & kMask29;
-        acc += (uint64_t)M[k] * PL[0];
+        fql_mac_const(acc, M[k], PL[0]);
         acc >>= 29;
     }
 #pragma unroll
     for (int k = 9; k < 18; ++k) {
 #pragma unroll
-        for (int i = k - 8; i < 9; ++i) acc += (uint64_t)a.l[i] * b.l[k - i];
+        for (int i = k - 8; i < 9; ++i) fql_mac(acc, a.l[i], b.l[k - i]);
 #pragma unroll
-        for (int i = k - 8; i < 9; ++i) acc += (uint64_t)M[i] * PL[k - i];
+        for (int i = k - 8; i < 9; ++i) fql_mac_const(acc, M[i], PL[k - i]);
         r.l[k - 9] = (uint32_t)acc & kMask29;
         acc >>= 29;
     }
@@ -157,24 +190,24 @@ JOLT_HD FqL fql_mul2(const FqL& a, const FqL& b, const FqL& c, const FqL& d) {
     for (int k = 0; k < 9; ++k) {
 #pragma unroll
         for (int i = 0; i <= k; ++i) {
-            acc += (uint64_t)a.l[i] * b.l[k - i];
-            acc += (uint64_t)c.l[i] * d.l[k - i];
+            fql_mac(acc, a.l[i], b.l[k - i]);
+            fql_mac(acc, c.l[i], d.l[k - i]);
         }
 #pragma unroll
-        for (int i = 0; i < k; ++i) acc += (uint64_t)M[i] * PL[k - i];
+        for (int i = 0; i < k; ++i) fql_mac_const(acc, M[i], PL[k - i]);
         M[k] = ((uint32_t)acc * fql::NINV) & kMask29;
-        acc += (uint64_t)M[k] * PL[0];
+        fql_mac_const(acc, M[k], PL[0]);
         acc >>= 29;
     }
 #pragma unroll
     for (int k = 9; k < 18; ++k) {
 #pragma unroll
         for (int i = k - 8; i < 9; ++i) {
-            acc += (uint64_t)a.l[i] * b.l[k - i];
-            acc += (uint64_t)c.l[i] * d.l[k - i];
+            fql_mac(acc, a.l[i], b.l[k - i]);
+            fql_mac(acc, c.l[i], d.l[k - i]);
         }
 #pragma unroll
-        for (int i = k - 8; i < 9; ++i) acc += (uint64_t)M[i] * PL[k - i];
+        for (int i = k - 8; i < 9; ++i) fql_mac_const(acc, M[i], PL[k - i]);
         r.l[k - 9] = (uint32_t)acc & kMask29;
         acc >>= 29;
     }
@@ -191,21 +224,21 @@ JOLT_HD FqL fql_sqr(const FqL& a) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
 #pragma unroll
-        for (int i = 0; 2 * i < k; ++i) acc += (uint64_t)a.l[i] * a2[k - i];
-        if (k % 2 == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
+        for (int i = 0; 2 * i < k; ++i) fql_mac(acc, a.l[i], a2[k - i]);
+        if (k % 2 == 0) fql_mac(acc, a.l[k / 2], a.l[k / 2]);
 #pragma unroll
-        for (int i = 0; i < k; ++i) acc += (uint64_t)M[i] * PL[k - i];
+        for (int i = 0; i < k; ++i) fql_mac_const(acc, M[i], PL[k - i]);
         M[k] = ((uint32_t)acc * fql::NINV) & kMask29;
-        acc += (uint64_t)M[k] * PL[0];
+        fql_mac_const(acc, M[k], PL[0]);
         acc >>= 29;
     }
 #pragma unroll
     for (int k = 9; k < 18; ++k) {
 #pragma unroll
-        for (int i = k - 8; 2 * i < k; ++i) acc += (uint64_t)a.l[i] * a2[k - i];
-        if (k % 2 == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
+        for (int i = k - 8; 2 * i < k; ++i) fql_mac(acc, a.l[i], a2[k - i]);
+        if (k % 2 == 0) fql_mac(acc, a.l[k / 2], a.l[k / 2]);
 #pragma unroll
-        for (int i = k - 8; i < 9; ++i) acc += (uint64_t)M[i] * PL[k - i];
+        for (int i = k - 8; i < 9; ++i) fql_mac_const(acc, M[i], PL[k - i]);
         r.l[k - 9] = (uint32_t)acc & kMask29;
         acc >>= 29;
     }
@@ -241,6 +274,24 @@ JOLT_HD FqL fql_diff(const FqL& a, const FqL& b, const FqL& c) {
         int32_t t = (int32_t)a.l[k] + (int32_t)MP[k] - (int32_t)b.l[k] + carry;  // every term below 2^29 (the top limbs far below): no overflow
         if (WITH_C) t -= (int32_t)(c.l[k] << 1);
         r.l[k] = k < 8 ? ((uint32_t)t & kMask29) : (uint32_t)t;  // the value is positive: the top limb takes what is left
+        carry = t >> 29;
+    }
+    return r;
+}
+// The difference of g1xl_add_mixed_common's R with the SIGN of a as a per-lane mask (m = 0: a + 4p - b, exactly fql_diff<4>; m = ~0: 7p - a - b),
+// still one carry pass.  With B = (3p + ones) / 2 and C = (11p + ones) / 2 (ones = sum_k 2^(29 k)) as limb constants:
+//   t_k = ((a_k - B_k) ^ m) + C_k - b_k;   m = 0: a - B + C - b = a + 4p - b;   m = ~0: (x ^ ~0 = -x - 1 per limb) -(a - B) - ones + C - b = 7p - a - b.
+// 7 is the smallest odd multiple that keeps the negated difference positive (a < 1.6 p, b < 3.6 p: the result lies in (1.8 p, 7 p)); an even one would need
+// (m p + ones) / 2 to be an integer, which it is not.  Every |term| < 2^29 (top limbs far below): no overflow.
+JOLT_HD FqL fql_diff_signed(const FqL& a, const FqL& b, uint32_t m) {
+    constexpr uint32_t BL[9] = {fql::PM1H(3, 0), fql::PM1H(3, 1), fql::PM1H(3, 2), fql::PM1H(3, 3), fql::PM1H(3, 4), fql::PM1H(3, 5), fql::PM1H(3, 6), fql::PM1H(3, 7), fql::PM1H(3, 8)};
+    constexpr uint32_t CL[9] = {fql::PM1H(11, 0), fql::PM1H(11, 1), fql::PM1H(11, 2), fql::PM1H(11, 3), fql::PM1H(11, 4), fql::PM1H(11, 5), fql::PM1H(11, 6), fql::PM1H(11, 7), fql::PM1H(11, 8)};
+    FqL r;
+    int32_t carry = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int32_t t = (((int32_t)a.l[k] - (int32_t)BL[k]) ^ (int32_t)m) + (int32_t)CL[k] - (int32_t)b.l[k] + carry;
+        r.l[k] = k < 8 ? ((uint32_t)t & kMask29) : (uint32_t)t;
         carry = t >> 29;
     }
     return r;
@@ -319,6 +370,92 @@ JOLT_HD G1XyzzL g1xl_add_mixed(const G1XyzzL& p, const FqL& qx, const FqL& qy, c
     r.y = fql_mul2(R, fql_diff<8, false>(Q, r.x, Q), fql_diff<4, false>(fql_zero(), p.y, Q), PPP);  // R (Q - X3) + (4p - Y) PPP: 53.8 + 6.4 p^2, below 1.4 p
     r.zzz = fql_mul(p.zzz, PPP);
     return r;
+}
+
+// ---- the same addition for the inner loop of the bucket sums: no test on the straight line -----------------------------------------------------------
+// g1xl_add_mixed evaluates its three tests (identity accumulator, ZZ3 = 0, R = 0) in full on every addition although a sum of random points practically never
+// meets them.  Here the ten products and five differences run unconditionally and ONE limb of ZZ3 decides whether anything more is looked at:
+//   * a value in [0, 2p) that is 0 mod p is 0 or p, so its limb 0 is 0 or P(0): `suspect` has no false negative, and a false positive has probability ~2^-28;
+//   * an identity accumulator (ZZ = 0 mod p) gives ZZ3 = ZZ PP = 0 mod p as well: the same flag covers it, no test of its own;
+//   * R is only looked at once ZZ3 is known to be zero (inside g1xl_add_mixed, on the slow path).
+// The sign of the point is a mask (neg_mask = ~0: add (qx, -qy)) applied inside R instead of a negation of the stored words: qy enters only as S2 = qy ZZZ and
+// R = S2 + 4p - Y; for the negated point R = 7p - S2 - Y (fql_diff_signed).  Ranges with the sign: R in (0.4, 5.6) as before or in (1.8, 7);
+// R^2 < 49 p^2, X3 = R^2 + 6p - PPP - 2Q still in (1.2, 7.6); R (Q + 8p - X3) + (4p - Y) PPP < 7 * 9.6 + 4 * 1.6 = 73.6 p^2 (53.8 + 6.4 without the sign), so
+// Y3 < 1.44 p (1.4 without); all far below the 169 p^2 the products accept, and X < 7.6, Y < 3.6, ZZ, ZZZ < 1.6 hold on exit as on entry.
+// For neg_mask = 0 every intermediate is the SAME integer as in g1xl_add_mixed, hence the same limbs; for ~0 the same residues.
+JOLT_HD G1XyzzL g1xl_add_mixed_common(const G1XyzzL& p, const FqL& qx, const FqL& qy, uint32_t neg_mask, bool& suspect) {
+    const FqL U2 = fql_mul(qx, p.zz);
+    const FqL S2 = fql_mul(qy, p.zzz);
+    const FqL P = fql_diff<8, false>(U2, p.x, U2);
+    const FqL R = fql_diff_signed(S2, p.y, neg_mask);
+    const FqL PP = fql_sqr(P);
+    const FqL PPP = fql_mul(P, PP);
+    const FqL Q = fql_mul(p.x, PP);
+    G1XyzzL r;
+    r.zz = fql_mul(p.zz, PP);
+    suspect = r.zz.l[0] == 0u || r.zz.l[0] == fql::P(0);
+    r.x = fql_diff<6, true>(fql_sqr(R), PPP, Q);
+    r.y = fql_mul2(R, fql_diff<8, false>(Q, r.x, Q), fql_diff<4, false>(fql_zero(), p.y, Q), PPP);
+    r.zzz = fql_mul(p.zzz, PPP);
+    return r;
+}
+JOLT_HD FqL fql_signed_y(const FqL& qy, uint32_t neg_mask) {  // qy canonical: p - qy in (0, p]
+    return neg_mask ? fql_diff<1, false>(fql_zero(), qy, qy) : qy;
+}
+// The slow path behind `suspect`.  It is entered with the common path's RESULT r and not with the accumulator the result came from: holding the accumulator across
+// the addition for a retry through g1xl_add_mixed costs 36 live registers (tried first: 168 VGPRs and 208 B of scratch in k_fx_buckets_ordered_staged against 154 and
+// none).  What the exact tests need is still there:
+//   * `ident`: the accumulator was the identity.  A loop carries this bit beside the accumulator; it only changes here and in g1xl_from_affine, because ZZ = 0 mod p
+//     arises in no other way (ZZ3 = ZZ PP is zero iff ZZ or P is, and P = 0 never gets past the filter);
+//   * otherwise ZZ3 = 0 mod p (exact test, all nine limbs) means P = 0 mod p, the same x.  Then PPP = Q = 0 and X3 = R^2: X3 (lazily reduced, in (1.2 p, 7.6 p)) is a
+//     multiple of p iff R is -- the same point again (double it) -- and anything else is its negative;
+//   * ZZ3 != 0 mod p: the filter's false positive, r stands as it is.
+JOLT_HD G1XyzzL g1xl_add_mixed_rare(const G1XyzzL& r, bool& ident, const FqL& qx, const FqL& qy, uint32_t neg_mask, const FqL& one) {
+    if (ident) {
+        ident = false;
+        G1XyzzL q;
+        q.x = qx;
+        q.y = fql_signed_y(qy, neg_mask);
+        q.zz = one;
+        q.zzz = one;
+        return q;
+    }
+    if (!fql_is_zero(r.zz)) return r;
+    if (fql_is_multiple_of_p<7>(r.x)) return g1xl_double_affine(qx, fql_signed_y(qy, neg_mask));
+    ident = true;
+    return g1xl_identity();
+}
+// the first point of a list: the accumulator starts as (x, +-y, 1, 1) instead of entering the common path as the identity
+JOLT_HD G1XyzzL g1xl_from_affine(const G1Affine& q, uint32_t neg_mask, const FqL& one, bool& ident) {
+    ident = g1_aff_is_inf(q);
+    if (ident) return g1xl_identity();
+    G1XyzzL r;
+    r.x = fql_from_words(q.x);
+    r.y = fql_signed_y(fql_from_words(q.y), neg_mask);
+    r.zz = one;
+    r.zzz = one;
+    return r;
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#define JOLT_WAVE_ANY(x) __any(x)
+#else
+#define JOLT_WAVE_ANY(x) (x)
+#endif
+// acc += +-q for a point given as the table's words (L-form coordinates, (0, 0) = infinity): the step of every limb-form bucket loop.  Both rare things sit behind
+// wave-uniform branches: the point at infinity behind one word of each coordinate (a table of random points has none; the 16-word test runs only when that word is
+// zero in some lane), the special cases of the addition behind `suspect`.  The slow path reads the point again from `src` (the loop's copy of the words is dead by then).
+JOLT_HD void g1xl_accumulate(G1XyzzL& acc, bool& ident, const G1Affine& q, const G1Affine* __restrict__ src, uint32_t neg_mask, const FqL& one) {
+    bool skip = false;
+    if (JOLT_WAVE_ANY((q.x.l[0] | q.y.l[0]) == 0u)) skip = g1_aff_is_inf(q);
+    if (skip) return;
+    bool suspect;
+    acc = g1xl_add_mixed_common(acc, fql_from_words(q.x), fql_from_words(q.y), neg_mask, suspect);
+    if (JOLT_WAVE_ANY(suspect)) {
+        if (suspect) {
+            const G1Affine again = *src;
+            acc = g1xl_add_mixed_rare(acc, ident, fql_from_words(again.x), fql_from_words(again.y), neg_mask, one);
+        }
+    }
 }
 
 }  // namespace jolt

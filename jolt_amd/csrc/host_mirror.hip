@@ -785,7 +785,8 @@ extern "C" int32_t jolt_host_fq_limb_op(int32_t op, const jolt_fr_t* a, const jo
     return JOLT_OK;
 }
 // sum of `count` affine points (standard Montgomery coordinates, (0, 0) = infinity; negate[i] != 0 adds -P_i) through the limb-form XYZZ
-// accumulator of the bucket kernels: g1xl_add_mixed with its identity / doubling / P + (-P) branches, then the conversion back
+// accumulator exactly as the bucket kernels walk a list: the first point starts the accumulator (g1xl_from_affine), every later one goes through
+// g1xl_accumulate (common path, then the slow path behind its `suspect` flag: identity / doubling / P + (-P) / infinity), then the conversion back
 extern "C" int32_t jolt_host_g1_sum_limb_form(const uint64_t* points /* count x 8 u64: x, y */, const uint8_t* negate, size_t count, jolt_g1_t* out) {
     if ((!points && count) || !out) return JOLT_ERR_INVALID_ARG;
     using namespace jolt;
@@ -794,20 +795,60 @@ extern "C" int32_t jolt_host_g1_sum_limb_form(const uint64_t* points /* count x 
     const Fq m32 = to_mont(thirty_two);
     const FqL one = fql_from_words(m32), r256 = fql_from_words(Fq::one());
     G1XyzzL acc = g1xl_identity();
+    bool ident = true;
     for (size_t i = 0; i < count; ++i) {
         G1Affine p;
         std::memcpy(&p, points + 8 * i, sizeof(p));
-        if (g1_aff_is_inf(p)) continue;
-        if (negate && negate[i]) p.y = neg(p.y);
-        acc = g1xl_add_mixed(acc, fql_from_words(mul(p.x, m32)), fql_from_words(mul(p.y, m32)), one);
+        p.x = mul(p.x, m32);  // the table's words: L-form, (0, 0) stays (0, 0)
+        p.y = mul(p.y, m32);
+        const uint32_t neg_mask = negate && negate[i] ? ~0u : 0u;
+        if (i == 0) acc = g1xl_from_affine(p, neg_mask, one, ident);
+        else g1xl_accumulate(acc, ident, p, &p, neg_mask, one);
     }
+    if (ident != g1xl_is_identity(acc)) return JOLT_ERR_INVALID_ARG;  // invariant: the carried bit and the exact test agree
     G1Jac r = g1_identity();
-    if (!g1xl_is_identity(acc)) {
+    if (!ident) {
         r.x = fql_to_std(fql_mul(acc.x, fql_sqr(acc.zz)), r256);
         r.y = fql_to_std(fql_mul(acc.y, fql_sqr(acc.zzz)), r256);
         r.z = fql_to_std(acc.zzz, r256);
     }
     std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+// ONE mixed addition on raw limbs, through both paths of fq_limb.hip.h.  acc = 36 limbs (X, Y, ZZ, ZZZ: nine 29-bit limbs each, the top limb takes what a lazily
+// reduced value has above 2^261), q = 18 limbs (qx, qy: canonical L-form values), negate != 0 adds (qx, -qy).  Out, 36 limbs each: `common` = g1xl_add_mixed_common,
+// `full` = the unchanged g1xl_add_mixed on (qx, +-qy), `step` = what a loop iteration leaves (common, then g1xl_add_mixed_rare when suspect);
+// *suspect = the common path's flag; canon = 2 x 4 x 8 words: common and full as canonical field elements (fql_to_std of X, Y, ZZ, ZZZ).
+extern "C" int32_t jolt_host_g1xl_add_paths(const uint32_t* acc, const uint32_t* q, int32_t negate, uint32_t* common, uint32_t* full, uint32_t* step, int32_t* suspect,
+                                            uint32_t* canon) {
+    if (!acc || !q || !common || !full || !step || !suspect || !canon) return JOLT_ERR_INVALID_ARG;
+    using namespace jolt;
+    Fq thirty_two = Fq::zero();
+    thirty_two.l[0] = 32;
+    const FqL one = fql_from_words(to_mont(thirty_two)), r256 = fql_from_words(Fq::one());
+    G1XyzzL p;
+    FqL qx, qy;
+    std::memcpy(&p, acc, sizeof(p));
+    std::memcpy(&qx, q, sizeof(qx));
+    std::memcpy(&qy, q + 9, sizeof(qy));
+    const uint32_t neg_mask = negate ? ~0u : 0u;
+    bool sus = false;
+    const G1XyzzL c = g1xl_add_mixed_common(p, qx, qy, neg_mask, sus);
+    const G1XyzzL f = g1xl_add_mixed(p, qx, fql_signed_y(qy, neg_mask), one);
+    bool ident = g1xl_is_identity(p);  // the bit a loop carries beside its accumulator
+    const G1XyzzL s = sus ? g1xl_add_mixed_rare(c, ident, qx, qy, neg_mask, one) : c;
+    std::memcpy(common, &c, sizeof(c));
+    std::memcpy(full, &f, sizeof(f));
+    std::memcpy(step, &s, sizeof(s));
+    *suspect = sus ? 1 : 0;
+    const G1XyzzL* both[2] = {&c, &f};
+    for (int k = 0; k < 2; ++k) {
+        const FqL* co[4] = {&both[k]->x, &both[k]->y, &both[k]->zz, &both[k]->zzz};
+        for (int j = 0; j < 4; ++j) {
+            const Fq v = fql_to_std(*co[j], r256);
+            std::memcpy(canon + (k * 4 + j) * 8, &v, sizeof(v));
+        }
+    }
     return JOLT_OK;
 }
 extern "C" int32_t jolt_host_fr_add(const jolt_fr_t* a, const jolt_fr_t* b, jolt_fr_t* out) {

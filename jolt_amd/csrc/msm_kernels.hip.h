@@ -269,30 +269,33 @@ struct LformConsts {
 };
 __device__ __forceinline__ G1Jac sum_bucket_points_lform(const uint32_t* __restrict__ src, const G1Affine* __restrict__ bases, uint32_t lo, uint32_t hi, uint32_t stride,
                                                          const LformConsts& lc) {
-    G1XyzzL acc = g1xl_identity();
     if (lo >= hi) return g1_identity();
     const FqL one = fql_from_words(lc.one_l);
     uint32_t v = src[lo];
     G1Affine p = ld_aff(bases + (v & 0x7FFFFFFFu));
-    for (uint32_t k = lo;;) {  // software pipeline: the next index and point are in flight during the addition
-        const uint32_t kn = k + stride;
-        const bool more = kn < hi;
-        uint32_t vn = 0;
-        G1Affine pn = p;
-        if (more) {
-            vn = src[kn];
-            pn = ld_aff(bases + (vn & 0x7FFFFFFFu));
+    bool ident;  // the accumulator is the identity: carried beside it, see g1xl_add_mixed_rare
+    G1XyzzL acc = g1xl_from_affine(p, (uint32_t)((int32_t)v >> 31), one, ident);  // the first point starts the accumulator: no identity enters the loop
+    if (lo + stride < hi) {
+        uint32_t k = lo + stride;
+        v = src[k];
+        p = ld_aff(bases + (v & 0x7FFFFFFFu));
+        for (;;) {  // software pipeline: the next index and point are in flight during the addition
+            const uint32_t kn = k + stride;
+            const bool more = kn < hi;
+            uint32_t vn = 0;
+            G1Affine pn = p;
+            if (more) {
+                vn = src[kn];
+                pn = ld_aff(bases + (vn & 0x7FFFFFFFu));
+            }
+            g1xl_accumulate(acc, ident, p, bases + (v & 0x7FFFFFFFu), (uint32_t)((int32_t)v >> 31), one);  // the sign goes into the addition as a mask (fq_limb.hip.h)
+            if (!more) break;
+            v = vn;
+            p = pn;
+            k = kn;
         }
-        if (!g1_aff_is_inf(p)) {
-            if (v >> 31) p.y = neg(p.y);  // the words are a canonical field element (the L-form of y): negation commutes
-            acc = g1xl_add_mixed(acc, fql_from_words(p.x), fql_from_words(p.y), one);
-        }
-        if (!more) break;
-        v = vn;
-        p = pn;
-        k = kn;
     }
-    if (g1xl_is_identity(acc)) return g1_identity();
+    if (ident) return g1_identity();
     const FqL r256 = fql_from_words(lc.r256);
     G1Jac out;  // (X, Y, ZZ, ZZZ) ~ Jacobian (X ZZ^2, Y ZZZ^2, ZZZ)
     out.x = fql_to_std(fql_mul(acc.x, fql_sqr(acc.zz)), r256);
@@ -322,34 +325,36 @@ template <int CH>
 __device__ __forceinline__ G1Jac sum_bucket_points_lform_staged(const uint32_t* __restrict__ src, const G1Affine* __restrict__ bases, uint32_t cnt, const LformConsts& lc,
                                                                 uint32_t* __restrict__ col /* this lane's LDS column: entry j at col[j * kBlock] */) {
     if (cnt == 0) return g1_identity();
-    G1XyzzL acc = g1xl_identity();
     const FqL one = fql_from_words(lc.one_l);
     stage_indices<CH>(col, src, 0u, cnt);
     uint32_t v = col[0], first = 0;
     G1Affine p = ld_aff(bases + (v & 0x7FFFFFFFu));
-    for (uint32_t k = 0;;) {  // software pipeline as in sum_bucket_points_lform: the next point is in flight during the addition
-        const uint32_t kn = k + 1;
-        const bool more = kn < cnt;
-        uint32_t vn = 0;
-        G1Affine pn = p;
-        if (more) {
-            if (kn - first == (uint32_t)CH) {  // chunk used up (wave-uniform for lists of equal length, which is how the bucket order hands them out)
-                first = kn;
-                stage_indices<CH>(col, src, first, cnt);
+    bool ident;  // the accumulator is the identity: carried beside it, see g1xl_add_mixed_rare
+    G1XyzzL acc = g1xl_from_affine(p, (uint32_t)((int32_t)v >> 31), one, ident);  // the first point starts the accumulator: no identity enters the loop
+    if (cnt > 1) {
+        v = col[kBlock];  // CH >= 2: entry 1 is in the first chunk
+        p = ld_aff(bases + (v & 0x7FFFFFFFu));
+        for (uint32_t k = 1;;) {  // software pipeline as in sum_bucket_points_lform: the next point is in flight during the addition
+            const uint32_t kn = k + 1;
+            const bool more = kn < cnt;
+            uint32_t vn = 0;
+            G1Affine pn = p;
+            if (more) {
+                if (kn - first == (uint32_t)CH) {  // chunk used up (wave-uniform for lists of equal length, which is how the bucket order hands them out)
+                    first = kn;
+                    stage_indices<CH>(col, src, first, cnt);
+                }
+                vn = col[(kn - first) * kBlock];
+                pn = ld_aff(bases + (vn & 0x7FFFFFFFu));
             }
-            vn = col[(kn - first) * kBlock];
-            pn = ld_aff(bases + (vn & 0x7FFFFFFFu));
+            g1xl_accumulate(acc, ident, p, bases + (v & 0x7FFFFFFFu), (uint32_t)((int32_t)v >> 31), one);  // the sign goes into the addition as a mask (fq_limb.hip.h)
+            if (!more) break;
+            v = vn;
+            p = pn;
+            k = kn;
         }
-        if (!g1_aff_is_inf(p)) {
-            if (v >> 31) p.y = neg(p.y);
-            acc = g1xl_add_mixed(acc, fql_from_words(p.x), fql_from_words(p.y), one);
-        }
-        if (!more) break;
-        v = vn;
-        p = pn;
-        k = kn;
     }
-    if (g1xl_is_identity(acc)) return g1_identity();
+    if (ident) return g1_identity();
     const FqL r256 = fql_from_words(lc.r256);
     G1Jac out;
     out.x = fql_to_std(fql_mul(acc.x, fql_sqr(acc.zz)), r256);

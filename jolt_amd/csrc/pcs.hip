@@ -48,9 +48,21 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(JOLT_BUC
     // accumulator stays in limb form (fq_limb.hip.h)
     G1Xyzz acc = g1x_identity();
     G1XyzzL acc_l = g1xl_identity();
+    bool ident = true;  // acc_l is the identity: carried beside it, see g1xl_add_mixed_rare
     const FqL one = fql_from_words(lc.one_l);
-    // software pipeline as in sum_bucket_points<true>: the next index byte and point are in flight during the mixed addition
     size_t j = lo + cls + (((size_t)blockIdx.x * kBlock + threadIdx.x) << shift);
+    if (LFORM) {
+        // the lane's first hot cycle starts the accumulator, so that no identity enters the common path of the addition (fq_limb.hip.h); a cold cycle is known
+        // from its index and costs no comparison of coordinates
+        for (; j < cycles; j += stride) {
+            const uint32_t a0 = hot_load(col, j, wide);
+            if (a0 == kColdIdx) continue;
+            acc_l = g1xl_from_affine(ld_aff(bases + (size_t)a0 * folded_cycles + (j >> shift)), 0u, one, ident);
+            j += stride;
+            break;
+        }
+    }
+    // software pipeline as in sum_bucket_points<true>: the next index byte and point are in flight during the mixed addition
     uint32_t a = j < cycles ? hot_load(col, j, wide) : kColdIdx;
     G1Affine pt;
     pt.x = Fq::zero();
@@ -64,17 +76,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(JOLT_BUC
         pn.y = Fq::zero();
         if (an != kColdIdx) pn = ld_aff(bases + (size_t)an * folded_cycles + (jn >> shift));
         if (LFORM) {
-            if (!g1_aff_is_inf(pt)) acc_l = g1xl_add_mixed(acc_l, fql_from_words(pt.x), fql_from_words(pt.y), one);
+            if (a != kColdIdx) g1xl_accumulate(acc_l, ident, pt, bases + (size_t)a * folded_cycles + (j >> shift), 0u, one);
         } else {
             acc = g1x_add_mixed(acc, pt);  // (0, 0) = infinity: a cold cycle adds nothing
         }
         pt = pn;
+        a = an;
         j = jn;
     }
     G1Jac mine = g1x_to_jac(acc);
     if (LFORM) {
         mine = g1_identity();
-        if (!g1xl_is_identity(acc_l)) {
+        if (!ident) {
             const FqL r256 = fql_from_words(lc.r256);
             mine.x = fql_to_std(fql_mul(acc_l.x, fql_sqr(acc_l.zz)), r256);
             mine.y = fql_to_std(fql_mul(acc_l.y, fql_sqr(acc_l.zzz)), r256);

@@ -1,5 +1,5 @@
 // jolt_amd/csrc/tools/microbench.hip -- measurement tool (not part of the shipped library).
-// Run on the GPU box:  hipcc --offload-arch=gfx950 -O3 -std=c++17 microbench.hip -o microbench && ./microbench
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 microbench.hip -o microbench; run: ./microbench [log_n] [issue]  (issue: only the instruction-class table)
 // Measures: HBM copy bandwidth, v_mad_u64_u32 issue rate, register-resident Fr mul rates (full / shifted challenge),
 // and the LowToHigh bind kernel variants, so that design choices in DESIGN.md are backed by numbers.
 #include <hip/hip_runtime.h>
@@ -185,6 +185,46 @@ static double time_ms(hipStream_t s, int reps, const std::function<void()>& f) {
     return ms / reps;
 }
 
+// ---- issue cost per instruction class at a fixed occupancy (the inner loop of the limb-form mixed addition, fq_limb.hip.h) -------------------------------------------
+// Register-only loops, eight independent chains per lane unless stated, 64 operations per iteration; the grid is waves-per-SIMD blocks of 256 lanes per CU, so every SIMD
+// holds exactly that many waves.  Plain C++: the class each loop compiles to is checked in the ISA (hipcc -S), not assumed.
+//   0 v_mad_u64_u32, 8 chains   1 v_mad_u64_u32, ONE dependent chain   2 v_mul_lo_u32   3 v_lshrrev_b64   4 v_lshl_add_u64   5 v_alignbit_b32   6 v_and_b32
+//   7 v_cndmask_b32   8 v_add_u32 (the plain VALU yardstick); 6 and 7 alternate with v_add_u32 (32 + 32 per iteration): subtract half of line 8
+template <int OP, int WAVES>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_issue(uint64_t* out, uint32_t a0, uint32_t sh, uint64_t v64, int iters) {
+    uint32_t x[8];
+    uint64_t w[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        x[k] = a0 * (k + 3) + threadIdx.x;
+        w[k] = ((uint64_t)x[k] << 32) | (a0 + k);
+    }
+    const bool pick = (threadIdx.x * a0) & 4;
+#pragma unroll 1
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int n = (k + 1) & 7;
+                if (OP == 0) w[k] = (uint64_t)(uint32_t)w[n] * x[k] + w[k];  // the factor comes from the neighbour chain's last step: no closed form
+                if (OP == 1) w[0] = (uint64_t)(uint32_t)w[0] * x[k] + w[0];
+                if (OP == 2) x[k] = x[k] * x[n];
+                if (OP == 3) w[k] = w[k] >> sh;
+                if (OP == 4) w[k] = (w[k] << 1) + w[n];
+                if (OP == 5) x[k] = __builtin_amdgcn_alignbit(x[k], x[n], sh);
+                if (OP == 6) x[k] = (u & 1) ? x[k] + x[n] : (x[k] & x[n]);        // every other step an addition: consecutive ands would fuse into v_bitop3_b32
+                if (OP == 7) x[k] = (u & 1) ? x[k] + x[n] : (pick ? x[k] : x[n]);  // likewise: a loop-invariant select alone has a closed form
+                if (OP == 8) x[k] = x[k] + x[n];
+            }
+        }
+    }
+    uint64_t r = v64;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r ^= w[k] ^ x[k];
+    out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = r;
+}
+
 #include <functional>
 
 int main(int argc, char** argv) {
@@ -204,6 +244,31 @@ int main(int argc, char** argv) {
     Fr rs = r; rs.l[0] = rs.l[1] = rs.l[2] = rs.l[3] = 0;
 
     printf("== table 2^%d Fr = %.1f MiB ==\n", logn, n * 32 / 1048576.0);
+    {
+        // issue cost per instruction class (see k_issue): cycles per wave-instruction and SIMD = waves * cycles elapsed / instructions of one wave
+        hipDeviceProp_t prop;
+        CK(hipGetDeviceProperties(&prop, 0));
+        const int cus = prop.multiProcessorCount, iters = 2048;
+        const double ghz = prop.clockRate / 1e6;
+        uint64_t* o; CK(hipMalloc(&o, (size_t)cus * 4 * 256 * sizeof(uint64_t)));
+        const char* names[9] = {"v_mad_u64_u32 x8 chains", "v_mad_u64_u32 dependent", "v_mul_lo_u32", "v_lshrrev_b64", "v_lshl_add_u64", "v_alignbit_b32", "v_and_b32 / v_add_u32", "v_cndmask_b32 / v_add_u32", "v_add_u32"};
+        // VALU instructions in one iteration of each loop as compiled (hipcc -S, ROCm 7): 64 except where the compiler needs two per operation -- v_lshl_add_u64: 121;
+        // the select loop: 74 v_cndmask_b32 + 32 v_add_u32 + 15 v_cmp_eq_u32
+        const int per_iter[9] = {64, 64, 64, 64, 121, 64, 64, 121, 64};
+        printf("== issue cost per instruction class, %d CUs at %.2f GHz (cycles per wave-instruction per SIMD) ==\n", cus, ghz);
+        auto run = [&](int op, int waves) {
+            const int blocks = cus * waves;
+            std::function<void()> f;
+#define JOLT_ISSUE_CASE(OP) if (op == OP) f = [&] { if (waves == 3) k_issue<OP, 3><<<blocks, 256, 0, s>>>(o, 12345u, 7u, 99ull, iters); else k_issue<OP, 1><<<blocks, 256, 0, s>>>(o, 12345u, 7u, 99ull, iters); };
+            JOLT_ISSUE_CASE(0) JOLT_ISSUE_CASE(1) JOLT_ISSUE_CASE(2) JOLT_ISSUE_CASE(3) JOLT_ISSUE_CASE(4) JOLT_ISSUE_CASE(5) JOLT_ISSUE_CASE(6) JOLT_ISSUE_CASE(7) JOLT_ISSUE_CASE(8)
+#undef JOLT_ISSUE_CASE
+            const double ms = time_ms(s, 5, f);
+            return ms * 1e-3 * ghz * 1e9 / ((double)iters * per_iter[op]) / waves;  // the SIMD's cycles per instruction it issued (waves share it)
+        };
+        for (int op = 0; op < 9; ++op) printf("  %-26s 1 wave/SIMD: %6.2f   3 waves/SIMD: %6.2f\n", names[op], run(op, 1), run(op, 3));
+        CK(hipFree(o));
+        if (argc > 2) return 0;  // microbench <logn> issue: this table only
+    }
     for (int blocks : {2048, 8192}) {
         double ms = time_ms(s, 10, [&] { k_copy<<<blocks, 256, 0, s>>>(in, out, n * 2); });
         printf("copy   grid %5d: %.3f ms  %.2f TB/s (r+w)\n", blocks, ms, 2.0 * n * 32 / ms / 1e9);

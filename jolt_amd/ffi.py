@@ -1738,6 +1738,19 @@ def host_g1_sum_limb_form(points, negate=None):
     return out[0]
 
 
+def host_g1xl_add_paths(acc, q, negate=False):
+    """one limb-form mixed addition through both paths of fq_limb.hip.h.  acc: 36 uint32 limbs (X, Y, ZZ, ZZZ), q: 18 limbs (qx, qy).
+    Returns dict(common, full, step: (4, 9) uint32 limbs; suspect: bool; canon_common, canon_full: (4, 8) uint32 standard Montgomery words)"""
+    a = np.ascontiguousarray(acc, dtype=np.uint32).reshape(36)
+    b = np.ascontiguousarray(q, dtype=np.uint32).reshape(18)
+    common, full, step = (np.zeros((4, 9), dtype=np.uint32) for _ in range(3))
+    canon = np.zeros((2, 4, 8), dtype=np.uint32)
+    sus = C.c_int32()
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    _ck(lib().jolt_host_g1xl_add_paths(vp(a), vp(b), C.c_int32(1 if negate else 0), vp(common), vp(full), vp(step), C.byref(sus), vp(canon)), "jolt_host_g1xl_add_paths")
+    return {"common": common, "full": full, "step": step, "suspect": bool(sus.value), "canon_common": canon[0], "canon_full": canon[1]}
+
+
 def host_fx_digits(scalar, window_bits):
     """(signed digits as Python ints, bucket count) of the fixed-base MSM's recoding of one Montgomery-form scalar"""
     keys = np.zeros(64, dtype=np.uint32)

@@ -248,6 +248,7 @@ extern "C" {
     pub fn jolt_host_mul_limbs29(field: i32, a: *const jolt_fr_t, b: *const jolt_fr_t, out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_fq_limb_op(op: i32, a: *const jolt_fr_t, b: *const jolt_fr_t, c: *const jolt_fr_t, d: *const jolt_fr_t, out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_g1_sum_limb_form(points: *const u64, negate: *const u8, count: usize, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_host_g1xl_add_paths(acc: *const u32, q: *const u32, negate: i32, common: *mut u32, full: *mut u32, step: *mut u32, suspect: *mut i32, canon: *mut u32) -> i32;
     pub fn jolt_host_fx_digits(scalar: *const jolt_fr_t, window_bits: u32, keys_out: *mut u32, n_windows_out: *mut u32, buckets_out: *mut u32) -> i32;
     pub fn jolt_host_fx_segment_capacity(n: u64, window_bits: u32, segment: u32, capacity: *mut u32) -> i32;
     pub fn jolt_host_univariate_from_evals(evals: *const jolt_fr_t, n: usize, coeffs_out: *mut jolt_fr_t) -> i32;
