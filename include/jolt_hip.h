@@ -563,8 +563,36 @@ int32_t jolt_ints_free(jolt_ctx *ctx, jolt_ints *values);
  * (JOLT_ERR_SIZE_MISMATCH, :192-195). */
 int32_t jolt_dory_commit_rows(jolt_ctx *ctx, const jolt_srs *srs, const jolt_ints *values, size_t row_width, jolt_g1_t *out);
 /* out[chunk*k + row] for the cycles / chunk_width chunks of hot-index column `poly`; an empty row gives the identity
- * (Bn254G1::default(), streaming.rs:409-418).  Same argument checks as above (:376-392). */
+ * (Bn254G1::default(), streaming.rs:409-418).  Same argument checks as above (:376-392).
+ * As an OpeningHint: finish_one_hot_column_major_chunks (streaming.rs:318-362) transposes the chunks, hint[row*chunks + chunk] =
+ * out[chunk*k + row]; with chunk_width = 2^sigma that is row (k << (log_t - sigma)) + chunk of the cycle-major grid matrix of 2^sigma
+ * columns -- the row order jolt_dory_fold_rows_grid's `left` and jolt_dory_combine_hints use.  A dense column's hint is
+ * jolt_dory_commit_rows with row_width = 2^sigma: the first T / 2^sigma rows of that matrix (address 0). */
 int32_t jolt_dory_commit_onehot(jolt_ctx *ctx, const jolt_srs *srs, const jolt_onehot *source, size_t poly, size_t chunk_width, jolt_g1_t *out);
+
+/* The G1 and Fr work of a Dory opening ahead of the pairing rounds.  Cycle-major placement (TracePolynomialOrder::CycleMajor): grid
+ * index k*T + j, dense columns at k = 0, as for the jolt_grid_* entry points below.  What stays on the host is G2 / GT: the tier-2
+ * multi-pairing and the reduce-and-fold rounds of dory::prove.
+ *
+ * RlcSource::fold_rows over TraceOpeningPoly (optimized/opening.rs:491-510, multilinear.rs:452-462), cycle-major -- the
+ * vector_matrix_product of dory::prove (crates/jolt-dory/src/scheme.rs:612-618), answered from the per-cycle columns without the K x T grid:
+ *   out[c] = sum_p onehot_scalars[p] * sum_{j hot in p, ((hot_p(j) << log_t) | j) & (2^sigma - 1) == c} left[((hot_p(j) << log_t) | j) >> sigma]
+ *          + sum_d dense_scalars[d]  * sum_{j & (2^sigma - 1) == c} left[j >> sigma] * dense[d][j]
+ * Sources, scalars and dense columns as in jolt_grid_joint_polynomial; left has 2^(log_k + log_t - sigma) entries; out gets 2^sigma.
+ * Every sigma in [0, log_k + log_t]; T must be a power of two.  JOLT_ERR_INVALID_ARG: sigma out of range, source->k > 2^log_k;
+ * JOLT_ERR_SIZE_MISMATCH: left or a dense column of the wrong length, sources with different cycle counts; JOLT_ERR_UNSUPPORTED: more
+ * than 4 sources or 8 dense columns, log_k > 8, or no column at all.  Temporary device memory is O(T), never O(K * T). */
+int32_t jolt_dory_fold_rows_grid(jolt_ctx *ctx, const jolt_onehot *const *sources, size_t n_sources, const jolt_fr_t *onehot_scalars,
+                                 jolt_table *const *dense, size_t n_dense, const jolt_fr_t *dense_scalars, uint32_t log_k, uint32_t sigma,
+                                 const jolt_table *left, jolt_table **out);
+/* DoryScheme::combine_hints (crates/jolt-dory/src/scheme.rs:325-360): out[row] = sum_i scalars[i] * hints[i][row] for row < max_i hint_rows[i];
+ * a hint shorter than the widest contributes the identity to the rows it lacks (:330-338).  Host pointers in and out, like the commit entry points that produced the hints.
+ * n_hints == 0 is JOLT_ERR_INVALID_ARG (the reference asserts).  The hint's commit_blind, a dot product of n_hints field elements, stays with the caller. */
+int32_t jolt_dory_combine_hints(jolt_ctx *ctx, const jolt_g1_t *const *hints, const size_t *hint_rows, size_t n_hints, const jolt_fr_t *scalars,
+                                jolt_g1_t *out /* max_i hint_rows[i] */);
+/* One row of jolt_dory_combine_hints on the host, out = sum_i scalars[i] * points[i] (scheme.rs:339-356), through the code the device rows run: shared signed-digit
+ * plan, per-window walk by descending digit, Horner recombination.  For the CPU suite. */
+int32_t jolt_host_dory_combine_row(const jolt_g1_t *points, const jolt_fr_t *scalars, size_t n, jolt_g1_t *out);
 
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)

@@ -13,6 +13,8 @@
 // one workgroup per row that folds its windows (running-sum reduction + Horner).  Only the windows the batch's largest
 // magnitude needs are processed (an OR-reduction over the batch decides).  Integer VALU work, no MFMA.
 #include <algorithm>
+#include <cstring>
+#include <vector>
 
 #include "ctx.hpp"
 #include "msm_kernels.hip.h"
@@ -509,5 +511,358 @@ extern "C" int32_t jolt_dory_commit_onehot(jolt_ctx* ctx, const jolt_srs* srs, c
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return hip_fail(ctx, "dory one-hot", e);
     }
+    return JOLT_OK;
+}
+
+// =====================================================================================================================
+// The opening's G1 and Fr work ahead of the pairing rounds (crates/jolt-dory/src/scheme.rs): the vector-matrix product
+// of dory::prove, answered lazily from the per-cycle columns (RlcSource::fold_rows over TraceOpeningPoly,
+// crates/jolt-kernels/src/optimized/opening.rs:439-511, crates/jolt-poly/src/multilinear.rs:447-462), and
+// DoryScheme::combine_hints (scheme.rs:325-360).  Tier 2 (G2 / GT) and the reduce-and-fold rounds stay on the host.
+// =====================================================================================================================
+namespace {
+
+constexpr int kFoldMaxSources = 4;   // the limits of jolt_grid_joint_polynomial (pcs.hip)
+constexpr int kFoldMaxDense = 8;
+constexpr uint32_t kFoldSlice = 32;  // matrix rows per address block that one workgroup stages in LDS and one thread walks
+struct FoldArgs {
+    const uint8_t* idx[kFoldMaxSources];  // [polys of the source][cycles]
+    uint32_t wide[kFoldMaxSources];
+    uint32_t n_polys[kFoldMaxSources];
+    uint32_t first[kFoldMaxSources];      // offset of the source's first polynomial in `scalars`
+    int n_sources;
+    const Fr* dense[kFoldMaxDense];
+    Fr dense_scalar[kFoldMaxDense];
+    int n_dense;
+};
+
+// sigma <= log_t: the column of grid entry (k, j) is j & (2^sigma - 1) whatever k, so output column c OWNS the cycles c, c + 2^sigma, ... -- a gather, no atomics.
+// The M = T / 2^sigma cycles of a column are cut into slices of `slice`; thread = (column, slice): lane <-> column, so the index bytes of a wavefront are 64
+// consecutive bytes.  Per polynomial the inner sum is additions only (left[(hot << log_m) + m] picked by the hot address), one multiplication by the polynomial's
+// scalar per (polynomial, column, slice).  The K * slice entries of `left` a workgroup can touch sit in LDS (pitch slice + 1: lanes with different hot
+// addresses fall on different banks); use_lds = 0 (K too large for LDS) gathers them from global memory, where the 2^nu-entry vector lives in L2.
+// partial[s * 2^sigma + c] = the share of slice s; k_dory_fold_sum adds the slices.
+__global__ __launch_bounds__(kBlock) void k_dory_fold_cols(FoldArgs a, const Fr* __restrict__ scalars, const Fr* __restrict__ left, uint32_t log_t, uint32_t sigma,
+                                                           uint32_t K, uint32_t slice, uint32_t col_groups, uint32_t use_lds, Fr* __restrict__ partial) {
+    extern __shared__ __align__(16) unsigned char fold_raw[];
+    Fr* sh = reinterpret_cast<Fr*>(fold_raw);
+    const uint32_t log_m = log_t - sigma, pitch = slice + 1;
+    const size_t cols = (size_t)1 << sigma;
+    const uint32_t sl = blockIdx.x / col_groups;
+    const size_t c = (size_t)(blockIdx.x % col_groups) * kBlock + threadIdx.x;
+    const size_t m0 = (size_t)sl * slice;
+    if (use_lds) {
+        for (uint32_t e = threadIdx.x; e < K * slice; e += kBlock) {
+            const uint32_t h = e / slice, mm = e % slice;
+            sh[h * pitch + mm] = ld_fr(left + ((size_t)h << log_m) + m0 + mm);
+        }
+        __syncthreads();
+    }
+    if (c >= cols) return;
+    Fr acc = Fr::zero();
+    for (int s = 0; s < a.n_sources; ++s) {
+        for (uint32_t p = 0; p < a.n_polys[s]; ++p) {
+            const uint8_t* col = hot_col(a.idx[s], (size_t)p << log_t, a.wide[s]);
+            Fr sum = Fr::zero();
+            bool any = false;
+#pragma unroll 8
+            for (uint32_t mm = 0; mm < slice; ++mm) {
+                const uint32_t h = hot_load(col, ((m0 + mm) << sigma) + c, a.wide[s]);
+                if (h < K) {  // cold cycles (the sentinel) select no row
+                    sum = add(sum, use_lds ? sh[h * pitch + mm] : ld_fr(left + ((size_t)h << log_m) + m0 + mm));
+                    any = true;
+                }
+            }
+            if (any) acc = add(acc, mul(sum, scalars[a.first[s] + p]));
+        }
+    }
+    for (int d = 0; d < a.n_dense; ++d) {  // dense columns live on address 0: matrix row m, the deferred-reduction accumulator over the slice's products
+        Fr sum = Fr::zero();
+        WideAcc<FrParams> w = wide_zero<FrParams>();
+        int pending = 0;
+        for (uint32_t mm = 0; mm < slice; ++mm) {
+            const Fr l = use_lds ? sh[mm] : ld_fr(left + m0 + mm);
+            wide_fmadd(w, l, ld_fr(a.dense[d] + ((m0 + mm) << sigma) + c));
+            if (++pending == kWideMaxProducts) {
+                sum = add(sum, wide_reduce(w));
+                w = wide_zero<FrParams>();
+                pending = 0;
+            }
+        }
+        if (pending) sum = add(sum, wide_reduce(w));
+        acc = add(acc, mul(sum, a.dense_scalar[d]));
+    }
+    st_fr(partial + (size_t)sl * cols + c, acc);
+}
+__global__ __launch_bounds__(kBlock) void k_dory_fold_sum(const Fr* __restrict__ partial, size_t cols, uint32_t slices, Fr* __restrict__ out) {
+    const size_t c = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= cols) return;
+    Fr acc = ld_fr(partial + c);
+    for (uint32_t s = 1; s < slices; ++s) acc = add(acc, ld_fr(partial + (size_t)s * cols + c));
+    st_fr(out + c, acc);
+}
+// sigma > log_t: the column index takes in the low sigma - log_t address bits, c = ((hot & amask) << log_t) | j, and the row is hot >> (sigma - log_t).  Still a
+// gather: one thread per output column walks the polynomials of its cycle.  The plain general path.
+__global__ __launch_bounds__(kBlock) void k_dory_fold_wide(FoldArgs a, const Fr* __restrict__ scalars, const Fr* __restrict__ left, uint32_t log_t, uint32_t sigma,
+                                                           uint32_t K, Fr* __restrict__ out) {
+    const size_t c = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= ((size_t)1 << sigma)) return;
+    const uint32_t shift = sigma - log_t, amask = (1u << shift) - 1;
+    const uint32_t lowaddr = (uint32_t)(c >> log_t);
+    const size_t j = c & (((size_t)1 << log_t) - 1);
+    Fr acc = Fr::zero();
+    for (int s = 0; s < a.n_sources; ++s) {
+        for (uint32_t p = 0; p < a.n_polys[s]; ++p) {
+            const uint32_t h = hot_load(a.idx[s], ((size_t)p << log_t) + j, a.wide[s]);
+            if (h < K && (h & amask) == lowaddr) acc = add(acc, mul(ld_fr(left + (h >> shift)), scalars[a.first[s] + p]));
+        }
+    }
+    if (lowaddr == 0) {
+        const Fr l0 = ld_fr(left);
+        for (int d = 0; d < a.n_dense; ++d) acc = add(acc, mul(mul(l0, ld_fr(a.dense[d] + j)), a.dense_scalar[d]));
+    }
+    st_fr(out + c, acc);
+}
+
+// ---- combine_hints ----------------------------------------------------------------------------------------------------
+// out[row] = sum_i s_i P_i[row]: every row multiplies by the SAME scalars, so the signed-digit decomposition is done once on the host and the bucket
+// of term i in window w is the same for every row.  Per window the host lists the terms by DESCENDING digit magnitude; a row then needs no bucket array at
+// all: walking the list with `running += +-P_i`, and `acc += running` once per magnitude level passed on the way down, gives sum_b b * (bucket b) with
+// two accumulators (the running-sum reduction of the bucket method, with the buckets emitted in order).  Control flow depends on the plan alone -- uniform
+// over the rows of a wavefront; only the special cases of the group law (identity, P + P, P - P) diverge.
+// Group operations per row: windows * (n + 2^(c-1) + c + 1) at most = 51 * (n + 22) for c = 5, against 1.5 * 254 * n of double-and-add.
+constexpr int kCombineWindow = 5;                                               // c: signed digits in [-16, 16]
+constexpr int kCombineWindows = (254 + 1 + kCombineWindow - 1) / kCombineWindow;  // r < 2^254; one spare bit takes the last carry
+constexpr uint32_t kCombineIdxMask = 0x00FFFFFFu;                               // plan entry: term | magnitude << 24 | negative << 31
+
+struct CombinePlan {
+    std::vector<uint32_t> ent;    // per window, the terms with a non-zero digit, by descending magnitude
+    std::vector<uint32_t> start;  // kCombineWindows + 1 offsets into ent
+};
+// scalars in Montgomery form; false: one of them is not canonical
+bool combine_plan(const jolt_fr_t* scalars, size_t n, CombinePlan* plan) {
+    constexpr uint32_t B = 1u << (kCombineWindow - 1);
+    std::vector<uint8_t> mag((size_t)kCombineWindows * n), sgn((size_t)kCombineWindows * n);
+    for (size_t i = 0; i < n; ++i) {
+        const Fr m = fr_from_abi(&scalars[i]);
+        if (!fr_is_canonical(m)) return false;
+        const Fr k = from_mont(m);
+        uint32_t carry = 0;
+        for (int w = 0; w < kCombineWindows; ++w) {
+            const int bit = w * kCombineWindow, limb = bit >> 5, off = bit & 31;
+            const uint64_t two = (uint64_t)k.l[limb] | (limb + 1 < 8 ? (uint64_t)k.l[limb + 1] << 32 : 0ull);
+            uint32_t raw = ((uint32_t)(two >> off) & ((1u << kCombineWindow) - 1)) + carry;
+            if (raw > B) { mag[w * n + i] = (uint8_t)((1u << kCombineWindow) - raw); sgn[w * n + i] = 1; carry = 1; }
+            else { mag[w * n + i] = (uint8_t)raw; sgn[w * n + i] = 0; carry = 0; }
+        }
+    }
+    plan->ent.clear();
+    plan->start.assign(kCombineWindows + 1, 0);
+    for (int w = 0; w < kCombineWindows; ++w) {
+        plan->start[w] = (uint32_t)plan->ent.size();
+        for (uint32_t b = B; b >= 1; --b)
+            for (size_t i = 0; i < n; ++i)
+                if (mag[w * n + i] == b) plan->ent.push_back((uint32_t)i | (b << 24) | ((uint32_t)sgn[w * n + i] << 31));
+    }
+    plan->start[kCombineWindows] = (uint32_t)plan->ent.size();
+    return true;
+}
+
+// sum over the window's terms of digit_i * P_i; load(i) = term i's point of this row
+template <class Load>
+JOLT_HD G1Jac combine_window(const uint32_t* __restrict__ ent, uint32_t count, Load&& load) {
+    G1Jac running = g1_identity(), acc = g1_identity();
+    uint32_t level = count ? (ent[0] >> 24) & 0x7Fu : 0u;
+    for (uint32_t k = 0; k < count; ++k) {
+        const uint32_t e = ent[k], m = (e >> 24) & 0x7Fu;
+        for (; level > m; --level) acc = g1_add(acc, running);
+        G1Jac p = load(e & kCombineIdxMask);
+        if (e >> 31) p.y = neg(p.y);
+        running = g1_add(running, p);
+    }
+    for (; level > 0; --level) acc = g1_add(acc, running);
+    return acc;
+}
+// sum_w 2^(c w) S_w, most significant window first; win(w) = S_w
+template <class Win>
+JOLT_HD G1Jac combine_horner(Win&& win) {
+    G1Jac acc = g1_identity();
+    for (int w = kCombineWindows - 1; w >= 0; --w) {
+        for (int k = 0; k < kCombineWindow; ++k) acc = g1_double(acc);
+        acc = g1_add(acc, win(w));
+    }
+    return acc;
+}
+
+// thread = (row, window): blockIdx.y = window, so the plan entries are uniform over the workgroup.  points = the hints back to back, hint i at offset[i] with
+// hint_rows[i] rows; a hint shorter than the widest contributes the identity to the rows it lacks.  wsum[w * rows + r], r counted from row0.
+__global__ __launch_bounds__(kBlock) void k_dory_combine_windows(const G1Jac* __restrict__ points, const uint64_t* __restrict__ offset, const uint64_t* __restrict__ hint_rows,
+                                                                 const uint32_t* __restrict__ ent, const uint32_t* __restrict__ start, size_t row0, size_t rows,
+                                                                 G1Jac* __restrict__ wsum) {
+    const size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= rows) return;
+    const uint32_t w = blockIdx.y;
+    const size_t row = row0 + r;
+    const uint32_t lo = start[w], hi = start[w + 1];
+    wsum[(size_t)w * rows + r] = combine_window(ent + lo, hi - lo, [&](uint32_t i) { return row < hint_rows[i] ? points[offset[i] + row] : g1_identity(); });
+}
+__global__ __launch_bounds__(kBlock) void k_dory_combine_horner(const G1Jac* __restrict__ wsum, size_t rows, G1Jac* __restrict__ out) {
+    const size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (r >= rows) return;
+    const G1Jac acc = combine_horner([&](int w) { return wsum[(size_t)w * rows + r]; });
+    out[r] = g1_is_identity(acc) ? g1_identity() : acc;
+}
+
+}  // namespace
+
+extern "C" int32_t jolt_dory_fold_rows_grid(jolt_ctx* ctx, const jolt_onehot* const* sources, size_t n_sources, const jolt_fr_t* onehot_scalars,
+                                            jolt_table* const* dense, size_t n_dense, const jolt_fr_t* dense_scalars, uint32_t log_k, uint32_t sigma,
+                                            const jolt_table* left, jolt_table** out) {
+    if (!ctx || !out || !left || (n_sources && (!sources || !onehot_scalars)) || (n_dense && (!dense || !dense_scalars))) return JOLT_ERR_INVALID_ARG;
+    if (n_sources > (size_t)kFoldMaxSources || n_dense > (size_t)kFoldMaxDense || log_k > 8 || n_sources + n_dense == 0) return JOLT_ERR_UNSUPPORTED;
+    const uint32_t K = 1u << log_k;
+    FoldArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (size_t s = 0; s < n_sources; ++s) if (!sources[s]) return JOLT_ERR_INVALID_ARG;
+    for (size_t d = 0; d < n_dense; ++d) if (!dense[d]) return JOLT_ERR_INVALID_ARG;
+    const size_t T = n_sources ? sources[0]->cycles : dense[0]->len;
+    const int log_t = log2_exact(T);
+    JOLT_REQUIRE(ctx, log_t >= 0, "fold_rows: the cycle count must be a power of two");
+    JOLT_REQUIRE(ctx, sigma <= log_k + (uint32_t)log_t, "fold_rows: sigma exceeds the grid's variables");
+    size_t total = 0;
+    for (size_t s = 0; s < n_sources; ++s) {
+        if (sources[s]->cycles != T) return JOLT_ERR_SIZE_MISMATCH;
+        JOLT_REQUIRE(ctx, sources[s]->k <= K, "fold_rows: a hot address outside the grid");
+        a.idx[s] = sources[s]->idx;
+        a.wide[s] = sources[s]->wide;
+        a.n_polys[s] = (uint32_t)sources[s]->n_polys;
+        a.first[s] = (uint32_t)total;
+        total += sources[s]->n_polys;
+    }
+    a.n_sources = (int)n_sources;
+    for (size_t d = 0; d < n_dense; ++d) {
+        if (dense[d]->len != T) return JOLT_ERR_SIZE_MISMATCH;
+        a.dense[d] = dense[d]->data();
+        a.dense_scalar[d] = fr_from_abi(&dense_scalars[d]);
+        JOLT_REQUIRE(ctx, fr_is_canonical(a.dense_scalar[d]), "scalar is not a canonical Fr");
+    }
+    a.n_dense = (int)n_dense;
+    const uint32_t nu = log_k + (uint32_t)log_t - sigma;
+    if (left->len != (size_t)1 << nu) return JOLT_ERR_SIZE_MISMATCH;
+    for (size_t p = 0; p < total; ++p) JOLT_REQUIRE(ctx, fr_is_canonical(fr_from_abi(&onehot_scalars[p])), "scalar is not a canonical Fr");
+
+    const size_t cols = (size_t)1 << sigma;
+    jolt_table *r = nullptr, *ds = nullptr;
+    JOLT_TRY(jolt_internal_table_new(ctx, cols, &r));
+    int32_t st = JOLT_OK;
+    if (total) st = jolt_table_upload(ctx, onehot_scalars, total, &ds);  // synchronises: the caller's array may be short-lived
+    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
+    const Fr* d_scalars = ds ? (const Fr*)ds->data() : (const Fr*)nullptr;
+    Fr* partial = nullptr;
+    if (sigma <= (uint32_t)log_t) {
+        const size_t M = T >> sigma;
+        const uint32_t slice = (uint32_t)std::min<size_t>(M, kFoldSlice);
+        const size_t slices = M / slice, groups = (cols + kBlock - 1) / kBlock;
+        const size_t lds = (size_t)K * (slice + 1) * sizeof(Fr);
+        const uint32_t use_lds = lds <= 48 * 1024 ? 1u : 0u;
+        if (slices * groups > 0x7FFFFFFFull) { st = JOLT_ERR_UNSUPPORTED; }
+        Fr* dst = r->data();
+        if (st == JOLT_OK && slices > 1) {
+            st = jolt_internal_dev_alloc(ctx, slices * cols * sizeof(Fr), (void**)&partial);
+            dst = partial;
+        }
+        if (st == JOLT_OK) {
+            hipLaunchKernelGGL(k_dory_fold_cols, dim3((unsigned)(slices * groups)), dim3(kBlock), use_lds ? lds : 0, ctx->stream, a, d_scalars, (const Fr*)left->data(),
+                               (uint32_t)log_t, sigma, K, slice, (uint32_t)groups, use_lds, dst);
+            if (slices > 1)
+                hipLaunchKernelGGL(k_dory_fold_sum, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, (const Fr*)partial, cols, (uint32_t)slices, r->data());
+        }
+    } else {
+        hipLaunchKernelGGL(k_dory_fold_wide, dim3((unsigned)((cols + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, a, d_scalars, (const Fr*)left->data(),
+                           (uint32_t)log_t, sigma, K, r->data());
+    }
+    hipError_t e = st == JOLT_OK ? hipGetLastError() : hipSuccess;
+    if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered
+    if (ds) jolt_table_free(ctx, ds);
+    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
+    if (e != hipSuccess) { jolt_table_free(ctx, r); ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
+    *out = r;
+    return JOLT_OK;
+}
+
+extern "C" int32_t jolt_dory_combine_hints(jolt_ctx* ctx, const jolt_g1_t* const* hints, const size_t* hint_rows, size_t n_hints, const jolt_fr_t* scalars,
+                                           jolt_g1_t* out) {
+    if (!ctx) return JOLT_ERR_INVALID_ARG;
+    JOLT_REQUIRE(ctx, n_hints != 0, "combine_hints: no hints");  // scheme.rs:326 assert
+    if (!hints || !hint_rows || !scalars) return JOLT_ERR_INVALID_ARG;
+    if (n_hints > (size_t)kCombineIdxMask) return JOLT_ERR_UNSUPPORTED;
+    size_t rows = 0, total = 0;
+    std::vector<uint64_t> meta(2 * n_hints);  // offsets, then row counts
+    for (size_t i = 0; i < n_hints; ++i) {
+        if (!hints[i] && hint_rows[i]) return JOLT_ERR_INVALID_ARG;
+        meta[i] = total;
+        meta[n_hints + i] = hint_rows[i];
+        total += hint_rows[i];
+        rows = std::max(rows, hint_rows[i]);
+    }
+    CombinePlan plan;
+    JOLT_REQUIRE(ctx, combine_plan(scalars, n_hints, &plan), "scalar is not a canonical Fr");
+    if (rows == 0) return JOLT_OK;
+    if (!out) return JOLT_ERR_INVALID_ARG;
+    hipStream_t st = ctx->stream;
+    const size_t batch = std::min<size_t>(rows, 8192);  // window sums of one pass: 51 * 8192 points, 40 MB
+    const size_t b_meta = meta.size() * 8, b_ent = std::max<size_t>(plan.ent.size(), 1) * 4, b_start = plan.start.size() * 4;
+    G1Jac *d_pts = nullptr, *d_wsum = nullptr, *d_out = nullptr;
+    unsigned char* d_plan = nullptr;
+    int32_t rc = jolt_internal_dev_alloc(ctx, total * sizeof(G1Jac), (void**)&d_pts);
+    if (rc == JOLT_OK) rc = jolt_internal_dev_alloc(ctx, (size_t)kCombineWindows * batch * sizeof(G1Jac), (void**)&d_wsum);
+    if (rc == JOLT_OK) rc = jolt_internal_dev_alloc(ctx, rows * sizeof(G1Jac), (void**)&d_out);
+    if (rc == JOLT_OK) rc = jolt_internal_dev_alloc(ctx, b_meta + b_ent + b_start, (void**)&d_plan);
+    hipError_t e = hipSuccess;
+    if (rc == JOLT_OK) {
+        for (size_t i = 0; i < n_hints && e == hipSuccess; ++i)
+            if (hint_rows[i]) e = hipMemcpyAsync(d_pts + meta[i], hints[i], hint_rows[i] * sizeof(G1Jac), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_plan, meta.data(), b_meta, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && !plan.ent.empty()) e = hipMemcpyAsync(d_plan + b_meta, plan.ent.data(), plan.ent.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_plan + b_meta + b_ent, plan.start.data(), b_start, hipMemcpyHostToDevice, st);
+        const uint64_t* d_off = (const uint64_t*)d_plan;
+        const uint32_t* d_ent = (const uint32_t*)(d_plan + b_meta);
+        const uint32_t* d_start = (const uint32_t*)(d_plan + b_meta + b_ent);
+        for (size_t r0 = 0; r0 < rows && e == hipSuccess; r0 += batch) {
+            const size_t nr = std::min(batch, rows - r0);
+            const unsigned g = (unsigned)((nr + kBlock - 1) / kBlock);
+            hipLaunchKernelGGL(k_dory_combine_windows, dim3(g, kCombineWindows), dim3(kBlock), 0, st, (const G1Jac*)d_pts, d_off, d_off + n_hints, d_ent, d_start, r0, nr,
+                               d_wsum);
+            hipLaunchKernelGGL(k_dory_combine_horner, dim3(g), dim3(kBlock), 0, st, (const G1Jac*)d_wsum, nr, d_out + r0);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, rows * sizeof(G1Jac), hipMemcpyDeviceToHost, st);
+        hipError_t e2 = hipStreamSynchronize(st);  // the plan and the caller's arrays are read until here
+        if (e == hipSuccess) e = e2;
+    }
+    jolt_internal_dev_free(ctx, d_pts);
+    jolt_internal_dev_free(ctx, d_wsum);
+    jolt_internal_dev_free(ctx, d_out);
+    jolt_internal_dev_free(ctx, d_plan);
+    if (rc != JOLT_OK) return rc;
+    if (e != hipSuccess) return hip_fail(ctx, "dory combine", e);
+    return JOLT_OK;
+}
+
+// The per-row routine of k_dory_combine_windows / k_dory_combine_horner on the host: out = sum_i scalars[i] * points[i], through the same plan, window walk and Horner
+// recombination, so that the suite pins them against the oracle without a GPU.
+extern "C" int32_t jolt_host_dory_combine_row(const jolt_g1_t* points, const jolt_fr_t* scalars, size_t n, jolt_g1_t* out) {
+    if (!out || (n && (!points || !scalars)) || n > (size_t)kCombineIdxMask) return JOLT_ERR_INVALID_ARG;
+    CombinePlan plan;
+    if (!combine_plan(scalars, n, &plan)) return JOLT_ERR_INVALID_ARG;
+    const G1Jac acc = combine_horner([&](int w) {
+        return combine_window(plan.ent.data() + plan.start[w], plan.start[w + 1] - plan.start[w], [&](uint32_t i) {
+            G1Jac p;
+            std::memcpy(&p, &points[i], sizeof(p));
+            return p;
+        });
+    });
+    const G1Jac r = g1_is_identity(acc) ? g1_identity() : acc;
+    std::memcpy(out, &r, sizeof(r));
     return JOLT_OK;
 }

@@ -1242,6 +1242,62 @@ Context.dory_commit_rows = _dory_commit_rows
 Context.dory_commit_onehot = _dory_commit_onehot
 
 
+# ---- the Dory opening ahead of the pairing rounds (dory.hip): lazy row fold and hint combination
+DORY_COMBINE_WINDOW = 5  # kCombineWindow of dory.hip: signed digits of 5 bits
+
+
+def dory_combine_ops_per_row(n_hints, window=DORY_COMBINE_WINDOW):
+    """Upper bound on the group operations one row of dory_combine_hints performs: per window one addition per term, one per magnitude level of the
+    running-sum walk, `window` doublings and the Horner addition; (double_and_add = 1.5 * 254 * n_hints is the number it is held against)."""
+    windows = (254 + 1 + window - 1) // window
+    return windows * (n_hints + (1 << (window - 1)) + window + 1)
+
+
+def dory_onehot_hint(chunk_commitments):
+    """finish_one_hot_column_major_chunks (streaming.rs:318-362): the (chunks, k, 12) output of dory_commit_onehot as the column's hint,
+    hint[row * chunks + chunk] = out[chunk * k + row] -- with chunk_width = 2^sigma, row (k << (log_t - sigma)) + chunk of the grid matrix."""
+    c = np.asarray(chunk_commitments, dtype=np.uint64)
+    return np.ascontiguousarray(c.transpose(1, 0, 2)).reshape(-1, c.shape[2])
+
+
+def _dory_fold_rows_grid(self, sources, onehot_scalars, dense, dense_scalars, log_k, sigma, left):
+    """RlcSource::fold_rows(left, sigma) of the batch's joint polynomial over the 2^log_k x T grid, from the hot indices and dense columns: 2^sigma entries."""
+    hs = (C.c_void_p * max(len(sources), 1))(*[s.h for s in sources])
+    ds = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
+    osc = fr(np.stack([fr(c) for c in onehot_scalars])).reshape(-1, 4) if len(onehot_scalars) else None
+    dsc = fr(np.stack([fr(c) for c in dense_scalars])).reshape(-1, 4) if len(dense_scalars) else None
+    h = C.c_void_p()
+    _ck(lib().jolt_dory_fold_rows_grid(self.h, hs if sources else None, C.c_size_t(len(sources)), _p(osc), ds if dense else None, C.c_size_t(len(dense)),
+                                       _p(dsc), C.c_uint32(log_k), C.c_uint32(sigma), left.h, C.byref(h)), "jolt_dory_fold_rows_grid", self)
+    return Table(self, h)
+
+
+def _dory_combine_hints(self, hints, scalars):
+    """DoryScheme::combine_hints: hints = list of (rows_i, 12) point arrays, scalars = one Fr each; (max rows_i, 12) points."""
+    hs = [np.ascontiguousarray(h, dtype=np.uint64).reshape(-1, 12) for h in hints]
+    n = len(hs)
+    ptrs = (C.c_void_p * max(n, 1))(*[h.ctypes.data for h in hs])
+    rows = (C.c_size_t * max(n, 1))(*[h.shape[0] for h in hs])
+    sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if n else fr_array(1)
+    width = max([h.shape[0] for h in hs], default=0)
+    out = g1_array(max(width, 1))
+    _ck(lib().jolt_dory_combine_hints(self.h, ptrs, rows, C.c_size_t(n), _p(sc), _p(out)), "jolt_dory_combine_hints", self)
+    return out[:width]
+
+
+def host_dory_combine_row(points, scalars):
+    """sum_i scalars[i] * points[i] through the per-row routine of dory_combine_hints, on the host"""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
+    sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if pts.shape[0] else fr_array(1)
+    out = g1_array(1)
+    _ck(lib().jolt_host_dory_combine_row(_p(pts), _p(sc), C.c_size_t(pts.shape[0]), _p(out)), "jolt_host_dory_combine_row")
+    return out[0]
+
+
+Context.dory_fold_rows_grid = _dory_fold_rows_grid
+Context.dory_combine_hints = _dory_combine_hints
+
+
 def _table_op2(name):
     def f(self, a, b):
         h = C.c_void_p()

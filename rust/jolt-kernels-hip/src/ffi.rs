@@ -317,6 +317,9 @@ extern "C" {
     pub fn jolt_ints_free(ctx: *mut jolt_ctx, values: *mut jolt_ints) -> i32;
     pub fn jolt_dory_commit_rows(ctx: *mut jolt_ctx, srs: *const jolt_srs, values: *const jolt_ints, row_width: usize, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_dory_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, poly: usize, chunk_width: usize, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_dory_fold_rows_grid(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, sigma: u32, left: *const jolt_table, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_dory_combine_hints(ctx: *mut jolt_ctx, hints: *const *const jolt_g1_t, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_host_dory_combine_row(points: *const jolt_g1_t, scalars: *const jolt_fr_t, n: usize, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;
