@@ -854,7 +854,7 @@ extern "C" int32_t jolt_stage_op_kept(const jolt_stage_op* op, const char* key, 
     return JOLT_OK;
 }
 extern "C" int32_t jolt_stage_op_window(jolt_stage_op* parent, size_t first, size_t n, jolt_stage_op** out) {
-    if (!parent || !out || first + n > parent->rounds || dynamic_cast<WindowOp*>(parent)) return JOLT_ERR_INVALID_ARG;
+    if (!parent || !out || first > parent->rounds || n > parent->rounds - first || dynamic_cast<WindowOp*>(parent)) return JOLT_ERR_INVALID_ARG;  // (first + n wraps)
     WindowOp* w = new_op<WindowOp>(parent->ctx, parent->name);
     if (!w) return JOLT_ERR_OOM;
     w->parent = parent;
@@ -1346,6 +1346,7 @@ extern "C" int32_t jolt_host_stage_op_prove_alone(jolt_stage_op* op, jolt_host_t
         UnivariatePoly poly;
         JOLT_TRY(op->prove_round(has_bind ? &bind : nullptr, round, running, &poly));
         if (coeffs_out && poly.coefficients.size() > stride) return JOLT_ERR_SIZE_MISMATCH;
+        if (add(poly.evaluate(Fr::zero()), poly.evaluate(Fr::one())) != running) return op->fail(JOLT_ERR_ROUND_CHECK, "round " + std::to_string(round) + ": s(0) + s(1) is not the running claim");  // prover.rs:316-324, as prove_batch
         std::vector<jolt_fr_t> c = to_abi(poly.coefficients);
         JOLT_TRY(jolt_host_transcript_append_fr(transcript, c.data(), poly.coefficients.size()));
         jolt_fr_t r;

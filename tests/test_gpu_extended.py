@@ -93,7 +93,8 @@ def test_a_stage_batch_over_operators_is_the_batch_over_their_members():
     """jolt_host_prove_batch_ops with MORE than one operator, as a stage driver batches the members of a stage (prover.rs:193-362): RAM RAF evaluation (degree 2) and the RAM
     output check (degree 3, split-eq) -- both log K rounds -- and booleanity's address phase (log K_chunk rounds, a later window of the batch: front-loaded inactive rounds)
     under one transcript and random batching coefficients.  The first two are dense members underneath, so the batch over the OPERATORS must equal jolt_host_prove_batch over
-    the same members built by hand (the round-5 path); prove_batch checks s(0) + s(1) against the running claim every round for all three."""
+    the same members built by hand (the round-5 path); prove_batch checks s(0) + s(1) against the running claim every round for all three.  The three-operator batch is
+    checked against the CPU oracle: each operator's twin replayed under the challenges of its window, the batch rebuilt from their messages (tests/stage_batch_replay.py)."""
     from jolt_amd import stages as S
     from util import rand_fr
     n_vars = 10
@@ -131,7 +132,7 @@ def test_a_stage_batch_over_operators_is_the_batch_over_their_members():
     want = ctx.prove_batch([m_raf, m_oc], claims[:2], coeffs[:2], [0, 0], rounds, 3, label=6)
     for key in ("polys", "challenges", "member_claims", "final_claim"):
         assert np.array_equal(ref_ops[key], want[key]), key
-    # the three-operator batch: its own consistency -- the final claim is the batching combination of the members' claims, and the operators' output claims are those of
+    # the three-operator batch: the final claim is the batching combination of the members' claims, and the operators' output claims are those of
     # the operators driven alone at the same point (the bound values are functions of the challenges only)
     acc = np.zeros(4, dtype=np.uint64)
     for c, mc in zip(coeffs, got["member_claims"]):
@@ -140,6 +141,17 @@ def test_a_stage_batch_over_operators_is_the_batch_over_their_members():
     f = folded_again(ctx, dops, raf)
     assert np.array_equal(ops[0].output_claims()[0], ctx.evaluate(f, got["challenges"][::-1]))
     f.free()
+    # ... and against the oracle: the twins of the three operators under the challenges of their windows, batched by the replay checker
+    from stage_batch_replay import ReplayTranscript, check_batch
+    twin = lambda: OracleExtended(n_vars, description=d)
+    adr = twin().address_domain(0, replay={10: got["challenges"], 20: got["challenges"]}, only=["ram_raf_evaluation", "ram_output_check"])
+    boo = twin().booleanity_address(0, transcript=ReplayTranscript(got["challenges"][offsets[2]:]))
+    twins = [adr["ram_raf_evaluation"], adr["ram_output_check"], boo]
+    for mine, t in zip(claims, twins):
+        assert np.array_equal(mine, t["claim"])
+    check_batch(got, [t["polys"] for t in twins], [t["claim"] for t in twins], coeffs, offsets, [rounds, rounds, bo["log_k"]], rounds, 3, label=5, challenge_mode=0)
+    assert np.array_equal(ops[0].output_claims()[0], adr["ram_raf_evaluation"]["ra_claim"]) and np.array_equal(ops[1].output_claims()[0], adr["ram_output_check"]["val_final_claim"])
+    assert np.array_equal(ops[2].output_claims()[0], boo["intermediate"])
     for o in ops + two:
         o.destroy()
     for t in (init, val_final, val_io):

@@ -118,6 +118,61 @@ def test_contract_errors():
     op.destroy()
 
 
+def test_a_window_whose_end_wraps_is_refused():
+    """jolt_stage_op_window: first + n is computed in size_t, so a window that starts or is sized near 2^64 must be refused by comparing n with rounds - first, not the
+    wrapped sum with rounds; the parent is untouched by the refusals"""
+    op, orc, degree, _, _ = members(41, 4, [[0, 1]])
+    for first, n in [(2**64 - 1, 2), (1, 2**64 - 1), (2**64 - 1, 1), (5, 0), (2**63, 2**63)]:
+        with pytest.raises(ffi.JoltError) as e:
+            op.window(first, n)
+        assert e.value.status == 1, (first, n)  # JOLT_ERR_INVALID_ARG
+    whole, empty = op.window(0, 4), op.window(4, 0)  # the limits that are inside
+    assert whole.rounds == 4 and empty.rounds == 0
+    claim = op.input_claim()
+    one = O.to_mont([1])[0]
+    got = ffi.prove_batch_ops([whole], [claim], [one], [0], 4, degree, label=3)
+    want = O.prove_batch([orc], [claim], [one], [0], 4, degree, label=3)
+    for key in ("polys", "challenges", "member_claims", "final_claim"):
+        assert np.array_equal(got[key], want[key]), key
+    assert np.array_equal(np.stack(op.output_claims()), orc.final_values())
+    for o in (whole, empty, op):
+        o.destroy()
+
+
+def test_the_alone_driver_refuses_a_wrong_claim():
+    """jolt_host_stage_op_prove_alone with a claim that is not the operator's sum is JOLT_ERR_ROUND_CHECK (status 8), as under jolt_host_prove_batch_ops.  With the host-only
+    operator it is the OPERATOR's own check that fires (HostExprOp::prove_round, naive.rs:298-306), in the first round, before the driver's s(0) + s(1) check is reached: the
+    host-only operator has no mode without it.  The driver's own check is reached by the device operators that sample every point of their message and never read the claim
+    (booleanity's address phase, the registers' address rounds): tests/test_gpu_stage_batches.py::test_the_alone_driver_checks_what_the_operator_does_not.  Afterwards the
+    transcript has absorbed nothing, and a fresh operator under the right claim proves as before."""
+    n_vars, shape = 5, [[0, 1], [2]]
+    op = members(51, n_vars, shape)[0]
+    claim = op.input_claim()
+    tr = ffi.HostTranscript(4)
+    with pytest.raises(ffi.JoltError) as e:
+        op.prove_alone(tr, O.fr_add(claim, O.to_mont([1])[0])[0])
+    assert e.value.status == 8  # JOLT_ERR_ROUND_CHECK
+    op.destroy()
+    op = members(51, n_vars, shape)[0]
+    w = op.prove_alone(tr, claim)  # the refused call absorbed nothing: the same transcript object goes on as a fresh one
+    tr.close()
+    again, tr = members(51, n_vars, shape)[0], ffi.HostTranscript(4)
+    v = again.prove_alone(tr, claim)
+    tr.close()
+    assert all(np.array_equal(x, y) for x, y in zip(w["polys"], v["polys"])) and np.array_equal(w["challenges"], v["challenges"])
+    # a window handed a claim that is not what the window before it left: refused as well
+    parent = members(51, n_vars, shape)[0]
+    first, second = parent.window(0, 2), parent.window(2, n_vars - 2)
+    tr = ffi.HostTranscript(4)
+    f = first.prove_alone(tr, claim)
+    with pytest.raises(ffi.JoltError) as e:
+        second.prove_alone(tr, claim)
+    assert e.value.status == 8
+    tr.close()
+    for o in (first, second, parent, op, again):
+        o.destroy()
+
+
 @pytest.mark.parametrize("kind", [ffi.TRANSCRIPT_BLAKE2B, ffi.TRANSCRIPT_KECCAK, ffi.TRANSCRIPT_BLAKE2B_SPONGE])
 def test_a_batch_under_the_reference_transcripts_is_the_oracle_batch(kind):
     """prove_batch over operators with the engine in the label's two top bits (LegacyBlake2bTranscript, KeccakTranscript, the Blake2b512 sponge): the library's C++ transcripts

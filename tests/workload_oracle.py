@@ -72,8 +72,10 @@ class OracleOps:
     """jolt_amd.stages.DeviceOps on the CPU oracle: tables are numpy (n, 4) arrays, the pushforwards are the restatements of oracle/address_ops.c (the bytecode one in the
     reference's split-eq two-table form when the weights are eq tables of known points, fold_cycles otherwise), members the dense ones of oracle/sumcheck.c."""
 
-    def __init__(self, indexes, chunk_cols, k_chunk):
-        self.indexes, self.chunk_cols, self.k_chunk = indexes, chunk_cols, k_chunk
+    def __init__(self, indexes, chunk_cols, k_chunk, replay=None):
+        """replay: {transcript label: challenges} -- a `prove` under one of these labels runs the member under the prescribed challenges (stage_batch_replay.replay_member:
+        the member as it runs inside a batch whose challenges these are) instead of as a one-member batch under its own transcript"""
+        self.indexes, self.chunk_cols, self.k_chunk, self.replay = indexes, chunk_cols, k_chunk, dict(replay or {})
         self.one = O.to_mont([1])[0]
         v = lambda a: np.asarray(a, dtype=np.uint64).reshape(1, 4)
         self.mul = lambda a, b: O.fr_mul(v(a), v(b))[0]
@@ -129,6 +131,10 @@ class OracleOps:
         return out, claim, fin
 
     def prove(self, member, claim, n_vars, degree, label):
+        if label in self.replay:
+            from stage_batch_replay import replay_member
+            out = replay_member(member, claim, self.replay[label])
+            return dict(polys=out["polys"], challenges=out["challenges"], final_claim=out["final_claim"])
         out = O.prove_batch([member], [claim], [self.one], [0], n_vars, degree, label=label)
         return dict(polys=out["polys"], challenges=out["challenges"], final_claim=out["final_claim"])
 
@@ -156,7 +162,8 @@ class OracleExtended:
         self.one = O.to_mont([1])[0]
         self.neg = lambda a: O.fr_neg(np.asarray(a).reshape(1, 4))[0]
 
-    def _spartan(self, inputs, eq_sums, tables, tau, kernel, label):
+    def _spartan(self, inputs, eq_sums, tables, tau, kernel, label, challenges=None):
+        """challenges: the remainder's rounds under these prescribed challenges (its rounds inside a batch) instead of as a one-member batch under label + 1"""
         sums = eq_sums()
         tr = O.MockTranscript(label)
         for v in sums:
@@ -166,12 +173,16 @@ class OracleExtended:
         member = O.Member.gruen_product(az, bz, tau, scale=kernel)
         claim = member.input_claim()
         rounds = len(tau)
-        out = O.prove_batch([member], [claim], [self.one], [0], rounds, 3, label=label + 1)
+        if challenges is not None:
+            from stage_batch_replay import replay_member
+            out = replay_member(member, claim, challenges)
+        else:
+            out = O.prove_batch([member], [claim], [self.one], [0], rounds, 3, label=label + 1)
         point = out["challenges"][rounds - self.n_vars:][::-1]
         values = np.stack([O.poly_evaluate(z, point) for z in inputs]) if self.n_vars else np.stack([z[0] for z in inputs])
         return dict(sums=sums, r0=r0, polys=out["polys"], challenges=out["challenges"], final_claim=out["final_claim"], values=values, claim=claim)
 
-    def spartan_outer(self, label):
+    def spartan_outer(self, label, challenges=None):
         d = self.d
         inputs = [O.fr_from_u64(c) for c in d["outer_cols"]]
         n = len(inputs)
@@ -180,9 +191,9 @@ class OracleExtended:
         wb_f = O.fr_from_i64(d["outer_iwb"].reshape(-1)).reshape(shape + (4,))
         eq = O.eq_evals(d["outer_tau"])
         return self._spartan(inputs, lambda: O.r1cs_uniskip_sums(inputs, eq, wa_f, wb_f), lambda: O.r1cs_materialize(inputs, d["outer_wa"], d["outer_wb"]),
-                             d["outer_tau"], d["outer_kernel"], label)
+                             d["outer_tau"], d["outer_kernel"], label, challenges)
 
-    def spartan_product(self, label):
+    def spartan_product(self, label, challenges=None):
         d = self.d
         rows = d["product_rows"]
         two64 = O.to_mont([1 << 64])[0].reshape(1, 4)
@@ -191,9 +202,12 @@ class OracleExtended:
         lanes = [O.fr_from_u64(rows["left_input"]), O.fr_from_u64(rows["lookup_output"]), O.fr_from_u64(rows["jump"].astype(np.uint64)), right,
                  O.fr_from_u64(rows["branch"].astype(np.uint64)), O.fr_from_u64(rows["next_is_noop"].astype(np.uint64))]
         eq = O.eq_evals(d["product_tau"]) if self.n_vars else O.to_mont([1])
-        return self._spartan(lanes, lambda: O.spartan_product_t1(rows, eq), lambda: O.spartan_product_tables(rows, d["product_w"]), d["product_tau"], d["product_kernel"], label)
+        return self._spartan(lanes, lambda: O.spartan_product_t1(rows, eq), lambda: O.spartan_product_tables(rows, d["product_w"]), d["product_tau"], d["product_kernel"], label,
+                             challenges)
 
-    def ram_read_write(self, label):
+    def ram_read_write(self, label, transcript=None):
+        """transcript: an object with append(values) / challenge() to absorb into and draw from instead of the oracle's transcript under `label`
+        (stage_batch_replay.ReplayTranscript: the member under a batch's challenges)"""
         S, d = self.S, self.d
         ram = d["ram"]
         log_t, log_k = ram["log_t"], ram["log_k"]
@@ -241,13 +255,13 @@ class OracleExtended:
                 return self.t.challenge()
 
         S._sub = lambda a, b: O.fr_sub(np.asarray(a).reshape(1, 4), np.asarray(b).reshape(1, 4))[0]
-        out = S.rw_rounds(matrix_round, lambda bind: ingest(log_t + log_k - 1, bind), final_values, log_t, log_k, claim, Tr(label), O.gruen_poly_deg_3,
+        out = S.rw_rounds(matrix_round, lambda bind: ingest(log_t + log_k - 1, bind), final_values, log_t, log_k, claim, transcript if transcript is not None else Tr(label), O.gruen_poly_deg_3,
                           O.univariate_from_evals, O.univariate_evaluate)
         out["claim"] = claim
         orc.close()
         return out
 
-    def registers_read_write(self, label):
+    def registers_read_write(self, label, transcript=None):
         from registers_fixture import inc_table
         S, d = self.S, self.d
         reg = d["registers"]
@@ -297,7 +311,7 @@ class OracleExtended:
                 return orc_tr.challenge()
 
         S._sub = lambda a, b: O.fr_sub(np.asarray(a).reshape(1, 4), np.asarray(b).reshape(1, 4))[0]
-        out = S.rw_rounds(matrix_round, lambda bind: ingest(log_t + log_k - 1, bind), final_values, log_t, log_k, claim, Tr(), O.gruen_poly_deg_3, O.univariate_from_evals,
+        out = S.rw_rounds(matrix_round, lambda bind: ingest(log_t + log_k - 1, bind), final_values, log_t, log_k, claim, transcript if transcript is not None else Tr(), O.gruen_poly_deg_3, O.univariate_from_evals,
                           O.univariate_evaluate, four_point_address=True)
         eq_adr, eq_cyc = O.eq_evals(out["challenges"][log_t:][::-1]), O.eq_evals(out["challenges"][:log_t][::-1])
         out["operand_claims"] = np.stack([O.regrw_operand_claim(reg["rs1"], eq_adr, eq_cyc), O.regrw_operand_claim(reg["rs2"], eq_adr, eq_cyc)])
@@ -319,8 +333,9 @@ class OracleExtended:
             return {8 * p + k for p in (0, 15) for k in range(8)} | {62}
         return {0, 62, 127}
 
-    def instruction_read_raf(self, label):
-        """The twin of DeviceExtended.instruction_read_raf.  The T-scale scans are the oracle's (oracle/read_raf.c) at every size and are compared sum for sum.
+    def instruction_read_raf(self, label, transcript=None, cycle_challenges=None):
+        """The twin of DeviceExtended.instruction_read_raf.  (transcript / cycle_challenges: the address rounds against this transcript instead of the oracle's under `label`,
+        the cycle rounds under these prescribed challenges instead of as a one-member batch under label + 1 -- the operator as ONE member of a batch.)  The T-scale scans are the oracle's (oracle/read_raf.c) at every size and are compared sum for sum.
         The address-round polynomials are the oracle's FROM THE DEFINITION (oracle/lookup_tables.c: evaluate_mle of the row's table at the mixed point, no
         prefix / suffix machinery) for every round up to T = 2^12.  Above that only the rounds of `sampled_direct_rounds` are from the definition -- they are
         asserted equal to what the product's host state machine produces from the ORACLE's scan sums, so at those rounds the address polynomials at trace scale
@@ -332,7 +347,7 @@ class OracleExtended:
         S, d = self.S, self.d
         lk = d["lookup"]
         lists = ffi.lookup_suffix_lists()
-        tr = O.MockTranscript(label)
+        tr = transcript if transcript is not None else O.MockTranscript(label)
         u0 = O.eq_evals(d["lookup_reduction"])
         gamma = d["lookup_gamma"]
         claim = O.read_raf_input_claim(lk["idx"], lk["table"], lk["raf"], u0, gamma)  # first principles: materialize_entry and the operands of every row
@@ -407,7 +422,11 @@ class OracleExtended:
         n_f = 1 + d["ra_count"]
         orc = O.Member.expr([O.eq_evals(d["lookup_reduction"]), combined] + [ra[i] for i in range(d["ra_count"])], [(self.one, list(range(1 + n_f)))], 1 + n_f)
         assert np.array_equal(orc.input_claim(), claim), "the running claim after 128 address rounds is not the sum the cycle rounds start from"
-        out = O.prove_batch([orc], [claim], [self.one], [0], self.n_vars, n_f + 1, label=label + 1)
+        if cycle_challenges is not None:
+            from stage_batch_replay import replay_member
+            out = replay_member(orc, claim, cycle_challenges)
+        else:
+            out = O.prove_batch([orc], [claim], [self.one], [0], self.n_vars, n_f + 1, label=label + 1)
         instruction_ra = orc.final_values()[2:1 + n_f]
         eq_cycle = O.eq_evals(np.asarray(out["challenges"])[::-1])
         flags = O.onehot_pushforward(lk["table"], 64, eq_cycle)
@@ -416,7 +435,7 @@ class OracleExtended:
                     raf_values=np.stack([raf_interleaved, raf_identity]), cycle_claim=claim, polys=out["polys"], challenges=out["challenges"], final_claim=out["final_claim"],
                     claim=input_claim)
 
-    def booleanity_address(self, label):
+    def booleanity_address(self, label, transcript=None):
         S, bo = self.S, self.d["booleanity"]
         K = 1 << bo["log_k"]
         eq = O.eq_evals(bo["reference_cycle"])
@@ -431,12 +450,13 @@ class OracleExtended:
             def challenge(self):
                 return orc_tr.challenge()
 
-        out = S.booleanity_address_rounds(O.BooleanityAddress(masses, bo["gamma"], bo["reference_address"]), bo["log_k"], Tr(), O.univariate_from_evals, O.univariate_evaluate)
+        out = S.booleanity_address_rounds(O.BooleanityAddress(masses, bo["gamma"], bo["reference_address"]), bo["log_k"], transcript if transcript is not None else Tr(),
+                                          O.univariate_from_evals, O.univariate_evaluate)
         out["masses"] = masses
         out["claim"] = np.zeros(4, dtype=np.uint64)
         return out
 
-    def booleanity_cycle(self, label, r_address):
+    def booleanity_cycle(self, label, r_address, challenges=None):
         """the cycle phase FROM THE DEFINITION (crates/jolt-kernels/src/reference/booleanity.rs, the naive tier): a flat Expr member over the dense eq table
         eq(reference_cycle, .) * eq(r_address, reference_address) and the dense columns H_i(j) = gamma^i eq(r_address, hot_i(j)) (0 on a cold cycle), summand
         sum_i (H_i^2 - gamma^i H_i); one-member prove_batch; the output claims are the bound columns divided by gamma^i"""
@@ -465,13 +485,17 @@ class OracleExtended:
             terms.append((neg(rho[i]), [0, 1 + i]))
         member = O.Member.expr([eq] + dense, terms, 3)
         claim = member.input_claim()
-        out = O.prove_batch([member], [claim], [one], [0], self.n_vars, 3, label=label)
+        if challenges is not None:
+            from stage_batch_replay import replay_member
+            out = replay_member(member, claim, challenges)
+        else:
+            out = O.prove_batch([member], [claim], [one], [0], self.n_vars, 3, label=label)
         fv = member.final_values()
         inv = lambda x: O.fr_inv(np.asarray(x).reshape(1, 4))[0]
         return dict(polys=out["polys"], challenges=out["challenges"], final_claim=out["final_claim"], claim=claim,
                     ra_claims=np.stack([mul(fv[1 + i], inv(rho[i])) for i in range(N)]), eq_scalar=fv[0])
 
-    def hamming_weight(self, label):
+    def hamming_weight(self, label, transcript=None):
         S, bo, hw = self.S, self.d["booleanity"], self.d["hamming"]
         K = 1 << bo["log_k"]
         eq = O.eq_evals(hw["r_cycle"]) if self.n_vars else O.to_mont([1])
@@ -487,15 +511,21 @@ class OracleExtended:
                 return orc_tr.challenge()
 
         sub = lambda a, b: O.fr_sub(np.asarray(a).reshape(1, 4), np.asarray(b).reshape(1, 4))[0]
-        out = S.hamming_weight_rounds(O.HammingWeight(masses, hw["gamma"], hw["r_address"], hw["virtualization_points"]), bo["log_k"], Tr(), O.univariate_from_evals,
-                                      O.univariate_evaluate, sub)
+        out = S.hamming_weight_rounds(O.HammingWeight(masses, hw["gamma"], hw["r_address"], hw["virtualization_points"]), bo["log_k"], transcript if transcript is not None else Tr(),
+                                      O.univariate_from_evals, O.univariate_evaluate, sub)
         out["masses"] = masses
         return out
 
-    def address_domain(self, label):
+    def address_domain(self, label, replay=None, only=None):
+        """replay: {transcript label: challenges} for OracleOps (the members under a batch's challenges); only: just these relations"""
         S, d = self.S, self.d
         ram, bc = d["ram"], d["bytecode"]
-        ops = OracleOps({"pc": (bc["push_pc"], 1 << bc["log_k"]), "ram": (ram["addresses"], 1 << ram["log_k"]), "ram_post": ram["post"]}, bc["chunk_cols"], 1 << bc["chunk_bits"])
+        ops = OracleOps({"pc": (bc["push_pc"], 1 << bc["log_k"]), "ram": (ram["addresses"], 1 << ram["log_k"]), "ram_post": ram["post"]}, bc["chunk_cols"], 1 << bc["chunk_bits"],
+                        replay=replay)
+        if only is not None:
+            drivers = {"bytecode_read_raf": lambda: S.bytecode_read_raf(ops, bc, self.n_vars, label), "ram_raf_evaluation": lambda: S.ram_raf_evaluation(ops, ram, d["ram_raf"], label + 10),
+                       "ram_output_check": lambda: S.ram_output_check(ops, ram, d["ram_output"], label + 20)}
+            return {name: drivers[name]() for name in only}
         return {"bytecode_read_raf": S.bytecode_read_raf(ops, bc, self.n_vars, label), "ram_raf_evaluation": S.ram_raf_evaluation(ops, ram, d["ram_raf"], label + 10),
                 "ram_output_check": S.ram_output_check(ops, ram, d["ram_output"], label + 20)}
 
