@@ -1023,6 +1023,16 @@ int32_t jolt_stage_ram_raf_evaluation_create(jolt_ctx *ctx, const jolt_key_index
  * output_claims: {val_final at the bound address point}. */
 int32_t jolt_stage_ram_output_check_create(jolt_ctx *ctx, const jolt_key_index *ram_index, const jolt_ints *post_values, const uint64_t *val_init /* K */,
                                            const uint64_t *val_io /* K */, uint64_t io_lo, uint64_t io_len, const jolt_fr_t *r_address, jolt_stage_op **out);
+/* A device jolt_member as a stage operator: what a slot's prepare returns for a relation that is ONE batch member (Box<dyn SumcheckKernel>, crates/jolt-kernels/src/kernel.rs:72-126;
+ * reference tier crates/jolt-kernels/src/reference/naive.rs:53-377) -- every member kind of this header (expr / lc, split-eq lc / product / uniform, lazily bound RA columns,
+ * compact-scalar columns).  rounds and degree (the message degree) are the member's, input_claim is jolt_member_input_claim, output_claims are jolt_member_final_values: the
+ * bound tables in table order, then the bound eq scalar of a member that carries a split eq.  `member` must belong to `ctx` (JOLT_ERR_INVALID_ARG otherwise) and may be
+ * one operator of a batch only once.
+ * Ownership: by default the operator BORROWS the member -- destroy the operator first, then the member; after jolt_stage_op_destroy the member is as the rounds left it
+ * and jolt_member_reset makes it provable again.  With JOLT_STAGE_MEMBER_OWN jolt_stage_op_destroy destroys the member too.  Either way: operator, then member, then
+ * the tables the member borrows, then the context. */
+#define JOLT_STAGE_MEMBER_OWN 1u
+int32_t jolt_stage_member_create(jolt_ctx *ctx, jolt_member *member, uint32_t flags, jolt_stage_op **out);
 /* Test hook (CPU suite; no device, no context): the reference tier's dense member (NaiveSumcheckProver, crates/jolt-kernels/src/reference/naive.rs:53-377, LowToHigh) over HOST
  * tables as a stage operator, so that the contract and the two drivers below run without a GPU against the oracle's prove_batch.  Tables are copied. */
 int32_t jolt_stage_host_expr_create(const jolt_fr_t *const *tables, size_t len, const jolt_member_desc *desc, jolt_stage_op **out);
@@ -1034,6 +1044,12 @@ int32_t jolt_host_prove_batch_ops(jolt_ctx *ctx, jolt_stage_op *const *ops, size
                                   jolt_fr_t *out_polys, jolt_fr_t *out_challenges, jolt_fr_t *out_member_claims, jolt_fr_t *out_final_claim);
 int32_t jolt_host_stage_op_prove_alone(jolt_stage_op *op, jolt_host_transcript *transcript, jolt_fr_t *claim, jolt_fr_t *coeffs_out, size_t stride,
                                        uint32_t *n_coeffs_out, jolt_fr_t *challenges_out);
+/* jolt_host_prove_batch_ops under the backend's round scheduler (BuildRoundScheduler, crates/jolt-kernels/src/backend.rs:68-70; RoundScheduler, prover.rs:110-120): per round the
+ * operators made by jolt_stage_member_create go into ONE jolt_round_group_prove (one launch set, one wait) and their last binds into ONE jolt_round_group_finish; every other
+ * operator runs as under SequentialRounds.  Same arguments, same outputs, the same bytes.  An operator or a member listed twice is JOLT_ERR_INVALID_ARG. */
+int32_t jolt_host_prove_batch_ops_grouped(jolt_ctx *ctx, jolt_stage_op *const *ops, size_t n_ops, const jolt_fr_t *input_claims, const jolt_fr_t *coefficients,
+                                          const size_t *offsets, size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode,
+                                          jolt_fr_t *out_polys, jolt_fr_t *out_challenges, jolt_fr_t *out_member_claims, jolt_fr_t *out_final_claim);
 
 #ifdef __cplusplus
 }

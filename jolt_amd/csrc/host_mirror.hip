@@ -584,53 +584,116 @@ int32_t SequentialRounds::batch_finish_rounds(std::vector<MemberFinish>& finishe
     return JOLT_OK;
 }
 
-int32_t DeviceGroupedRounds::batch_prove_round(std::vector<MemberRound>& work) {
-    std::vector<jolt_member*> ms;
-    std::vector<jolt_fr_t> bind_store(work.size());
+// One round of `ms` (all on `ctx`) with ONE launch set and ONE wait; item i's message lands in *items[i].  The one inversion of each split-eq message depends only
+// on the challenge: it is computed while the device runs the round.
+static int32_t group_round(jolt_ctx* ctx, const std::vector<jolt_member*>& ms, const std::vector<MemberRound*>& items) {
+    const size_t n = ms.size();
+    std::vector<DeviceMember> dms;
+    std::vector<jolt_fr_t> bind_store(n);
     std::vector<const jolt_fr_t*> binds;
     size_t total = 0;
-    for (size_t i = 0; i < work.size(); ++i) {
-        DeviceMember* dm = dynamic_cast<DeviceMember*>(work[i].member);
-        if (!dm) return JOLT_ERR_UNSUPPORTED;  // mixed host/device batches go through SequentialRounds
-        ms.push_back(dm->m);
-        if (work[i].has_bind) { fr_to_abi(&bind_store[i], work[i].bind); binds.push_back(&bind_store[i]); }
+    for (size_t i = 0; i < n; ++i) {
+        dms.emplace_back(ms[i]);
+        if (items[i]->has_bind) { fr_to_abi(&bind_store[i], items[i]->bind); binds.push_back(&bind_store[i]); }
         else binds.push_back(nullptr);
-        total += dm->n_evals();
+        total += dms[i].n_evals();
     }
     std::vector<jolt_fr_t> evals(total ? total : 1);
-    // the one inversion of each split-eq message depends only on the challenge: compute it while the device runs the round
-    std::vector<Fr> l1(work.size()), inv_l1(work.size());
-    std::vector<char> has_l1(work.size(), 0);
-    for (size_t i = 0; i < work.size(); ++i)
-        has_l1[i] = static_cast<DeviceMember*>(work[i].member)->next_l1(work[i].has_bind, work[i].bind, &l1[i]) && !l1[i].is_zero() ? 1 : 0;
+    std::vector<Fr> l1(n), inv_l1(n);
+    std::vector<char> has_l1(n, 0);
+    for (size_t i = 0; i < n; ++i) has_l1[i] = dms[i].next_l1(items[i]->has_bind, items[i]->bind, &l1[i]) && !l1[i].is_zero() ? 1 : 0;
     const std::function<void()> overlap = [&]() {
-        for (size_t i = 0; i < work.size(); ++i)
+        for (size_t i = 0; i < n; ++i)
             if (has_l1[i]) inv_l1[i] = inv(l1[i]);
     };
-    JOLT_TRY(jolt_internal_round_group_prove(ctx, ms.data(), ms.size(), binds.data(), evals.data(), evals.size(), &overlap));
+    JOLT_TRY(jolt_internal_round_group_prove(ctx, ms.data(), n, binds.data(), evals.data(), evals.size(), &overlap));
     size_t off = 0;
-    for (size_t i = 0; i < work.size(); ++i) {
-        DeviceMember* dm = static_cast<DeviceMember*>(work[i].member);
+    for (size_t i = 0; i < n; ++i) {
         Fr ev[JOLT_MAX_DEGREE + 1];
-        for (size_t k = 0; k < dm->n_evals(); ++k) ev[k] = fr_from_abi(&evals[off + k]);
-        off += dm->n_evals();
-        JOLT_TRY(dm->assemble(ev, work[i].claim, &work[i].message, has_l1[i] ? &inv_l1[i] : nullptr));
-        work[i].has_message = true;
+        for (size_t k = 0; k < dms[i].n_evals(); ++k) ev[k] = fr_from_abi(&evals[off + k]);
+        off += dms[i].n_evals();
+        JOLT_TRY(dms[i].assemble(ev, items[i]->claim, &items[i]->message, has_l1[i] ? &inv_l1[i] : nullptr));
+        items[i]->has_message = true;
     }
     return JOLT_OK;
 }
-int32_t DeviceGroupedRounds::batch_finish_rounds(std::vector<MemberFinish>& finishes) {
-    std::vector<jolt_member*> ms;
-    std::vector<jolt_fr_t> store(finishes.size());
+static int32_t group_finish(jolt_ctx* ctx, const std::vector<jolt_member*>& ms, const std::vector<Fr>& bind_values) {
+    std::vector<jolt_fr_t> store(ms.size());
     std::vector<const jolt_fr_t*> binds;
-    for (size_t i = 0; i < finishes.size(); ++i) {
-        DeviceMember* dm = dynamic_cast<DeviceMember*>(finishes[i].member);
-        if (!dm) return JOLT_ERR_UNSUPPORTED;
-        ms.push_back(dm->m);
-        fr_to_abi(&store[i], finishes[i].bind);
+    for (size_t i = 0; i < ms.size(); ++i) {
+        fr_to_abi(&store[i], bind_values[i]);
         binds.push_back(&store[i]);
     }
     return jolt_round_group_finish(ctx, ms.data(), ms.size(), binds.data());
+}
+
+int32_t DeviceGroupedRounds::batch_prove_round(std::vector<MemberRound>& work) {
+    std::vector<jolt_member*> ms;
+    std::vector<MemberRound*> items;
+    for (MemberRound& item : work) {
+        DeviceMember* dm = dynamic_cast<DeviceMember*>(item.member);
+        if (!dm) return JOLT_ERR_UNSUPPORTED;  // mixed host/device batches go through SequentialRounds or MemberGroupedRounds
+        ms.push_back(dm->m);
+        items.push_back(&item);
+    }
+    return group_round(ctx, ms, items);
+}
+int32_t DeviceGroupedRounds::batch_finish_rounds(std::vector<MemberFinish>& finishes) {
+    std::vector<jolt_member*> ms;
+    std::vector<Fr> binds;
+    for (MemberFinish& f : finishes) {
+        DeviceMember* dm = dynamic_cast<DeviceMember*>(f.member);
+        if (!dm) return JOLT_ERR_UNSUPPORTED;
+        ms.push_back(dm->m);
+        binds.push_back(f.bind);
+    }
+    return group_finish(ctx, ms, binds);
+}
+
+// the contexts of the members that can be grouped, in the order they first appear (one group per context: a stage's batch normally has one)
+template <class Item>
+static std::vector<jolt_ctx*> group_contexts(std::vector<Item>& items) {
+    std::vector<jolt_ctx*> out;
+    for (Item& it : items) {
+        jolt_member* m = it.member->group_member();
+        if (m && std::find(out.begin(), out.end(), m->ctx) == out.end()) out.push_back(m->ctx);
+    }
+    return out;
+}
+int32_t MemberGroupedRounds::batch_prove_round(std::vector<MemberRound>& work) {
+    for (jolt_ctx* ctx : group_contexts(work)) {
+        std::vector<jolt_member*> ms;
+        std::vector<MemberRound*> items;
+        for (MemberRound& item : work) {
+            jolt_member* m = item.member->group_member();
+            if (!m || m->ctx != ctx) continue;
+            ms.push_back(m);
+            items.push_back(&item);
+        }
+        JOLT_TRY(group_round(ctx, ms, items));
+    }
+    for (MemberRound& item : work) {
+        if (item.member->group_member()) continue;
+        JOLT_TRY(item.member->prove_round(item.has_bind ? &item.bind : nullptr, item.local_round, item.claim, &item.message));
+        item.has_message = true;
+    }
+    return JOLT_OK;
+}
+int32_t MemberGroupedRounds::batch_finish_rounds(std::vector<MemberFinish>& finishes) {
+    for (jolt_ctx* ctx : group_contexts(finishes)) {
+        std::vector<jolt_member*> ms;
+        std::vector<Fr> binds;
+        for (MemberFinish& f : finishes) {
+            jolt_member* m = f.member->group_member();
+            if (!m || m->ctx != ctx) continue;
+            ms.push_back(m);
+            binds.push_back(f.bind);
+        }
+        JOLT_TRY(group_finish(ctx, ms, binds));
+    }
+    for (MemberFinish& f : finishes)
+        if (!f.member->group_member()) JOLT_TRY(f.member->finish_rounds(f.bind));
+    return JOLT_OK;
 }
 
 // ---- prove_batch ---------------------------------------------------------------------------------------------

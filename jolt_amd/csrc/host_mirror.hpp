@@ -128,6 +128,8 @@ struct ProveRounds {
     virtual size_t num_rounds() const = 0;
     virtual int32_t prove_round(const Fr* bind, size_t round, const Fr& previous_claim, UnivariatePoly* out) = 0;
     virtual int32_t finish_rounds(const Fr& bind) = 0;
+    // the device member whose rounds ARE this object's rounds (its round sums may be fetched together with other members', MemberGroupedRounds); NULL: none
+    virtual jolt_member* group_member() const { return nullptr; }
 };
 
 // A batch member whose tables live on the GPU: calls jolt_member_prove_round / jolt_member_finish and assembles the
@@ -144,6 +146,7 @@ struct DeviceMember final : ProveRounds {
     // l(1) = scalar * w_i of the NEXT round message, given the bind that the round applies first (split-eq members)
     bool next_l1(bool has_bind, const Fr& bind, Fr* l1) const;
     size_t n_evals() const;
+    jolt_member* group_member() const override { return m; }
 };
 
 // prover.rs:74-107
@@ -175,6 +178,13 @@ struct SequentialRounds final : RoundScheduler {  // prover.rs:124-146
 struct DeviceGroupedRounds final : RoundScheduler {
     jolt_ctx* ctx;
     explicit DeviceGroupedRounds(jolt_ctx* c) : ctx(c) {}
+    int32_t batch_prove_round(std::vector<MemberRound>& work) override;
+    int32_t batch_finish_rounds(std::vector<MemberFinish>& finishes) override;
+};
+// BuildRoundScheduler for a batch that MIXES device members with other ProveRounds objects (a protocol stage: catalogue relations beside stage operators): per round
+// the members that name a device member (ProveRounds::group_member) go into ONE jolt_round_group_prove per context, the final binds into ONE jolt_round_group_finish;
+// everything else runs as under SequentialRounds, after the group.  The messages are SequentialRounds' messages: the grouping changes launches, not values.
+struct MemberGroupedRounds final : RoundScheduler {
     int32_t batch_prove_round(std::vector<MemberRound>& work) override;
     int32_t batch_finish_rounds(std::vector<MemberFinish>& finishes) override;
 };

@@ -19,9 +19,11 @@
 //   jolt_stage_bytecode_read_raf_cycle_create      bytecode_read_raf_cycle                      optimized/bytecode_read_raf.rs:440-690
 //   jolt_stage_ram_raf_evaluation_create           ram_raf_evaluation                           optimized/ram_raf_evaluation.rs:17-62
 //   jolt_stage_ram_output_check_create             ram_output_check                             optimized/ram_output_check.rs:50-215
+//   jolt_stage_member_create                       any Box<dyn SumcheckKernel> a slot returned  kernel.rs:72-126 (a device jolt_member: the catalogue's cycle-domain relations)
 //
 // Drivers (the reference's callers, restated above the contract for the tests and the bench; a Rust host calls prove_round / finish_rounds from ITS prove_batch):
 //   jolt_host_prove_batch_ops     prove_batch (prover.rs:193-362) over operators, the library's test transcript
+//   jolt_host_prove_batch_ops_grouped  the same batch with the member-backed operators of a round in one launch set (MemberGroupedRounds; BuildRoundScheduler, backend.rs:68-70)
 //   jolt_host_stage_op_prove_alone  one operator driven alone, every message absorbed coefficient by coefficient (the loop of the kernels' own unit tests)
 #include <map>
 #include <string>
@@ -687,6 +689,29 @@ struct RamOutputCheckOp final : jolt_stage_op {
     }
 };
 
+// A device jolt_member as a stage operator: what a backend slot returns for a relation that IS one batch member (kernel.rs:72-126) -- the catalogue's cycle-domain
+// relations (lc, split-eq lc / product / uniform, lazily bound RA columns, compact-scalar columns).  The rounds are the member's; group_member() lets
+// MemberGroupedRounds fetch them together with the other members of the round.
+struct MemberOp final : jolt_stage_op {
+    jolt_member* m = nullptr;
+    bool owned = false;
+
+    ~MemberOp() override {
+        if (owned && m) jolt_member_destroy(m);
+    }
+    jolt_member* group_member() const override { return m; }
+    int32_t prove_round(const Fr* bind, size_t, const Fr& claim, UnivariatePoly* out) override { return member_round(ctx, m, bind, claim, out); }
+    int32_t finish_rounds(const Fr& bind) override { return member_finish(m, bind); }
+    int32_t input_claim(Fr* out) override {
+        jolt_fr_t c;
+        JOLT_TRY(jolt_member_input_claim(m, &c));
+        *out = fr_from_abi(&c);
+        return JOLT_OK;
+    }
+    // SumcheckKernel::output_claims (naive.rs:331-347): every table's bound value in table order, then the bound eq scalar of a member that carries a split eq
+    int32_t output_claims(std::vector<Fr>* out) override { return member_finals(m, m->tables.size() + (m->has_split_eq() ? 1 : 0), out); }
+};
+
 // rounds [first, first + n) of a parent operator as an operator of its own: lets a caller put the phases of one kernel (instruction read-RAF: address rounds,
 // cycle rounds) under different drivers or transcripts.  The window's last challenge is carried to the parent's next round by the next window.
 struct WindowOp final : jolt_stage_op {
@@ -1268,6 +1293,27 @@ extern "C" int32_t jolt_stage_ram_output_check_create(jolt_ctx* ctx, const jolt_
     return JOLT_OK;
 }
 
+// A device member as a stage operator (MemberOp).  The operator BORROWS the member unless JOLT_STAGE_MEMBER_OWN is set: destroying a borrowing operator leaves the
+// member as the rounds left it (jolt_member_reset rewinds a member that borrows its tables).
+extern "C" int32_t jolt_stage_member_create(jolt_ctx* ctx, jolt_member* member, uint32_t flags, jolt_stage_op** out) {
+    if (!ctx || !member || !out || (flags & ~(uint32_t)JOLT_STAGE_MEMBER_OWN)) return JOLT_ERR_INVALID_ARG;
+    if (member->ctx != ctx) {
+        ctx->last_error = "stage_member: the member belongs to another context";
+        return JOLT_ERR_INVALID_ARG;
+    }
+    MemberOp* op = new_op<MemberOp>(ctx, "stage_member");
+    if (!op) return JOLT_ERR_OOM;
+    op->m = member;
+    op->owned = (flags & JOLT_STAGE_MEMBER_OWN) != 0;
+    op->rounds = member->rounds;
+    // the largest degree of a round message: cubic Gruen completions; l * q of the uniform product (F factors) and of an eq-weighted summand; the summand's own otherwise
+    if (member->kind == jolt_member::kSplitEqProduct || member->kind == jolt_member::kSplitEqBooleanity) op->degree = 3;
+    else if (member->kind == jolt_member::kSplitEqUniform) op->degree = (size_t)member->uni_F + 1;
+    else op->degree = (size_t)member->degree + (member->eq_weighted ? 1 : 0);
+    *out = op;
+    return JOLT_OK;
+}
+
 // Test hook (CPU suite): the reference tier's dense member over host tables as a stage operator -- see HostExprOp.  `tables`: n_tables arrays of `len` (a power of two)
 // canonical field elements, copied; the descriptor as for jolt_member_create_expr (LowToHigh only).
 extern "C" int32_t jolt_stage_host_expr_create(const jolt_fr_t* const* tables, size_t len, const jolt_member_desc* desc, jolt_stage_op** out) {
@@ -1303,25 +1349,31 @@ extern "C" int32_t jolt_stage_host_expr_create(const jolt_fr_t* const* tables, s
 // drivers
 // ------------------------------------------------------------------------------------------------------------------
 // prove_batch (prover.rs:193-362) over stage operators with the library's test transcript: what a stage driver does with the kernels a backend's slots returned.
-extern "C" int32_t jolt_host_prove_batch_ops(jolt_ctx* ctx, jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients,
-                                             const size_t* offsets, size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode,
-                                             jolt_fr_t* out_polys, jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim) {
-    (void)ctx;  // (may be NULL: host-only operators carry none; device-backed ones carry their own)
+static int32_t prove_batch_ops(jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients, const size_t* offsets,
+                               size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode, bool grouped, jolt_fr_t* out_polys,
+                               jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim) {
     if ((!ops && n_ops) || !input_claims || !coefficients || !offsets || !out_polys || !out_challenges || !out_member_claims || !out_final_claim) return JOLT_ERR_INVALID_ARG;
     std::vector<ProveRounds*> ms;
     std::vector<BatchMember> described;
     for (size_t i = 0; i < n_ops; ++i) {
         if (!ops[i]) return JOLT_ERR_INVALID_ARG;
         if (offsets[i] > max_num_vars || ops[i]->rounds > max_num_vars - offsets[i]) return JOLT_ERR_INVALID_ARG;  // WindowOutOfRange (before the prelude scales claims by 2^(max - rounds))
+        for (size_t j = 0; j < i; ++j) {
+            // one member cannot be two members of a batch (both would bind its tables); the grouped driver also refuses one operator listed twice before any round runs
+            const jolt_member* a = ops[i]->group_member();
+            if ((a && a == ops[j]->group_member()) || (grouped && ops[i] == ops[j])) return ops[i]->fail(JOLT_ERR_INVALID_ARG, "listed twice in one batch");
+        }
         ms.push_back(ops[i]);
         described.push_back(BatchMember{fr_from_abi(&input_claims[i]), fr_from_abi(&coefficients[i]), ops[i]->rounds, offsets[i]});
     }
     BatchPrelude prelude = BatchPrelude::make(std::move(described), max_num_vars, max_degree);
     LabelledTranscript tr(transcript_label);
     SequentialRounds seq;
+    MemberGroupedRounds group;
+    RoundScheduler& sched = grouped ? static_cast<RoundScheduler&>(group) : static_cast<RoundScheduler&>(seq);
     ProvedBatch proved;
     SumcheckError err;
-    JOLT_TRY(prove_batch(prelude, ms, seq, tr, challenge_mode != 0, &proved, &err));
+    JOLT_TRY(prove_batch(prelude, ms, sched, tr, challenge_mode != 0, &proved, &err));
     const size_t stride = max_degree + 1;
     const Fr zero = Fr::zero();
     for (size_t r = 0; r < max_num_vars; ++r)
@@ -1330,6 +1382,22 @@ extern "C" int32_t jolt_host_prove_batch_ops(jolt_ctx* ctx, jolt_stage_op* const
     for (size_t i = 0; i < n_ops; ++i) fr_to_abi(&out_member_claims[i], proved.member_claims[i]);
     fr_to_abi(out_final_claim, proved.final_claim);
     return JOLT_OK;
+}
+extern "C" int32_t jolt_host_prove_batch_ops(jolt_ctx* ctx, jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients,
+                                             const size_t* offsets, size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode,
+                                             jolt_fr_t* out_polys, jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim) {
+    (void)ctx;  // (may be NULL: host-only operators carry none; device-backed ones carry their own)
+    return prove_batch_ops(ops, n_ops, input_claims, coefficients, offsets, max_num_vars, max_degree, transcript_label, challenge_mode, false, out_polys, out_challenges,
+                           out_member_claims, out_final_claim);
+}
+// The same batch under MemberGroupedRounds: per round ONE jolt_round_group_prove over the operators that are device members (jolt_stage_member_create), ONE
+// jolt_round_group_finish at the end, every other operator as above.  The same bytes as jolt_host_prove_batch_ops.
+extern "C" int32_t jolt_host_prove_batch_ops_grouped(jolt_ctx* ctx, jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients,
+                                                     const size_t* offsets, size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode,
+                                                     jolt_fr_t* out_polys, jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim) {
+    (void)ctx;
+    return prove_batch_ops(ops, n_ops, input_claims, coefficients, offsets, max_num_vars, max_degree, transcript_label, challenge_mode, true, out_polys, out_challenges,
+                           out_member_claims, out_final_claim);
 }
 
 // ONE operator driven alone, the way the reference's kernel tests drive a ProveRounds (and the way rounds 2-5 drove these operators from Python): per round the

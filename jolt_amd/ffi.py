@@ -2062,8 +2062,14 @@ def prove_batch_ops(ops, input_claims, coefficients, offsets, max_num_vars, max_
     return _prove_batch_ops(None, ops, input_claims, coefficients, offsets, max_num_vars, max_degree, label, challenge_mode)
 
 
-def _prove_batch_ops(self, ops, input_claims, coefficients, offsets, max_num_vars, max_degree, label=0, challenge_mode=0):
-    """prove_batch (prover.rs:193-362) over stage operators (jolt_host_prove_batch_ops): the same outputs as Context.prove_batch"""
+def prove_batch_ops_grouped(ops, input_claims, coefficients, offsets, max_num_vars, max_degree, label=0, challenge_mode=0):
+    """jolt_host_prove_batch_ops_grouped without a context (host-only operators)"""
+    return _prove_batch_ops(None, ops, input_claims, coefficients, offsets, max_num_vars, max_degree, label, challenge_mode, grouped=True)
+
+
+def _prove_batch_ops(self, ops, input_claims, coefficients, offsets, max_num_vars, max_degree, label=0, challenge_mode=0, grouped=False):
+    """prove_batch (prover.rs:193-362) over stage operators (jolt_host_prove_batch_ops): the same outputs as Context.prove_batch.  grouped: jolt_host_prove_batch_ops_grouped --
+    the operators that are device members (Context.stage_member) go through one round-group launch set per round; the same bytes"""
     n = len(ops)
     hs = (C.c_void_p * n)(*[o.h for o in ops])
     ic = np.ascontiguousarray(np.stack(input_claims), dtype=np.uint64).reshape(-1, 4)
@@ -2071,8 +2077,9 @@ def _prove_batch_ops(self, ops, input_claims, coefficients, offsets, max_num_var
     offs = (C.c_size_t * n)(*offsets)
     polys, chal = fr_array(max(max_num_vars * (max_degree + 1), 1)), fr_array(max(max_num_vars, 1))
     mclaims, final = fr_array(n), fr_array(1)
-    _ck(lib().jolt_host_prove_batch_ops(self.h if self is not None else None, hs, C.c_size_t(n), _p(ic), _p(co), offs, C.c_size_t(max_num_vars), C.c_size_t(max_degree), C.c_uint64(label),
-                                        C.c_int32(challenge_mode), _p(polys), _p(chal), _p(mclaims), _p(final)), "jolt_host_prove_batch_ops", self)
+    name = "jolt_host_prove_batch_ops_grouped" if grouped else "jolt_host_prove_batch_ops"
+    _ck(getattr(lib(), name)(self.h if self is not None else None, hs, C.c_size_t(n), _p(ic), _p(co), offs, C.c_size_t(max_num_vars), C.c_size_t(max_degree), C.c_uint64(label),
+                             C.c_int32(challenge_mode), _p(polys), _p(chal), _p(mclaims), _p(final)), name, self)
     return dict(polys=polys[: max_num_vars * (max_degree + 1)].reshape(max_num_vars, max_degree + 1, 4), challenges=chal[:max_num_vars], member_claims=mclaims, final_claim=final[0])
 
 
@@ -2175,7 +2182,22 @@ def _stage_ram_output_check(self, ram_index, post_values, val_init, val_io, io_l
     return StageOp(self, h, keep=[ram_index, post_values])
 
 
+STAGE_MEMBER_OWN = 1  # JOLT_STAGE_MEMBER_OWN
+
+
+def _stage_member(self, member, own=False):
+    """jolt_stage_member_create: a device Member as a stage operator.  It borrows `member` (which stays the caller's: reset() after the operator is destroyed makes it
+    provable again) unless own=True, in which case destroying the operator destroys the member and the Member handle is emptied here."""
+    h = C.c_void_p()
+    _ck(lib().jolt_stage_member_create(self.h, member.h if member is not None else None, C.c_uint32(STAGE_MEMBER_OWN if own else 0), C.byref(h)), "jolt_stage_member_create", self)
+    if own:
+        member.h = None
+    return StageOp(self, h, keep=[member])
+
+
+Context.stage_member = _stage_member
 Context.prove_batch_ops = _prove_batch_ops
+Context.prove_batch_ops_grouped = lambda self, *a, **k: _prove_batch_ops(self, *a, grouped=True, **k)
 Context.stage_spartan_uniskip_sums = _stage_spartan_uniskip_sums
 Context.stage_spartan_remainder = _stage_spartan_remainder
 Context.stage_ram_read_write = _stage_ram_read_write
