@@ -332,6 +332,11 @@ def committed_address_chunks(r_address, chunk_bits):
     return [padded[i:i + chunk_bits] for i in range(0, padded.shape[0], chunk_bits)]
 
 
+def first_pc(bc):
+    """the PC of the trace's first cycle: that of this block's first row, unless the description says it (a sharded prover's rank > 0 is told rank 0's)"""
+    return int(bc["first_pc"]) if "first_pc" in bc else int(bc["push_pc"][0])
+
+
 def bytecode_read_raf(ops, bc, n_vars, label):
     """Stage 6a then 6b of the bytecode read+RAF check over the adapter `ops` (the device or the oracle): AddressKernel (optimized/bytecode_read_raf.rs:238-437) as the
     reference tier's dense member over the 13 address tables -- the optimized kernel's fused group_evals (:371-392) is field-identical to it, which is its own parity
@@ -346,7 +351,7 @@ def bytecode_read_raf(ops, bc, n_vars, label):
     V = [ops.upload(bc["stage_values"][s]) for s in range(5)]
     hot = np.zeros(K, dtype=np.uint64)
     entry_trace, entry_expected = hot.copy(), hot.copy()
-    entry_trace[int(bc["first_pc"]) if "first_pc" in bc else int(bc["push_pc"][0])] = 1  # the PC of the trace's first cycle (a sharded prover's rank > 0 is told it)
+    entry_trace[first_pc(bc)] = 1
     entry_expected[bc["entry_index"]] = 1
     tables = F + V + [ops.u64_table(np.arange(K, dtype=np.uint64)), ops.u64_table(entry_trace), ops.u64_table(entry_expected)]
     terms = [(gp[s], [s, 5 + s]) for s in range(5)] + [(gp[5], [0, 10]), (gp[6], [2, 10]), (gp[7], [11, 12])]  # stage_weights * raf_weights: g^0 g^5, g^2 g^4 (:303-311)
@@ -598,6 +603,8 @@ class DeviceExtended:
         lk = d["lookup"]
         self.read_raf = ctx.read_raf(lk["idx"], lk["table"], lk["raf"], lk["n_tables"])
         self.lookup_lists = ffi.lookup_suffix_lists()  # LookupTableKind::suffixes() of the 42 tables
+        self.lookup_present = np.zeros(N_LOOKUP_TABLES, dtype=np.uint8)  # the description's list of present tables as the mask the read-RAF operator takes
+        self.lookup_present[lk["present"]] = 1
         # the packed output-claim facts of the kernel (claim_columns, instruction_read_raf.rs:1163-1173) as one-hot columns with K = 16, the size the per-lane
         # pushforward kernel is built for: tables 0..15, 16..31, 32..41 in three columns (a row is hot in the one its table falls into), and 0 on RAF rows
         # (one K = 64 column went through the generic kernel: 4.7 ms per proof against ~0.3)
@@ -647,8 +654,59 @@ class DeviceExtended:
         """operators the CALLING thread creates from now on live on `ctx` (its stream, scratch and pool); the resident inputs stay where they are and are only read"""
         self._tls.ctx = ctx
 
-    # ---- the operators: each one a jolt_stage_op (csrc/stage_ops.hip) -- created (= the slot's PrepareKernel::prepare), driven through the ProveRounds contract by a
-    # ---- driver of the library (prove_batch over operators, or alone against a test transcript), asked for its output claims, destroyed.  Nothing else happens here.
+    # ---- the operators: each one a jolt_stage_op (csrc/stage_ops.hip).  OPERATORS is the ONE place that says how each is created from the resident inputs and the
+    # ---- description (= the slot's PrepareKernel::prepare), `input_claim` the one place that says where its input claim comes from; everybody who needs an operator
+    # ---- asks `operator`: the per-operator methods below (what DeviceWorkload.step runs: create, drive through the ProveRounds contract with a driver of the library --
+    # ---- prove_batch over operators, or alone against a test transcript --, ask for the output claims, destroy; nothing else happens there),
+    # ---- DeviceWorkload.prove_stage_batches (a whole stage's operators in one batch) and the tests.  What differs from proof to proof is an argument of the entry:
+    # ---- `index` (the key index over the RAM / PC column: ram_index / pc_index, the caller frees it), `address` (the bound bytecode address operator the cycle operator
+    # ---- is prepared from), `r_address` (the point booleanity's address phase bound).
+    OPERATORS = {
+        "spartan_outer": lambda s, ctx: s._spartan_remainder(ctx, s.outer_ints, s.d["outer_wa"], s.d["outer_wb"], s.d["outer_tau"], s.d["outer_kernel"], 2),
+        "spartan_product": lambda s, ctx: s._spartan_remainder(ctx, s.product_ints, s.product_fa, s.product_fb, s.d["product_tau"], s.d["product_kernel"], 1),
+        "ram_read_write": lambda s, ctx: ctx.stage_ram_read_write(*s.ram_cols, s.ram_inc, s.ram_val_init, s.d["ram_tau"], s.d["ram_gamma"]),
+        "ram_raf_evaluation": lambda s, ctx, index: ctx.stage_ram_raf_evaluation(index, s.d["ram_raf"]["tau_low"], s.d["ram_raf"]["lowest_address"]),
+        "ram_output_check": lambda s, ctx, index: ctx.stage_ram_output_check(index, s.ram_cols[2], s.d["ram"]["val_init"], *(s.d["ram_output"][k] for k in ("val_io", "io_lo", "io_len", "point"))),
+        "registers_read_write": lambda s, ctx: ctx.stage_registers_read_write(s.reg_idx, *s.reg_cols, s.reg_inc, s.d["registers_r_cycle"], s.d["registers_gamma"]),
+        "instruction_read_raf": lambda s, ctx: ctx.stage_instruction_read_raf(s.read_raf, s.lookup_claim_columns, s.d["lookup_reduction"], s.d["lookup_gamma"], s.lookup_present, s.d["ra_count"]),
+        "bytecode_read_raf_address": lambda s, ctx, index: ctx.stage_bytecode_read_raf_address(index, *(s.d["bytecode"][k] for k in ("stage_points", "stage_values", "gamma")),
+                                                                                                 first_pc(s.d["bytecode"]), s.d["bytecode"]["entry_index"]),
+        "bytecode_read_raf_cycle": lambda s, ctx, address: ctx.stage_bytecode_read_raf_cycle(address, s.pc_chunks, s.d["bytecode"]["chunk_bits"]),
+        "booleanity_address": lambda s, ctx: ctx.stage_booleanity_address(s.bool_cols, *(s.d["booleanity"][k] for k in ("reference_cycle", "reference_address", "gamma"))),
+        "booleanity_cycle": lambda s, ctx, r_address: ctx.stage_booleanity_cycle(s.bool_cols, r_address, *(s.d["booleanity"][k] for k in ("reference_address", "reference_cycle", "gamma"))),
+        "hamming_weight": lambda s, ctx: ctx.stage_hamming_weight(s.bool_cols, *(s.d["hamming"][k] for k in ("r_cycle", "r_address", "virtualization_points", "gamma"))),
+    }
+    # whose input claim is a previous stage's output claim, held in self.claims; every other operator sums its own (input_claim)
+    HELD_CLAIMS = {"spartan_outer": "outer", "spartan_product": "product", "ram_read_write": "ram", "registers_read_write": "registers", "instruction_read_raf": "lookup"}
+
+    @staticmethod
+    def _spartan_remainder(ctx, cols, fa, fb, tau, kernel, streams):
+        return ctx.stage_spartan_remainder(cols, fa, fb, tau, kernel, streams)
+
+    def operator(self, name, ctx=None, **given):
+        """a fresh operator `name` of OPERATORS on `ctx` (default: the calling thread's context); given: the entry's per-proof arguments.  The caller destroys it."""
+        return self.OPERATORS[name](self, ctx or self.ctx, **given)
+
+    def ram_index(self, ctx=None):
+        """the sorted index of the RAM address column (RamAccessColumns, once per proof): `index` of the RAM RAF evaluation and the RAM output check"""
+        return (ctx or self.ctx).key_index(self.ram_cols[0], 1 << self.d["ram"]["log_k"])
+
+    def pc_index(self, ctx=None):
+        """the sorted index of the PC column (the reference builds its PC rows once per proof): `index` of bytecode read + RAF's address phase"""
+        return (ctx or self.ctx).key_index(self.pc_ints, 1 << self.d["bytecode"]["log_k"])
+
+    def input_claim(self, name, op, claim=None):
+        """the input claim operator `op` = operator(name, ...) is proved under; claim: the caller's, for booleanity's cycle phase (the address phase's intermediate
+        output claim: a wrong one fails the first round check)"""
+        if name in self.HELD_CLAIMS:
+            key = self.HELD_CLAIMS[name]
+            if self.claims[key] is None:  # "lookup" (the prover holds it from the earlier stages): summed from the first phase's tables by the first proof's operator, once
+                self.claims[key] = op.input_claim()
+            return self.claims[key]
+        if name == "booleanity_address":  # zero by construction
+            return np.zeros(4, dtype=np.uint64)
+        return claim if name == "booleanity_cycle" else op.input_claim()
+
     def _alone(self, op, claim, label):
         tr = self.ffi.HostTranscript(label)
         out = op.prove_alone(tr, claim)
@@ -659,31 +717,33 @@ class DeviceExtended:
         out = self.ctx.prove_batch_ops([op], [claim], [self.one], [0], rounds, degree, label=label)
         return dict(polys=out["polys"], challenges=out["challenges"], final_claim=out["final_claim"])
 
-    def spartan(self, cols, iwa, iwb, fa, fb, tau, kernel, claim, streams, label):
-        ctx, ffi = self.ctx, self.ffi
-        sums = ctx.stage_spartan_uniskip_sums(cols, tau, iwa, iwb, streams)
-        tr = ffi.HostTranscript(label)
+    def spartan_uniskip(self, cols, iwa, iwb, tau, streams, label):
+        """the uni-skip first round: -> (the sums off the integer witness columns, the challenge a transcript `label` draws after absorbing them)"""
+        sums = self.ctx.stage_spartan_uniskip_sums(cols, tau, iwa, iwb, streams)
+        tr = self.ffi.HostTranscript(label)
         tr.append(sums)
         r0 = tr.challenge()  # the uni-skip challenge (the Lagrange weights of the remainder are a function of it; fixed weights here)
         tr.close()
-        op = ctx.stage_spartan_remainder(cols, fa, fb, tau, kernel, streams)
+        return sums, r0
+
+    def spartan(self, cols, iwa, iwb, fa, fb, tau, kernel, claim, streams, label):
+        sums, r0 = self.spartan_uniskip(cols, iwa, iwb, tau, streams, label)
+        op = self._spartan_remainder(self.ctx, cols, fa, fb, tau, kernel, streams)  # (over the resident columns: OPERATORS["spartan_outer"] / ["spartan_product"])
         out = self._batch(op, claim, len(tau), 3, label + 1)
         values = op.output_claims()
         op.destroy()
         return dict(sums=sums, r0=r0, polys=out["polys"], challenges=out["challenges"], final_claim=out["final_claim"], values=values)
 
     def ram_read_write(self, label):
-        d = self.d
-        op = self.ctx.stage_ram_read_write(self.ram_cols[0], self.ram_cols[1], self.ram_cols[2], self.ram_inc, self.ram_val_init, d["ram_tau"], d["ram_gamma"])
-        out = self._alone(op, self.claims["ram"], label)
+        op = self.operator("ram_read_write")
+        out = self._alone(op, self.input_claim("ram_read_write", op), label)
         out["final_values"] = op.output_claims()
         op.destroy()
         return out
 
     def registers_read_write(self, label):
-        d = self.d
-        op = self.ctx.stage_registers_read_write(self.reg_idx, *self.reg_cols, self.reg_inc, d["registers_r_cycle"], d["registers_gamma"])
-        out = self._alone(op, self.claims["registers"], label)
+        op = self.operator("registers_read_write")
+        out = self._alone(op, self.input_claim("registers_read_write", op), label)
         claims = op.output_claims()
         op.destroy()
         out["final_values"], out["operand_claims"] = claims[:5], claims[5:7]  # RegistersReadWriteOutputClaims::{rs1_ra, rs2_ra} last
@@ -691,8 +751,8 @@ class DeviceExtended:
 
     def booleanity_address(self, label):
         bo = self.d["booleanity"]
-        op = self.ctx.stage_booleanity_address(self.bool_cols, bo["reference_cycle"], bo["reference_address"], bo["gamma"])
-        out = self._alone(op, np.zeros(4, dtype=np.uint64), label)
+        op = self.operator("booleanity_address")
+        out = self._alone(op, self.input_claim("booleanity_address", op), label)
         out["intermediate"] = op.output_claims()[0]
         out["masses"] = op.kept("masses").reshape(bo["cols"].shape[0], 1 << bo["log_k"], 4)
         op.destroy()
@@ -701,9 +761,8 @@ class DeviceExtended:
     def booleanity_cycle(self, label, r_address, claim):
         """stage 6b after 6a: `r_address` = the address phase's bound point (its challenges, last first), `claim` = that phase's intermediate output claim (a wrong one
         fails the batch's first round check)"""
-        bo = self.d["booleanity"]
-        op = self.ctx.stage_booleanity_cycle(self.bool_cols, r_address, bo["reference_address"], bo["reference_cycle"], bo["gamma"])
-        out = self._batch(op, claim, self.n_vars, 3, label)
+        op = self.operator("booleanity_cycle", r_address=r_address)
+        out = self._batch(op, self.input_claim("booleanity_cycle", op, claim), self.n_vars, 3, label)
         out["claim"] = claim
         out["ra_claims"] = op.output_claims()
         out["eq_scalar"] = op.kept("eq_scalar")[0]
@@ -711,9 +770,9 @@ class DeviceExtended:
         return out
 
     def hamming_weight(self, label):
-        bo, hw = self.d["booleanity"], self.d["hamming"]
-        op = self.ctx.stage_hamming_weight(self.bool_cols, hw["r_cycle"], hw["r_address"], hw["virtualization_points"], hw["gamma"])
-        claim = op.input_claim()
+        bo = self.d["booleanity"]
+        op = self.operator("hamming_weight")
+        claim = self.input_claim("hamming_weight", op)
         out = self._alone(op, claim, label)
         out["claim"] = claim
         out["g_claims"] = op.output_claims()
@@ -724,19 +783,16 @@ class DeviceExtended:
     def instruction_read_raf(self, label):
         """OptimizedInstructionReadRafKernel as ONE operator of 128 + log T rounds; the address rounds run against the test transcript `label`, the cycle rounds as a
         one-member batch under `label + 1` (two windows of the operator), as the oracle twin does"""
-        ctx, d = self.ctx, self.d
+        d = self.d
         lk = d["lookup"]
-        present = np.zeros(N_LOOKUP_TABLES, dtype=np.uint8)
-        present[lk["present"]] = 1
-        op = ctx.stage_instruction_read_raf(self.read_raf, self.lookup_claim_columns, d["lookup_reduction"], d["lookup_gamma"], present, d["ra_count"])
-        if self.claims["lookup"] is None:  # the relation's input claim (the prover holds it from the earlier stages): summed from the first phase's tables, once
-            self.claims["lookup"] = op.input_claim()
+        op = self.operator("instruction_read_raf")
+        claim = self.input_claim("instruction_read_raf", op)
         address, cycle = op.window(0, ADDRESS_BITS), op.window(ADDRESS_BITS, self.n_vars)
-        adr = self._alone(address, self.claims["lookup"], label)
+        adr = self._alone(address, claim, label)
         n_f = 1 + d["ra_count"]
         out = self._batch(cycle, adr["final_claim"], self.n_vars, n_f + 1, label + 1)  # its round check holds only if the address rounds were right
         claims = op.output_claims()
-        n_present = int(present.sum())
+        n_present = int(self.lookup_present.sum())
         raf_scans = op.kept("scan_raf").reshape(PHASES, 6, CHUNK, 4)
         suf_scans = op.kept("scan_suffix").reshape(PHASES, -1, CHUNK, 4)
         res = dict(lookup_table_flags=claims[:n_present], instruction_raf_flag=claims[n_present], instruction_ra=claims[n_present + 1:],
@@ -749,44 +805,37 @@ class DeviceExtended:
         return res
 
     def bytecode_read_raf(self, label):
-        """stage 6a / 6b: bytecode read + RAF over a sorted index of the PC column (per-proof work: the reference builds its PC rows once per proof)"""
-        ctx, d, n_vars = self.ctx, self.d, self.n_vars
-        bc = d["bytecode"]
-        pc_index = ctx.key_index(self.pc_ints, 1 << bc["log_k"])
-        first_pc = int(bc["first_pc"]) if "first_pc" in bc else int(bc["push_pc"][0])
-        a_op = ctx.stage_bytecode_read_raf_address(pc_index, bc["stage_points"], bc["stage_values"], bc["gamma"], first_pc, bc["entry_index"])
-        claim_a = a_op.input_claim()
+        """stage 6a / 6b: bytecode read + RAF, the cycle phase prepared from the bound address operator"""
+        bc = self.d["bytecode"]
+        index = self.pc_index()
+        a_op = self.operator("bytecode_read_raf_address", index=index)
+        claim_a = self.input_claim("bytecode_read_raf_address", a_op)
         adr = self._batch(a_op, claim_a, bc["log_k"], 2, label)
         fin = a_op.output_claims()  # the 13 bound tables, then the intermediate claim
-        c_op = ctx.stage_bytecode_read_raf_cycle(a_op, self.pc_chunks, bc["chunk_bits"])
-        claim_c = c_op.input_claim()
-        cyc = self._batch(c_op, claim_c, n_vars, c_op.degree, label + 1)
+        c_op = self.operator("bytecode_read_raf_cycle", address=a_op)
+        claim_c = self.input_claim("bytecode_read_raf_cycle", c_op)
+        cyc = self._batch(c_op, claim_c, self.n_vars, c_op.degree, label + 1)
         bytecode = dict(address=adr, claim_address=claim_a, intermediate=fin[13], val_stages=fin[5:10], r_address=adr["challenges"][::-1], cycle=cyc, claim_cycle=claim_c,
                         ra_claims=c_op.output_claims())
         c_op.destroy()
         a_op.destroy()
-        pc_index.free()
+        index.free()
         return bytecode
 
     def ram_address_domain(self, label):
-        """stage 2: RAM RAF evaluation and the RAM output check over a sorted index of the address column (RamAccessColumns, once per proof)"""
-        ctx, d = self.ctx, self.d
-        ram, raf, io = d["ram"], d["ram_raf"], d["ram_output"]
-        ram_index = ctx.key_index(self.ram_cols[0], 1 << ram["log_k"])
-        op = ctx.stage_ram_raf_evaluation(ram_index, raf["tau_low"], raf["lowest_address"])
-        claim = op.input_claim()
-        raf_out = self._batch(op, claim, ram["log_k"], 2, label + 10)
-        raf_out["claim"] = claim
-        raf_out["ra_claim"] = op.output_claims()[0]
-        op.destroy()
-        op = ctx.stage_ram_output_check(ram_index, self.ram_cols[2], ram["val_init"], io["val_io"], io["io_lo"], io["io_len"], io["point"])
-        claim = op.input_claim()
-        oc = self._batch(op, claim, ram["log_k"], 3, label + 20)
-        oc["claim"] = claim
-        oc["val_final_claim"] = op.output_claims()[0]
-        op.destroy()
-        ram_index.free()
-        return {"ram_raf_evaluation": raf_out, "ram_output_check": oc}
+        """stage 2: RAM RAF evaluation (its output claim: the bound ra_folded) and the RAM output check (the bound val_final), one after the other over one index"""
+        log_k = self.d["ram"]["log_k"]
+        index = self.ram_index()
+        out = {}
+        for name, degree, label_k, key in (("ram_raf_evaluation", 2, label + 10, "ra_claim"), ("ram_output_check", 3, label + 20, "val_final_claim")):
+            op = self.operator(name, index=index)
+            claim = self.input_claim(name, op)
+            out[name] = self._batch(op, claim, log_k, degree, label_k)
+            out[name]["claim"] = claim
+            out[name][key] = op.output_claims()[0]
+            op.destroy()
+        index.free()
+        return out
 
     def address_domain(self, label):
         """the joint-domain relations whose rounds run over K-sized tables: bytecode read+RAF (6a, 6b), RAM RAF evaluation, RAM output check"""

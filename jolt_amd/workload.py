@@ -593,30 +593,36 @@ class DeviceWorkload:
         return self._stage_batch_coeffs[name]
 
     def prove_stage_batches(self, label=0, stages=(2, 3, 4, 5, 6, 7), grouped=True, challenge_mode=0):
-        """Every protocol stage as ONE batched sumcheck on the MAIN context (needs extended=True): the stage's operators are created here over the resident inputs of
-        `self.ext`, the stage's catalogue members are wrapped (Context.stage_member: borrowed), and jolt_host_prove_batch_ops_grouped runs the batch under label +
+        """Every protocol stage as ONE batched sumcheck on the MAIN context (needs extended=True): the stage's operators come from the catalogue of `self.ext`
+        (DeviceExtended.operator / input_claim, over its resident inputs), the stage's catalogue members are wrapped (Context.stage_member: borrowed), and jolt_host_prove_batch_ops_grouped runs the batch under label +
         STAGE_BATCH_LABELS[stage] -- per round ONE round-group launch set over the wrapped members, the operators beside it.  stages: a subset of (2, 3, 4, 5, 6, 7); 6 is
         6a followed by 6b (6b starts from what 6a leaves).  grouped=False: the same batches under SequentialRounds (the same bytes); challenge_mode: as Context.prove_batch_ops.
         -> {stage: what prove_batch_ops returns + names, rounds, offsets, input_claims, coefficients, max_num_vars, max_degree, output_claims (per operator)}.
         The members are rewound afterwards: `prove` / `step` see them as `prepare` left them."""
         if self.ext is None:
             raise ValueError("prove_stage_batches needs the stage operators' resident inputs: DeviceWorkload(..., extended=True)")
-        from .stages import N_LOOKUP_TABLES
         if not self.prepared:
             self.prepare()
-        ctx, ext, d, n_vars = self.ctx, self.ext, self.ext.d, self.n_vars
+        ctx, ext = self.ctx, self.ext
         by_name = {ms.name: i for i, ms in enumerate(self.members_spec)}
-        ram, reg, bc, bo, hw = d["ram"], d["registers"], d["bytecode"], d["booleanity"], d["hamming"]
         outs = {}
 
-        def run(key, named, claims):
-            """named: [(name, operator)] in the reference's order; claims: {name: input claim} for the operators (a catalogue member's is self.claims[i])"""
+        def release(named):
+            for _, op in reversed(named):  # (the bytecode cycle operator before the address operator it was prepared from)
+                op.destroy()
+
+        def run(key, claim=None, **given):
+            """the batch of STAGE_BATCHES[key], the reference's order: a catalogue member wrapped, anything else an operator of ext.OPERATORS created with the arguments given[name]
+            and proved under ext.input_claim (claim: booleanity's cycle phase's).  -> [(name, operator)], for the caller to read and release"""
+            named = []
             try:
+                for name in self.STAGE_BATCHES[key]:
+                    named.append((name, ctx.stage_member(self.members[by_name[name]]) if name in by_name else ext.operator(name, ctx, **given.get(name, {}))))
                 ops = [op for _, op in named]
                 rounds = [op.rounds for op in ops]
                 total, degree = max(rounds), max(op.degree for op in ops)
                 offsets = [total - r for r in rounds]  # instance_point_offset (relations.rs:202-213; stage2/mod.rs:25-49): every window ends with the batch
-                input_claims = [claims[name] if name in claims else self.claims[by_name[name]] for name, _ in named]
+                input_claims = [self.claims[by_name[name]] if name in by_name else ext.input_claim(name, op, claim) for name, op in named]
                 coeffs = [self.stage_batch_coefficient(name) for name, _ in named]
                 prove = ctx.prove_batch_ops_grouped if grouped else ctx.prove_batch_ops
                 out = prove(ops, input_claims, coeffs, offsets, total, degree, label=label + self.STAGE_BATCH_LABELS[key], challenge_mode=challenge_mode)
@@ -624,76 +630,35 @@ class DeviceWorkload:
                            max_num_vars=total, max_degree=degree, output_claims=[op.output_claims() for op in ops])
                 outs[key] = out
             except Exception:
-                for _, op in named:
-                    op.destroy()
+                release(named)
                 raise
-
-        def wrapped(name):
-            return name, ctx.stage_member(self.members[by_name[name]])
-
-        def release(named):
-            for _, op in reversed(named):  # (the bytecode cycle operator before the address operator it was prepared from)
-                op.destroy()
+            return named
 
         try:
             for stage in stages:
-                if stage == 2:
-                    index = ctx.key_index(ext.ram_cols[0], 1 << ram["log_k"])
+                if stage == 2:  # one index of the RAM address column for the stage
+                    index = ext.ram_index(ctx)
                     try:
-                        raf, io = d["ram_raf"], d["ram_output"]
-                        named = [("ram_read_write", ctx.stage_ram_read_write(ext.ram_cols[0], ext.ram_cols[1], ext.ram_cols[2], ext.ram_inc, ext.ram_val_init, d["ram_tau"], d["ram_gamma"])),
-                                 ("spartan_product", ctx.stage_spartan_remainder(ext.product_ints, ext.product_fa, ext.product_fb, d["product_tau"], d["product_kernel"], 1)),
-                                 wrapped("instruction_claim_reduction"),
-                                 ("ram_raf_evaluation", ctx.stage_ram_raf_evaluation(index, raf["tau_low"], raf["lowest_address"])),
-                                 ("ram_output_check", ctx.stage_ram_output_check(index, ext.ram_cols[2], ram["val_init"], io["val_io"], io["io_lo"], io["io_len"], io["point"]))]
-                        run(2, named, {"ram_read_write": ext.claims["ram"], "spartan_product": ext.claims["product"], "ram_raf_evaluation": named[3][1].input_claim(),
-                                       "ram_output_check": named[4][1].input_claim()})
-                        release(named)
+                        release(run(2, ram_raf_evaluation=dict(index=index), ram_output_check=dict(index=index)))
                     finally:
                         index.free()
-                elif stage == 3:
-                    named = [wrapped(name) for name in self.STAGE_BATCHES[3]]
-                    run(3, named, {})
-                    release(named)
-                elif stage == 4:
-                    named = [("registers_read_write", ctx.stage_registers_read_write(ext.reg_idx, *ext.reg_cols, ext.reg_inc, d["registers_r_cycle"], d["registers_gamma"])),
-                             wrapped("ram_val_check")]
-                    run(4, named, {"registers_read_write": ext.claims["registers"]})
-                    release(named)
-                elif stage == 5:
-                    present = np.zeros(N_LOOKUP_TABLES, dtype=np.uint8)
-                    present[d["lookup"]["present"]] = 1
-                    op = ctx.stage_instruction_read_raf(ext.read_raf, ext.lookup_claim_columns, d["lookup_reduction"], d["lookup_gamma"], present, d["ra_count"])
-                    if ext.claims["lookup"] is None:
-                        ext.claims["lookup"] = op.input_claim()
-                    named = [("instruction_read_raf", op), wrapped("ram_ra_claim_reduction"), wrapped("registers_val_evaluation")]
-                    run(5, named, {"instruction_read_raf": ext.claims["lookup"]})
-                    release(named)
-                elif stage == 6:
-                    pc_index = ctx.key_index(ext.pc_ints, 1 << bc["log_k"])
+                elif stage in (3, 4, 5, 7):
+                    release(run(stage))
+                elif stage == 6:  # 6b starts from what 6a leaves: the bound bytecode address operator, booleanity's window of the challenges and its intermediate claim
+                    index = ext.pc_index(ctx)
                     try:
-                        first_pc = int(bc["first_pc"]) if "first_pc" in bc else int(bc["push_pc"][0])
-                        a_named = [("bytecode_read_raf_address", ctx.stage_bytecode_read_raf_address(pc_index, bc["stage_points"], bc["stage_values"], bc["gamma"], first_pc, bc["entry_index"])),
-                                   ("booleanity_address", ctx.stage_booleanity_address(ext.bool_cols, bo["reference_cycle"], bo["reference_address"], bo["gamma"]))]
-                        run("6a", a_named, {"bytecode_read_raf_address": a_named[0][1].input_claim(), "booleanity_address": np.zeros(4, dtype=np.uint64)})
-                        a = outs["6a"]
-                        r_address = a["challenges"][a["offsets"][1]:][::-1]  # the booleanity window's challenges, most significant address bit first
-                        intermediate = a["output_claims"][1][0]
+                        a_named = run("6a", bytecode_read_raf_address=dict(index=index))
                         try:
-                            b_named = [("bytecode_read_raf_cycle", ctx.stage_bytecode_read_raf_cycle(a_named[0][1], ext.pc_chunks, bc["chunk_bits"])),
-                                       ("booleanity_cycle", ctx.stage_booleanity_cycle(ext.bool_cols, r_address, bo["reference_address"], bo["reference_cycle"], bo["gamma"]))]
-                            b_named += [wrapped(name) for name in self.STAGE_BATCHES["6b"][2:]]
-                            run("6b", b_named, {"bytecode_read_raf_cycle": b_named[0][1].input_claim(), "booleanity_cycle": intermediate})
-                            outs["6b"]["eq_scalar"] = b_named[1][1].kept("eq_scalar")[0]
+                            a, k = outs["6a"], self.STAGE_BATCHES["6a"].index("booleanity_address")
+                            r_address = a["challenges"][a["offsets"][k]:][::-1]  # most significant address bit first
+                            b_named = run("6b", claim=a["output_claims"][k][0], bytecode_read_raf_cycle=dict(address=dict(a_named)["bytecode_read_raf_address"]),
+                                          booleanity_cycle=dict(r_address=r_address))
+                            outs["6b"]["eq_scalar"] = dict(b_named)["booleanity_cycle"].kept("eq_scalar")[0]
                             release(b_named)
                         finally:
                             release(a_named)
                     finally:
-                        pc_index.free()
-                elif stage == 7:
-                    named = [("hamming_weight", ctx.stage_hamming_weight(ext.bool_cols, hw["r_cycle"], hw["r_address"], hw["virtualization_points"], hw["gamma"]))]
-                    run(7, named, {"hamming_weight": named[0][1].input_claim()})
-                    release(named)
+                        index.free()
                 else:
                     raise ValueError(f"no stage batch {stage!r}")
         finally:

@@ -6,21 +6,10 @@ import pytest
 
 from jolt_amd import ffi
 from jolt_amd.stages import DeviceExtended
+from util import same
 from workload_oracle import OracleExtended
 
 pytestmark = pytest.mark.gpu
-
-
-def same(a, b, path=""):
-    if isinstance(a, dict):
-        for k in a:
-            same(a[k], b[k], f"{path}.{k}")
-    elif isinstance(a, (list, tuple)):
-        assert len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            same(x, y, f"{path}[{i}]")
-    else:
-        assert np.array_equal(np.asarray(a), np.asarray(b)), path
 
 
 def run(n_vars, seed, **kw):
@@ -102,15 +91,14 @@ def test_a_stage_batch_over_operators_is_the_batch_over_their_members():
     dev = DeviceExtended(ctx, n_vars, seed=31, n_tables=5, log_k=6, log_kb=5)
     d = dev.d
     ram, raf, io, bo = d["ram"], d["ram_raf"], d["ram_output"], d["booleanity"]
-    index = ctx.key_index(dev.ram_cols[0], 1 << ram["log_k"])
+    index = dev.ram_index()
+    given = {"ram_raf_evaluation": dict(index=index), "ram_output_check": dict(index=index), "booleanity_address": {}}
     coeffs = rand_fr(3, 77)
 
     def operators():
-        return [ctx.stage_ram_raf_evaluation(index, raf["tau_low"], raf["lowest_address"]),
-                ctx.stage_ram_output_check(index, dev.ram_cols[2], ram["val_init"], io["val_io"], io["io_lo"], io["io_len"], io["point"]),
-                ctx.stage_booleanity_address(dev.bool_cols, bo["reference_cycle"], bo["reference_address"], bo["gamma"])]
+        return [dev.operator(name, **kw) for name, kw in given.items()]
     ops = operators()
-    claims = [ops[0].input_claim(), ops[1].input_claim(), np.zeros(4, dtype=np.uint64)]
+    claims = [dev.input_claim(name, op) for name, op in zip(given, ops)]
     rounds, offsets = ram["log_k"], [0, 0, ram["log_k"] - bo["log_k"]]
     got = ctx.prove_batch_ops(ops, claims, coeffs, offsets, rounds, 3, label=5)
     # the same two dense members by hand (stages.ram_raf_evaluation / ram_output_check, the round-5 drivers), batched by jolt_host_prove_batch; booleanity's operator alone

@@ -28,6 +28,7 @@ from jolt_amd import workload as W
 from jolt_amd.stages import ADDRESS_BITS, N_LOOKUP_TABLES
 from jolt_amd.workload import DeviceWorkload
 from stage_batch_replay import ReplayTranscript, check_batch, replay_member
+from util import same
 from workload_oracle import OracleExtended, OracleWorkload
 
 pytestmark = pytest.mark.gpu
@@ -39,20 +40,6 @@ ORDER = (2, 3, 4, 5, "6a", "6b", 7)
 
 class EveryRoundDirect(OracleExtended):  # all 128 read-RAF address rounds from the definition up to T = 2^16 (tests/test_gpu_extended.py does the same at that size)
     DIRECT_ADDRESS_ROUNDS_MAX_LOG_T = 16
-
-
-def same(a, b, path=""):
-    if isinstance(a, dict):
-        for k in a:
-            same(a[k], b[k], f"{path}.{k}")
-    elif isinstance(a, (list, tuple)) or isinstance(b, (list, tuple)):
-        assert len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            same(x, y, f"{path}[{i}]")
-    elif isinstance(a, (str, int)):
-        assert a == b, path
-    else:
-        assert np.array_equal(np.asarray(a), np.asarray(b)), path
 
 
 class Bed:

@@ -8,29 +8,15 @@ import numpy as np
 import pytest
 
 from jolt_amd import ffi
-from jolt_amd.stages import ADDRESS_BITS, CHUNK, N_LOOKUP_TABLES, PHASES, DeviceExtended, build_extended
+from jolt_amd.stages import ADDRESS_BITS, CHUNK, PHASES, DeviceExtended, build_extended
 from stage_batch_replay import ReplayTranscript, check_batch
-from util import rand_fr
+from util import rand_fr, same
 from workload_oracle import OracleExtended
 
 pytestmark = pytest.mark.gpu
 
 SEED = 733
 SIZES = {6: dict(n_tables=6, log_k=4), 10: dict(n_tables=5, log_k=6, log_kb=5), 16: dict(log_k=14)}  # 2^16 x 2^14: many columns per merged group, many workgroups per scan
-ZERO = np.zeros(4, dtype=np.uint64)
-
-
-def same(a, b, path=""):
-    """`a` (the device's) against `b` (the twin's): every key the device returns, arrays bit for bit"""
-    if isinstance(a, dict):
-        for k in a:
-            same(a[k], b[k], f"{path}.{k}")
-    elif isinstance(a, (list, tuple)) or isinstance(b, (list, tuple)):
-        assert len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            same(x, y, f"{path}[{i}]")
-    else:
-        assert np.array_equal(np.asarray(a), np.asarray(b)), path
 
 
 class Bed:
@@ -76,22 +62,19 @@ def check(got, twins, coeffs, offsets, rounds, max_num_vars, max_degree, label, 
 @pytest.mark.parametrize("n_vars,engine,challenge_mode", [(6, 0, 0), (10, 0, 0), (16, 0, 0), (10, ffi.TRANSCRIPT_BLAKE2B, 0), (10, 0, 1)])
 def test_stage_2_batch(n_vars, engine, challenge_mode):
     bed = Bed(n_vars)
-    ctx, dev, d = bed.ctx, bed.dev, bed.d
-    ram, raf, io = d["ram"], d["ram_raf"], d["ram_output"]
-    log_t, log_k = n_vars, ram["log_k"]
+    dev, d = bed.dev, bed.d
+    log_t, log_k = n_vars, d["ram"]["log_k"]
     total, label = log_t + log_k, engine | 81
     rounds = [total, log_t, log_k, log_k]
     offsets = [total - r for r in rounds]
     coeffs = list(rand_fr(4, 5 + n_vars))
 
     def make():
-        index = ctx.key_index(dev.ram_cols[0], 1 << log_k)
-        ops = [ctx.stage_ram_read_write(dev.ram_cols[0], dev.ram_cols[1], dev.ram_cols[2], dev.ram_inc, dev.ram_val_init, d["ram_tau"], d["ram_gamma"]),
-               ctx.stage_spartan_remainder(dev.product_ints, dev.product_fa, dev.product_fb, d["product_tau"], d["product_kernel"], 1),
-               ctx.stage_ram_raf_evaluation(index, raf["tau_low"], raf["lowest_address"]),
-               ctx.stage_ram_output_check(index, dev.ram_cols[2], ram["val_init"], io["val_io"], io["io_lo"], io["io_len"], io["point"])]
+        index = dev.ram_index()
+        given = {"ram_read_write": {}, "spartan_product": {}, "ram_raf_evaluation": dict(index=index), "ram_output_check": dict(index=index)}
+        ops = [dev.operator(name, **kw) for name, kw in given.items()]
         assert [op.rounds for op in ops] == rounds
-        claims = [dev.claims["ram"], dev.claims["product"], ops[2].input_claim(), ops[3].input_claim()]
+        claims = [dev.input_claim(name, op) for name, op in zip(given, ops)]
 
         def release():
             for op in ops:
@@ -126,22 +109,22 @@ def test_stage_2_batch(n_vars, engine, challenge_mode):
 @pytest.mark.parametrize("n_vars", [6, 10, 16])
 def test_stage_4_and_7_batch(n_vars):
     bed = Bed(n_vars)
-    ctx, dev, d = bed.ctx, bed.dev, bed.d
-    bo, hw, reg = d["booleanity"], d["hamming"], d["registers"]
+    dev, d = bed.dev, bed.d
+    bo, reg = d["booleanity"], d["registers"]
     total, label = n_vars + reg["log_k"], 82
     rounds = [total, bo["log_k"]]
     offsets = [0, total - bo["log_k"]]
     coeffs = list(rand_fr(2, 15 + n_vars))
 
     def make():
-        ops = [ctx.stage_registers_read_write(dev.reg_idx, *dev.reg_cols, dev.reg_inc, d["registers_r_cycle"], d["registers_gamma"]),
-               ctx.stage_hamming_weight(dev.bool_cols, hw["r_cycle"], hw["r_address"], hw["virtualization_points"], hw["gamma"])]
+        names = ["registers_read_write", "hamming_weight"]
+        ops = [dev.operator(name) for name in names]
         assert [op.rounds for op in ops] == rounds
 
         def release():
             for op in ops:
                 op.destroy()
-        return ops, [dev.claims["registers"], ops[1].input_claim()], lambda: dict(registers=ops[0].output_claims(), g_claims=ops[1].output_claims(), masses=ops[1].kept("masses")), release
+        return ops, [dev.input_claim(name, op) for name, op in zip(names, ops)], lambda: dict(registers=ops[0].output_claims(), g_claims=ops[1].output_claims(), masses=ops[1].kept("masses")), release
 
     got, claims, outputs = bed.twice(make, coeffs, offsets, total, 3, label)
     ch = got["challenges"]
@@ -167,20 +150,18 @@ def test_stage_4_and_7_batch(n_vars):
 def test_stage_5_batch(n_vars):
     assert n_vars <= OracleExtended.DIRECT_ADDRESS_ROUNDS_MAX_LOG_T
     bed = Bed(n_vars)
-    ctx, dev, d = bed.ctx, bed.dev, bed.d
+    dev, d = bed.dev, bed.d
     lk = d["lookup"]
     total, label = ADDRESS_BITS + n_vars, 83
     rounds = [total, n_vars + 1]
     offsets = [0, total - (n_vars + 1)]
     max_degree = d["ra_count"] + 2
     coeffs = list(rand_fr(2, 25 + n_vars))
-    present = np.zeros(N_LOOKUP_TABLES, dtype=np.uint8)
-    present[lk["present"]] = 1
-    n_present = int(present.sum())
+    n_present = int(dev.lookup_present.sum())
 
     def make():
-        ops = [ctx.stage_instruction_read_raf(dev.read_raf, dev.lookup_claim_columns, d["lookup_reduction"], d["lookup_gamma"], present, d["ra_count"]),
-               ctx.stage_spartan_remainder(dev.outer_ints, d["outer_wa"], d["outer_wb"], d["outer_tau"], d["outer_kernel"], 2)]
+        names = ["instruction_read_raf", "spartan_outer"]
+        ops = [dev.operator(name) for name in names]
         assert [op.rounds for op in ops] == rounds and ops[0].degree == max_degree
 
         def collect():
@@ -194,7 +175,7 @@ def test_stage_5_batch(n_vars):
         def release():
             for op in ops:
                 op.destroy()
-        return ops, [ops[0].input_claim(), dev.claims["outer"]], collect, release
+        return ops, [dev.input_claim(name, op) for name, op in zip(names, ops)], collect, release
 
     got, claims, outputs = bed.twice(make, coeffs, offsets, total, max_degree, label)
     ch = got["challenges"]
@@ -230,20 +211,18 @@ def stage_6(n_vars, with_cycle):
 
     def chain():
         """6a, then (with_cycle) 6b over what 6a left"""
-        pc_index = ctx.key_index(dev.pc_ints, 1 << log_kb)
-        a_ops = [ctx.stage_bytecode_read_raf_address(pc_index, bc["stage_points"], bc["stage_values"], bc["gamma"], int(bc["push_pc"][0]), bc["entry_index"]),
-                 ctx.stage_booleanity_address(dev.bool_cols, bo["reference_cycle"], bo["reference_address"], bo["gamma"])]
+        pc_index = dev.pc_index()
+        a_ops = [dev.operator("bytecode_read_raf_address", index=pc_index), dev.operator("booleanity_address")]
         assert [op.rounds for op in a_ops] == rounds_a
-        claims_a = [a_ops[0].input_claim(), ZERO]
+        claims_a = [dev.input_claim("bytecode_read_raf_address", a_ops[0]), dev.input_claim("booleanity_address", a_ops[1])]
         got_a = ctx.prove_batch_ops(a_ops, claims_a, coeffs_a, offsets_a, log_kb, 3, label=label_a)
         fin = a_ops[0].output_claims()
         out = dict(a=got_a, claims_a=claims_a, fin=fin, intermediate=a_ops[1].output_claims()[0], masses=a_ops[1].kept("masses").reshape(n_cols, 1 << log_kc, 4))
         if with_cycle:
             r_address = got_a["challenges"][offsets_a[1]:][::-1]
-            b_ops = [ctx.stage_bytecode_read_raf_cycle(a_ops[0], dev.pc_chunks, bc["chunk_bits"]),
-                     ctx.stage_booleanity_cycle(dev.bool_cols, r_address, bo["reference_address"], bo["reference_cycle"], bo["gamma"])]
+            b_ops = [dev.operator("bytecode_read_raf_cycle", address=a_ops[0]), dev.operator("booleanity_cycle", r_address=r_address)]
             assert [op.rounds for op in b_ops] == rounds_b and max(op.degree for op in b_ops) == degree_b
-            claims_b = [b_ops[0].input_claim(), out["intermediate"]]
+            claims_b = [dev.input_claim("bytecode_read_raf_cycle", b_ops[0]), dev.input_claim("booleanity_cycle", b_ops[1], out["intermediate"])]
             got_b = ctx.prove_batch_ops(b_ops, claims_b, coeffs_b, offsets_b, n_vars, degree_b, label=label_b)
             out.update(b=got_b, claims_b=claims_b, ra_claims=b_ops[0].output_claims(), bool_ra_claims=b_ops[1].output_claims(), eq_scalar=b_ops[1].kept("eq_scalar")[0])
             for op in b_ops:
@@ -299,8 +278,7 @@ def test_the_alone_driver_checks_what_the_operator_does_not():
     its message and never reads the claim, so under a claim that is not its sum (zero) nothing in the operator objects: the DRIVER must report JOLT_ERR_ROUND_CHECK.  A
     fresh operator under the right claim then proves what the twin proves."""
     bed = Bed(6)
-    bo = bed.d["booleanity"]
-    op = bed.ctx.stage_booleanity_address(bed.dev.bool_cols, bo["reference_cycle"], bo["reference_address"], bo["gamma"])
+    op = bed.dev.operator("booleanity_address")
     tr = ffi.HostTranscript(450)
     with pytest.raises(ffi.JoltError) as e:
         op.prove_alone(tr, ffi.host_fr_from_u64(1))

@@ -9,6 +9,7 @@ import pytest
 import oracle_lib as O
 from jolt_amd import ffi
 from stage_batch_replay import ReplayTranscript, check_batch, replay_member
+import util
 from util import rand_fr
 from workload_oracle import OracleExtended
 
@@ -156,16 +157,9 @@ def test_a_replay_transcript_runs_out():
 
 
 def same(a, b, path=""):
-    if isinstance(a, dict):
-        assert set(a) == set(b), path
-        for k in a:
-            same(a[k], b[k], f"{path}.{k}")
-    elif isinstance(a, (list, tuple)) or isinstance(b, (list, tuple)):  # (a one-member batch returns its messages as one array, a replay as one array per round)
-        assert len(a) == len(b), path
-        for i, (x, y) in enumerate(zip(a, b)):
-            same(x, y, f"{path}[{i}]")
-    else:
-        assert np.array_equal(np.asarray(a), np.asarray(b)), path
+    """util.same both ways round: the same keys on both sides, at every level"""
+    util.same(a, b, path)
+    util.same(b, a, path)
 
 
 def test_every_twin_replayed_under_its_own_challenges_is_the_twin():

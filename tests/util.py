@@ -23,6 +23,22 @@ def rand_challenge(seed, shifted=True):
     return c
 
 
+def same(a, b, path=""):
+    """`a` (what the code under test returns) against `b` (what it must be): every key `a` has, sequences element by element, strings and plain integers by value,
+    arrays bit for bit.  Keys only `b` has are not looked at: call it both ways round where the two must hold the same keys."""
+    if isinstance(a, dict):
+        for k in a:
+            same(a[k], b[k], f"{path}.{k}")
+    elif isinstance(a, (list, tuple)) or isinstance(b, (list, tuple)):  # (a one-member batch returns its messages as one array, a replay as one array per round)
+        assert len(a) == len(b), path
+        for i, (x, y) in enumerate(zip(a, b)):
+            same(x, y, f"{path}[{i}]")
+    elif isinstance(a, (str, int)):
+        assert a == b, path
+    else:
+        assert np.array_equal(np.asarray(a), np.asarray(b)), path
+
+
 def small_fr(vals, oracle):
     return oracle.fr_from_u64(np.asarray(vals, dtype=np.uint64))
 

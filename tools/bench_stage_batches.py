@@ -41,11 +41,7 @@ def main():
 
     def batches():
         out = ext.prove_stage(1, label)
-        sums = ctx.stage_spartan_uniskip_sums(ext.product_ints, d["product_tau"], ext.product_ia, ext.product_ib, 1)
-        tr = ffi.HostTranscript(label + 200)
-        tr.append(sums)
-        out["spartan_product_r0"] = tr.challenge()
-        tr.close()
+        out["spartan_product_r0"] = ext.spartan_uniskip(ext.product_ints, ext.product_ia, ext.product_ib, d["product_tau"], 1, label + 200)[1]
         out["batches"] = wl.prove_stage_batches(label)
         return out
 
