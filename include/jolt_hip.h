@@ -844,6 +844,11 @@ int32_t jolt_round_group_final_values(jolt_ctx *ctx, jolt_member *const *members
 int32_t jolt_host_hyperkzg_commit(jolt_ctx *ctx, const jolt_srs *srs, const jolt_table *evals, jolt_g1_t *out);
 int32_t jolt_host_hyperkzg_open(jolt_ctx *ctx, const jolt_srs *srs, const jolt_table *evals, const jolt_fr_t *point, size_t ell,
                                 uint64_t transcript_label, jolt_g1_t *com, jolt_g1_t *w, jolt_fr_t *v, jolt_fr_t *challenges_out);
+/* The combination that turns the commitments of ONE polynomial against shifted bases into the three witness commitments of kzg_open_batch (kzg.rs:108-116), as the
+ * opening runs it after its three bucket passes over one digit sort; host code, no GPU.  With u = r^2, B = q (X^2 - u) + alpha X + beta and q = Q3 (X - u) + a:
+ * c[k] = commit(X^k Q3) (k = 0, 1, 2), g0 / g1 = the first two SRS points;  w[0], w[1], w[2] = commit of the witness polynomial at r, -r, r^2. */
+int32_t jolt_host_hyperkzg_witness_triple(const jolt_g1_t *c /* 3 */, const jolt_g1_t *g0, const jolt_g1_t *g1, const jolt_fr_t *r, const jolt_fr_t *a,
+                                          const jolt_fr_t *alpha, jolt_g1_t *w /* 3 */);
 
 /* The same opening under the CALLER's Fiat-Shamir transcript -- CommitmentScheme::open(poly, point, eval, setup, hint, transcript) (crates/jolt-openings/src/
  * schemes.rs:66-72; impl crates/jolt-hyperkzg/src/scheme.rs:314-325) with the polynomial resident in HBM.  `fn` is called three times per opening, in order:

@@ -129,7 +129,7 @@ extern "C" int32_t jolt_ctx_destroy(jolt_ctx* ctx) {
     if (ctx->hint_stream) { (void)hipStreamSynchronize(ctx->hint_stream); (void)hipStreamDestroy(ctx->hint_stream); }
     if (ctx->msm_batch_ws) (void)hipFree(ctx->msm_batch_ws);
     if (ctx->msm_aux_stream) { (void)hipStreamSynchronize(ctx->msm_aux_stream); (void)hipStreamDestroy(ctx->msm_aux_stream); }
-    for (auto& pair : ctx->ev_aux) for (hipEvent_t e : pair) if (e) (void)hipEventDestroy(e);
+    for (auto& lane_events : ctx->ev_aux) for (hipEvent_t e : lane_events) if (e) (void)hipEventDestroy(e);
     if (ctx->msm_batch_host) (void)hipHostFree(ctx->msm_batch_host);
     if (ctx->ev_begin) (void)hipEventDestroy(ctx->ev_begin);
     for (hipEvent_t e : ctx->ev_fx)

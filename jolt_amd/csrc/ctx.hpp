@@ -60,11 +60,11 @@ struct jolt_ctx {
     size_t msm_batch_ws_cap = 0;
     void* msm_batch_host = nullptr;
     size_t msm_batch_host_cap = 0;
-    // a pair of fixed-base MSMs over one sort (msm_fixed.hip): the first result's reduction runs here, under the second pass's bucket sums
+    // fixed-base MSMs against shifted bases over one sort (msm_fixed.hip): a pass's reduction runs here, under the next pass's bucket sums.  Per lane and bucket set:
+    // the set's sums are complete, its reduction has ended
     hipStream_t msm_aux_stream = nullptr;
-    hipEvent_t ev_aux[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+    hipEvent_t ev_aux[4][4] = {};
     bool msm_tables_pending = false;  // between jolt_msm_g1_tables_begin and _finish: the side lanes hold MSMs in flight
-    void* msm_pending_one = nullptr;  // an MSM begun by jolt_internal_msm_one_begin and not yet collected (msm.hip)
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
     // jolt_msm_profile_buckets: HIP events around the fixed-base MSM's dominant kernel (k_fx_buckets_ordered) ON THE STREAM IT IS LAUNCHED ON, and where the launch's
     // count of non-zero digits (= mixed additions) lives on the device -- the `roofline_msm` object of bench.py

@@ -9,6 +9,8 @@
 // All are HBM-bound streaming passes (<= 2 multiplies per element); the MSMs they feed dominate (msm.hip).
 #include <algorithm>
 #include <cstdlib>
+#include <system_error>
+#include <thread>
 
 #include "ctx.hpp"
 #include "g1.hip.h"
@@ -21,10 +23,7 @@
 using namespace jolt;
 
 int32_t jolt_internal_msm(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, G1Jac* out);
-int32_t jolt_internal_msm_pair_and_one(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_a, size_t n_a, size_t shift, const Fr* d_b, size_t n_b, G1Jac* out);
-int32_t jolt_internal_msm_one_begin(jolt_ctx* ctx, const jolt_srs* srs, size_t n_a, size_t shift, const Fr* d_b, size_t n_b);
-int32_t jolt_internal_msm_pair_finish(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_a, size_t n_a, size_t shift, G1Jac* out);
-void jolt_internal_msm_one_abandon(jolt_ctx* ctx);
+int32_t jolt_internal_msm_shifted(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, const size_t* shifts, int n_shifts, G1Jac* out);
 int32_t jolt_internal_msm_many(jolt_ctx* ctx, const jolt_srs* srs, const Fr* const* d_scalars, const size_t* n, size_t count, G1Jac* out,
                                const size_t* base_offsets = nullptr);
 
@@ -438,6 +437,55 @@ static int32_t sharded_msm_many(jolt_ctx* ctx, const jolt_srs* srs, const std::v
     return JOLT_OK;
 }
 
+// The three witness commitments of kzg_open_batch (kzg.rs:108-116) from the commitments of ONE polynomial against shifted bases.  With u = r^2,
+// B = q (X^2 - u) + alpha X + beta and q = Q3 (X - u) + a (a = q(u)), the witness polynomials are
+//   h_r    = q (X + r) + alpha = Q3 (X - u)(X + r) + a (X + r) + alpha
+//   h_(-r) = q (X - r) + alpha = Q3 (X - u)(X - r) + a (X - r) + alpha
+//   h_u    = Q3 (X^2 - u) + a (X + u) + alpha                                  (B - B(u) = q (X^2 - u) - a (u^2 - u) + alpha (X - u))
+// so with C_k = commit(X^k Q3), E = C2 + a G1 + alpha G0 and O = r C1 - (u r) C0 + (a r) G0:
+//   w_r = E - u C1 + O,   w_(-r) = E - u C1 - O,   w_u = E - u C0 + (a u) G0
+// The scalars are folded in Fr first, which leaves eight scalar multiplications that do not depend on one another.  Each takes a few tenths of a millisecond of host time and the
+// opening waits for them behind its last reduction, so they run side by side on threads of their own (inline, should the process not get the threads): 0.24 ms in all.
+// Built for the host as well (jolt_host_hyperkzg_witness_triple): the CPU suite holds it to the oracle's three commitments.
+static void witness_triple_combine(const G1Jac c[3], const G1Jac& g0, const G1Jac& g1, const Fr& r, const Fr& a, const Fr& alpha, G1Jac w[3]) {
+    const Fr u = mul(r, r);
+    enum { R_C1, U_C1, UR_C0, U_C0, A_G1, AR_G0, AU_G0, ALPHA_G0, N_MUL };
+    const G1Jac* const base[N_MUL] = {&c[1], &c[1], &c[0], &c[0], &g1, &g0, &g0, &g0};
+    const Fr scalar[N_MUL] = {from_mont(r), from_mont(u), from_mont(mul(u, r)), from_mont(u), from_mont(a), from_mont(mul(a, r)), from_mont(mul(a, u)), from_mont(alpha)};
+    G1Jac m[N_MUL];
+    std::thread workers[N_MUL];
+    for (int i = 0; i < N_MUL; ++i) {
+        auto one = [&m, &base, &scalar, i]() { m[i] = g1_mul_canonical(*base[i], scalar[i].l); };
+        try {
+            if (i + 1 < N_MUL) workers[i] = std::thread(one);
+        } catch (const std::system_error&) {
+        }
+        if (!workers[i].joinable()) one();
+    }
+    for (std::thread& t : workers) if (t.joinable()) t.join();
+    const G1Jac e = g1_add(g1_add(c[2], m[A_G1]), m[ALPHA_G0]);
+    const G1Jac o = g1_add(g1_add(m[R_C1], g1_neg(m[UR_C0])), m[AR_G0]);
+    const G1Jac even = g1_add(e, g1_neg(m[U_C1]));
+    w[0] = g1_add(even, o);
+    w[1] = g1_add(even, g1_neg(o));
+    w[2] = g1_add(g1_add(e, g1_neg(m[U_C0])), m[AU_G0]);
+}
+extern "C" int32_t jolt_host_hyperkzg_witness_triple(const jolt_g1_t* c, const jolt_g1_t* g0, const jolt_g1_t* g1, const jolt_fr_t* r, const jolt_fr_t* a,
+                                                     const jolt_fr_t* alpha, jolt_g1_t* w) {
+    if (!c || !g0 || !g1 || !r || !a || !alpha || !w) return JOLT_ERR_INVALID_ARG;
+    G1Jac pts[5], out[3];
+    std::memcpy(&pts[0], c, 3 * sizeof(G1Jac));
+    std::memcpy(&pts[3], g0, sizeof(G1Jac));
+    std::memcpy(&pts[4], g1, sizeof(G1Jac));
+    for (const G1Jac& p : pts) if (!g1_is_on_curve(p)) return JOLT_ERR_INVALID_ARG;
+    const Fr rr = fr_from_abi(r), aa = fr_from_abi(a), al = fr_from_abi(alpha);
+    if (!fr_is_canonical(rr) || !fr_is_canonical(aa) || !fr_is_canonical(al)) return JOLT_ERR_INVALID_ARG;
+    witness_triple_combine(pts, pts[3], pts[4], rr, aa, al, out);
+    for (G1Jac& p : out) if (g1_is_identity(p)) p = g1_identity();
+    std::memcpy(w, out, sizeof(out));
+    return JOLT_OK;
+}
+
 // The opening's Fiat-Shamir: the library's test transcript, or the CALLER's (jolt_open_transcript_fn: the reference's Blake2b / Keccak transcript stays in Rust).
 // Three absorb-then-challenge steps: the level commitments -> r (scheme.rs:148-152), the 3 ell evaluations -> q (kzg.rs:88-95), the three witness
 // commitments -> d_0 (kzg.rs:118-124).
@@ -598,24 +646,17 @@ static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt
     G1Jac ws[3];
     bool paired = false;
     if (world == 1 && b_poly->len >= 4) {
-        // The witness commitments at r and -r from ONE sorted scalar vector.  B = q (X^2 - r^2) + alpha X + beta gives h_r = (B - B(r)) / (X - r) = q (X + r) + alpha
-        // and h_(-r) = q (X - r) + alpha, so with Cq = commit(q) and Cxq = commit(X q) (the same scalars against the bases shifted by one):
-        //   w[0] = Cxq + r Cq + alpha G_0,   w[1] = Cxq - r Cq + alpha G_0
-        // -- the same group elements kzg.rs:108-116 commits to, from two bucket passes over one digit sort (jolt_internal_msm_fixed_enqueue, pair_shift) instead of two
-        // full MSMs.  q = (h_r - alpha) / (X + r): the quotient recurrence again, whose remainder h_r[0] + q[0] (-r) is alpha.  h_(r^2) keeps its own MSM, on a second lane.
+        // ALL THREE witness commitments from ONE sorted scalar vector.  B = q (X^2 - r^2) + alpha X + beta, and one more linear division q = Q3 (X - r^2) + a: the three
+        // witness polynomials are Q3 times a monic quadratic plus a linear remainder each (witness_triple_combine above), so with C_k = commit(X^k Q3) -- the same scalars
+        // against the bases shifted by k = 0, 1, 2: three bucket passes over one digit sort (jolt_internal_msm_fixed_enqueue with base shifts) -- the host combines the
+        // same group elements kzg.rs:108-116 commits to.  h_(r^2) is never built, and the second lane sorts nothing.
         // q in ONE pass over B when its length is even (every opening of >= 2 variables): q[k] = B[k + 2] + r^2 q[k + 2], two interleaved chains (suffix_scan<2>), and
-        // alpha = B[1] + r^2 q[1] (the X^1 coefficient of B = q (X^2 - r^2) + alpha X + beta); otherwise two divisions, by (X - r) and then by (X + r)
-        jolt_table *h0 = nullptr, *qp = nullptr, *h2 = nullptr;
-        bool direct = false, begun = false;
-        // h at r^2 FIRST, and its MSM enqueued on the second lane at once: its digit sort (HBM bound) runs under the scan that produces q (bound by its multiplications)
-        s = jolt_hyperkzg_witness_poly(ctx, b_poly, &u_abi[2], &h2);
-        if (s == JOLT_OK) {
-            ctx->msm_full_width_scalars = ctx->msm_uniform_scalars = true;  // quotients of the random linear combination: uniform field elements (lets the sort use capacity regions, msm_fixed.hip 2d)
-            const int32_t bs = jolt_internal_msm_one_begin(ctx, srs, b_poly->len - 2, 1, h2->data(), h2->len);
-            ctx->msm_full_width_scalars = ctx->msm_uniform_scalars = false;
-            if (bs == JOLT_OK) begun = true;
-            else if (bs != JOLT_ERR_UNSUPPORTED) s = bs;
-        }
+        // alpha = B[1] + r^2 q[1] (the X^1 coefficient of B = q (X^2 - r^2) + alpha X + beta); otherwise two divisions, by (X - r) and then by (X + r), whose second
+        // remainder h_r[0] + q[0] (-r) is alpha.  Q3[k] = q[k + 1] + r^2 Q3[k + 1] (len - 3 coefficients), a = q[0] + r^2 Q3[0].
+        jolt_table *h0 = nullptr, *qp = nullptr, *q3 = nullptr;
+        bool direct = false;
+        const size_t q3_len = b_poly->len - 3;
+        if (srs->n < 2 || q3_len > srs->n - 2) s = JOLT_ERR_SRS_TOO_SMALL;  // (what the three commitments of len - 1 coefficients need)
         if (s == JOLT_OK && b_poly->len % 2 == 0) {
             s = jolt_internal_table_new(ctx, b_poly->len - 2, &qp);
             if (s == JOLT_OK) {
@@ -629,35 +670,38 @@ static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt
             s = jolt_hyperkzg_witness_poly(ctx, b_poly, &u_abi[0], &h0);
             if (s == JOLT_OK) s = jolt_hyperkzg_witness_poly(ctx, h0, &u_abi[1], &qp);
         }
-        Fr a_lo, q_lo;  // direct: B[1], q[1];  else h_r[0], q[0]
-        G1Affine g0;
+        if (s == JOLT_OK) s = jolt_hyperkzg_witness_poly(ctx, qp, &u_abi[2], &q3);
+        // the five words and two points the combination needs go to the pinned result buffer BEHIND the scans and AHEAD of the MSMs on the main stream: the collect
+        // step's synchronisation is the only one.  [0], [1]: direct: B[1], q[1]; else h_r[0], q[0];  [2]: q[0];  [3]: Q3[0];  [4..8): G_0, G_1
+        static_assert(2 * sizeof(G1Affine) == 4 * sizeof(Fr), "two affine points take four result slots");
+        if (s == JOLT_OK) s = jolt_internal_ensure_scratch(ctx, 1, 8);
         if (s == JOLT_OK) {
-            hipError_t e = hipMemcpyAsync(&a_lo, direct ? b_poly->data() + 1 : h0->data(), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&q_lo, direct ? qp->data() + 1 : qp->data(), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&g0, srs->pts, sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) { ctx->last_error = std::string("hyperkzg open: ") + hipGetErrorString(e); s = JOLT_ERR_HIP; }
+            Fr* hr = ctx->h_results;
+            hipError_t e = hipMemcpyAsync(&hr[0], direct ? b_poly->data() + 1 : h0->data(), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&hr[1], direct ? qp->data() + 1 : qp->data(), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&hr[2], qp->data(), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&hr[3], q3->data(), sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&hr[4], srs->pts, 2 * sizeof(G1Affine), hipMemcpyDeviceToHost, ctx->stream);
+            if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); ctx->last_error = std::string("hyperkzg open: ") + hipGetErrorString(e); s = JOLT_ERR_HIP; }
         }
         if (s == JOLT_OK) {
             G1Jac three[3];
-            ctx->msm_full_width_scalars = ctx->msm_uniform_scalars = true;
-            const int32_t ps = begun ? jolt_internal_msm_pair_finish(ctx, srs, qp->data(), qp->len, 1, three)
-                                     : jolt_internal_msm_pair_and_one(ctx, srs, qp->data(), qp->len, 1, h2->data(), h2->len, three);
+            const size_t shifts[3] = {0, 1, 2};
+            ctx->msm_full_width_scalars = ctx->msm_uniform_scalars = true;  // quotients of the random linear combination: uniform field elements (lets the sort use capacity regions, msm_fixed.hip 2d)
+            const int32_t ts = jolt_internal_msm_shifted(ctx, srs, q3->data(), q3->len, shifts, 3, three);  // lane 0 = the main stream: ordered behind Q3's producer
             ctx->msm_full_width_scalars = ctx->msm_uniform_scalars = false;
-            begun = false;
-            if (ps == JOLT_OK) {
-                const Fr alpha = direct ? add(a_lo, mul(q_lo, u[2])) : add(a_lo, mul(q_lo, u[1])), r_can = from_mont(r), a_can = from_mont(alpha);
-                const G1Jac r_cq = g1_mul_canonical(three[0], r_can.l), base = g1_add(three[1], g1_mul_canonical(g1_from_affine(g0), a_can.l));
-                ws[0] = g1_add(base, r_cq);
-                ws[1] = g1_add(base, g1_neg(r_cq));
-                ws[2] = three[2];
+            if (ts == JOLT_OK) {
+                const Fr* hr = ctx->h_results;
+                G1Affine g01[2];
+                std::memcpy(g01, &hr[4], sizeof(g01));
+                const Fr alpha = add(hr[0], mul(hr[1], direct ? u[2] : u[1])), a = add(hr[2], mul(hr[3], u[2]));
+                witness_triple_combine(three, g1_from_affine(g01[0]), g1_from_affine(g01[1]), r, a, alpha, ws);
                 paired = true;
-            } else if (ps != JOLT_ERR_UNSUPPORTED) {
-                s = ps;
+            } else if (ts != JOLT_ERR_UNSUPPORTED) {
+                s = ts;
             }
         }
-        if (begun) jolt_internal_msm_one_abandon(ctx);  // an error between begin and finish: the lane still reads h2
-        for (jolt_table* t : {h0, qp, h2}) if (t) jolt_table_free(ctx, t);
+        for (jolt_table* t : {h0, qp, q3}) if (t) jolt_table_free(ctx, t);
         if (s != JOLT_OK) { cleanup(b_poly); return s; }
     }
     if (!paired) {  // kzg.rs:108-116: three witness polynomials, then their three independent MSMs on the MSM lanes

@@ -58,9 +58,11 @@ struct MsmJob {
     size_t n = 0;
     int lane = 0, c = 0, W = 0;
     uint32_t nb = 0;
-    int results = 1;  // 2: a pair of MSMs over the same scalars (jolt_internal_msm_fixed_enqueue with pair_shift): the second result follows the first in msm_host
+    int results = 1;  // 2, 3: MSMs over the same scalars against shifted bases (jolt_internal_msm_fixed_enqueue with base shifts): the results follow one another in msm_host
 };
-int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, int lane, MsmJob* job, size_t pair_shift = 0);  // msm_fixed.hip
+constexpr int kFxMaxShifts = 3;  // base shifts one sort serves (msm_fixed.hip)
+int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, int lane, MsmJob* job, const size_t* shifts = nullptr,
+                                        int n_shifts = 0);  // msm_fixed.hip
 namespace {
 struct MsmPlan {
     int c, W, L;  // window bits, windows, lanes per light bucket
@@ -324,17 +326,19 @@ int32_t jolt_internal_msm_collect(jolt_ctx* ctx, const MsmJob* job, G1Jac* out) 
     }
     return JOLT_OK;
 }
-// sum_i s_i P_i and sum_i s_i P_(i + shift) on `lane` with ONE sort of the scalars' digits (msm_fixed.hip); JOLT_ERR_UNSUPPORTED when this SRS / length does not take the
-// fixed-base method (the caller then runs two MSMs)
-int32_t jolt_internal_msm_enqueue_pair(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, size_t shift, int lane, MsmJob* job) {
+// sum_i s_i P_(i + shifts[k]), k < n_shifts <= kFxMaxShifts, on `lane` with ONE sort of the scalars' digits (msm_fixed.hip): job->results = n_shifts points for
+// jolt_internal_msm_collect.  JOLT_ERR_UNSUPPORTED, with nothing enqueued, when this SRS / length does not take the fixed-base method (the caller then runs one MSM per shift)
+int32_t jolt_internal_msm_enqueue_shifted(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, const size_t* shifts, int n_shifts, int lane, MsmJob* job) {
+    if (!shifts || n_shifts < 1 || n_shifts > kFxMaxShifts) return JOLT_ERR_INVALID_ARG;
     job->n = n;
     job->lane = lane;
-    job->results = 2;
-    if (shift > srs->n || n > srs->n - shift) return JOLT_ERR_SRS_TOO_SMALL;
+    job->results = n_shifts;
+    for (int k = 0; k < n_shifts; ++k)
+        if (shifts[k] > srs->n || n > srs->n - shifts[k]) return JOLT_ERR_SRS_TOO_SMALL;
     if (n == 0) return JOLT_OK;
     if (n >= ((size_t)1 << 31)) return JOLT_ERR_UNSUPPORTED;
     if (!(srs->pre && n >= srs->pre_min_n)) return JOLT_ERR_UNSUPPORTED;
-    return jolt_internal_msm_fixed_enqueue(ctx, srs, d_scalars, n, lane, job, shift);
+    return jolt_internal_msm_fixed_enqueue(ctx, srs, d_scalars, n, lane, job, shifts, n_shifts);
 }
 
 // Sharded term assignments (term_map.hip.h): a rank's SRS object holds exactly its terms' bases, compacted in index order, so the
@@ -555,73 +559,15 @@ int32_t jolt_internal_msm_many(jolt_ctx* ctx, const jolt_srs* srs, const Fr* con
     return status;
 }
 
-// out[0] = sum_i a_i P_i, out[1] = sum_i a_i P_(i + shift) (one sort of a's digits for both: msm_fixed.hip) and out[2] = sum_i b_i P_i on a second lane beside them.
-// JOLT_ERR_UNSUPPORTED, with nothing enqueued, when the pair cannot take the fixed-base method.
-int32_t jolt_internal_msm_pair_and_one(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_a, size_t n_a, size_t shift, const Fr* d_b, size_t n_b, G1Jac* out) {
-    if (shift > srs->n || n_a > srs->n - shift) return JOLT_ERR_SRS_TOO_SMALL;
-    if (n_a == 0 || !(srs->pre && n_a >= srs->pre_min_n) || ctx->msm_tables_pending) return JOLT_ERR_UNSUPPORTED;
-    JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    for (int k = 0; k < 3; ++k) JOLT_HIP_TRY(ctx, hipStreamWaitEvent(ctx->side[k], ctx->ev_fork, 0));
-    MsmJob pair, one;
-    int32_t status = jolt_internal_msm_enqueue_pair(ctx, srs, d_a, n_a, shift, 0, &pair);
-    if (status == JOLT_ERR_UNSUPPORTED) return status;  // (decided before any launch: window count / LDS limits)
-    const int lane_b = ctx->msm_lanes > 1 ? 1 : 0;
-    if (status == JOLT_OK && lane_b == 0) status = jolt_internal_msm_collect(ctx, &pair, out);  // one lane: its workspace serves one MSM at a time
-    if (status == JOLT_OK) status = jolt_internal_msm_enqueue(ctx, srs, d_b, n_b, lane_b, &one);
-    if (status == JOLT_OK && lane_b != 0) status = jolt_internal_msm_collect(ctx, &pair, out);
-    if (status == JOLT_OK) status = jolt_internal_msm_collect(ctx, &one, out + 2);
-    if (status != JOLT_OK)
-        for (int k = 0; k < 3; ++k) (void)hipStreamSynchronize(ctx->side[k]);
-    return status;
-}
-
-// The same three results with the SINGLE MSM started early: jolt_internal_msm_one_begin enqueues sum_i b_i P_i on lane 1 as soon as b exists (its sort then runs under
-// whatever the main stream does next -- in an opening, the scan that produces the pair's scalars), jolt_internal_msm_pair_finish enqueues the pair on lane 0 and
-// collects both.  begin returns JOLT_ERR_UNSUPPORTED, with nothing enqueued, when the pair could not take the fixed-base method anyway or there is only one lane
-// (the caller then uses jolt_internal_msm_pair_and_one or three MSMs).
-struct MsmPendingOne {
+// out[k] = sum_i s_i P_(i + shifts[k]) from one sort, on lane 0 (the main stream: ordered behind the scalars' producer), collected before the call returns.
+// JOLT_ERR_UNSUPPORTED with nothing enqueued, as jolt_internal_msm_enqueue_shifted.
+int32_t jolt_internal_msm_shifted(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, const size_t* shifts, int n_shifts, G1Jac* out) {
+    if (ctx->msm_tables_pending) return JOLT_ERR_UNSUPPORTED;
     MsmJob job;
-};
-int32_t jolt_internal_msm_one_begin(jolt_ctx* ctx, const jolt_srs* srs, size_t n_a, size_t shift, const Fr* d_b, size_t n_b) {
-    if (shift > srs->n || n_a > srs->n - shift) return JOLT_ERR_SRS_TOO_SMALL;
-    if (n_a == 0 || !(srs->pre && n_a >= srs->pre_min_n) || ctx->msm_lanes < 2 || ctx->msm_pending_one || ctx->msm_tables_pending) return JOLT_ERR_UNSUPPORTED;
-    if ((size_t)srs->pre_W * n_a >= ((size_t)1 << 32)) return JOLT_ERR_UNSUPPORTED;  // what jolt_internal_msm_fixed_enqueue would refuse for the pair
-    MsmPendingOne* p = new (std::nothrow) MsmPendingOne();
-    if (!p) return JOLT_ERR_OOM;
-    int32_t status = JOLT_OK;
-    hipError_t e = hipEventRecord(ctx->ev_fork, ctx->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->side[0], ctx->ev_fork, 0);
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); status = JOLT_ERR_HIP; }
-    if (status == JOLT_OK) status = jolt_internal_msm_enqueue(ctx, srs, d_b, n_b, 1, &p->job);
-    if (status != JOLT_OK) { (void)hipStreamSynchronize(ctx->side[0]); delete p; return status; }
-    ctx->msm_pending_one = p;
-    return JOLT_OK;
-}
-// out[0], out[1]: the pair over d_a (shift as in jolt_internal_msm_pair_and_one); out[2]: the MSM begun above
-int32_t jolt_internal_msm_pair_finish(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_a, size_t n_a, size_t shift, G1Jac* out) {
-    MsmPendingOne* p = static_cast<MsmPendingOne*>(ctx->msm_pending_one);
-    if (!p) return JOLT_ERR_INVALID_ARG;
-    ctx->msm_pending_one = nullptr;
-    MsmJob pair;
-    int32_t status = jolt_internal_msm_enqueue_pair(ctx, srs, d_a, n_a, shift, 0, &pair);  // lane 0 = the main stream: ordered behind d_a's producer
-    if (status == JOLT_OK) status = jolt_internal_msm_collect(ctx, &pair, out);
-    else if (status == JOLT_ERR_UNSUPPORTED) {  // (not expected after begin's checks) two plain MSMs, the second against the shifted bases
-        status = jolt_internal_msm(ctx, srs, d_a, n_a, &out[0]);
-        const jolt_srs view = jolt_srs_range_view(*srs, shift);
-        if (status == JOLT_OK) status = jolt_internal_msm(ctx, &view, d_a, n_a, &out[1]);
-    }
-    const int32_t one_status = jolt_internal_msm_collect(ctx, &p->job, out + 2);  // always: the lane must be drained before its workspace is used again
-    delete p;
-    if (status != JOLT_OK) (void)hipStreamSynchronize(ctx->side[0]);
-    return status != JOLT_OK ? status : one_status;
-}
-// a begun MSM whose opening failed in between: drain the lane and drop the state
-void jolt_internal_msm_one_abandon(jolt_ctx* ctx) {
-    MsmPendingOne* p = static_cast<MsmPendingOne*>(ctx->msm_pending_one);
-    if (!p) return;
-    ctx->msm_pending_one = nullptr;
-    (void)hipStreamSynchronize(ctx->side[0]);
-    delete p;
+    const int32_t status = jolt_internal_msm_enqueue_shifted(ctx, srs, d_scalars, n, shifts, n_shifts, 0, &job);
+    if (status == JOLT_OK) return jolt_internal_msm_collect(ctx, &job, out);
+    if (status != JOLT_ERR_UNSUPPORTED && status != JOLT_ERR_SRS_TOO_SMALL && status != JOLT_ERR_INVALID_ARG) (void)hipStreamSynchronize(ctx->stream);  // a failed launch: drain what went out
+    return status;
 }
 
 // Up to three MSMs over prefixes of one SRS begun on the side lanes and collected later: the dense columns of a commitment (CommitWitness::commit_witness walks the
@@ -634,7 +580,7 @@ struct jolt_msm_pending {
 extern "C" int32_t jolt_msm_g1_tables_begin(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* const* scalars, const size_t* n, size_t count, jolt_msm_pending** out) {
     if (!ctx || !srs || !scalars || !n || !out || count == 0) return JOLT_ERR_INVALID_ARG;
     *out = nullptr;
-    if (count > 3 || (size_t)ctx->msm_lanes < count + 1 || ctx->msm_tables_pending || ctx->msm_pending_one) return JOLT_ERR_UNSUPPORTED;
+    if (count > 3 || (size_t)ctx->msm_lanes < count + 1 || ctx->msm_tables_pending) return JOLT_ERR_UNSUPPORTED;
     for (size_t i = 0; i < count; ++i) {
         if (!scalars[i]) return JOLT_ERR_INVALID_ARG;
         if (n[i] > scalars[i]->len) return JOLT_ERR_SIZE_MISMATCH;

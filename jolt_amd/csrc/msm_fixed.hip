@@ -22,8 +22,8 @@
 //   5. buckets  : one lane per bucket, XYZZ accumulator in limb form over the L-form tables (k_fx_buckets_ordered_staged); over-full buckets (repeated scalars, the
 //                 carry window of 64-bit witness scalars) as segments of 128 entries, one lane each, folded per bucket (k_fx_heavy_segments_staged / k_fx_heavy_combine)
 //   6. reduce   : sum_b b * B_b by rows and columns of the bucket matrix (k_fx_red_cols / _rows / _fold) and two small running-sum reductions
-// With pair_shift the phases 5-6 run twice over the same sorted lists, the second time against the tables moved by pair_shift points (two MSMs over one set of
-// scalars: the witness commitments at r and -r of a HyperKZG opening).
+// With a list of base shifts the phases 5-6 run once per shift over the same sorted lists, each time against the tables moved by that many points (up to three MSMs
+// over one set of scalars: the three witness commitments of a HyperKZG opening).
 #include <algorithm>
 #include <cstdlib>
 
@@ -38,8 +38,9 @@ struct MsmJob {
     size_t n = 0;
     int lane = 0, c = 0, W = 0;
     uint32_t nb = 0;
-    int results = 1;  // 2: a pair of MSMs over the same scalars (jolt_internal_msm_fixed_enqueue with pair_shift): the second result follows the first in msm_host
+    int results = 1;  // 2, 3: MSMs over the same scalars against shifted bases (jolt_internal_msm_fixed_enqueue with base shifts): the results follow one another in msm_host
 };
+constexpr int kFxMaxShifts = 3;  // base shifts one sort serves
 
 namespace {
 
@@ -1023,9 +1024,6 @@ static int32_t fx_precompute_into(jolt_ctx* ctx, jolt_srs* srs, uint32_t window_
 // ------------------------------------------------------------------------------------------------------------------
 constexpr size_t kMsmHostEntries = 128;
 
-// pair_shift > 0: TWO MSMs over the same scalars, sum_i s_i P_i and sum_i s_i P_(i + pair_shift): the digits, and with them the whole sort, are the scalars' alone,
-// so the second MSM is one more pass of bucket sums and reduction over the same sorted lists with the table pointer moved by pair_shift points (the witness
-// commitments at r and -r of a HyperKZG opening are such a pair: hyperkzg.hip).  n + pair_shift must not exceed the tables' point count.
 // the digit model of n uniform scalars under c-bit signed windows with an unsigned top window (section 2d); false when the top window does not fit the model
 static bool fx_capacity_model(size_t n, int c, int W, FxCapModel* m) {
     const int top_shift = c * (W - 1) + 1;  // the top window's range: ((r - 1) / 2) >> (c (W - 1)), as jolt_host_fx_digits computes it
@@ -1051,7 +1049,15 @@ extern "C" int32_t jolt_host_fx_segment_capacity(uint64_t n, uint32_t window_bit
     return JOLT_OK;
 }
 
-int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, int lane, MsmJob* job, size_t pair_shift) {
+// n_shifts > 0: one MSM per base shift over the same scalars, sum_i s_i P_(i + shifts[k]) for k < n_shifts <= kFxMaxShifts: the digits, and with them the whole sort,
+// are the scalars' alone, so every further MSM is one more pass of bucket sums and reduction over the same sorted lists with the table pointer moved by shifts[k]
+// points (the three witness commitments of a HyperKZG opening come from such a family with shifts 0, 1, 2: hyperkzg.hip).  n + shifts[k] must not exceed the tables'
+// point count.  n_shifts == 0: the one MSM against the unshifted tables.
+int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, const Fr* d_scalars, size_t n, int lane, MsmJob* job, const size_t* shifts, int n_shifts) {
+    if (n_shifts < 0 || n_shifts > kFxMaxShifts || (n_shifts && !shifts)) return JOLT_ERR_INVALID_ARG;
+    const size_t shift_none = 0;
+    const int passes = n_shifts ? n_shifts : 1;
+    if (!n_shifts) shifts = &shift_none;
     const int c = srs->pre_c, W = srs->pre_W;
     const int lo_bits = fx_lo_bits(c);
     const uint32_t kSegBuckets = 1u << lo_bits;
@@ -1118,9 +1124,9 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
                  o_seg = take((size_t)heavy_cap * sizeof(G1Jac)), o_cls = take(kClasses * 4 * 2), o_order = take(n_buckets * 4),
                  o_grouped = take(soa ? span * 6 + 512 : (ctx->msm_fx_partition == 2 ? total * 8 : 256)), o_gcur = take(kPartBins * 4), o_glim = take(kPartBins * 4);
     if (soa) o_keys = o_grouped;
-    // a pair's second pass sums into its OWN bucket set and reduces through its own scratch, so that the first pass's reduction (latency bound: chains of additions on
-    // a few thousand threads) runs on the auxiliary stream under the second pass's bucket sums instead of between the two
-    const bool overlap_reduction = pair_shift != 0 && grid_reduce;
+    // with several passes there are TWO bucket sets, each with its own reduction scratch, and the passes alternate between them, so that a pass's reduction (latency
+    // bound: chains of additions on a few thousand threads) runs on the auxiliary stream under the next pass's bucket sums instead of between the two
+    const bool overlap_reduction = passes > 1 && grid_reduce;
     const size_t o_buckets2 = take(overlap_reduction ? n_buckets * sizeof(G1Jac) : 256), o_red2 = take(overlap_reduction ? red_points * sizeof(G1Jac) : 256),
                  o_wsum2 = take(2 * sizeof(G1Jac));
     hipStream_t st = lane == 0 ? ctx->stream : ctx->side[lane - 1];
@@ -1150,6 +1156,8 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
     const uint32_t n_groups = (nb1 + kGroupBins - 1) >> kGroupBits;
     const size_t lds_bytes = (size_t)nb1 * sizeof(uint32_t);
     if (lds_bytes > ctx->max_lds_per_block) return JOLT_ERR_UNSUPPORTED;
+    const int per_result = grid_reduce ? 2 : 1;  // partial sums a result leaves in msm_host for the collect step's Horner
+    static_assert((size_t)2 * kFxMaxShifts <= kMsmHostEntries, "msm_host takes the partial sums of every pass");
     if (!ctx->msm_fx_attr_set) {
         hipError_t a1 = hipFuncSetAttribute((const void*)k_fx_hist<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->max_lds_per_block);
         hipError_t a2 = hipFuncSetAttribute((const void*)k_fx_scatter<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->max_lds_per_block);
@@ -1288,8 +1296,6 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
         lc.r256 = Fq::one();
     }
     const unsigned bucket_grid = (unsigned)((n_buckets + kBlock - 1) / kBlock);
-    const int per_result = grid_reduce ? 2 : 1;  // partial sums a result leaves in msm_host for the collect step's Horner
-    if ((size_t)per_result * (pair_shift ? 2 : 1) > kMsmHostEntries) return JOLT_ERR_UNSUPPORTED;
     // bucket sums over the sorted lists against the tables at `bases` into `buckets` ...
     auto bucket_sums = [&](const G1Affine* bases, G1Jac* buckets) -> int32_t {
         const bool profile = ctx->fx_profile && ctx->ev_fx[0] && ctx->ev_fx[1];
@@ -1338,33 +1344,44 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
         JOLT_HIP_TRY(ctx, hipMemcpyAsync((G1Jac*)ctx->msm_host[lane] + slot, wsum, (size_t)per_result * sizeof(G1Jac), hipMemcpyDeviceToHost, rs));
         return JOLT_OK;
     };
-    JOLT_TRY(bucket_sums((const G1Affine*)srs->pre, buckets));
-    if (!pair_shift) {
-        JOLT_TRY(reduction(buckets, o_red, wsum, 0, st));
-    } else if (overlap_reduction) {
+    if (!overlap_reduction) {  // one pass, or a small bucket set: the one set zeroed and reused serially
+        for (int k = 0; k < passes; ++k) {
+            // empty buckets rely on the identity the pass before overwrote nowhere; light / heavy ones are rewritten
+            if (k) JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets, 0, n_buckets * sizeof(G1Jac), st));
+            JOLT_TRY(bucket_sums((const G1Affine*)srs->pre + shifts[k], buckets));
+            JOLT_TRY(reduction(buckets, o_red, wsum, k * per_result, st));
+        }
+    } else {
         if (!ctx->msm_aux_stream) JOLT_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->msm_aux_stream, hipStreamNonBlocking));
         if (!ctx->ev_aux[lane][0]) for (hipEvent_t& ev : ctx->ev_aux[lane]) JOLT_HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        G1Jac* buckets2 = (G1Jac*)(ws + o_buckets2);
-        JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[lane][0], st));  // the first pass's buckets are complete
-        JOLT_HIP_TRY(ctx, hipStreamWaitEvent(ctx->msm_aux_stream, ctx->ev_aux[lane][0], 0));
-        JOLT_TRY(reduction(buckets, o_red, wsum, 0, ctx->msm_aux_stream));
-        JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[lane][1], ctx->msm_aux_stream));
-        JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets2, 0, n_buckets * sizeof(G1Jac), st));
-        JOLT_TRY(bucket_sums((const G1Affine*)srs->pre + pair_shift, buckets2));
-        JOLT_TRY(reduction(buckets2, o_red2, (G1Jac*)(ws + o_wsum2), per_result, st));
-        JOLT_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[lane][1], 0));  // the lane's stream covers both results (jolt_internal_msm_collect waits for it alone)
-    } else {
-        JOLT_TRY(reduction(buckets, o_red, wsum, 0, st));
-        JOLT_HIP_TRY(ctx, hipMemsetAsync(buckets, 0, n_buckets * sizeof(G1Jac), st));  // empty buckets rely on the identity the first pass overwrote nowhere; light / heavy ones are rewritten
-        JOLT_TRY(bucket_sums((const G1Affine*)srs->pre + pair_shift, buckets));
-        JOLT_TRY(reduction(buckets, o_red, wsum, per_result, st));
+        // pass k sums into set k & 1; every pass but the last hands its set to the auxiliary stream for the reduction.  ev_aux[lane][2 set]: the set's sums are
+        // complete (lane's stream), [2 set + 1]: its reduction has ended (auxiliary stream) -- what the pass that takes the set again waits for before it zeroes it
+        G1Jac* const set_buckets[2] = {buckets, (G1Jac*)(ws + o_buckets2)};
+        G1Jac* const set_wsum[2] = {wsum, (G1Jac*)(ws + o_wsum2)};
+        const size_t set_red[2] = {o_red, o_red2};
+        for (int k = 0; k < passes; ++k) {
+            const int set = k & 1;
+            if (k >= 2) JOLT_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[lane][2 * set + 1], 0));
+            if (k) JOLT_HIP_TRY(ctx, hipMemsetAsync(set_buckets[set], 0, n_buckets * sizeof(G1Jac), st));
+            JOLT_TRY(bucket_sums((const G1Affine*)srs->pre + shifts[k], set_buckets[set]));
+            if (k + 1 < passes) {
+                JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[lane][2 * set], st));
+                JOLT_HIP_TRY(ctx, hipStreamWaitEvent(ctx->msm_aux_stream, ctx->ev_aux[lane][2 * set], 0));
+                JOLT_TRY(reduction(set_buckets[set], set_red[set], set_wsum[set], k * per_result, ctx->msm_aux_stream));
+                JOLT_HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[lane][2 * set + 1], ctx->msm_aux_stream));
+            } else {
+                JOLT_TRY(reduction(set_buckets[set], set_red[set], set_wsum[set], k * per_result, st));
+                // the lane's stream covers every result (jolt_internal_msm_collect waits for it alone): the auxiliary stream runs its reductions in order
+                JOLT_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_aux[lane][2 * ((k - 1) & 1) + 1], 0));
+            }
+        }
     }
     job->n = n;
     job->lane = lane;
     job->c = grid_reduce ? kRedS : 0;  // the collect step's Horner: 2^S * (row-weighted sum) + (column-weighted sum); or a single "window"
     job->W = per_result;
     job->nb = nb;
-    job->results = pair_shift ? 2 : 1;
+    job->results = passes;
     return JOLT_OK;
 }
 

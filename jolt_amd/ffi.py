@@ -1294,6 +1294,15 @@ def host_dory_combine_row(points, scalars):
     return out[0]
 
 
+def host_hyperkzg_witness_triple(c, g0, g1, r, a, alpha):
+    """the three witness commitments of an opening (at r, -r, r^2) from c[k] = commit(X^k Q3), the first two SRS points and the remainders a, alpha, on the host"""
+    cs = np.ascontiguousarray(c, dtype=np.uint64).reshape(3, 12)
+    p0, p1 = (np.ascontiguousarray(p, dtype=np.uint64).reshape(12) for p in (g0, g1))
+    out = g1_array(3)
+    _ck(lib().jolt_host_hyperkzg_witness_triple(_p(cs), _p(p0), _p(p1), _p(fr(r)), _p(fr(a)), _p(fr(alpha)), _p(out)), "jolt_host_hyperkzg_witness_triple")
+    return out
+
+
 Context.dory_fold_rows_grid = _dory_fold_rows_grid
 Context.dory_combine_hints = _dory_combine_hints
 
