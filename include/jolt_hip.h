@@ -720,6 +720,63 @@ int32_t jolt_r1cs_uniskip_sums_small(jolt_ctx *ctx, const jolt_ints *const *inpu
 int32_t jolt_r1cs_materialize_small(jolt_ctx *ctx, const jolt_ints *const *inputs, size_t n_inputs, uint32_t n_streams, const jolt_fr_t *a_weights,
                                     const jolt_fr_t *b_weights, jolt_table **az_out, jolt_table **bz_out);
 int32_t jolt_ints_evaluate(jolt_ctx *ctx, const jolt_ints *const *columns, size_t k, const jolt_fr_t *point, size_t n, jolt_fr_t *out);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * A constraint system as ROWS over a centred uni-skip domain, and the first round off the rows.
+ *
+ * The column form above takes the rows already folded with the integer extension coefficients into int64 column weights.  The reference's own system cannot be
+ * folded that way: row 8's B side is right_lookup - left + right - 2^64 (crates/jolt-kernels/src/optimized/spartan_outer.rs:243-247), and that constant times an
+ * extension coefficient of about 2^18 has no int64.  A jolt_r1cs_rows keeps the rows: n_streams in {1, 2} (spartan_outer has two row groups selected by the stream
+ * variable, crates/jolt-r1cs/src/constraints/jolt.rs:69-92; spartan_product has one), the uni-skip domain_size D (2 <= D <= 16), per stream at most D rows at the
+ * domain positions 0, 1, ... (rows_per_stream; the rows are listed stream 0 first), n_inputs columns (<= 64), and per row the A and the B side as a sparse linear
+ * form over z = (1, inputs): entries [offsets[r], offsets[r + 1]) of columns (0-based input index) / coefficients (int64, not INT64_MIN), an int64 constant for A
+ * and a signed 128-bit constant (lo, hi; two's complement) for B.  zero_on_domain: the rows hold on every cycle, so t1 vanishes on the D domain nodes and only the
+ * D - 1 nodes outside are evaluated (reference/spartan_outer.rs:183-188); without it all 2D - 1 nodes are (reference/spartan_product.rs:180-200).
+ * Creation computes the integer extension coefficients L_i(node) of the 2D - 1 centred extended nodes -(D - 1) .. D - 1 in 128-bit arithmetic and refuses a
+ * system whose coefficients leave int64 (JOLT_ERR_UNSUPPORTED); an out-of-range column, an INT64_MIN coefficient, more than D rows in a stream or a D outside the
+ * range is JOLT_ERR_INVALID_ARG.
+ *   jolt_r1cs_rows_extension: the (2D - 1) x D coefficients.  jolt_r1cs_rows_fold_small: the column form [node][stream][1 + n_inputs] of the evaluated nodes (what
+ *     jolt_r1cs_uniskip_sums_small takes) where every folded weight has an int64, JOLT_ERR_UNSUPPORTED otherwise; NULL outputs ask for the node count.
+ *   jolt_r1cs_uniskip_sums_rows: sums_out[node] (2D - 1 entries, skipped nodes 0) = sum_t sum_s eq[t * S + s] * Az(node,s,t) * Bz(node,s,t) with
+ *     Az(node,s,t) = sum_i L_i(node) a_{s,i}(t), Bz likewise: per cycle and stream the row values once as exact integers, per node a D-term integer extension, one
+ *     exact product and one field multiplication (optimized/spartan_outer.rs:183-340).  Columns: jolt_ints of kind U64 / I64 / I128, n_cols = n_inputs.
+ *   Range contract (the caller's, as for the column form): |row A value| and |Az(node)| < 2^127, |row B value| and |Bz(node)| < 2^191, |Az * Bz| < 2^254; the
+ *     reference's rows stay below 2^22, 2^152 and 2^174.
+ *   jolt_host_r1cs_rows_cycle: the same per-cycle text built for the host (no device): Az (128-bit) and Bz (256-bit) two's complement, |Az * Bz| and its sign, for
+ *     one cycle's inputs (2 words per input as the column kind stores them), one stream and one extended-node position.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct jolt_r1cs_rows jolt_r1cs_rows;
+int32_t jolt_r1cs_rows_create(uint32_t n_streams, uint32_t domain_size, const uint32_t *rows_per_stream, uint32_t n_inputs, const uint32_t *a_offsets,
+                              const uint32_t *a_columns, const int64_t *a_coefficients, const int64_t *a_constants, const uint32_t *b_offsets,
+                              const uint32_t *b_columns, const int64_t *b_coefficients, const uint64_t *b_constants /* 2 per row */, int32_t zero_on_domain,
+                              jolt_r1cs_rows **out);
+int32_t jolt_r1cs_rows_destroy(jolt_r1cs_rows *rows);
+int32_t jolt_r1cs_rows_extension(const jolt_r1cs_rows *rows, int64_t *out /* (2D - 1) x D */);
+int32_t jolt_r1cs_rows_fold_small(const jolt_r1cs_rows *rows, int64_t *a_weights, int64_t *b_weights, size_t *n_nodes);
+int32_t jolt_r1cs_uniskip_sums_rows(jolt_ctx *ctx, const jolt_r1cs_rows *rows, const jolt_ints *const *cols, size_t n_cols, const jolt_table *eq,
+                                    jolt_fr_t *sums_out /* 2D - 1 */);
+int32_t jolt_host_r1cs_rows_cycle(const jolt_r1cs_rows *rows, const uint64_t *values, const int32_t *kinds, uint32_t stream, uint32_t node, uint64_t *az_out /* 2 */,
+                                  uint64_t *bz_out /* 4 */, uint64_t *product_out /* 4 */, int32_t *negative_out);
+
+/* The uni-skip first round above the sums (host; any transcript engine of this header).
+ *   jolt_host_centered_lagrange_evals: L_0(r) .. L_{D-1}(r) over the centred domain -((D - 1) / 2) .. (crates/jolt-poly/src/lagrange.rs:25-77; a grid point gives the
+ *     unit vector).  jolt_host_centered_lagrange_kernel: LK(x, y) = sum_i L_i(x) L_i(y) (:92-104).  jolt_host_interpolate_to_coeffs: the monomial coefficients of
+ *     the polynomial through `values` at domain_start, domain_start + 1, ... (:567-608).
+ *   jolt_host_uniskip_first_round_poly: s1 = interpolate_to_coeffs(domain_start, centered_lagrange_evals(D, tau_high)) x interpolate_to_coeffs(extended_start, t1),
+ *     3D - 2 coefficients (crates/jolt-kernels/src/reference/spartan_outer.rs:217-225).
+ *   jolt_host_prove_uniskip: prove_uniskip_clear (crates/jolt-sumcheck/src/prover.rs:415-440): the degree bound 3D - 3 (n - 1 above it: JOLT_ERR_UNSUPPORTED), the
+ *     centred-domain round check sum_k c_k S_k = input_claim with the i128 power sums (domain.rs:11-41, lagrange.rs:499-534; JOLT_ERR_ROUND_CHECK; a power sum that
+ *     leaves i128 is the reference's InvalidIntegerDomain, JOLT_ERR_UNSUPPORTED), LabelWithCount("uniskip_poly", n) and ALL n coefficients absorbed
+ *     (round_proof.rs:70-86), Transcript::challenge, the output claim s1(r0), append_labeled("opening_claim", claim).
+ *   jolt_host_r1cs_rows_remainder_weights: what jolt_stage_spartan_remainder_rows_create derives, without a device: a_weights / b_weights [stream][1 + n_inputs]. */
+int32_t jolt_host_centered_lagrange_evals(size_t domain_size, const jolt_fr_t *r, jolt_fr_t *out);
+int32_t jolt_host_centered_lagrange_kernel(size_t domain_size, const jolt_fr_t *x, const jolt_fr_t *y, jolt_fr_t *out);
+int32_t jolt_host_interpolate_to_coeffs(int64_t domain_start, const jolt_fr_t *values, size_t n, jolt_fr_t *out);
+int32_t jolt_host_uniskip_first_round_poly(size_t domain_size, const jolt_fr_t *tau_high, const jolt_fr_t *t1 /* 2D - 1 */, jolt_fr_t *coeffs_out /* 3D - 2 */);
+int32_t jolt_host_prove_uniskip(jolt_host_transcript *transcript, const jolt_fr_t *coeffs, size_t n, size_t domain_size, const jolt_fr_t *input_claim, jolt_fr_t *r0_out,
+                                jolt_fr_t *output_claim_out);
+int32_t jolt_host_r1cs_rows_remainder_weights(const jolt_r1cs_rows *rows, const jolt_fr_t *r0, const jolt_fr_t *tau_high, jolt_fr_t *a_weights, jolt_fr_t *b_weights,
+                                              jolt_fr_t *scale);
 /* csrc/small_scalar.hip.h built for the host (CPU suite): sum_k values[k] * scalars[k], scalars as signed 128-bit (lo, hi) pairs. */
 int32_t jolt_host_small_scalar_dot(const jolt_fr_t *values, const uint64_t *scalars, size_t n, jolt_fr_t *out);
 
@@ -987,6 +1044,12 @@ int32_t jolt_stage_spartan_uniskip_sums(jolt_ctx *ctx, const jolt_ints *const *c
  * (field weights [stream][1 + n_cols]), the split-eq product member over them, n_tau rounds of degree 3.  output_claims: the n_cols claimed inputs at the cycle point. */
 int32_t jolt_stage_spartan_remainder_create(jolt_ctx *ctx, const jolt_ints *const *cols, size_t n_cols, uint32_t n_streams, const jolt_fr_t *a_weights,
                                             const jolt_fr_t *b_weights, const jolt_fr_t *tau, size_t n_tau, const jolt_fr_t *scale, jolt_stage_op **out);
+/* The remainder of a row system at the DRAWN uni-skip challenge r0: column weights fa[s][v] = sum_i L_i(r0) A_{s,i}[v] (constants in column 0), fb likewise
+ * (spartan_outer_row_weights, crates/jolt-r1cs/src/constraints/jolt.rs:141-170; weighted_columns + public_column_contributions, reference/spartan_outer.rs:239-262),
+ * the scale LK(tau_high, r0) (:240-244), then jolt_r1cs_materialize_small and the split-eq product member: an ordinary operator with the output claims of
+ * jolt_stage_spartan_remainder_create.  tau: the n_tau coordinates of the rounds (cycle variables, then the stream).  jolt_stage_op_kept: "a_weights", "b_weights", "scale". */
+int32_t jolt_stage_spartan_remainder_rows_create(jolt_ctx *ctx, const jolt_r1cs_rows *rows, const jolt_ints *const *cols, size_t n_cols, const jolt_fr_t *tau, size_t n_tau,
+                                                 const jolt_fr_t *tau_high, const jolt_fr_t *r0, jolt_stage_op **out);
 /* ram_read_write (optimized/ram_read_write.rs:58-330): RamAccessColumns (u64 jolt_ints of T entries), RamInc (i64, T), the initial memory (u64, K); log T cycle rounds
  * (cubic, gruen_poly_deg_3) then log K address rounds (quadratic).  output_claims: {ra, val, inc, bound cycle-eq factor}. */
 int32_t jolt_stage_ram_read_write_create(jolt_ctx *ctx, const jolt_ints *addresses, const jolt_ints *pre_values, const jolt_ints *post_values, const jolt_ints *inc,
@@ -1047,6 +1110,20 @@ int32_t jolt_stage_host_expr_create(const jolt_fr_t *const *tables, size_t len, 
 int32_t jolt_host_prove_batch_ops(jolt_ctx *ctx, jolt_stage_op *const *ops, size_t n_ops, const jolt_fr_t *input_claims, const jolt_fr_t *coefficients,
                                   const size_t *offsets, size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode,
                                   jolt_fr_t *out_polys, jolt_fr_t *out_challenges, jolt_fr_t *out_member_claims, jolt_fr_t *out_final_claim);
+/* jolt_host_prove_batch_ops on a transcript the caller already holds (the same bytes when that transcript is fresh under the same label). */
+int32_t jolt_host_prove_batch_ops_on(jolt_ctx *ctx, jolt_stage_op *const *ops, size_t n_ops, const jolt_fr_t *input_claims, const jolt_fr_t *coefficients,
+                                     const size_t *offsets, size_t max_num_vars, size_t max_degree, jolt_host_transcript *transcript, int32_t challenge_mode,
+                                     jolt_fr_t *out_polys, jolt_fr_t *out_challenges, jolt_fr_t *out_member_claims, jolt_fr_t *out_final_claim);
+/* A Spartan stage on ONE transcript (crates/jolt-prover/src/stages/stage1.rs:63-111): jolt_r1cs_uniskip_sums_rows against eq(tau_low, .), the first-round polynomial,
+ * jolt_host_prove_uniskip, the remainder operator at the drawn challenge, and a one-member batch (degree 3, n_tau - 1 rounds) whose input claim is the uni-skip output
+ * claim.  tau: log T cycle coordinates, the stream coordinate of a two-stream system, then tau_high (n_tau = log T + n_streams).  The caller draws tau and the batch
+ * coefficient.  Outputs: the 3D - 2 uni-skip coefficients, r0, the uni-skip output claim, the remainder's round polynomials ((n_tau - 1) x 4), challenges, final
+ * claim and the n_cols output claims.  An unsatisfied witness fails the remainder's first round check (JOLT_ERR_ROUND_CHECK): the remainder's sum is taken
+ * once over its tables and compared with the uni-skip output claim, because the split-eq round message is assembled from the claim and would pass its own check.  Everything is released. */
+int32_t jolt_host_prove_spartan_stage(jolt_ctx *ctx, const jolt_r1cs_rows *rows, const jolt_ints *const *cols, size_t n_cols, const jolt_fr_t *tau, size_t n_tau,
+                                      const jolt_fr_t *input_claim, const jolt_fr_t *coefficient, jolt_host_transcript *transcript, jolt_fr_t *uniskip_coeffs_out,
+                                      jolt_fr_t *r0_out, jolt_fr_t *uniskip_claim_out, jolt_fr_t *polys_out, jolt_fr_t *challenges_out, jolt_fr_t *final_claim_out,
+                                      jolt_fr_t *output_claims_out);
 int32_t jolt_host_stage_op_prove_alone(jolt_stage_op *op, jolt_host_transcript *transcript, jolt_fr_t *claim, jolt_fr_t *coeffs_out, size_t stride,
                                        uint32_t *n_coeffs_out, jolt_fr_t *challenges_out);
 /* jolt_host_prove_batch_ops under the backend's round scheduler (BuildRoundScheduler, crates/jolt-kernels/src/backend.rs:68-70; RoundScheduler, prover.rs:110-120): per round the

@@ -1105,11 +1105,6 @@ extern "C" int32_t jolt_host_pair_tables_bind(jolt_fr_t* g, jolt_fr_t* w, size_t
 
 // ---- the caller-side Fiat-Shamir of members that are driven round by round outside prove_batch (sparse read-write matrix, read-RAF
 // phases): the deterministic test transcript behind four entry points; a Rust caller uses its own Transcript instead.
-struct jolt_host_transcript {
-    LabelledTranscript t;
-    explicit jolt_host_transcript(uint64_t label) : t(label) {}
-    jolt_host_transcript(int kind, const uint8_t* label, size_t n) : t(kind, label, n) {}
-};
 extern "C" int32_t jolt_host_transcript_create(uint64_t label, jolt_host_transcript** out) {
     if (!out) return JOLT_ERR_INVALID_ARG;
     *out = new (std::nothrow) jolt_host_transcript(label);

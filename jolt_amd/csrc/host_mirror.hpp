@@ -224,3 +224,10 @@ Fr fr_from_challenge_bytes(const uint8_t* b, size_t n);
 Fr fr_from_scalar_challenge_bytes(const uint8_t* b, size_t n);
 
 }  // namespace jolt_host
+
+// the object behind jolt_host_transcript_* (host_mirror.hip); the drivers that prove on a transcript the caller holds reach the engine through it
+struct jolt_host_transcript {
+    jolt_host::LabelledTranscript t;
+    explicit jolt_host_transcript(uint64_t label) : t(label) {}
+    jolt_host_transcript(int kind, const uint8_t* label, size_t n) : t(kind, label, n) {}
+};

@@ -17,11 +17,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "ctx.hpp"
 #include "ints.hpp"
 #include "poly_kernels.hip.h"
+#include "r1cs_rows.hpp"
 #include "small_scalar.hip.h"
 
 using namespace jolt;
@@ -112,6 +114,77 @@ __global__ __launch_bounds__(kBlock) void k_small_uniskip(IntInputs in, const Fr
     }
     Fr acc[1] = {mul(sub(pos, neg_sum), Fr::r2())};  // plain -> Montgomery, once per thread
     block_reduce_store_at<1>(acc, partials + (node * n_slices + slice));
+}
+
+template <int... I, class F>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&& f) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+
+// block_reduce_store_at with the accumulators indexed by instantiation (NE = 9 is past what the loop unroller does before the accumulators are split into registers)
+template <int NE>
+__device__ __forceinline__ void block_reduce_store_static(Fr (&acc)[NE], Fr* __restrict__ dst) {
+    __shared__ Fr sm[kBlock / 64][NE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    static_for(std::make_integer_sequence<int, NE>{}, [&](auto tc) __attribute__((always_inline)) {
+        constexpr int t = decltype(tc)::value;
+        Fr v = acc[t];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            Fr o;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) o.l[k] = __shfl_xor(v.l[k], off, 64);
+            v = add(v, o);
+        }
+        if (lane == 0) sm[wave][t] = v;
+    });
+    __syncthreads();
+    if (threadIdx.x < NE) {
+        Fr s = sm[0][threadIdx.x];
+        for (int w = 1; w < kBlock / 64; ++w) s = add(s, sm[w][threadIdx.x]);
+        st_fr_agent(dst + threadIdx.x, s);
+    }
+}
+
+// The first round over a system given as ROWS (jolt_r1cs_rows; r1cs_rows.hip.h): per cycle and stream the D row values once (A 128-bit, B 192-bit exact integers), then per
+// node of this workgroup's node group the D-term integer extension, ONE exact product and ONE field multiplication, accumulated in plain form with the product's sign.
+// partials[(slice * n_groups + group) * NC + j] = this block's share of t1(nodes[group * NC + j]).  The row tables, the extension coefficients and the column
+// pointers are indexed by values that are the same for every lane (scalar loads).  Workgroup numbering as k_small_uniskip: the groups of one slice are neighbours on one XCD.
+template <int STREAMS, int DCAP, int NC>
+__global__ __launch_bounds__(kBlock) void k_rows_uniskip(IntInputs in, const Fr* __restrict__ eq, size_t cycles, RowsView rv, Fr* __restrict__ partials, uint32_t n_groups,
+                                                         uint32_t n_slices) {
+    const uint32_t b = blockIdx.x, slice = (b & 7u) + 8u * (b / (8u * n_groups)), group = (b >> 3) % n_groups;
+    if (slice >= n_slices) return;  // block-uniform (the slice count is padded to a multiple of 8)
+    const uint32_t k0 = group * NC;
+    Fr acc[NC];
+    static_for(std::make_integer_sequence<int, NC>{}, [&](auto jc) __attribute__((always_inline)) { acc[decltype(jc)::value] = Fr::zero(); });
+    const size_t stride = (size_t)n_slices * kBlock;
+    for (size_t t = (size_t)slice * kBlock + threadIdx.x; t < cycles; t += stride) {
+        const auto load = [&](uint32_t c) __attribute__((always_inline)) { return load_small(in.z[c], in.kind[c], t); };
+        const auto stream = [&](uint32_t s) __attribute__((always_inline)) {
+            unsigned __int128 a[DCAP];
+            I192 bv[DCAP];
+            rows_cycle_values<DCAP>(rv, s, load, a, bv);
+            const Fr e = ld_fr(eq + STREAMS * t + s);
+            // (unrolled by instantiation, not by the loop unroller: the accumulators must be split into registers before the late passes see them)
+            static_for(std::make_integer_sequence<int, NC>{}, [&](auto jc) __attribute__((always_inline)) {
+                constexpr int j = decltype(jc)::value;
+                if (k0 + j < rv.n_eval) {  // wave-uniform
+                    unsigned __int128 az;
+                    I256 bz;
+                    rows_extend<DCAP>(rv.ext + (size_t)rv.nodes[k0 + j] * rv.D, rv.D, a, bv, &az, &bz);
+                    U256 prod;
+                    const bool negative = rows_product(az, bz, prod.l);
+                    const Fr term = mul(e, fr_from_u256(prod));
+                    acc[j] = negative ? sub(acc[j], term) : add(acc[j], term);
+                }
+            });
+        };
+        stream(0u);
+        if (STREAMS == 2) stream(1u);
+    }
+    static_for(std::make_integer_sequence<int, NC>{}, [&](auto jc) __attribute__((always_inline)) { acc[decltype(jc)::value] = mul(acc[decltype(jc)::value], Fr::r2()); });  // plain -> Montgomery, once per thread
+    block_reduce_store_static<NC>(acc, partials + ((size_t)slice * n_groups + group) * NC);
 }
 
 // ws[i] = w[i] * R (Montgomery form of w*R: REDC of sum ws*z lands in Montgomery form), nws[i] = -ws[i]; mask bit per weight != 0
@@ -247,6 +320,57 @@ extern "C" int32_t jolt_r1cs_uniskip_sums_small(jolt_ctx* ctx, const jolt_ints* 
     jolt_internal_dev_free(ctx, wa);
     jolt_internal_dev_free(ctx, wb);
     return s;
+}
+
+// t1 at the 2D - 1 centred extended nodes of a row system (jolt_r1cs_rows), straight off the integer columns; nodes the system marks as vanishing are reported as 0
+template <int STREAMS, int DCAP, int NC>
+static void launch_rows_uniskip(jolt_ctx* ctx, unsigned blocks, const IntInputs& in, const Fr* eq, size_t cycles, const RowsView& rv, uint32_t n_groups, uint32_t n_slices) {
+    hipLaunchKernelGGL((k_rows_uniskip<STREAMS, DCAP, NC>), dim3(blocks), dim3(kBlock), 0, ctx->stream, in, eq, cycles, rv, ctx->d_partials, n_groups, n_slices);
+}
+
+extern "C" int32_t jolt_r1cs_uniskip_sums_rows(jolt_ctx* ctx, const jolt_r1cs_rows* rows, const jolt_ints* const* cols, size_t n_cols, const jolt_table* eq, jolt_fr_t* sums_out) {
+    if (!ctx || !rows || !cols || !eq || !sums_out) return JOLT_ERR_INVALID_ARG;
+    if (n_cols != rows->n_inputs) return JOLT_ERR_SIZE_MISMATCH;
+    IntInputs in;
+    size_t cycles = 0;
+    JOLT_TRY(gather_ints(ctx, cols, n_cols, &in, &cycles));
+    const uint32_t S = rows->n_streams, D = rows->D, n_eval = (uint32_t)rows->nodes.size();
+    if (eq->len != S * cycles) return JOLT_ERR_SIZE_MISMATCH;
+    // one blob: the 64-bit arrays first, then the 32-bit ones
+    const size_t n64 = rows->a_cf.size() + rows->a_c0.size() + rows->b_cf.size() + rows->b_c0.size() + rows->ext.size();
+    const size_t n32 = rows->a_off.size() + rows->a_col.size() + rows->b_off.size() + rows->b_col.size() + rows->nodes.size();
+    std::vector<uint8_t> blob(n64 * 8 + n32 * 4 + 8);
+    size_t at = 0;
+    auto put = [&](const void* p, size_t bytes) { if (bytes) std::memcpy(blob.data() + at, p, bytes); const size_t o = at; at += bytes; return o; };
+    const size_t o_acf = put(rows->a_cf.data(), rows->a_cf.size() * 8), o_ac0 = put(rows->a_c0.data(), rows->a_c0.size() * 8), o_bcf = put(rows->b_cf.data(), rows->b_cf.size() * 8);
+    const size_t o_bc0 = put(rows->b_c0.data(), rows->b_c0.size() * 8), o_ext = put(rows->ext.data(), rows->ext.size() * 8);
+    const size_t o_aoff = put(rows->a_off.data(), rows->a_off.size() * 4), o_acol = put(rows->a_col.data(), rows->a_col.size() * 4);
+    const size_t o_boff = put(rows->b_off.data(), rows->b_off.size() * 4), o_bcol = put(rows->b_col.data(), rows->b_col.size() * 4), o_nodes = put(rows->nodes.data(), rows->nodes.size() * 4);
+    uint8_t* d = nullptr;
+    JOLT_TRY(upload_bytes(ctx, blob.data(), blob.size(), (void**)&d));
+    const RowsView rv{(const uint32_t*)(d + o_aoff), (const uint32_t*)(d + o_acol), (const int64_t*)(d + o_acf), (const int64_t*)(d + o_ac0), (const uint32_t*)(d + o_boff),
+                      (const uint32_t*)(d + o_bcol), (const int64_t*)(d + o_bcf), (const uint64_t*)(d + o_bc0), (const int64_t*)(d + o_ext), (const uint32_t*)(d + o_nodes), D, n_eval};
+    // the cycle slices of k_small_uniskip; a lane takes more than one cycle above num_cus * 4 * kBlock cycles.  Nodes per workgroup: as many as the row values and one plain
+    // accumulator each leave room for without scratch (profiles/uniskip_rows_ab.txt has the register counts)
+    const uint32_t nc = D <= 3 ? 5u : D <= 10 ? 9u : 5u;
+    const uint32_t n_groups = (n_eval + nc - 1) / nc, ne = n_groups * nc;
+    const int grid = (int)std::max<size_t>(1, std::min<size_t>((cycles + kBlock - 1) / kBlock, (size_t)ctx->num_cus * 4));
+    int32_t s = jolt_internal_ensure_scratch(ctx, (size_t)grid * ne + 8, ne + 8);
+    std::vector<jolt_fr_t> sums(ne);
+    if (s == JOLT_OK) {
+        const unsigned blocks = (unsigned)(((size_t)grid + 7) / 8 * 8 * n_groups);
+        const Fr* e = (const Fr*)eq->data();
+        if (D <= 3) { if (S == 2) launch_rows_uniskip<2, 3, 5>(ctx, blocks, in, e, cycles, rv, n_groups, (uint32_t)grid); else launch_rows_uniskip<1, 3, 5>(ctx, blocks, in, e, cycles, rv, n_groups, (uint32_t)grid); }
+        else if (D <= 10) { if (S == 2) launch_rows_uniskip<2, 10, 9>(ctx, blocks, in, e, cycles, rv, n_groups, (uint32_t)grid); else launch_rows_uniskip<1, 10, 9>(ctx, blocks, in, e, cycles, rv, n_groups, (uint32_t)grid); }
+        else { if (S == 2) launch_rows_uniskip<2, 16, 5>(ctx, blocks, in, e, cycles, rv, n_groups, (uint32_t)grid); else launch_rows_uniskip<1, 16, 5>(ctx, blocks, in, e, cycles, rv, n_groups, (uint32_t)grid); }
+        s = hipGetLastError() == hipSuccess ? JOLT_OK : JOLT_ERR_HIP;
+    }
+    if (s == JOLT_OK) s = reduce_rows_to_host(ctx, 1, grid, (int)ne, sums.data());
+    jolt_internal_dev_free(ctx, d);
+    if (s != JOLT_OK) return s;
+    std::memset(sums_out, 0, (size_t)(2 * D - 1) * sizeof(jolt_fr_t));
+    for (uint32_t k = 0; k < n_eval; ++k) sums_out[rows->nodes[k]] = sums[k];
+    return JOLT_OK;
 }
 
 extern "C" int32_t jolt_r1cs_materialize_small(jolt_ctx* ctx, const jolt_ints* const* inputs, size_t n_inputs, uint32_t n_streams, const jolt_fr_t* a_weights,

@@ -32,6 +32,7 @@
 #include "ints.hpp"
 #include "member.hpp"
 #include "onehot.hpp"
+#include "r1cs_rows.hpp"
 
 using namespace jolt;
 using namespace jolt_host;
@@ -894,6 +895,10 @@ extern "C" int32_t jolt_stage_op_destroy(jolt_stage_op* op) {
     return JOLT_OK;
 }
 
+static int32_t prove_batch_ops_on(jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients, const size_t* offsets,
+                                  size_t max_num_vars, size_t max_degree, Transcript& tr, int32_t challenge_mode, bool grouped, jolt_fr_t* out_polys,
+                                  jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim);  // (drivers, below)
+
 // ------------------------------------------------------------------------------------------------------------------
 // constructors (= PrepareKernel::prepare of the slot)
 // ------------------------------------------------------------------------------------------------------------------
@@ -924,6 +929,66 @@ extern "C" int32_t jolt_stage_spartan_remainder_create(jolt_ctx* ctx, const jolt
     ha.release();
     hb.release();
     *out = hold.release();
+    return JOLT_OK;
+}
+
+// The remainder of a row system at the drawn uni-skip challenge: the column weights fa[s][v] = sum_i L_i(r0) A_{s,i}[v] (constants in column 0), fb likewise, and the scale
+// LK(tau_high, r0) (spartan_outer_row_weights + weighted_columns + public_column_contributions, reference/spartan_outer.rs:239-262), then the operator above.  The
+// derived weights stay readable: kept "a_weights", "b_weights", "scale".
+extern "C" int32_t jolt_stage_spartan_remainder_rows_create(jolt_ctx* ctx, const jolt_r1cs_rows* rows, const jolt_ints* const* cols, size_t n_cols, const jolt_fr_t* tau, size_t n_tau,
+                                                            const jolt_fr_t* tau_high, const jolt_fr_t* r0, jolt_stage_op** out) {
+    if (!ctx || !rows || !cols || !tau || !tau_high || !r0 || !out || !all_canonical(tau_high, 1) || !all_canonical(r0, 1)) return JOLT_ERR_INVALID_ARG;
+    if (n_cols != rows->n_inputs) return JOLT_ERR_SIZE_MISMATCH;
+    std::vector<Fr> fa, fb;
+    Fr scale;
+    jolt_r1cs_rows_host::remainder_weights(*rows, fr_from_abi(r0), fr_from_abi(tau_high), &fa, &fb, &scale);
+    std::vector<jolt_fr_t> wa = to_abi(fa), wb = to_abi(fb);
+    jolt_fr_t k;
+    fr_to_abi(&k, scale);
+    JOLT_TRY(jolt_stage_spartan_remainder_create(ctx, cols, n_cols, rows->n_streams, wa.data(), wb.data(), tau, n_tau, &k, out));
+    (*out)->kept["a_weights"] = std::move(fa);
+    (*out)->kept["b_weights"] = std::move(fb);
+    (*out)->kept["scale"] = {scale};
+    return JOLT_OK;
+}
+
+// A Spartan stage on ONE transcript (crates/jolt-prover/src/stages/stage1.rs:63-111): t1 off the rows (jolt_r1cs_uniskip_sums_rows against eq(tau_low, .)), the first-round
+// polynomial LK(tau_high, .) x t1, prove_uniskip_clear, the remainder at the drawn challenge, and a one-member batch whose input claim is the uni-skip output claim.
+// tau: log T cycle coordinates, the stream coordinate of a two-stream system, then tau_high.  polys_out: n_rounds x 4 (n_rounds = n_tau - 1).
+extern "C" int32_t jolt_host_prove_spartan_stage(jolt_ctx* ctx, const jolt_r1cs_rows* rows, const jolt_ints* const* cols, size_t n_cols, const jolt_fr_t* tau, size_t n_tau,
+                                                 const jolt_fr_t* input_claim, const jolt_fr_t* coefficient, jolt_host_transcript* transcript, jolt_fr_t* uniskip_coeffs_out,
+                                                 jolt_fr_t* r0_out, jolt_fr_t* uniskip_claim_out, jolt_fr_t* polys_out, jolt_fr_t* challenges_out, jolt_fr_t* final_claim_out,
+                                                 jolt_fr_t* output_claims_out) {
+    if (!ctx || !rows || !cols || !tau || !input_claim || !coefficient || !transcript || !uniskip_coeffs_out || !r0_out || !uniskip_claim_out || !polys_out || !challenges_out ||
+        !final_claim_out || !output_claims_out)
+        return JOLT_ERR_INVALID_ARG;
+    if (n_tau < rows->n_streams || !all_canonical(tau, n_tau)) return JOLT_ERR_INVALID_ARG;
+    if (n_cols != rows->n_inputs) return JOLT_ERR_SIZE_MISMATCH;
+    const size_t D = rows->D, n_low = n_tau - 1;
+    const jolt_fr_t* tau_high = tau + n_low;
+    std::vector<jolt_fr_t> t1(2 * D - 1), coeffs(3 * D - 2);
+    {
+        TableH eq;
+        JOLT_TRY(eq_table(ctx, from_abi(tau, n_low), &eq));
+        JOLT_TRY(jolt_r1cs_uniskip_sums_rows(ctx, rows, cols, n_cols, eq.t, t1.data()));
+    }
+    JOLT_TRY(jolt_host_uniskip_first_round_poly(D, tau_high, t1.data(), coeffs.data()));
+    JOLT_TRY(jolt_host_prove_uniskip(transcript, coeffs.data(), coeffs.size(), D, input_claim, r0_out, uniskip_claim_out));
+    std::memcpy(uniskip_coeffs_out, coeffs.data(), coeffs.size() * sizeof(jolt_fr_t));
+    jolt_stage_op* op = nullptr;
+    JOLT_TRY(jolt_stage_spartan_remainder_rows_create(ctx, rows, cols, n_cols, tau, n_low, tau_high, r0_out, &op));
+    std::unique_ptr<jolt_stage_op> hold(op);  // released on every path below
+    // The remainder's first round must sum to the uni-skip output claim.  The split-eq message is assembled FROM the claim (gruen_poly_deg_3 takes s(0) + s(1) as
+    // given), so prove_batch's own round check cannot see a witness that breaks a row: the sum is taken here, once, over the materialized tables.
+    Fr sum;
+    JOLT_TRY(op->input_claim(&sum));
+    if (sum != fr_from_abi(uniskip_claim_out)) return op->fail(JOLT_ERR_ROUND_CHECK, "round 0: the remainder does not sum to the uni-skip output claim (a constraint row does not hold)");
+    const size_t offset = 0;
+    jolt_fr_t member_claim;
+    JOLT_TRY(prove_batch_ops_on(&op, 1, uniskip_claim_out, coefficient, &offset, n_low, 3, transcript->t, 0, false, polys_out, challenges_out, &member_claim, final_claim_out));
+    std::vector<Fr> claims;
+    JOLT_TRY(op->output_claims(&claims));
+    for (size_t i = 0; i < claims.size(); ++i) fr_to_abi(&output_claims_out[i], claims[i]);
     return JOLT_OK;
 }
 
@@ -1349,9 +1414,9 @@ extern "C" int32_t jolt_stage_host_expr_create(const jolt_fr_t* const* tables, s
 // drivers
 // ------------------------------------------------------------------------------------------------------------------
 // prove_batch (prover.rs:193-362) over stage operators with the library's test transcript: what a stage driver does with the kernels a backend's slots returned.
-static int32_t prove_batch_ops(jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients, const size_t* offsets,
-                               size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode, bool grouped, jolt_fr_t* out_polys,
-                               jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim) {
+static int32_t prove_batch_ops_on(jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients, const size_t* offsets,
+                                  size_t max_num_vars, size_t max_degree, Transcript& tr, int32_t challenge_mode, bool grouped, jolt_fr_t* out_polys,
+                                  jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim) {
     if ((!ops && n_ops) || !input_claims || !coefficients || !offsets || !out_polys || !out_challenges || !out_member_claims || !out_final_claim) return JOLT_ERR_INVALID_ARG;
     std::vector<ProveRounds*> ms;
     std::vector<BatchMember> described;
@@ -1367,7 +1432,6 @@ static int32_t prove_batch_ops(jolt_stage_op* const* ops, size_t n_ops, const jo
         described.push_back(BatchMember{fr_from_abi(&input_claims[i]), fr_from_abi(&coefficients[i]), ops[i]->rounds, offsets[i]});
     }
     BatchPrelude prelude = BatchPrelude::make(std::move(described), max_num_vars, max_degree);
-    LabelledTranscript tr(transcript_label);
     SequentialRounds seq;
     MemberGroupedRounds group;
     RoundScheduler& sched = grouped ? static_cast<RoundScheduler&>(group) : static_cast<RoundScheduler&>(seq);
@@ -1382,6 +1446,22 @@ static int32_t prove_batch_ops(jolt_stage_op* const* ops, size_t n_ops, const jo
     for (size_t i = 0; i < n_ops; ++i) fr_to_abi(&out_member_claims[i], proved.member_claims[i]);
     fr_to_abi(out_final_claim, proved.final_claim);
     return JOLT_OK;
+}
+static int32_t prove_batch_ops(jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients, const size_t* offsets,
+                               size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode, bool grouped, jolt_fr_t* out_polys,
+                               jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim) {
+    LabelledTranscript tr(transcript_label);
+    return prove_batch_ops_on(ops, n_ops, input_claims, coefficients, offsets, max_num_vars, max_degree, tr, challenge_mode, grouped, out_polys, out_challenges, out_member_claims,
+                              out_final_claim);
+}
+// the same batch on a transcript the caller already holds (a stage's batch follows its uni-skip round on ONE transcript)
+extern "C" int32_t jolt_host_prove_batch_ops_on(jolt_ctx* ctx, jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients,
+                                                const size_t* offsets, size_t max_num_vars, size_t max_degree, jolt_host_transcript* transcript, int32_t challenge_mode,
+                                                jolt_fr_t* out_polys, jolt_fr_t* out_challenges, jolt_fr_t* out_member_claims, jolt_fr_t* out_final_claim) {
+    (void)ctx;
+    if (!transcript) return JOLT_ERR_INVALID_ARG;
+    return prove_batch_ops_on(ops, n_ops, input_claims, coefficients, offsets, max_num_vars, max_degree, transcript->t, challenge_mode, false, out_polys, out_challenges,
+                              out_member_claims, out_final_claim);
 }
 extern "C" int32_t jolt_host_prove_batch_ops(jolt_ctx* ctx, jolt_stage_op* const* ops, size_t n_ops, const jolt_fr_t* input_claims, const jolt_fr_t* coefficients,
                                              const size_t* offsets, size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode,

@@ -2219,3 +2219,159 @@ Context.stage_bytecode_read_raf_address = _stage_bytecode_read_raf_address
 Context.stage_bytecode_read_raf_cycle = _stage_bytecode_read_raf_cycle
 Context.stage_ram_raf_evaluation = _stage_ram_raf_evaluation
 Context.stage_ram_output_check = _stage_ram_output_check
+
+
+# ---- a constraint system as rows, the uni-skip round above it (r1cs_rows.hip, small_r1cs.hip, stage_ops.hip) ---------------------------------------------------
+class R1csRows:
+    """jolt_r1cs_rows: streams = per stream a list of rows (a_terms, a_const, b_terms, b_const) at the domain positions 0, 1, ...; terms = [(input index, int64 coefficient)],
+    b_const any integer of 128 signed bits.  No device, no context."""
+
+    def __init__(self, streams, domain_size, n_inputs, zero_on_domain=True):
+        rows = [r for st in streams for r in st]
+        def flat(side):
+            offs, cols, cfs = [0], [], []
+            for r in rows:
+                for c, a in r[side]:
+                    cols.append(c)
+                    cfs.append(a)
+                offs.append(len(cols))
+            return np.array(offs, dtype=np.uint32), np.array(cols if cols else [0], dtype=np.uint32), np.array(cfs if cfs else [0], dtype=np.int64)
+        ao, ac, af = flat(0)
+        bo, bc, bf = flat(2)
+        a0 = np.array([r[1] for r in rows] if rows else [0], dtype=np.int64)
+        b0 = np.array([[int(r[3]) & (2**64 - 1), (int(r[3]) >> 64) & (2**64 - 1)] for r in rows] if rows else [[0, 0]], dtype=np.uint64)
+        per = np.array([len(st) for st in streams] + [0], dtype=np.uint32)
+        self.h = C.c_void_p()
+        self.n_streams, self.domain_size, self.n_inputs, self.zero_on_domain = len(streams), domain_size, n_inputs, bool(zero_on_domain)
+        _ck(lib().jolt_r1cs_rows_create(C.c_uint32(len(streams)), C.c_uint32(domain_size), _p(per), C.c_uint32(n_inputs), _p(ao), _p(ac), _p(af), _p(a0), _p(bo), _p(bc), _p(bf),
+                                        _p(b0), C.c_int32(1 if zero_on_domain else 0), C.byref(self.h)), "jolt_r1cs_rows_create")
+
+    @property
+    def n_nodes(self):
+        return 2 * self.domain_size - 1
+
+    def extension(self):
+        """L_i(node): (2D - 1, D) int64"""
+        out = np.zeros((self.n_nodes, self.domain_size), dtype=np.int64)
+        _ck(lib().jolt_r1cs_rows_extension(self.h, _p(out)), "jolt_r1cs_rows_extension")
+        return out
+
+    def fold_small(self):
+        """the column form of the evaluated nodes: (wa, wb) int64 [node][stream][1 + n_inputs] (JoltError `unsupported` where a folded weight has no int64)"""
+        n = C.c_size_t()
+        _ck(lib().jolt_r1cs_rows_fold_small(self.h, None, None, C.byref(n)), "jolt_r1cs_rows_fold_small")
+        wa = np.zeros((n.value, self.n_streams, 1 + self.n_inputs), dtype=np.int64)
+        wb = np.zeros_like(wa)
+        _ck(lib().jolt_r1cs_rows_fold_small(self.h, _p(wa), _p(wb), C.byref(n)), "jolt_r1cs_rows_fold_small")
+        return wa, wb
+
+    def host_cycle(self, values, kinds, stream, node):
+        """jolt_host_r1cs_rows_cycle: one cycle's inputs (Python ints) -> (Az, Bz, Az * Bz) as Python ints"""
+        v = np.array([[int(x) & (2**64 - 1), (int(x) >> 64) & (2**64 - 1)] for x in values], dtype=np.uint64)
+        k = np.array([Ints.KINDS[q] for q in kinds], dtype=np.int32)
+        az, bz, pr, ng = np.zeros(2, dtype=np.uint64), np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_int32()
+        _ck(lib().jolt_host_r1cs_rows_cycle(self.h, _p(v), _p(k), C.c_uint32(stream), C.c_uint32(node), _p(az), _p(bz), _p(pr), C.byref(ng)), "jolt_host_r1cs_rows_cycle")
+        def signed(words, bits):
+            x = sum(int(w) << (64 * i) for i, w in enumerate(words))
+            return x - (1 << bits) if x >> (bits - 1) else x
+        mag = sum(int(w) << (64 * i) for i, w in enumerate(pr))
+        return signed(az, 128), signed(bz, 256), -mag if ng.value else mag
+
+    def remainder_weights(self, r0, tau_high):
+        """jolt_host_r1cs_rows_remainder_weights -> (fa, fb) [stream][1 + n_inputs], scale"""
+        fa, fb, k = fr_array(self.n_streams * (1 + self.n_inputs)), fr_array(self.n_streams * (1 + self.n_inputs)), fr_array(1)
+        _ck(lib().jolt_host_r1cs_rows_remainder_weights(self.h, _p(fr(r0)), _p(fr(tau_high)), _p(fa), _p(fb), _p(k)), "jolt_host_r1cs_rows_remainder_weights")
+        shape = (self.n_streams, 1 + self.n_inputs, 4)
+        return fa.reshape(shape), fb.reshape(shape), k[0]
+
+    def destroy(self):
+        if self.h:
+            lib().jolt_r1cs_rows_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def host_centered_lagrange_evals(domain_size, r):
+    out = fr_array(domain_size)
+    _ck(lib().jolt_host_centered_lagrange_evals(C.c_size_t(domain_size), _p(fr(r)), _p(out)), "jolt_host_centered_lagrange_evals")
+    return out
+
+
+def host_centered_lagrange_kernel(domain_size, x, y):
+    out = fr_array(1)
+    _ck(lib().jolt_host_centered_lagrange_kernel(C.c_size_t(domain_size), _p(fr(x)), _p(fr(y)), _p(out)), "jolt_host_centered_lagrange_kernel")
+    return out[0]
+
+
+def host_interpolate_to_coeffs(domain_start, values):
+    v = fr(values).reshape(-1, 4)
+    out = fr_array(v.shape[0])
+    _ck(lib().jolt_host_interpolate_to_coeffs(C.c_int64(domain_start), _p(v), C.c_size_t(v.shape[0]), _p(out)), "jolt_host_interpolate_to_coeffs")
+    return out
+
+
+def host_uniskip_first_round_poly(domain_size, tau_high, t1):
+    v = fr(t1).reshape(-1, 4)
+    assert v.shape[0] == 2 * domain_size - 1
+    out = fr_array(3 * domain_size - 2)
+    _ck(lib().jolt_host_uniskip_first_round_poly(C.c_size_t(domain_size), _p(fr(tau_high)), _p(v), _p(out)), "jolt_host_uniskip_first_round_poly")
+    return out
+
+
+def host_prove_uniskip(transcript, coeffs, domain_size, input_claim):
+    """jolt_host_prove_uniskip -> (r0, output claim)"""
+    c = fr(coeffs).reshape(-1, 4)
+    r0, claim = fr_array(1), fr_array(1)
+    _ck(lib().jolt_host_prove_uniskip(transcript.h, _p(c), C.c_size_t(c.shape[0]), C.c_size_t(domain_size), _p(fr(input_claim)), _p(r0), _p(claim)), "jolt_host_prove_uniskip")
+    return r0[0], claim[0]
+
+
+def prove_batch_ops_on(ops, input_claims, coefficients, offsets, max_num_vars, max_degree, transcript, challenge_mode=0, ctx=None):
+    """jolt_host_prove_batch_ops_on: prove_batch over operators on a transcript the caller holds"""
+    n = len(ops)
+    hs = (C.c_void_p * n)(*[o.h for o in ops])
+    ic = np.ascontiguousarray(np.stack(input_claims), dtype=np.uint64).reshape(-1, 4)
+    co = np.ascontiguousarray(np.stack(coefficients), dtype=np.uint64).reshape(-1, 4)
+    offs = (C.c_size_t * n)(*offsets)
+    polys, chal = fr_array(max(max_num_vars * (max_degree + 1), 1)), fr_array(max(max_num_vars, 1))
+    mclaims, final = fr_array(n), fr_array(1)
+    _ck(lib().jolt_host_prove_batch_ops_on(ctx.h if ctx is not None else None, hs, C.c_size_t(n), _p(ic), _p(co), offs, C.c_size_t(max_num_vars), C.c_size_t(max_degree), transcript.h,
+                                           C.c_int32(challenge_mode), _p(polys), _p(chal), _p(mclaims), _p(final)), "jolt_host_prove_batch_ops_on", ctx)
+    return dict(polys=polys[: max_num_vars * (max_degree + 1)].reshape(max_num_vars, max_degree + 1, 4), challenges=chal[:max_num_vars], member_claims=mclaims, final_claim=final[0])
+
+
+def _r1cs_uniskip_sums_rows(self, rows, cols, eq):
+    """jolt_r1cs_uniskip_sums_rows: t1 at the 2D - 1 extended nodes (nodes the system marks as vanishing: 0)"""
+    out = fr_array(rows.n_nodes)
+    _ck(lib().jolt_r1cs_uniskip_sums_rows(self.h, rows.h, _handles(cols), C.c_size_t(len(cols)), eq.h, _p(out)), "jolt_r1cs_uniskip_sums_rows", self)
+    return out
+
+
+def _stage_spartan_remainder_rows(self, rows, cols, tau, tau_high, r0):
+    t = fr(tau).reshape(-1, 4)
+    h = C.c_void_p()
+    _ck(lib().jolt_stage_spartan_remainder_rows_create(self.h, rows.h, _handles(cols), C.c_size_t(len(cols)), _p(t), C.c_size_t(t.shape[0]), _p(fr(tau_high)), _p(fr(r0)), C.byref(h)),
+        "jolt_stage_spartan_remainder_rows_create", self)
+    return StageOp(self, h, keep=list(cols) + [rows])
+
+
+def _prove_spartan_stage(self, rows, cols, tau, input_claim, coefficient, transcript):
+    """jolt_host_prove_spartan_stage on the caller's transcript -> dict(uniskip_coeffs, r0, uniskip_claim, polys, challenges, final_claim, values)"""
+    t = fr(tau).reshape(-1, 4)
+    n = t.shape[0] - 1
+    D = rows.domain_size
+    uc, r0, claim = fr_array(3 * D - 2), fr_array(1), fr_array(1)
+    polys, chal, final, values = fr_array(max(n * 4, 1)), fr_array(max(n, 1)), fr_array(1), fr_array(len(cols))
+    _ck(lib().jolt_host_prove_spartan_stage(self.h, rows.h, _handles(cols), C.c_size_t(len(cols)), _p(t), C.c_size_t(t.shape[0]), _p(fr(input_claim)), _p(fr(coefficient)), transcript.h,
+                                            _p(uc), _p(r0), _p(claim), _p(polys), _p(chal), _p(final), _p(values)), "jolt_host_prove_spartan_stage", self)
+    return dict(uniskip_coeffs=uc, r0=r0[0], uniskip_claim=claim[0], polys=polys[: n * 4].reshape(n, 4, 4), challenges=chal[:n], final_claim=final[0], values=values)
+
+
+Context.r1cs_uniskip_sums_rows = _r1cs_uniskip_sums_rows
+Context.stage_spartan_remainder_rows = _stage_spartan_remainder_rows
+Context.prove_spartan_stage = _prove_spartan_stage

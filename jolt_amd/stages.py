@@ -213,6 +213,98 @@ def extended_params(n_vars, seed=2026, n_outer=35, n_nodes=9, n_tables=42, ra_co
     return p
 
 
+def random_row_system(n_streams, domain_size, seed=2026, second_stream_rows=None, n_flags=5, n_free=6, foldable=False):
+    """A random constraint system of shape (S, D) in the reference's row form guard * (left - right) = 0 for jolt_r1cs_rows: A rows over flag columns (a flag, or a
+    difference of two, coefficients of both signs), B rows differences and sums over U64 / I64 / I128 columns.  Every row owns one `solve` column (coefficient +-1, in no
+    other row) through which a witness makes it hold; row (0, 0) has A = flag 0 alone; one row of stream 0 carries the constant -2^64 (as row 8 of the reference's
+    outer system does).  foldable: every constant stays below 2^36 and none is 2^64, so that the rows folded with the extension coefficients keep int64 column weights
+    (the column form can run the same system).  -> dict(streams = per stream [(a_terms, a_const, b_terms, b_const)], kinds, n_inputs, solve = per stream the solve column of each row)"""
+    rng = np.random.default_rng([seed, 0x5057, n_streams, domain_size])
+    counts = [domain_size] + ([domain_size if second_stream_rows is None else second_stream_rows] if n_streams == 2 else [])
+    kinds = ["u64"] * n_flags + [("u64", "i64", "i128")[k % 3] for k in range(n_free)]
+    free = list(range(n_flags, n_flags + n_free))
+    free_u64 = [c for c in free if kinds[c] == "u64"]
+    streams, solve = [], []
+    for s, count in enumerate(counts):
+        rows, sol = [], []
+        for i in range(count):
+            if s == 0 and i == 0:
+                a_terms, a_const = [(0, 1)], 0
+            elif rng.integers(0, 2):
+                f, g = rng.choice(n_flags, size=2, replace=False)
+                a_terms, a_const = [(int(f), 1), (int(g), -1)], 0
+            else:
+                a_terms, a_const = [(int(rng.integers(0, n_flags)), int(rng.choice([1, -1, 2])))], 0
+            col = len(kinds)
+            shape = 3 if (s == 0 and i == 1 and not foldable) else int(rng.integers(0, 3))
+            if shape == 0:    # a copy: u64 solve = a u64 input
+                kinds.append("u64")
+                b_terms, b_const = [(int(rng.choice(free_u64)), 1), (col, -1)], 0
+            elif shape == 1:  # an i64 solve against a small constant and a flag
+                kinds.append("i64")
+                b_terms, b_const = [(col, 1), (int(rng.integers(0, n_flags)), int(rng.integers(-5, 6)) or 1)], int(rng.integers(-2**36, 2**36))
+            else:             # an i128 solve against a signed sum of inputs; shape 3: with the constant -2^64
+                kinds.append("i128")
+                picks = rng.choice(free, size=2, replace=False)
+                b_terms = [(int(picks[0]), 1), (int(picks[1]), -int(rng.integers(1, 4))), (col, int(rng.choice([1, -1])))]
+                b_const = -(1 << 64) if shape == 3 else int(rng.integers(-2**36, 2**36)) if foldable else int(rng.integers(-2**62, 2**62))
+            rows.append((a_terms, a_const, b_terms, b_const))
+            sol.append(col)
+        streams.append(rows)
+        solve.append(sol)
+    return dict(streams=streams, kinds=kinds, n_inputs=len(kinds), solve=solve, domain_size=domain_size, n_flags=n_flags)
+
+
+def _int_column(values, kind):
+    if kind == "u64":
+        return np.array([int(v) for v in values], dtype=np.uint64)
+    if kind == "i64":
+        return np.array([int(v) for v in values], dtype=np.int64)
+    return np.array([[int(v) & (2**64 - 1), (int(v) >> 64) & (2**64 - 1)] for v in values], dtype=np.uint64).reshape(-1, 2)
+
+
+def satisfied_rows_block(p, n_block, block, system=None, seed=2026, broken_cycle=None):
+    """A satisfied trace of block `block` (T_b = 2^n_block cycles) for a row system (random_row_system(*p["rows_shape"]) by default): on every cycle every row holds --
+    its guard is 0, or its solve column makes left = right.  Deterministic per block, as extended_block is.  broken_cycle: row (0, 0) is violated on that cycle (its
+    guard flag set, its solve column off by one).  -> dict(system, cols = numpy columns in input order, ints = the same values as Python integers per column)"""
+    system = system or random_row_system(*p["rows_shape"], seed=seed)
+    T = 1 << n_block
+    rng = np.random.default_rng([seed + 500, 0xB10C, block, 7])
+    kinds, n_flags = system["kinds"], system["n_flags"]
+    solve_cols = {c for sol in system["solve"] for c in sol}
+    ints = [None] * system["n_inputs"]
+    for c, kind in enumerate(kinds):
+        if c in solve_cols:
+            continue
+        if c < n_flags:
+            ints[c] = [int(v) for v in rng.integers(0, 2, size=T)]
+        elif kind == "u64":
+            ints[c] = [int(v) for v in rng.integers(0, 2**64, size=T, dtype=np.uint64)]
+        elif kind == "i64":
+            ints[c] = [int(v) for v in rng.integers(-2**62, 2**62, size=T)]
+        else:
+            ints[c] = [(int(h) << 64) | int(l) for l, h in zip(rng.integers(0, 2**64, size=T, dtype=np.uint64), rng.integers(-2**40, 2**40, size=T))]
+    if broken_cycle is not None:
+        ints[0][broken_cycle] = 1
+    for rows, sol in zip(system["streams"], system["solve"]):
+        for (a_terms, a_const, b_terms, b_const), col in zip(rows, sol):
+            own = next(a for c, a in b_terms if c == col)  # +-1
+            vals = []
+            for t in range(T):
+                rest = b_const + sum(a * ints[c][t] for c, a in b_terms if c != col)
+                guard = a_const + sum(a * ints[c][t] for c, a in a_terms)
+                v = -rest * own  # own * v + rest = 0
+                lo, hi = {"u64": (0, 2**64), "i64": (-2**63 + 1, 2**63), "i128": (-2**127 + 1, 2**127)}[kinds[col]]
+                if not lo <= v < hi or (guard == 0 and rng.integers(0, 2)):  # an unguarded row may hold anything; a solution outside the column's range needs the guard off
+                    assert guard == 0 or lo <= v < hi, "row system whose solve column cannot hold the solution"
+                    v = int(rng.integers(0, 2**62))
+                vals.append(v)
+            ints[col] = vals
+    if broken_cycle is not None:
+        ints[system["solve"][0][0]][broken_cycle] += 1
+    return dict(system=system, ints=ints, cols=[_int_column(v, k) for v, k in zip(ints, kinds)])
+
+
 def extended_block(p, n_block, block, seed=2026, ram_init=None, reg_init=None, only_state=False):
     """The witness columns of block `block` of the trace: T_b = 2^n_block cycles, drawn from the block's own generators, so that any rank of a sharded prover
     builds ITS block without the others' columns.  What ties blocks together is the machine state: the RAM and the register file a block starts from are what the
@@ -725,6 +817,17 @@ class DeviceExtended:
         r0 = tr.challenge()  # the uni-skip challenge (the Lagrange weights of the remainder are a function of it; fixed weights here)
         tr.close()
         return sums, r0
+
+    def spartan_stage(self, rows, cols, tau, claim, label):
+        """A Spartan stage as the reference proves it, on ONE transcript `label` (jolt_host_prove_spartan_stage): t1 off the constraint ROWS (an ffi.R1csRows over the
+        resident integer columns `cols`), the uni-skip round LK(tau_high, .) x t1, the remainder at the drawn challenge with input claim = the uni-skip output claim.
+        tau: log T cycle coordinates, the stream coordinate of a two-stream system, tau_high; claim: the uni-skip input claim (0 for the outer relation).  Not one of
+        OPERATORS and not in the step: the step keeps spartan() below."""
+        tr = self.ffi.HostTranscript(label)
+        try:
+            return self.ctx.prove_spartan_stage(rows, cols, tau, claim, self.one, tr)
+        finally:
+            tr.close()
 
     def spartan(self, cols, iwa, iwb, fa, fb, tau, kernel, claim, streams, label):
         sums, r0 = self.spartan_uniskip(cols, iwa, iwb, tau, streams, label)

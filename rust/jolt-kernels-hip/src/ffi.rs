@@ -77,6 +77,10 @@ pub struct jolt_read_raf_address {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct jolt_r1cs_rows {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct jolt_rw_matrix {
     _private: [u8; 0],
 }
@@ -354,6 +358,18 @@ extern "C" {
     pub fn jolt_r1cs_uniskip_sums_small(ctx: *mut jolt_ctx, inputs: *const *const jolt_ints, n_inputs: usize, eq: *const jolt_table, n_streams: u32, a_weights: *const i64, b_weights: *const i64, n_nodes: usize, out: *mut jolt_fr_t) -> i32;
     pub fn jolt_r1cs_materialize_small(ctx: *mut jolt_ctx, inputs: *const *const jolt_ints, n_inputs: usize, n_streams: u32, a_weights: *const jolt_fr_t, b_weights: *const jolt_fr_t, az_out: *mut *mut jolt_table, bz_out: *mut *mut jolt_table) -> i32;
     pub fn jolt_ints_evaluate(ctx: *mut jolt_ctx, columns: *const *const jolt_ints, k: usize, point: *const jolt_fr_t, n: usize, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_r1cs_rows_create(n_streams: u32, domain_size: u32, rows_per_stream: *const u32, n_inputs: u32, a_offsets: *const u32, a_columns: *const u32, a_coefficients: *const i64, a_constants: *const i64, b_offsets: *const u32, b_columns: *const u32, b_coefficients: *const i64, b_constants: *const u64, zero_on_domain: i32, out: *mut *mut jolt_r1cs_rows) -> i32;
+    pub fn jolt_r1cs_rows_destroy(rows: *mut jolt_r1cs_rows) -> i32;
+    pub fn jolt_r1cs_rows_extension(rows: *const jolt_r1cs_rows, out: *mut i64) -> i32;
+    pub fn jolt_r1cs_rows_fold_small(rows: *const jolt_r1cs_rows, a_weights: *mut i64, b_weights: *mut i64, n_nodes: *mut usize) -> i32;
+    pub fn jolt_r1cs_uniskip_sums_rows(ctx: *mut jolt_ctx, rows: *const jolt_r1cs_rows, cols: *const *const jolt_ints, n_cols: usize, eq: *const jolt_table, sums_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_r1cs_rows_cycle(rows: *const jolt_r1cs_rows, values: *const u64, kinds: *const i32, stream: u32, node: u32, az_out: *mut u64, bz_out: *mut u64, product_out: *mut u64, negative_out: *mut i32) -> i32;
+    pub fn jolt_host_centered_lagrange_evals(domain_size: usize, r: *const jolt_fr_t, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_centered_lagrange_kernel(domain_size: usize, x: *const jolt_fr_t, y: *const jolt_fr_t, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_interpolate_to_coeffs(domain_start: i64, values: *const jolt_fr_t, n: usize, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_uniskip_first_round_poly(domain_size: usize, tau_high: *const jolt_fr_t, t1: *const jolt_fr_t, coeffs_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_prove_uniskip(transcript: *mut jolt_host_transcript, coeffs: *const jolt_fr_t, n: usize, domain_size: usize, input_claim: *const jolt_fr_t, r0_out: *mut jolt_fr_t, output_claim_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_r1cs_rows_remainder_weights(rows: *const jolt_r1cs_rows, r0: *const jolt_fr_t, tau_high: *const jolt_fr_t, a_weights: *mut jolt_fr_t, b_weights: *mut jolt_fr_t, scale: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_small_scalar_dot(values: *const jolt_fr_t, scalars: *const u64, n: usize, out: *mut jolt_fr_t) -> i32;
     pub fn jolt_rw_matrix_create(ctx: *mut jolt_ctx, addresses: *const u64, pre_values: *const u64, post_values: *const u64, cycles: usize, inc: *const jolt_table, val_init: *const jolt_table, tau_low: *const jolt_fr_t, gamma: *const jolt_fr_t, out: *mut *mut jolt_rw_matrix) -> i32;
     pub fn jolt_rw_matrix_create_resident(ctx: *mut jolt_ctx, addresses: *const jolt_ints, pre_values: *const jolt_ints, post_values: *const jolt_ints, inc: *const jolt_table, val_init: *const jolt_table, tau_low: *const jolt_fr_t, gamma: *const jolt_fr_t, out: *mut *mut jolt_rw_matrix) -> i32;
@@ -428,6 +444,7 @@ extern "C" {
     pub fn jolt_stage_op_destroy(op: *mut jolt_stage_op) -> i32;
     pub fn jolt_stage_spartan_uniskip_sums(ctx: *mut jolt_ctx, cols: *const *const jolt_ints, n_cols: usize, n_streams: u32, tau: *const jolt_fr_t, n_tau: usize, a_weights: *const i64, b_weights: *const i64, n_nodes: usize, sums_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_stage_spartan_remainder_create(ctx: *mut jolt_ctx, cols: *const *const jolt_ints, n_cols: usize, n_streams: u32, a_weights: *const jolt_fr_t, b_weights: *const jolt_fr_t, tau: *const jolt_fr_t, n_tau: usize, scale: *const jolt_fr_t, out: *mut *mut jolt_stage_op) -> i32;
+    pub fn jolt_stage_spartan_remainder_rows_create(ctx: *mut jolt_ctx, rows: *const jolt_r1cs_rows, cols: *const *const jolt_ints, n_cols: usize, tau: *const jolt_fr_t, n_tau: usize, tau_high: *const jolt_fr_t, r0: *const jolt_fr_t, out: *mut *mut jolt_stage_op) -> i32;
     pub fn jolt_stage_ram_read_write_create(ctx: *mut jolt_ctx, addresses: *const jolt_ints, pre_values: *const jolt_ints, post_values: *const jolt_ints, inc: *const jolt_ints, val_init: *const jolt_ints, tau_low: *const jolt_fr_t, gamma: *const jolt_fr_t, out: *mut *mut jolt_stage_op) -> i32;
     pub fn jolt_stage_registers_read_write_create(ctx: *mut jolt_ctx, regs: *const jolt_onehot, rs1_val: *const jolt_ints, rs2_val: *const jolt_ints, rd_pre: *const jolt_ints, rd_post: *const jolt_ints, inc: *const jolt_ints, r_cycle: *const jolt_fr_t, gamma: *const jolt_fr_t, out: *mut *mut jolt_stage_op) -> i32;
     pub fn jolt_stage_booleanity_address_create(ctx: *mut jolt_ctx, cols: *const jolt_onehot, reference_cycle: *const jolt_fr_t, n_cycle: usize, reference_address: *const jolt_fr_t, gamma: *const jolt_fr_t, out: *mut *mut jolt_stage_op) -> i32;
@@ -441,6 +458,8 @@ extern "C" {
     pub fn jolt_stage_member_create(ctx: *mut jolt_ctx, member: *mut jolt_member, flags: u32, out: *mut *mut jolt_stage_op) -> i32;
     pub fn jolt_stage_host_expr_create(tables: *const *const jolt_fr_t, len: usize, desc: *const jolt_member_desc, out: *mut *mut jolt_stage_op) -> i32;
     pub fn jolt_host_prove_batch_ops(ctx: *mut jolt_ctx, ops: *const *mut jolt_stage_op, n_ops: usize, input_claims: *const jolt_fr_t, coefficients: *const jolt_fr_t, offsets: *const usize, max_num_vars: usize, max_degree: usize, transcript_label: u64, challenge_mode: i32, out_polys: *mut jolt_fr_t, out_challenges: *mut jolt_fr_t, out_member_claims: *mut jolt_fr_t, out_final_claim: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_prove_batch_ops_on(ctx: *mut jolt_ctx, ops: *const *mut jolt_stage_op, n_ops: usize, input_claims: *const jolt_fr_t, coefficients: *const jolt_fr_t, offsets: *const usize, max_num_vars: usize, max_degree: usize, transcript: *mut jolt_host_transcript, challenge_mode: i32, out_polys: *mut jolt_fr_t, out_challenges: *mut jolt_fr_t, out_member_claims: *mut jolt_fr_t, out_final_claim: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_prove_spartan_stage(ctx: *mut jolt_ctx, rows: *const jolt_r1cs_rows, cols: *const *const jolt_ints, n_cols: usize, tau: *const jolt_fr_t, n_tau: usize, input_claim: *const jolt_fr_t, coefficient: *const jolt_fr_t, transcript: *mut jolt_host_transcript, uniskip_coeffs_out: *mut jolt_fr_t, r0_out: *mut jolt_fr_t, uniskip_claim_out: *mut jolt_fr_t, polys_out: *mut jolt_fr_t, challenges_out: *mut jolt_fr_t, final_claim_out: *mut jolt_fr_t, output_claims_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_stage_op_prove_alone(op: *mut jolt_stage_op, transcript: *mut jolt_host_transcript, claim: *mut jolt_fr_t, coeffs_out: *mut jolt_fr_t, stride: usize, n_coeffs_out: *mut u32, challenges_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_prove_batch_ops_grouped(ctx: *mut jolt_ctx, ops: *const *mut jolt_stage_op, n_ops: usize, input_claims: *const jolt_fr_t, coefficients: *const jolt_fr_t, offsets: *const usize, max_num_vars: usize, max_degree: usize, transcript_label: u64, challenge_mode: i32, out_polys: *mut jolt_fr_t, out_challenges: *mut jolt_fr_t, out_member_claims: *mut jolt_fr_t, out_final_claim: *mut jolt_fr_t) -> i32;
 }

@@ -104,6 +104,93 @@ impl SpartanSums<'_> {
     }
 }
 
+/// One row of a [`HipR1csRows`] side: `(input index, coefficient)` terms.
+pub type RowTerms = Vec<(u32, i64)>;
+
+/// A constraint system as ROWS over a centred uni-skip domain (`jolt_r1cs_rows`): the path beside [`SpartanSums::uniskip_sums`] that needs no folded
+/// int64 weights and no crate-private helper of `jolt-kernels` -- `t1` straight off the rows (`optimized/spartan_outer.rs:183-340`), the first-round
+/// polynomial (`reference/spartan_outer.rs:217-225`) and the remainder's field weights at the drawn challenge (`:239-262`) come from the library.
+pub struct HipR1csRows {
+    pub(crate) raw: *mut ffi::jolt_r1cs_rows,
+    pub domain_size: usize,
+    pub streams: u32,
+    pub inputs: usize,
+}
+// SAFETY: the object is immutable host data after creation.
+unsafe impl Send for HipR1csRows {}
+unsafe impl Sync for HipR1csRows {}
+
+impl HipR1csRows {
+    /// `streams[s][i] = (A terms, A constant, B terms, B constant)` at domain position `i`; `zero_on_domain`: the rows hold on every cycle (outer), so only the
+    /// `D - 1` nodes outside the domain are evaluated.
+    pub fn new(streams: &[Vec<(RowTerms, i64, RowTerms, i128)>], domain_size: usize, inputs: usize, zero_on_domain: bool) -> Result<Self, HipError> {
+        let per: Vec<u32> = streams.iter().map(|s| s.len() as u32).collect();
+        let (mut a_off, mut a_col, mut a_cf, mut a_c0) = (vec![0u32], Vec::new(), Vec::new(), Vec::new());
+        let (mut b_off, mut b_col, mut b_cf, mut b_c0) = (vec![0u32], Vec::new(), Vec::new(), Vec::<u64>::new());
+        for (a, a0, b, b0) in streams.iter().flatten() {
+            a_col.extend(a.iter().map(|t| t.0));
+            a_cf.extend(a.iter().map(|t| t.1));
+            a_off.push(a_col.len() as u32);
+            a_c0.push(*a0);
+            b_col.extend(b.iter().map(|t| t.0));
+            b_cf.extend(b.iter().map(|t| t.1));
+            b_off.push(b_col.len() as u32);
+            b_c0.extend([*b0 as u64, (*b0 >> 64) as u64]);
+        }
+        let mut raw = ptr::null_mut();
+        // SAFETY: offset arrays have one entry more than there are rows; the term arrays have offsets.last() entries; two words per B constant.
+        check(
+            unsafe {
+                ffi::jolt_r1cs_rows_create(streams.len() as u32, domain_size as u32, per.as_ptr(), inputs as u32, a_off.as_ptr(), a_col.as_ptr(), a_cf.as_ptr(), a_c0.as_ptr(),
+                                           b_off.as_ptr(), b_col.as_ptr(), b_cf.as_ptr(), b_c0.as_ptr(), i32::from(zero_on_domain), &mut raw)
+            },
+            ptr::null(),
+        )?;
+        Ok(Self { raw, domain_size, streams: streams.len() as u32, inputs })
+    }
+
+    /// `t1` at the `2D - 1` extended nodes (nodes the system marks as vanishing: zero) against `eq[(t * streams) + s]`.
+    pub fn uniskip_sums(&self, ctx: &Arc<HipContext>, columns: &[&HipInts], eq: &HipTable) -> Result<Vec<Fr>, HipError> {
+        let cols = raw_ints(columns);
+        let mut out = vec![Fr::default(); 2 * self.domain_size - 1];
+        // SAFETY: live handles of one context; `out` holds 2D - 1 elements.
+        check(unsafe { ffi::jolt_r1cs_uniskip_sums_rows(ctx.raw, self.raw, cols.as_ptr(), cols.len(), eq.raw, out.as_mut_ptr().cast()) }, ctx.raw)?;
+        Ok(out)
+    }
+
+    /// The coefficients of `LK(tau_high, .) x t1` (what `UniskipKernel::first_round_poly` returns: `UnivariatePoly::new` of them).
+    pub fn first_round_coefficients(&self, tau_high: Fr, t1: &[Fr]) -> Result<Vec<Fr>, HipError> {
+        debug_assert_eq!(t1.len(), 2 * self.domain_size - 1);
+        let mut out = vec![Fr::default(); 3 * self.domain_size - 2];
+        // SAFETY: array lengths as asserted.
+        check(unsafe { ffi::jolt_host_uniskip_first_round_poly(self.domain_size, (&tau_high as *const Fr).cast(), t1.as_ptr().cast(), out.as_mut_ptr().cast()) }, ptr::null())?;
+        Ok(out)
+    }
+
+    /// The remainder's column weights `[stream][1 + inputs]` at the uni-skip challenge and its scale `LK(tau_high, r0)`: what
+    /// `Mi355xParts::{outer,product}_remainder_weights` compute through a pointer today.
+    pub fn remainder_weights(&self, r0: Fr, tau_high: Fr) -> Result<(Vec<Fr>, Vec<Fr>, Fr), HipError> {
+        let n = self.streams as usize * (1 + self.inputs);
+        let (mut a, mut b, mut scale) = (vec![Fr::default(); n], vec![Fr::default(); n], Fr::default());
+        // SAFETY: `a`, `b` hold streams x (1 + inputs) elements.
+        check(
+            unsafe {
+                ffi::jolt_host_r1cs_rows_remainder_weights(self.raw, (&r0 as *const Fr).cast(), (&tau_high as *const Fr).cast(), a.as_mut_ptr().cast(), b.as_mut_ptr().cast(),
+                                                           (&mut scale as *mut Fr).cast())
+            },
+            ptr::null(),
+        )?;
+        Ok((a, b, scale))
+    }
+}
+
+impl Drop for HipR1csRows {
+    fn drop(&mut self) {
+        // SAFETY: created by jolt_r1cs_rows_create, destroyed once.
+        unsafe { ffi::jolt_r1cs_rows_destroy(self.raw) };
+    }
+}
+
 /// `CycleMajorMatrix` / `AddressMajorMatrix` of RAM read/write checking (`optimized/rw_matrix.rs`, `optimized/ram_read_write.rs:58-330`).
 pub struct HipRwMatrix {
     ctx: Arc<HipContext>,
