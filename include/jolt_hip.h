@@ -35,6 +35,8 @@ extern "C" {
 typedef struct { uint64_t l[4]; } jolt_fr_t;
 typedef struct { uint64_t l[4]; } jolt_fq_t;
 typedef struct { jolt_fq_t x, y, z; } jolt_g1_t;
+typedef struct { jolt_fq_t c0, c1; } jolt_fq2_t;  /* c0 + c1 u, u^2 = -1 == ark_bn254::Fq2 */
+typedef struct { jolt_fq2_t x, y, z; } jolt_g2_t; /* Jacobian on the twist y^2 = x^3 + 3 / (9 + u), identity <=> z == 0 == ark_bn254::G2Projective (dory's ArkG2) */
 
 typedef struct jolt_ctx jolt_ctx;       /* device + stream + scratch                                  */
 typedef struct jolt_table jolt_table;   /* device-resident dense table of Fr (Polynomial<Fr>)         */
@@ -571,8 +573,8 @@ int32_t jolt_dory_commit_rows(jolt_ctx *ctx, const jolt_srs *srs, const jolt_int
 int32_t jolt_dory_commit_onehot(jolt_ctx *ctx, const jolt_srs *srs, const jolt_onehot *source, size_t poly, size_t chunk_width, jolt_g1_t *out);
 
 /* The G1 and Fr work of a Dory opening ahead of the pairing rounds.  Cycle-major placement (TracePolynomialOrder::CycleMajor): grid
- * index k*T + j, dense columns at k = 0, as for the jolt_grid_* entry points below.  What stays on the host is G2 / GT: the tier-2
- * multi-pairing and the reduce-and-fold rounds of dory::prove.
+ * index k*T + j, dense columns at k = 0, as for the jolt_grid_* entry points below.  What stays on the host is the tier-2
+ * multi-pairing and, of the reduce-and-fold rounds of dory::prove, the pairings, GT and the control flow (their group routines: jolt_dory_g1_* / jolt_dory_g2_* below).
  *
  * RlcSource::fold_rows over TraceOpeningPoly (optimized/opening.rs:491-510, multilinear.rs:452-462), cycle-major -- the
  * vector_matrix_product of dory::prove (crates/jolt-dory/src/scheme.rs:612-618), answered from the per-cycle columns without the K x T grid:
@@ -593,6 +595,51 @@ int32_t jolt_dory_combine_hints(jolt_ctx *ctx, const jolt_g1_t *const *hints, co
 /* One row of jolt_dory_combine_hints on the host, out = sum_i scalars[i] * points[i] (scheme.rs:339-356), through the code the device rows run: shared signed-digit
  * plan, per-window walk by descending digit, Horner recombination.  For the CPU suite. */
 int32_t jolt_host_dory_combine_row(const jolt_g1_t *points, const jolt_fr_t *scalars, size_t n, jolt_g1_t *out);
+
+/* The group and field routines of dory::prove's reduce-and-fold rounds: dory's DoryRoutines seam as the reference implements it for both groups,
+ * JoltG1Routines (crates/jolt-dory/src/routines.rs:60-97) and JoltG2Routines (:101-147).  Host pointers in and out, like jolt_dory_combine_hints: the trait works
+ * on host slices and the pairings need the vectors on the host every round.  `vs` / `left` are updated in place.  Results are the reference's group elements; the
+ * Jacobian representative is free, the identity comes back as (1, 1, 0).  Pairings, GT and the control flow of dory::prove stay with the caller.
+ * Every entry refuses with JOLT_ERR_INVALID_ARG: a null pointer with n > 0, a scalar that is not canonical, a point whose coordinates are not canonical or that
+ * is not on its curve.  For G2 that is the twist equation ONLY -- there is NO subgroup check (the twist has cofactor 2q - r); the routines are group-law
+ * identities on the whole twist, so a point outside the order-r subgroup gets the answer the same formulas give on the CPU.  A refused call enqueues nothing,
+ * writes nothing and leaves the context usable.  n = 0 succeeds and writes nothing (the MSM writes the empty sum, the identity).  n <= 2^30. */
+/* DoryRoutines::msm (routines.rs:62-64, :103-105): out = sum_i scalars[i] * bases[i], bases projective */
+int32_t jolt_dory_g1_msm(jolt_ctx *ctx, const jolt_g1_t *bases, const jolt_fr_t *scalars, size_t n, jolt_g1_t *out);
+/* DoryRoutines::fixed_base_vector_scalar_mul (routines.rs:66-72, :107-122): out[i] = scalars[i] * base; an empty input gives an empty output */
+int32_t jolt_dory_g1_fixed_base_mul(jolt_ctx *ctx, const jolt_g1_t *base, const jolt_fr_t *scalars, size_t n, jolt_g1_t *out);
+/* DoryRoutines::fixed_scalar_mul_bases_then_add (routines.rs:74-82, :124-132): vs[i] = vs[i] + scalar * bases[i] */
+int32_t jolt_dory_g1_scale_bases_add(jolt_ctx *ctx, const jolt_g1_t *bases, jolt_g1_t *vs, size_t n, const jolt_fr_t *scalar);
+/* DoryRoutines::fixed_scalar_mul_vs_then_add (routines.rs:84-92, :134-142): vs[i] = scalar * vs[i] + addends[i] */
+int32_t jolt_dory_g1_scale_vs_add(jolt_ctx *ctx, jolt_g1_t *vs, const jolt_g1_t *addends, size_t n, const jolt_fr_t *scalar);
+int32_t jolt_dory_g2_msm(jolt_ctx *ctx, const jolt_g2_t *bases, const jolt_fr_t *scalars, size_t n, jolt_g2_t *out);
+int32_t jolt_dory_g2_fixed_base_mul(jolt_ctx *ctx, const jolt_g2_t *base, const jolt_fr_t *scalars, size_t n, jolt_g2_t *out);
+int32_t jolt_dory_g2_scale_bases_add(jolt_ctx *ctx, const jolt_g2_t *bases, jolt_g2_t *vs, size_t n, const jolt_fr_t *scalar);
+int32_t jolt_dory_g2_scale_vs_add(jolt_ctx *ctx, jolt_g2_t *vs, const jolt_g2_t *addends, size_t n, const jolt_fr_t *scalar);
+/* DoryRoutines::fold_field_vectors (routines.rs:94-96, :144-146; jolt_dory_routines.rs:10-18): left[i] = left[i] * scalar + right[i] in Fr, the same function for
+ * both groups; every entry of left and right must be canonical too */
+int32_t jolt_dory_fold_field_vectors(jolt_ctx *ctx, jolt_fr_t *left, const jolt_fr_t *right, size_t n, const jolt_fr_t *scalar);
+/* Measurement aid of tools/bench_dory_routines.py: out_ms (may be NULL) receives the wall milliseconds of the phases of the last routine call made while timing was
+ * on -- argument checks, host -> device, kernels, device -> host -- then timing is switched on or off.  While on, a call drains the stream between its phases. */
+int32_t jolt_dory_routines_timing(jolt_ctx *ctx, int32_t enable, double *out_ms /* 4 */);
+/* Fq2 and G2 on the host, as the kernels compute them (fq2.hip.h, g2.hip.h), for the CPU suite.  jolt_host_fq2_op refuses an operand that is not canonical
+ * (b is ignored for SQR and NEG and may be NULL); the G2 functions take any coordinates, jolt_host_g2_is_on_curve is the check the entry points above apply. */
+enum { JOLT_FQ2_ADD = 0, JOLT_FQ2_SUB = 1, JOLT_FQ2_MUL = 2, JOLT_FQ2_SQR = 3, JOLT_FQ2_NEG = 4 };
+int32_t jolt_host_fq2_op(int32_t op, const jolt_fq2_t *a, const jolt_fq2_t *b, jolt_fq2_t *out);
+int32_t jolt_host_g2_add(const jolt_g2_t *p, const jolt_g2_t *q, jolt_g2_t *out);
+int32_t jolt_host_g2_double(const jolt_g2_t *p, jolt_g2_t *out);
+int32_t jolt_host_g2_neg(const jolt_g2_t *p, jolt_g2_t *out);
+int32_t jolt_host_g2_eq(const jolt_g2_t *p, const jolt_g2_t *q, int32_t *equal);
+int32_t jolt_host_g2_is_on_curve(const jolt_g2_t *p, int32_t *on_curve);
+int32_t jolt_host_g2_scalar_mul(const jolt_g2_t *p, const jolt_fr_t *scalar, jolt_g2_t *out); /* plain MSB-first double-and-add */
+/* One element of the routines through the code the device lanes run: out = addend + scalar * scaled (both shared-scalar routines: the non-adjacent form of the
+ * scalar and its walk), out = scalar * base (the fixed-base table and window walk), out = scalar * base (one MSM term).  Same refusals as the device entries. */
+int32_t jolt_host_dory_g1_scale_add_one(const jolt_g1_t *scaled, const jolt_g1_t *addend, const jolt_fr_t *scalar, jolt_g1_t *out);
+int32_t jolt_host_dory_g2_scale_add_one(const jolt_g2_t *scaled, const jolt_g2_t *addend, const jolt_fr_t *scalar, jolt_g2_t *out);
+int32_t jolt_host_dory_g1_fixed_base_one(const jolt_g1_t *base, const jolt_fr_t *scalar, jolt_g1_t *out);
+int32_t jolt_host_dory_g2_fixed_base_one(const jolt_g2_t *base, const jolt_fr_t *scalar, jolt_g2_t *out);
+int32_t jolt_host_dory_g1_msm_term(const jolt_g1_t *base, const jolt_fr_t *scalar, jolt_g1_t *out);
+int32_t jolt_host_dory_g2_msm_term(const jolt_g2_t *base, const jolt_fr_t *scalar, jolt_g2_t *out);
 
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)

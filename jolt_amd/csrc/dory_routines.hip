@@ -1,0 +1,587 @@
+// jolt_amd/csrc/dory_routines.hip -- the group and field routines dory::prove calls in every reduce-and-fold round, for G1 and G2.
+//
+// Replaces the two impls of dory's DoryRoutines seam in crates/jolt-dory/src/routines.rs (JoltG1Routines :60-97, JoltG2Routines :101-147;
+// the field fold written out in crates/jolt-prover-legacy/src/poly/commitment/dory/jolt_dory_routines.rs:10-18):
+//   msm(bases, scalars)                              -> jolt_dory_g{1,2}_msm            sum_i scalars[i] * bases[i]
+//   fixed_base_vector_scalar_mul(base, scalars)      -> jolt_dory_g{1,2}_fixed_base_mul out[i] = scalars[i] * base
+//   fixed_scalar_mul_bases_then_add(bases, vs, s)    -> jolt_dory_g{1,2}_scale_bases_add vs[i] += s * bases[i]
+//   fixed_scalar_mul_vs_then_add(vs, addends, s)     -> jolt_dory_g{1,2}_scale_vs_add   vs[i] = s * vs[i] + addends[i]
+//   fold_field_vectors(left, right, s)               -> jolt_dory_fold_field_vectors    left[i] = left[i] * s + right[i]
+// Pairings, GT and the control flow of dory::prove stay with the caller.
+//
+// One lane per element.  In the two per-round vector operations every element is multiplied by the SAME scalar: the host recodes it once into
+// non-adjacent form (digits in {-1, 0, 1}, no two adjacent non-zero), and every lane walks that one sequence of doublings and additions -- control
+// flow is uniform over the wavefront, only the special cases of the group law (identity, P + P, P - P) diverge.  At most 255 doublings and 128
+// additions per element (85 on average), no table.  The per-element-scalar routines cannot share a sequence: the fixed-base one takes k * base
+// (k = 0..8, signed 4-bit windows) from one shared table by index, the MSM is one double-and-add per term followed by a tree of additions.
+// Integer VALU work, no MFMA; the chains are ~254 dependent doublings long, so these kernels are latency bound (docs/kernels.md).
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "ctx.hpp"
+#include "g1.hip.h"
+#include "g2.hip.h"
+#include "poly_kernels.hip.h"
+
+using namespace jolt;
+
+namespace {
+
+// The two groups behind one set of kernels: G1 through the functions of g1.hip.h as they stand, G2 through g2.hip.h.
+struct G1Ops {
+    using Pt = G1Jac;
+    using Abi = jolt_g1_t;
+    static JOLT_HD Pt identity() { return g1_identity(); }
+    static JOLT_HD bool is_identity(const Pt& p) { return g1_is_identity(p); }
+    static JOLT_HD Pt dbl(const Pt& p) { return g1_double(p); }
+    static JOLT_HD Pt add(const Pt& p, const Pt& q) { return g1_add(p, q); }
+    static JOLT_HD Pt neg(const Pt& p) { return g1_neg(p); }
+    static JOLT_HD bool on_curve(const Pt& p) { return g1_is_on_curve(p); }
+};
+struct G2Ops {
+    using Pt = G2Jac;
+    using Abi = jolt_g2_t;
+    static JOLT_HD Pt identity() { return g2_identity(); }
+    static JOLT_HD bool is_identity(const Pt& p) { return g2_is_identity(p); }
+    static JOLT_HD Pt dbl(const Pt& p) { return g2_double(p); }
+    static JOLT_HD Pt add(const Pt& p, const Pt& q) { return g2_add(p, q); }
+    static JOLT_HD Pt neg(const Pt& p) { return g2_neg(p); }
+    static JOLT_HD bool on_curve(const Pt& p) { return g2_is_on_curve(p); }
+};
+static_assert(sizeof(jolt_g2_t) == sizeof(G2Jac) && sizeof(jolt_fq2_t) == sizeof(Fq2), "G2 ABI layouts");
+
+template <class O>
+JOLT_HD typename O::Pt normalised(const typename O::Pt& p) { return O::is_identity(p) ? O::identity() : p; }
+
+// ---- the shared scalar: non-adjacent form, two bits per digit (0: zero, 1: +1, 3: -1), digit i at bits 2 * (i & 15) of w[i >> 4] ----
+constexpr int kNafMax = 256;  // s < r < 2^254: the form has at most 255 digits
+struct NafPlan {
+    uint32_t w[kNafMax / 16];
+    int32_t len;  // digits in use; the top one is non-zero (0 for s = 0)
+};
+JOLT_HD int naf_digit(const NafPlan& plan, int i) {
+    const uint32_t d = (plan.w[i >> 4] >> (2 * (i & 15))) & 3u;
+    return d == 3u ? -1 : (int)d;
+}
+// scalar in Montgomery form; false: not canonical
+bool naf_plan(const jolt_fr_t* scalar, NafPlan* plan) {
+    const Fr m = fr_from_abi(scalar);
+    if (!fr_is_canonical(m)) return false;
+    Fr k = from_mont(m);
+    std::memset(plan, 0, sizeof(*plan));
+    int i = 0, len = 0;
+    while (!k.is_zero()) {
+        uint32_t d = 0;
+        if (k.l[0] & 1u) {
+            if ((k.l[0] & 3u) == 1u) {  // digit +1: clear the low bit
+                d = 1u;
+                k.l[0] &= ~1u;
+            } else {  // digit -1: k + 1 (k < 2^254, no carry out of the top limb)
+                d = 3u;
+                uint32_t c = 1;
+                for (int j = 0; j < 8 && c; ++j) {
+                    k.l[j] += c;
+                    c = k.l[j] == 0 ? 1u : 0u;
+                }
+            }
+            plan->w[i >> 4] |= d << (2 * (i & 15));
+            len = i + 1;
+        }
+        for (int j = 0; j < 8; ++j) k.l[j] = (k.l[j] >> 1) | (j + 1 < 8 ? k.l[j + 1] << 31 : 0u);
+        ++i;
+    }
+    plan->len = len;
+    return true;
+}
+
+// s * p along the plan: what every lane of k_dory_scale_add runs, and the host functions of the CPU suite
+template <class O>
+JOLT_HD typename O::Pt naf_mul(const NafPlan& plan, const typename O::Pt& p) {
+    typename O::Pt acc = O::identity();
+#pragma unroll 1
+    for (int i = plan.len - 1; i >= 0; --i) {
+        acc = O::dbl(acc);
+        const int d = naf_digit(plan, i);
+        if (d != 0) {
+            typename O::Pt q = p;
+            if (d < 0) q.y = neg(p.y);
+            acc = O::add(acc, q);
+        }
+    }
+    return acc;
+}
+// one element of both shared-scalar routines: addend + s * scaled, the identity as (1, 1, 0)
+template <class O>
+JOLT_HD typename O::Pt scale_add_one(const NafPlan& plan, const typename O::Pt& scaled, const typename O::Pt& addend) {
+    return normalised<O>(O::add(naf_mul<O>(plan, scaled), addend));
+}
+
+// ---- per-element scalars over one base: signed 4-bit windows, table[k] = k * base for k = 0..8 ----
+constexpr int kFixedWindow = 4;
+constexpr int kFixedWindows = 64;  // 256 bits; digits in [-8, 7] (fixed_mul_one)
+constexpr int kFixedTable = (1 << (kFixedWindow - 1)) + 1;
+template <class O>
+void fixed_table(const typename O::Pt& base, typename O::Pt* table) {
+    table[0] = O::identity();
+    table[1] = base;
+    for (int k = 2; k < kFixedTable; ++k) table[k] = (k & 1) ? O::add(table[k - 1], base) : O::dbl(table[k / 2]);
+}
+// k << S over the eight limbs (S < 32): the scalar walks are MSB-first shifts of the whole integer, so no limb is ever indexed by a loop variable
+template <int S>
+JOLT_HD void shl256(Fr& k) {
+#pragma unroll
+    for (int j = 7; j >= 1; --j) k.l[j] = (k.l[j] << S) | (k.l[j - 1] >> (32 - S));
+    k.l[0] <<= S;
+}
+// scalar * base.  Signed digits without a carry chain: k' = k + 0x88..8 (8 in each of the 64 nibbles; k < 2^254, so k' < 2^256), digit w = nibble w of k' - 8 in [-8, 7],
+// since sum_w 8 * 16^w is exactly what was added.  The table entry is taken by index (digits differ from lane to lane), its sign by a select on y.
+template <class O>
+JOLT_HD typename O::Pt fixed_mul_one(const typename O::Pt* __restrict__ table, const Fr& scalar_mont) {
+    Fr k = from_mont(scalar_mont);
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) k.l[j] = __builtin_addc(k.l[j], 0x88888888u, c, &c);
+    typename O::Pt acc = O::identity();
+#pragma unroll 1
+    for (int w = kFixedWindows - 1; w >= 0; --w) {
+#pragma unroll 1
+        for (int j = 0; j < kFixedWindow; ++j) acc = O::dbl(acc);
+        const uint32_t nib = k.l[7] >> 28;
+        shl256<kFixedWindow>(k);
+        const bool negative = nib < 8u;
+        const uint32_t mag = negative ? 8u - nib : nib - 8u;
+        typename O::Pt t = table[mag];
+        if (negative) t = O::neg(t);
+        acc = O::add(acc, t);
+    }
+    return normalised<O>(acc);
+}
+
+// one term of the MSM: plain MSB-first double-and-add over the canonical scalar (the digits differ from lane to lane)
+template <class O>
+JOLT_HD typename O::Pt term_mul_one(const typename O::Pt& p, const Fr& scalar_mont) {
+    Fr k = from_mont(scalar_mont);
+    shl256<2>(k);  // r < 2^254: bit 253 to the top
+    typename O::Pt acc = O::identity();
+#pragma unroll 1
+    for (int i = 253; i >= 0; --i) {
+        acc = O::dbl(acc);
+        const bool bit = (k.l[7] >> 31) != 0;
+        shl256<1>(k);
+        if (bit) acc = O::add(acc, p);
+    }
+    return acc;
+}
+
+// ---- kernels: one wavefront per workgroup, one wavefront per SIMD (a G2 addition holds two 48-register points and its temporaries) ----
+constexpr int kLanes = 64;
+
+// out[i] = addend[i] + s * scaled[i], as scale_add_one; out may alias either input (each lane reads its own element before it writes it)
+template <class O>
+__global__ __launch_bounds__(kLanes) void k_dory_scale_add(NafPlan plan, const typename O::Pt* scaled, const typename O::Pt* addend, typename O::Pt* out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
+    if (i >= n) return;
+    const typename O::Pt acc = naf_mul<O>(plan, scaled[i]);
+    out[i] = normalised<O>(O::add(acc, addend[i]));  // the addend is loaded after the walk: 48 registers of a G2 point that the loop does not have to carry
+}
+template <class O>
+__global__ __launch_bounds__(kLanes) void k_dory_fixed_base(const typename O::Pt* __restrict__ table, const Fr* __restrict__ scalars, typename O::Pt* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
+    if (i >= n) return;
+    out[i] = fixed_mul_one<O>(table, scalars[i]);
+}
+template <class O>
+__global__ __launch_bounds__(kLanes) void k_dory_msm_terms(const typename O::Pt* __restrict__ bases, const Fr* __restrict__ scalars, typename O::Pt* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
+    if (i >= n) return;
+    out[i] = term_mul_one<O>(bases[i], scalars[i]);
+}
+// one level of the addition tree: terms[i] += terms[i + half] for i + half < m
+template <class O>
+__global__ __launch_bounds__(kLanes) void k_dory_tree_level(typename O::Pt* terms, size_t half, size_t m) {
+    const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
+    if (i >= half || i + half >= m) return;
+    terms[i] = O::add(terms[i], terms[i + half]);
+}
+__global__ __launch_bounds__(256) void k_dory_fold_field(Fr* __restrict__ left, const Fr* __restrict__ right, Fr s, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    st_fr(left + i, add(mul(ld_fr(left + i), s), ld_fr(right + i)));
+}
+
+// ---- host side of the entry points ----
+int32_t hip_fail(jolt_ctx* ctx, const char* what, hipError_t e) {
+    ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? JOLT_ERR_OOM : JOLT_ERR_HIP;
+}
+
+// The argument checks run on the host before anything is enqueued (a refused call enqueues nothing).  A G2 on-curve check costs ~2 us of host time and a round holds
+// 2^14 ... 2^16 points, which is more than the kernels take: long vectors are checked by up to 16 host threads.
+template <class Ok>
+bool parallel_all(size_t n, Ok&& ok_range) {
+    const size_t hw = std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
+    const size_t parts = std::min(hw, n / 1024);
+    if (parts <= 1) return ok_range((size_t)0, n);
+    std::vector<char> ok(parts, 1);
+    std::vector<std::thread> workers;
+    size_t started = 0;
+    try {
+        for (; started + 1 < parts; ++started) workers.emplace_back([&ok, &ok_range, started, n, parts] { ok[started] = ok_range(n * started / parts, n * (started + 1) / parts) ? 1 : 0; });
+    } catch (...) {  // no more threads to be had: the calling thread takes the rest
+    }
+    bool all = ok_range(n * started / parts, n);
+    for (std::thread& w : workers) w.join();
+    for (size_t t = 0; t < started; ++t) all = all && ok[t];
+    return all;
+}
+template <class O>
+bool all_on_curve(const typename O::Abi* pts, size_t n) {
+    return parallel_all(n, [pts](size_t lo, size_t hi) {
+        for (size_t i = lo; i < hi; ++i) {
+            typename O::Pt p;
+            std::memcpy(&p, &pts[i], sizeof(p));
+            if (!O::on_curve(p)) return false;
+        }
+        return true;
+    });
+}
+bool all_canonical(const jolt_fr_t* s, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!fr_is_canonical(fr_from_abi(&s[i]))) return false;
+    return true;
+}
+
+// Phase clock of jolt_dory_routines_timing: when it is on, the stream is drained between the phases of a call so that each gets its own wall time.
+struct Phases {
+    jolt_ctx* ctx;
+    std::chrono::steady_clock::time_point t0;
+    explicit Phases(jolt_ctx* c) : ctx(c), t0(std::chrono::steady_clock::now()) {
+        if (c->dory_timing)
+            for (double& v : c->dory_ms) v = 0.0;
+    }
+    hipError_t mark(int phase) {  // closes `phase`: 0 checks, 1 host -> device, 2 kernels, 3 device -> host
+        if (!ctx->dory_timing) return hipSuccess;
+        const hipError_t e = phase ? hipStreamSynchronize(ctx->stream) : hipSuccess;
+        const auto t1 = std::chrono::steady_clock::now();
+        ctx->dory_ms[phase] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+        return e;
+    }
+};
+
+struct DevBufs {  // pool blocks of one call, returned on every path
+    jolt_ctx* ctx;
+    std::vector<void*> blocks;
+    explicit DevBufs(jolt_ctx* c) : ctx(c) {}
+    ~DevBufs() {
+        for (void* b : blocks) jolt_internal_dev_free(ctx, b);
+    }
+    template <class T>
+    int32_t take(size_t count, T** out) {
+        void* p = nullptr;
+        const int32_t rc = jolt_internal_dev_alloc(ctx, std::max<size_t>(count, 1) * sizeof(T), &p);
+        if (rc == JOLT_OK) blocks.push_back(p);
+        *out = (T*)p;
+        return rc;
+    }
+};
+
+unsigned lanes_grid(size_t n) { return (unsigned)((n + kLanes - 1) / kLanes); }
+constexpr size_t kMaxElements = (size_t)1 << 30;  // keeps every grid below 2^31 workgroups; a Dory round holds 2^nu <= 2^20 points
+
+// vs[i] = addend + s * scaled with (scaled, addend) = (other, vs) [bases_then_add] or (vs, other) [vs_then_add]
+template <class O>
+int32_t scale_add(jolt_ctx* ctx, typename O::Abi* vs, const typename O::Abi* other, size_t n, const jolt_fr_t* scalar, bool scale_vs, const char* what) {
+    if (!ctx || !scalar || (n && (!vs || !other))) return JOLT_ERR_INVALID_ARG;
+    if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
+    Phases ph(ctx);
+    NafPlan plan;
+    JOLT_REQUIRE(ctx, naf_plan(scalar, &plan), "scalar is not a canonical Fr");
+    JOLT_REQUIRE(ctx, all_on_curve<O>(vs, n) && all_on_curve<O>(other, n), "a point is not on its curve or not canonical");
+    if (n == 0) return JOLT_OK;
+    (void)ph.mark(0);
+    using Pt = typename O::Pt;
+    hipStream_t st = ctx->stream;
+    DevBufs bufs(ctx);
+    Pt *d_vs = nullptr, *d_other = nullptr;
+    JOLT_TRY(bufs.take(n, &d_vs));
+    JOLT_TRY(bufs.take(n, &d_other));
+    hipError_t e = hipMemcpyAsync(d_vs, vs, n * sizeof(Pt), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_other, other, n * sizeof(Pt), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = ph.mark(1);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_dory_scale_add<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, plan, (const Pt*)(scale_vs ? d_vs : d_other), (const Pt*)(scale_vs ? d_other : d_vs), d_vs, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = ph.mark(2);
+    if (e == hipSuccess) e = hipMemcpyAsync(vs, d_vs, n * sizeof(Pt), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);  // the caller's arrays are read and written until here
+    if (e == hipSuccess) e = e2;
+    (void)ph.mark(3);
+    if (e != hipSuccess) return hip_fail(ctx, what, e);
+    return JOLT_OK;
+}
+
+template <class O>
+int32_t fixed_base(jolt_ctx* ctx, const typename O::Abi* base, const jolt_fr_t* scalars, size_t n, typename O::Abi* out, const char* what) {
+    if (!ctx || !base || (n && (!scalars || !out))) return JOLT_ERR_INVALID_ARG;
+    if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
+    Phases ph(ctx);
+    using Pt = typename O::Pt;
+    JOLT_REQUIRE(ctx, all_on_curve<O>(base, 1), "a point is not on its curve or not canonical");
+    JOLT_REQUIRE(ctx, all_canonical(scalars, n), "scalar is not a canonical Fr");
+    if (n == 0) return JOLT_OK;  // an empty input gives an empty output (routines.rs:67-69)
+    Pt b, table[kFixedTable];
+    std::memcpy(&b, base, sizeof(b));
+    fixed_table<O>(b, table);
+    (void)ph.mark(0);
+    hipStream_t st = ctx->stream;
+    DevBufs bufs(ctx);
+    Pt *d_table = nullptr, *d_out = nullptr;
+    Fr* d_scalars = nullptr;
+    JOLT_TRY(bufs.take(kFixedTable, &d_table));
+    JOLT_TRY(bufs.take(n, &d_out));
+    JOLT_TRY(bufs.take(n, &d_scalars));
+    hipError_t e = hipMemcpyAsync(d_table, table, sizeof(table), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_scalars, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = ph.mark(1);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_dory_fixed_base<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, (const Pt*)d_table, (const Fr*)d_scalars, d_out, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = ph.mark(2);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * sizeof(Pt), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);  // `table` (on this stack) and the caller's arrays are read until here
+    if (e == hipSuccess) e = e2;
+    (void)ph.mark(3);
+    if (e != hipSuccess) return hip_fail(ctx, what, e);
+    return JOLT_OK;
+}
+
+template <class O>
+int32_t msm(jolt_ctx* ctx, const typename O::Abi* bases, const jolt_fr_t* scalars, size_t n, typename O::Abi* out, const char* what) {
+    if (!ctx || !out || (n && (!bases || !scalars))) return JOLT_ERR_INVALID_ARG;
+    if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
+    Phases ph(ctx);
+    using Pt = typename O::Pt;
+    JOLT_REQUIRE(ctx, all_canonical(scalars, n), "scalar is not a canonical Fr");
+    JOLT_REQUIRE(ctx, all_on_curve<O>(bases, n), "a point is not on its curve or not canonical");
+    if (n == 0) {  // the empty sum
+        const Pt id = O::identity();
+        std::memcpy(out, &id, sizeof(id));
+        return JOLT_OK;
+    }
+    (void)ph.mark(0);
+    hipStream_t st = ctx->stream;
+    DevBufs bufs(ctx);
+    Pt *d_bases = nullptr, *d_terms = nullptr;
+    Fr* d_scalars = nullptr;
+    JOLT_TRY(bufs.take(n, &d_bases));
+    JOLT_TRY(bufs.take(n, &d_terms));
+    JOLT_TRY(bufs.take(n, &d_scalars));
+    hipError_t e = hipMemcpyAsync(d_bases, bases, n * sizeof(Pt), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_scalars, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = ph.mark(1);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_dory_msm_terms<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, (const Pt*)d_bases, (const Fr*)d_scalars, d_terms, n);
+        for (size_t m = n; m > 1;) {
+            const size_t half = (m + 1) / 2;
+            hipLaunchKernelGGL(k_dory_tree_level<O>, dim3(lanes_grid(half)), dim3(kLanes), 0, st, d_terms, half, m);
+            m = half;
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = ph.mark(2);
+    Pt sum = O::identity();
+    if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_terms, sizeof(Pt), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    (void)ph.mark(3);
+    if (e != hipSuccess) return hip_fail(ctx, what, e);
+    sum = normalised<O>(sum);
+    std::memcpy(out, &sum, sizeof(sum));
+    return JOLT_OK;
+}
+
+template <class Pt>
+Pt pt_from_abi(const void* p) {
+    Pt r;
+    std::memcpy(&r, p, sizeof(r));
+    return r;
+}
+
+template <class O>
+int32_t host_scale_add_one(const typename O::Abi* scaled, const typename O::Abi* addend, const jolt_fr_t* scalar, typename O::Abi* out) {
+    if (!scaled || !addend || !scalar || !out) return JOLT_ERR_INVALID_ARG;
+    NafPlan plan;
+    if (!naf_plan(scalar, &plan)) return JOLT_ERR_INVALID_ARG;
+    const auto p = pt_from_abi<typename O::Pt>(scaled), a = pt_from_abi<typename O::Pt>(addend);
+    if (!O::on_curve(p) || !O::on_curve(a)) return JOLT_ERR_INVALID_ARG;
+    const typename O::Pt r = scale_add_one<O>(plan, p, a);
+    std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+template <class O>
+int32_t host_fixed_base_one(const typename O::Abi* base, const jolt_fr_t* scalar, typename O::Abi* out) {
+    if (!base || !scalar || !out) return JOLT_ERR_INVALID_ARG;
+    const Fr s = fr_from_abi(scalar);
+    const auto b = pt_from_abi<typename O::Pt>(base);
+    if (!fr_is_canonical(s) || !O::on_curve(b)) return JOLT_ERR_INVALID_ARG;
+    typename O::Pt table[kFixedTable];
+    fixed_table<O>(b, table);
+    const typename O::Pt r = fixed_mul_one<O>(table, s);
+    std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+template <class O>
+int32_t host_msm_term(const typename O::Abi* base, const jolt_fr_t* scalar, typename O::Abi* out) {
+    if (!base || !scalar || !out) return JOLT_ERR_INVALID_ARG;
+    const Fr s = fr_from_abi(scalar);
+    const auto b = pt_from_abi<typename O::Pt>(base);
+    if (!fr_is_canonical(s) || !O::on_curve(b)) return JOLT_ERR_INVALID_ARG;
+    const typename O::Pt r = normalised<O>(term_mul_one<O>(b, s));
+    std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t jolt_dory_g1_msm(jolt_ctx* ctx, const jolt_g1_t* bases, const jolt_fr_t* scalars, size_t n, jolt_g1_t* out) {
+    return msm<G1Ops>(ctx, bases, scalars, n, out, "dory g1 msm");
+}
+extern "C" int32_t jolt_dory_g1_fixed_base_mul(jolt_ctx* ctx, const jolt_g1_t* base, const jolt_fr_t* scalars, size_t n, jolt_g1_t* out) {
+    return fixed_base<G1Ops>(ctx, base, scalars, n, out, "dory g1 fixed base");
+}
+extern "C" int32_t jolt_dory_g1_scale_bases_add(jolt_ctx* ctx, const jolt_g1_t* bases, jolt_g1_t* vs, size_t n, const jolt_fr_t* scalar) {
+    return scale_add<G1Ops>(ctx, vs, bases, n, scalar, false, "dory g1 scale bases");
+}
+extern "C" int32_t jolt_dory_g1_scale_vs_add(jolt_ctx* ctx, jolt_g1_t* vs, const jolt_g1_t* addends, size_t n, const jolt_fr_t* scalar) {
+    return scale_add<G1Ops>(ctx, vs, addends, n, scalar, true, "dory g1 scale vs");
+}
+extern "C" int32_t jolt_dory_g2_msm(jolt_ctx* ctx, const jolt_g2_t* bases, const jolt_fr_t* scalars, size_t n, jolt_g2_t* out) {
+    return msm<G2Ops>(ctx, bases, scalars, n, out, "dory g2 msm");
+}
+extern "C" int32_t jolt_dory_g2_fixed_base_mul(jolt_ctx* ctx, const jolt_g2_t* base, const jolt_fr_t* scalars, size_t n, jolt_g2_t* out) {
+    return fixed_base<G2Ops>(ctx, base, scalars, n, out, "dory g2 fixed base");
+}
+extern "C" int32_t jolt_dory_g2_scale_bases_add(jolt_ctx* ctx, const jolt_g2_t* bases, jolt_g2_t* vs, size_t n, const jolt_fr_t* scalar) {
+    return scale_add<G2Ops>(ctx, vs, bases, n, scalar, false, "dory g2 scale bases");
+}
+extern "C" int32_t jolt_dory_g2_scale_vs_add(jolt_ctx* ctx, jolt_g2_t* vs, const jolt_g2_t* addends, size_t n, const jolt_fr_t* scalar) {
+    return scale_add<G2Ops>(ctx, vs, addends, n, scalar, true, "dory g2 scale vs");
+}
+
+extern "C" int32_t jolt_dory_fold_field_vectors(jolt_ctx* ctx, jolt_fr_t* left, const jolt_fr_t* right, size_t n, const jolt_fr_t* scalar) {
+    if (!ctx || !scalar || (n && (!left || !right))) return JOLT_ERR_INVALID_ARG;
+    if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
+    Phases ph(ctx);
+    const Fr s = fr_from_abi(scalar);
+    JOLT_REQUIRE(ctx, fr_is_canonical(s) && all_canonical(left, n) && all_canonical(right, n), "scalar is not a canonical Fr");
+    if (n == 0) return JOLT_OK;
+    (void)ph.mark(0);
+    hipStream_t st = ctx->stream;
+    DevBufs bufs(ctx);
+    Fr *d_left = nullptr, *d_right = nullptr;
+    JOLT_TRY(bufs.take(n, &d_left));
+    JOLT_TRY(bufs.take(n, &d_right));
+    hipError_t e = hipMemcpyAsync(d_left, left, n * sizeof(Fr), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_right, right, n * sizeof(Fr), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = ph.mark(1);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_dory_fold_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_left, (const Fr*)d_right, s, n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = ph.mark(2);
+    if (e == hipSuccess) e = hipMemcpyAsync(left, d_left, n * sizeof(Fr), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    (void)ph.mark(3);
+    if (e != hipSuccess) return hip_fail(ctx, "dory field fold", e);
+    return JOLT_OK;
+}
+
+extern "C" int32_t jolt_dory_routines_timing(jolt_ctx* ctx, int32_t enable, double* out_ms) {
+    if (!ctx) return JOLT_ERR_INVALID_ARG;
+    if (out_ms)
+        for (int k = 0; k < 4; ++k) out_ms[k] = ctx->dory_ms[k];
+    ctx->dory_timing = enable != 0;
+    return JOLT_OK;
+}
+
+// ---- host functions for the CPU suite: Fq2 and G2 as the kernels compute them, and single elements of the routines through the lanes' code ----
+extern "C" int32_t jolt_host_fq2_op(int32_t op, const jolt_fq2_t* a, const jolt_fq2_t* b, jolt_fq2_t* out) {
+    if (!a || !out || (op <= JOLT_FQ2_MUL && !b)) return JOLT_ERR_INVALID_ARG;
+    const Fq2 x = pt_from_abi<Fq2>(a);
+    const Fq2 y = op <= JOLT_FQ2_MUL ? pt_from_abi<Fq2>(b) : Fq2::zero();
+    if (!fq2_is_canonical(x) || !fq2_is_canonical(y)) return JOLT_ERR_INVALID_ARG;
+    Fq2 r;
+    switch (op) {
+        case JOLT_FQ2_ADD: r = add(x, y); break;
+        case JOLT_FQ2_SUB: r = sub(x, y); break;
+        case JOLT_FQ2_MUL: r = mul(x, y); break;
+        case JOLT_FQ2_SQR: r = sqr(x); break;
+        case JOLT_FQ2_NEG: r = neg(x); break;
+        default: return JOLT_ERR_INVALID_ARG;
+    }
+    std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_g2_add(const jolt_g2_t* p, const jolt_g2_t* q, jolt_g2_t* out) {
+    if (!p || !q || !out) return JOLT_ERR_INVALID_ARG;
+    const G2Jac r = g2_add(pt_from_abi<G2Jac>(p), pt_from_abi<G2Jac>(q));
+    std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_g2_double(const jolt_g2_t* p, jolt_g2_t* out) {
+    if (!p || !out) return JOLT_ERR_INVALID_ARG;
+    const G2Jac r = g2_double(pt_from_abi<G2Jac>(p));
+    std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_g2_neg(const jolt_g2_t* p, jolt_g2_t* out) {
+    if (!p || !out) return JOLT_ERR_INVALID_ARG;
+    const G2Jac r = g2_neg(pt_from_abi<G2Jac>(p));
+    std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_g2_eq(const jolt_g2_t* p, const jolt_g2_t* q, int32_t* equal) {
+    if (!p || !q || !equal) return JOLT_ERR_INVALID_ARG;
+    *equal = g2_eq(pt_from_abi<G2Jac>(p), pt_from_abi<G2Jac>(q)) ? 1 : 0;
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_g2_is_on_curve(const jolt_g2_t* p, int32_t* on_curve) {
+    if (!p || !on_curve) return JOLT_ERR_INVALID_ARG;
+    *on_curve = g2_is_on_curve(pt_from_abi<G2Jac>(p)) ? 1 : 0;
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_g2_scalar_mul(const jolt_g2_t* p, const jolt_fr_t* scalar, jolt_g2_t* out) {
+    if (!p || !scalar || !out) return JOLT_ERR_INVALID_ARG;
+    const Fr s = fr_from_abi(scalar);
+    if (!fr_is_canonical(s)) return JOLT_ERR_INVALID_ARG;
+    const Fr k = from_mont(s);
+    const G2Jac r = normalised<G2Ops>(g2_mul_canonical(pt_from_abi<G2Jac>(p), k.l));
+    std::memcpy(out, &r, sizeof(r));
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_dory_g1_scale_add_one(const jolt_g1_t* scaled, const jolt_g1_t* addend, const jolt_fr_t* scalar, jolt_g1_t* out) {
+    return host_scale_add_one<G1Ops>(scaled, addend, scalar, out);
+}
+extern "C" int32_t jolt_host_dory_g2_scale_add_one(const jolt_g2_t* scaled, const jolt_g2_t* addend, const jolt_fr_t* scalar, jolt_g2_t* out) {
+    return host_scale_add_one<G2Ops>(scaled, addend, scalar, out);
+}
+extern "C" int32_t jolt_host_dory_g1_fixed_base_one(const jolt_g1_t* base, const jolt_fr_t* scalar, jolt_g1_t* out) {
+    return host_fixed_base_one<G1Ops>(base, scalar, out);
+}
+extern "C" int32_t jolt_host_dory_g2_fixed_base_one(const jolt_g2_t* base, const jolt_fr_t* scalar, jolt_g2_t* out) {
+    return host_fixed_base_one<G2Ops>(base, scalar, out);
+}
+extern "C" int32_t jolt_host_dory_g1_msm_term(const jolt_g1_t* base, const jolt_fr_t* scalar, jolt_g1_t* out) {
+    return host_msm_term<G1Ops>(base, scalar, out);
+}
+extern "C" int32_t jolt_host_dory_g2_msm_term(const jolt_g2_t* base, const jolt_fr_t* scalar, jolt_g2_t* out) {
+    return host_msm_term<G2Ops>(base, scalar, out);
+}

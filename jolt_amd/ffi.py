@@ -1294,6 +1294,150 @@ def host_dory_combine_row(points, scalars):
     return out[0]
 
 
+# ---- the group and field routines of dory::prove's reduce-and-fold rounds (dory_routines.hip): DoryRoutines<ArkG1> / DoryRoutines<ArkG2>
+def g2_array(n):
+    """G2 points: (n, 24) uint64 -- Jacobian over Fq2, x.c0, x.c1, y.c0, y.c1, z.c0, z.c1 (ark_bn254::G2Projective)"""
+    return np.zeros((n, 24), dtype=np.uint64)
+
+
+_DORY_GROUPS = {"g1": 12, "g2": 24}
+
+
+def _dory_pts(group, a):
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, _DORY_GROUPS[group])
+
+
+def _dory_msm(self, group, bases, scalars):
+    """DoryRoutines::msm: sum_i scalars[i] * bases[i] over projective bases; one point"""
+    b = _dory_pts(group, bases)
+    sc = fr(scalars).reshape(-1, 4)
+    if b.shape[0] != sc.shape[0]:
+        raise ValueError("msm: bases and scalars differ in length")
+    out = np.zeros(_DORY_GROUPS[group], dtype=np.uint64)
+    name = f"jolt_dory_{group}_msm"
+    _ck(getattr(lib(), name)(self.h, _p(b) if b.shape[0] else None, _p(sc) if b.shape[0] else None, C.c_size_t(b.shape[0]), _p(out)), name, self)
+    return out
+
+
+def _dory_fixed_base_mul(self, group, base, scalars):
+    """DoryRoutines::fixed_base_vector_scalar_mul: out[i] = scalars[i] * base"""
+    b = _dory_pts(group, base)
+    sc = fr(scalars).reshape(-1, 4)
+    n = sc.shape[0]
+    out = np.zeros((max(n, 1), _DORY_GROUPS[group]), dtype=np.uint64)
+    name = f"jolt_dory_{group}_fixed_base_mul"
+    _ck(getattr(lib(), name)(self.h, _p(b), _p(sc) if n else None, C.c_size_t(n), _p(out) if n else None), name, self)
+    return out[:n]
+
+
+def _dory_scale_bases_add(self, group, bases, vs, scalar):
+    """DoryRoutines::fixed_scalar_mul_bases_then_add: vs[i] + scalar * bases[i]; returns the new vs (the C entry updates its copy in place)"""
+    b, v = _dory_pts(group, bases), _dory_pts(group, vs).copy()
+    if b.shape[0] != v.shape[0]:
+        raise ValueError("lengths must match")
+    n = v.shape[0]
+    name = f"jolt_dory_{group}_scale_bases_add"
+    _ck(getattr(lib(), name)(self.h, _p(b) if n else None, _p(v) if n else None, C.c_size_t(n), _p(fr(scalar))), name, self)
+    return v
+
+
+def _dory_scale_vs_add(self, group, vs, addends, scalar):
+    """DoryRoutines::fixed_scalar_mul_vs_then_add: scalar * vs[i] + addends[i]; returns the new vs"""
+    v, a = _dory_pts(group, vs).copy(), _dory_pts(group, addends)
+    if a.shape[0] != v.shape[0]:
+        raise ValueError("lengths must match")
+    n = v.shape[0]
+    name = f"jolt_dory_{group}_scale_vs_add"
+    _ck(getattr(lib(), name)(self.h, _p(v) if n else None, _p(a) if n else None, C.c_size_t(n), _p(fr(scalar))), name, self)
+    return v
+
+
+def _dory_fold_field_vectors(self, left, right, scalar):
+    """DoryRoutines::fold_field_vectors: left[i] * scalar + right[i]; returns the new left"""
+    l, r = fr(left).reshape(-1, 4).copy(), fr(right).reshape(-1, 4)
+    if l.shape[0] != r.shape[0]:
+        raise ValueError("lengths must match")
+    n = l.shape[0]
+    _ck(lib().jolt_dory_fold_field_vectors(self.h, _p(l) if n else None, _p(r) if n else None, C.c_size_t(n), _p(fr(scalar))), "jolt_dory_fold_field_vectors", self)
+    return l
+
+
+def _dory_routines_timing(self, enable):
+    """(checks, host -> device, kernels, device -> host) wall ms of the last routine call made while timing was on; then switches timing on / off"""
+    ms = (C.c_double * 4)()
+    _ck(lib().jolt_dory_routines_timing(self.h, C.c_int32(1 if enable else 0), ms), "jolt_dory_routines_timing", self)
+    return tuple(ms)
+
+
+Context.dory_g1_msm = lambda self, bases, scalars: _dory_msm(self, "g1", bases, scalars)
+Context.dory_g2_msm = lambda self, bases, scalars: _dory_msm(self, "g2", bases, scalars)
+Context.dory_g1_fixed_base_mul = lambda self, base, scalars: _dory_fixed_base_mul(self, "g1", base, scalars)
+Context.dory_g2_fixed_base_mul = lambda self, base, scalars: _dory_fixed_base_mul(self, "g2", base, scalars)
+Context.dory_g1_scale_bases_add = lambda self, bases, vs, scalar: _dory_scale_bases_add(self, "g1", bases, vs, scalar)
+Context.dory_g2_scale_bases_add = lambda self, bases, vs, scalar: _dory_scale_bases_add(self, "g2", bases, vs, scalar)
+Context.dory_g1_scale_vs_add = lambda self, vs, addends, scalar: _dory_scale_vs_add(self, "g1", vs, addends, scalar)
+Context.dory_g2_scale_vs_add = lambda self, vs, addends, scalar: _dory_scale_vs_add(self, "g2", vs, addends, scalar)
+Context.dory_fold_field_vectors = _dory_fold_field_vectors
+Context.dory_routines_timing = _dory_routines_timing
+
+FQ2_ADD, FQ2_SUB, FQ2_MUL, FQ2_SQR, FQ2_NEG = 0, 1, 2, 3, 4
+
+
+def host_fq2_op(op, a, b=None):
+    """Fq2 on the host as the kernels compute it; a, b = (8,) uint64 (c0, c1); raises JoltError(1) for an operand that is not canonical"""
+    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(8)
+    b = np.ascontiguousarray(b, dtype=np.uint64).reshape(8) if b is not None else None
+    out = np.zeros(8, dtype=np.uint64)
+    _ck(lib().jolt_host_fq2_op(C.c_int32(op), _p(a), _p(b), _p(out)), "jolt_host_fq2_op")
+    return out
+
+
+def _host_g2(name, *pts):
+    out = np.zeros(24, dtype=np.uint64)
+    args = [_p(np.ascontiguousarray(p, dtype=np.uint64)) for p in pts]
+    _ck(getattr(lib(), name)(*args, _p(out)), name)
+    return out
+
+
+def host_g2_add(p, q): return _host_g2("jolt_host_g2_add", p, q)
+def host_g2_double(p): return _host_g2("jolt_host_g2_double", p)
+def host_g2_neg(p): return _host_g2("jolt_host_g2_neg", p)
+def host_g2_scalar_mul(p, s): return _host_g2("jolt_host_g2_scalar_mul", p, s)
+
+
+def host_g2_eq(p, q):
+    e = C.c_int32()
+    _ck(lib().jolt_host_g2_eq(_p(np.ascontiguousarray(p, dtype=np.uint64)), _p(np.ascontiguousarray(q, dtype=np.uint64)), C.byref(e)), "jolt_host_g2_eq")
+    return bool(e.value)
+
+
+def host_g2_is_on_curve(p):
+    e = C.c_int32()
+    _ck(lib().jolt_host_g2_is_on_curve(_p(np.ascontiguousarray(p, dtype=np.uint64)), C.byref(e)), "jolt_host_g2_is_on_curve")
+    return bool(e.value)
+
+
+def _host_dory_one(name, group, *args):
+    out = np.zeros(_DORY_GROUPS[group], dtype=np.uint64)
+    _ck(getattr(lib(), name)(*[_p(np.ascontiguousarray(a, dtype=np.uint64)) for a in args], _p(out)), name)
+    return out
+
+
+def host_dory_scale_add_one(group, scaled, addend, scalar):
+    """addend + scalar * scaled: one element of both shared-scalar routines through the lanes' code (non-adjacent form and its walk), on the host"""
+    return _host_dory_one(f"jolt_host_dory_{group}_scale_add_one", group, scaled, addend, scalar)
+
+
+def host_dory_fixed_base_one(group, base, scalar):
+    """scalar * base through the fixed-base table and window walk of the device lanes, on the host"""
+    return _host_dory_one(f"jolt_host_dory_{group}_fixed_base_one", group, base, scalar)
+
+
+def host_dory_msm_term(group, base, scalar):
+    """scalar * base as one MSM term of the device lanes, on the host"""
+    return _host_dory_one(f"jolt_host_dory_{group}_msm_term", group, base, scalar)
+
+
 def host_hyperkzg_witness_triple(c, g0, g1, r, a, alpha):
     """the three witness commitments of an opening (at r, -r, r^2) from c[k] = commit(X^k Q3), the first two SRS points and the remainders a, alpha, on the host"""
     cs = np.ascontiguousarray(c, dtype=np.uint64).reshape(3, 12)

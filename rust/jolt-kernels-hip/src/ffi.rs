@@ -1,7 +1,7 @@
 //! Raw FFI declarations of `libjolt_hip.so` -- GENERATED from `include/jolt_hip.h` by `tools/gen_rust_ffi.py`; do not edit.
 //! One declaration per entry point of the C header, same order, same arity, same types (checked by tests/test_abi_cpu.py).
 //! `jolt_fr_t` is bit-identical to `jolt_field::Fr` (4 x u64 Montgomery limbs, crates/jolt-field/src/bn254/mod.rs:33-43) and
-//! `jolt_g1_t` to `jolt_crypto::Bn254G1` (ark_bn254::G1Projective, crates/jolt-crypto/src/ec/bn254/mod.rs:17-24).
+//! `jolt_g1_t` to `jolt_crypto::Bn254G1` (ark_bn254::G1Projective, crates/jolt-crypto/src/ec/bn254/mod.rs:17-24); `jolt_g2_t` to ark_bn254::G2Projective.
 #![allow(non_camel_case_types, clippy::too_many_arguments, clippy::missing_safety_doc)]
 use core::ffi::{c_char, c_void};
 
@@ -23,6 +23,19 @@ pub struct jolt_g1_t {
     pub x: jolt_fq_t,
     pub y: jolt_fq_t,
     pub z: jolt_fq_t,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct jolt_fq2_t {
+    pub c0: jolt_fq_t,
+    pub c1: jolt_fq_t,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct jolt_g2_t {
+    pub x: jolt_fq2_t,
+    pub y: jolt_fq2_t,
+    pub z: jolt_fq2_t,
 }
 #[repr(C)]
 pub struct jolt_ctx {
@@ -126,6 +139,11 @@ pub const JOLT_INT_U64: i32 = 0;
 pub const JOLT_INT_I64: i32 = 1;
 pub const JOLT_INT_I128: i32 = 2;
 pub const JOLT_SCALAR_FR: i32 = 3;
+pub const JOLT_FQ2_ADD: i32 = 0;
+pub const JOLT_FQ2_SUB: i32 = 1;
+pub const JOLT_FQ2_MUL: i32 = 2;
+pub const JOLT_FQ2_SQR: i32 = 3;
+pub const JOLT_FQ2_NEG: i32 = 4;
 pub const JOLT_MAX_MEMBER_TABLES: usize = 40;
 pub const JOLT_MAX_MEMBER_TERMS: usize = 16;
 pub const JOLT_MAX_MEMBER_FACTORS: usize = 64;
@@ -324,6 +342,29 @@ extern "C" {
     pub fn jolt_dory_fold_rows_grid(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, sigma: u32, left: *const jolt_table, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_dory_combine_hints(ctx: *mut jolt_ctx, hints: *const *const jolt_g1_t, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_host_dory_combine_row(points: *const jolt_g1_t, scalars: *const jolt_fr_t, n: usize, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_dory_g1_msm(ctx: *mut jolt_ctx, bases: *const jolt_g1_t, scalars: *const jolt_fr_t, n: usize, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_dory_g1_fixed_base_mul(ctx: *mut jolt_ctx, base: *const jolt_g1_t, scalars: *const jolt_fr_t, n: usize, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_dory_g1_scale_bases_add(ctx: *mut jolt_ctx, bases: *const jolt_g1_t, vs: *mut jolt_g1_t, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_g1_scale_vs_add(ctx: *mut jolt_ctx, vs: *mut jolt_g1_t, addends: *const jolt_g1_t, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_g2_msm(ctx: *mut jolt_ctx, bases: *const jolt_g2_t, scalars: *const jolt_fr_t, n: usize, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_dory_g2_fixed_base_mul(ctx: *mut jolt_ctx, base: *const jolt_g2_t, scalars: *const jolt_fr_t, n: usize, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_dory_g2_scale_bases_add(ctx: *mut jolt_ctx, bases: *const jolt_g2_t, vs: *mut jolt_g2_t, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_g2_scale_vs_add(ctx: *mut jolt_ctx, vs: *mut jolt_g2_t, addends: *const jolt_g2_t, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_fold_field_vectors(ctx: *mut jolt_ctx, left: *mut jolt_fr_t, right: *const jolt_fr_t, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_routines_timing(ctx: *mut jolt_ctx, enable: i32, out_ms: *mut f64) -> i32;
+    pub fn jolt_host_fq2_op(op: i32, a: *const jolt_fq2_t, b: *const jolt_fq2_t, out: *mut jolt_fq2_t) -> i32;
+    pub fn jolt_host_g2_add(p: *const jolt_g2_t, q: *const jolt_g2_t, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_host_g2_double(p: *const jolt_g2_t, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_host_g2_neg(p: *const jolt_g2_t, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_host_g2_eq(p: *const jolt_g2_t, q: *const jolt_g2_t, equal: *mut i32) -> i32;
+    pub fn jolt_host_g2_is_on_curve(p: *const jolt_g2_t, on_curve: *mut i32) -> i32;
+    pub fn jolt_host_g2_scalar_mul(p: *const jolt_g2_t, scalar: *const jolt_fr_t, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_host_dory_g1_scale_add_one(scaled: *const jolt_g1_t, addend: *const jolt_g1_t, scalar: *const jolt_fr_t, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_host_dory_g2_scale_add_one(scaled: *const jolt_g2_t, addend: *const jolt_g2_t, scalar: *const jolt_fr_t, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_host_dory_g1_fixed_base_one(base: *const jolt_g1_t, scalar: *const jolt_fr_t, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_host_dory_g2_fixed_base_one(base: *const jolt_g2_t, scalar: *const jolt_fr_t, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_host_dory_g1_msm_term(base: *const jolt_g1_t, scalar: *const jolt_fr_t, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_host_dory_g2_msm_term(base: *const jolt_g2_t, scalar: *const jolt_fr_t, out: *mut jolt_g2_t) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;

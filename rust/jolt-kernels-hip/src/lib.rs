@@ -18,6 +18,7 @@
 //! | the stage-operator slots: `spartan_{outer,product}_remainder`, `ram_read_write`, `registers_read_write`, `instruction_read_raf`, `booleanity_address`, `bytecode_read_raf_{address,cycle}`, `hamming_weight_claim_reduction`, `ram_raf_evaluation`, `ram_output_check` (`crates/jolt-kernels/src/backend.rs:126-171`) | [`stage`]: one `PrepareKernel` per slot over a `jolt_stage_op` |
 //! | the eleven cycle-domain relation slots of stages 2 - 6b (`crates/jolt-kernels/src/reference/*.rs`) | [`leaves`]: one `ResolveLeaves` per relation for [`member::HipPrepare`] |
 //! | `CommitmentScheme::OpeningHint`, `AdditivelyHomomorphic::combine_hints`, `JointOpeningPolynomials` (`crates/jolt-openings/src/schemes.rs:49-50,157-162`, `crates/jolt-kernels/src/opening.rs:42-54`) | [`opening`]: resident columns + commit-time class sums -> `jolt_host_hyperkzg_open_grid` |
+//! | dory's `DoryRoutines<ArkG1>` / `DoryRoutines<ArkG2>`, the group routines of `dory::prove`'s reduce-and-fold rounds (`crates/jolt-dory/src/routines.rs:58-147`) | [`dory_routines::HipG1Routines`], [`dory_routines::HipG2Routines`] over `jolt_dory_g1_*` / `jolt_dory_g2_*` / `jolt_dory_fold_field_vectors` |
 //! | `UniskipKernel`, `CommitWitness`, the backend constructor (`crates/jolt-kernels/src/{uniskip.rs:28-54, commitment.rs:137-160, optimized/mod.rs:136-196}`) | [`backend::HipUniskip`], [`backend::HipCommitWitness`], [`backend::mi355x`] |
 //!
 //! Host code stays Rust: Fiat-Shamir, claim wiring, round-polynomial assembly (`UnivariatePoly::from_evals`,
@@ -27,6 +28,7 @@
 
 pub mod ffi;
 pub mod context;
+pub mod dory_routines;
 pub mod leaves;
 pub mod member;
 pub mod msm;
@@ -41,6 +43,7 @@ pub mod status;
 pub mod streaming;
 
 pub use context::{HipContext, HipTable};
+pub use dory_routines::{HipG1Routines, HipG2Routines};
 pub use member::{HipMember, HipPrepare, HipSumcheckProver, MemberShape, MemberSlot};
 pub use msm::{msm_cache_clear, msm_cache_evict, msm_g1, HipShardedOpening, HipSrs, SharedMsmContext};
 pub use ops::{HipHotIndices, HipInts, HipKeyIndex, HipR1csRows, HipReadRaf, HipRegistersRw, HipRwMatrix, RowTerms, RwRow, SpartanSums};

@@ -1,0 +1,152 @@
+"""The host build of the Dory reduce-and-fold routines (dory_routines.hip, fq2.hip.h, g2.hip.h): Fq2 and G2 as the kernels compute them against Python integers and
+the big-integer model of tests/g2_model.py, and single elements of the routines -- through the code the device lanes run: the shared scalar's non-adjacent form and
+its walk, the fixed-base table and window walk, one MSM term -- against the model (G2) and the oracle (G1).  No GPU."""
+import numpy as np
+import pytest
+
+import g2_model as M
+import oracle_lib as O
+from dory_groups import G1, G2, GROUPS, R, SHARED_SCALARS, fr_int, rand_ints
+from jolt_amd import ffi
+
+Q = O.Q_MOD
+NOT_CANONICAL_FQ = np.array(O.int_to_limbs(Q), dtype=np.uint64)  # the limbs of q itself: one past the largest canonical value
+
+
+def test_model_obeys_the_group_laws():
+    g = M.GENERATOR
+    a, b = rand_ints(2, 11)
+    assert M.add(M.mul(g, a), M.mul(g, b)) == M.mul(g, (a + b) % R)  # (a + b) P = a P + b P
+    p = M.mul(g, a)
+    assert M.on_curve(p) and M.add(p, M.neg(p)) is None
+    assert M.double(p) == M.add(p, p) == M.mul(g, 2 * a % R)
+    assert M.add(p, None) == p and M.add(None, p) == p and M.double(None) is None
+    for k in (0, 1, 255, 256, a, R - 1, R):
+        assert M.mul_generator(k) == M.mul(g, k % R), k  # the windowed multiplication the GPU tests lean on
+    t = M.TWIST_POINT  # outside the order-r subgroup: r * t is not the identity, (2q - r) r * t is
+    assert M.mul(t, R) is not None and M.mul(M.mul(t, R), M.COFACTOR) is None
+
+
+def test_host_fq2_matches_python_integers_at_the_corners():
+    rng = np.random.default_rng(5)
+    corners = [(0, 0), (1, 0), (0, 1), (Q - 1, Q - 1)]
+    rand = [(int.from_bytes(rng.bytes(40), "little") % Q, int.from_bytes(rng.bytes(40), "little") % Q) for _ in range(4)]
+    ops = [(ffi.FQ2_ADD, M.f2_add), (ffi.FQ2_SUB, M.f2_sub), (ffi.FQ2_MUL, M.f2_mul)]
+    for a in corners + rand:
+        for b in corners + rand[:2]:
+            for op, model in ops:
+                assert M.fq2_from_abi(ffi.host_fq2_op(op, M.fq2_to_abi(a), M.fq2_to_abi(b))) == model(a, b), (op, a, b)
+        assert M.fq2_from_abi(ffi.host_fq2_op(ffi.FQ2_SQR, M.fq2_to_abi(a))) == M.f2_sqr(a), a
+        assert M.fq2_from_abi(ffi.host_fq2_op(ffi.FQ2_NEG, M.fq2_to_abi(a))) == M.f2_neg(a), a
+    # one operand that is not canonical is refused, whichever component and whichever side
+    good = M.fq2_to_abi((3, 4))
+    for half in (0, 1):
+        bad = good.copy()
+        bad[4 * half:4 * half + 4] = NOT_CANONICAL_FQ
+        for args in ((ffi.FQ2_MUL, bad, good), (ffi.FQ2_ADD, good, bad), (ffi.FQ2_SQR, bad)):
+            with pytest.raises(ffi.JoltError) as e:
+                ffi.host_fq2_op(*args)
+            assert e.value.status == 1
+
+
+def test_host_g2_matches_the_model():
+    a, b = rand_ints(2, 21)
+    pa, pb = M.mul_generator(a), M.mul_generator(b)
+    A, B = M.to_abi(pa), M.to_abi(pb, M.f2(5, 7))
+    ident = M.to_abi(None)
+    assert M.from_abi(ffi.host_g2_add(A, B)) == M.add(pa, pb)
+    assert M.from_abi(ffi.host_g2_add(A, M.to_abi(pa, M.f2(2, 9)))) == M.double(pa)         # P + P across representatives
+    assert M.from_abi(ffi.host_g2_add(A, M.to_abi(M.neg(pa), M.f2(3, 1)))) is None           # P - P
+    assert M.from_abi(ffi.host_g2_add(ident, B)) == pb and M.from_abi(ffi.host_g2_add(B, ident)) == pb
+    assert M.from_abi(ffi.host_g2_double(B)) == M.double(pb) and M.from_abi(ffi.host_g2_double(ident)) is None
+    assert M.from_abi(ffi.host_g2_neg(B)) == M.neg(pb)
+    # equality as group elements: different Jacobian representatives of one point, different points, the identity
+    assert ffi.host_g2_eq(A, M.to_abi(pa, M.f2(11, 13))) and not ffi.host_g2_eq(A, B) and not ffi.host_g2_eq(A, M.to_abi(M.neg(pa)))
+    garbage_identity = B.copy()
+    garbage_identity[16:] = 0  # z = 0 with any x, y is the identity
+    assert ffi.host_g2_eq(ident, garbage_identity) and not ffi.host_g2_eq(ident, A)
+    # the on-curve check: good points in and outside the subgroup, the identity, one limb changed, one coordinate not canonical
+    for good in (A, B, ident, garbage_identity, M.to_abi(M.TWIST_POINT, M.f2(4, 2))):
+        assert ffi.host_g2_is_on_curve(good)
+    for limb in (0, 7, 9, 15, 17, 23):
+        bad = B.copy()
+        bad[limb] ^= np.uint64(1)
+        assert not ffi.host_g2_is_on_curve(bad), limb
+    bad = ident.copy()
+    bad[0:4] = NOT_CANONICAL_FQ  # even the identity must have canonical coordinates
+    assert not ffi.host_g2_is_on_curve(bad)
+    # scalar multiplication, subgroup and not
+    for k in (0, 1, 2, a, R - 1):
+        assert M.from_abi(ffi.host_g2_scalar_mul(B, fr_int(k))) == M.mul(pb, k), k
+    assert M.from_abi(ffi.host_g2_scalar_mul(M.to_abi(M.TWIST_POINT), fr_int(b))) == M.mul(M.TWIST_POINT, b)
+
+
+@pytest.mark.parametrize("G", GROUPS, ids=lambda G: G.name)
+def test_host_shared_scalar_element_matches_the_reference(G):
+    """addend + s * scaled for the shared scalars of the issue and a random one; the planted cases are the final addition's: result the identity (z = 0), the
+    last addition a doubling, an identity on either side"""
+    b, v, s_rand = rand_ints(3, 31)
+    for s in SHARED_SCALARS + [s_rand]:
+        sc = fr_int(s)
+        cases = [(b, v), (b, -s * b), (b, s * b), (0, v), (b, 0), (0, 0)]
+        for kb, kv in cases:
+            out = ffi.host_dory_scale_add_one(G.name, G.point(kb, rep=3), G.point(kv, rep=4), sc)
+            assert G.same(out, kv + s * kb), (s, kb, kv)
+            if (kv + s * kb) % R == 0:
+                assert G.z_is_zero(out)
+                assert np.array_equal(out, G.point(0)), "the identity is returned as (1, 1, 0)"
+
+
+@pytest.mark.parametrize("G", GROUPS, ids=lambda G: G.name)
+def test_host_per_element_scalar_routines_match_the_reference(G):
+    b = rand_ints(1, 41)[0]
+    # nibbles 0x7, 0x8, 0x9 sit on both sides of the signed-digit boundary of the fixed-base windows
+    scalars = [0, 1, 2, 7, 8, 9, 0x88888888, int("7" * 63, 16) % R, int("9" * 63, 16) % R, R - 1, (1 << 253) - 1] + rand_ints(4, 42)
+    for s in scalars:
+        for kb in (b, 0):
+            assert G.same(ffi.host_dory_fixed_base_one(G.name, G.point(kb, rep=5), fr_int(s)), s * kb), (s, kb)
+            assert G.same(ffi.host_dory_msm_term(G.name, G.point(kb, rep=5), fr_int(s)), s * kb), (s, kb)
+    assert G.z_is_zero(ffi.host_dory_fixed_base_one(G.name, G.point(b), fr_int(0)))
+
+
+def test_host_g2_routines_work_outside_the_subgroup():
+    """no subgroup check: a point of the twist outside the order-r subgroup gets what the group law gives"""
+    t, s = M.TWIST_POINT, rand_ints(1, 51)[0]
+    T = M.to_abi(t, M.f2(6, 5))
+    assert M.from_abi(ffi.host_dory_scale_add_one("g2", T, M.to_abi(M.double(t)), fr_int(s))) == M.mul(t, s + 2)
+    assert M.from_abi(ffi.host_dory_fixed_base_one("g2", T, fr_int(s))) == M.mul(t, s)
+    assert M.from_abi(ffi.host_dory_msm_term("g2", T, fr_int(s))) == M.mul(t, s)
+
+
+@pytest.mark.parametrize("G", GROUPS, ids=lambda G: G.name)
+def test_host_routines_refuse_what_the_device_entries_refuse(G):
+    p, s = G.point(7), fr_int(9)
+    off_curve = p.copy()
+    off_curve[1] ^= np.uint64(1)
+    not_canonical_point = p.copy()
+    not_canonical_point[0:4] = NOT_CANONICAL_FQ
+    not_canonical_scalar = np.array(O.int_to_limbs(R), dtype=np.uint64)
+    for bad in (off_curve, not_canonical_point):
+        for call in (lambda: ffi.host_dory_scale_add_one(G.name, bad, p, s), lambda: ffi.host_dory_scale_add_one(G.name, p, bad, s),
+                     lambda: ffi.host_dory_fixed_base_one(G.name, bad, s), lambda: ffi.host_dory_msm_term(G.name, bad, s)):
+            with pytest.raises(ffi.JoltError) as e:
+                call()
+            assert e.value.status == 1
+    for call in (lambda: ffi.host_dory_scale_add_one(G.name, p, p, not_canonical_scalar), lambda: ffi.host_dory_fixed_base_one(G.name, p, not_canonical_scalar),
+                 lambda: ffi.host_dory_msm_term(G.name, p, not_canonical_scalar)):
+        with pytest.raises(ffi.JoltError) as e:
+            call()
+        assert e.value.status == 1
+
+
+def test_rust_routines_name_the_reference_trait_functions():
+    """rust/jolt-kernels-hip/src/dory_routines.rs implements DoryRoutines for both groups with the function names and arities of the reference's own two impls
+    (tools/rust_seam_audit.py holds them; the trait itself lives in the external dory-pcs crate)"""
+    import importlib.util
+    import os
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    spec = importlib.util.spec_from_file_location("rust_seam_audit", os.path.join(root, "tools", "rust_seam_audit.py"))
+    A = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(A)
+    assert A.dory_routines_findings() == []
+    assert "pub mod dory_routines;" in open(os.path.join(root, "rust", "jolt-kernels-hip", "src", "lib.rs")).read()

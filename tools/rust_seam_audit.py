@@ -20,6 +20,9 @@ suite uses where the reference is absent.  Round 4's `JoltBackend::<Fr, HipHyper
 
     python tools/rust_seam_audit.py                  # audit, findings on stdout, exit 1 if any
     python tools/rust_seam_audit.py --write-fixture  # re-extract the reference surface the crate touches
+
+dory's `DoryRoutines` (src/dory_routines.rs) is outside all of this -- the trait lives in the external dory-pcs crate -- so `dory_routines_findings` holds the crate's two
+impls against the function names and arities of the reference's own two (crates/jolt-dory/src/routines.rs), frozen into tests/golden/dory_routines_surface.json.
 """
 import json
 import os
@@ -752,6 +755,49 @@ class Audit:
         return self.findings
 
 
+# ---- dory's DoryRoutines seam ---------------------------------------------------------------------------------------------------------------------------------
+# The trait lives in the external dory-pcs crate, which neither the reference checkout nor this repository holds, so checks 2 and 3 cannot reach it.  What CAN be held
+# is the surface of the reference's own two impls (crates/jolt-dory/src/routines.rs): the function names and arities of `impl DoryRoutines<ArkG1> for JoltG1Routines` and
+# `impl DoryRoutines<ArkG2> for JoltG2Routines`, frozen into tests/golden/dory_routines_surface.json by --write-fixture.
+DORY_FIXTURE = os.path.join(ROOT, "tests", "golden", "dory_routines_surface.json")
+DORY_IMPLS = {"ArkG1": ("JoltG1Routines", "HipG1Routines"), "ArkG2": ("JoltG2Routines", "HipG2Routines")}
+
+
+def _dory_impls(crate):
+    return {i["trait_args"].strip(): i for i in crate.impls if i["trait"] == "DoryRoutines"}
+
+
+def dory_routines_surface(live=False):
+    """{group argument: {function: arity}} of the reference's impls: from a reference checkout when `live`, else from the fixture"""
+    if not live:
+        return json.load(open(DORY_FIXTURE))
+    ref = Crate.__new__(Crate)
+    ref.impls = list(Crate._impls(ref, "routines.rs", strip(open(os.path.join(REFERENCE, "crates", "jolt-dory", "src", "routines.rs")).read())))
+    found = _dory_impls(ref)
+    return {g: dict(sorted(found[g]["methods"].items())) for g in sorted(DORY_IMPLS) if g in found and found[g]["type"] == DORY_IMPLS[g][0]}
+
+
+def dory_routines_findings(crate=None, surface=None):
+    crate, surface = crate or Crate(), surface or dory_routines_surface()
+    ours, out = _dory_impls(crate), []
+    for group, (_, ty) in sorted(DORY_IMPLS.items()):
+        want, got = surface.get(group), ours.get(group)
+        if not want:
+            out.append(f"no reference impl of DoryRoutines<{group}> in the surface")
+        elif not got or got["type"] != ty:
+            out.append(f"no `impl DoryRoutines<{group}> for {ty}` in the crate")
+        else:
+            for name, arity in want.items():
+                if name not in got["methods"]:
+                    out.append(f"{got['file']}:{got['line']} impl DoryRoutines<{group}> for {ty}: function `{name}` of the reference's impl is missing")
+                elif got["methods"][name] != arity:
+                    out.append(f"{got['file']}:{got['line']} impl DoryRoutines<{group}> for {ty}: `{name}` takes {got['methods'][name]} parameter(s), the reference's impl {arity}")
+            for name in got["methods"]:
+                if name not in want:
+                    out.append(f"{got['file']}:{got['line']} impl DoryRoutines<{group}> for {ty}: `{name}` is not a function of the reference's impl")
+    return out
+
+
 def features_of(cfgs):
     """cfg attribute list -> the set of features that must be ON for the item to exist (`not(feature = ..)` items exist with the feature off: empty set)"""
     out = set()
@@ -782,9 +828,13 @@ def main():
         with open(FIXTURE, "w") as f:
             json.dump(a.surface, f, indent=1, sort_keys=True)
         print(f"{FIXTURE}: {len(a.surface['traits'])} traits, {len(a.surface['generic'])} generic items; {len(a.findings)} finding(s)")
+        with open(DORY_FIXTURE, "w") as f:
+            json.dump(dory_routines_surface(live=True), f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"{DORY_FIXTURE}: the reference's DoryRoutines impls")
         return
     a = Audit() if live else Audit(json.load(open(FIXTURE)))
-    findings = a.run()
+    findings = a.run() + dory_routines_findings(a.crate, dory_routines_surface(live=True) if live else None)
     for f in findings:
         print("FINDING", f)
     served = getattr(a, "slots_served", {})
