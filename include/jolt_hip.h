@@ -573,8 +573,9 @@ int32_t jolt_dory_commit_rows(jolt_ctx *ctx, const jolt_srs *srs, const jolt_int
 int32_t jolt_dory_commit_onehot(jolt_ctx *ctx, const jolt_srs *srs, const jolt_onehot *source, size_t poly, size_t chunk_width, jolt_g1_t *out);
 
 /* The G1 and Fr work of a Dory opening ahead of the pairing rounds.  Cycle-major placement (TracePolynomialOrder::CycleMajor): grid
- * index k*T + j, dense columns at k = 0, as for the jolt_grid_* entry points below.  What stays on the host is the tier-2
- * multi-pairing and, of the reduce-and-fold rounds of dory::prove, the pairings, GT and the control flow (their group routines: jolt_dory_g1_* / jolt_dory_g2_* below).
+ * index k*T + j, dense columns at k = 0, as for the jolt_grid_* entry points below.  The tier-2 multi-pairing and the multi-pairings of the reduce-and-fold rounds of
+ * dory::prove are jolt_dory_multi_pair / jolt_dory_multi_pair_g2_setup below, the rounds' group routines jolt_dory_g1_* / jolt_dory_g2_*; what stays on the host is
+ * GT scalings, the transcript, the control flow and commit_blind.
  *
  * RlcSource::fold_rows over TraceOpeningPoly (optimized/opening.rs:491-510, multilinear.rs:452-462), cycle-major -- the
  * vector_matrix_product of dory::prove (crates/jolt-dory/src/scheme.rs:612-618), answered from the per-cycle columns without the K x T grid:
@@ -599,7 +600,8 @@ int32_t jolt_host_dory_combine_row(const jolt_g1_t *points, const jolt_fr_t *sca
 /* The group and field routines of dory::prove's reduce-and-fold rounds: dory's DoryRoutines seam as the reference implements it for both groups,
  * JoltG1Routines (crates/jolt-dory/src/routines.rs:60-97) and JoltG2Routines (:101-147).  Host pointers in and out, like jolt_dory_combine_hints: the trait works
  * on host slices and the pairings need the vectors on the host every round.  `vs` / `left` are updated in place.  Results are the reference's group elements; the
- * Jacobian representative is free, the identity comes back as (1, 1, 0).  Pairings, GT and the control flow of dory::prove stay with the caller.
+ * Jacobian representative is free, the identity comes back as (1, 1, 0).  The rounds' multi-pairings are jolt_dory_multi_pair below; GT scalings and the control flow of
+ * dory::prove stay with the caller.
  * Every entry refuses with JOLT_ERR_INVALID_ARG: a null pointer with n > 0, a scalar that is not canonical, a point whose coordinates are not canonical or that
  * is not on its curve.  For G2 that is the twist equation ONLY -- there is NO subgroup check (the twist has cofactor 2q - r); the routines are group-law
  * identities on the whole twist, so a point outside the order-r subgroup gets the answer the same formulas give on the CPU.  A refused call enqueues nothing,
@@ -640,6 +642,45 @@ int32_t jolt_host_dory_g1_fixed_base_one(const jolt_g1_t *base, const jolt_fr_t 
 int32_t jolt_host_dory_g2_fixed_base_one(const jolt_g2_t *base, const jolt_fr_t *scalar, jolt_g2_t *out);
 int32_t jolt_host_dory_g1_msm_term(const jolt_g1_t *base, const jolt_fr_t *scalar, jolt_g1_t *out);
 int32_t jolt_host_dory_g2_msm_term(const jolt_g2_t *base, const jolt_fr_t *scalar, jolt_g2_t *out);
+
+/* Dory's multi-pairings: the BN254 optimal ate pairing (pairing.hip.h), one Miller loop per pair on the device, their product by a halving tree, the final
+ * exponentiation on the host.  jolt_gt_t == ark_bn254::Fq12 (Bn254GT, crates/jolt-crypto/src/ec/bn254/gt.rs:30-32): twelve Montgomery Fq in the order c0.c0.c0,
+ * c0.c0.c1, c0.c1.c0, ..., c1.c2.c1; the Fq2 coefficient c_h.c_j multiplies w^(2 j + h), w^6 = 9 + u.  The final exponent is (p^12 - 1) / r * 2 z (6 z^2 + 3 z + 1),
+ * the power ark-ec's BN model is recalled to compute: a convention that no reference vector pins (docs/parity.md).  Host pointers in and out, like the routines
+ * above, and their refusals: JOLT_ERR_INVALID_ARG for a null pointer with n > 0, coordinates that are not canonical, a point off its curve; NO subgroup check,
+ * as in arkworks (a G2 point outside the order-r subgroup traps nothing and gives an unspecified value).  A refused call enqueues nothing and writes nothing.
+ * A pair with the identity on either side contributes one; n = 0 gives one.  n <= 2^20 (JOLT_ERR_UNSUPPORTED above: the line table takes 16.5 KiB per pair). */
+typedef struct { jolt_fq_t c[12]; } jolt_gt_t;
+typedef struct jolt_g2_prepared jolt_g2_prepared;
+#define JOLT_PAIRING_LINES 88 /* lines of one prepared G2 point: 65 doublings and 21 additions of 6z + 2 in non-adjacent form, the two Frobenius steps */
+/* PairingGroup::multi_pairing (crates/jolt-crypto/src/ec/bn254/mod.rs:274-284), dory's multi_pair in every round of dory::prove: out = prod_i e(g1s[i], g2s[i]) */
+int32_t jolt_dory_multi_pair(jolt_ctx *ctx, const jolt_g1_t *g1s, const jolt_g2_t *g2s, size_t n, jolt_gt_t *out);
+/* The same product BEFORE the final exponentiation: what the device computes, bit for bit what jolt_host_miller_loop gives (field arithmetic is exact) */
+int32_t jolt_dory_multi_miller(jolt_ctx *ctx, const jolt_g1_t *g1s, const jolt_g2_t *g2s, size_t n, jolt_gt_t *out);
+/* The line tables of n G2 points, resident on the device, step-major: built once per setup for the g2_vec bases (the G2 Miller preprocessing scheme.rs:147-153
+ * remarks on).  Freed with jolt_g2_prepared_free; n = 0 gives an empty table. */
+int32_t jolt_dory_g2_prepare(jolt_ctx *ctx, const jolt_g2_t *g2s, size_t n, jolt_g2_prepared **out);
+int32_t jolt_g2_prepared_free(jolt_ctx *ctx, jolt_g2_prepared *prepared);
+/* dory's multi_pair_g2_setup over srs_prefix (crates/jolt-dory/src/scheme.rs:543-552), the tier-2 commitment: out = prod_{i < n} e(g1s[i], prepared point i).
+ * n beyond the prepared length is JOLT_ERR_INVALID_ARG. */
+int32_t jolt_dory_multi_pair_g2_setup(jolt_ctx *ctx, const jolt_g1_t *g1s, const jolt_g2_prepared *prepared, size_t n, jolt_gt_t *out);
+/* Measurement aid of tools/bench_dory_pairing.py, as jolt_dory_routines_timing: the wall milliseconds of the phases of the last multi-pairing or prepare call made
+ * while timing was on -- argument checks, host -> device, prepare kernel, Miller kernel, product tree, device -> host, final exponentiation. */
+int32_t jolt_dory_pairing_timing(jolt_ctx *ctx, int32_t enable, double *out_ms /* 7 */);
+/* Fq12 and the pairing on the host through the code the kernels run (fq12.hip.h, pairing.hip.h), for the CPU suite.  jolt_host_fq12_op refuses operands that are
+ * not canonical (JOLT_ERR_INVALID_ARG) and the inverse of zero (JOLT_ERR_NOT_INVERTIBLE); b is read by MUL and MUL_SPARSE only.  MUL_SPARSE multiplies through the
+ * line routine (mul_by_034) and refuses a b that has a non-zero coefficient outside c0.c0, c1.c0, c1.c1. */
+enum { JOLT_FQ12_MUL = 0, JOLT_FQ12_SQR = 1, JOLT_FQ12_INV = 2, JOLT_FQ12_CONJ = 3, JOLT_FQ12_FROBENIUS1 = 4, JOLT_FQ12_FROBENIUS2 = 5, JOLT_FQ12_FROBENIUS3 = 6,
+       JOLT_FQ12_MUL_SPARSE = 7 };
+int32_t jolt_host_fq12_op(int32_t op, const jolt_gt_t *a, const jolt_gt_t *b, jolt_gt_t *out);
+/* The line table of one G2 point, lines[3 * step + {0, 1, 2}] = the coefficients (a, b, c) of a y_P + b x_P w + c w^3; *skip = 1 for the identity */
+int32_t jolt_host_g2_prepare_one(const jolt_g2_t *g2, jolt_fq2_t *lines /* 3 * JOLT_PAIRING_LINES */, int32_t *skip);
+/* prod_i of the Miller values of the pairs, before the final exponentiation */
+int32_t jolt_host_miller_loop(const jolt_g1_t *g1s, const jolt_g2_t *g2s, size_t n, jolt_gt_t *out);
+/* f^((p^12 - 1) / r * 2 z (6 z^2 + 3 z + 1)); zero is JOLT_ERR_NOT_INVERTIBLE */
+int32_t jolt_host_final_exponentiation(const jolt_gt_t *f, jolt_gt_t *out);
+/* gt^scalar by square-and-multiply over the canonical scalar: the GT scaling that stays with the caller */
+int32_t jolt_host_gt_pow(const jolt_gt_t *gt, const jolt_fr_t *scalar, jolt_gt_t *out);
 
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)

@@ -109,6 +109,9 @@ struct jolt_ctx {
     // jolt_dory_routines_timing: per-phase wall time of the last Dory routine call (checks, host -> device, kernels, device -> host)
     bool dory_timing = false;
     double dory_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // jolt_dory_pairing_timing: checks, host -> device, prepare, Miller, product, device -> host, final exponentiation
+    bool pairing_timing = false;
+    double pairing_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
 // Make the main stream wait for side streams that ran a table-writing kernel (ev_join); a null context is accepted.

@@ -1,0 +1,68 @@
+// jolt_amd/csrc/dory_host.hpp -- host-side helpers shared by the Dory entry points that take host pointers (dory_routines.hip, dory_pairing.hip).
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "ctx.hpp"
+
+namespace jolt {
+namespace dory_host {
+
+// one wavefront per workgroup, one element per lane: the launch shape of every latency-bound Dory kernel (docs/kernels.md 3.5f)
+constexpr int kLanes = 64;
+inline unsigned lanes_grid(size_t n) { return (unsigned)((n + kLanes - 1) / kLanes); }
+
+inline int32_t hip_fail(jolt_ctx* ctx, const char* what, hipError_t e) {
+    ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? JOLT_ERR_OOM : JOLT_ERR_HIP;
+}
+
+// The argument checks run on the host before anything is enqueued (a refused call enqueues nothing).  A G2 on-curve check costs ~2 us of host time and a round holds
+// 2^14 ... 2^16 points, which is more than the kernels take: long vectors are checked by up to 16 host threads.
+template <class Ok>
+bool parallel_all(size_t n, Ok&& ok_range) {
+    const size_t hw = std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
+    const size_t parts = std::min(hw, n / 1024);
+    if (parts <= 1) return ok_range((size_t)0, n);
+    std::vector<char> ok(parts, 1);
+    std::vector<std::thread> workers;
+    size_t started = 0;
+    try {
+        for (; started + 1 < parts; ++started) workers.emplace_back([&ok, &ok_range, started, n, parts] { ok[started] = ok_range(n * started / parts, n * (started + 1) / parts) ? 1 : 0; });
+    } catch (...) {  // no more threads to be had: the calling thread takes the rest
+    }
+    bool all = ok_range(n * started / parts, n);
+    for (std::thread& w : workers) w.join();
+    for (size_t t = 0; t < started; ++t) all = all && ok[t];
+    return all;
+}
+
+struct DevBufs {  // pool blocks of one call, returned on every path
+    jolt_ctx* ctx;
+    std::vector<void*> blocks;
+    explicit DevBufs(jolt_ctx* c) : ctx(c) {}
+    ~DevBufs() {
+        for (void* b : blocks) jolt_internal_dev_free(ctx, b);
+    }
+    template <class T>
+    int32_t take(size_t count, T** out) {
+        void* p = nullptr;
+        const int32_t rc = jolt_internal_dev_alloc(ctx, std::max<size_t>(count, 1) * sizeof(T), &p);
+        if (rc == JOLT_OK) blocks.push_back(p);
+        *out = (T*)p;
+        return rc;
+    }
+};
+
+template <class Pt>
+Pt pt_from_abi(const void* p) {
+    Pt r;
+    std::memcpy(&r, p, sizeof(r));
+    return r;
+}
+
+}  // namespace dory_host
+}  // namespace jolt

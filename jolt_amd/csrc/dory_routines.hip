@@ -7,7 +7,7 @@
 //   fixed_scalar_mul_bases_then_add(bases, vs, s)    -> jolt_dory_g{1,2}_scale_bases_add vs[i] += s * bases[i]
 //   fixed_scalar_mul_vs_then_add(vs, addends, s)     -> jolt_dory_g{1,2}_scale_vs_add   vs[i] = s * vs[i] + addends[i]
 //   fold_field_vectors(left, right, s)               -> jolt_dory_fold_field_vectors    left[i] = left[i] * s + right[i]
-// Pairings, GT and the control flow of dory::prove stay with the caller.
+// The rounds' multi-pairings are dory_pairing.hip; GT scalings and the control flow of dory::prove stay with the caller.
 //
 // One lane per element.  In the two per-round vector operations every element is multiplied by the SAME scalar: the host recodes it once into
 // non-adjacent form (digits in {-1, 0, 1}, no two adjacent non-zero), and every lane walks that one sequence of doublings and additions -- control
@@ -23,11 +23,13 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "dory_host.hpp"
 #include "g1.hip.h"
 #include "g2.hip.h"
 #include "poly_kernels.hip.h"
 
 using namespace jolt;
+using namespace jolt::dory_host;
 
 namespace {
 
@@ -177,9 +179,7 @@ JOLT_HD typename O::Pt term_mul_one(const typename O::Pt& p, const Fr& scalar_mo
     return acc;
 }
 
-// ---- kernels: one wavefront per workgroup, one wavefront per SIMD (a G2 addition holds two 48-register points and its temporaries) ----
-constexpr int kLanes = 64;
-
+// ---- kernels: one wavefront per workgroup (kLanes), one wavefront per SIMD (a G2 addition holds two 48-register points and its temporaries) ----
 // out[i] = addend[i] + s * scaled[i], as scale_add_one; out may alias either input (each lane reads its own element before it writes it)
 template <class O>
 __global__ __launch_bounds__(kLanes) void k_dory_scale_add(NafPlan plan, const typename O::Pt* scaled, const typename O::Pt* addend, typename O::Pt* out, size_t n) {
@@ -214,30 +214,6 @@ __global__ __launch_bounds__(256) void k_dory_fold_field(Fr* __restrict__ left, 
 }
 
 // ---- host side of the entry points ----
-int32_t hip_fail(jolt_ctx* ctx, const char* what, hipError_t e) {
-    ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? JOLT_ERR_OOM : JOLT_ERR_HIP;
-}
-
-// The argument checks run on the host before anything is enqueued (a refused call enqueues nothing).  A G2 on-curve check costs ~2 us of host time and a round holds
-// 2^14 ... 2^16 points, which is more than the kernels take: long vectors are checked by up to 16 host threads.
-template <class Ok>
-bool parallel_all(size_t n, Ok&& ok_range) {
-    const size_t hw = std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency()));
-    const size_t parts = std::min(hw, n / 1024);
-    if (parts <= 1) return ok_range((size_t)0, n);
-    std::vector<char> ok(parts, 1);
-    std::vector<std::thread> workers;
-    size_t started = 0;
-    try {
-        for (; started + 1 < parts; ++started) workers.emplace_back([&ok, &ok_range, started, n, parts] { ok[started] = ok_range(n * started / parts, n * (started + 1) / parts) ? 1 : 0; });
-    } catch (...) {  // no more threads to be had: the calling thread takes the rest
-    }
-    bool all = ok_range(n * started / parts, n);
-    for (std::thread& w : workers) w.join();
-    for (size_t t = 0; t < started; ++t) all = all && ok[t];
-    return all;
-}
 template <class O>
 bool all_on_curve(const typename O::Abi* pts, size_t n) {
     return parallel_all(n, [pts](size_t lo, size_t hi) {
@@ -273,24 +249,6 @@ struct Phases {
     }
 };
 
-struct DevBufs {  // pool blocks of one call, returned on every path
-    jolt_ctx* ctx;
-    std::vector<void*> blocks;
-    explicit DevBufs(jolt_ctx* c) : ctx(c) {}
-    ~DevBufs() {
-        for (void* b : blocks) jolt_internal_dev_free(ctx, b);
-    }
-    template <class T>
-    int32_t take(size_t count, T** out) {
-        void* p = nullptr;
-        const int32_t rc = jolt_internal_dev_alloc(ctx, std::max<size_t>(count, 1) * sizeof(T), &p);
-        if (rc == JOLT_OK) blocks.push_back(p);
-        *out = (T*)p;
-        return rc;
-    }
-};
-
-unsigned lanes_grid(size_t n) { return (unsigned)((n + kLanes - 1) / kLanes); }
 constexpr size_t kMaxElements = (size_t)1 << 30;  // keeps every grid below 2^31 workgroups; a Dory round holds 2^nu <= 2^20 points
 
 // vs[i] = addend + s * scaled with (scaled, addend) = (other, vs) [bases_then_add] or (vs, other) [vs_then_add]
@@ -405,13 +363,6 @@ int32_t msm(jolt_ctx* ctx, const typename O::Abi* bases, const jolt_fr_t* scalar
     sum = normalised<O>(sum);
     std::memcpy(out, &sum, sizeof(sum));
     return JOLT_OK;
-}
-
-template <class Pt>
-Pt pt_from_abi(const void* p) {
-    Pt r;
-    std::memcpy(&r, p, sizeof(r));
-    return r;
 }
 
 template <class O>

@@ -1438,6 +1438,112 @@ def host_dory_msm_term(group, base, scalar):
     return _host_dory_one(f"jolt_host_dory_{group}_msm_term", group, base, scalar)
 
 
+# ---- Dory's multi-pairings (dory_pairing.hip): the tier-2 commitment and the multi-pairings of the reduce-and-fold rounds
+PAIRING_LINES = 88  # JOLT_PAIRING_LINES
+FQ12_MUL, FQ12_SQR, FQ12_INV, FQ12_CONJ, FQ12_FROBENIUS1, FQ12_FROBENIUS2, FQ12_FROBENIUS3, FQ12_MUL_SPARSE = range(8)
+
+
+def gt_array():
+    """one GT element: (48,) uint64 -- twelve Montgomery Fq, c0.c0.c0, c0.c0.c1, c0.c1.c0, ..., c1.c2.c1 (ark_bn254::Fq12)"""
+    return np.zeros(48, dtype=np.uint64)
+
+
+def _pair_g1(g1s):
+    return np.ascontiguousarray(g1s, dtype=np.uint64).reshape(-1, 12)
+
+
+def _dory_multi_pair(self, g1s, g2s, final_exponentiation=True):
+    """prod_i e(g1s[i], g2s[i]) (PairingGroup::multi_pairing, dory's multi_pair); final_exponentiation=False: the raw Miller product"""
+    a, b = _pair_g1(g1s), _dory_pts("g2", g2s)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("multi_pair: the two sides differ in length")
+    n, out = a.shape[0], gt_array()
+    name = "jolt_dory_multi_pair" if final_exponentiation else "jolt_dory_multi_miller"
+    _ck(getattr(lib(), name)(self.h, _p(a) if n else None, _p(b) if n else None, C.c_size_t(n), _p(out)), name, self)
+    return out
+
+
+class G2Prepared:
+    """the line tables of n G2 points, resident on the device (jolt_dory_g2_prepare)"""
+
+    def __init__(self, ctx, h, n):
+        self.ctx, self.h, self.n = ctx, h, n
+
+    def free(self):
+        if self.h:
+            _ck(lib().jolt_g2_prepared_free(self.ctx.h, self.h), "jolt_g2_prepared_free", self.ctx)
+            self.h = None
+
+
+def _dory_g2_prepare(self, g2s):
+    b = _dory_pts("g2", g2s)
+    h = C.c_void_p()
+    _ck(lib().jolt_dory_g2_prepare(self.h, _p(b) if b.shape[0] else None, C.c_size_t(b.shape[0]), C.byref(h)), "jolt_dory_g2_prepare", self)
+    return G2Prepared(self, h, b.shape[0])
+
+
+def _dory_multi_pair_g2_setup(self, g1s, prepared, n=None):
+    """prod_{i < n} e(g1s[i], prepared point i) (dory's multi_pair_g2_setup over srs_prefix); n defaults to len(g1s)"""
+    a = _pair_g1(g1s)
+    n = a.shape[0] if n is None else n
+    out = gt_array()
+    _ck(lib().jolt_dory_multi_pair_g2_setup(self.h, _p(a) if a.shape[0] else None, prepared.h, C.c_size_t(n), _p(out)), "jolt_dory_multi_pair_g2_setup", self)
+    return out
+
+
+def _dory_pairing_timing(self, enable):
+    """(checks, host -> device, prepare, Miller, product, device -> host, final exponentiation) wall ms of the last pairing call made while timing was on"""
+    ms = (C.c_double * 7)()
+    _ck(lib().jolt_dory_pairing_timing(self.h, C.c_int32(1 if enable else 0), ms), "jolt_dory_pairing_timing", self)
+    return tuple(ms)
+
+
+Context.dory_multi_pair = _dory_multi_pair
+Context.dory_g2_prepare = _dory_g2_prepare
+Context.dory_multi_pair_g2_setup = _dory_multi_pair_g2_setup
+Context.dory_pairing_timing = _dory_pairing_timing
+
+
+def _gt(a):
+    return np.ascontiguousarray(a, dtype=np.uint64).reshape(48)
+
+
+def host_fq12_op(op, a, b=None):
+    """Fq12 on the host as the kernels compute it; raises JoltError(1) for an operand that is not canonical, JoltError(11) for the inverse of zero"""
+    out = gt_array()
+    _ck(lib().jolt_host_fq12_op(C.c_int32(op), _p(_gt(a)), _p(_gt(b)) if b is not None else None, _p(out)), "jolt_host_fq12_op")
+    return out
+
+
+def host_g2_prepare_one(g2):
+    """-> ((PAIRING_LINES, 3, 8) uint64 line coefficients (a, b, c), skip)"""
+    lines, skip = np.zeros((PAIRING_LINES, 3, 8), dtype=np.uint64), C.c_int32()
+    _ck(lib().jolt_host_g2_prepare_one(_p(np.ascontiguousarray(g2, dtype=np.uint64).reshape(24)), _p(lines), C.byref(skip)), "jolt_host_g2_prepare_one")
+    return lines, bool(skip.value)
+
+
+def host_miller_loop(g1s, g2s):
+    """the product of the Miller values of the pairs, before the final exponentiation"""
+    a, b = _pair_g1(g1s), _dory_pts("g2", g2s)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("miller_loop: the two sides differ in length")
+    n, out = a.shape[0], gt_array()
+    _ck(lib().jolt_host_miller_loop(_p(a) if n else None, _p(b) if n else None, C.c_size_t(n), _p(out)), "jolt_host_miller_loop")
+    return out
+
+
+def host_final_exponentiation(f):
+    out = gt_array()
+    _ck(lib().jolt_host_final_exponentiation(_p(_gt(f)), _p(out)), "jolt_host_final_exponentiation")
+    return out
+
+
+def host_gt_pow(gt, scalar):
+    out = gt_array()
+    _ck(lib().jolt_host_gt_pow(_p(_gt(gt)), _p(fr(scalar)), _p(out)), "jolt_host_gt_pow")
+    return out
+
+
 def host_hyperkzg_witness_triple(c, g0, g1, r, a, alpha):
     """the three witness commitments of an opening (at r, -r, r^2) from c[k] = commit(X^k Q3), the first two SRS points and the remainders a, alpha, on the host"""
     cs = np.ascontiguousarray(c, dtype=np.uint64).reshape(3, 12)

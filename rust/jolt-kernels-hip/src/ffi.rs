@@ -1,7 +1,7 @@
 //! Raw FFI declarations of `libjolt_hip.so` -- GENERATED from `include/jolt_hip.h` by `tools/gen_rust_ffi.py`; do not edit.
 //! One declaration per entry point of the C header, same order, same arity, same types (checked by tests/test_abi_cpu.py).
 //! `jolt_fr_t` is bit-identical to `jolt_field::Fr` (4 x u64 Montgomery limbs, crates/jolt-field/src/bn254/mod.rs:33-43) and
-//! `jolt_g1_t` to `jolt_crypto::Bn254G1` (ark_bn254::G1Projective, crates/jolt-crypto/src/ec/bn254/mod.rs:17-24); `jolt_g2_t` to ark_bn254::G2Projective.
+//! `jolt_g1_t` to `jolt_crypto::Bn254G1` (ark_bn254::G1Projective, crates/jolt-crypto/src/ec/bn254/mod.rs:17-24); `jolt_g2_t` to ark_bn254::G2Projective, `jolt_gt_t` to ark_bn254::Fq12 (Bn254GT).
 #![allow(non_camel_case_types, clippy::too_many_arguments, clippy::missing_safety_doc)]
 use core::ffi::{c_char, c_void};
 
@@ -36,6 +36,11 @@ pub struct jolt_g2_t {
     pub x: jolt_fq2_t,
     pub y: jolt_fq2_t,
     pub z: jolt_fq2_t,
+}
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct jolt_gt_t {
+    pub c: [jolt_fq_t; 12],
 }
 #[repr(C)]
 pub struct jolt_ctx {
@@ -79,6 +84,10 @@ pub struct jolt_onehot {
 }
 #[repr(C)]
 pub struct jolt_rows {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct jolt_g2_prepared {
     _private: [u8; 0],
 }
 #[repr(C)]
@@ -144,6 +153,15 @@ pub const JOLT_FQ2_SUB: i32 = 1;
 pub const JOLT_FQ2_MUL: i32 = 2;
 pub const JOLT_FQ2_SQR: i32 = 3;
 pub const JOLT_FQ2_NEG: i32 = 4;
+pub const JOLT_FQ12_MUL: i32 = 0;
+pub const JOLT_FQ12_SQR: i32 = 1;
+pub const JOLT_FQ12_INV: i32 = 2;
+pub const JOLT_FQ12_CONJ: i32 = 3;
+pub const JOLT_FQ12_FROBENIUS1: i32 = 4;
+pub const JOLT_FQ12_FROBENIUS2: i32 = 5;
+pub const JOLT_FQ12_FROBENIUS3: i32 = 6;
+pub const JOLT_FQ12_MUL_SPARSE: i32 = 7;
+pub const JOLT_PAIRING_LINES: usize = 88;
 pub const JOLT_MAX_MEMBER_TABLES: usize = 40;
 pub const JOLT_MAX_MEMBER_TERMS: usize = 16;
 pub const JOLT_MAX_MEMBER_FACTORS: usize = 64;
@@ -365,6 +383,17 @@ extern "C" {
     pub fn jolt_host_dory_g2_fixed_base_one(base: *const jolt_g2_t, scalar: *const jolt_fr_t, out: *mut jolt_g2_t) -> i32;
     pub fn jolt_host_dory_g1_msm_term(base: *const jolt_g1_t, scalar: *const jolt_fr_t, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_host_dory_g2_msm_term(base: *const jolt_g2_t, scalar: *const jolt_fr_t, out: *mut jolt_g2_t) -> i32;
+    pub fn jolt_dory_multi_pair(ctx: *mut jolt_ctx, g1s: *const jolt_g1_t, g2s: *const jolt_g2_t, n: usize, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_dory_multi_miller(ctx: *mut jolt_ctx, g1s: *const jolt_g1_t, g2s: *const jolt_g2_t, n: usize, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_dory_g2_prepare(ctx: *mut jolt_ctx, g2s: *const jolt_g2_t, n: usize, out: *mut *mut jolt_g2_prepared) -> i32;
+    pub fn jolt_g2_prepared_free(ctx: *mut jolt_ctx, prepared: *mut jolt_g2_prepared) -> i32;
+    pub fn jolt_dory_multi_pair_g2_setup(ctx: *mut jolt_ctx, g1s: *const jolt_g1_t, prepared: *const jolt_g2_prepared, n: usize, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_dory_pairing_timing(ctx: *mut jolt_ctx, enable: i32, out_ms: *mut f64) -> i32;
+    pub fn jolt_host_fq12_op(op: i32, a: *const jolt_gt_t, b: *const jolt_gt_t, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_host_g2_prepare_one(g2: *const jolt_g2_t, lines: *mut jolt_fq2_t, skip: *mut i32) -> i32;
+    pub fn jolt_host_miller_loop(g1s: *const jolt_g1_t, g2s: *const jolt_g2_t, n: usize, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_host_final_exponentiation(f: *const jolt_gt_t, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_host_gt_pow(gt: *const jolt_gt_t, scalar: *const jolt_fr_t, out: *mut jolt_gt_t) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;

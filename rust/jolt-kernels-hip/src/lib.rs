@@ -33,6 +33,7 @@ pub mod leaves;
 pub mod member;
 pub mod msm;
 pub mod opening;
+pub mod pairing;
 pub mod ops;
 pub mod pcs;
 pub mod rows;
@@ -48,6 +49,7 @@ pub use member::{HipMember, HipPrepare, HipSumcheckProver, MemberShape, MemberSl
 pub use msm::{msm_cache_clear, msm_cache_evict, msm_g1, HipShardedOpening, HipSrs, SharedMsmContext};
 pub use ops::{HipHotIndices, HipInts, HipKeyIndex, HipR1csRows, HipReadRaf, HipRegistersRw, HipRwMatrix, RowTerms, RwRow, SpartanSums};
 pub use backend::{mi355x, with_relation, HipCommitWitness, HipUniskip, Mi355xParts, NodeWeights};
+pub use pairing::{multi_pair, multi_pair_g2_setup, HipG2Prepared};
 pub use pcs::{HipHyperKzg, HipHyperKzgSetup, HipPoly};
 pub use rows::{HipPinnedRows, HipRows, HipRowsInFlight};
 pub use scheduler::{HipBuildRoundScheduler, HipRoundScheduler};

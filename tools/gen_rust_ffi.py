@@ -108,7 +108,7 @@ def render(decls):
     out.append("//! Raw FFI declarations of `libjolt_hip.so` -- GENERATED from `include/jolt_hip.h` by `tools/gen_rust_ffi.py`; do not edit.")
     out.append("//! One declaration per entry point of the C header, same order, same arity, same types (checked by tests/test_abi_cpu.py).")
     out.append("//! `jolt_fr_t` is bit-identical to `jolt_field::Fr` (4 x u64 Montgomery limbs, crates/jolt-field/src/bn254/mod.rs:33-43) and")
-    out.append("//! `jolt_g1_t` to `jolt_crypto::Bn254G1` (ark_bn254::G1Projective, crates/jolt-crypto/src/ec/bn254/mod.rs:17-24); `jolt_g2_t` to ark_bn254::G2Projective.")
+    out.append("//! `jolt_g1_t` to `jolt_crypto::Bn254G1` (ark_bn254::G1Projective, crates/jolt-crypto/src/ec/bn254/mod.rs:17-24); `jolt_g2_t` to ark_bn254::G2Projective, `jolt_gt_t` to ark_bn254::Fq12 (Bn254GT).")
     out.append("#![allow(non_camel_case_types, clippy::too_many_arguments, clippy::missing_safety_doc)]")
     out.append("use core::ffi::{c_char, c_void};")
     out.append("")
@@ -119,6 +119,7 @@ def render(decls):
     out.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]\npub struct jolt_g1_t {\n    pub x: jolt_fq_t,\n    pub y: jolt_fq_t,\n    pub z: jolt_fq_t,\n}")
     out.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]\npub struct jolt_fq2_t {\n    pub c0: jolt_fq_t,\n    pub c1: jolt_fq_t,\n}")
     out.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]\npub struct jolt_g2_t {\n    pub x: jolt_fq2_t,\n    pub y: jolt_fq2_t,\n    pub z: jolt_fq2_t,\n}")
+    out.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]\npub struct jolt_gt_t {\n    pub c: [jolt_fq_t; 12],\n}")
     for o in opaque_handles():
         out.append(f"#[repr(C)]\npub struct {o} {{\n    _private: [u8; 0],\n}}")
     out.append("")
@@ -130,6 +131,8 @@ def render(decls):
     out.append("pub const JOLT_MEMBER_FLAG_SKIP_ONE: u32 = 1;\npub const JOLT_MEMBER_FLAG_BORROW_TABLES: u32 = 2;")
     out.append("pub const JOLT_INT_U64: i32 = 0;\npub const JOLT_INT_I64: i32 = 1;\npub const JOLT_INT_I128: i32 = 2;\npub const JOLT_SCALAR_FR: i32 = 3;")
     out.append("pub const JOLT_FQ2_ADD: i32 = 0;\npub const JOLT_FQ2_SUB: i32 = 1;\npub const JOLT_FQ2_MUL: i32 = 2;\npub const JOLT_FQ2_SQR: i32 = 3;\npub const JOLT_FQ2_NEG: i32 = 4;")
+    out.append("pub const JOLT_FQ12_MUL: i32 = 0;\npub const JOLT_FQ12_SQR: i32 = 1;\npub const JOLT_FQ12_INV: i32 = 2;\npub const JOLT_FQ12_CONJ: i32 = 3;\npub const JOLT_FQ12_FROBENIUS1: i32 = 4;\n"
+               "pub const JOLT_FQ12_FROBENIUS2: i32 = 5;\npub const JOLT_FQ12_FROBENIUS3: i32 = 6;\npub const JOLT_FQ12_MUL_SPARSE: i32 = 7;\npub const JOLT_PAIRING_LINES: usize = 88;")
     out.append("pub const JOLT_MAX_MEMBER_TABLES: usize = 40;\npub const JOLT_MAX_MEMBER_TERMS: usize = 16;\npub const JOLT_MAX_MEMBER_FACTORS: usize = 64;\npub const JOLT_MAX_DEGREE: usize = 7;")
     out.append("")
     out.append("#[repr(C)]\npub struct jolt_member_desc {\n    pub n_tables: u32,\n    pub n_terms: u32,\n    pub degree: u32,\n    pub order: i32,\n"
