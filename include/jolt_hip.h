@@ -682,6 +682,63 @@ int32_t jolt_host_final_exponentiation(const jolt_gt_t *f, jolt_gt_t *out);
 /* gt^scalar by square-and-multiply over the canonical scalar: the GT scaling that stays with the caller */
 int32_t jolt_host_gt_pow(const jolt_gt_t *gt, const jolt_fr_t *scalar, jolt_gt_t *out);
 
+/* Dory's reduce-and-fold rounds on vectors that stay on the device.  A jolt_dory_vec is a device array of G1 points, G2 points or Fr elements from the context's
+ * pool; the routines and multi-pairings above take host pointers, so a round through them uploads, runs alone, synchronises and downloads once per product.  Here
+ * the argument checks of those entry points -- canonical coordinates, the curve or twist equation (no subgroup check), canonical scalars -- run ONCE, in
+ * jolt_dory_vec_upload; nothing below re-checks a resident vector.  A view is (vector, first, n) with first <= len and n <= len - first.  Every entry refuses with
+ * JOLT_ERR_INVALID_ARG: a null handle, a vector of another context or of the wrong kind, a view outside its vector; a refused call enqueues nothing and writes
+ * nothing.  Resident operations and product batches take effect in call order on a context. */
+typedef struct jolt_dory_vec jolt_dory_vec;
+enum { JOLT_DORY_KIND_G1 = 0, JOLT_DORY_KIND_G2 = 1, JOLT_DORY_KIND_FR = 2 };
+/* host: n elements of jolt_g1_t / jolt_g2_t / jolt_fr_t by kind; n = 0 gives an empty vector; n <= 2^30 */
+int32_t jolt_dory_vec_upload(jolt_ctx *ctx, int32_t kind, const void *host, size_t n, jolt_dory_vec **out);
+int32_t jolt_dory_vec_download(jolt_ctx *ctx, const jolt_dory_vec *vec, size_t first, size_t n, void *host);
+int32_t jolt_dory_vec_len(const jolt_dory_vec *vec, size_t *len);
+int32_t jolt_dory_vec_kind(const jolt_dory_vec *vec, int32_t *kind);
+int32_t jolt_dory_vec_free(jolt_ctx *ctx, jolt_dory_vec *vec);
+/* the vector becomes its first n elements (after a fold, its first half); n > len is refused */
+int32_t jolt_dory_vec_truncate(jolt_dory_vec *vec, size_t n);
+/* jolt_dory_g2_prepare from elements [first, first + n) of a resident G2 vector, with no host round trip: once per setup for the g2_vec bases -- a prefix of the
+ * table serves every later round (jolt_dory_item.prepared_first) */
+int32_t jolt_dory_g2_prepare_vec(jolt_ctx *ctx, const jolt_dory_vec *vec, size_t first, size_t n, jolt_g2_prepared **out);
+/* The shared-scalar routines and the field fold in place on views, enqueued on the context's stream (no synchronisation): the per-element functions of
+ * jolt_dory_g{1,2}_scale_bases_add, _scale_vs_add and jolt_dory_fold_field_vectors.  Both vectors of a call have the same kind (G1 or G2; Fr for the fold).  The
+ * two views may lie in one vector if their ranges are disjoint -- the fold v <- alpha v_L + v_R; overlapping ranges are refused. */
+/* vs[vs_first + i] += scalar * bases[bases_first + i] */
+int32_t jolt_dory_vec_scale_bases_add(jolt_ctx *ctx, const jolt_dory_vec *bases, size_t bases_first, jolt_dory_vec *vs, size_t vs_first, size_t n, const jolt_fr_t *scalar);
+/* vs[vs_first + i] = scalar * vs[vs_first + i] + addends[addends_first + i] */
+int32_t jolt_dory_vec_scale_vs_add(jolt_ctx *ctx, jolt_dory_vec *vs, size_t vs_first, const jolt_dory_vec *addends, size_t addends_first, size_t n, const jolt_fr_t *scalar);
+/* left[left_first + i] = left[left_first + i] * scalar + right[right_first + i] */
+int32_t jolt_dory_vec_fold_field(jolt_ctx *ctx, jolt_dory_vec *left, size_t left_first, const jolt_dory_vec *right, size_t right_first, size_t n, const jolt_fr_t *scalar);
+/* A batch of inner products over resident views, one launch set for all of them: per item
+ *   JOLT_DORY_PAIR    prod_i e(a[a_first + i], b[b_first + i]); a is a G1 vector, b a G2 vector -- or NULL, and the G2 side is points
+ *                     [prepared_first, prepared_first + n) of `prepared`
+ *   JOLT_DORY_MSM_G1  sum_i b[b_first + i] * a[a_first + i]; a is a G1 vector, b an Fr vector (`prepared` is NULL)
+ *   JOLT_DORY_MSM_G2  the same with a G2 vector
+ * The pairing chain (one prepare launch over the distinct G2 views, one Miller launch over all pairs, one product level per launch over all items' segments), the
+ * G1 chain and the G2 chain (one term launch, one addition level per launch) run on three streams beside each other; one read-back, one synchronisation, then one
+ * final exponentiation per PAIR item on up to 16 host threads.  outs[k] holds item k's result in its leading words: a jolt_gt_t (48 words, the canonical value,
+ * bit for bit jolt_dory_multi_pair's), a jolt_g1_t (12) or a jolt_g2_t (24), normalised as jolt_dory_g{1,2}_msm normalises; the rest of outs[k] is not written.
+ * An empty item gives one, or the identity (1, 1, 0).  The sum of the item lengths is at most 2^24 per chain (JOLT_ERR_UNSUPPORTED above). */
+enum { JOLT_DORY_PAIR = 0, JOLT_DORY_MSM_G1 = 1, JOLT_DORY_MSM_G2 = 2 };
+typedef struct {
+    int32_t op;
+    const jolt_dory_vec *a;
+    size_t a_first;
+    const jolt_dory_vec *b;
+    size_t b_first;
+    const jolt_g2_prepared *prepared;
+    size_t prepared_first;
+    size_t n;
+} jolt_dory_item;
+typedef struct { uint64_t w[48]; } jolt_dory_result;
+int32_t jolt_dory_products(jolt_ctx *ctx, const jolt_dory_item *items, size_t n_items, jolt_dory_result *outs);
+/* The launch plan of one chain of a batch, for the CPU suite: item k of length lens[k] is padded to whole wavefronts of 64 lanes, so a workgroup belongs to one
+ * item; item_base[k] = the item's first slot in the chain's packed array (the padded lengths before it); workgroup w works on slots item_base[wg_item[w]] +
+ * wg_first[w] + lane; *levels = ceil(log2) of the longest item, the launches of the segmented reduction.  wg_item / wg_first hold wg_cap entries and may be NULL
+ * with wg_cap = 0 to ask for *n_wgs alone; more workgroups than wg_cap is JOLT_ERR_SIZE_MISMATCH, a padded total above 2^24 JOLT_ERR_UNSUPPORTED. */
+int32_t jolt_host_dory_batch_plan(const size_t *lens, size_t n_items, size_t wg_cap, uint32_t *wg_item, uint32_t *wg_first, size_t *item_base, size_t *n_wgs, uint32_t *levels);
+
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)
  * for witness columns that already sit in HBM (no host round trip; jolt_table_from_u64 is the same from host memory). */

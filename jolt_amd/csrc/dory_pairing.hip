@@ -16,29 +16,18 @@
 
 #include "ctx.hpp"
 #include "dory_host.hpp"
+#include "dory_prepared.hip.h"
 #include "pairing.hip.h"
 
 using namespace jolt;
 using namespace jolt::dory_host;
+using namespace jolt::dory_dev;
 
 static_assert(sizeof(jolt_gt_t) == sizeof(Fq12) && sizeof(jolt_g1_t) == sizeof(G1Jac) && sizeof(jolt_g2_t) == sizeof(G2Jac), "pairing ABI layouts");
 static_assert(JOLT_PAIRING_LINES == kPairingLines, "jolt_hip.h and pairing_constants.hip.h disagree on the line count");
 
-struct jolt_g2_prepared {
-    jolt_ctx* ctx = nullptr;
-    size_t n = 0;
-    PairLine* lines = nullptr;  // device, [kPairingLines][n]
-    uint8_t* skip = nullptr;    // device, [n]: the point is the identity
-};
-
 namespace {
 
-__global__ __launch_bounds__(kLanes) void k_pair_prepare_g2(const G2Jac* __restrict__ pts, PairLine* __restrict__ lines, uint8_t* __restrict__ skip, size_t n) {
-    const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
-    if (i >= n) return;
-    const PairLineTable table = {lines + i, n};
-    skip[i] = g2_prepare_walk(pts[i], table) ? 1 : 0;
-}
 // lines: a table of `stride` >= n points, of which the first n are used
 __global__ __launch_bounds__(kLanes) void k_pair_miller(const G1Jac* __restrict__ g1s, const PairLine* lines, const uint8_t* __restrict__ skip, size_t stride, Fq12* __restrict__ out, size_t n) {
     const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
@@ -87,11 +76,6 @@ struct Phases {
         return e;
     }
 };
-
-hipError_t launch_prepare(hipStream_t st, const G2Jac* d_g2, PairLine* d_lines, uint8_t* d_skip, size_t n) {
-    hipLaunchKernelGGL(k_pair_prepare_g2, dim3(lanes_grid(n)), dim3(kLanes), 0, st, d_g2, d_lines, d_skip, n);
-    return hipGetLastError();
-}
 
 // Miller values of (d_g1[i], table point i), i < n, their product into *raw; n > 0
 int32_t miller_product(jolt_ctx* ctx, Phases& ph, DevBufs& bufs, const G1Jac* d_g1, const PairLine* d_lines, const uint8_t* d_skip, size_t stride, size_t n, Fq12* raw, const char* what) {

@@ -1504,6 +1504,140 @@ Context.dory_multi_pair_g2_setup = _dory_multi_pair_g2_setup
 Context.dory_pairing_timing = _dory_pairing_timing
 
 
+# ---- Dory's rounds on resident vectors (dory_resident.hip): vectors that stay in HBM, in-place routines on views, product batches
+DORY_KIND_G1, DORY_KIND_G2, DORY_KIND_FR = range(3)
+DORY_PAIR, DORY_MSM_G1, DORY_MSM_G2 = range(3)
+_DORY_KIND_WIDTH = {DORY_KIND_G1: 12, DORY_KIND_G2: 24, DORY_KIND_FR: 4}
+_DORY_RESULT_WIDTH = {DORY_PAIR: 48, DORY_MSM_G1: 12, DORY_MSM_G2: 24}
+
+
+class DoryItem(C.Structure):
+    """jolt_dory_item"""
+    _fields_ = [("op", C.c_int32), ("a", C.c_void_p), ("a_first", C.c_size_t), ("b", C.c_void_p), ("b_first", C.c_size_t),
+                ("prepared", C.c_void_p), ("prepared_first", C.c_size_t), ("n", C.c_size_t)]
+
+
+class DoryVec:
+    """A G1 / G2 / Fr array resident on the device (jolt_dory_vec); its elements were checked when it was uploaded.  v.view(first, n) names a range of it."""
+
+    def __init__(self, ctx, h, kind):
+        self.ctx, self.h, self.kind = ctx, h, kind
+
+    def __len__(self):
+        n = C.c_size_t()
+        _ck(lib().jolt_dory_vec_len(self.h, C.byref(n)), "jolt_dory_vec_len", self.ctx)
+        return n.value
+
+    def view(self, first=0, n=None):
+        return (self, first, len(self) - first if n is None else n)
+
+    def device_kind(self):
+        """the kind the library holds for the handle"""
+        k = C.c_int32()
+        _ck(lib().jolt_dory_vec_kind(self.h, C.byref(k)), "jolt_dory_vec_kind", self.ctx)
+        return k.value
+
+    def download(self, first=0, n=None):
+        n = len(self) - first if n is None else n
+        out = np.zeros((n, _DORY_KIND_WIDTH[self.kind]), dtype=np.uint64)
+        _ck(lib().jolt_dory_vec_download(self.ctx.h, self.h, C.c_size_t(first), C.c_size_t(n), _p(out) if n else None), "jolt_dory_vec_download", self.ctx)
+        return out
+
+    def truncate(self, n):
+        _ck(lib().jolt_dory_vec_truncate(self.h, C.c_size_t(n)), "jolt_dory_vec_truncate", self.ctx)
+
+    def free(self):
+        if self.h:
+            _ck(lib().jolt_dory_vec_free(self.ctx.h, self.h), "jolt_dory_vec_free", self.ctx)
+            self.h = None
+
+
+def _dory_view(v):
+    """a DoryVec (all of it) or (DoryVec, first, n)"""
+    return v.view() if isinstance(v, DoryVec) else v
+
+
+def _dory_vec_upload(self, kind, host):
+    a = np.ascontiguousarray(host, dtype=np.uint64).reshape(-1, _DORY_KIND_WIDTH[kind])
+    h = C.c_void_p()
+    _ck(lib().jolt_dory_vec_upload(self.h, C.c_int32(kind), _p(a) if a.shape[0] else None, C.c_size_t(a.shape[0]), C.byref(h)), "jolt_dory_vec_upload", self)
+    return DoryVec(self, h, kind)
+
+
+def _dory_g2_prepare_vec(self, view):
+    """the line table of a resident G2 view, built on the device (jolt_dory_g2_prepare_vec)"""
+    v, first, n = _dory_view(view)
+    h = C.c_void_p()
+    _ck(lib().jolt_dory_g2_prepare_vec(self.h, v.h, C.c_size_t(first), C.c_size_t(n), C.byref(h)), "jolt_dory_g2_prepare_vec", self)
+    return G2Prepared(self, h, n)
+
+
+def _dory_two_views(x, y):
+    (xv, xf, xn), (yv, yf, yn) = _dory_view(x), _dory_view(y)
+    if xn != yn:
+        raise ValueError("the two views differ in length")
+    return xv, xf, yv, yf, xn
+
+
+def _dory_vec_scale_bases_add(self, bases, vs, scalar):
+    """vs[i] += scalar * bases[i] in place on views (fixed_scalar_mul_bases_then_add); enqueued, not awaited"""
+    bv, bf, vv, vf, n = _dory_two_views(bases, vs)
+    _ck(lib().jolt_dory_vec_scale_bases_add(self.h, bv.h, C.c_size_t(bf), vv.h, C.c_size_t(vf), C.c_size_t(n), _p(fr(scalar))), "jolt_dory_vec_scale_bases_add", self)
+
+
+def _dory_vec_scale_vs_add(self, vs, addends, scalar):
+    """vs[i] = scalar * vs[i] + addends[i] in place on views (fixed_scalar_mul_vs_then_add); enqueued, not awaited"""
+    vv, vf, av, af, n = _dory_two_views(vs, addends)
+    _ck(lib().jolt_dory_vec_scale_vs_add(self.h, vv.h, C.c_size_t(vf), av.h, C.c_size_t(af), C.c_size_t(n), _p(fr(scalar))), "jolt_dory_vec_scale_vs_add", self)
+
+
+def _dory_vec_fold_field(self, left, right, scalar):
+    """left[i] = left[i] * scalar + right[i] in place on Fr views (fold_field_vectors); enqueued, not awaited"""
+    lv, lf, rv, rf, n = _dory_two_views(left, right)
+    _ck(lib().jolt_dory_vec_fold_field(self.h, lv.h, C.c_size_t(lf), rv.h, C.c_size_t(rf), C.c_size_t(n), _p(fr(scalar))), "jolt_dory_vec_fold_field", self)
+
+
+def dory_item(op, a, b, prepared_first=0):
+    """one item of a product batch: a, b = DoryVec or (DoryVec, first, n); for DORY_PAIR b may be a G2Prepared, read from point prepared_first on"""
+    av, af, n = _dory_view(a)
+    if isinstance(b, G2Prepared):
+        return DoryItem(op, av.h, af, None, 0, b.h, prepared_first, n)
+    bv, bf, bn = _dory_view(b)
+    if bn != n:
+        raise ValueError("the two views of an item differ in length")
+    return DoryItem(op, av.h, af, bv.h, bf, None, 0, n)
+
+
+def _dory_products(self, items):
+    """jolt_dory_products: every item (dory_item) of the list in one launch set; one (48,) GT, (12,) G1 or (24,) G2 array per item"""
+    n = len(items)
+    arr = (DoryItem * max(n, 1))(*items)
+    outs = np.zeros((max(n, 1), 48), dtype=np.uint64)
+    _ck(lib().jolt_dory_products(self.h, arr if n else None, C.c_size_t(n), _p(outs) if n else None), "jolt_dory_products", self)
+    return [outs[k, :_DORY_RESULT_WIDTH[items[k].op]].copy() for k in range(n)]
+
+
+def host_dory_batch_plan(lens):
+    """the launch plan of one chain of a product batch (dory_batch_plan.hpp): (wg_item, wg_first, item_base, levels)"""
+    n = len(lens)
+    a = (C.c_size_t * max(n, 1))(*lens)
+    base = (C.c_size_t * max(n, 1))()
+    n_wgs, levels = C.c_size_t(), C.c_uint32()
+    _ck(lib().jolt_host_dory_batch_plan(a, C.c_size_t(n), C.c_size_t(0), None, None, base, C.byref(n_wgs), C.byref(levels)), "jolt_host_dory_batch_plan")
+    w = n_wgs.value
+    wg_item, wg_first = np.zeros(max(w, 1), dtype=np.uint32), np.zeros(max(w, 1), dtype=np.uint32)
+    _ck(lib().jolt_host_dory_batch_plan(a, C.c_size_t(n), C.c_size_t(max(w, 1)), _p(wg_item), _p(wg_first), base, C.byref(n_wgs), C.byref(levels)), "jolt_host_dory_batch_plan")
+    return wg_item[:w], wg_first[:w], [int(b) for b in base[:n]], levels.value
+
+
+Context.dory_vec_upload = _dory_vec_upload
+Context.dory_g2_prepare_vec = _dory_g2_prepare_vec
+Context.dory_vec_scale_bases_add = _dory_vec_scale_bases_add
+Context.dory_vec_scale_vs_add = _dory_vec_scale_vs_add
+Context.dory_vec_fold_field = _dory_vec_fold_field
+Context.dory_products = _dory_products
+
+
 def _gt(a):
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(48)
 

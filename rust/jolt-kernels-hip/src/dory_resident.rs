@@ -1,0 +1,212 @@
+//! Dory's reduce-and-fold rounds on vectors that stay on the device: thin safe wrappers over `jolt_dory_vec_*`, `jolt_dory_g2_prepare_vec`
+//! and `jolt_dory_products`.
+//!
+//! WRITTEN BLIND, like the rest of this crate: no Rust toolchain has seen this file.  dory's `DoryRoutines` seam works on host slices and its
+//! `multi_pair` on host slices too, so nothing here binds to a trait: a caller reaches these wrappers from a prover loop of its own in front of
+//! dory, handing every challenge in.  The library is agnostic about which half a message calls left and which of a challenge
+//! and its inverse folds which vector; `jolt_amd/dory_reduce.py` is the statement of the Dory paper's choice (docs/parity.md).
+//!
+//! Elements are checked once, in [`HipDoryVec::upload`]; values of the arkworks types are always canonical and on their curves, so a refusal
+//! there is a bug and surfaces as the `HipError` of the call.  Views are `(vector, first, n)`; the library refuses a view outside its vector.
+use std::sync::Arc;
+
+use dory::backends::arkworks::{ArkFr, ArkG1, ArkG2, ArkGT};
+
+use crate::context::HipContext;
+use crate::ffi;
+use crate::pairing::HipG2Prepared;
+use crate::status::{check, HipError};
+
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum VecKind {
+    G1,
+    G2,
+    Fr,
+}
+
+impl VecKind {
+    fn raw(self) -> i32 {
+        match self {
+            VecKind::G1 => ffi::JOLT_DORY_KIND_G1,
+            VecKind::G2 => ffi::JOLT_DORY_KIND_G2,
+            VecKind::Fr => ffi::JOLT_DORY_KIND_FR,
+        }
+    }
+}
+
+/// A G1, G2 or Fr array resident on the device.
+pub struct HipDoryVec {
+    ctx: Arc<HipContext>,
+    raw: *mut ffi::jolt_dory_vec,
+    kind: VecKind,
+}
+
+impl HipDoryVec {
+    fn upload(ctx: &Arc<HipContext>, kind: VecKind, host: *const core::ffi::c_void, n: usize) -> Result<Self, HipError> {
+        let mut raw = core::ptr::null_mut();
+        let _device = ctx.exclusive();
+        // SAFETY: `host` points at `n` elements of the kind's ABI type (the callers below pass slices of the layout-compatible arkworks types).
+        check(unsafe { ffi::jolt_dory_vec_upload(ctx.raw, kind.raw(), host, n, &mut raw) }, ctx.raw)?;
+        Ok(Self { ctx: Arc::clone(ctx), raw, kind })
+    }
+
+    pub fn from_g1(ctx: &Arc<HipContext>, points: &[ArkG1]) -> Result<Self, HipError> {
+        Self::upload(ctx, VecKind::G1, points.as_ptr().cast(), points.len())
+    }
+
+    pub fn from_g2(ctx: &Arc<HipContext>, points: &[ArkG2]) -> Result<Self, HipError> {
+        Self::upload(ctx, VecKind::G2, points.as_ptr().cast(), points.len())
+    }
+
+    pub fn from_fr(ctx: &Arc<HipContext>, scalars: &[ArkFr]) -> Result<Self, HipError> {
+        Self::upload(ctx, VecKind::Fr, scalars.as_ptr().cast(), scalars.len())
+    }
+
+    pub fn kind(&self) -> VecKind {
+        self.kind
+    }
+
+    pub fn len(&self) -> usize {
+        let mut n = 0usize;
+        // SAFETY: `raw` is a live handle.
+        unsafe { ffi::jolt_dory_vec_len(self.raw, &mut n) };
+        n
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+
+    /// The vector becomes its first `n` elements: after a fold, its first half.
+    pub fn truncate(&mut self, n: usize) -> Result<(), HipError> {
+        // SAFETY: `raw` is a live handle.
+        check(unsafe { ffi::jolt_dory_vec_truncate(self.raw, n) }, self.ctx.raw)
+    }
+
+    /// Elements `[first, first + out.len())` of a G1 vector.
+    pub fn download_g1(&self, first: usize, out: &mut [ArkG1]) -> Result<(), HipError> {
+        assert_eq!(self.kind, VecKind::G1);
+        self.download(first, out.len(), out.as_mut_ptr().cast())
+    }
+
+    pub fn download_g2(&self, first: usize, out: &mut [ArkG2]) -> Result<(), HipError> {
+        assert_eq!(self.kind, VecKind::G2);
+        self.download(first, out.len(), out.as_mut_ptr().cast())
+    }
+
+    pub fn download_fr(&self, first: usize, out: &mut [ArkFr]) -> Result<(), HipError> {
+        assert_eq!(self.kind, VecKind::Fr);
+        self.download(first, out.len(), out.as_mut_ptr().cast())
+    }
+
+    fn download(&self, first: usize, n: usize, host: *mut core::ffi::c_void) -> Result<(), HipError> {
+        let _device = self.ctx.exclusive();
+        // SAFETY: `host` has room for `n` elements of this vector's kind (asserted by the typed callers above).
+        check(unsafe { ffi::jolt_dory_vec_download(self.ctx.raw, self.raw, first, n, host) }, self.ctx.raw)
+    }
+
+    /// The line table of G2 points `[first, first + n)`, built on the device: once per setup for the `g2_vec` bases.
+    pub fn prepare_g2(&self, first: usize, n: usize) -> Result<HipG2Prepared, HipError> {
+        let mut raw = core::ptr::null_mut();
+        let _device = self.ctx.exclusive();
+        // SAFETY: `self.raw` is a live handle; the library refuses a vector that is not G2 and a view outside it.
+        check(unsafe { ffi::jolt_dory_g2_prepare_vec(self.ctx.raw, self.raw, first, n, &mut raw) }, self.ctx.raw)?;
+        Ok(HipG2Prepared { ctx: Arc::clone(&self.ctx), raw, len: n })
+    }
+
+    /// `self[vs_first + i] += scalar * bases[bases_first + i]`: `fixed_scalar_mul_bases_then_add` in place, enqueued.
+    pub fn scale_bases_add(&mut self, vs_first: usize, bases: &HipDoryVec, bases_first: usize, n: usize, scalar: &ArkFr) -> Result<(), HipError> {
+        let _device = self.ctx.exclusive();
+        // SAFETY: live handles; `ArkFr` is layout-compatible with `jolt_fr_t` (asserted in dory_routines.rs); the library validates kinds and views.
+        check(unsafe { ffi::jolt_dory_vec_scale_bases_add(self.ctx.raw, bases.raw, bases_first, self.raw, vs_first, n, (scalar as *const ArkFr).cast()) }, self.ctx.raw)
+    }
+
+    /// `self[vs_first + i] = scalar * self[vs_first + i] + addends[addends_first + i]`: `fixed_scalar_mul_vs_then_add` in place, enqueued.
+    pub fn scale_vs_add(&mut self, vs_first: usize, addends: &HipDoryVec, addends_first: usize, n: usize, scalar: &ArkFr) -> Result<(), HipError> {
+        let _device = self.ctx.exclusive();
+        // SAFETY: as scale_bases_add.
+        check(unsafe { ffi::jolt_dory_vec_scale_vs_add(self.ctx.raw, self.raw, vs_first, addends.raw, addends_first, n, (scalar as *const ArkFr).cast()) }, self.ctx.raw)
+    }
+
+    /// The fold of one vector onto its first half: `self[i] = scalar * self[i] + self[n + i]` for `i < n` (points), or `self[i] * scalar + self[n + i]` (Fr);
+    /// the vector is then truncated to `n`.
+    pub fn fold_halves(&mut self, n: usize, scalar: &ArkFr) -> Result<(), HipError> {
+        let s = (scalar as *const ArkFr).cast();
+        {
+            let _device = self.ctx.exclusive();
+            // SAFETY: one live handle for both views; the library refuses ranges that overlap or leave the vector.
+            let status = unsafe {
+                match self.kind {
+                    VecKind::Fr => ffi::jolt_dory_vec_fold_field(self.ctx.raw, self.raw, 0, self.raw, n, n, s),
+                    _ => ffi::jolt_dory_vec_scale_vs_add(self.ctx.raw, self.raw, 0, self.raw, n, n, s),
+                }
+            };
+            check(status, self.ctx.raw)?;
+        }
+        self.truncate(n)
+    }
+}
+
+impl Drop for HipDoryVec {
+    fn drop(&mut self) {
+        let _device = self.ctx.exclusive();
+        // SAFETY: `raw` came from jolt_dory_vec_upload on this context and is freed once.
+        unsafe { ffi::jolt_dory_vec_free(self.ctx.raw, self.raw) };
+    }
+}
+
+/// One inner product of a batch, over views `(vector, first)` of `n` elements.
+pub enum DoryItem<'a> {
+    /// `prod_i e(a[i], b[i])`
+    Pair { a: (&'a HipDoryVec, usize), b: (&'a HipDoryVec, usize), n: usize },
+    /// `prod_i e(a[i], prepared point first + i)`
+    PairPrepared { a: (&'a HipDoryVec, usize), prepared: (&'a HipG2Prepared, usize), n: usize },
+    /// `sum_i scalars[i] * points[i]`, G1 or G2 by the kind of `points`
+    Msm { points: (&'a HipDoryVec, usize), scalars: (&'a HipDoryVec, usize), n: usize },
+}
+
+pub enum DoryProduct {
+    Gt(ArkGT),
+    G1(ArkG1),
+    G2(ArkG2),
+}
+
+/// Every item in one launch set, one synchronisation: `jolt_dory_products`.
+pub fn products(ctx: &Arc<HipContext>, items: &[DoryItem<'_>]) -> Result<Vec<DoryProduct>, HipError> {
+    let raw_items: Vec<ffi::jolt_dory_item> = items
+        .iter()
+        .map(|it| match *it {
+            DoryItem::Pair { a, b, n } => ffi::jolt_dory_item { op: ffi::JOLT_DORY_PAIR, a: a.0.raw, a_first: a.1, b: b.0.raw, b_first: b.1, prepared: core::ptr::null(), prepared_first: 0, n },
+            DoryItem::PairPrepared { a, prepared, n } => {
+                ffi::jolt_dory_item { op: ffi::JOLT_DORY_PAIR, a: a.0.raw, a_first: a.1, b: core::ptr::null(), b_first: 0, prepared: prepared.0.raw, prepared_first: prepared.1, n }
+            }
+            DoryItem::Msm { points, scalars, n } => {
+                let op = if points.0.kind == VecKind::G1 { ffi::JOLT_DORY_MSM_G1 } else { ffi::JOLT_DORY_MSM_G2 };
+                ffi::jolt_dory_item { op, a: points.0.raw, a_first: points.1, b: scalars.0.raw, b_first: scalars.1, prepared: core::ptr::null(), prepared_first: 0, n }
+            }
+        })
+        .collect();
+    let mut outs = vec![ffi::jolt_dory_result { w: [0u64; 48] }; items.len()];
+    {
+        let _device = ctx.exclusive();
+        // SAFETY: `raw_items` and `outs` hold `items.len()` entries; every handle is borrowed for the call.
+        check(unsafe { ffi::jolt_dory_products(ctx.raw, raw_items.as_ptr(), raw_items.len(), outs.as_mut_ptr()) }, ctx.raw)?;
+    }
+    Ok(raw_items
+        .iter()
+        .zip(outs.iter())
+        .map(|(it, out)| {
+            // SAFETY: the result block holds the item's value in its leading words; `ArkGT` / `ArkG1` / `ArkG2` are layout-compatible with
+            // `jolt_gt_t` / `jolt_g1_t` / `jolt_g2_t` (asserted in pairing.rs and dory_routines.rs) and no larger than the block.
+            unsafe {
+                if it.op == ffi::JOLT_DORY_PAIR {
+                    DoryProduct::Gt(core::mem::transmute_copy::<ffi::jolt_dory_result, ArkGT>(out))
+                } else if it.op == ffi::JOLT_DORY_MSM_G1 {
+                    DoryProduct::G1(core::mem::transmute_copy::<ffi::jolt_dory_result, ArkG1>(out))
+                } else {
+                    DoryProduct::G2(core::mem::transmute_copy::<ffi::jolt_dory_result, ArkG2>(out))
+                }
+            }
+        })
+        .collect())
+}

@@ -91,6 +91,10 @@ pub struct jolt_g2_prepared {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct jolt_dory_vec {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct jolt_read_raf {
     _private: [u8; 0],
 }
@@ -162,6 +166,12 @@ pub const JOLT_FQ12_FROBENIUS2: i32 = 5;
 pub const JOLT_FQ12_FROBENIUS3: i32 = 6;
 pub const JOLT_FQ12_MUL_SPARSE: i32 = 7;
 pub const JOLT_PAIRING_LINES: usize = 88;
+pub const JOLT_DORY_KIND_G1: i32 = 0;
+pub const JOLT_DORY_KIND_G2: i32 = 1;
+pub const JOLT_DORY_KIND_FR: i32 = 2;
+pub const JOLT_DORY_PAIR: i32 = 0;
+pub const JOLT_DORY_MSM_G1: i32 = 1;
+pub const JOLT_DORY_MSM_G2: i32 = 2;
 pub const JOLT_MAX_MEMBER_TABLES: usize = 40;
 pub const JOLT_MAX_MEMBER_TERMS: usize = 16;
 pub const JOLT_MAX_MEMBER_FACTORS: usize = 64;
@@ -191,6 +201,22 @@ pub struct jolt_member_lc_desc {
     pub factor_consts: *const jolt_fr_t,
     pub lc_tables: *const u32,
     pub lc_coeffs: *const jolt_fr_t,
+}
+#[repr(C)]
+pub struct jolt_dory_item {
+    pub op: i32,
+    pub a: *const jolt_dory_vec,
+    pub a_first: usize,
+    pub b: *const jolt_dory_vec,
+    pub b_first: usize,
+    pub prepared: *const jolt_g2_prepared,
+    pub prepared_first: usize,
+    pub n: usize,
+}
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct jolt_dory_result {
+    pub w: [u64; 48],
 }
 pub type jolt_local_round_fn = Option<
     unsafe extern "C" fn(user: *mut c_void, active: *const usize, n_active: usize, binds: *const *const jolt_fr_t, evals_out: *mut jolt_fr_t, evals_count: usize) -> i32,
@@ -394,6 +420,18 @@ extern "C" {
     pub fn jolt_host_miller_loop(g1s: *const jolt_g1_t, g2s: *const jolt_g2_t, n: usize, out: *mut jolt_gt_t) -> i32;
     pub fn jolt_host_final_exponentiation(f: *const jolt_gt_t, out: *mut jolt_gt_t) -> i32;
     pub fn jolt_host_gt_pow(gt: *const jolt_gt_t, scalar: *const jolt_fr_t, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_dory_vec_upload(ctx: *mut jolt_ctx, kind: i32, host: *const c_void, n: usize, out: *mut *mut jolt_dory_vec) -> i32;
+    pub fn jolt_dory_vec_download(ctx: *mut jolt_ctx, vec: *const jolt_dory_vec, first: usize, n: usize, host: *mut c_void) -> i32;
+    pub fn jolt_dory_vec_len(vec: *const jolt_dory_vec, len: *mut usize) -> i32;
+    pub fn jolt_dory_vec_kind(vec: *const jolt_dory_vec, kind: *mut i32) -> i32;
+    pub fn jolt_dory_vec_free(ctx: *mut jolt_ctx, vec: *mut jolt_dory_vec) -> i32;
+    pub fn jolt_dory_vec_truncate(vec: *mut jolt_dory_vec, n: usize) -> i32;
+    pub fn jolt_dory_g2_prepare_vec(ctx: *mut jolt_ctx, vec: *const jolt_dory_vec, first: usize, n: usize, out: *mut *mut jolt_g2_prepared) -> i32;
+    pub fn jolt_dory_vec_scale_bases_add(ctx: *mut jolt_ctx, bases: *const jolt_dory_vec, bases_first: usize, vs: *mut jolt_dory_vec, vs_first: usize, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_vec_scale_vs_add(ctx: *mut jolt_ctx, vs: *mut jolt_dory_vec, vs_first: usize, addends: *const jolt_dory_vec, addends_first: usize, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_vec_fold_field(ctx: *mut jolt_ctx, left: *mut jolt_dory_vec, left_first: usize, right: *const jolt_dory_vec, right_first: usize, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_products(ctx: *mut jolt_ctx, items: *const jolt_dory_item, n_items: usize, outs: *mut jolt_dory_result) -> i32;
+    pub fn jolt_host_dory_batch_plan(lens: *const usize, n_items: usize, wg_cap: usize, wg_item: *mut u32, wg_first: *mut u32, item_base: *mut usize, n_wgs: *mut usize, levels: *mut u32) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;

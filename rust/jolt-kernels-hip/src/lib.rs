@@ -19,6 +19,7 @@
 //! | the eleven cycle-domain relation slots of stages 2 - 6b (`crates/jolt-kernels/src/reference/*.rs`) | [`leaves`]: one `ResolveLeaves` per relation for [`member::HipPrepare`] |
 //! | `CommitmentScheme::OpeningHint`, `AdditivelyHomomorphic::combine_hints`, `JointOpeningPolynomials` (`crates/jolt-openings/src/schemes.rs:49-50,157-162`, `crates/jolt-kernels/src/opening.rs:42-54`) | [`opening`]: resident columns + commit-time class sums -> `jolt_host_hyperkzg_open_grid` |
 //! | dory's `DoryRoutines<ArkG1>` / `DoryRoutines<ArkG2>`, the group routines of `dory::prove`'s reduce-and-fold rounds (`crates/jolt-dory/src/routines.rs:58-147`) | [`dory_routines::HipG1Routines`], [`dory_routines::HipG2Routines`] over `jolt_dory_g1_*` / `jolt_dory_g2_*` / `jolt_dory_fold_field_vectors` |
+//! | the inner products and folds of one reduce-and-fold round of `dory::prove` on vectors that stay on the device (no trait: dory's `DoryRoutines` works on host slices) | [`dory_resident`]: [`dory_resident::HipDoryVec`], [`dory_resident::products`] over `jolt_dory_vec_*` / `jolt_dory_products` |
 //! | `UniskipKernel`, `CommitWitness`, the backend constructor (`crates/jolt-kernels/src/{uniskip.rs:28-54, commitment.rs:137-160, optimized/mod.rs:136-196}`) | [`backend::HipUniskip`], [`backend::HipCommitWitness`], [`backend::mi355x`] |
 //!
 //! Host code stays Rust: Fiat-Shamir, claim wiring, round-polynomial assembly (`UnivariatePoly::from_evals`,
@@ -28,6 +29,7 @@
 
 pub mod ffi;
 pub mod context;
+pub mod dory_resident;
 pub mod dory_routines;
 pub mod leaves;
 pub mod member;
@@ -44,6 +46,7 @@ pub mod status;
 pub mod streaming;
 
 pub use context::{HipContext, HipTable};
+pub use dory_resident::{products, DoryItem, DoryProduct, HipDoryVec, VecKind};
 pub use dory_routines::{HipG1Routines, HipG2Routines};
 pub use member::{HipMember, HipPrepare, HipSumcheckProver, MemberShape, MemberSlot};
 pub use msm::{msm_cache_clear, msm_cache_evict, msm_g1, HipShardedOpening, HipSrs, SharedMsmContext};

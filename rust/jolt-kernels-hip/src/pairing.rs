@@ -36,9 +36,9 @@ pub fn multi_pair(ctx: &HipContext, g1s: &[ArkG1], g2s: &[ArkG2]) -> Result<ArkG
 
 /// The line tables of the setup's `g2_vec` bases, resident on the device: built once per setup.
 pub struct HipG2Prepared {
-    ctx: Arc<HipContext>,
-    raw: *mut ffi::jolt_g2_prepared,
-    len: usize,
+    pub(crate) ctx: Arc<HipContext>,
+    pub(crate) raw: *mut ffi::jolt_g2_prepared,
+    pub(crate) len: usize,
 }
 
 impl HipG2Prepared {

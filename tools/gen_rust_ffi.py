@@ -133,6 +133,8 @@ def render(decls):
     out.append("pub const JOLT_FQ2_ADD: i32 = 0;\npub const JOLT_FQ2_SUB: i32 = 1;\npub const JOLT_FQ2_MUL: i32 = 2;\npub const JOLT_FQ2_SQR: i32 = 3;\npub const JOLT_FQ2_NEG: i32 = 4;")
     out.append("pub const JOLT_FQ12_MUL: i32 = 0;\npub const JOLT_FQ12_SQR: i32 = 1;\npub const JOLT_FQ12_INV: i32 = 2;\npub const JOLT_FQ12_CONJ: i32 = 3;\npub const JOLT_FQ12_FROBENIUS1: i32 = 4;\n"
                "pub const JOLT_FQ12_FROBENIUS2: i32 = 5;\npub const JOLT_FQ12_FROBENIUS3: i32 = 6;\npub const JOLT_FQ12_MUL_SPARSE: i32 = 7;\npub const JOLT_PAIRING_LINES: usize = 88;")
+    out.append("pub const JOLT_DORY_KIND_G1: i32 = 0;\npub const JOLT_DORY_KIND_G2: i32 = 1;\npub const JOLT_DORY_KIND_FR: i32 = 2;\n"
+               "pub const JOLT_DORY_PAIR: i32 = 0;\npub const JOLT_DORY_MSM_G1: i32 = 1;\npub const JOLT_DORY_MSM_G2: i32 = 2;")
     out.append("pub const JOLT_MAX_MEMBER_TABLES: usize = 40;\npub const JOLT_MAX_MEMBER_TERMS: usize = 16;\npub const JOLT_MAX_MEMBER_FACTORS: usize = 64;\npub const JOLT_MAX_DEGREE: usize = 7;")
     out.append("")
     out.append("#[repr(C)]\npub struct jolt_member_desc {\n    pub n_tables: u32,\n    pub n_terms: u32,\n    pub degree: u32,\n    pub order: i32,\n"
@@ -140,6 +142,9 @@ def render(decls):
     out.append("#[repr(C)]\npub struct jolt_member_lc_desc {\n    pub n_tables: u32,\n    pub n_groups: u32,\n    pub n_factors: u32,\n    pub n_lc: u32,\n    pub degree: u32,\n"
                "    pub order: i32,\n    pub flags: u32,\n    pub group_factor_offsets: *const u32,\n    pub factor_lc_offsets: *const u32,\n    pub factor_consts: *const jolt_fr_t,\n"
                "    pub lc_tables: *const u32,\n    pub lc_coeffs: *const jolt_fr_t,\n}")
+    out.append("#[repr(C)]\npub struct jolt_dory_item {\n    pub op: i32,\n    pub a: *const jolt_dory_vec,\n    pub a_first: usize,\n    pub b: *const jolt_dory_vec,\n    pub b_first: usize,\n"
+               "    pub prepared: *const jolt_g2_prepared,\n    pub prepared_first: usize,\n    pub n: usize,\n}")
+    out.append("#[repr(C)]\n#[derive(Clone, Copy)]\npub struct jolt_dory_result {\n    pub w: [u64; 48],\n}")
     out.append("pub type jolt_local_round_fn = Option<\n    unsafe extern \"C\" fn(user: *mut c_void, active: *const usize, n_active: usize, binds: *const *const jolt_fr_t, evals_out: *mut jolt_fr_t, evals_count: usize) -> i32,\n>;")
     out.append("pub type jolt_gather_fn = Option<unsafe extern \"C\" fn(user: *mut c_void, local: *const jolt_fr_t, count: usize, gathered: *mut jolt_fr_t) -> i32>;")
     out.append("pub type jolt_round_transcript_fn = Option<unsafe extern \"C\" fn(user: *mut c_void, compressed_coeffs: *const jolt_fr_t, n_coeffs: usize, challenge_out: *mut jolt_fr_t) -> i32>;")
