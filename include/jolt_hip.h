@@ -710,6 +710,26 @@ int32_t jolt_dory_vec_scale_bases_add(jolt_ctx *ctx, const jolt_dory_vec *bases,
 int32_t jolt_dory_vec_scale_vs_add(jolt_ctx *ctx, jolt_dory_vec *vs, size_t vs_first, const jolt_dory_vec *addends, size_t addends_first, size_t n, const jolt_fr_t *scalar);
 /* left[left_first + i] = left[left_first + i] * scalar + right[right_first + i] */
 int32_t jolt_dory_vec_fold_field(jolt_ctx *ctx, jolt_dory_vec *left, size_t left_first, const jolt_dory_vec *right, size_t right_first, size_t n, const jolt_fr_t *scalar);
+/* The state an opening's rounds start from, built on the device.  Same contract as the entries above: a null handle, a vector (or table) of another context or of
+ * the wrong kind, a view or range outside its vector (or table), or a scalar that is not canonical is JOLT_ERR_INVALID_ARG, and a refused call enqueues nothing and
+ * writes nothing.  The first two are enqueued on the context's stream like the in-place routines (no synchronisation); the last two stage a plan or a table of this
+ * call from host memory and synchronise before they return. */
+/* n neutral elements: the identity (1, 1, 0) for G1 / G2, zero for Fr; n = 0 gives an empty vector; n <= 2^30 */
+int32_t jolt_dory_state_alloc(jolt_ctx *ctx, int32_t kind, size_t n, jolt_dory_vec **out);
+/* dst[dst_first + i] = table[table_first + i] for i < n: entries of a device Fr table (jolt_dory_fold_rows_grid's output, an eq table) into an Fr vector view.
+ * Both hold Montgomery words, so this is a device copy. */
+int32_t jolt_dory_state_from_table(jolt_ctx *ctx, const jolt_table *table, size_t table_first, jolt_dory_vec *dst, size_t dst_first, size_t n);
+/* DoryScheme::combine_hints (crates/jolt-dory/src/scheme.rs:325-360) as jolt_dory_combine_hints computes it, with resident G1 views in and a resident view out:
+ *   out[out_first + row] = sum_i scalars[i] * hints[i][hint_first[i] + row]   for row < max_i hint_rows[i],
+ * a hint shorter than the widest contributing the identity to the rows it lacks (:330-338).  The same digit plan and the same two kernels: the rows are the
+ * group elements the host-pointer entry gives.  n_hints == 0 is JOLT_ERR_INVALID_ARG (the reference asserts), as is an `out` range that shares an element with a hint. */
+int32_t jolt_dory_state_combine_hints(jolt_ctx *ctx, const jolt_dory_vec *const *hints, const size_t *hint_first, const size_t *hint_rows, size_t n_hints,
+                                    const jolt_fr_t *scalars, jolt_dory_vec *out, size_t out_first);
+/* DoryRoutines::fixed_base_vector_scalar_mul (crates/jolt-dory/src/routines.rs:66-72, :107-122) on resident views: out[out_first + i] = scalars[scalars_first + i] * base.
+ * kind is JOLT_DORY_KIND_G1 or _G2 and names the group of `base` (one host jolt_g1_t / jolt_g2_t, checked as jolt_dory_g{1,2}_fixed_base_mul check it) and of `out`;
+ * `scalars` is an Fr vector.  The elements come back as that entry's: the identity as (1, 1, 0). */
+int32_t jolt_dory_state_fixed_base_mul(jolt_ctx *ctx, int32_t kind, const void *base, const jolt_dory_vec *scalars, size_t scalars_first, jolt_dory_vec *out,
+                                     size_t out_first, size_t n);
 /* A batch of inner products over resident views, one launch set for all of them: per item
  *   JOLT_DORY_PAIR    prod_i e(a[a_first + i], b[b_first + i]); a is a G1 vector, b a G2 vector -- or NULL, and the G2 side is points
  *                     [prepared_first, prepared_first + n) of `prepared`

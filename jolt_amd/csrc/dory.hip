@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "dory_host.hpp"
 #include "msm_kernels.hip.h"
 #include "onehot.hpp"
 #include "srs.hpp"
@@ -635,12 +636,10 @@ constexpr int kCombineWindow = 5;                                               
 constexpr int kCombineWindows = (254 + 1 + kCombineWindow - 1) / kCombineWindow;  // r < 2^254; one spare bit takes the last carry
 constexpr uint32_t kCombineIdxMask = 0x00FFFFFFu;                               // plan entry: term | magnitude << 24 | negative << 31
 
-struct CombinePlan {
-    std::vector<uint32_t> ent;    // per window, the terms with a non-zero digit, by descending magnitude
-    std::vector<uint32_t> start;  // kCombineWindows + 1 offsets into ent
-};
+}  // namespace
+
 // scalars in Montgomery form; false: one of them is not canonical
-bool combine_plan(const jolt_fr_t* scalars, size_t n, CombinePlan* plan) {
+bool jolt::dory_host::combine_plan(const jolt_fr_t* scalars, size_t n, CombinePlan* plan) {
     constexpr uint32_t B = 1u << (kCombineWindow - 1);
     std::vector<uint8_t> mag((size_t)kCombineWindows * n), sgn((size_t)kCombineWindows * n);
     for (size_t i = 0; i < n; ++i) {
@@ -667,6 +666,10 @@ bool combine_plan(const jolt_fr_t* scalars, size_t n, CombinePlan* plan) {
     plan->start[kCombineWindows] = (uint32_t)plan->ent.size();
     return true;
 }
+
+namespace {
+using jolt::dory_host::CombinePlan;
+using jolt::dory_host::combine_plan;
 
 // sum over the window's terms of digit_i * P_i; load(i) = term i's point of this row
 template <class Load>
@@ -790,6 +793,43 @@ extern "C" int32_t jolt_dory_fold_rows_grid(jolt_ctx* ctx, const jolt_onehot* co
     return JOLT_OK;
 }
 
+// The window sums and the Horner recombination of `rows` combined rows over points that are on the device already: the plan's upload and, per pass of at most 8192
+// rows, the two launches.  Enqueued on the context's stream; the temporaries go back to the pool at once (reuse is stream-ordered).  `meta` and `plan` are read by
+// the copies enqueued here: the caller synchronises the stream before they go, on every path.
+int32_t jolt::dory_host::combine_enqueue(jolt_ctx* ctx, const void* d_points, const std::vector<uint64_t>& meta, const CombinePlan& plan, size_t rows, void* d_out_rows) {
+    const size_t n_hints = meta.size() / 2;
+    const G1Jac* d_pts = (const G1Jac*)d_points;
+    G1Jac* d_out = (G1Jac*)d_out_rows;
+    hipStream_t st = ctx->stream;
+    const size_t batch = std::min<size_t>(rows, 8192);  // window sums of one pass: 51 * 8192 points, 40 MB
+    const size_t b_meta = meta.size() * 8, b_ent = std::max<size_t>(plan.ent.size(), 1) * 4, b_start = plan.start.size() * 4;
+    G1Jac* d_wsum = nullptr;
+    unsigned char* d_plan = nullptr;
+    int32_t rc = jolt_internal_dev_alloc(ctx, (size_t)kCombineWindows * batch * sizeof(G1Jac), (void**)&d_wsum);
+    if (rc == JOLT_OK) rc = jolt_internal_dev_alloc(ctx, b_meta + b_ent + b_start, (void**)&d_plan);
+    hipError_t e = hipSuccess;
+    if (rc == JOLT_OK) {
+        e = hipMemcpyAsync(d_plan, meta.data(), b_meta, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && !plan.ent.empty()) e = hipMemcpyAsync(d_plan + b_meta, plan.ent.data(), plan.ent.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_plan + b_meta + b_ent, plan.start.data(), b_start, hipMemcpyHostToDevice, st);
+        const uint64_t* d_off = (const uint64_t*)d_plan;
+        const uint32_t* d_ent = (const uint32_t*)(d_plan + b_meta);
+        const uint32_t* d_start = (const uint32_t*)(d_plan + b_meta + b_ent);
+        for (size_t r0 = 0; r0 < rows && e == hipSuccess; r0 += batch) {
+            const size_t nr = std::min(batch, rows - r0);
+            const unsigned g = (unsigned)((nr + kBlock - 1) / kBlock);
+            hipLaunchKernelGGL(k_dory_combine_windows, dim3(g, kCombineWindows), dim3(kBlock), 0, st, d_pts, d_off, d_off + n_hints, d_ent, d_start, r0, nr, d_wsum);
+            hipLaunchKernelGGL(k_dory_combine_horner, dim3(g), dim3(kBlock), 0, st, (const G1Jac*)d_wsum, nr, d_out + r0);
+            e = hipGetLastError();
+        }
+    }
+    jolt_internal_dev_free(ctx, d_wsum);
+    jolt_internal_dev_free(ctx, d_plan);
+    if (rc != JOLT_OK) return rc;
+    if (e != hipSuccess) return hip_fail(ctx, "dory combine", e);
+    return JOLT_OK;
+}
+
 extern "C" int32_t jolt_dory_combine_hints(jolt_ctx* ctx, const jolt_g1_t* const* hints, const size_t* hint_rows, size_t n_hints, const jolt_fr_t* scalars,
                                            jolt_g1_t* out) {
     if (!ctx) return JOLT_ERR_INVALID_ARG;
@@ -810,40 +850,20 @@ extern "C" int32_t jolt_dory_combine_hints(jolt_ctx* ctx, const jolt_g1_t* const
     if (rows == 0) return JOLT_OK;
     if (!out) return JOLT_ERR_INVALID_ARG;
     hipStream_t st = ctx->stream;
-    const size_t batch = std::min<size_t>(rows, 8192);  // window sums of one pass: 51 * 8192 points, 40 MB
-    const size_t b_meta = meta.size() * 8, b_ent = std::max<size_t>(plan.ent.size(), 1) * 4, b_start = plan.start.size() * 4;
-    G1Jac *d_pts = nullptr, *d_wsum = nullptr, *d_out = nullptr;
-    unsigned char* d_plan = nullptr;
+    G1Jac *d_pts = nullptr, *d_out = nullptr;
     int32_t rc = jolt_internal_dev_alloc(ctx, total * sizeof(G1Jac), (void**)&d_pts);
-    if (rc == JOLT_OK) rc = jolt_internal_dev_alloc(ctx, (size_t)kCombineWindows * batch * sizeof(G1Jac), (void**)&d_wsum);
     if (rc == JOLT_OK) rc = jolt_internal_dev_alloc(ctx, rows * sizeof(G1Jac), (void**)&d_out);
-    if (rc == JOLT_OK) rc = jolt_internal_dev_alloc(ctx, b_meta + b_ent + b_start, (void**)&d_plan);
     hipError_t e = hipSuccess;
     if (rc == JOLT_OK) {
         for (size_t i = 0; i < n_hints && e == hipSuccess; ++i)
             if (hint_rows[i]) e = hipMemcpyAsync(d_pts + meta[i], hints[i], hint_rows[i] * sizeof(G1Jac), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_plan, meta.data(), b_meta, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && !plan.ent.empty()) e = hipMemcpyAsync(d_plan + b_meta, plan.ent.data(), plan.ent.size() * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_plan + b_meta + b_ent, plan.start.data(), b_start, hipMemcpyHostToDevice, st);
-        const uint64_t* d_off = (const uint64_t*)d_plan;
-        const uint32_t* d_ent = (const uint32_t*)(d_plan + b_meta);
-        const uint32_t* d_start = (const uint32_t*)(d_plan + b_meta + b_ent);
-        for (size_t r0 = 0; r0 < rows && e == hipSuccess; r0 += batch) {
-            const size_t nr = std::min(batch, rows - r0);
-            const unsigned g = (unsigned)((nr + kBlock - 1) / kBlock);
-            hipLaunchKernelGGL(k_dory_combine_windows, dim3(g, kCombineWindows), dim3(kBlock), 0, st, (const G1Jac*)d_pts, d_off, d_off + n_hints, d_ent, d_start, r0, nr,
-                               d_wsum);
-            hipLaunchKernelGGL(k_dory_combine_horner, dim3(g), dim3(kBlock), 0, st, (const G1Jac*)d_wsum, nr, d_out + r0);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, rows * sizeof(G1Jac), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) rc = dory_host::combine_enqueue(ctx, d_pts, meta, plan, rows, d_out);
+        if (e == hipSuccess && rc == JOLT_OK) e = hipMemcpyAsync(out, d_out, rows * sizeof(G1Jac), hipMemcpyDeviceToHost, st);
         hipError_t e2 = hipStreamSynchronize(st);  // the plan and the caller's arrays are read until here
         if (e == hipSuccess) e = e2;
     }
     jolt_internal_dev_free(ctx, d_pts);
-    jolt_internal_dev_free(ctx, d_wsum);
     jolt_internal_dev_free(ctx, d_out);
-    jolt_internal_dev_free(ctx, d_plan);
     if (rc != JOLT_OK) return rc;
     if (e != hipSuccess) return hip_fail(ctx, "dory combine", e);
     return JOLT_OK;

@@ -1,4 +1,4 @@
-// jolt_amd/csrc/dory_host.hpp -- host-side helpers shared by the Dory entry points that take host pointers (dory_routines.hip, dory_pairing.hip).
+// jolt_amd/csrc/dory_host.hpp -- host-side helpers shared by the Dory entry points (dory.hip, dory_routines.hip, dory_pairing.hip, dory_resident.hip).
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -63,6 +63,15 @@ Pt pt_from_abi(const void* p) {
     std::memcpy(&r, p, sizeof(r));
     return r;
 }
+
+// ---- combine_hints (dory.hip): the shared-scalar digit plan and the launches over points on the device, for the host-pointer entry and the resident one ----
+struct CombinePlan {
+    std::vector<uint32_t> ent;    // per window, the terms with a non-zero digit, by descending magnitude
+    std::vector<uint32_t> start;  // one offset into ent per window, and the end
+};
+bool combine_plan(const jolt_fr_t* scalars, size_t n, CombinePlan* plan);
+// d_points: G1Jac, the hints back to back; meta: the hints' offsets into d_points, then their row counts; d_out: G1Jac, `rows` of them
+int32_t combine_enqueue(jolt_ctx* ctx, const void* d_points, const std::vector<uint64_t>& meta, const CombinePlan& plan, size_t rows, void* d_out);
 
 }  // namespace dory_host
 }  // namespace jolt

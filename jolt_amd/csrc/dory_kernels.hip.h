@@ -1,5 +1,5 @@
 // jolt_amd/csrc/dory_kernels.hip.h -- what the Dory round entry points share: the two groups behind one interface, the shared scalar's non-adjacent form and its
-// walk, one MSM term, and the kernels over them.  dory_routines.hip runs them on the caller's host arrays, dory_resident.hip on vectors that stay in HBM.
+// walk, the fixed-base table and its signed-nibble walk, one MSM term, and the kernels over them.  dory_routines.hip runs them on the caller's host arrays, dory_resident.hip on vectors that stay in HBM.
 #pragma once
 #include <cstring>
 
@@ -128,6 +128,40 @@ JOLT_HD typename O::Pt term_mul_one(const typename O::Pt& p, const Fr& scalar_mo
     return acc;
 }
 
+// ---- per-element scalars over one base: signed 4-bit windows, table[k] = k * base for k = 0..8 ----
+constexpr int kFixedWindow = 4;
+constexpr int kFixedWindows = 64;  // 256 bits; digits in [-8, 7] (fixed_mul_one)
+constexpr int kFixedTable = (1 << (kFixedWindow - 1)) + 1;
+template <class O>
+void fixed_table(const typename O::Pt& base, typename O::Pt* table) {
+    table[0] = O::identity();
+    table[1] = base;
+    for (int k = 2; k < kFixedTable; ++k) table[k] = (k & 1) ? O::add(table[k - 1], base) : O::dbl(table[k / 2]);
+}
+// scalar * base.  Signed digits without a carry chain: k' = k + 0x88..8 (8 in each of the 64 nibbles; k < 2^254, so k' < 2^256), digit w = nibble w of k' - 8 in [-8, 7],
+// since sum_w 8 * 16^w is exactly what was added.  The table entry is taken by index (digits differ from lane to lane), its sign by a select on y.
+template <class O>
+JOLT_HD typename O::Pt fixed_mul_one(const typename O::Pt* __restrict__ table, const Fr& scalar_mont) {
+    Fr k = from_mont(scalar_mont);
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) k.l[j] = __builtin_addc(k.l[j], 0x88888888u, c, &c);
+    typename O::Pt acc = O::identity();
+#pragma unroll 1
+    for (int w = kFixedWindows - 1; w >= 0; --w) {
+#pragma unroll 1
+        for (int j = 0; j < kFixedWindow; ++j) acc = O::dbl(acc);
+        const uint32_t nib = k.l[7] >> 28;
+        shl256<kFixedWindow>(k);
+        const bool negative = nib < 8u;
+        const uint32_t mag = negative ? 8u - nib : nib - 8u;
+        typename O::Pt t = table[mag];
+        if (negative) t = O::neg(t);
+        acc = O::add(acc, t);
+    }
+    return normalised<O>(acc);
+}
+
 // ---- kernels: one wavefront per workgroup (kLanes), one wavefront per SIMD (a G2 addition holds two 48-register points and its temporaries) ----
 // out[i] = addend[i] + s * scaled[i], as scale_add_one; out may alias either input (each lane reads its own element before it writes it)
 template <class O>
@@ -142,6 +176,12 @@ __global__ __launch_bounds__(kLanes) void k_dory_msm_terms(const typename O::Pt*
     const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
     if (i >= n) return;
     out[i] = term_mul_one<O>(bases[i], scalars[i]);
+}
+template <class O>
+__global__ __launch_bounds__(kLanes) void k_dory_fixed_base(const typename O::Pt* __restrict__ table, const Fr* __restrict__ scalars, typename O::Pt* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
+    if (i >= n) return;
+    out[i] = fixed_mul_one<O>(table, scalars[i]);
 }
 // one level of the addition tree: terms[i] += terms[i + half] for i + half < m
 template <class O>

@@ -12,6 +12,9 @@
 //     k_batch_tree_level     one launch per LEVEL over all items of a chain: f[i] *= f[i + half] / terms[i] += terms[i + half] inside each item's segment, with that
 //                            segment's own m -- the step of k_pair_product_level and k_dory_tree_level
 //     k_batch_gather         each item's element 0 (or the neutral element of an empty item) into one result block: one read-back for the batch
+//   jolt_dory_state_alloc / _from_table / _combine_hints / _fixed_base_mul   the state an opening's rounds start from, built where it is used: neutral vectors
+//                            (k_dory_fill), entries of an Fr table (a device copy), the combined hints (the plan and the two kernels of dory.hip's combine_hints, on
+//                            the hints gathered back to back by device copies), multiples of one base (k_dory_fixed_base of dory_kernels.hip.h)
 //   The three chains are independent: they run on the context's side streams, forked from the main stream by one event and joined before the read-back.
 // Workgroups of one wavefront, one element per lane, integer VALU work, no MFMA, as the kernels these are made of; register figures in docs/kernels.md 3.5h.
 #include <algorithm>
@@ -53,8 +56,40 @@ bool views_overlap(const jolt_dory_vec* a, size_t a_first, const jolt_dory_vec* 
     if (a != b || n == 0) return false;
     return a_first < b_first ? b_first - a_first < n : a_first - b_first < n;
 }
+// two valid views of different lengths share an element
+bool ranges_overlap(const jolt_dory_vec* a, size_t a_first, size_t a_n, const jolt_dory_vec* b, size_t b_first, size_t b_n) {
+    if (a != b || a_n == 0 || b_n == 0) return false;
+    return a_first < b_first ? b_first - a_first < a_n : a_first - b_first < b_n;
+}
 template <class T>
 T* at(const jolt_dory_vec* v, size_t first) { return (T*)v->data + first; }
+
+// a vector of n elements whose block is not written yet
+int32_t vec_new(jolt_ctx* ctx, int32_t kind, size_t n, jolt_dory_vec** out) {
+    jolt_dory_vec* v = new (std::nothrow) jolt_dory_vec();
+    if (!v) return JOLT_ERR_OOM;
+    v->ctx = ctx;
+    v->kind = kind;
+    v->len = n;
+    const int32_t rc = jolt_internal_dev_alloc(ctx, std::max<size_t>(n * kind_size(kind), 16), &v->data);
+    if (rc != JOLT_OK) {
+        delete v;
+        return rc;
+    }
+    *out = v;
+    return JOLT_OK;
+}
+
+template <class T>
+__global__ __launch_bounds__(kLanes) void k_dory_fill(T* __restrict__ out, size_t n, T value) {
+    const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
+    if (i < n) out[i] = value;
+}
+template <class T>
+hipError_t fill(hipStream_t st, jolt_dory_vec* v, const T& value) {
+    hipLaunchKernelGGL(k_dory_fill<T>, dim3(lanes_grid(v->len)), dim3(kLanes), 0, st, (T*)v->data, v->len, value);
+    return hipGetLastError();
+}
 
 // ---- the tables of a batch: per workgroup (item, first), per item its pointers, its first slot in the chain's packed array and its length ----
 struct WgDev {
@@ -193,14 +228,11 @@ extern "C" int32_t jolt_dory_vec_upload(jolt_ctx* ctx, int32_t kind, const void*
         const bool ok = kind == JOLT_DORY_KIND_G1 ? all_on_curve<G1Ops>((const jolt_g1_t*)host, n) : all_on_curve<G2Ops>((const jolt_g2_t*)host, n);
         JOLT_REQUIRE(ctx, ok, "a point is not on its curve or not canonical");
     }
-    jolt_dory_vec* v = new (std::nothrow) jolt_dory_vec();
-    if (!v) return JOLT_ERR_OOM;
-    v->ctx = ctx;
-    v->kind = kind;
-    v->len = n;
+    jolt_dory_vec* v = nullptr;
+    JOLT_TRY(vec_new(ctx, kind, n, &v));
     const size_t bytes = n * kind_size(kind);
-    int32_t rc = jolt_internal_dev_alloc(ctx, std::max<size_t>(bytes, 16), &v->data);
-    if (rc == JOLT_OK && n) {
+    int32_t rc = JOLT_OK;
+    if (n) {
         hipError_t e = hipMemcpyAsync(v->data, host, bytes, hipMemcpyHostToDevice, ctx->stream);
         const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the caller's array is read until here
         if (e == hipSuccess) e = e2;
@@ -290,6 +322,97 @@ extern "C" int32_t jolt_dory_vec_fold_field(jolt_ctx* ctx, jolt_dory_vec* left, 
     hipLaunchKernelGGL(k_dory_fold_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, at<Fr>(left, left_first), (const Fr*)at<Fr>(right, right_first), s, n);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory vec field fold", e);
+}
+
+extern "C" int32_t jolt_dory_state_alloc(jolt_ctx* ctx, int32_t kind, size_t n, jolt_dory_vec** out) {
+    if (!ctx || !out) return JOLT_ERR_INVALID_ARG;
+    JOLT_REQUIRE(ctx, kind == JOLT_DORY_KIND_G1 || kind == JOLT_DORY_KIND_G2 || kind == JOLT_DORY_KIND_FR, "unknown vector kind");
+    if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
+    jolt_dory_vec* v = nullptr;
+    JOLT_TRY(vec_new(ctx, kind, n, &v));
+    if (n) {
+        const hipError_t e = kind == JOLT_DORY_KIND_G1 ? fill(ctx->stream, v, G1Ops::identity()) : kind == JOLT_DORY_KIND_G2 ? fill(ctx->stream, v, G2Ops::identity()) : fill(ctx->stream, v, Fr::zero());
+        if (e != hipSuccess) {
+            (void)jolt_dory_vec_free(ctx, v);
+            return hip_fail(ctx, "dory state alloc", e);
+        }
+    }
+    *out = v;
+    return JOLT_OK;
+}
+
+extern "C" int32_t jolt_dory_state_from_table(jolt_ctx* ctx, const jolt_table* table, size_t table_first, jolt_dory_vec* dst, size_t dst_first, size_t n) {
+    if (!ctx || !table || !dst) return JOLT_ERR_INVALID_ARG;
+    JOLT_REQUIRE(ctx, table->ctx == ctx && table->data() && !(table_first > table->len || n > table->len - table_first), "the range is outside the table, or the table belongs to another context");
+    JOLT_REQUIRE(ctx, view_ok(ctx, dst, JOLT_DORY_KIND_FR, dst_first, n), "the view is outside its vector, or not an Fr vector of this context");
+    if (n == 0) return JOLT_OK;
+    const hipError_t e = hipMemcpyAsync(at<Fr>(dst, dst_first), table->data() + table_first, n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream);
+    return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory state from table", e);
+}
+
+extern "C" int32_t jolt_dory_state_combine_hints(jolt_ctx* ctx, const jolt_dory_vec* const* hints, const size_t* hint_first, const size_t* hint_rows, size_t n_hints, const jolt_fr_t* scalars,
+                                               jolt_dory_vec* out, size_t out_first) {
+    if (!ctx) return JOLT_ERR_INVALID_ARG;
+    JOLT_REQUIRE(ctx, n_hints != 0, "combine_hints: no hints");  // scheme.rs:326 assert
+    if (!hints || !hint_first || !hint_rows || !scalars || !out) return JOLT_ERR_INVALID_ARG;
+    if (n_hints > (size_t)0x00FFFFFFu) return JOLT_ERR_UNSUPPORTED;  // a plan entry holds the term in 24 bits
+    size_t rows = 0, total = 0;
+    std::vector<uint64_t> meta(2 * n_hints);  // offsets into the gathered points, then row counts
+    for (size_t i = 0; i < n_hints; ++i) {
+        JOLT_REQUIRE(ctx, view_ok(ctx, hints[i], JOLT_DORY_KIND_G1, hint_first[i], hint_rows[i]), "a hint is not a G1 view of this context");
+        meta[i] = total;
+        meta[n_hints + i] = hint_rows[i];
+        total += hint_rows[i];
+        rows = std::max(rows, hint_rows[i]);
+    }
+    JOLT_REQUIRE(ctx, view_ok(ctx, out, JOLT_DORY_KIND_G1, out_first, rows), "out is not a G1 view of this context that holds the combined rows");
+    for (size_t i = 0; i < n_hints; ++i) JOLT_REQUIRE(ctx, !ranges_overlap(out, out_first, rows, hints[i], hint_first[i], hint_rows[i]), "out overlaps a hint");
+    CombinePlan plan;
+    JOLT_REQUIRE(ctx, combine_plan(scalars, n_hints, &plan), "scalar is not a canonical Fr");
+    if (rows == 0) return JOLT_OK;
+    hipStream_t st = ctx->stream;
+    DevBufs bufs(ctx);
+    G1Jac* d_pts = nullptr;
+    JOLT_TRY(bufs.take(total, &d_pts));
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < n_hints && e == hipSuccess; ++i)  // back to back, the layout k_dory_combine_windows indexes
+        if (hint_rows[i]) e = hipMemcpyAsync(d_pts + meta[i], at<G1Jac>(hints[i], hint_first[i]), hint_rows[i] * sizeof(G1Jac), hipMemcpyDeviceToDevice, st);
+    int32_t rc = JOLT_OK;
+    if (e == hipSuccess) rc = combine_enqueue(ctx, d_pts, meta, plan, rows, at<G1Jac>(out, out_first));
+    const hipError_t e2 = hipStreamSynchronize(st);  // the plan (host memory of this call) is read until here
+    if (e == hipSuccess) e = e2;
+    if (rc != JOLT_OK) return rc;
+    return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory state combine", e);
+}
+
+namespace {
+template <class O>
+int32_t fixed_base_views(jolt_ctx* ctx, const void* base, const jolt_dory_vec* scalars, size_t scalars_first, jolt_dory_vec* out, size_t out_first, size_t n) {
+    using Pt = typename O::Pt;
+    JOLT_REQUIRE(ctx, all_on_curve<O>((const typename O::Abi*)base, 1), "a point is not on its curve or not canonical");
+    if (n == 0) return JOLT_OK;
+    Pt table[kFixedTable];
+    fixed_table<O>(pt_from_abi<Pt>(base), table);
+    hipStream_t st = ctx->stream;
+    DevBufs bufs(ctx);
+    Pt* d_table = nullptr;
+    JOLT_TRY(bufs.take(kFixedTable, &d_table));
+    hipError_t e = hipMemcpyAsync(d_table, table, sizeof(table), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_dory_fixed_base<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, (const Pt*)d_table, (const Fr*)at<Fr>(scalars, scalars_first), at<Pt>(out, out_first), n);
+        e = hipGetLastError();
+    }
+    const hipError_t e2 = hipStreamSynchronize(st);  // `table` (on this stack) is read until here
+    if (e == hipSuccess) e = e2;
+    return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory state fixed base", e);
+}
+}  // namespace
+
+extern "C" int32_t jolt_dory_state_fixed_base_mul(jolt_ctx* ctx, int32_t kind, const void* base, const jolt_dory_vec* scalars, size_t scalars_first, jolt_dory_vec* out, size_t out_first, size_t n) {
+    if (!ctx || !base || !scalars || !out) return JOLT_ERR_INVALID_ARG;
+    JOLT_REQUIRE(ctx, kind == JOLT_DORY_KIND_G1 || kind == JOLT_DORY_KIND_G2, "a fixed-base multiplication gives points");
+    JOLT_REQUIRE(ctx, view_ok(ctx, scalars, JOLT_DORY_KIND_FR, scalars_first, n) && view_ok(ctx, out, kind, out_first, n), "a view is outside its vector, or of another kind or context");
+    return kind == JOLT_DORY_KIND_G1 ? fixed_base_views<G1Ops>(ctx, base, scalars, scalars_first, out, out_first, n) : fixed_base_views<G2Ops>(ctx, base, scalars, scalars_first, out, out_first, n);
 }
 
 extern "C" int32_t jolt_dory_products(jolt_ctx* ctx, const jolt_dory_item* items, size_t n_items, jolt_dory_result* outs) {

@@ -32,47 +32,6 @@ using namespace jolt::dory_dev;
 
 namespace {
 
-// ---- per-element scalars over one base: signed 4-bit windows, table[k] = k * base for k = 0..8 ----
-constexpr int kFixedWindow = 4;
-constexpr int kFixedWindows = 64;  // 256 bits; digits in [-8, 7] (fixed_mul_one)
-constexpr int kFixedTable = (1 << (kFixedWindow - 1)) + 1;
-template <class O>
-void fixed_table(const typename O::Pt& base, typename O::Pt* table) {
-    table[0] = O::identity();
-    table[1] = base;
-    for (int k = 2; k < kFixedTable; ++k) table[k] = (k & 1) ? O::add(table[k - 1], base) : O::dbl(table[k / 2]);
-}
-// scalar * base.  Signed digits without a carry chain: k' = k + 0x88..8 (8 in each of the 64 nibbles; k < 2^254, so k' < 2^256), digit w = nibble w of k' - 8 in [-8, 7],
-// since sum_w 8 * 16^w is exactly what was added.  The table entry is taken by index (digits differ from lane to lane), its sign by a select on y.
-template <class O>
-JOLT_HD typename O::Pt fixed_mul_one(const typename O::Pt* __restrict__ table, const Fr& scalar_mont) {
-    Fr k = from_mont(scalar_mont);
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) k.l[j] = __builtin_addc(k.l[j], 0x88888888u, c, &c);
-    typename O::Pt acc = O::identity();
-#pragma unroll 1
-    for (int w = kFixedWindows - 1; w >= 0; --w) {
-#pragma unroll 1
-        for (int j = 0; j < kFixedWindow; ++j) acc = O::dbl(acc);
-        const uint32_t nib = k.l[7] >> 28;
-        shl256<kFixedWindow>(k);
-        const bool negative = nib < 8u;
-        const uint32_t mag = negative ? 8u - nib : nib - 8u;
-        typename O::Pt t = table[mag];
-        if (negative) t = O::neg(t);
-        acc = O::add(acc, t);
-    }
-    return normalised<O>(acc);
-}
-
-template <class O>
-__global__ __launch_bounds__(kLanes) void k_dory_fixed_base(const typename O::Pt* __restrict__ table, const Fr* __restrict__ scalars, typename O::Pt* __restrict__ out, size_t n) {
-    const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
-    if (i >= n) return;
-    out[i] = fixed_mul_one<O>(table, scalars[i]);
-}
-
 // Phase clock of jolt_dory_routines_timing: when it is on, the stream is drained between the phases of a call so that each gets its own wall time.
 struct Phases {
     jolt_ctx* ctx;

@@ -37,7 +37,29 @@ class DoryReduce:
             self.close()
             raise ValueError("the vectors of a Dory-Reduce have one length")
         self.gamma2_prepared = ctx.dory_g2_prepare_vec(self.gamma2)  # once: a prefix of the table serves every later round
+        self._owns_prepared = True
         self._one = ffi.host_fr_from_u64(1)
+
+    @classmethod
+    def from_resident(cls, ctx, v1, v2, s1, s2, gamma1, gamma2, gamma2_prepared):
+        """The same reduction over six vectors that are on the device already (DoryVec) and the prepared table of gamma2, all of them the caller's: nothing is
+        uploaded, and close() frees none of them.  v1, v2, s1, s2 have one length n, a power of two, and are folded in place (truncated to one element at the end);
+        the bases and the table hold at least n elements and are only read."""
+        n = len(v1)
+        if n == 0 or n & (n - 1):
+            raise ValueError("the length of a Dory-Reduce is a power of two")
+        if any(len(v) != n for v in (v2, s1, s2)):
+            raise ValueError("the vectors of a Dory-Reduce have one length")
+        if len(gamma1) < n or len(gamma2) < n or gamma2_prepared.n < n:
+            raise ValueError("the bases of a Dory-Reduce are at least as long as its vectors")
+        self = cls.__new__(cls)
+        self.ctx, self.n = ctx, n
+        self._owned = []
+        self.v1, self.v2, self.s1, self.s2, self.gamma1, self.gamma2 = v1, v2, s1, s2, gamma1, gamma2
+        self.gamma2_prepared = gamma2_prepared
+        self._owns_prepared = False
+        self._one = ffi.host_fr_from_u64(1)
+        return self
 
     def _keep(self, v):
         self._owned.append(v)
@@ -48,7 +70,8 @@ class DoryReduce:
             v.free()
         self._owned = []
         if getattr(self, "gamma2_prepared", None) is not None:
-            self.gamma2_prepared.free()
+            if self._owns_prepared:
+                self.gamma2_prepared.free()
             self.gamma2_prepared = None
 
     def _inverse_pair(self, x, x_inv, name):

@@ -1597,6 +1597,41 @@ def _dory_vec_fold_field(self, left, right, scalar):
     _ck(lib().jolt_dory_vec_fold_field(self.h, lv.h, C.c_size_t(lf), rv.h, C.c_size_t(rf), C.c_size_t(n), _p(fr(scalar))), "jolt_dory_vec_fold_field", self)
 
 
+def _dory_state_alloc(self, kind, n):
+    """n neutral elements on the device (jolt_dory_state_alloc): identities (1, 1, 0), or zeros for DORY_KIND_FR; enqueued, not awaited"""
+    h = C.c_void_p()
+    _ck(lib().jolt_dory_state_alloc(self.h, C.c_int32(kind), C.c_size_t(n), C.byref(h)), "jolt_dory_state_alloc", self)
+    return DoryVec(self, h, kind)
+
+
+def _dory_state_from_table(self, table, dst, table_first=0):
+    """dst[i] = table[table_first + i] over the Fr view dst = DoryVec or (DoryVec, first, n): a device copy (jolt_dory_state_from_table); enqueued, not awaited"""
+    dv, df, n = _dory_view(dst)
+    _ck(lib().jolt_dory_state_from_table(self.h, table.h, C.c_size_t(table_first), dv.h, C.c_size_t(df), C.c_size_t(n)), "jolt_dory_state_from_table", self)
+
+
+def _dory_state_combine_hints(self, hints, scalars, out, out_first=0):
+    """DoryScheme::combine_hints on resident G1 views: out[out_first + row] = sum_i scalars[i] * hints[i][row], hints = DoryVec or (DoryVec, first, rows) each
+    (jolt_dory_state_combine_hints); the number of rows written, max_i rows_i"""
+    views = [_dory_view(h) for h in hints]
+    n = len(views)
+    hs = (C.c_void_p * max(n, 1))(*[v.h for v, _, _ in views])
+    firsts = (C.c_size_t * max(n, 1))(*[f for _, f, _ in views])
+    rows = (C.c_size_t * max(n, 1))(*[r for _, _, r in views])
+    sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if n else fr_array(1)
+    if sc.shape[0] != max(n, 1):
+        raise ValueError("one scalar per hint")
+    _ck(lib().jolt_dory_state_combine_hints(self.h, hs, firsts, rows, C.c_size_t(n), _p(sc), out.h, C.c_size_t(out_first)), "jolt_dory_state_combine_hints", self)
+    return max([r for _, _, r in views], default=0)
+
+
+def _dory_state_fixed_base_mul(self, kind, base, scalars, out):
+    """out[i] = scalars[i] * base on views (fixed_base_vector_scalar_mul): kind = DORY_KIND_G1 / _G2, base one host point, scalars an Fr view, out a view of `kind`"""
+    b = np.ascontiguousarray(base, dtype=np.uint64).reshape(_DORY_KIND_WIDTH[kind])
+    sv, sf, ov, of, n = _dory_two_views(scalars, out)
+    _ck(lib().jolt_dory_state_fixed_base_mul(self.h, C.c_int32(kind), _p(b), sv.h, C.c_size_t(sf), ov.h, C.c_size_t(of), C.c_size_t(n)), "jolt_dory_state_fixed_base_mul", self)
+
+
 def dory_item(op, a, b, prepared_first=0):
     """one item of a product batch: a, b = DoryVec or (DoryVec, first, n); for DORY_PAIR b may be a G2Prepared, read from point prepared_first on"""
     av, af, n = _dory_view(a)
@@ -1636,6 +1671,10 @@ Context.dory_vec_scale_bases_add = _dory_vec_scale_bases_add
 Context.dory_vec_scale_vs_add = _dory_vec_scale_vs_add
 Context.dory_vec_fold_field = _dory_vec_fold_field
 Context.dory_products = _dory_products
+Context.dory_state_alloc = _dory_state_alloc
+Context.dory_state_from_table = _dory_state_from_table
+Context.dory_state_combine_hints = _dory_state_combine_hints
+Context.dory_state_fixed_base_mul = _dory_state_fixed_base_mul
 
 
 def _gt(a):

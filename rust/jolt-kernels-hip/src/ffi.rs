@@ -430,6 +430,10 @@ extern "C" {
     pub fn jolt_dory_vec_scale_bases_add(ctx: *mut jolt_ctx, bases: *const jolt_dory_vec, bases_first: usize, vs: *mut jolt_dory_vec, vs_first: usize, n: usize, scalar: *const jolt_fr_t) -> i32;
     pub fn jolt_dory_vec_scale_vs_add(ctx: *mut jolt_ctx, vs: *mut jolt_dory_vec, vs_first: usize, addends: *const jolt_dory_vec, addends_first: usize, n: usize, scalar: *const jolt_fr_t) -> i32;
     pub fn jolt_dory_vec_fold_field(ctx: *mut jolt_ctx, left: *mut jolt_dory_vec, left_first: usize, right: *const jolt_dory_vec, right_first: usize, n: usize, scalar: *const jolt_fr_t) -> i32;
+    pub fn jolt_dory_state_alloc(ctx: *mut jolt_ctx, kind: i32, n: usize, out: *mut *mut jolt_dory_vec) -> i32;
+    pub fn jolt_dory_state_from_table(ctx: *mut jolt_ctx, table: *const jolt_table, table_first: usize, dst: *mut jolt_dory_vec, dst_first: usize, n: usize) -> i32;
+    pub fn jolt_dory_state_combine_hints(ctx: *mut jolt_ctx, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, out: *mut jolt_dory_vec, out_first: usize) -> i32;
+    pub fn jolt_dory_state_fixed_base_mul(ctx: *mut jolt_ctx, kind: i32, base: *const c_void, scalars: *const jolt_dory_vec, scalars_first: usize, out: *mut jolt_dory_vec, out_first: usize, n: usize) -> i32;
     pub fn jolt_dory_products(ctx: *mut jolt_ctx, items: *const jolt_dory_item, n_items: usize, outs: *mut jolt_dory_result) -> i32;
     pub fn jolt_host_dory_batch_plan(lens: *const usize, n_items: usize, wg_cap: usize, wg_item: *mut u32, wg_first: *mut u32, item_base: *mut usize, n_wgs: *mut usize, levels: *mut u32) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
