@@ -759,6 +759,28 @@ int32_t jolt_dory_products(jolt_ctx *ctx, const jolt_dory_item *items, size_t n_
  * with wg_cap = 0 to ask for *n_wgs alone; more workgroups than wg_cap is JOLT_ERR_SIZE_MISMATCH, a padded total above 2^24 JOLT_ERR_UNSUPPORTED. */
 int32_t jolt_host_dory_batch_plan(const size_t *lens, size_t n_items, size_t wg_cap, uint32_t *wg_item, uint32_t *wg_first, size_t *item_base, size_t *n_wgs, uint32_t *levels);
 
+/* The witness commitment in front of an opening: the row commitments of jolt_dory_commit_onehot / jolt_dory_commit_rows written on the device, in OpeningHint order,
+ * into views of resident G1 vectors (jolt_dory_state_alloc), where jolt_dory_state_combine_hints and jolt_dory_products (one PAIR item per column against Gamma2's
+ * prepared table: the tier-2 commitments of a whole witness in one batch) read them.  Nothing crosses the link.  Every point is written normalised, (x / z^2, y / z^3, 1),
+ * by one batched inversion; the identity is (1, 1, 0).  The ABI leaves the Jacobian representative free, so this is a promise of these two entries alone.
+ * Contract of the resident entries above: a null handle, an `out` of another context or not of kind G1, or a view that does not hold the result is
+ * JOLT_ERR_INVALID_ARG; the shape checks keep the codes of the host-pointer entries (power-of-two width, JOLT_ERR_SRS_TOO_SMALL, JOLT_ERR_SIZE_MISMATCH); a refused call
+ * enqueues nothing and writes nothing.  Both are enqueued on the context's stream; jolt_dory_hints_rows synchronises once for the bit-length probe of its column. */
+/* out[out_first + p*K*chunks + row*chunks + chunk] for columns [first_poly, first_poly + n_polys) of `source`, K = source->k, chunks = cycles / chunk_width:
+ * the OpeningHint order of jolt_dory_commit_onehot's comment.  batch_points = 0: the default 2^26 keys per launch set; otherwise the cap (a whole number of
+ * chunks, >= chunk_width), for the tests. */
+int32_t jolt_dory_hints_onehot(jolt_ctx *ctx, const jolt_srs *srs, const jolt_onehot *source, size_t first_poly, size_t n_polys, size_t chunk_width,
+                               jolt_dory_vec *out, size_t out_first, size_t batch_points);
+/* out[out_first + r] = row commitment r of jolt_dory_commit_rows, normalised */
+int32_t jolt_dory_hints_rows(jolt_ctx *ctx, const jolt_srs *srs, const jolt_ints *values, size_t row_width, jolt_dory_vec *out, size_t out_first);
+/* The per-lane routine of the kernel behind both, on the host for the CPU suite: out[i] = points[i] normalised, the inversions batched by Montgomery's trick over runs
+ * of `run` consecutive points (one inversion per run; a point with z = 0 enters the running product as one and comes back as (1, 1, 0)).  The points are not checked.
+ * run = 0 or a null pointer with n > 0 is JOLT_ERR_INVALID_ARG. */
+int32_t jolt_host_dory_g1_normalise(const jolt_g1_t *points, size_t n, size_t run, jolt_g1_t *out);
+/* The kernel's index map for the one-hot columns, on the host: element e of a launch set that starts at window window0 (window = column * chunks + chunk) reads
+ * workspace bucket *src = (e / k) * (k + 1) + e % k + 1 and is element *dst of the destination view */
+int32_t jolt_host_dory_hint_map(uint32_t k, size_t chunks, size_t window0, size_t e, size_t *src, size_t *dst);
+
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)
  * for witness columns that already sit in HBM (no host round trip; jolt_table_from_u64 is the same from host memory). */

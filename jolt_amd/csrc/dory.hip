@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "dory_hints.hip.h"
 #include "dory_host.hpp"
 #include "msm_kernels.hip.h"
 #include "onehot.hpp"
@@ -299,15 +300,17 @@ BucketPlan plan_buckets(size_t V, uint32_t B, size_t n) {
 struct Workspace {
     uint32_t *keys, *sorted, *hist, *offs, *cur, *heavy, *hcnt;
     G1Jac *buckets, *seg, *out;
+    Fq* pool;
 };
-// Carve lane 0's grow-only MSM workspace for V windows of n points, B buckets each, `outs` result points.
-int32_t carve(jolt_ctx* ctx, size_t V, size_t n, uint32_t B, uint32_t heavy_cap, size_t outs, Workspace* w) {
+// Carve lane 0's grow-only MSM workspace for V windows of n points, B buckets each, `outs` result points and `pool` Fq cells (the running products of
+// k_dory_hints_normalise; none: the layout the host-pointer entries have always had).
+int32_t carve(jolt_ctx* ctx, size_t V, size_t n, uint32_t B, uint32_t heavy_cap, size_t outs, Workspace* w, size_t pool = 0) {
     const size_t VB = V * (B + 1);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
     size_t o_keys = take(V * n * 4), o_sorted = take(V * n * 4), o_hist = take(VB * 4), o_offs = take(VB * 4), o_cur = take(VB * 4),
            o_heavy = take((size_t)heavy_cap * 8), o_hcnt = take(256), o_buckets = take(VB * sizeof(G1Jac)),
-           o_seg = take((size_t)heavy_cap * sizeof(G1Jac)), o_out = take(outs * sizeof(G1Jac));
+           o_seg = take((size_t)heavy_cap * sizeof(G1Jac)), o_out = take(outs * sizeof(G1Jac)), o_pool = take(pool * sizeof(Fq));
     if (off > ctx->msm_ws_cap[0]) {
         if (ctx->msm_ws[0]) {
             JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -329,6 +332,7 @@ int32_t carve(jolt_ctx* ctx, size_t V, size_t n, uint32_t B, uint32_t heavy_cap,
     w->buckets = (G1Jac*)(ws + o_buckets);
     w->seg = (G1Jac*)(ws + o_seg);
     w->out = (G1Jac*)(ws + o_out);
+    w->pool = (Fq*)(ws + o_pool);
     return JOLT_OK;
 }
 
@@ -397,14 +401,42 @@ extern "C" int32_t jolt_ints_free(jolt_ctx* ctx, jolt_ints* v) {
     return JOLT_OK;
 }
 
-extern "C" int32_t jolt_dory_commit_rows(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, jolt_g1_t* out) {
-    if (!ctx || !srs || !values || (!out && values->count)) return JOLT_ERR_INVALID_ARG;
-    const int wl = log2_exact(row_width);
-    JOLT_REQUIRE(ctx, wl >= 0, "streaming: row width must be a power of two");  // streaming.rs:99-102
-    if (row_width > srs->n) return JOLT_ERR_SRS_TOO_SMALL;                        // :103-108
-    if (values->count % row_width) return JOLT_ERR_SIZE_MISMATCH;                 // :192-195
-    const size_t rows = values->count / row_width;
-    if (rows == 0) return JOLT_OK;
+namespace {
+
+// Where a batch of row commitments goes once the fold kernels have left it in the workspace: to the caller's host array, as jolt_dory_commit_rows always has ...
+struct RowsToHost {
+    jolt_g1_t* out;
+    size_t pool_cells(size_t) const { return 0; }
+    hipError_t zeros(jolt_ctx*, size_t rows) const {  // all-zero batch: every row commitment is the identity (Bn254G1::default())
+        G1Jac id = g1_identity();
+        for (size_t r = 0; r < rows; ++r) std::memcpy(&out[r], &id, sizeof(id));
+        return hipSuccess;
+    }
+    hipError_t emit(jolt_ctx* ctx, const Workspace& w, size_t r0, size_t nr) const {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out + r0, w.out, nr * sizeof(G1Jac), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        return e;
+    }
+};
+// ... or normalised into a resident G1 view (jolt_dory_hints_rows): enqueued only
+struct RowsToView {
+    G1Jac* out;
+    size_t pool_cells(size_t nr) const { return nr; }
+    hipError_t zeros(jolt_ctx* ctx, size_t rows) const {
+        hipLaunchKernelGGL(dory_hints::k_dory_hints_identity, dim3((unsigned)((rows + dory_hints::kLanes - 1) / dory_hints::kLanes)), dim3(dory_hints::kLanes), 0, ctx->stream, out, rows);
+        return hipGetLastError();
+    }
+    hipError_t emit(jolt_ctx* ctx, const Workspace& w, size_t r0, size_t nr) const {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = dory_hints::launch_normalise(ctx->stream, (const G1Jac*)w.out, dory_hints::RowsMap{}, nr, w.pool, out + r0);
+        return e;
+    }
+};
+
+// The row commitments of `values` (checked by the caller: wl = log2(row_width), rows > 0), batch by batch into `sink`
+template <class Sink>
+int32_t commit_rows_into(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, int wl, size_t rows, const Sink& sink) {
     hipStream_t st = ctx->stream;
     const int kind = values->kind;
 
@@ -425,10 +457,9 @@ extern "C" int32_t jolt_dory_commit_rows(jolt_ctx* ctx, const jolt_srs* srs, con
     int bits = 0;
     for (int k = 3; k >= 0 && !bits; --k)
         if (h_or[k]) bits = 32 * k + 32 - __builtin_clz(h_or[k]);
-    if (bits == 0) {  // all-zero batch: every row commitment is the identity (Bn254G1::default())
-        G1Jac id = g1_identity();
-        for (size_t r = 0; r < rows; ++r) std::memcpy(&out[r], &id, sizeof(id));
-        return JOLT_OK;
+    if (bits == 0) {
+        const hipError_t e = sink.zeros(ctx, rows);
+        return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory rows", e);
     }
 
     // ---- plan: ~16 points per bucket; the top window keeps one spare bit for the signed-digit carry
@@ -441,7 +472,7 @@ extern "C" int32_t jolt_dory_commit_rows(jolt_ctx* ctx, const jolt_srs* srs, con
         const size_t nr = std::min(batch_rows, rows - r0), V = nr * (size_t)W, nvals = nr * row_width;
         BucketPlan p = plan_buckets(V, B, row_width);
         Workspace w;
-        JOLT_TRY(carve(ctx, V, row_width, B, p.heavy_cap, nr, &w));
+        JOLT_TRY(carve(ctx, V, row_width, B, p.heavy_cap, nr, &w, sink.pool_cells(nr)));
         const size_t VB = V * (B + 1);
         hipError_t e = hipMemsetAsync(w.hist, 0, VB * 4, st);
         if (e == hipSuccess) e = hipMemsetAsync(w.hcnt, 0, 256, st);
@@ -473,12 +504,42 @@ extern "C" int32_t jolt_dory_commit_rows(jolt_ctx* ctx, const jolt_srs* srs, con
             hipLaunchKernelGGL(k_rows_fold_lanes, dim3((unsigned)nr), dim3(B <= 64 ? 64 : 128), 0, st, (const G1Jac*)w.buckets, B, c, W, w.out);
         else
             hipLaunchKernelGGL(k_rows_fold, dim3((unsigned)nr), dim3(kBlock), 0, st, (const G1Jac*)w.buckets, B, c, W, w.out);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out + r0, w.out, nr * sizeof(G1Jac), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        e = sink.emit(ctx, w, r0, nr);
         if (e != hipSuccess) return hip_fail(ctx, "dory rows", e);
     }
     return JOLT_OK;
+}
+
+// the argument checks the two row entries share, with the reference's codes; rows = 0: nothing to do
+int32_t rows_shape(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, int* wl, size_t* rows) {
+    *wl = log2_exact(row_width);
+    JOLT_REQUIRE(ctx, *wl >= 0, "streaming: row width must be a power of two");  // streaming.rs:99-102
+    if (row_width > srs->n) return JOLT_ERR_SRS_TOO_SMALL;                         // :103-108
+    if (values->count % row_width) return JOLT_ERR_SIZE_MISMATCH;                  // :192-195
+    *rows = values->count / row_width;
+    return JOLT_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t jolt_dory_commit_rows(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, jolt_g1_t* out) {
+    if (!ctx || !srs || !values || (!out && values->count)) return JOLT_ERR_INVALID_ARG;
+    int wl;
+    size_t rows;
+    JOLT_TRY(rows_shape(ctx, srs, values, row_width, &wl, &rows));
+    if (rows == 0) return JOLT_OK;
+    return commit_rows_into(ctx, srs, values, row_width, wl, rows, RowsToHost{out});
+}
+
+extern "C" int32_t jolt_dory_hints_rows(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, jolt_dory_vec* out, size_t out_first) {
+    if (!ctx || !srs || !values || !out) return JOLT_ERR_INVALID_ARG;
+    int wl;
+    size_t rows;
+    JOLT_TRY(rows_shape(ctx, srs, values, row_width, &wl, &rows));
+    G1Jac* dst = (G1Jac*)dory_host::g1_view(ctx, out, out_first, rows);
+    JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the row commitments");
+    if (rows == 0) return JOLT_OK;
+    return commit_rows_into(ctx, srs, values, row_width, wl, rows, RowsToView{dst});
 }
 
 extern "C" int32_t jolt_dory_commit_onehot(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t poly, size_t chunk_width, jolt_g1_t* out) {
@@ -512,6 +573,82 @@ extern "C" int32_t jolt_dory_commit_onehot(jolt_ctx* ctx, const jolt_srs* srs, c
         if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return hip_fail(ctx, "dory one-hot", e);
     }
+    return JOLT_OK;
+}
+
+// The hints of columns [first_poly, first_poly + n_polys) at once.  The index array is [poly][cycle] contiguous and chunk_width divides the cycle count, so the range is
+// ONE key stream whose window i >> log2(chunk_width) runs over (column, chunk): k_onehot_keys and launch_bucket_sums serve a batch of those windows wherever it starts and
+// ends, inside a column or across several, and k_dory_hints_normalise writes each bucket where OneHotMap places its window.  Enqueued only: nothing comes back.
+extern "C" int32_t jolt_dory_hints_onehot(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t first_poly, size_t n_polys, size_t chunk_width,
+                                          jolt_dory_vec* out, size_t out_first, size_t batch_points) {
+    if (!ctx || !srs || !source || !out) return JOLT_ERR_INVALID_ARG;
+    JOLT_REQUIRE(ctx, !(first_poly > source->n_polys || n_polys > source->n_polys - first_poly), "the columns are past the source");
+    const int wl = log2_exact(chunk_width);
+    JOLT_REQUIRE(ctx, wl >= 0, "streaming one-hot: chunk length must be a power of two");  // streaming.rs:376-380
+    if (chunk_width > srs->n) return JOLT_ERR_SRS_TOO_SMALL;                                 // :381-392
+    if (source->cycles % chunk_width) return JOLT_ERR_SIZE_MISMATCH;
+    JOLT_REQUIRE(ctx, batch_points == 0 || (batch_points >= chunk_width && batch_points % chunk_width == 0), "batch_points is a whole number of chunks");
+    const size_t chunks = source->cycles / chunk_width;
+    const uint32_t K = source->k;
+    size_t per_column = 0, total = 0, windows = 0;
+    if (__builtin_mul_overflow((size_t)K, chunks, &per_column) || __builtin_mul_overflow(per_column, n_polys, &total) || __builtin_mul_overflow(n_polys, chunks, &windows))
+        return JOLT_ERR_UNSUPPORTED;
+    G1Jac* dst = (G1Jac*)dory_host::g1_view(ctx, out, out_first, total);
+    JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the hints");
+    if (total == 0) return JOLT_OK;
+    hipStream_t st = ctx->stream;
+    size_t batch = batch_points ? batch_points / chunk_width : std::max<size_t>(1, ((size_t)1 << 26) / chunk_width);
+    batch = std::min(std::min(batch, windows), (size_t)0xFFFFFFFFu / ((size_t)K + 1));  // bucket slots are u32
+    if (batch == 0) return JOLT_ERR_UNSUPPORTED;
+    for (size_t v0 = 0; v0 < windows; v0 += batch) {
+        const size_t V = std::min(batch, windows - v0), nvals = V * chunk_width;
+        BucketPlan p = plan_buckets(V, K, chunk_width);
+        Workspace w;
+        JOLT_TRY(carve(ctx, V, chunk_width, K, p.heavy_cap, 0, &w, V * K));
+        const size_t VB = V * ((size_t)K + 1);
+        hipError_t e = hipMemsetAsync(w.hist, 0, VB * 4, st);
+        if (e == hipSuccess) e = hipMemsetAsync(w.hcnt, 0, 256, st);
+        if (e == hipSuccess) e = hipMemsetAsync(w.buckets, 0, VB * sizeof(G1Jac), st);  // z = 0: identity
+        if (e != hipSuccess) return hip_fail(ctx, "dory one-hot hints", e);
+        const uint8_t* idx = source->idx + ((first_poly * source->cycles + v0 * chunk_width) << source->wide);
+        hipLaunchKernelGGL(k_onehot_keys, dim3((unsigned)((nvals + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, idx, source->wide, nvals, (uint32_t)wl, K, w.keys, w.hist);
+        launch_bucket_sums(ctx, w, srs->pts, V, chunk_width, K, p);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = dory_hints::launch_normalise(st, (const G1Jac*)w.buckets, dory_hints::OneHotMap{K, chunks, v0}, V * K, w.pool, dst);
+        if (e != hipSuccess) return hip_fail(ctx, "dory one-hot hints", e);
+    }
+    return JOLT_OK;
+}
+
+// k_dory_hints_normalise on the host, for the suite: lane r owns the points [r * run, (r + 1) * run) (on the device a lane's points are interleaved with its neighbours';
+// the routine is the same), the pool is a host array
+extern "C" int32_t jolt_host_dory_g1_normalise(const jolt_g1_t* points, size_t n, size_t run, jolt_g1_t* out) {
+    if (n == 0) return JOLT_OK;
+    if (!points || !out || run == 0) return JOLT_ERR_INVALID_ARG;
+    std::vector<Fq> pool(n);
+    struct Access {
+        const jolt_g1_t* points;
+        jolt_g1_t* out;
+        Fq* pool;
+        size_t first;
+        G1Jac point(uint32_t j) const {
+            G1Jac p;
+            std::memcpy(&p, &points[first + j], sizeof(p));
+            return p;
+        }
+        Fq z(uint32_t j) const { return point(j).z; }
+        void put(uint32_t j, const Fq& v) const { pool[first + j] = v; }
+        Fq get(uint32_t j) const { return pool[first + j]; }
+        void store(uint32_t j, const G1Jac& p) const { std::memcpy(&out[first + j], &p, sizeof(p)); }
+    };
+    const size_t lane_run = std::min<size_t>(run, 0xFFFFFFFFu);
+    for (size_t first = 0; first < n; first += lane_run) dory_hints::normalise_run((uint32_t)std::min(lane_run, n - first), Access{points, out, pool.data(), first});
+    return JOLT_OK;
+}
+// OneHotMap on the host: element e of a batch that starts at window0 reads workspace bucket *src and is hint element *dst
+extern "C" int32_t jolt_host_dory_hint_map(uint32_t k, size_t chunks, size_t window0, size_t e, size_t* src, size_t* dst) {
+    if (!src || !dst || k == 0 || chunks == 0) return JOLT_ERR_INVALID_ARG;
+    dory_hints::OneHotMap{k, chunks, window0}.at(e, *src, *dst);
     return JOLT_OK;
 }
 

@@ -73,5 +73,9 @@ bool combine_plan(const jolt_fr_t* scalars, size_t n, CombinePlan* plan);
 // d_points: G1Jac, the hints back to back; meta: the hints' offsets into d_points, then their row counts; d_out: G1Jac, `rows` of them
 int32_t combine_enqueue(jolt_ctx* ctx, const void* d_points, const std::vector<uint64_t>& meta, const CombinePlan& plan, size_t rows, void* d_out);
 
+// elements [first, first + n) of a resident G1 vector of this context (dory_resident.hip, where jolt_dory_vec is defined): the device address (G1Jac), or null when the
+// vector is of another kind or context or the view leaves it -- for the entries of dory.hip that write their results into resident vectors
+void* g1_view(const jolt_ctx* ctx, const jolt_dory_vec* vec, size_t first, size_t n);
+
 }  // namespace dory_host
 }  // namespace jolt

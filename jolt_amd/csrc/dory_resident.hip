@@ -217,6 +217,10 @@ constexpr size_t kMaxItems = 4096;
 
 }  // namespace
 
+void* jolt::dory_host::g1_view(const jolt_ctx* ctx, const jolt_dory_vec* vec, size_t first, size_t n) {
+    return view_ok(ctx, vec, JOLT_DORY_KIND_G1, first, n) ? (void*)at<G1Jac>(vec, first) : nullptr;
+}
+
 extern "C" int32_t jolt_dory_vec_upload(jolt_ctx* ctx, int32_t kind, const void* host, size_t n, jolt_dory_vec** out) {
     if (!ctx || !out || (n && !host)) return JOLT_ERR_INVALID_ARG;
     JOLT_REQUIRE(ctx, kind == JOLT_DORY_KIND_G1 || kind == JOLT_DORY_KIND_G2 || kind == JOLT_DORY_KIND_FR, "unknown vector kind");

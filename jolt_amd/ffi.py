@@ -1677,6 +1677,41 @@ Context.dory_state_combine_hints = _dory_state_combine_hints
 Context.dory_state_fixed_base_mul = _dory_state_fixed_base_mul
 
 
+# ---- the witness commitment in front of an opening (dory.hip, dory_hints.hip.h): row commitments written on the device, normalised, in hint order
+def _dory_hints_onehot(self, srs, source, out, chunk_width, first_poly=0, n_polys=None, out_first=0, batch_points=0):
+    """the hints of columns [first_poly, first_poly + n_polys) of a OneHot into the G1 vector `out` from element out_first on (jolt_dory_hints_onehot):
+    out[out_first + p * k * chunks + row * chunks + chunk]; enqueued, not awaited.  The number of elements written."""
+    n_polys = source.n_polys - first_poly if n_polys is None else n_polys
+    _ck(lib().jolt_dory_hints_onehot(self.h, srs.h, source.h, C.c_size_t(first_poly), C.c_size_t(n_polys), C.c_size_t(chunk_width), out.h, C.c_size_t(out_first),
+                                     C.c_size_t(batch_points)), "jolt_dory_hints_onehot", self)
+    return n_polys * source.k * (source.cycles // chunk_width)
+
+
+def _dory_hints_rows(self, srs, values, row_width, out, out_first=0):
+    """the row commitments of dory_commit_rows into the G1 vector `out` from element out_first on, normalised (jolt_dory_hints_rows).  The number of rows."""
+    _ck(lib().jolt_dory_hints_rows(self.h, srs.h, values.h, C.c_size_t(row_width), out.h, C.c_size_t(out_first)), "jolt_dory_hints_rows", self)
+    return values.count // row_width
+
+
+def host_dory_g1_normalise(points, run):
+    """the per-lane routine of the hint kernel on the host: every point as (x / z^2, y / z^3, 1), the identity as (1, 1, 0), one inversion per `run` points"""
+    pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
+    out = g1_array(max(pts.shape[0], 1))
+    _ck(lib().jolt_host_dory_g1_normalise(_p(pts) if pts.shape[0] else None, C.c_size_t(pts.shape[0]), C.c_size_t(run), _p(out)), "jolt_host_dory_g1_normalise")
+    return out[:pts.shape[0]]
+
+
+def host_dory_hint_map(k, chunks, window0, e):
+    """the hint kernel's index map for one-hot columns: (workspace bucket, hint element) of element e of a launch set that starts at window0"""
+    src, dst = C.c_size_t(), C.c_size_t()
+    _ck(lib().jolt_host_dory_hint_map(C.c_uint32(k), C.c_size_t(chunks), C.c_size_t(window0), C.c_size_t(e), C.byref(src), C.byref(dst)), "jolt_host_dory_hint_map")
+    return src.value, dst.value
+
+
+Context.dory_hints_onehot = _dory_hints_onehot
+Context.dory_hints_rows = _dory_hints_rows
+
+
 def _gt(a):
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(48)
 

@@ -1,5 +1,5 @@
 //! Dory's reduce-and-fold rounds on vectors that stay on the device: thin safe wrappers over `jolt_dory_vec_*`, `jolt_dory_g2_prepare_vec`
-//! and `jolt_dory_products`.
+//! and `jolt_dory_products`; and the witness commitment that fills such vectors with opening hints (`jolt_dory_hints_onehot`, `jolt_dory_hints_rows`).
 //!
 //! WRITTEN BLIND, like the rest of this crate: no Rust toolchain has seen this file.  dory's `DoryRoutines` seam works on host slices and its
 //! `multi_pair` on host slices too, so nothing here binds to a trait: a caller reaches these wrappers from a prover loop of its own in front of
@@ -14,6 +14,8 @@ use dory::backends::arkworks::{ArkFr, ArkG1, ArkG2, ArkGT};
 
 use crate::context::HipContext;
 use crate::ffi;
+use crate::msm::HipSrs;
+use crate::ops::{HipHotIndices, HipInts};
 use crate::pairing::HipG2Prepared;
 use crate::status::{check, HipError};
 
@@ -62,8 +64,34 @@ impl HipDoryVec {
         Self::upload(ctx, VecKind::Fr, scalars.as_ptr().cast(), scalars.len())
     }
 
+    /// `n` neutral elements -- the identity (1, 1, 0), or zero for `Fr` -- made on the device: `jolt_dory_state_alloc`.  What [`HipDoryVec::hints_onehot`] and
+    /// [`HipDoryVec::hints_rows`] write into.
+    pub fn neutral(ctx: &Arc<HipContext>, kind: VecKind, n: usize) -> Result<Self, HipError> {
+        let mut raw = core::ptr::null_mut();
+        let _device = ctx.exclusive();
+        // SAFETY: `ctx.raw` is a live context; the library allocates and fills the vector.
+        check(unsafe { ffi::jolt_dory_state_alloc(ctx.raw, kind.raw(), n, &mut raw) }, ctx.raw)?;
+        Ok(Self { ctx: Arc::clone(ctx), raw, kind })
+    }
+
     pub fn kind(&self) -> VecKind {
         self.kind
+    }
+
+    /// The opening hints of columns `[first_column, first_column + n_columns)` of `source` into `self[out_first ..]`, element
+    /// `p * k * chunks + row * chunks + chunk` (the order of `finish_one_hot_column_major_chunks`), every point normalised: `jolt_dory_hints_onehot`, enqueued.
+    /// `chunk_width` is `2^sigma`; the launch sets hold the library's default number of keys.
+    pub fn hints_onehot(&mut self, out_first: usize, srs: &HipSrs, source: &HipHotIndices, first_column: usize, n_columns: usize, chunk_width: usize) -> Result<(), HipError> {
+        let _device = self.ctx.exclusive();
+        // SAFETY: live handles of one context; the library refuses a vector that is not G1 and a view that does not hold the hints.
+        check(unsafe { ffi::jolt_dory_hints_onehot(self.ctx.raw, srs.raw, source.raw, first_column, n_columns, chunk_width, self.raw, out_first, 0) }, self.ctx.raw)
+    }
+
+    /// The row commitments of a dense column of machine integers into `self[out_first ..]`, normalised: `jolt_dory_hints_rows` (`row_width` is `2^sigma`).
+    pub fn hints_rows(&mut self, out_first: usize, srs: &HipSrs, values: &HipInts, row_width: usize) -> Result<(), HipError> {
+        let _device = self.ctx.exclusive();
+        // SAFETY: as hints_onehot.
+        check(unsafe { ffi::jolt_dory_hints_rows(self.ctx.raw, srs.raw, values.raw, row_width, self.raw, out_first) }, self.ctx.raw)
     }
 
     pub fn len(&self) -> usize {

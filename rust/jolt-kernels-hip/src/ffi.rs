@@ -436,6 +436,10 @@ extern "C" {
     pub fn jolt_dory_state_fixed_base_mul(ctx: *mut jolt_ctx, kind: i32, base: *const c_void, scalars: *const jolt_dory_vec, scalars_first: usize, out: *mut jolt_dory_vec, out_first: usize, n: usize) -> i32;
     pub fn jolt_dory_products(ctx: *mut jolt_ctx, items: *const jolt_dory_item, n_items: usize, outs: *mut jolt_dory_result) -> i32;
     pub fn jolt_host_dory_batch_plan(lens: *const usize, n_items: usize, wg_cap: usize, wg_item: *mut u32, wg_first: *mut u32, item_base: *mut usize, n_wgs: *mut usize, levels: *mut u32) -> i32;
+    pub fn jolt_dory_hints_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, first_poly: usize, n_polys: usize, chunk_width: usize, out: *mut jolt_dory_vec, out_first: usize, batch_points: usize) -> i32;
+    pub fn jolt_dory_hints_rows(ctx: *mut jolt_ctx, srs: *const jolt_srs, values: *const jolt_ints, row_width: usize, out: *mut jolt_dory_vec, out_first: usize) -> i32;
+    pub fn jolt_host_dory_g1_normalise(points: *const jolt_g1_t, n: usize, run: usize, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_host_dory_hint_map(k: u32, chunks: usize, window0: usize, e: usize, src: *mut usize, dst: *mut usize) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;
