@@ -573,7 +573,7 @@ int32_t jolt_dory_commit_rows(jolt_ctx *ctx, const jolt_srs *srs, const jolt_int
 int32_t jolt_dory_commit_onehot(jolt_ctx *ctx, const jolt_srs *srs, const jolt_onehot *source, size_t poly, size_t chunk_width, jolt_g1_t *out);
 
 /* The G1 and Fr work of a Dory opening ahead of the pairing rounds.  Cycle-major placement (TracePolynomialOrder::CycleMajor): grid
- * index k*T + j, dense columns at k = 0, as for the jolt_grid_* entry points below.  The tier-2 multi-pairing and the multi-pairings of the reduce-and-fold rounds of
+ * index k*T + j, dense columns at k = 0, as for the jolt_grid_* entry points below (the address-major twins are jolt_dory_*_am further down).  The tier-2 multi-pairing and the multi-pairings of the reduce-and-fold rounds of
  * dory::prove are jolt_dory_multi_pair / jolt_dory_multi_pair_g2_setup below, the rounds' group routines jolt_dory_g1_* / jolt_dory_g2_*; what stays on the host is
  * GT scalings, the transcript, the control flow and commit_blind.
  *
@@ -780,6 +780,42 @@ int32_t jolt_host_dory_g1_normalise(const jolt_g1_t *points, size_t n, size_t ru
 /* The kernel's index map for the one-hot columns, on the host: element e of a launch set that starts at window window0 (window = column * chunks + chunk) reads
  * workspace bucket *src = (e / k) * (k + 1) + e % k + 1 and is element *dst of the destination view */
 int32_t jolt_host_dory_hint_map(uint32_t k, size_t chunks, size_t window0, size_t e, size_t *src, size_t *dst);
+
+/* The same witness commitment and row fold in the ADDRESS-MAJOR trace placement.  The reference's prover proves in either layout
+ * (crates/jolt-prover/src/dory/prover.rs:104-110; TracePolynomialOrder::{CycleMajor, AddressMajor}, crates/jolt-claims/src/protocols/jolt/geometry/dimensions.rs:20-59)
+ * and places both with one formula (TracePlacement, crates/jolt-kernels/src/optimized/opening.rs:340-373): the coefficient of (cycle t, address k) sits at grid index
+ *   (t << log_block) + (k << log_stride),   log_block = log2 CommitmentGrid::cycle_stride() = log_k + e,  log_stride = log2 CommitmentGrid::one_hot_stride() = e,
+ * e >= 0 the embedding extra of a widened grid (0 otherwise: index = cycle * K + address, address_cycle_to_index); dense columns at k = 0; with 2^sigma matrix
+ * columns row = index >> sigma, col = index & (2^sigma - 1).  For sigma >= log_block a row holds C = 2^(sigma - log_block) whole cycles, row r = the cycles
+ * [r C, (r + 1) C), and EVERY column, one-hot or dense, has cycles / C rows: hint[r] by matrix row is the only hint order there is.
+ * Contract of the resident entries above (views validated, null handles and foreign or non-G1 vectors JOLT_ERR_INVALID_ARG, a refused call enqueues nothing and writes
+ * nothing), and for all three: sigma < log_block is JOLT_ERR_UNSUPPORTED (a cycle's block wider than a row; it does not occur for log_k <= 8 and T >= 2^9, where
+ * sigma = ceil((log_k + log_t) / 2) >= log_k); log_stride > log_block, source->k > 2^(log_block - log_stride) and C not dividing the cycle count are
+ * JOLT_ERR_INVALID_ARG; 2^sigma > the SRS length is JOLT_ERR_SRS_TOO_SMALL. */
+/* out[out_first + p*rows + r] = sum_{j < C, hot_p(r C + j) not cold} srs[(j << log_block) + (hot_p(r C + j) << log_stride)] for the columns
+ * [first_poly, first_poly + n_polys) of `source`, rows = cycles >> (sigma - log_block); normalised, the identity as (1, 1, 0), as jolt_dory_hints_onehot promises.
+ * 8-bit and 16-bit sources.  Enqueued only. */
+int32_t jolt_dory_hints_onehot_am(jolt_ctx *ctx, const jolt_srs *srs, const jolt_onehot *source, size_t first_poly, size_t n_polys,
+                                  uint32_t sigma, uint32_t log_block, uint32_t log_stride, jolt_dory_vec *out, size_t out_first);
+/* out[out_first + r] = sum_{j < C} values[r C + j] * srs[j << log_block], normalised: jolt_dory_hints_rows with row width C over the C strided bases, which are
+ * gathered into a compact device array first (every integer kind; synchronises once for the bit-length probe, like jolt_dory_hints_rows). */
+int32_t jolt_dory_hints_rows_am(jolt_ctx *ctx, const jolt_srs *srs, const jolt_ints *values, uint32_t sigma, uint32_t log_block,
+                                jolt_dory_vec *out, size_t out_first);
+/* RlcSource::fold_rows in the address-major placement, the limits and codes of jolt_dory_fold_rows_grid (log_k there = log_block - log_stride here):
+ *   out[(j << log_block) + (k << log_stride)] = sum_p onehot_scalars[p] * sum_r [hot_p(r C + j) = k] * left[r]   (+ at k = 0: sum_d dense_scalars[d] * sum_r left[r] * dense_d[r C + j])
+ * and zero at every other entry.  left has T >> (sigma - log_block) entries (JOLT_ERR_SIZE_MISMATCH otherwise), out gets 2^sigma.  Temporary device memory is
+ * O(T + 2^sigma * T / (128 C)), never O(K * T). */
+int32_t jolt_dory_fold_rows_grid_am(jolt_ctx *ctx, const jolt_onehot *const *sources, size_t n_sources, const jolt_fr_t *onehot_scalars,
+                                    jolt_table *const *dense, size_t n_dense, const jolt_fr_t *dense_scalars,
+                                    uint32_t log_block, uint32_t log_stride, uint32_t sigma, const jolt_table *left, jolt_table **out);
+/* The placement on the host: *row and *col of (cycle, address).  log_stride > log_block or a null pointer is JOLT_ERR_INVALID_ARG. */
+int32_t jolt_host_dory_am_place(uint32_t log_block, uint32_t log_stride, uint32_t sigma, size_t cycle, size_t address, size_t *row, size_t *col);
+/* One row of jolt_dory_hints_onehot_am on the host, through the accumulation routine every lane of its kernel runs (limb-form mixed additions, the exceptional
+ * cases out of line) and the normalisation: out = sum_{j < cycles_in_row, hot[j] != 0xFFFF} bases[(j << log_block) + (hot[j] << log_stride)].  A lane owns a whole row,
+ * so there is no partition to pass.  JOLT_ERR_INVALID_ARG: a null pointer, k = 0 or k > 2^(log_block - log_stride), log_stride > log_block, or fewer bases than
+ * ((cycles_in_row - 1) << log_block) + ((k - 1) << log_stride) + 1.  For the CPU suite. */
+int32_t jolt_host_dory_am_row(const jolt_g1_t *bases /* z = 1 */, size_t n_bases, const uint16_t *hot, size_t cycles_in_row, uint32_t k, uint32_t log_block,
+                              uint32_t log_stride, jolt_g1_t *out);
 
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)

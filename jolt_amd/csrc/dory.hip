@@ -13,10 +13,12 @@
 // one workgroup per row that folds its windows (running-sum reduction + Horner).  Only the windows the batch's largest
 // magnitude needs are processed (an OR-reduction over the batch decides).  Integer VALU work, no MFMA.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "ctx.hpp"
+#include "dory_am.hip.h"
 #include "dory_hints.hip.h"
 #include "dory_host.hpp"
 #include "msm_kernels.hip.h"
@@ -435,8 +437,9 @@ struct RowsToView {
 };
 
 // The row commitments of `values` (checked by the caller: wl = log2(row_width), rows > 0), batch by batch into `sink`
+// (min_window: the narrow rows of the address-major entry ask for wider digits than the ~16 points per bucket rule gives them; 0: the rule alone)
 template <class Sink>
-int32_t commit_rows_into(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, int wl, size_t rows, const Sink& sink) {
+int32_t commit_rows_into(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, int wl, size_t rows, const Sink& sink, int min_window = 0) {
     hipStream_t st = ctx->stream;
     const int kind = values->kind;
 
@@ -463,7 +466,7 @@ int32_t commit_rows_into(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* va
     }
 
     // ---- plan: ~16 points per bucket; the top window keeps one spare bit for the signed-digit carry
-    const int c = std::max(3, std::min(13, wl - 4));
+    const int c = std::max(std::max(3, std::min(13, wl - 4)), min_window);
     const int W = (bits + 1 + c - 1) / c;
     if (W > kMaxRowWindows) return JOLT_ERR_UNSUPPORTED;
     const uint32_t B = 1u << (c - 1);
@@ -653,6 +656,134 @@ extern "C" int32_t jolt_host_dory_hint_map(uint32_t k, size_t chunks, size_t win
 }
 
 // =====================================================================================================================
+// Address-major placement (dory_am.hip.h): the hints of one-hot and dense columns.  Row r of every column is the cycles [r C, (r + 1) C), C = 2^(sigma - log_block).
+// =====================================================================================================================
+namespace {
+
+// the shape checks the address-major entries share; *C = cycles per row
+int32_t am_shape(jolt_ctx* ctx, uint32_t sigma, uint32_t log_block, uint32_t log_stride, size_t* C) {
+    JOLT_REQUIRE(ctx, log_stride <= log_block, "address-major: the one-hot stride exceeds the cycle stride");
+    if (sigma < log_block) return JOLT_ERR_UNSUPPORTED;  // a cycle's block wider than a row
+    JOLT_REQUIRE(ctx, sigma < 48, "address-major: sigma out of range");
+    *C = (size_t)1 << (sigma - log_block);
+    return JOLT_OK;
+}
+
+size_t am_batch_rows() {  // rows per launch set: 2^20 (128 MiB of sums and pool cells), or the cap the suite sets to force a cut inside a column
+    if (const char* e = std::getenv("JOLT_DORY_AM_BATCH_ROWS"))
+        if (std::atoll(e) > 0) return (size_t)std::atoll(e);
+    return (size_t)1 << 20;
+}
+
+}  // namespace
+
+extern "C" int32_t jolt_dory_hints_onehot_am(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t first_poly, size_t n_polys, uint32_t sigma,
+                                             uint32_t log_block, uint32_t log_stride, jolt_dory_vec* out, size_t out_first) {
+    if (!ctx || !srs || !source || !out) return JOLT_ERR_INVALID_ARG;
+    JOLT_REQUIRE(ctx, !(first_poly > source->n_polys || n_polys > source->n_polys - first_poly), "the columns are past the source");
+    size_t C;
+    JOLT_TRY(am_shape(ctx, sigma, log_block, log_stride, &C));
+    if (((size_t)1 << sigma) > srs->n) return JOLT_ERR_SRS_TOO_SMALL;
+    const uint32_t K = source->k;
+    JOLT_REQUIRE(ctx, (log_block - log_stride >= 32 || K <= (1u << (log_block - log_stride))), "address-major: a hot address outside the cycle's block");
+    JOLT_REQUIRE(ctx, source->cycles % C == 0, "address-major: the cycles per row do not divide the cycle count");
+    const size_t rows = source->cycles / C;
+    size_t total = 0;
+    if (__builtin_mul_overflow(rows, n_polys, &total)) return JOLT_ERR_UNSUPPORTED;
+    G1Jac* dst = (G1Jac*)dory_host::g1_view(ctx, out, out_first, total);
+    JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the hints");
+    if (total == 0) return JOLT_OK;
+    if (C > 0xFFFFFFFFull) return JOLT_ERR_UNSUPPORTED;
+    hipStream_t st = ctx->stream;
+    const size_t width = (size_t)1 << sigma, batch = std::min(am_batch_rows(), total);
+    // workspace: the sums of a launch set, their pool cells for the normalisation, then the L-form table (two Fq per base)
+    Workspace w;
+    JOLT_TRY(carve(ctx, 1, 1, 1, 16, batch, &w, batch + 2 * width));
+    G1Affine* table = reinterpret_cast<G1Affine*>(w.pool + batch);
+    const dory_am::Consts lc = dory_am::consts();
+    hipLaunchKernelGGL(dory_am::k_dory_am_bases, dim3((unsigned)((width + 255) / 256)), dim3(256), 0, st, (const G1Affine*)srs->pts, width, 0u, 1u, lc.one_l, table);
+    const uint8_t* idx = source->idx + ((first_poly * source->cycles) << source->wide);
+    const uint32_t words = (((C << source->wide) & 7) == 0 && ((uintptr_t)idx & 7) == 0) ? 1u : 0u;
+    for (size_t i0 = 0; i0 < total; i0 += batch) {
+        const size_t n = std::min(batch, total - i0);
+        hipLaunchKernelGGL(dory_am::k_dory_am_onehot_rows, dim3((unsigned)((n + dory_am::kLanes - 1) / dory_am::kLanes)), dim3(dory_am::kLanes), 0, st,
+                           idx + ((i0 * C) << source->wide), source->wide, words, n, (uint32_t)C, K, log_block, log_stride, (const G1Affine*)table, lc, w.out);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = dory_hints::launch_normalise(st, (const G1Jac*)w.out, dory_hints::RowsMap{}, n, w.pool, dst + i0);
+        if (e != hipSuccess) return hip_fail(ctx, "dory address-major one-hot hints", e);
+    }
+    return JOLT_OK;
+}
+
+// jolt_dory_hints_rows with row width C over the C strided bases srs[j << log_block]: they are gathered into a compact array (at most 2^sigma * 64 bytes, from the
+// pool) and the row kernels and the sink of the cycle-major entry run over it, with wider digits than their rule gives short rows.
+extern "C" int32_t jolt_dory_hints_rows_am(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, uint32_t sigma, uint32_t log_block, jolt_dory_vec* out,
+                                           size_t out_first) {
+    if (!ctx || !srs || !values || !out) return JOLT_ERR_INVALID_ARG;
+    size_t C;
+    JOLT_TRY(am_shape(ctx, sigma, log_block, 0, &C));
+    if (((size_t)1 << sigma) > srs->n) return JOLT_ERR_SRS_TOO_SMALL;
+    JOLT_REQUIRE(ctx, values->count % C == 0, "address-major: the cycles per row do not divide the column's length");
+    const size_t rows = values->count / C;
+    G1Jac* dst = (G1Jac*)dory_host::g1_view(ctx, out, out_first, rows);
+    JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the row commitments");
+    if (rows == 0) return JOLT_OK;
+    G1Affine* compact = nullptr;
+    JOLT_TRY(jolt_internal_dev_alloc(ctx, C * sizeof(G1Affine), (void**)&compact));
+    hipLaunchKernelGGL(dory_am::k_dory_am_bases, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, ctx->stream, (const G1Affine*)srs->pts, C, log_block, 0u, Fq::one(), compact);
+    hipError_t e = hipGetLastError();
+    int32_t rc = e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory address-major rows", e);
+    if (rc == JOLT_OK) {
+        jolt_srs strided;
+        strided.ctx = ctx;
+        strided.pts = compact;
+        strided.n = C;
+        // Rows of C = 2^8 or 2^9 values would get 8 or 16 buckets per window: one bucket per lane leaves most of a wavefront idle in the bucket sums and the row fold
+        // (measured 25 ms per column at T = 2^20).  Digits of up to 7 bits fill the 64 lanes; rows shorter than 2^4 keep the rule.
+        const int wl = (int)(sigma - log_block);
+        rc = commit_rows_into(ctx, &strided, values, C, wl, rows, RowsToView{dst}, std::min(7, wl - 1));
+    }
+    jolt_internal_dev_free(ctx, compact);  // back to the pool: reuse is stream-ordered
+    return rc;
+}
+
+extern "C" int32_t jolt_host_dory_am_place(uint32_t log_block, uint32_t log_stride, uint32_t sigma, size_t cycle, size_t address, size_t* row, size_t* col) {
+    if (!row || !col || log_stride > log_block || sigma >= 64 || log_block >= 64) return JOLT_ERR_INVALID_ARG;
+    if ((cycle << log_block) >> log_block != cycle || (address << log_stride) >> log_stride != address) return JOLT_ERR_INVALID_ARG;
+    const size_t index = dory_am::place(log_block, log_stride, cycle, address);
+    if (index < (cycle << log_block)) return JOLT_ERR_INVALID_ARG;
+    *row = index >> sigma;
+    *col = index & (((size_t)1 << sigma) - 1);
+    return JOLT_OK;
+}
+
+// dory_am::row_sum -- the routine every lane of k_dory_am_onehot_rows runs -- over one row on the host, then the normalisation; bases in the ABI's form with z = 1
+// (z = 0: the point at infinity), cold = 0xFFFF.  One lane sums a whole row, so there is no partition to pass.
+extern "C" int32_t jolt_host_dory_am_row(const jolt_g1_t* bases, size_t n_bases, const uint16_t* hot, size_t cycles_in_row, uint32_t k, uint32_t log_block,
+                                         uint32_t log_stride, jolt_g1_t* out) {
+    if (!bases || !out || (!hot && cycles_in_row) || k == 0 || log_stride > log_block || log_block >= 32 || cycles_in_row > 0xFFFFFFFFull) return JOLT_ERR_INVALID_ARG;
+    if (k > (1u << (log_block - log_stride))) return JOLT_ERR_INVALID_ARG;
+    if (cycles_in_row && dory_am::place(log_block, log_stride, cycles_in_row - 1, k - 1) >= n_bases) return JOLT_ERR_INVALID_ARG;
+    const dory_am::Consts lc = dory_am::consts();
+    std::vector<G1Affine> table(n_bases);
+    for (size_t i = 0; i < n_bases; ++i) {
+        G1Jac p;
+        std::memcpy(&p, &bases[i], sizeof(p));
+        G1Affine a;
+        a.x = p.z.is_zero() ? Fq::zero() : p.x;
+        a.y = p.z.is_zero() ? Fq::zero() : p.y;
+        table[i] = dory_am::to_lform(a, lc.one_l);
+    }
+    G1Jac sum = g1_identity();
+    if (cycles_in_row)
+        sum = dory_am::row_sum((uint32_t)cycles_in_row, k, log_block, log_stride, [&](uint32_t j) { return hot[j] == 0xFFFFu ? 0xFFFFFFFFu : (uint32_t)hot[j]; },
+                               table.data(), [](const G1Affine* p) { return *p; }, lc);
+    jolt_g1_t raw;
+    std::memcpy(&raw, &sum, sizeof(sum));
+    return jolt_host_dory_g1_normalise(&raw, 1, 1, out);
+}
+
+// =====================================================================================================================
 // The opening's G1 and Fr work ahead of the pairing rounds (crates/jolt-dory/src/scheme.rs): the vector-matrix product
 // of dory::prove, answered lazily from the per-cycle columns (RlcSource::fold_rows over TraceOpeningPoly,
 // crates/jolt-kernels/src/optimized/opening.rs:439-511, crates/jolt-poly/src/multilinear.rs:447-462), and
@@ -662,6 +793,7 @@ namespace {
 
 constexpr int kFoldMaxSources = 4;   // the limits of jolt_grid_joint_polynomial (pcs.hip)
 constexpr int kFoldMaxDense = 8;
+constexpr uint32_t kAmFoldSlice = 128;  // matrix rows per thread of k_dory_am_fold: 2^sigma * rows / 128 threads, partial sums of 2^sigma * rows / 128 entries
 constexpr uint32_t kFoldSlice = 32;  // matrix rows per address block that one workgroup stages in LDS and one thread walks
 struct FoldArgs {
     const uint8_t* idx[kFoldMaxSources];  // [polys of the source][cycles]
@@ -738,6 +870,57 @@ __global__ __launch_bounds__(kBlock) void k_dory_fold_sum(const Fr* __restrict__
     Fr acc = ld_fr(partial + c);
     for (uint32_t s = 1; s < slices; ++s) acc = add(acc, ld_fr(partial + (size_t)s * cols + c));
     st_fr(out + c, acc);
+}
+// The same product in the address-major placement: output column c = (j << log_block) + (k << log_stride) takes the cycles r C + j of every matrix row r whose hot
+// address is k -- a gather, no atomics, and no bins: thread = (column, row slice) compares each index byte with ITS address, so log_k = 8 costs compares, not registers.
+// The 2^log_block lanes that share j read the same byte (a broadcast), left[r] is uniform per step; additions only inside, one multiplication by the polynomial's
+// scalar per (polynomial, column, slice).  Columns no (j, k) maps to (widened grids) get zero.  Dense columns live on k = 0.  partial[s * 2^sigma + c].
+__global__ __launch_bounds__(kBlock) void k_dory_am_fold(FoldArgs a, const Fr* __restrict__ scalars, const Fr* __restrict__ left, size_t T, size_t rows, uint32_t log_block,
+                                                         uint32_t log_stride, uint32_t sigma, uint32_t slice, uint32_t col_groups, Fr* __restrict__ partial) {
+    const size_t cols = (size_t)1 << sigma;
+    const uint32_t sl = blockIdx.x / col_groups;
+    const size_t c = (size_t)(blockIdx.x % col_groups) * kBlock + threadIdx.x;
+    if (c >= cols) return;
+    const size_t C = (size_t)1 << (sigma - log_block), j = c >> log_block;
+    const uint32_t within = (uint32_t)(c & (((size_t)1 << log_block) - 1));
+    const bool mapped = (within & ((1u << log_stride) - 1)) == 0;
+    const uint32_t k = mapped ? within >> log_stride : kColdIdx;  // a cold cycle never equals an address: hot_load gives kColdIdx, an unmapped column asks for it
+    const size_t r0 = (size_t)sl * slice, r1 = r0 + slice < rows ? r0 + slice : rows;
+    Fr acc = Fr::zero();
+    for (int s = 0; s < a.n_sources; ++s) {
+        for (uint32_t p = 0; p < a.n_polys[s]; ++p) {
+            const uint8_t* col = hot_col(a.idx[s], (size_t)p * T, a.wide[s]);
+            Fr sum = Fr::zero();
+            bool any = false;
+#pragma unroll 4
+            for (size_t r = r0; r < r1; ++r) {
+                const uint32_t h = hot_load(col, r * C + j, a.wide[s]);
+                if (mapped && h == k) {
+                    sum = add(sum, ld_fr(left + r));
+                    any = true;
+                }
+            }
+            if (any) acc = add(acc, mul(sum, scalars[a.first[s] + p]));
+        }
+    }
+    if (within == 0) {
+        for (int d = 0; d < a.n_dense; ++d) {
+            Fr sum = Fr::zero();
+            WideAcc<FrParams> w = wide_zero<FrParams>();
+            int pending = 0;
+            for (size_t r = r0; r < r1; ++r) {
+                wide_fmadd(w, ld_fr(left + r), ld_fr(a.dense[d] + r * C + j));
+                if (++pending == kWideMaxProducts) {
+                    sum = add(sum, wide_reduce(w));
+                    w = wide_zero<FrParams>();
+                    pending = 0;
+                }
+            }
+            if (pending) sum = add(sum, wide_reduce(w));
+            acc = add(acc, mul(sum, a.dense_scalar[d]));
+        }
+    }
+    st_fr(partial + (size_t)sl * cols + c, acc);
 }
 // sigma > log_t: the column index takes in the low sigma - log_t address bits, c = ((hot & amask) << log_t) | j, and the row is hot >> (sigma - log_t).  Still a
 // gather: one thread per output column walks the polynomials of its cycle.  The plain general path.
@@ -920,6 +1103,73 @@ extern "C" int32_t jolt_dory_fold_rows_grid(jolt_ctx* ctx, const jolt_onehot* co
     } else {
         hipLaunchKernelGGL(k_dory_fold_wide, dim3((unsigned)((cols + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, a, d_scalars, (const Fr*)left->data(),
                            (uint32_t)log_t, sigma, K, r->data());
+    }
+    hipError_t e = st == JOLT_OK ? hipGetLastError() : hipSuccess;
+    if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered
+    if (ds) jolt_table_free(ctx, ds);
+    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
+    if (e != hipSuccess) { jolt_table_free(ctx, r); ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
+    *out = r;
+    return JOLT_OK;
+}
+
+extern "C" int32_t jolt_dory_fold_rows_grid_am(jolt_ctx* ctx, const jolt_onehot* const* sources, size_t n_sources, const jolt_fr_t* onehot_scalars,
+                                               jolt_table* const* dense, size_t n_dense, const jolt_fr_t* dense_scalars, uint32_t log_block, uint32_t log_stride,
+                                               uint32_t sigma, const jolt_table* left, jolt_table** out) {
+    if (!ctx || !out || !left || (n_sources && (!sources || !onehot_scalars)) || (n_dense && (!dense || !dense_scalars))) return JOLT_ERR_INVALID_ARG;
+    size_t C;
+    JOLT_TRY(am_shape(ctx, sigma, log_block, log_stride, &C));
+    if (n_sources > (size_t)kFoldMaxSources || n_dense > (size_t)kFoldMaxDense || log_block - log_stride > 8 || n_sources + n_dense == 0) return JOLT_ERR_UNSUPPORTED;
+    const uint32_t K = 1u << (log_block - log_stride);
+    FoldArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (size_t s = 0; s < n_sources; ++s) if (!sources[s]) return JOLT_ERR_INVALID_ARG;
+    for (size_t d = 0; d < n_dense; ++d) if (!dense[d]) return JOLT_ERR_INVALID_ARG;
+    const size_t T = n_sources ? sources[0]->cycles : dense[0]->len;
+    JOLT_REQUIRE(ctx, T % C == 0, "address-major: the cycles per row do not divide the cycle count");
+    const size_t rows = T / C;
+    size_t total = 0;
+    for (size_t s = 0; s < n_sources; ++s) {
+        if (sources[s]->cycles != T) return JOLT_ERR_SIZE_MISMATCH;
+        JOLT_REQUIRE(ctx, sources[s]->k <= K, "fold_rows: a hot address outside the grid");
+        a.idx[s] = sources[s]->idx;
+        a.wide[s] = sources[s]->wide;
+        a.n_polys[s] = (uint32_t)sources[s]->n_polys;
+        a.first[s] = (uint32_t)total;
+        total += sources[s]->n_polys;
+    }
+    a.n_sources = (int)n_sources;
+    for (size_t d = 0; d < n_dense; ++d) {
+        if (dense[d]->len != T) return JOLT_ERR_SIZE_MISMATCH;
+        a.dense[d] = dense[d]->data();
+        a.dense_scalar[d] = fr_from_abi(&dense_scalars[d]);
+        JOLT_REQUIRE(ctx, fr_is_canonical(a.dense_scalar[d]), "scalar is not a canonical Fr");
+    }
+    a.n_dense = (int)n_dense;
+    if (left->len != rows) return JOLT_ERR_SIZE_MISMATCH;
+    for (size_t p = 0; p < total; ++p) JOLT_REQUIRE(ctx, fr_is_canonical(fr_from_abi(&onehot_scalars[p])), "scalar is not a canonical Fr");
+
+    const size_t cols = (size_t)1 << sigma;
+    jolt_table *r = nullptr, *ds = nullptr;
+    JOLT_TRY(jolt_internal_table_new(ctx, cols, &r));
+    int32_t st = JOLT_OK;
+    if (rows == 0) st = JOLT_ERR_SIZE_MISMATCH;
+    if (st == JOLT_OK && total) st = jolt_table_upload(ctx, onehot_scalars, total, &ds);  // synchronises: the caller's array may be short-lived
+    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
+    const Fr* d_scalars = ds ? (const Fr*)ds->data() : (const Fr*)nullptr;
+    Fr* partial = nullptr;
+    const uint32_t slice = (uint32_t)std::min<size_t>(rows, kAmFoldSlice);
+    const size_t slices = (rows + slice - 1) / slice, groups = (cols + kBlock - 1) / kBlock;
+    if (slices * groups > 0x7FFFFFFFull) st = JOLT_ERR_UNSUPPORTED;
+    Fr* dst = r->data();
+    if (st == JOLT_OK && slices > 1) {
+        st = jolt_internal_dev_alloc(ctx, slices * cols * sizeof(Fr), (void**)&partial);
+        dst = partial;
+    }
+    if (st == JOLT_OK) {
+        hipLaunchKernelGGL(k_dory_am_fold, dim3((unsigned)(slices * groups)), dim3(kBlock), 0, ctx->stream, a, d_scalars, (const Fr*)left->data(), T, rows, log_block,
+                           log_stride, sigma, slice, (uint32_t)groups, dst);
+        if (slices > 1) hipLaunchKernelGGL(k_dory_fold_sum, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, (const Fr*)partial, cols, (uint32_t)slices, r->data());
     }
     hipError_t e = st == JOLT_OK ? hipGetLastError() : hipSuccess;
     if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered

@@ -11,31 +11,63 @@ Every source is ONE jolt_dory_hints_onehot call over all of its columns, every d
 straight into resident G1 vectors, so nothing crosses the link between the witness and the first message of the opening.  `.hints` are views of those vectors,
 `DoryOpening(setup, commitment.hints, ...)` takes them as they are, and `.commit()` is one Context.dory_products call with one PAIR item per column against the
 setup's prepared Gamma2.
+
+order="address_major" commits the same columns in the other placement the reference proves in (TracePolynomialOrder::AddressMajor): grid index
+(t << log_block) + (k << log_stride) with log_block = log_k + log_extra, log_stride = log_extra.  A matrix row is then C = 2^(sigma - log_block) whole cycles and EVERY
+column, one-hot or dense, has cycles / C rows:
+
+    one-hot column                 hint[r] = the sum of Gamma1[(j << log_block) + (hot(r C + j) << log_stride)] over the hot cycles j < C of row r
+    dense column                   hint[r] = sum_j values[r C + j] * Gamma1[j << log_block]
+
+through one jolt_dory_hints_onehot_am call per source and one jolt_dory_hints_rows_am call per dense column.  The hints are resident G1 views of `rows` normalised
+points in matrix-row order either way, so DoryOpening and .commit() do not know the difference; the row fold of such an opening is Context.dory_fold_rows_grid_am.
 """
 from . import ffi
 
 
 class DoryWitnessCommitment:
-    def __init__(self, setup, srs, sources, dense, sigma):
+    def __init__(self, setup, srs, sources, dense, sigma, order="cycle_major", log_k=None, log_extra=0):
         """setup: a dory_open.DorySetup; srs: a jolt_srs (ffi.Srs) over Gamma1's first 2^sigma points at least; sources: ffi.OneHot handles; dense: ffi.Ints columns.
-        Every shape is checked here, before anything is enqueued; the inputs stay the caller's."""
+        order: "cycle_major" (log_k and log_extra are not used) or "address_major" (log_k: log2 of the grid's addresses, log_extra: the embedding extra of a widened
+        grid).  Every shape is checked here, before anything is enqueued; the inputs stay the caller's."""
+        if order not in ("cycle_major", "address_major"):
+            raise ValueError("order is cycle_major or address_major")
+        address_major = order == "address_major"
         width = 1 << sigma
         if width > len(srs):
             raise ValueError("the SRS holds fewer than 2^sigma bases")
         shapes = []  # per vector: (source or column, rows per column, columns)
-        for s in sources:
-            if s.cycles % width:
-                raise ValueError("2^sigma does not divide a source's cycle count")
-            shapes.append((s, s.k * (s.cycles // width), s.n_polys))
-        for d in dense:
-            if d.count % width:
-                raise ValueError("2^sigma does not divide a dense column's length")
-            shapes.append((d, d.count // width, 1))
+        if address_major:
+            if log_k is None or log_k < 0 or log_extra < 0:
+                raise ValueError("address_major needs log_k, and log_extra >= 0")
+            log_block = log_k + log_extra
+            if sigma < log_block:
+                raise ValueError("sigma < log_k + log_extra: a cycle's block is wider than a matrix row")
+            per_row = 1 << (sigma - log_block)
+            for s in sources:
+                if s.k > 1 << log_k:
+                    raise ValueError("a source has more than 2^log_k addresses")
+                if s.cycles % per_row:
+                    raise ValueError("the cycles of a matrix row do not divide a source's cycle count")
+                shapes.append((s, s.cycles // per_row, s.n_polys))
+            for d in dense:
+                if d.count % per_row:
+                    raise ValueError("the cycles of a matrix row do not divide a dense column's length")
+                shapes.append((d, d.count // per_row, 1))
+        else:
+            for s in sources:
+                if s.cycles % width:
+                    raise ValueError("2^sigma does not divide a source's cycle count")
+                shapes.append((s, s.k * (s.cycles // width), s.n_polys))
+            for d in dense:
+                if d.count % width:
+                    raise ValueError("2^sigma does not divide a dense column's length")
+                shapes.append((d, d.count // width, 1))
         if not shapes:
             raise ValueError("a witness has at least one column")
         if any(rows > setup.n for _, rows, _ in shapes):
             raise ValueError("a column has more rows than the setup has Gamma2 bases")
-        self.setup, self.ctx, self.sigma = setup, setup.ctx, sigma
+        self.setup, self.ctx, self.sigma, self.order = setup, setup.ctx, sigma, order
         self.hints = []
         self._vecs = []
         self._commitments = None
@@ -43,7 +75,11 @@ class DoryWitnessCommitment:
             for k, (col, rows, columns) in enumerate(shapes):
                 vec = self.ctx.dory_state_alloc(ffi.DORY_KIND_G1, rows * columns)
                 self._vecs.append(vec)
-                if k < len(sources):
+                if address_major and k < len(sources):
+                    self.ctx.dory_hints_onehot_am(srs, col, vec, sigma, log_block, log_extra)
+                elif address_major:
+                    self.ctx.dory_hints_rows_am(srs, col, sigma, log_block, vec)
+                elif k < len(sources):
                     self.ctx.dory_hints_onehot(srs, col, vec, chunk_width=width)
                 else:
                     self.ctx.dory_hints_rows(srs, col, width, vec)

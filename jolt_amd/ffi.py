@@ -1712,6 +1712,58 @@ Context.dory_hints_onehot = _dory_hints_onehot
 Context.dory_hints_rows = _dory_hints_rows
 
 
+# ---- the same in the address-major trace placement (dory_am.hip.h): grid index (t << log_block) + (k << log_stride), row r = the cycles [r C, (r + 1) C)
+def _dory_hints_onehot_am(self, srs, source, out, sigma, log_block, log_stride=0, first_poly=0, n_polys=None, out_first=0):
+    """the address-major hints of columns [first_poly, first_poly + n_polys) of a OneHot into the G1 vector `out` (jolt_dory_hints_onehot_am):
+    out[out_first + p * rows + r], rows = cycles >> (sigma - log_block); enqueued, not awaited.  The number of elements written."""
+    n_polys = source.n_polys - first_poly if n_polys is None else n_polys
+    _ck(lib().jolt_dory_hints_onehot_am(self.h, srs.h, source.h, C.c_size_t(first_poly), C.c_size_t(n_polys), C.c_uint32(sigma), C.c_uint32(log_block),
+                                        C.c_uint32(log_stride), out.h, C.c_size_t(out_first)), "jolt_dory_hints_onehot_am", self)
+    return n_polys * (source.cycles >> (sigma - log_block))
+
+
+def _dory_hints_rows_am(self, srs, values, sigma, log_block, out, out_first=0):
+    """the address-major row commitments of a dense column, out[out_first + r] = sum_j values[r C + j] * srs[j << log_block], normalised (jolt_dory_hints_rows_am)"""
+    _ck(lib().jolt_dory_hints_rows_am(self.h, srs.h, values.h, C.c_uint32(sigma), C.c_uint32(log_block), out.h, C.c_size_t(out_first)), "jolt_dory_hints_rows_am", self)
+    return values.count >> (sigma - log_block)
+
+
+def _dory_fold_rows_grid_am(self, sources, onehot_scalars, dense, dense_scalars, log_block, log_stride, sigma, left):
+    """RlcSource::fold_rows(left, sigma) of the batch's joint polynomial in the address-major placement (jolt_dory_fold_rows_grid_am): 2^sigma entries."""
+    hs = (C.c_void_p * max(len(sources), 1))(*[s.h for s in sources])
+    ds = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
+    osc = fr(np.stack([fr(c) for c in onehot_scalars])).reshape(-1, 4) if len(onehot_scalars) else None
+    dsc = fr(np.stack([fr(c) for c in dense_scalars])).reshape(-1, 4) if len(dense_scalars) else None
+    h = C.c_void_p()
+    _ck(lib().jolt_dory_fold_rows_grid_am(self.h, hs if sources else None, C.c_size_t(len(sources)), _p(osc), ds if dense else None, C.c_size_t(len(dense)),
+                                          _p(dsc), C.c_uint32(log_block), C.c_uint32(log_stride), C.c_uint32(sigma), left.h, C.byref(h)), "jolt_dory_fold_rows_grid_am", self)
+    return Table(self, h)
+
+
+def host_dory_am_place(log_block, log_stride, sigma, cycle, address):
+    """(row, column) of the coefficient of (cycle, address) in the address-major matrix of 2^sigma columns"""
+    row, col = C.c_size_t(), C.c_size_t()
+    _ck(lib().jolt_host_dory_am_place(C.c_uint32(log_block), C.c_uint32(log_stride), C.c_uint32(sigma), C.c_size_t(cycle), C.c_size_t(address), C.byref(row), C.byref(col)),
+        "jolt_host_dory_am_place")
+    return row.value, col.value
+
+
+def host_dory_am_row(bases, hot, k, log_block, log_stride=0):
+    """one row of dory_hints_onehot_am through the kernel's accumulation routine and the normalisation: bases (n, 12) with z = 1, hot = the row's hot addresses
+    (0xFFFF = cold); the (12,) point"""
+    pts = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 12)
+    idx = np.ascontiguousarray(hot, dtype=np.uint16)
+    out = g1_array(1)
+    _ck(lib().jolt_host_dory_am_row(_p(pts), C.c_size_t(pts.shape[0]), idx.ctypes.data_as(C.c_void_p) if idx.size else None, C.c_size_t(idx.size), C.c_uint32(k),
+                                    C.c_uint32(log_block), C.c_uint32(log_stride), _p(out)), "jolt_host_dory_am_row")
+    return out[0]
+
+
+Context.dory_hints_onehot_am = _dory_hints_onehot_am
+Context.dory_hints_rows_am = _dory_hints_rows_am
+Context.dory_fold_rows_grid_am = _dory_fold_rows_grid_am
+
+
 def _gt(a):
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(48)
 

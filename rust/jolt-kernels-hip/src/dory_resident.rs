@@ -1,5 +1,6 @@
 //! Dory's reduce-and-fold rounds on vectors that stay on the device: thin safe wrappers over `jolt_dory_vec_*`, `jolt_dory_g2_prepare_vec`
-//! and `jolt_dory_products`; and the witness commitment that fills such vectors with opening hints (`jolt_dory_hints_onehot`, `jolt_dory_hints_rows`).
+//! and `jolt_dory_products`; and the witness commitment that fills such vectors with opening hints (`jolt_dory_hints_onehot`, `jolt_dory_hints_rows`),
+//! in either trace placement (`jolt_dory_hints_onehot_am`, `jolt_dory_hints_rows_am`, `jolt_dory_fold_rows_grid_am` for `TraceOrder::AddressMajor`).
 //!
 //! WRITTEN BLIND, like the rest of this crate: no Rust toolchain has seen this file.  dory's `DoryRoutines` seam works on host slices and its
 //! `multi_pair` on host slices too, so nothing here binds to a trait: a caller reaches these wrappers from a prover loop of its own in front of
@@ -12,7 +13,7 @@ use std::sync::Arc;
 
 use dory::backends::arkworks::{ArkFr, ArkG1, ArkG2, ArkGT};
 
-use crate::context::HipContext;
+use crate::context::{HipContext, HipTable};
 use crate::ffi;
 use crate::msm::HipSrs;
 use crate::ops::{HipHotIndices, HipInts};
@@ -34,6 +35,15 @@ impl VecKind {
             VecKind::Fr => ffi::JOLT_DORY_KIND_FR,
         }
     }
+}
+
+/// The layout of the committed trace polynomials: the shape of `TracePolynomialOrder` (crates/jolt-claims/src/protocols/jolt/geometry/dimensions.rs:20-59).
+/// `AddressMajor` carries the placement of `TracePlacement`: `log_block = log2 cycle_stride()`, `log_stride = log2 one_hot_stride()`; the coefficient of
+/// (cycle t, address k) sits at grid index `(t << log_block) + (k << log_stride)`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum TraceOrder {
+    CycleMajor,
+    AddressMajor { log_block: u32, log_stride: u32 },
 }
 
 /// A G1, G2 or Fr array resident on the device.
@@ -92,6 +102,31 @@ impl HipDoryVec {
         let _device = self.ctx.exclusive();
         // SAFETY: as hints_onehot.
         check(unsafe { ffi::jolt_dory_hints_rows(self.ctx.raw, srs.raw, values.raw, row_width, self.raw, out_first) }, self.ctx.raw)
+    }
+
+    /// [`HipDoryVec::hints_onehot`] in the given trace order.  Address-major: element `p * rows + r`, `rows = cycles >> (sigma - log_block)`, row `r` the sum over
+    /// the cycles `[r C, (r + 1) C)`: `jolt_dory_hints_onehot_am`, enqueued.
+    pub fn hints_onehot_in(&mut self, order: TraceOrder, out_first: usize, srs: &HipSrs, source: &HipHotIndices, first_column: usize, n_columns: usize, sigma: u32) -> Result<(), HipError> {
+        match order {
+            TraceOrder::CycleMajor => self.hints_onehot(out_first, srs, source, first_column, n_columns, 1usize << sigma),
+            TraceOrder::AddressMajor { log_block, log_stride } => {
+                let _device = self.ctx.exclusive();
+                // SAFETY: as hints_onehot; the library refuses sigma < log_block and a source with more addresses than the block holds.
+                check(unsafe { ffi::jolt_dory_hints_onehot_am(self.ctx.raw, srs.raw, source.raw, first_column, n_columns, sigma, log_block, log_stride, self.raw, out_first) }, self.ctx.raw)
+            }
+        }
+    }
+
+    /// [`HipDoryVec::hints_rows`] in the given trace order.  Address-major: `self[out_first + r] = sum_j values[r C + j] * srs[j << log_block]`: `jolt_dory_hints_rows_am`.
+    pub fn hints_rows_in(&mut self, order: TraceOrder, out_first: usize, srs: &HipSrs, values: &HipInts, sigma: u32) -> Result<(), HipError> {
+        match order {
+            TraceOrder::CycleMajor => self.hints_rows(out_first, srs, values, 1usize << sigma),
+            TraceOrder::AddressMajor { log_block, .. } => {
+                let _device = self.ctx.exclusive();
+                // SAFETY: as hints_onehot.
+                check(unsafe { ffi::jolt_dory_hints_rows_am(self.ctx.raw, srs.raw, values.raw, sigma, log_block, self.raw, out_first) }, self.ctx.raw)
+            }
+        }
     }
 
     pub fn len(&self) -> usize {
@@ -237,4 +272,24 @@ pub fn products(ctx: &Arc<HipContext>, items: &[DoryItem<'_>]) -> Result<Vec<Dor
             }
         })
         .collect())
+}
+
+/// `RlcSource::fold_rows(left, sigma)` of a batch's joint polynomial from its per-cycle columns, in the given trace order: `jolt_dory_fold_rows_grid` (`log_k` is the
+/// grid's address bits) or `jolt_dory_fold_rows_grid_am` (`log_k` is not used: the placement says it).  `2^sigma` entries.
+#[allow(clippy::too_many_arguments)]
+pub fn fold_rows_in(ctx: &Arc<HipContext>, order: TraceOrder, sources: &[&HipHotIndices], onehot_scalars: &[ArkFr], dense: &[&HipTable], dense_scalars: &[ArkFr], log_k: u32,
+                    sigma: u32, left: &HipTable) -> Result<HipTable, HipError> {
+    let hs: Vec<*const ffi::jolt_onehot> = sources.iter().map(|s| s.raw as *const ffi::jolt_onehot).collect();
+    let ds: Vec<*mut ffi::jolt_table> = dense.iter().map(|t| t.raw).collect();
+    let mut raw = core::ptr::null_mut();
+    let _device = ctx.exclusive();
+    // SAFETY: live handles of one context, borrowed for the call; `ArkFr` is layout-compatible with `jolt_fr_t`; the library checks every length.
+    let status = unsafe {
+        match order {
+            TraceOrder::CycleMajor => ffi::jolt_dory_fold_rows_grid(ctx.raw, hs.as_ptr(), hs.len(), onehot_scalars.as_ptr().cast(), ds.as_ptr(), ds.len(), dense_scalars.as_ptr().cast(), log_k, sigma, left.raw, &mut raw),
+            TraceOrder::AddressMajor { log_block, log_stride } => ffi::jolt_dory_fold_rows_grid_am(ctx.raw, hs.as_ptr(), hs.len(), onehot_scalars.as_ptr().cast(), ds.as_ptr(), ds.len(), dense_scalars.as_ptr().cast(), log_block, log_stride, sigma, left.raw, &mut raw),
+        }
+    };
+    check(status, ctx.raw)?;
+    Ok(HipTable { ctx: Arc::clone(ctx), raw })
 }

@@ -440,6 +440,11 @@ extern "C" {
     pub fn jolt_dory_hints_rows(ctx: *mut jolt_ctx, srs: *const jolt_srs, values: *const jolt_ints, row_width: usize, out: *mut jolt_dory_vec, out_first: usize) -> i32;
     pub fn jolt_host_dory_g1_normalise(points: *const jolt_g1_t, n: usize, run: usize, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_host_dory_hint_map(k: u32, chunks: usize, window0: usize, e: usize, src: *mut usize, dst: *mut usize) -> i32;
+    pub fn jolt_dory_hints_onehot_am(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, first_poly: usize, n_polys: usize, sigma: u32, log_block: u32, log_stride: u32, out: *mut jolt_dory_vec, out_first: usize) -> i32;
+    pub fn jolt_dory_hints_rows_am(ctx: *mut jolt_ctx, srs: *const jolt_srs, values: *const jolt_ints, sigma: u32, log_block: u32, out: *mut jolt_dory_vec, out_first: usize) -> i32;
+    pub fn jolt_dory_fold_rows_grid_am(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_block: u32, log_stride: u32, sigma: u32, left: *const jolt_table, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_host_dory_am_place(log_block: u32, log_stride: u32, sigma: u32, cycle: usize, address: usize, row: *mut usize, col: *mut usize) -> i32;
+    pub fn jolt_host_dory_am_row(bases: *const jolt_g1_t, n_bases: usize, hot: *const u16, cycles_in_row: usize, k: u32, log_block: u32, log_stride: u32, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;
