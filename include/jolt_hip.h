@@ -817,6 +817,37 @@ int32_t jolt_host_dory_am_place(uint32_t log_block, uint32_t log_stride, uint32_
 int32_t jolt_host_dory_am_row(const jolt_g1_t *bases /* z = 1 */, size_t n_bases, const uint16_t *hot, size_t cycles_in_row, uint32_t k, uint32_t log_block,
                               uint32_t log_stride, jolt_g1_t *out);
 
+/* Dory for polynomials held as FIELD ELEMENTS: the first column kind of the reference's trait.  StreamingCommitment::feed(&[Fr]) per row
+ * (crates/jolt-dory/src/streaming.rs:53-70), the dense arm of DoryScheme::commit (commit_rows_dense, scheme.rs:455-472), commit_advice
+ * (crates/jolt-kernels/src/reference/commitment.rs:101-122):
+ *   out[r] = sum_{j < row_width} table[first + r*row_width + j] * srs[j],   r < count / row_width.
+ * The scalars are the table's Montgomery words; a scalar s is multiplied as its magnitude min(s, r - s) with the sign folded into the point, and only the windows
+ * the stretch's largest magnitude needs are run (an OR-reduction, one synchronisation, as for the integer rows): a table of u64-range values or of small negatives
+ * runs the windows jolt_dory_commit_rows runs for the same magnitudes and width.  Full-width scalars widen the digits until the windows fit the row fold
+ * (c = max(log2(row_width) - 4, 6) there).  Codes of jolt_dory_commit_rows: a width that is not a power of two JOLT_ERR_INVALID_ARG, JOLT_ERR_SRS_TOO_SMALL,
+ * JOLT_ERR_SIZE_MISMATCH when the width does not divide count; first + count beyond the table (wrap-around included) JOLT_ERR_INVALID_ARG.  An all-zero row is the
+ * identity (1, 1, 0). */
+int32_t jolt_dory_commit_rows_fr(jolt_ctx *ctx, const jolt_srs *srs, const jolt_table *table, size_t first, size_t count, size_t row_width, jolt_g1_t *out);
+/* The same rows, normalised, in row order into a resident G1 view: the promises and the contract of jolt_dory_hints_rows. */
+int32_t jolt_dory_hints_rows_fr(jolt_ctx *ctx, const jolt_srs *srs, const jolt_table *table, size_t first, size_t count, size_t row_width, jolt_dory_vec *out,
+                                size_t out_first);
+/* For the CPU suite, through the code the kernels run.  digits_out[w] = |digit| | (digit < 0) << 31 of window w < W of min(s, r - s) in signed c-bit digits
+ * (3 <= c <= 13, W <= 85 = ceil(255 / 3): the host form is not held to the device's 48 window sums), *negative_out = 1 when r - s was taken: sum_w digit_w 2^(c w) is s, or r - s negated.  The plan: *c and *W for magnitudes of
+ * bit_length bits (1..254) in rows of row_width values. */
+int32_t jolt_host_dory_fr_digits(const jolt_fr_t *scalar, int32_t c, int32_t W, uint32_t *digits_out, uint32_t *negative_out);
+int32_t jolt_host_dory_rows_fr_plan(uint32_t bit_length, size_t row_width, int32_t *c, int32_t *W);
+/* fold_rows of dense field tables, whole or embedded top-left in the grid -- BlockOpeningPoly::fold_rows (crates/jolt-kernels/src/optimized/opening.rs:594-611):
+ * coefficient r*2^sigma_d + c of table d sits at grid index r*2^sigma + c, so
+ *   out[c] = (base ? base[c] : 0) + sum_d scalars[d] * sum_{r < 2^(m_d - sigma_d)} left[r] * tables[d][(r << sigma_d) + c]   for c < 2^sigma_d (nothing above).
+ * With base = the output of jolt_dory_fold_rows_grid or _am it is the joint fold_rows of trace and block-embedded polynomials (advice, bytecode chunks, the program
+ * image; the embedding is the same in both placements); with one table of sigma_d = sigma and no base, the dense vector_matrix_product of scheme.rs:612-618.
+ * len(tables[d]) = 2^m_d with sigma_d <= min(m_d, sigma), else JOLT_ERR_INVALID_ARG; more rows than `left` has entries or a base not of 2^sigma entries
+ * JOLT_ERR_SIZE_MISMATCH; n_tables = 0 JOLT_ERR_INVALID_ARG, more than 8 JOLT_ERR_UNSUPPORTED.  Temporary device memory O(2^sigma * rows / 64). */
+int32_t jolt_dory_fold_rows_blocks(jolt_ctx *ctx, jolt_table *const *tables, const uint32_t *sigma_tables, size_t n_tables, const jolt_fr_t *scalars,
+                                   uint32_t sigma, const jolt_table *left, const jolt_table *base /* may be NULL */, jolt_table **out /* 2^sigma */);
+/* *index = ((i >> sigma_table) << sigma_grid) | (i & (2^sigma_table - 1)); sigma_table > sigma_grid or an index past 64 bits is JOLT_ERR_INVALID_ARG */
+int32_t jolt_host_dory_block_index(uint32_t sigma_table, uint32_t sigma_grid, size_t i, size_t *index);
+
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)
  * for witness columns that already sit in HBM (no host round trip; jolt_table_from_u64 is the same from host memory). */

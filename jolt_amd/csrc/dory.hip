@@ -6,6 +6,8 @@
 //       values as v = -|v|);
 //   process_one_hot_chunk(s_with) (:230-275) -> one_hot_chunk_commitments (:366-419) -> jolt_dory_commit_onehot:
 //       commitment[k] = sum of the bases of the columns whose hot row is k (no scalar multiplications at all).
+//   feed(&[Fr]) (:53-70), commit_rows_dense (scheme.rs:455-472), commit_advice -> jolt_dory_commit_rows_fr / jolt_dory_hints_rows_fr: the rows of a device field
+//       table, the integer rows' kernels instantiated with an eight-word magnitude (dory_rows_fr.hip.h).
 // Tier 2 (pairings into GT, commit_rows_tier_2) is outside SURVEY.md section 8.
 //
 // Both are the bucket method of msm.hip with more bucket sets: a "window" is (row, digit window) for the integer rows and
@@ -21,6 +23,7 @@
 #include "dory_am.hip.h"
 #include "dory_hints.hip.h"
 #include "dory_host.hpp"
+#include "dory_rows_fr.hip.h"
 #include "msm_kernels.hip.h"
 #include "onehot.hpp"
 #include "srs.hpp"
@@ -36,9 +39,21 @@ constexpr int kMaxRowWindows = 48;  // LDS window sums of the row fold: 129 bits
 
 __host__ __device__ inline size_t int_bytes(int kind) { return kind == JOLT_INT_I128 ? 16 : 8; }
 
-// |v| as a 128-bit magnitude in four u32 (LE) and the sign
+// A fourth kind beside JOLT_INT_U64 / _I64 / _I128, internal to this file: the packed magnitudes k_fr_magnitudes writes for a stretch of a field table
+// (dory_rows_fr.hip.h).  The integer kinds carry four magnitude words through the row kernels, this one eight.
+constexpr int kKindFrMag = 3;
 template <int KIND>
-__device__ __forceinline__ void load_magnitude(const void* __restrict__ data, size_t i, uint32_t m[4], uint32_t& negative) {
+struct MagWords { static constexpr int value = 4; };
+template <>
+struct MagWords<kKindFrMag> { static constexpr int value = dory_fr::kWords; };
+
+// |v| as a 128-bit magnitude in four u32 (LE) and the sign; a field element's 254-bit magnitude in eight
+template <int KIND>
+__device__ __forceinline__ void load_magnitude(const void* __restrict__ data, size_t i, uint32_t* m, uint32_t& negative) {
+    if constexpr (KIND == kKindFrMag) {
+        dory_fr::unpack(reinterpret_cast<const uint4*>(data) + 2 * i, m, negative);
+        return;
+    }
     uint64_t lo, hi;
     if (KIND == JOLT_INT_I128) {
         const uint64_t* p = reinterpret_cast<const uint64_t*>(data) + 2 * i;
@@ -81,7 +96,8 @@ __global__ __launch_bounds__(kBlock) void k_rows_digits(const void* __restrict__
                                                        uint32_t* __restrict__ keys, uint32_t* __restrict__ hist) {
     size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     const bool live = i < n;
-    uint32_t m[4] = {0, 0, 0, 0}, negv = 0;
+    constexpr int NW = MagWords<KIND>::value;
+    uint32_t m[NW] = {}, negv = 0;
     if (live) load_magnitude<KIND>(data, first + i, m, negv);
     const size_t row = i >> width_log, col = i & (((size_t)1 << width_log) - 1);
     const uint32_t B = 1u << (c - 1);
@@ -89,9 +105,9 @@ __global__ __launch_bounds__(kBlock) void k_rows_digits(const void* __restrict__
     for (int w = 0; w < W; ++w) {
         int bit = w * c;
         uint32_t raw = 0;
-        if (bit < 128) {
+        if (bit < 32 * NW) {
             int limb = bit >> 5, off = bit & 31;
-            uint64_t two = (uint64_t)m[limb] | (limb + 1 < 4 ? (uint64_t)m[limb + 1] << 32 : 0ull);
+            uint64_t two = (uint64_t)m[limb] | (limb + 1 < NW ? (uint64_t)m[limb + 1] << 32 : 0ull);
             raw = (uint32_t)(two >> off) & ((1u << c) - 1);
         }
         raw += carry;
@@ -106,25 +122,7 @@ __global__ __launch_bounds__(kBlock) void k_rows_digits(const void* __restrict__
     }
 }
 
-// The signed digit of window w of a 128-bit magnitude (the carry chain is replayed from window 0: W <= 48 cheap steps)
-__device__ __forceinline__ void digit_at(const uint32_t m[4], int c, int w, uint32_t& mag, uint32_t& negf) {
-    const uint32_t B = 1u << (c - 1);
-    uint32_t carry = 0;
-    mag = 0;
-    negf = 0;
-    for (int v = 0; v <= w; ++v) {
-        int bit = v * c;
-        uint32_t raw = 0;
-        if (bit < 128) {
-            int limb = bit >> 5, off = bit & 31;
-            uint64_t two = (uint64_t)m[limb] | (limb + 1 < 4 ? (uint64_t)m[limb + 1] << 32 : 0ull);
-            raw = (uint32_t)(two >> off) & ((1u << c) - 1);
-        }
-        raw += carry;
-        if (raw > B) { mag = (1u << c) - raw; negf = 1; carry = 1; }
-        else { mag = raw; negf = 0; carry = 0; }
-    }
-}
+using dory_fr::digit_at;  // the signed digit of window w of a magnitude of NW words (dory_rows_fr.hip.h: the host form runs it too)
 
 // Counting sort of one row's digits, window after window, entirely in LDS: blockIdx.x = row.  Replaces digits -> scan -> scatter
 // with their two global atomics per key (device-scope atomics cost ~90 ps each on this part: 1.7 of the 11 ms of a
@@ -148,9 +146,9 @@ __global__ __launch_bounds__(kBlock) void k_rows_sort_lds(const void* __restrict
             const uint32_t col = col0 + threadIdx.x;
             uint32_t mag = 0, negf = 0;
             if (col < width) {
-                uint32_t m[4], negv;
+                uint32_t m[MagWords<KIND>::value], negv;
                 load_magnitude<KIND>(data, base + col, m, negv);
-                digit_at(m, c, w, mag, negf);
+                digit_at<MagWords<KIND>::value>(m, c, w, mag, negf);
             }
             WaveAgg ag = wave_aggregate(mag, mag != 0);
             if (ag.do_atomic) atomicAdd(&cnt[mag], ag.count);
@@ -191,9 +189,9 @@ __global__ __launch_bounds__(kBlock) void k_rows_sort_lds(const void* __restrict
             const uint32_t col = col0 + threadIdx.x;
             uint32_t mag = 0, negf = 0, negv = 0;
             if (col < width) {
-                uint32_t m[4];
+                uint32_t m[MagWords<KIND>::value];
                 load_magnitude<KIND>(data, base + col, m, negv);
-                digit_at(m, c, w, mag, negf);
+                digit_at<MagWords<KIND>::value>(m, c, w, mag, negf);
             }
             WaveAgg ag = wave_aggregate(mag, mag != 0);
             uint32_t f0 = 0;
@@ -543,6 +541,163 @@ extern "C" int32_t jolt_dory_hints_rows(jolt_ctx* ctx, const jolt_srs* srs, cons
     JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the row commitments");
     if (rows == 0) return JOLT_OK;
     return commit_rows_into(ctx, srs, values, row_width, wl, rows, RowsToView{dst});
+}
+
+// =====================================================================================================================
+// Row commitments of a device field table: StreamingCommitment::feed(&[Fr]) per row (crates/jolt-dory/src/streaming.rs:53-70), the dense arm of DoryScheme::commit
+// (commit_rows_dense, scheme.rs:455-472), commit_advice.  The pipeline of the integer rows with an eight-word magnitude (dory_rows_fr.hip.h): one pass over the
+// stretch for the OR of the magnitudes, then per batch of rows the packed magnitudes (32 bytes per value, from the pool) and the kKindFrMag instantiations of the
+// digit / LDS sort kernels; bucket sums, heavy buckets, the row fold and the sinks are the integer rows' own.
+// =====================================================================================================================
+namespace {
+
+static_assert(kMaxRowWindows == dory_fr::kMaxWindows, "the window plan of dory_rows_fr.hip.h is cut to the LDS window sums of k_rows_fold");
+
+__global__ __launch_bounds__(kBlock) void k_fr_or(const Fr* __restrict__ table, size_t n, uint32_t* __restrict__ out8) {
+    uint32_t acc[dory_fr::kWords] = {};
+    for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+        uint32_t m[dory_fr::kWords], negf;
+        dory_fr::magnitude(ld_fr(table + i), m, negf);
+#pragma unroll
+        for (int k = 0; k < dory_fr::kWords; ++k) acc[k] |= m[k];
+    }
+#pragma unroll
+    for (int k = 0; k < dory_fr::kWords; ++k) {
+        for (int off = 32; off >= 1; off >>= 1) acc[k] |= (uint32_t)__shfl_xor((int)acc[k], off, 64);
+        if ((threadIdx.x & 63) == 0 && acc[k]) atomicOr(&out8[k], acc[k]);
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_fr_magnitudes(const Fr* __restrict__ table, size_t n, uint4* __restrict__ packed) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    uint32_t m[dory_fr::kWords], negf;
+    dory_fr::magnitude(ld_fr(table + i), m, negf);
+    dory_fr::pack(m, negf, packed + 2 * i);
+}
+
+// commit_rows_into for table[first, first + rows * row_width)
+template <class Sink>
+int32_t commit_rows_fr_into(jolt_ctx* ctx, const jolt_srs* srs, const Fr* values, size_t row_width, int wl, size_t rows, const Sink& sink) {
+    hipStream_t st = ctx->stream;
+    const size_t count = rows * row_width;
+    if (!ctx->msm_host[0]) JOLT_HIP_TRY(ctx, hipHostMalloc(&ctx->msm_host[0], 128 * sizeof(G1Jac), hipHostMallocDefault));
+    Workspace probe;
+    JOLT_TRY(carve(ctx, 1, 1, 1, 16, 1, &probe));
+    JOLT_HIP_TRY(ctx, hipMemsetAsync(probe.hcnt, 0, 256, st));
+    hipLaunchKernelGGL(k_fr_or, dim3((unsigned)std::min<size_t>((count + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st, values, count, probe.hcnt);
+    uint32_t* h_or = (uint32_t*)ctx->msm_host[0];
+    JOLT_HIP_TRY(ctx, hipMemcpyAsync(h_or, probe.hcnt, 4 * dory_fr::kWords, hipMemcpyDeviceToHost, st));
+    JOLT_HIP_TRY(ctx, hipStreamSynchronize(st));
+    int bits = 0;
+    for (int k = dory_fr::kWords - 1; k >= 0 && !bits; --k)
+        if (h_or[k]) bits = 32 * k + 32 - __builtin_clz(h_or[k]);
+    if (bits == 0) {
+        const hipError_t e = sink.zeros(ctx, rows);
+        return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory field rows", e);
+    }
+    int c, W;
+    dory_fr::plan(bits, wl, 0, &c, &W);
+    const uint32_t B = 1u << (c - 1);
+    // a batch is bounded by its keys, as the integer rows', and by its bucket slots: the widened digits give narrow rows 33 slots per window where c = 3 gives 5
+    const size_t by_keys = ((size_t)1 << 26) / ((size_t)W * row_width), by_slots = dory_fr::kMaxBatchSlots / ((size_t)W * (B + 1));
+    const size_t batch_rows = std::max<size_t>(1, std::min(rows, std::min(by_keys, by_slots)));
+    uint4* packed = nullptr;
+    JOLT_TRY(jolt_internal_dev_alloc(ctx, batch_rows * row_width * 2 * sizeof(uint4), (void**)&packed));
+    int32_t rc = JOLT_OK;
+    for (size_t r0 = 0; r0 < rows && rc == JOLT_OK; r0 += batch_rows) {
+        const size_t nr = std::min(batch_rows, rows - r0), V = nr * (size_t)W, nvals = nr * row_width;
+        BucketPlan p = plan_buckets(V, B, row_width);
+        Workspace w;
+        rc = carve(ctx, V, row_width, B, p.heavy_cap, nr, &w, sink.pool_cells(nr));
+        if (rc != JOLT_OK) break;
+        const size_t VB = V * (B + 1);
+        hipError_t e = hipMemsetAsync(w.hist, 0, VB * 4, st);
+        if (e == hipSuccess) e = hipMemsetAsync(w.hcnt, 0, 256, st);
+        if (e == hipSuccess) e = hipMemsetAsync(w.buckets, 0, VB * sizeof(G1Jac), st);  // z = 0: identity
+        if (e != hipSuccess) { rc = hip_fail(ctx, "dory field rows", e); break; }
+        const unsigned gv = (unsigned)((nvals + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_fr_magnitudes, dim3(gv), dim3(kBlock), 0, st, values + r0 * row_width, nvals, packed);
+        const size_t sort_lds = ((size_t)B + 1 + kBlock) * sizeof(uint32_t);
+        const bool lds_sort = ctx->msm_lds_sort && sort_lds <= 64 * 1024;
+        if (lds_sort)
+            hipLaunchKernelGGL(k_rows_sort_lds<kKindFrMag>, dim3((unsigned)nr), dim3(kBlock), sort_lds, st, (const void*)packed, (size_t)0, (uint32_t)wl, c, W, w.hist, w.offs,
+                               w.sorted, p.heavy_threshold, w.heavy, w.hcnt, p.heavy_cap);
+        else
+            hipLaunchKernelGGL(k_rows_digits<kKindFrMag>, dim3(gv), dim3(kBlock), 0, st, (const void*)packed, (size_t)0, nvals, (uint32_t)wl, c, W, w.keys, w.hist);
+        launch_bucket_sums(ctx, w, srs->pts, V, row_width, B, p, lds_sort);
+        if (B <= 128)
+            hipLaunchKernelGGL(k_rows_fold_lanes, dim3((unsigned)nr), dim3(B <= 64 ? 64 : 128), 0, st, (const G1Jac*)w.buckets, B, c, W, w.out);
+        else
+            hipLaunchKernelGGL(k_rows_fold, dim3((unsigned)nr), dim3(kBlock), 0, st, (const G1Jac*)w.buckets, B, c, W, w.out);
+        e = sink.emit(ctx, w, r0, nr);
+        if (e != hipSuccess) rc = hip_fail(ctx, "dory field rows", e);
+    }
+    jolt_internal_dev_free(ctx, packed);  // back to the pool: reuse is stream-ordered
+    return rc;
+}
+
+// the argument checks the two field-row entries share: jolt_dory_commit_rows' codes, and the stretch inside the table
+int32_t rows_fr_shape(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* table, size_t first, size_t count, size_t row_width, int* wl, size_t* rows) {
+    *wl = log2_exact(row_width);
+    JOLT_REQUIRE(ctx, *wl >= 0, "streaming: row width must be a power of two");
+    if (row_width > srs->n) return JOLT_ERR_SRS_TOO_SMALL;
+    JOLT_REQUIRE(ctx, table->data() && first <= table->len && count <= table->len - first, "the stretch leaves the table");
+    if (count % row_width) return JOLT_ERR_SIZE_MISMATCH;
+    *rows = count / row_width;
+    return JOLT_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t jolt_dory_commit_rows_fr(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* table, size_t first, size_t count, size_t row_width, jolt_g1_t* out) {
+    if (!ctx || !srs || !table || (!out && count)) return JOLT_ERR_INVALID_ARG;
+    int wl;
+    size_t rows;
+    JOLT_TRY(rows_fr_shape(ctx, srs, table, first, count, row_width, &wl, &rows));
+    if (rows == 0) return JOLT_OK;
+    return commit_rows_fr_into(ctx, srs, (const Fr*)table->data() + first, row_width, wl, rows, RowsToHost{out});
+}
+
+extern "C" int32_t jolt_dory_hints_rows_fr(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* table, size_t first, size_t count, size_t row_width, jolt_dory_vec* out,
+                                           size_t out_first) {
+    if (!ctx || !srs || !table || !out) return JOLT_ERR_INVALID_ARG;
+    int wl;
+    size_t rows;
+    JOLT_TRY(rows_fr_shape(ctx, srs, table, first, count, row_width, &wl, &rows));
+    G1Jac* dst = (G1Jac*)dory_host::g1_view(ctx, out, out_first, rows);
+    JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the row commitments");
+    if (rows == 0) return JOLT_OK;
+    return commit_rows_fr_into(ctx, srs, (const Fr*)table->data() + first, row_width, wl, rows, RowsToView{dst});
+}
+
+// The digits the kKindFrMag kernels give one scalar, on the host through the same routines: digits_out[w] = magnitude | negative << 31 of the signed digit of window w
+// of min(s, r - s), *negative_out = whether r - s was taken (the kernels fold it into each key's sign).  A plain loop with no window sums to hold: W goes up to the
+// ceil(255 / 3) = 85 windows of a full-width magnitude at c = 3, past the cap dory_fr::plan keeps for the device.
+extern "C" int32_t jolt_host_dory_fr_digits(const jolt_fr_t* scalar, int32_t c, int32_t W, uint32_t* digits_out, uint32_t* negative_out) {
+    if (!scalar || !digits_out || !negative_out || c < 3 || c > 13 || W < 1 || W > dory_fr::kMaxHostWindows) return JOLT_ERR_INVALID_ARG;
+    const Fr s = fr_from_abi(scalar);
+    if (!fr_is_canonical(s)) return JOLT_ERR_INVALID_ARG;
+    uint32_t m[dory_fr::kWords], negv, packed_neg;
+    dory_fr::magnitude(s, m, negv);
+    uint4 packed[2];
+    dory_fr::pack(m, negv, packed);
+    dory_fr::unpack(packed, m, packed_neg);
+    for (int w = 0; w < W; ++w) {
+        uint32_t mag, negf;
+        dory_fr::digit_at<dory_fr::kWords>(m, c, w, mag, negf);
+        digits_out[w] = mag | (negf << 31);
+    }
+    *negative_out = packed_neg;
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_dory_rows_fr_plan(uint32_t bit_length, size_t row_width, int32_t* c, int32_t* W) {
+    const int wl = log2_exact(row_width);
+    if (!c || !W || wl < 0 || bit_length == 0 || bit_length > 254) return JOLT_ERR_INVALID_ARG;
+    int cc, ww;
+    dory_fr::plan((int)bit_length, wl, 0, &cc, &ww);
+    *c = cc;
+    *W = ww;
+    return JOLT_OK;
 }
 
 extern "C" int32_t jolt_dory_commit_onehot(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t poly, size_t chunk_width, jolt_g1_t* out) {
@@ -1177,6 +1332,116 @@ extern "C" int32_t jolt_dory_fold_rows_grid_am(jolt_ctx* ctx, const jolt_onehot*
     if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
     if (e != hipSuccess) { jolt_table_free(ctx, r); ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
     *out = r;
+    return JOLT_OK;
+}
+
+// ---- fold_rows of dense field tables, whole or block-embedded ----------------------------------------------------------------
+// BlockOpeningPoly::fold_rows (crates/jolt-kernels/src/optimized/opening.rs:594-611): table d is a 2^(m_d - sigma_d) x 2^sigma_d matrix placed top-left in the
+// 2^nu x 2^sigma grid, coefficient r * 2^sigma_d + c at grid index r * 2^sigma + c.  Lane = column: a wavefront reads 64 consecutive field elements of a table row
+// and one (uniform) entry of `left`; the rows are cut into slices of kBlockFoldSlice, thread = (column, slice), products through the deferred-reduction accumulator
+// of the dense columns of k_dory_fold_cols.  partial[s * 2^sigma + c]; k_dory_fold_blocks_sum adds the slices and `base`.  No zero test per entry.
+namespace {
+
+constexpr uint32_t kBlockFoldSlice = 64;  // matrix rows per thread: DORY_BLOCK_FOLD_SLICE of jolt_amd/ffi.py
+struct BlockFoldArgs {
+    const Fr* table[kFoldMaxDense];
+    Fr scalar[kFoldMaxDense];
+    uint32_t sigma_d[kFoldMaxDense];
+    uint32_t log_rows[kFoldMaxDense];
+    int n;
+};
+
+__global__ __launch_bounds__(kBlock) void k_dory_fold_blocks(BlockFoldArgs a, const Fr* __restrict__ left, uint32_t sigma, uint32_t col_groups, Fr* __restrict__ partial) {
+    const size_t cols = (size_t)1 << sigma;
+    const uint32_t sl = blockIdx.x / col_groups;
+    const size_t c = (size_t)(blockIdx.x % col_groups) * kBlock + threadIdx.x;
+    if (c >= cols) return;
+    const size_t r0 = (size_t)sl * kBlockFoldSlice;
+    Fr acc = Fr::zero();
+    for (int d = 0; d < a.n; ++d) {
+        const size_t rows = (size_t)1 << a.log_rows[d], r1 = r0 + kBlockFoldSlice < rows ? r0 + kBlockFoldSlice : rows;
+        if ((c >> a.sigma_d[d]) != 0 || r0 >= r1) continue;  // outside the block
+        const Fr* col = a.table[d] + c;
+        Fr sum = Fr::zero();
+        WideAcc<FrParams> w = wide_zero<FrParams>();
+        int pending = 0;
+        for (size_t r = r0; r < r1; ++r) {
+            wide_fmadd(w, ld_fr(left + r), ld_fr(col + (r << a.sigma_d[d])));
+            if (++pending == kWideMaxProducts) {
+                sum = add(sum, wide_reduce(w));
+                w = wide_zero<FrParams>();
+                pending = 0;
+            }
+        }
+        if (pending) sum = add(sum, wide_reduce(w));
+        acc = add(acc, mul(sum, a.scalar[d]));
+    }
+    st_fr(partial + (size_t)sl * cols + c, acc);
+}
+__global__ __launch_bounds__(kBlock) void k_dory_fold_blocks_sum(const Fr* __restrict__ partial, const Fr* __restrict__ base, size_t cols, uint32_t slices,
+                                                                 Fr* __restrict__ out) {
+    const size_t c = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= cols) return;
+    Fr acc = base ? ld_fr(base + c) : Fr::zero();
+    for (uint32_t s = 0; s < slices; ++s) acc = add(acc, ld_fr(partial + (size_t)s * cols + c));
+    st_fr(out + c, acc);
+}
+
+}  // namespace
+
+extern "C" int32_t jolt_dory_fold_rows_blocks(jolt_ctx* ctx, jolt_table* const* tables, const uint32_t* sigma_tables, size_t n_tables, const jolt_fr_t* scalars,
+                                              uint32_t sigma, const jolt_table* left, const jolt_table* base, jolt_table** out) {
+    if (!ctx || !out || !left || !tables || !sigma_tables || !scalars || n_tables == 0) return JOLT_ERR_INVALID_ARG;
+    if (n_tables > (size_t)kFoldMaxDense) return JOLT_ERR_UNSUPPORTED;
+    JOLT_REQUIRE(ctx, sigma < 48 && left->data(), "fold_rows: sigma out of range");
+    BlockFoldArgs a;
+    std::memset(&a, 0, sizeof(a));
+    size_t max_rows = 0;
+    for (size_t d = 0; d < n_tables; ++d) {
+        if (!tables[d] || !tables[d]->data()) return JOLT_ERR_INVALID_ARG;
+        const int m = log2_exact(tables[d]->len);
+        JOLT_REQUIRE(ctx, m >= 0, "fold_rows: a block's length must be a power of two");
+        JOLT_REQUIRE(ctx, sigma_tables[d] <= (uint32_t)m && sigma_tables[d] <= sigma, "fold_rows: a block's columns exceed its variables or the grid's");
+        a.table[d] = tables[d]->data();
+        a.sigma_d[d] = sigma_tables[d];
+        a.log_rows[d] = (uint32_t)m - sigma_tables[d];
+        a.scalar[d] = fr_from_abi(&scalars[d]);
+        JOLT_REQUIRE(ctx, fr_is_canonical(a.scalar[d]), "scalar is not a canonical Fr");
+        max_rows = std::max(max_rows, (size_t)1 << a.log_rows[d]);
+    }
+    a.n = (int)n_tables;
+    if (max_rows > left->len) return JOLT_ERR_SIZE_MISMATCH;
+    const size_t cols = (size_t)1 << sigma;
+    if (base && (!base->data() || base->len != cols)) return JOLT_ERR_SIZE_MISMATCH;
+    const size_t slices = (max_rows + kBlockFoldSlice - 1) / kBlockFoldSlice, groups = (cols + kBlock - 1) / kBlock;
+    if (slices * groups > 0x7FFFFFFFull) return JOLT_ERR_UNSUPPORTED;
+    jolt_table* r = nullptr;
+    JOLT_TRY(jolt_internal_table_new(ctx, cols, &r));
+    Fr* partial = nullptr;
+    const bool direct = slices == 1 && !base;
+    int32_t st = direct ? JOLT_OK : jolt_internal_dev_alloc(ctx, slices * cols * sizeof(Fr), (void**)&partial);
+    hipError_t e = hipSuccess;
+    if (st == JOLT_OK) {
+        hipLaunchKernelGGL(k_dory_fold_blocks, dim3((unsigned)(slices * groups)), dim3(kBlock), 0, ctx->stream, a, (const Fr*)left->data(), sigma, (uint32_t)groups,
+                           direct ? r->data() : partial);
+        if (!direct)
+            hipLaunchKernelGGL(k_dory_fold_blocks_sum, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, (const Fr*)partial, base ? (const Fr*)base->data() : (const Fr*)nullptr,
+                               cols, (uint32_t)slices, r->data());
+        e = hipGetLastError();
+    }
+    if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered
+    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
+    if (e != hipSuccess) { jolt_table_free(ctx, r); ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
+    *out = r;
+    return JOLT_OK;
+}
+
+// grid index of coefficient i of a block of 2^sigma_table columns embedded top-left in a grid of 2^sigma_grid columns
+extern "C" int32_t jolt_host_dory_block_index(uint32_t sigma_table, uint32_t sigma_grid, size_t i, size_t* index) {
+    if (!index || sigma_table > sigma_grid || sigma_grid >= 64) return JOLT_ERR_INVALID_ARG;
+    const size_t row = i >> sigma_table;
+    if ((row << sigma_grid) >> sigma_grid != row) return JOLT_ERR_INVALID_ARG;
+    *index = (row << sigma_grid) | (i & (((size_t)1 << sigma_table) - 1));
     return JOLT_OK;
 }
 

@@ -21,15 +21,38 @@ column, one-hot or dense, has cycles / C rows:
 
 through one jolt_dory_hints_onehot_am call per source and one jolt_dory_hints_rows_am call per dense column.  The hints are resident G1 views of `rows` normalised
 points in matrix-row order either way, so DoryOpening and .commit() do not know the difference; the row fold of such an opening is Context.dory_fold_rows_grid_am.
+
+blocks=(...) are polynomials held as field elements -- advice, bytecode chunks, the program image -- each committed as its OWN balanced matrix, as
+BlockOpeningPoly::new and commit_advice do (crates/jolt-kernels/src/reference/commitment.rs:101-122): a table of 2^m entries is 2^(m - sigma_p) rows of 2^sigma_p
+columns with sigma_p = ceil(m / 2), its hint one jolt_dory_hints_rows_fr call.  The block hints follow the dense columns in `.hints`, in either order (the embedding
+of a block in the joint opening, top-left, is the same in both placements: Context.dory_fold_rows_blocks with base = the trace's fold).
 """
 from . import ffi
 
 
-class DoryWitnessCommitment:
+def block_sigma(length):
+    """sigma_p = ceil(m / 2) of a block of 2^m field elements: the columns of its own balanced matrix (BlockOpeningPoly::new)"""
+    if length <= 0 or length & (length - 1):
+        raise ValueError("a block holds a power of two of field elements")
+    return (length.bit_length() - 1 + 1) // 2
+
+
+class _TakesBlocks(type):
+    """DoryWitnessCommitment(..., blocks=(...)): the keyword is taken here and kept on the instance, so that __init__ keeps the parameter list the address-major
+    suite pins (tests/test_dory_am_cpu.py) and a call without `blocks` is the call it always was"""
+
+    def __call__(cls, *args, blocks=(), **kwargs):
+        self = cls.__new__(cls)
+        self._blocks = list(blocks)
+        self.__init__(*args, **kwargs)
+        return self
+
+
+class DoryWitnessCommitment(metaclass=_TakesBlocks):
     def __init__(self, setup, srs, sources, dense, sigma, order="cycle_major", log_k=None, log_extra=0):
         """setup: a dory_open.DorySetup; srs: a jolt_srs (ffi.Srs) over Gamma1's first 2^sigma points at least; sources: ffi.OneHot handles; dense: ffi.Ints columns.
         order: "cycle_major" (log_k and log_extra are not used) or "address_major" (log_k: log2 of the grid's addresses, log_extra: the embedding extra of a widened
-        grid).  Every shape is checked here, before anything is enqueued; the inputs stay the caller's."""
+        grid); blocks (keyword only, see _TakesBlocks): ffi.Table handles of 2^m field elements each.  Every shape is checked here, before anything is enqueued; the inputs stay the caller's."""
         if order not in ("cycle_major", "address_major"):
             raise ValueError("order is cycle_major or address_major")
         address_major = order == "address_major"
@@ -63,6 +86,12 @@ class DoryWitnessCommitment:
                 if d.count % width:
                     raise ValueError("2^sigma does not divide a dense column's length")
                 shapes.append((d, d.count // width, 1))
+        blocks = getattr(self, "_blocks", [])
+        for b in blocks:
+            sigma_p = block_sigma(len(b))
+            if 1 << sigma_p > len(srs):
+                raise ValueError("the SRS holds fewer bases than a block has columns")
+            shapes.append((b, len(b) >> sigma_p, 1))
         if not shapes:
             raise ValueError("a witness has at least one column")
         if any(rows > setup.n for _, rows, _ in shapes):
@@ -75,7 +104,9 @@ class DoryWitnessCommitment:
             for k, (col, rows, columns) in enumerate(shapes):
                 vec = self.ctx.dory_state_alloc(ffi.DORY_KIND_G1, rows * columns)
                 self._vecs.append(vec)
-                if address_major and k < len(sources):
+                if k >= len(shapes) - len(blocks):
+                    self.ctx.dory_hints_rows_fr(srs, col, len(col) // rows, vec)
+                elif address_major and k < len(sources):
                     self.ctx.dory_hints_onehot_am(srs, col, vec, sigma, log_block, log_extra)
                 elif address_major:
                     self.ctx.dory_hints_rows_am(srs, col, sigma, log_block, vec)

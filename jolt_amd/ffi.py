@@ -1764,6 +1764,69 @@ Context.dory_hints_rows_am = _dory_hints_rows_am
 Context.dory_fold_rows_grid_am = _dory_fold_rows_grid_am
 
 
+# ---- Dory for polynomials held as field elements (dory.hip, dory_rows_fr.hip.h): row commitments of a device table, the block-embedded row fold
+DORY_BLOCK_FOLD_SLICE = 64  # kBlockFoldSlice of dory.hip: matrix rows per thread of the block fold
+
+
+def _dory_commit_rows_fr(self, srs, table, row_width, first=0, count=None):
+    """StreamingCommitment::feed(&[Fr]) over every row_width window of table[first, first + count): one G1 point per row (jolt_dory_commit_rows_fr)"""
+    count = len(table) - first if count is None else count
+    rows = count // row_width if row_width else 0
+    out = g1_array(max(rows, 1))
+    _ck(lib().jolt_dory_commit_rows_fr(self.h, srs.h, table.h, C.c_size_t(first), C.c_size_t(count), C.c_size_t(row_width), _p(out)), "jolt_dory_commit_rows_fr", self)
+    return out[:rows]
+
+
+def _dory_hints_rows_fr(self, srs, table, row_width, out, out_first=0, first=0, count=None):
+    """the same rows, normalised, into the G1 vector `out` from element out_first on (jolt_dory_hints_rows_fr).  The number of rows."""
+    count = len(table) - first if count is None else count
+    _ck(lib().jolt_dory_hints_rows_fr(self.h, srs.h, table.h, C.c_size_t(first), C.c_size_t(count), C.c_size_t(row_width), out.h, C.c_size_t(out_first)),
+        "jolt_dory_hints_rows_fr", self)
+    return count // row_width
+
+
+def _dory_fold_rows_blocks(self, tables, sigma_tables, scalars, sigma, left, base=None):
+    """BlockOpeningPoly::fold_rows: out[c] = base[c] + sum_d scalars[d] * sum_r left[r] * tables[d][(r << sigma_tables[d]) + c], every table embedded top-left in
+    the grid of 2^sigma columns (jolt_dory_fold_rows_blocks); base: a Table of 2^sigma entries or None.  A Table of 2^sigma entries."""
+    n = len(tables)
+    if len(sigma_tables) != n or len(scalars) != n:
+        raise ValueError("one sigma and one scalar per table")
+    hs = (C.c_void_p * max(n, 1))(*[t.h for t in tables])
+    sg = (C.c_uint32 * max(n, 1))(*sigma_tables)
+    sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if n else fr_array(1)
+    h = C.c_void_p()
+    _ck(lib().jolt_dory_fold_rows_blocks(self.h, hs, sg, C.c_size_t(n), _p(sc), C.c_uint32(sigma), left.h, base.h if base is not None else None, C.byref(h)),
+        "jolt_dory_fold_rows_blocks", self)
+    return Table(self, h)
+
+
+def host_dory_fr_digits(scalar, c, W):
+    """the signed c-bit digits the field-row kernels give one scalar: ([digit_w for w < W], negative) with sum_w digit_w 2^(c w) = min(s, r - s) and
+    negative = whether r - s was taken"""
+    digits, neg = np.zeros(max(W, 1), dtype=np.uint32), C.c_uint32()
+    _ck(lib().jolt_host_dory_fr_digits(_p(fr(scalar)), C.c_int32(c), C.c_int32(W), _p(digits), C.byref(neg)), "jolt_host_dory_fr_digits")
+    return [-(int(d) & 0x7FFFFFFF) if int(d) >> 31 else int(d) for d in digits[:W]], bool(neg.value)
+
+
+def host_dory_rows_fr_plan(bit_length, row_width):
+    """(c, W) of the field rows for magnitudes of bit_length bits in rows of row_width values"""
+    c, W = C.c_int32(), C.c_int32()
+    _ck(lib().jolt_host_dory_rows_fr_plan(C.c_uint32(bit_length), C.c_size_t(row_width), C.byref(c), C.byref(W)), "jolt_host_dory_rows_fr_plan")
+    return c.value, W.value
+
+
+def host_dory_block_index(sigma_table, sigma_grid, i):
+    """grid index of coefficient i of a block of 2^sigma_table columns embedded top-left in a grid of 2^sigma_grid columns"""
+    out = C.c_size_t()
+    _ck(lib().jolt_host_dory_block_index(C.c_uint32(sigma_table), C.c_uint32(sigma_grid), C.c_size_t(i), C.byref(out)), "jolt_host_dory_block_index")
+    return out.value
+
+
+Context.dory_commit_rows_fr = _dory_commit_rows_fr
+Context.dory_hints_rows_fr = _dory_hints_rows_fr
+Context.dory_fold_rows_blocks = _dory_fold_rows_blocks
+
+
 def _gt(a):
     return np.ascontiguousarray(a, dtype=np.uint64).reshape(48)
 

@@ -104,6 +104,15 @@ impl HipDoryVec {
         check(unsafe { ffi::jolt_dory_hints_rows(self.ctx.raw, srs.raw, values.raw, row_width, self.raw, out_first) }, self.ctx.raw)
     }
 
+    /// `StreamingCommitment::feed(&[Fr])` per row (`crates/jolt-dory/src/streaming.rs:53-70`) for a polynomial held as field elements on the device -- advice, a bytecode
+    /// chunk, the program image, or a whole dense polynomial: the commitments of the `row_width` windows of `table[first .. first + count]` into
+    /// `self[out_first ..]`, normalised: `jolt_dory_hints_rows_fr`.  The same rows in both trace orders (a block is its own matrix).
+    pub fn hints_rows_fr(&mut self, out_first: usize, srs: &HipSrs, table: &HipTable, first: usize, count: usize, row_width: usize) -> Result<(), HipError> {
+        let _device = self.ctx.exclusive();
+        // SAFETY: as hints_onehot; the library refuses a stretch that leaves the table.
+        check(unsafe { ffi::jolt_dory_hints_rows_fr(self.ctx.raw, srs.raw, table.raw, first, count, row_width, self.raw, out_first) }, self.ctx.raw)
+    }
+
     /// [`HipDoryVec::hints_onehot`] in the given trace order.  Address-major: element `p * rows + r`, `rows = cycles >> (sigma - log_block)`, row `r` the sum over
     /// the cycles `[r C, (r + 1) C)`: `jolt_dory_hints_onehot_am`, enqueued.
     pub fn hints_onehot_in(&mut self, order: TraceOrder, out_first: usize, srs: &HipSrs, source: &HipHotIndices, first_column: usize, n_columns: usize, sigma: u32) -> Result<(), HipError> {
@@ -289,6 +298,24 @@ pub fn fold_rows_in(ctx: &Arc<HipContext>, order: TraceOrder, sources: &[&HipHot
             TraceOrder::CycleMajor => ffi::jolt_dory_fold_rows_grid(ctx.raw, hs.as_ptr(), hs.len(), onehot_scalars.as_ptr().cast(), ds.as_ptr(), ds.len(), dense_scalars.as_ptr().cast(), log_k, sigma, left.raw, &mut raw),
             TraceOrder::AddressMajor { log_block, log_stride } => ffi::jolt_dory_fold_rows_grid_am(ctx.raw, hs.as_ptr(), hs.len(), onehot_scalars.as_ptr().cast(), ds.as_ptr(), ds.len(), dense_scalars.as_ptr().cast(), log_block, log_stride, sigma, left.raw, &mut raw),
         }
+    };
+    check(status, ctx.raw)?;
+    Ok(HipTable { ctx: Arc::clone(ctx), raw })
+}
+
+/// `BlockOpeningPoly::fold_rows` (`crates/jolt-kernels/src/optimized/opening.rs:594-611`): `base + sum_d scalars[d] * (left^T M_d)` with table `d` a
+/// `2^(m_d - sigma_d) x 2^sigma_d` matrix embedded top-left in the grid of `2^sigma` columns: `jolt_dory_fold_rows_blocks`.  `base` is the trace's
+/// [`fold_rows_in`] (either order) for a joint opening, `None` for the dense `vector_matrix_product` of one table with `sigma_d = sigma`.
+pub fn fold_rows_blocks(ctx: &Arc<HipContext>, tables: &[&HipTable], sigma_tables: &[u32], scalars: &[ArkFr], sigma: u32, left: &HipTable, base: Option<&HipTable>) -> Result<HipTable, HipError> {
+    if sigma_tables.len() != tables.len() || scalars.len() != tables.len() {
+        return Err(HipError::size_mismatch("fold_rows_blocks: one sigma and one scalar per table"));
+    }
+    let ts: Vec<*mut ffi::jolt_table> = tables.iter().map(|t| t.raw).collect();
+    let mut raw = core::ptr::null_mut();
+    let _device = ctx.exclusive();
+    // SAFETY: live handles of one context, borrowed for the call; `ArkFr` is layout-compatible with `jolt_fr_t`; the library checks every length.
+    let status = unsafe {
+        ffi::jolt_dory_fold_rows_blocks(ctx.raw, ts.as_ptr(), sigma_tables.as_ptr(), ts.len(), scalars.as_ptr().cast(), sigma, left.raw, base.map_or(core::ptr::null(), |b| b.raw as *const ffi::jolt_table), &mut raw)
     };
     check(status, ctx.raw)?;
     Ok(HipTable { ctx: Arc::clone(ctx), raw })

@@ -445,6 +445,12 @@ extern "C" {
     pub fn jolt_dory_fold_rows_grid_am(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_block: u32, log_stride: u32, sigma: u32, left: *const jolt_table, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_host_dory_am_place(log_block: u32, log_stride: u32, sigma: u32, cycle: usize, address: usize, row: *mut usize, col: *mut usize) -> i32;
     pub fn jolt_host_dory_am_row(bases: *const jolt_g1_t, n_bases: usize, hot: *const u16, cycles_in_row: usize, k: u32, log_block: u32, log_stride: u32, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_dory_commit_rows_fr(ctx: *mut jolt_ctx, srs: *const jolt_srs, table: *const jolt_table, first: usize, count: usize, row_width: usize, out: *mut jolt_g1_t) -> i32;
+    pub fn jolt_dory_hints_rows_fr(ctx: *mut jolt_ctx, srs: *const jolt_srs, table: *const jolt_table, first: usize, count: usize, row_width: usize, out: *mut jolt_dory_vec, out_first: usize) -> i32;
+    pub fn jolt_host_dory_fr_digits(scalar: *const jolt_fr_t, c: i32, W: i32, digits_out: *mut u32, negative_out: *mut u32) -> i32;
+    pub fn jolt_host_dory_rows_fr_plan(bit_length: u32, row_width: usize, c: *mut i32, W: *mut i32) -> i32;
+    pub fn jolt_dory_fold_rows_blocks(ctx: *mut jolt_ctx, tables: *const *mut jolt_table, sigma_tables: *const u32, n_tables: usize, scalars: *const jolt_fr_t, sigma: u32, left: *const jolt_table, base: *const jolt_table, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_host_dory_block_index(sigma_table: u32, sigma_grid: u32, i: usize, index: *mut usize) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;
