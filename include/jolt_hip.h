@@ -4,7 +4,8 @@
  * This is the drop-in boundary: the entry points below are what a thin Rust FFI crate (`jolt-kernels-hip`,
  * sketched in INTEGRATION.md) binds in order to implement the reference's own trait surface for this path --
  * `ProveRounds`/`SumcheckKernel`/`PrepareKernel` (jolt-sumcheck, jolt-kernels), `JoltGroup::msm` (jolt-crypto) and
- * `CommitmentScheme::{commit,open}` for HyperKZG (jolt-openings / jolt-hyperkzg).  Every function cites the
+ * `CommitmentScheme::{commit,open}` for HyperKZG (jolt-openings / jolt-hyperkzg) and, for Dory (jolt-dory), the commitment
+ * and the prover's side of an evaluation proof as one call each under the caller's transcript.  Every function cites the
  * reference interface it replaces (paths relative to the a16z/jolt checkout).
  *
  * Conventions:
@@ -847,6 +848,75 @@ int32_t jolt_dory_fold_rows_blocks(jolt_ctx *ctx, jolt_table *const *tables, con
                                    uint32_t sigma, const jolt_table *left, const jolt_table *base /* may be NULL */, jolt_table **out /* 2^sigma */);
 /* *index = ((i >> sigma_table) << sigma_grid) | (i & (2^sigma_table - 1)); sigma_table > sigma_grid or an index past 64 bits is JOLT_ERR_INVALID_ARG */
 int32_t jolt_host_dory_block_index(uint32_t sigma_table, uint32_t sigma_grid, size_t i, size_t *index);
+
+/* Dory evaluation proofs as one call (dory_scheme.hip): the setup object, a round's in-place update as one call, the prover's side of Eval-VMV-RE under Fiat-Shamir,
+ * and the byte forms a transcript absorbs.  The protocol is the one jolt_amd/dory_open.py and dory_reduce.py drive message by message (Dory paper, transparent mode;
+ * alpha folds v1 and s1, 1/alpha folds v2 and s2); those drivers stay, as the second implementation the tests compare against.  Contract of the resident entries above:
+ * a null handle, a vector, table or setup of another context or of the wrong kind, or a view outside its vector is JOLT_ERR_INVALID_ARG, and a refused call enqueues
+ * nothing and writes nothing. */
+/* Gamma1 (G1) and Gamma2 (G2) of n points each as resident vectors, Gamma2's prepared line table, H1 and H2: the C counterpart of dory_open.py's DorySetup.  The host
+ * arrays pass the checks of jolt_dory_vec_upload once, here.  n = 0 or not a power of two is JOLT_ERR_INVALID_ARG. */
+typedef struct jolt_dory_setup jolt_dory_setup;
+int32_t jolt_dory_setup_create(jolt_ctx *ctx, const jolt_g1_t *gamma1, const jolt_g2_t *gamma2, size_t n, const jolt_g1_t *h1, const jolt_g2_t *h2, jolt_dory_setup **out);
+int32_t jolt_dory_setup_free(jolt_ctx *ctx, jolt_dory_setup *setup);
+int32_t jolt_dory_setup_size(const jolt_dory_setup *setup, size_t *n);
+/* outs[k] = prod_{i < hint_rows[k]} e(hints[k][hint_first[k] + i], Gamma2[i]): the tier-2 commitments of n resident G1 views as ONE jolt_dory_products batch of PAIR
+ * items against the prepared table (an empty view gives one).  A view longer than the setup is JOLT_ERR_INVALID_ARG. */
+int32_t jolt_dory_setup_tier2(jolt_ctx *ctx, const jolt_dory_setup *setup, const jolt_dory_vec *const *hints, const size_t *hint_first, const size_t *hint_rows, size_t n,
+                              jolt_gt_t *outs);
+/* One of the two in-place updates of a Dory-Reduce round as one call.  The G1 work runs on the context's main stream and the G2 work beside it on a side stream,
+ * forked and joined by events as jolt_dory_products forks its chains: two launches (k_dory_scale_add per group), in alpha mode followed on each stream by that group's
+ * field fold.  Enqueued only, no host synchronisation.  The per-lane functions are the ones of jolt_dory_vec_scale_bases_add / _scale_vs_add / _fold_field, so the
+ * vectors hold bit for bit what those separate calls write.
+ *   JOLT_DORY_UPDATE_BETA   a = Gamma1 (G1), b = Gamma2 (G2):  v1[v1_first + i] += scalar * a[a_first + i],  v2[v2_first + i] += scalar_inv * b[b_first + i],  i < n
+ *   JOLT_DORY_UPDATE_ALPHA  a = s1, b = s2 (Fr), n even, h = n / 2:  x[x_first + i] = c * x[x_first + i] + x[x_first + h + i] for i < h, with c = scalar for v1 and
+ *                           s1 and c = scalar_inv for v2 and s2; then each of the four vectors is truncated to its x_first + h elements
+ * Beyond the common contract, JOLT_ERR_INVALID_ARG for: an unknown mode, an odd n in alpha mode, overlapping views of one vector in beta mode, a scalar that is not
+ * canonical, scalar * scalar_inv != 1. */
+enum { JOLT_DORY_UPDATE_BETA = 0, JOLT_DORY_UPDATE_ALPHA = 1 };
+int32_t jolt_dory_round_update(jolt_ctx *ctx, int32_t mode, jolt_dory_vec *v1, size_t v1_first, jolt_dory_vec *v2, size_t v2_first, jolt_dory_vec *a, size_t a_first,
+                               jolt_dory_vec *b, size_t b_first, size_t n, const jolt_fr_t *scalar, const jolt_fr_t *scalar_inv);
+/* The prover's side of one evaluation proof.  Inputs as dory_open.py's DoryOpening: n_hints >= 1 resident G1 views of at most 2^nu row commitments each with one scalar
+ * per hint, the device tables v = L^T M (2^sigma entries), L (2^nu) and R (2^sigma); nu <= sigma <= 30.  Everything is checked before anything is enqueued:
+ * JOLT_ERR_INVALID_ARG for the common contract, nu > sigma, a hint longer than 2^nu, a table of another length, a scalar that is not canonical;
+ * JOLT_ERR_SRS_TOO_SMALL for 2^sigma above the setup's size.  The state is built by jolt_dory_state_*, each message is one jolt_dory_products batch, the updates are
+ * jolt_dory_round_update.  After each message `fn` is called with the message's elements and returns the challenge that follows it:
+ *   JOLT_DORY_PHASE_VMV     round 0          gts C, D2; g1s E1                                        no challenge
+ *   JOLT_DORY_PHASE_FIRST   round k < sigma  gts D1L, D1R, D2L, D2R; g1s E1beta; g2s E2beta           beta_k
+ *   JOLT_DORY_PHASE_SECOND  round k          gts C+, C-; g1s E1+, E1-; g2s E2+, E2-                   alpha_k
+ *   JOLT_DORY_PHASE_GAMMA   round sigma      no elements                                              gamma
+ *   JOLT_DORY_PHASE_FINAL   round sigma      g1s w1; g2s w2                                           no challenge
+ * A transcript absorbs a phase's elements in that order (gts, then g1s, then g2s).  challenge_out is never NULL; what VMV and FINAL write there is ignored.  A non-zero
+ * return aborts the opening with that status (as jolt_open_transcript_fn).  The library inverts the challenges: zero is JOLT_ERR_NOT_INVERTIBLE, a value that is not
+ * canonical JOLT_ERR_INVALID_ARG.  Outputs in protocol order, sized by jolt_host_dory_proof_counts: gts 2 + 6 sigma, g1s 2 + 3 sigma, g2s 1 + 3 sigma,
+ * challenges_out (beta_k, alpha_k) per round and then gamma.  GT values are the canonical values of jolt_dory_products, points as its MSM results and the in-place
+ * routines leave them (the identity as (1, 1, 0)).  On every exit, an abort included, the streams are drained before the state vectors go back to the pool, and
+ * the context stays usable; the inputs stay the caller's. */
+enum { JOLT_DORY_PHASE_VMV = 0, JOLT_DORY_PHASE_FIRST = 1, JOLT_DORY_PHASE_SECOND = 2, JOLT_DORY_PHASE_GAMMA = 3, JOLT_DORY_PHASE_FINAL = 4 };
+typedef int32_t (*jolt_dory_transcript_fn)(void *user, int32_t phase, size_t round, const jolt_gt_t *gts, size_t n_gt, const jolt_g1_t *g1s, size_t n_g1,
+                                           const jolt_g2_t *g2s, size_t n_g2, jolt_fr_t *challenge_out);
+int32_t jolt_host_dory_open_with_transcript(jolt_ctx *ctx, const jolt_dory_setup *setup, const jolt_dory_vec *const *hints, const size_t *hint_first,
+                                            const size_t *hint_rows, size_t n_hints, const jolt_fr_t *scalars, const jolt_table *v_table, const jolt_table *left,
+                                            const jolt_table *right, uint32_t nu, uint32_t sigma, jolt_dory_transcript_fn fn, void *user, jolt_gt_t *gts,
+                                            jolt_g1_t *g1s, jolt_g2_t *g2s, jolt_fr_t *challenges_out);
+/* The same under one of the library's engines: every element goes in as the reference's adapter absorbs a group element (JoltToDoryTranscript::append_group,
+ * crates/jolt-dory/src/transcript.rs:46-53) -- jolt_host_dory_transcript_append_* below -- and every challenge is Transcript::challenge_scalar (full width).  The
+ * order of the appends is this header's phase order; dory-pcs's own order is pinned by nothing in the reference checkout (docs/parity.md). */
+int32_t jolt_host_dory_open(jolt_ctx *ctx, const jolt_dory_setup *setup, const jolt_dory_vec *const *hints, const size_t *hint_first, const size_t *hint_rows,
+                            size_t n_hints, const jolt_fr_t *scalars, const jolt_table *v_table, const jolt_table *left, const jolt_table *right, uint32_t nu,
+                            uint32_t sigma, jolt_host_transcript *t, jolt_gt_t *gts, jolt_g1_t *g1s, jolt_g2_t *g2s, jolt_fr_t *challenges_out);
+/* sigma > 30 is JOLT_ERR_INVALID_ARG; any of the four pointers may be NULL */
+int32_t jolt_host_dory_proof_counts(uint32_t sigma, size_t *n_gt, size_t *n_g1, size_t *n_g2, size_t *n_challenges);
+/* ark-serialize's compressed forms on the host.  G2: x.c0 then x.c1, 32 little-endian bytes of the canonical value each; the top two bits of the last byte hold the
+ * flags: 0x80 when y > -y (c1 compared first, then c0), 0x40 for the identity (x zero).  GT: the twelve canonical Fq coefficients in jolt_gt_t order, 32
+ * little-endian bytes each, no flags.  The elements are not checked beyond canonical coordinates (JOLT_ERR_INVALID_ARG).  The G1 form
+ * (jolt_host_g1_serialize_compressed) is pinned through the oracle; these two rest on ark-serialize's definition alone (docs/parity.md). */
+int32_t jolt_host_g2_serialize_compressed(const jolt_g2_t *p, uint8_t out[64]);
+int32_t jolt_host_gt_serialize(const jolt_gt_t *f, uint8_t out[384]);
+/* LabelWithCount(b"dory_group", len) and then the bytes above (len = 384, 32, 64) */
+int32_t jolt_host_dory_transcript_append_gt(jolt_host_transcript *t, const jolt_gt_t *element);
+int32_t jolt_host_dory_transcript_append_g1(jolt_host_transcript *t, const jolt_g1_t *element);
+int32_t jolt_host_dory_transcript_append_g2(jolt_host_transcript *t, const jolt_g2_t *element);
 
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)

@@ -8,8 +8,26 @@
 
 #include "ctx.hpp"
 
+// the object behind jolt_dory_vec (dory_resident.hip makes and frees them; dory_scheme.hip reads them too)
+struct jolt_dory_vec {
+    jolt_ctx* ctx = nullptr;
+    int32_t kind = 0;
+    size_t len = 0;
+    void* data = nullptr;  // device, from the context's pool
+};
+
 namespace jolt {
 namespace dory_host {
+
+// (vec, first, n) lies inside a vector of this context and kind.  Never first + n: that sum can wrap.
+inline bool view_ok(const jolt_ctx* ctx, const jolt_dory_vec* v, int32_t kind, size_t first, size_t n) {
+    return v && v->ctx == ctx && v->kind == kind && !(first > v->len || n > v->len - first);
+}
+// two valid views of n elements share an element
+inline bool views_overlap(const jolt_dory_vec* a, size_t a_first, const jolt_dory_vec* b, size_t b_first, size_t n) {
+    if (a != b || n == 0) return false;
+    return a_first < b_first ? b_first - a_first < n : a_first - b_first < n;
+}
 
 // one wavefront per workgroup, one element per lane: the launch shape of every latency-bound Dory kernel (docs/kernels.md 3.5f)
 constexpr int kLanes = 64;

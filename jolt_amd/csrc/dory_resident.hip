@@ -36,26 +36,10 @@ using namespace jolt::dory_plan;
 static_assert(kPlanLanes == (size_t)kLanes, "the plan pads to the kernels' wavefront");
 static_assert(sizeof(jolt_dory_result) >= sizeof(Fq12) && sizeof(jolt_gt_t) == sizeof(Fq12), "result block");
 
-struct jolt_dory_vec {
-    jolt_ctx* ctx = nullptr;
-    int32_t kind = 0;
-    size_t len = 0;
-    void* data = nullptr;  // device, from the context's pool
-};
-
 namespace {
 
 size_t kind_size(int32_t kind) { return kind == JOLT_DORY_KIND_G1 ? sizeof(G1Jac) : kind == JOLT_DORY_KIND_G2 ? sizeof(G2Jac) : sizeof(Fr); }
 
-// (vec, first, n) lies inside a vector of this context and kind.  Never first + n: that sum can wrap.
-bool view_ok(const jolt_ctx* ctx, const jolt_dory_vec* v, int32_t kind, size_t first, size_t n) {
-    return v && v->ctx == ctx && v->kind == kind && !(first > v->len || n > v->len - first);
-}
-// two valid views of n elements share an element
-bool views_overlap(const jolt_dory_vec* a, size_t a_first, const jolt_dory_vec* b, size_t b_first, size_t n) {
-    if (a != b || n == 0) return false;
-    return a_first < b_first ? b_first - a_first < n : a_first - b_first < n;
-}
 // two valid views of different lengths share an element
 bool ranges_overlap(const jolt_dory_vec* a, size_t a_first, size_t a_n, const jolt_dory_vec* b, size_t b_first, size_t b_n) {
     if (a != b || a_n == 0 || b_n == 0) return false;

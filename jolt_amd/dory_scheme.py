@@ -96,3 +96,30 @@ class DorySchemeOpening:
 
 def open(setup, table, hint, point):  # noqa: A001 -- the reference's name
     return DorySchemeOpening(setup, table, hint, point)
+
+
+def prove(setup, table, hint, point, transcript):
+    """The same opening as ONE call of the library under a transcript (dory_proof.prove): setup is a dory_proof.DoryProofSetup over the bases commit() was given,
+    transcript a HostTranscript.  (proof, y): the DoryProof and the evaluation y = L^T M R (one Fr)."""
+    from . import dory_proof
+    nu, sigma = _check(setup, table)
+    point = ffi.fr(np.ascontiguousarray(point, dtype=np.uint64)).reshape(-1, 4)
+    if point.shape[0] != nu + sigma:
+        raise ValueError("the point has one coordinate per variable")
+    view = ffi._dory_view(hint)
+    if view[0].kind != ffi.DORY_KIND_G1 or view[2] != 1 << nu:
+        raise ValueError("the hint is a G1 vector of 2^nu row commitments")
+    ctx = setup.ctx
+    one = ffi.host_fr_from_u64(1)
+    tables = []
+    try:
+        tables.append(ctx.eq_evals(point[:nu]) if nu else ctx.upload(one.reshape(1, 4)))
+        tables.append(ctx.eq_evals(point[nu:]) if sigma else ctx.upload(one.reshape(1, 4)))
+        left, right = tables
+        tables.append(ctx.dory_fold_rows_blocks([table], [sigma], [one], sigma, left))
+        v = tables[2]
+        proof = dory_proof.prove(setup, [view], [one], v, left, right, nu, sigma, transcript=transcript)
+        return proof, ctx.table_dot(v, right)
+    finally:
+        for t in tables:
+            t.free()

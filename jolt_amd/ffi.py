@@ -1677,6 +1677,143 @@ Context.dory_state_combine_hints = _dory_state_combine_hints
 Context.dory_state_fixed_base_mul = _dory_state_fixed_base_mul
 
 
+# ---- Dory evaluation proofs as one call (dory_scheme.hip): the setup object, a round's update as one call, the opening under Fiat-Shamir, the byte forms
+DORY_UPDATE_BETA, DORY_UPDATE_ALPHA = range(2)
+DORY_PHASE_VMV, DORY_PHASE_FIRST, DORY_PHASE_SECOND, DORY_PHASE_GAMMA, DORY_PHASE_FINAL = range(5)
+DORY_TRANSCRIPT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p)
+
+
+def _dory_view_arrays(views):
+    n = len(views)
+    hs = (C.c_void_p * max(n, 1))(*[v.h for v, _, _ in views])
+    firsts = (C.c_size_t * max(n, 1))(*[f for _, f, _ in views])
+    rows = (C.c_size_t * max(n, 1))(*[r for _, _, r in views])
+    return hs, firsts, rows
+
+
+class DoryLibSetup:
+    """jolt_dory_setup: Gamma1, Gamma2 (resident, checked once), Gamma2's prepared table, H1 and H2 behind one handle of the library"""
+
+    def __init__(self, ctx, gamma1, gamma2, h1, h2):
+        g1 = np.ascontiguousarray(gamma1, dtype=np.uint64).reshape(-1, 12)
+        g2 = np.ascontiguousarray(gamma2, dtype=np.uint64).reshape(-1, 24)
+        if g1.shape[0] != g2.shape[0]:
+            raise ValueError("Gamma1 and Gamma2 have one length, a power of two")
+        self.ctx, self.h = ctx, C.c_void_p()
+        self.h1 = np.ascontiguousarray(h1, dtype=np.uint64).reshape(12).copy()
+        self.h2 = np.ascontiguousarray(h2, dtype=np.uint64).reshape(24).copy()
+        _ck(lib().jolt_dory_setup_create(ctx.h, _p(g1), _p(g2), C.c_size_t(g1.shape[0]), _p(self.h1), _p(self.h2), C.byref(self.h)), "jolt_dory_setup_create", ctx)
+        n = C.c_size_t()
+        _ck(lib().jolt_dory_setup_size(self.h, C.byref(n)), "jolt_dory_setup_size", ctx)
+        self.n = n.value
+
+    def tier2(self, hints):
+        """the tier-2 commitments of resident G1 views (DoryVec or (DoryVec, first, rows)): one product batch (jolt_dory_setup_tier2); one (48,) GT each"""
+        views = [_dory_view(h) for h in hints]
+        hs, firsts, rows = _dory_view_arrays(views)
+        outs = np.zeros((max(len(views), 1), 48), dtype=np.uint64)
+        _ck(lib().jolt_dory_setup_tier2(self.ctx.h, self.h, hs, firsts, rows, C.c_size_t(len(views)), _p(outs)), "jolt_dory_setup_tier2", self.ctx)
+        return [outs[k].copy() for k in range(len(views))]
+
+    def close(self):
+        if self.h:
+            _ck(lib().jolt_dory_setup_free(self.ctx.h, self.h), "jolt_dory_setup_free", self.ctx)
+            self.h = None
+
+    free = close
+
+
+def _dory_round_update(self, mode, v1, v2, a, b, scalar, scalar_inv):
+    """jolt_dory_round_update: one of a round's two in-place updates as one call, the G1 work beside the G2 work; enqueued, not awaited.  Views of one length n:
+    DORY_UPDATE_BETA   v1 += scalar * a, v2 += scalar_inv * b with a, b = views of Gamma1, Gamma2
+    DORY_UPDATE_ALPHA  v1, a = s1 folded under scalar, v2, b = s2 under scalar_inv; the four vectors are truncated to first + n / 2"""
+    views = [_dory_view(x) for x in (v1, v2, a, b)]
+    if len({n for _, _, n in views}) != 1:
+        raise ValueError("the four views of a round update have one length")
+    (v1v, v1f, n), (v2v, v2f, _), (av, af, _), (bv, bf, _) = views
+    _ck(lib().jolt_dory_round_update(self.h, C.c_int32(mode), v1v.h, C.c_size_t(v1f), v2v.h, C.c_size_t(v2f), av.h, C.c_size_t(af), bv.h, C.c_size_t(bf), C.c_size_t(n),
+                                     _p(fr(scalar)), _p(fr(scalar_inv))), "jolt_dory_round_update", self)
+
+
+def host_dory_proof_counts(sigma):
+    """(GT elements, G1 points, G2 points, challenges) of an opening of 2^sigma columns (jolt_host_dory_proof_counts)"""
+    c = [C.c_size_t() for _ in range(4)]
+    _ck(lib().jolt_host_dory_proof_counts(C.c_uint32(sigma), *[C.byref(x) for x in c]), "jolt_host_dory_proof_counts")
+    return tuple(x.value for x in c)
+
+
+def _dory_open(self, setup, hints, scalars, v_table, left, right, nu, sigma, transcript=None, callback=None):
+    """One evaluation proof in one call: jolt_host_dory_open under `transcript` (a HostTranscript), or jolt_host_dory_open_with_transcript under
+    callback(phase, round, gts (k, 48), g1s (k, 12), g2s (k, 24)) -> the (4,) challenge after that message (None for DORY_PHASE_VMV / _FINAL) or an int status that
+    aborts the opening.  dict(gts, g1s, g2s, challenges) in protocol order."""
+    if (transcript is None) == (callback is None):
+        raise ValueError("an opening runs under a transcript or under a callback")
+    views = [_dory_view(h) for h in hints]
+    hs, firsts, rows = _dory_view_arrays(views)
+    sc = fr(np.stack([fr(c).reshape(4) for c in scalars])) if len(scalars) else fr_array(1)
+    if sc.shape[0] != max(len(views), 1) or len(scalars) != len(views):
+        raise ValueError("one scalar per hint")
+    n_gt, n_g1, n_g2, n_ch = host_dory_proof_counts(sigma)
+    gts, g1s, g2s, ch = np.zeros((n_gt, 48), dtype=np.uint64), np.zeros((n_g1, 12), dtype=np.uint64), np.zeros((n_g2, 24), dtype=np.uint64), fr_array(n_ch)
+    head = (self.h, setup.h, hs, firsts, rows, C.c_size_t(len(views)), _p(sc), v_table.h, left.h, right.h, C.c_uint32(nu), C.c_uint32(sigma))
+    tail = (_p(gts), _p(g1s), _p(g2s), _p(ch))
+    if transcript is not None:
+        _ck(lib().jolt_host_dory_open(*head, transcript.h, *tail), "jolt_host_dory_open", self)
+    else:
+        err = []
+
+        def cb(user, phase, rnd, p_gt, k_gt, p_g1, k_g1, p_g2, k_g2, out):
+            try:
+                take = lambda p, k, w: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(k, w)).copy() if k else np.zeros((0, w), dtype=np.uint64)  # noqa: E731
+                c = callback(phase, rnd, take(p_gt, k_gt, 48), take(p_g1, k_g1, 12), take(p_g2, k_g2, 24))
+                if isinstance(c, (int, np.integer)) and not isinstance(c, bool):
+                    return int(c)
+                if c is not None:
+                    c = np.ascontiguousarray(c, dtype=np.uint64).reshape(4)
+                    C.memmove(out, c.ctypes.data, 32)
+                return 0
+            except Exception as e:  # never unwind through the C frame
+                err.append(e)
+                return 4
+
+        fn = DORY_TRANSCRIPT_FN(cb)
+        st = lib().jolt_host_dory_open_with_transcript(*head, fn, None, *tail)
+        if err:
+            raise err[0]
+        _ck(st, "jolt_host_dory_open_with_transcript", self)
+    return dict(gts=gts, g1s=g1s, g2s=g2s, challenges=ch)
+
+
+def host_g2_serialize_compressed(p):
+    out = (C.c_uint8 * 64)()
+    _ck(lib().jolt_host_g2_serialize_compressed(_p(np.ascontiguousarray(p, dtype=np.uint64)), out), "jolt_host_g2_serialize_compressed")
+    return bytes(out)
+
+
+def host_gt_serialize(f):
+    out = (C.c_uint8 * 384)()
+    _ck(lib().jolt_host_gt_serialize(_p(np.ascontiguousarray(f, dtype=np.uint64)), out), "jolt_host_gt_serialize")
+    return bytes(out)
+
+
+def host_dory_transcript_append(transcript, element):
+    """one group element as JoltToDoryTranscript::append_group absorbs it; the kind by the element's width: (48,) GT, (12,) G1, (24,) G2"""
+    e = np.ascontiguousarray(element, dtype=np.uint64).reshape(-1)
+    if e.size == 48:
+        _ck(lib().jolt_host_dory_transcript_append_gt(transcript.h, _p(e)), "jolt_host_dory_transcript_append_gt")
+    elif e.size == 12:
+        _ck(lib().jolt_host_dory_transcript_append_g1(transcript.h, _p(e)), "jolt_host_dory_transcript_append_g1")
+    elif e.size == 24:
+        _ck(lib().jolt_host_dory_transcript_append_g2(transcript.h, _p(e)), "jolt_host_dory_transcript_append_g2")
+    else:
+        raise ValueError("a GT element has 48 words, a G1 point 12, a G2 point 24")
+
+
+Context.dory_setup_create = lambda self, gamma1, gamma2, h1, h2: DoryLibSetup(self, gamma1, gamma2, h1, h2)
+Context.dory_round_update = _dory_round_update
+Context.dory_open = _dory_open
+
+
 # ---- the witness commitment in front of an opening (dory.hip, dory_hints.hip.h): row commitments written on the device, normalised, in hint order
 def _dory_hints_onehot(self, srs, source, out, chunk_width, first_poly=0, n_polys=None, out_first=0, batch_points=0):
     """the hints of columns [first_poly, first_poly + n_polys) of a OneHot into the G1 vector `out` from element out_first on (jolt_dory_hints_onehot):

@@ -48,9 +48,9 @@ pub enum TraceOrder {
 
 /// A G1, G2 or Fr array resident on the device.
 pub struct HipDoryVec {
-    ctx: Arc<HipContext>,
-    raw: *mut ffi::jolt_dory_vec,
-    kind: VecKind,
+    pub(crate) ctx: Arc<HipContext>,
+    pub(crate) raw: *mut ffi::jolt_dory_vec,
+    pub(crate) kind: VecKind,
 }
 
 impl HipDoryVec {

@@ -95,6 +95,10 @@ pub struct jolt_dory_vec {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct jolt_dory_setup {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct jolt_read_raf {
     _private: [u8; 0],
 }
@@ -172,6 +176,13 @@ pub const JOLT_DORY_KIND_FR: i32 = 2;
 pub const JOLT_DORY_PAIR: i32 = 0;
 pub const JOLT_DORY_MSM_G1: i32 = 1;
 pub const JOLT_DORY_MSM_G2: i32 = 2;
+pub const JOLT_DORY_UPDATE_BETA: i32 = 0;
+pub const JOLT_DORY_UPDATE_ALPHA: i32 = 1;
+pub const JOLT_DORY_PHASE_VMV: i32 = 0;
+pub const JOLT_DORY_PHASE_FIRST: i32 = 1;
+pub const JOLT_DORY_PHASE_SECOND: i32 = 2;
+pub const JOLT_DORY_PHASE_GAMMA: i32 = 3;
+pub const JOLT_DORY_PHASE_FINAL: i32 = 4;
 pub const JOLT_MAX_MEMBER_TABLES: usize = 40;
 pub const JOLT_MAX_MEMBER_TERMS: usize = 16;
 pub const JOLT_MAX_MEMBER_FACTORS: usize = 64;
@@ -225,6 +236,9 @@ pub type jolt_gather_fn = Option<unsafe extern "C" fn(user: *mut c_void, local: 
 pub type jolt_round_transcript_fn = Option<unsafe extern "C" fn(user: *mut c_void, compressed_coeffs: *const jolt_fr_t, n_coeffs: usize, challenge_out: *mut jolt_fr_t) -> i32>;
 pub type jolt_open_transcript_fn = Option<
     unsafe extern "C" fn(user: *mut c_void, phase: i32, points: *const jolt_g1_t, n_points: usize, values: *const jolt_fr_t, n_values: usize, challenge_out: *mut jolt_fr_t) -> i32,
+>;
+pub type jolt_dory_transcript_fn = Option<
+    unsafe extern "C" fn(user: *mut c_void, phase: i32, round: usize, gts: *const jolt_gt_t, n_gt: usize, g1s: *const jolt_g1_t, n_g1: usize, g2s: *const jolt_g2_t, n_g2: usize, challenge_out: *mut jolt_fr_t) -> i32,
 >;
 
 #[link(name = "jolt_hip")]
@@ -451,6 +465,19 @@ extern "C" {
     pub fn jolt_host_dory_rows_fr_plan(bit_length: u32, row_width: usize, c: *mut i32, W: *mut i32) -> i32;
     pub fn jolt_dory_fold_rows_blocks(ctx: *mut jolt_ctx, tables: *const *mut jolt_table, sigma_tables: *const u32, n_tables: usize, scalars: *const jolt_fr_t, sigma: u32, left: *const jolt_table, base: *const jolt_table, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_host_dory_block_index(sigma_table: u32, sigma_grid: u32, i: usize, index: *mut usize) -> i32;
+    pub fn jolt_dory_setup_create(ctx: *mut jolt_ctx, gamma1: *const jolt_g1_t, gamma2: *const jolt_g2_t, n: usize, h1: *const jolt_g1_t, h2: *const jolt_g2_t, out: *mut *mut jolt_dory_setup) -> i32;
+    pub fn jolt_dory_setup_free(ctx: *mut jolt_ctx, setup: *mut jolt_dory_setup) -> i32;
+    pub fn jolt_dory_setup_size(setup: *const jolt_dory_setup, n: *mut usize) -> i32;
+    pub fn jolt_dory_setup_tier2(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n: usize, outs: *mut jolt_gt_t) -> i32;
+    pub fn jolt_dory_round_update(ctx: *mut jolt_ctx, mode: i32, v1: *mut jolt_dory_vec, v1_first: usize, v2: *mut jolt_dory_vec, v2_first: usize, a: *mut jolt_dory_vec, a_first: usize, b: *mut jolt_dory_vec, b_first: usize, n: usize, scalar: *const jolt_fr_t, scalar_inv: *const jolt_fr_t) -> i32;
+    pub fn jolt_host_dory_open_with_transcript(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, v_table: *const jolt_table, left: *const jolt_table, right: *const jolt_table, nu: u32, sigma: u32, r#fn: jolt_dory_transcript_fn, user: *mut c_void, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_dory_open(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, v_table: *const jolt_table, left: *const jolt_table, right: *const jolt_table, nu: u32, sigma: u32, t: *mut jolt_host_transcript, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_dory_proof_counts(sigma: u32, n_gt: *mut usize, n_g1: *mut usize, n_g2: *mut usize, n_challenges: *mut usize) -> i32;
+    pub fn jolt_host_g2_serialize_compressed(p: *const jolt_g2_t, out: *mut u8) -> i32;
+    pub fn jolt_host_gt_serialize(f: *const jolt_gt_t, out: *mut u8) -> i32;
+    pub fn jolt_host_dory_transcript_append_gt(t: *mut jolt_host_transcript, element: *const jolt_gt_t) -> i32;
+    pub fn jolt_host_dory_transcript_append_g1(t: *mut jolt_host_transcript, element: *const jolt_g1_t) -> i32;
+    pub fn jolt_host_dory_transcript_append_g2(t: *mut jolt_host_transcript, element: *const jolt_g2_t) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;

@@ -20,6 +20,7 @@
 //! | `CommitmentScheme::OpeningHint`, `AdditivelyHomomorphic::combine_hints`, `JointOpeningPolynomials` (`crates/jolt-openings/src/schemes.rs:49-50,157-162`, `crates/jolt-kernels/src/opening.rs:42-54`) | [`opening`]: resident columns + commit-time class sums -> `jolt_host_hyperkzg_open_grid` |
 //! | dory's `DoryRoutines<ArkG1>` / `DoryRoutines<ArkG2>`, the group routines of `dory::prove`'s reduce-and-fold rounds (`crates/jolt-dory/src/routines.rs:58-147`) | [`dory_routines::HipG1Routines`], [`dory_routines::HipG2Routines`] over `jolt_dory_g1_*` / `jolt_dory_g2_*` / `jolt_dory_fold_field_vectors` |
 //! | the inner products and folds of one reduce-and-fold round of `dory::prove` on vectors that stay on the device (no trait: dory's `DoryRoutines` works on host slices) | [`dory_resident`]: [`dory_resident::HipDoryVec`], [`dory_resident::products`] over `jolt_dory_vec_*` / `jolt_dory_products` |
+//! | `DoryScheme::open`'s prover side as one call under the caller's `Transcript`: state, VMV message, the rounds, fold-scalars, final message (no trait: `dory::prove` owns that loop in the reference) | [`dory_proof`]: [`dory_proof::HipDorySetup`] and its `open_with` over `jolt_dory_setup_*` / `jolt_host_dory_open_with_transcript`, [`dory_proof::round_update`] over `jolt_dory_round_update` |
 //! | `UniskipKernel`, `CommitWitness`, the backend constructor (`crates/jolt-kernels/src/{uniskip.rs:28-54, commitment.rs:137-160, optimized/mod.rs:136-196}`) | [`backend::HipUniskip`], [`backend::HipCommitWitness`], [`backend::mi355x`] |
 //!
 //! Host code stays Rust: Fiat-Shamir, claim wiring, round-polynomial assembly (`UnivariatePoly::from_evals`,
@@ -29,6 +30,7 @@
 
 pub mod ffi;
 pub mod context;
+pub mod dory_proof;
 pub mod dory_resident;
 pub mod dory_routines;
 pub mod leaves;
@@ -46,6 +48,7 @@ pub mod status;
 pub mod streaming;
 
 pub use context::{HipContext, HipTable};
+pub use dory_proof::{round_update, HipDoryProof, HipDorySetup, RoundUpdate};
 pub use dory_resident::{products, DoryItem, DoryProduct, HipDoryVec, VecKind};
 pub use dory_routines::{HipG1Routines, HipG2Routines};
 pub use member::{HipMember, HipPrepare, HipSumcheckProver, MemberShape, MemberSlot};

@@ -23,7 +23,7 @@ def opaque_handles(path=None):
     return re.findall(r"typedef\s+struct\s+(jolt_\w+)\s+\1\s*;", open(path or HEADER).read())
 
 
-FNPTR = {"jolt_local_round_fn", "jolt_gather_fn", "jolt_round_transcript_fn", "jolt_open_transcript_fn"}
+FNPTR = {"jolt_local_round_fn", "jolt_gather_fn", "jolt_round_transcript_fn", "jolt_open_transcript_fn", "jolt_dory_transcript_fn"}
 
 
 def strip_comments(src):
@@ -135,6 +135,9 @@ def render(decls):
                "pub const JOLT_FQ12_FROBENIUS2: i32 = 5;\npub const JOLT_FQ12_FROBENIUS3: i32 = 6;\npub const JOLT_FQ12_MUL_SPARSE: i32 = 7;\npub const JOLT_PAIRING_LINES: usize = 88;")
     out.append("pub const JOLT_DORY_KIND_G1: i32 = 0;\npub const JOLT_DORY_KIND_G2: i32 = 1;\npub const JOLT_DORY_KIND_FR: i32 = 2;\n"
                "pub const JOLT_DORY_PAIR: i32 = 0;\npub const JOLT_DORY_MSM_G1: i32 = 1;\npub const JOLT_DORY_MSM_G2: i32 = 2;")
+    out.append("pub const JOLT_DORY_UPDATE_BETA: i32 = 0;\npub const JOLT_DORY_UPDATE_ALPHA: i32 = 1;\n"
+               "pub const JOLT_DORY_PHASE_VMV: i32 = 0;\npub const JOLT_DORY_PHASE_FIRST: i32 = 1;\npub const JOLT_DORY_PHASE_SECOND: i32 = 2;\n"
+               "pub const JOLT_DORY_PHASE_GAMMA: i32 = 3;\npub const JOLT_DORY_PHASE_FINAL: i32 = 4;")
     out.append("pub const JOLT_MAX_MEMBER_TABLES: usize = 40;\npub const JOLT_MAX_MEMBER_TERMS: usize = 16;\npub const JOLT_MAX_MEMBER_FACTORS: usize = 64;\npub const JOLT_MAX_DEGREE: usize = 7;")
     out.append("")
     out.append("#[repr(C)]\npub struct jolt_member_desc {\n    pub n_tables: u32,\n    pub n_terms: u32,\n    pub degree: u32,\n    pub order: i32,\n"
@@ -149,6 +152,8 @@ def render(decls):
     out.append("pub type jolt_gather_fn = Option<unsafe extern \"C\" fn(user: *mut c_void, local: *const jolt_fr_t, count: usize, gathered: *mut jolt_fr_t) -> i32>;")
     out.append("pub type jolt_round_transcript_fn = Option<unsafe extern \"C\" fn(user: *mut c_void, compressed_coeffs: *const jolt_fr_t, n_coeffs: usize, challenge_out: *mut jolt_fr_t) -> i32>;")
     out.append("pub type jolt_open_transcript_fn = Option<\n    unsafe extern \"C\" fn(user: *mut c_void, phase: i32, points: *const jolt_g1_t, n_points: usize, values: *const jolt_fr_t, n_values: usize, challenge_out: *mut jolt_fr_t) -> i32,\n>;")
+    out.append("pub type jolt_dory_transcript_fn = Option<\n    unsafe extern \"C\" fn(user: *mut c_void, phase: i32, round: usize, gts: *const jolt_gt_t, n_gt: usize, g1s: *const jolt_g1_t, n_g1: usize, "
+               "g2s: *const jolt_g2_t, n_g2: usize, challenge_out: *mut jolt_fr_t) -> i32,\n>;")
     out.append("")
     out.append('#[link(name = "jolt_hip")]\nextern "C" {')
     for name, ret, params in decls:
