@@ -1457,6 +1457,65 @@ int32_t jolt_host_prove_batch_ops_grouped(jolt_ctx *ctx, jolt_stage_op *const *o
                                           const size_t *offsets, size_t max_num_vars, size_t max_degree, uint64_t transcript_label, int32_t challenge_mode,
                                           jolt_fr_t *out_polys, jolt_fr_t *out_challenges, jolt_fr_t *out_member_claims, jolt_fr_t *out_final_claim);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Precommitted claim reductions (crates/jolt-kernels/src/precommitted_reduction.rs; builders crates/jolt-kernels/src/optimized/precommitted_reduction.rs):
+ * the stage-6b cycle phases and stage-7 address phases of the trusted-advice, untrusted-advice, committed-bytecode and program-image reductions as ONE generic
+ * operator pair.  The round schedule (which rounds of a phase's window bind a variable) and the variable permutation are the CALLER's inputs, as they are relation
+ * accessors in the reference (PrecommittedClaimReduction::cycle_phase_rounds / address_phase_rounds / poly_opening_round_permutation_be).
+ *
+ * State (:76-85): `value` and `eq` of 2^n entries ALREADY in opening-round order, n_aux passenger tables of the same length that bind alongside without entering
+ * the summand, a running scale (1/2 per inactive round ingested) and its inverse.  The operator is head-aligned (batch offset 0): it is consulted in every round
+ * of its window and `bind` is NULL in round 0 only.
+ *   prove_round(bind, round, previous_claim) (:140-151): the pending challenge belongs to round - 1 -- active: bind every table LowToHigh; inactive: scale *= 1/2,
+ *     scale_inv *= 2 (:160-172).  Then the message (:96-133): inactive -> the ONE coefficient previous_claim / 2; active -> e0 = sum_j value[2j] eq[2j],
+ *     e2 = sum_j (2 value[2j+1] - value[2j]) (2 eq[2j+1] - eq[2j]), the HINT e1 = previous_claim scale_inv - e0, c2 = (e0 - 2 e1 + e2) / 2, c1 = e1 - e0 - c2, and the
+ *     THREE coefficients (e0, c1, c2) scale.  e1 comes from the claim, not from the tables: under a batch's 2^(max - rounds) padding the emitted quadratic carries the
+ *     padding factor (module doc :30-37), and there is no round check to fail.
+ *   finish_rounds(bind) (:154-156): the bind of the last round.
+ *   output_claims, cycle operator (:359-365, :492-510): with an address phase scheduled (n_address_active > 0) the intermediate claim sum value eq scale over the
+ *     bound tables (:176-192); without one the bound value[0], then the bound aux[i][0] -- JOLT_ERR_NOT_FULLY_BOUND while a variable is unbound (:194-202).
+ *   output_claims, address operator (:536-590): the bound value[0], then the aux[i][0]; JOLT_ERR_NOT_FULLY_BOUND likewise.
+ * Degree 2; num_rounds = the phase's total; jolt_stage_op_input_claim = sum value eq scale (the cycle operator before a round: sum value eq).
+ *
+ * jolt_stage_precommitted_cycle_create: the operator works on its OWN copies of the tables (the caller's stay intact and need not outlive it).  n_aux <= 256.
+ *   cycle_active / address_active: strictly ascending round indices below cycle_total / address_total (JOLT_ERR_INVALID_ARG otherwise); cycle_total >= 1.
+ *   JOLT_ERR_SIZE_MISMATCH: tables of unequal length, n_cycle_active + n_address_active != n (:317-329 TableSizeMismatch); JOLT_ERR_INVALID_ARG: a length that is
+ *   not a power of two, a null or foreign table, n_aux > 256.
+ * jolt_stage_precommitted_address_create: reclaims the carry -- the bound tables AND the running scale (:225-234, :418-426) -- out of a FINISHED cycle operator, the
+ *   way jolt_stage_bytecode_read_raf_cycle_create consumes its address operator.  A cycle operator without an address phase, one whose rounds are not finished, or
+ *   one whose carry has been reclaimed is JOLT_ERR_INVALID_ARG with the reference's diagnostic in jolt_last_error ("stage 6b parked no precommitted reduction state
+ *   for the scheduled address phase").  The cycle operator keeps answering output_claims (its intermediate claim is kept).
+ * jolt_stage_host_precommitted_create / _address_create: the same contract over HOST tables with no device and no context (tables copied), as
+ *   jolt_stage_host_expr_create is for the dense member: what the CPU suite drives against the definition.
+ * ---------------------------------------------------------------------------------------------------------- */
+int32_t jolt_stage_precommitted_cycle_create(jolt_ctx *ctx, const jolt_table *value, const jolt_table *eq, const jolt_table *const *aux, size_t n_aux,
+                                             const size_t *cycle_active, size_t n_cycle_active, size_t cycle_total, const size_t *address_active,
+                                             size_t n_address_active, size_t address_total, jolt_stage_op **out);
+int32_t jolt_stage_precommitted_address_create(jolt_ctx *ctx, jolt_stage_op *cycle_op, jolt_stage_op **out);
+int32_t jolt_stage_host_precommitted_create(const jolt_fr_t *value, const jolt_fr_t *eq, const jolt_fr_t *const *aux, size_t n_aux, size_t len,
+                                            const size_t *cycle_active, size_t n_cycle_active, size_t cycle_total, const size_t *address_active,
+                                            size_t n_address_active, size_t address_total, jolt_stage_op **out);
+int32_t jolt_stage_host_precommitted_address_create(jolt_stage_op *cycle_op, jolt_stage_op **out);
+/* The prepare side (optimized/precommitted_reduction.rs), each a small kernel or a composition of entries above; the bytecode value fold sum_c w_c chunk_c is
+ * jolt_rlc (in groups above 40 chunks), the program image jolt_table_from_ints then jolt_table_permute_bits, advice_opening jolt_table_evaluate.
+ * jolt_host_precommitted_lsb_permutation: lsb_permutation (precommitted_reduction.rs:595-609).  perm_be[be_index] = the opening round of big-endian variable be_index,
+ *   all distinct (a duplicate is JOLT_ERR_INVALID_ARG); the variables sorted by round become the new LSB order, old_lsb_to_new_lsb[n - 1 - be_index] = new_lsb.
+ *   *is_identity = 1 when the relabeling moves nothing (the reference's None).  n <= 40.
+ * jolt_host_precommitted_permute_challenges: permute_challenges (:641-652): out[n - 1 - map[n - 1 - old_be]] = challenges_be[old_be].
+ * jolt_table_permute_bits: permute_coefficients (:615-636): out[new] = table[old] with bit b of `new` moved to its pre-image position; a pure gather into a fresh
+ *   table.  table length 2^n (JOLT_ERR_SIZE_MISMATCH); a map that is not a permutation of 0 .. n-1 is JOLT_ERR_INVALID_ARG.
+ * jolt_eq_evals_shifted: shifted_eq_slice (optimized/precommitted_reduction.rs:337-360): out[i] = eq(r, (start_index + i) mod 2^n), big-endian as jolt_eq_evals, for
+ *   1 <= len <= 2^n, assembled from maximal aligned blocks (jolt_eq_evals_aligned_block), wrap included; the full 2^n table is never built.
+ * jolt_table_outer: the bytecode eq template lane_weights[lane] * cycle_table[cycle] at index -> (lane, cycle) = TracePolynomialOrder::index_to_address_cycle
+ *   (crates/jolt-claims/src/protocols/jolt/geometry/dimensions.rs:48-58): JOLT_TRACE_CYCLE_MAJOR (index / cycles, index % cycles), JOLT_TRACE_ADDRESS_MAJOR
+ *   (index % lanes, index / lanes); cycles = the length of cycle_table. */
+enum { JOLT_TRACE_CYCLE_MAJOR = 0, JOLT_TRACE_ADDRESS_MAJOR = 1 }; /* TracePolynomialOrder::transcript_scalar (dimensions.rs:28-33) */
+int32_t jolt_host_precommitted_lsb_permutation(const size_t *perm_be, size_t n, size_t *old_lsb_to_new_lsb, int32_t *is_identity);
+int32_t jolt_host_precommitted_permute_challenges(const jolt_fr_t *challenges_be, size_t n, const size_t *map, jolt_fr_t *out);
+int32_t jolt_table_permute_bits(jolt_ctx *ctx, const jolt_table *table, const size_t *old_lsb_to_new_lsb, size_t n, jolt_table **out);
+int32_t jolt_eq_evals_shifted(jolt_ctx *ctx, const jolt_fr_t *r, size_t n, size_t start_index, size_t len, jolt_table **out);
+int32_t jolt_table_outer(jolt_ctx *ctx, const jolt_fr_t *lane_weights, size_t n_lanes, const jolt_table *cycle_table, int32_t order, jolt_table **out);
+
 #ifdef __cplusplus
 }
 #endif

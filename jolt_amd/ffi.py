@@ -2720,8 +2720,8 @@ class StageOp:
 
     def output_claims(self):
         n = C.c_size_t()
-        out = fr_array(256)
-        _ck(lib().jolt_stage_op_output_claims(self.h, _p(out), C.c_size_t(256), C.byref(n)), "jolt_stage_op_output_claims", self.ctx)
+        out = fr_array(320)  # (a precommitted reduction answers with up to 1 + 256 claims)
+        _ck(lib().jolt_stage_op_output_claims(self.h, _p(out), C.c_size_t(320), C.byref(n)), "jolt_stage_op_output_claims", self.ctx)
         return out[: n.value].copy()
 
     def kept(self, key):
@@ -3085,3 +3085,92 @@ def _prove_spartan_stage(self, rows, cols, tau, input_claim, coefficient, transc
 Context.r1cs_uniskip_sums_rows = _r1cs_uniskip_sums_rows
 Context.stage_spartan_remainder_rows = _stage_spartan_remainder_rows
 Context.prove_spartan_stage = _prove_spartan_stage
+
+
+# ---- precommitted claim reductions (precommitted.hip): the operator pair, its host twin, the table builders ----------------------------------------------------
+TRACE_CYCLE_MAJOR, TRACE_ADDRESS_MAJOR = 0, 1  # JOLT_TRACE_*
+
+
+def _size_array(values):
+    v = [int(x) for x in values]
+    return (C.c_size_t * max(len(v), 1))(*v), len(v)
+
+
+def _stage_precommitted_cycle(self, value, eq, aux, cycle_active, cycle_total, address_active=(), address_total=0):
+    """jolt_stage_precommitted_cycle_create: the stage-6b cycle phase over COPIES of the resident tables (already in opening-round order)"""
+    ca, n_ca = _size_array(cycle_active)
+    aa, n_aa = _size_array(address_active)
+    h = C.c_void_p()
+    _ck(lib().jolt_stage_precommitted_cycle_create(self.h, value.h, eq.h, _handles(aux), C.c_size_t(len(aux)), ca, C.c_size_t(n_ca), C.c_size_t(cycle_total), aa, C.c_size_t(n_aa),
+                                                   C.c_size_t(address_total), C.byref(h)), "jolt_stage_precommitted_cycle_create", self)
+    return StageOp(self, h)
+
+
+def _stage_precommitted_address(self, cycle_op):
+    """jolt_stage_precommitted_address_create: the stage-7 address phase from the carry of a FINISHED cycle operator"""
+    h = C.c_void_p()
+    _ck(lib().jolt_stage_precommitted_address_create(self.h, cycle_op.h, C.byref(h)), "jolt_stage_precommitted_address_create", self)
+    return StageOp(self, h)
+
+
+def stage_host_precommitted(value, eq, aux, cycle_active, cycle_total, address_active=(), address_total=0, length=None):
+    """jolt_stage_host_precommitted_create: the same operator over HOST tables (no device, no context).  `length` overrides the table length handed over (refusal tests)"""
+    tabs = [np.ascontiguousarray(t, dtype=np.uint64).reshape(-1, 4) for t in [value, eq] + list(aux)]
+    ptrs = (C.c_void_p * max(len(tabs) - 2, 1))(*[t.ctypes.data for t in tabs[2:]])
+    ca, n_ca = _size_array(cycle_active)
+    aa, n_aa = _size_array(address_active)
+    h = C.c_void_p()
+    _ck(lib().jolt_stage_host_precommitted_create(_p(tabs[0]), _p(tabs[1]), ptrs, C.c_size_t(len(tabs) - 2), C.c_size_t(tabs[0].shape[0] if length is None else length), ca,
+                                                  C.c_size_t(n_ca), C.c_size_t(cycle_total), aa, C.c_size_t(n_aa), C.c_size_t(address_total), C.byref(h)),
+        "jolt_stage_host_precommitted_create")
+    return StageOp(None, h)
+
+
+def stage_host_precommitted_address(cycle_op):
+    h = C.c_void_p()
+    _ck(lib().jolt_stage_host_precommitted_address_create(cycle_op.h, C.byref(h)), "jolt_stage_host_precommitted_address_create")
+    return StageOp(None, h)
+
+
+def host_precommitted_lsb_permutation(perm_be):
+    """lsb_permutation -> (old_lsb_to_new_lsb as a list, is_identity)"""
+    p, n = _size_array(perm_be)
+    out, same = (C.c_size_t * max(n, 1))(), C.c_int32()
+    _ck(lib().jolt_host_precommitted_lsb_permutation(p, C.c_size_t(n), out, C.byref(same)), "jolt_host_precommitted_lsb_permutation")
+    return [int(out[i]) for i in range(n)], bool(same.value)
+
+
+def host_precommitted_permute_challenges(challenges_be, mapping):
+    c = fr(challenges_be).reshape(-1, 4)
+    m, n = _size_array(mapping)
+    out = fr_array(max(n, 1))
+    _ck(lib().jolt_host_precommitted_permute_challenges(_p(c), C.c_size_t(c.shape[0]), m, _p(out)), "jolt_host_precommitted_permute_challenges")
+    return out[:n]
+
+
+def _table_permute_bits(self, table, old_lsb_to_new_lsb):
+    m, n = _size_array(old_lsb_to_new_lsb)
+    h = C.c_void_p()
+    _ck(lib().jolt_table_permute_bits(self.h, table.h, m, C.c_size_t(n), C.byref(h)), "jolt_table_permute_bits", self)
+    return Table(self, h)
+
+
+def _eq_evals_shifted(self, r, start_index, length):
+    r = fr(r).reshape(-1, 4)
+    h = C.c_void_p()
+    _ck(lib().jolt_eq_evals_shifted(self.h, _p(r), C.c_size_t(r.shape[0]), C.c_size_t(start_index), C.c_size_t(length), C.byref(h)), "jolt_eq_evals_shifted", self)
+    return Table(self, h)
+
+
+def _table_outer(self, lane_weights, cycle_table, order):
+    w = fr(lane_weights).reshape(-1, 4)
+    h = C.c_void_p()
+    _ck(lib().jolt_table_outer(self.h, _p(w), C.c_size_t(w.shape[0]), cycle_table.h, C.c_int32(order), C.byref(h)), "jolt_table_outer", self)
+    return Table(self, h)
+
+
+Context.stage_precommitted_cycle = _stage_precommitted_cycle
+Context.stage_precommitted_address = _stage_precommitted_address
+Context.table_permute_bits = _table_permute_bits
+Context.eq_evals_shifted = _eq_evals_shifted
+Context.table_outer = _table_outer

@@ -21,6 +21,8 @@ use jolt_kernels::{JoltBackend, KernelError, ProofSession};
 use jolt_poly::UnivariatePoly;
 use jolt_verifier::stages::stage1::outer_remainder::OuterRemainder;
 use jolt_verifier::stages::stage2::product_remainder::ProductRemainder;
+use jolt_verifier::stages::stage7::advice_address_phase::{TrustedAdviceAddressPhase, UntrustedAdviceAddressPhase};
+use jolt_verifier::stages::stage7::committed_reduction_address_phase::{BytecodeReductionAddressPhase, ProgramImageReductionAddressPhase};
 use jolt_witness::{JoltWitnessOracle, JoltWitnessPlane};
 
 use crate::context::{HipContext, HipTable};
@@ -28,6 +30,7 @@ use crate::leaves;
 use crate::member::HipPrepare;
 use crate::opening::{HipGridHint, HipJointOpening, HipOpeningHint, ResidentCommitted, ResidentGridBlock};
 use crate::ops::{HipHotIndices, HipInts, SpartanSums};
+use crate::precommitted::{HipPrecommittedAddress, HipPrecommittedCycle};
 use crate::stage;
 use crate::pcs::{HipHyperKzg, HipHyperKzgSetup};
 use crate::scheduler::HipBuildRoundScheduler;
@@ -294,10 +297,10 @@ pub struct Mi355xParts {
 }
 
 /// `JoltBackend::optimized()` with the slots this crate serves overwritten by their device kernels -- the composition pattern of
-/// `optimized/mod.rs:136-196`.  27 of the registry's 37 slots (`crates/jolt-kernels/src/backend.rs:126-171`): the commit slot, the round-traversal factory, the two
+/// `optimized/mod.rs:136-196`.  All 37 slots of the registry (`crates/jolt-kernels/src/backend.rs:126-171`): the commit slot, the round-traversal factory, the two
 /// uni-skip fronts and the joint opening; the eleven stage operators as `jolt_stage_op` kernels (`crate::stage`); the eleven cycle-domain relations of stages 2 - 6b
 /// through [`with_relation`] with each relation's leaf resolver (`crate::leaves`: which opening / derived table each leaf of its `Expr` is,
-/// `crates/jolt-kernels/src/reference/views.rs:20-138`).  A slot whose `prepare`
+/// `crates/jolt-kernels/src/reference/views.rs:20-138`); the nine slots of the precommitted claim reductions (`crate::precommitted`).  A slot whose `prepare`
 /// answers `KernelError::Unsupported` (no gfx950 device, a descriptor beyond the library's compiled limits, out of HBM) is recoverable: the
 /// stage driver retries it against `optimized()`.
 ///
@@ -342,8 +345,22 @@ pub fn mi355x(ctx: &Arc<HipContext>, parts: Mi355xParts) -> JoltBackend<Fr, HipH
     backend.ram_hamming_booleanity = with_relation(ctx, LowToHigh, leaves::RamHammingBooleanityLeaves);
     backend.ram_ra_virtualization = with_relation(ctx, LowToHigh, leaves::RamRaVirtualizationLeaves);
     backend.instruction_ra_virtualization = with_relation(ctx, LowToHigh, leaves::InstructionRaVirtualizationLeaves);
-    // left on `optimized()`: booleanity_cycle (its joint (address || cycle) member is harness-scale in the reference tier), the advice and
-    // precommitted-program reductions and the advice opening evaluation (no T-scale work: DESIGN.md section 7)
+    // ---- the precommitted claim reductions (crate::precommitted): the four stage-6b cycle phases and the stage-4 advice opening behind one slot type, the four
+    // stage-7 address phases reclaiming the carry the cycle kernel parked.  A Hip cycle slot pairs ONLY with a Hip address slot (the reference's carry type has
+    // private fields), which is why all eight are assigned together; the reason strings are the reference's.
+    backend.advice_opening = Box::new(HipPrecommittedCycle::new(ctx));
+    backend.trusted_advice_cycle = Box::new(HipPrecommittedCycle::new(ctx));
+    backend.untrusted_advice_cycle = Box::new(HipPrecommittedCycle::new(ctx));
+    backend.bytecode_reduction_cycle = Box::new(HipPrecommittedCycle::new(ctx));
+    backend.program_image_reduction_cycle = Box::new(HipPrecommittedCycle::new(ctx));
+    backend.trusted_advice_address =
+        Box::new(HipPrecommittedAddress::<TrustedAdviceAddressPhase<Fr>>::new(ctx, "stage 6b parked no trusted-advice reduction state for the scheduled address phase"));
+    backend.untrusted_advice_address =
+        Box::new(HipPrecommittedAddress::<UntrustedAdviceAddressPhase<Fr>>::new(ctx, "stage 6b parked no untrusted-advice reduction state for the scheduled address phase"));
+    backend.bytecode_reduction_address =
+        Box::new(HipPrecommittedAddress::<BytecodeReductionAddressPhase<Fr>>::new(ctx, "stage 6b parked no bytecode reduction state for the scheduled address phase"));
+    backend.program_image_reduction_address =
+        Box::new(HipPrecommittedAddress::<ProgramImageReductionAddressPhase<Fr>>::new(ctx, "stage 6b parked no program-image reduction state for the scheduled address phase"));
     backend
 }
 

@@ -150,6 +150,8 @@ pub const JOLT_ERR_EMPTY_POINT: i32 = 10;
 pub const JOLT_ERR_NOT_INVERTIBLE: i32 = 11;
 pub const JOLT_ORDER_LOW_TO_HIGH: i32 = 0;
 pub const JOLT_ORDER_HIGH_TO_LOW: i32 = 1;
+pub const JOLT_TRACE_CYCLE_MAJOR: i32 = 0;
+pub const JOLT_TRACE_ADDRESS_MAJOR: i32 = 1;
 pub const JOLT_MEMBER_FLAG_SKIP_ONE: u32 = 1;
 pub const JOLT_MEMBER_FLAG_BORROW_TABLES: u32 = 2;
 pub const JOLT_INT_U64: i32 = 0;
@@ -616,4 +618,13 @@ extern "C" {
     pub fn jolt_host_prove_spartan_stage(ctx: *mut jolt_ctx, rows: *const jolt_r1cs_rows, cols: *const *const jolt_ints, n_cols: usize, tau: *const jolt_fr_t, n_tau: usize, input_claim: *const jolt_fr_t, coefficient: *const jolt_fr_t, transcript: *mut jolt_host_transcript, uniskip_coeffs_out: *mut jolt_fr_t, r0_out: *mut jolt_fr_t, uniskip_claim_out: *mut jolt_fr_t, polys_out: *mut jolt_fr_t, challenges_out: *mut jolt_fr_t, final_claim_out: *mut jolt_fr_t, output_claims_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_stage_op_prove_alone(op: *mut jolt_stage_op, transcript: *mut jolt_host_transcript, claim: *mut jolt_fr_t, coeffs_out: *mut jolt_fr_t, stride: usize, n_coeffs_out: *mut u32, challenges_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_prove_batch_ops_grouped(ctx: *mut jolt_ctx, ops: *const *mut jolt_stage_op, n_ops: usize, input_claims: *const jolt_fr_t, coefficients: *const jolt_fr_t, offsets: *const usize, max_num_vars: usize, max_degree: usize, transcript_label: u64, challenge_mode: i32, out_polys: *mut jolt_fr_t, out_challenges: *mut jolt_fr_t, out_member_claims: *mut jolt_fr_t, out_final_claim: *mut jolt_fr_t) -> i32;
+    pub fn jolt_stage_precommitted_cycle_create(ctx: *mut jolt_ctx, value: *const jolt_table, eq: *const jolt_table, aux: *const *const jolt_table, n_aux: usize, cycle_active: *const usize, n_cycle_active: usize, cycle_total: usize, address_active: *const usize, n_address_active: usize, address_total: usize, out: *mut *mut jolt_stage_op) -> i32;
+    pub fn jolt_stage_precommitted_address_create(ctx: *mut jolt_ctx, cycle_op: *mut jolt_stage_op, out: *mut *mut jolt_stage_op) -> i32;
+    pub fn jolt_stage_host_precommitted_create(value: *const jolt_fr_t, eq: *const jolt_fr_t, aux: *const *const jolt_fr_t, n_aux: usize, len: usize, cycle_active: *const usize, n_cycle_active: usize, cycle_total: usize, address_active: *const usize, n_address_active: usize, address_total: usize, out: *mut *mut jolt_stage_op) -> i32;
+    pub fn jolt_stage_host_precommitted_address_create(cycle_op: *mut jolt_stage_op, out: *mut *mut jolt_stage_op) -> i32;
+    pub fn jolt_host_precommitted_lsb_permutation(perm_be: *const usize, n: usize, old_lsb_to_new_lsb: *mut usize, is_identity: *mut i32) -> i32;
+    pub fn jolt_host_precommitted_permute_challenges(challenges_be: *const jolt_fr_t, n: usize, map: *const usize, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_table_permute_bits(ctx: *mut jolt_ctx, table: *const jolt_table, old_lsb_to_new_lsb: *const usize, n: usize, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_eq_evals_shifted(ctx: *mut jolt_ctx, r: *const jolt_fr_t, n: usize, start_index: usize, len: usize, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_table_outer(ctx: *mut jolt_ctx, lane_weights: *const jolt_fr_t, n_lanes: usize, cycle_table: *const jolt_table, order: i32, out: *mut *mut jolt_table) -> i32;
 }

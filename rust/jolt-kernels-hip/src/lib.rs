@@ -21,6 +21,7 @@
 //! | dory's `DoryRoutines<ArkG1>` / `DoryRoutines<ArkG2>`, the group routines of `dory::prove`'s reduce-and-fold rounds (`crates/jolt-dory/src/routines.rs:58-147`) | [`dory_routines::HipG1Routines`], [`dory_routines::HipG2Routines`] over `jolt_dory_g1_*` / `jolt_dory_g2_*` / `jolt_dory_fold_field_vectors` |
 //! | the inner products and folds of one reduce-and-fold round of `dory::prove` on vectors that stay on the device (no trait: dory's `DoryRoutines` works on host slices) | [`dory_resident`]: [`dory_resident::HipDoryVec`], [`dory_resident::products`] over `jolt_dory_vec_*` / `jolt_dory_products` |
 //! | `DoryScheme::open`'s prover side as one call under the caller's `Transcript`: state, VMV message, the rounds, fold-scalars, final message (no trait: `dory::prove` owns that loop in the reference) | [`dory_proof`]: [`dory_proof::HipDorySetup`] and its `open_with` over `jolt_dory_setup_*` / `jolt_host_dory_open_with_transcript`, [`dory_proof::round_update`] over `jolt_dory_round_update` |
+//! | the precommitted claim reductions: `{trusted,untrusted}_advice_{cycle,address}`, `bytecode_reduction_{cycle,address}`, `program_image_reduction_{cycle,address}`, `advice_opening` (`crates/jolt-kernels/src/{precommitted_reduction.rs, optimized/precommitted_reduction.rs}`) | [`precommitted`]: [`precommitted::HipPrecommittedCycle`], [`precommitted::HipPrecommittedAddress`] over `jolt_stage_precommitted_{cycle,address}_create` and the device table builders |
 //! | `UniskipKernel`, `CommitWitness`, the backend constructor (`crates/jolt-kernels/src/{uniskip.rs:28-54, commitment.rs:137-160, optimized/mod.rs:136-196}`) | [`backend::HipUniskip`], [`backend::HipCommitWitness`], [`backend::mi355x`] |
 //!
 //! Host code stays Rust: Fiat-Shamir, claim wiring, round-polynomial assembly (`UnivariatePoly::from_evals`,
@@ -40,6 +41,7 @@ pub mod opening;
 pub mod pairing;
 pub mod ops;
 pub mod pcs;
+pub mod precommitted;
 pub mod rows;
 pub mod backend;
 pub mod scheduler;
@@ -62,4 +64,5 @@ pub use scheduler::{HipBuildRoundScheduler, HipRoundScheduler};
 pub use status::HipError;
 pub use streaming::{HipOneHotChunk, HipOneHotStream, HipPartialCommitment};
 pub use opening::{HipGridColumn, HipGridHint, HipJointOpening, HipOpeningHint, ResidentGridBlock};
+pub use precommitted::{HipPrecommittedAddress, HipPrecommittedCarry, HipPrecommittedCycle};
 pub use stage::{HipStageKernel, HipStageOp, ResidentTrace};

@@ -81,9 +81,9 @@ impl HipStageOp {
     }
 
     pub fn output_values(&mut self) -> Result<Vec<Fr>, HipError> {
-        let mut out = vec![Fr::default(); 256];
+        let mut out = vec![Fr::default(); 320]; // (a precommitted reduction answers with up to 1 + 256 values)
         let mut n = 0usize;
-        // SAFETY: `out` holds 256 elements of jolt_fr_t layout; the library reports how many it wrote.
+        // SAFETY: `out` holds 320 elements of jolt_fr_t layout; the library reports how many it wrote.
         check(unsafe { ffi::jolt_stage_op_output_claims(self.raw, out.as_mut_ptr().cast(), out.len(), &mut n) }, self.ctx.raw)?;
         out.truncate(n);
         Ok(out)
@@ -131,7 +131,7 @@ impl Drop for HipStageOp {
 }
 
 /// How a slot turns the operator's output values (in the order its constructor documents) into the relation's typed output claims.
-type Extract<R> = Box<dyn Fn(&[Fr], &SumcheckInputClaims<Fr, R>) -> Result<SumcheckOutputClaims<Fr, R>, SumcheckKernelError<Fr>> + Send>;
+pub(crate) type Extract<R> = Box<dyn Fn(&[Fr], &SumcheckInputClaims<Fr, R>) -> Result<SumcheckOutputClaims<Fr, R>, SumcheckKernelError<Fr>> + Send>;
 
 /// The typed kernel of a stage-operator slot: a [`HipStageOp`] plus the slot's claim extraction.  `keep`: device inputs the operator borrows.
 pub struct HipStageKernel<R: ConcreteSumcheck<Fr>>
@@ -200,7 +200,7 @@ where
     }
 }
 
-fn kernel<R>(op: HipStageOp, keep: Vec<Arc<dyn core::any::Any + Send + Sync>>, extract: Extract<R>) -> Box<dyn SumcheckKernel<Fr, Relation = R>>
+pub(crate) fn kernel<R>(op: HipStageOp, keep: Vec<Arc<dyn core::any::Any + Send + Sync>>, extract: Extract<R>) -> Box<dyn SumcheckKernel<Fr, Relation = R>>
 where
     R: ConcreteSumcheck<Fr> + 'static,
     SumcheckInputClaims<Fr, R>: InputClaims<Fr>,
@@ -210,7 +210,23 @@ where
     Box::new(HipStageKernel { op, extract, park: None, _keep: keep })
 }
 
-fn short(values: &[Fr], need: usize) -> Result<(), SumcheckKernelError<Fr>> {
+/// [`kernel`] whose `park_residue` moves the finished operator into the session (the precommitted cycle phases park their carry for stage 7).
+pub(crate) fn kernel_parking<R>(
+    op: HipStageOp,
+    keep: Vec<Arc<dyn core::any::Any + Send + Sync>>,
+    extract: Extract<R>,
+    park: fn(HipStageOp, &mut ProofSession),
+) -> Box<dyn SumcheckKernel<Fr, Relation = R>>
+where
+    R: ConcreteSumcheck<Fr> + 'static,
+    SumcheckInputClaims<Fr, R>: InputClaims<Fr>,
+    SumcheckOutputClaims<Fr, R>: OutputClaims<Fr>,
+    ConcreteSumcheckChallenges<Fr, R>: SumcheckChallenges<Fr, JoltChallengeId>,
+{
+    Box::new(HipStageKernel { op, extract, park: Some(park), _keep: keep })
+}
+
+pub(crate) fn short(values: &[Fr], need: usize) -> Result<(), SumcheckKernelError<Fr>> {
     if values.len() < need {
         return Err(SumcheckKernelError::InvariantViolation { reason: "a stage operator returned fewer output values than its slot reads" });
     }

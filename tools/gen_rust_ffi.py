@@ -128,6 +128,7 @@ def render(decls):
                               "JOLT_ERR_NOT_FULLY_BOUND", "JOLT_ERR_ROUND_CHECK", "JOLT_ERR_SRS_TOO_SMALL", "JOLT_ERR_EMPTY_POINT", "JOLT_ERR_NOT_INVERTIBLE"]):
         out.append(f"pub const {name}: i32 = {k};")
     out.append("pub const JOLT_ORDER_LOW_TO_HIGH: i32 = 0;\npub const JOLT_ORDER_HIGH_TO_LOW: i32 = 1;")
+    out.append("pub const JOLT_TRACE_CYCLE_MAJOR: i32 = 0;\npub const JOLT_TRACE_ADDRESS_MAJOR: i32 = 1;")
     out.append("pub const JOLT_MEMBER_FLAG_SKIP_ONE: u32 = 1;\npub const JOLT_MEMBER_FLAG_BORROW_TABLES: u32 = 2;")
     out.append("pub const JOLT_INT_U64: i32 = 0;\npub const JOLT_INT_I64: i32 = 1;\npub const JOLT_INT_I128: i32 = 2;\npub const JOLT_SCALAR_FR: i32 = 3;")
     out.append("pub const JOLT_FQ2_ADD: i32 = 0;\npub const JOLT_FQ2_SUB: i32 = 1;\npub const JOLT_FQ2_MUL: i32 = 2;\npub const JOLT_FQ2_SQR: i32 = 3;\npub const JOLT_FQ2_NEG: i32 = 4;")

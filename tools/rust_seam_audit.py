@@ -20,6 +20,8 @@ suite uses where the reference is absent.  Round 4's `JoltBackend::<Fr, HipHyper
 
     python tools/rust_seam_audit.py                  # audit, findings on stdout, exit 1 if any
     python tools/rust_seam_audit.py --write-fixture  # re-extract the reference surface the crate touches
+    python tools/rust_seam_audit.py --write-fixture-extra  # leave that file as recorded; what the crate names beyond it goes to reference_trait_surface_extra.json,
+                                                           # which every audit over a recorded surface merges in (entries the recorded file has are never overwritten)
 
 dory's `DoryRoutines` (src/dory_routines.rs) is outside all of this -- the trait lives in the external dory-pcs crate -- so `dory_routines_findings` holds the crate's two
 impls against the function names and arities of the reference's own two (crates/jolt-dory/src/routines.rs), frozen into tests/golden/dory_routines_surface.json.
@@ -33,6 +35,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CRATE = os.path.join(ROOT, "rust", "jolt-kernels-hip")
 REFERENCE = "/root/reference"
 FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_trait_surface.json")
+# what the crate has come to name since FIXTURE was recorded (--write-fixture-extra: the live surface's entries FIXTURE lacks); merged into any recorded surface an Audit is given
+FIXTURE_EXTRA = os.path.join(ROOT, "tests", "golden", "reference_trait_surface_extra.json")
+
+
+def merge_surface(surface, extra):
+    """entries of `extra` that `surface` lacks, section by section (a recorded entry is never overwritten)"""
+    for section, entries in extra.items():
+        if isinstance(entries, dict):
+            have = surface.setdefault(section, {})
+            for key, value in entries.items():
+                have.setdefault(key, value)
+    return surface
+
+
+def surface_delta(surface, base):
+    return {section: {k: v for k, v in entries.items() if k not in base.get(section, {})} for section, entries in surface.items() if isinstance(entries, dict)}
 STD_ROOTS = {"std", "core", "alloc", "crate", "self", "super"}
 PRIMITIVES = {"u8", "u16", "u32", "u64", "u128", "usize", "i8", "i16", "i32", "i64", "i128", "isize", "f32", "f64", "bool", "char", "str"}
 DERIVABLE = {"Clone", "Copy", "Debug", "Default", "PartialEq", "Eq", "Hash", "PartialOrd", "Ord"}
@@ -377,7 +395,7 @@ class Crate:
             if ch != "{":
                 continue
             header = src[i:end]
-            head, _, where = header.partition(" where ")
+            head = re.split(r"\swhere\s", header, maxsplit=1)[0]  # (the where clause may start on a line of its own)
             fm = re.match(r"^\s*(.*?)\s+for\s+(.*?)\s*$", head, re.S)
             if not fm:
                 continue  # inherent impl
@@ -424,6 +442,8 @@ class Audit:
         self.crate = crate or Crate()
         self.live = surface is None
         self.surface = surface if surface is not None else {"traits": {}, "blanket": {}, "generic": {}}
+        if surface is not None and os.path.isfile(FIXTURE_EXTRA):
+            merge_surface(self.surface, json.load(open(FIXTURE_EXTRA)))
         self.findings = []
 
     # reference lookups, memoised into self.surface (which is what --write-fixture saves)
@@ -832,6 +852,17 @@ def main():
             json.dump(dory_routines_surface(live=True), f, indent=1, sort_keys=True)
             f.write("\n")
         print(f"{DORY_FIXTURE}: the reference's DoryRoutines impls")
+        return
+    if "--write-fixture-extra" in sys.argv:  # FIXTURE stays as recorded; what the crate names beyond it goes beside it
+        if not live:
+            sys.exit("the reference checkout is not here")
+        a = Audit()
+        a.run()
+        delta = {k: v for k, v in surface_delta(a.surface, json.load(open(FIXTURE))).items() if v}
+        with open(FIXTURE_EXTRA, "w") as f:
+            json.dump(delta, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"{FIXTURE_EXTRA}: {sum(len(v) for v in delta.values())} entries beyond {os.path.basename(FIXTURE)}; {len(a.findings)} finding(s)")
         return
     a = Audit() if live else Audit(json.load(open(FIXTURE)))
     findings = a.run() + dory_routines_findings(a.crate, dory_routines_surface(live=True) if live else None)
