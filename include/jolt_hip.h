@@ -88,6 +88,21 @@ int32_t jolt_ctx_trim(jolt_ctx *ctx);
 int32_t jolt_ctx_memory_stats(const jolt_ctx *ctx, size_t *live_bytes, size_t *cached_bytes, size_t *peak_bytes);
 /* ... and what the context holds outside the pool: the grow-only workspaces of its MSM lanes and of the batch of short MSMs (bytes). */
 int32_t jolt_ctx_workspace_stats(const jolt_ctx *ctx, size_t *msm_lane_bytes, size_t *msm_batch_bytes);
+/* Which kernel path the batch rounds of this context took: host-side launch counts since the context was created or the counts were last zeroed (a test names the
+ * kernel it means to reach with them; nothing on the device reads or writes them).  counts[k], k < min(cap, JOLT_ROUND_PATH_COUNT), is the count of the enum below;
+ * reset != 0 zeroes all of them after the copy (counts may be NULL to zero only). */
+enum {
+    JOLT_ROUND_PATH_TAIL = 0,             /* k_round_evals_tail launches                                                                    */
+    JOLT_ROUND_PATH_GROUP = 1,            /* k_round_evals_group launches: 8 counts at GROUP + 4 * order + 2 * skip_one + fused             */
+    JOLT_ROUND_PATH_SMALL = 9,            /* k_round_evals_small launches (integer-backed round 0)                                          */
+    JOLT_ROUND_PATH_SPLIT_EQ_PRODUCT = 10, /* k_split_eq_product launches: unfused, then (+1) with the pending bind fused                    */
+    JOLT_ROUND_PATH_UNIFORM_ITEMS = 12,   /* dense uniform member on (product, pair) items                                                  */
+    JOLT_ROUND_PATH_UNIFORM_ROWS = 13,    /* dense uniform member rows-major (one item per pair)                                            */
+    JOLT_ROUND_PATH_LAZY = 14,            /* every index-encoded form (uniform first / LDS / rows / items, booleanity) together             */
+    JOLT_ROUND_PATH_BIND = 15,            /* grouped separate binds (one per challenge and order): LowToHigh, then (+1) HighToLow           */
+    JOLT_ROUND_PATH_COUNT = 17
+};
+int32_t jolt_ctx_round_path_stats(jolt_ctx *ctx, uint64_t *counts, size_t cap, int32_t reset);
 /* Device-event timing of everything enqueued between begin and end on the context's stream (milliseconds). */
 int32_t jolt_timer_begin(jolt_ctx *ctx);
 int32_t jolt_timer_end(jolt_ctx *ctx, float *elapsed_ms);

@@ -263,6 +263,14 @@ extern "C" int32_t jolt_ctx_workspace_stats(const jolt_ctx* ctx, size_t* msm_lan
     return JOLT_OK;
 }
 
+/* Launch counts of group_enqueue per kernel path (the JOLT_ROUND_PATH_* indices), optionally zeroed after the copy. */
+extern "C" int32_t jolt_ctx_round_path_stats(jolt_ctx* ctx, uint64_t* counts, size_t cap, int32_t reset) {
+    if (!ctx) return JOLT_ERR_INVALID_ARG;
+    if (counts) std::memcpy(counts, ctx->round_paths, std::min<size_t>(cap, JOLT_ROUND_PATH_COUNT) * sizeof(uint64_t));
+    if (reset) std::memset(ctx->round_paths, 0, sizeof(ctx->round_paths));
+    return JOLT_OK;
+}
+
 int32_t jolt_internal_ensure_scratch(jolt_ctx* ctx, size_t partials, size_t results) {
     if (partials > ctx->partials_cap || results > ctx->results_cap)
         for (int k = 0; k < 3; ++k) if (ctx->side[k]) JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->side[k]));
@@ -1510,7 +1518,10 @@ static int32_t group_enqueue(jolt_ctx* ctx, jolt_member* const* members, size_t 
         }
     }
     if (etrace) e1 = eclk::now();
-    for (BindGroup& g : bgs) JOLT_TRY(jolt_internal_bind(ctx, g.tabs.data(), g.tabs.size(), g.r, g.order));
+    for (BindGroup& g : bgs) {
+        ctx->round_paths[JOLT_ROUND_PATH_BIND + (g.order == JOLT_ORDER_HIGH_TO_LOW ? 1 : 0)]++;
+        JOLT_TRY(jolt_internal_bind(ctx, g.tabs.data(), g.tabs.size(), g.r, g.order));
+    }
     if (etrace) e2 = eclk::now();
     size_t slot = 0, part_total = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -1690,6 +1701,7 @@ static int32_t group_enqueue(jolt_ctx* ctx, jolt_member* const* members, size_t 
         Fr* part = ctx->d_partials + it.part_off;
         hipStream_t st = next_stream();
         if (m->lazy_width) {  // selector columns still index-encoded: gather instead of loading dense pairs
+            ctx->round_paths[JOLT_ROUND_PATH_LAZY]++;
             LazyArgs la;
             la.idx = m->onehot->idx;
             la.wide = m->onehot->wide;
@@ -1722,24 +1734,28 @@ static int32_t group_enqueue(jolt_ctx* ctx, jolt_member* const* members, size_t 
             continue;
         }
         if (it.rows_major) {
+            ctx->round_paths[JOLT_ROUND_PATH_UNIFORM_ROWS]++;
             if (m->uni_F == 2) hipLaunchKernelGGL(k_split_eq_uniform_rows<2>, g, b, 0, st, ua, e_out, e_in, (int)m->e_in_bits, m->len / 2, part, (uint32_t)i, (uint32_t)it.slot, rd);
             else if (m->uni_F == 3) hipLaunchKernelGGL(k_split_eq_uniform_rows<3>, g, b, 0, st, ua, e_out, e_in, (int)m->e_in_bits, m->len / 2, part, (uint32_t)i, (uint32_t)it.slot, rd);
             else hipLaunchKernelGGL(k_split_eq_uniform_rows<4>, g, b, 0, st, ua, e_out, e_in, (int)m->e_in_bits, m->len / 2, part, (uint32_t)i, (uint32_t)it.slot, rd);
             JOLT_HIP_TRY(ctx, hipGetLastError());
             continue;
         }
+        ctx->round_paths[JOLT_ROUND_PATH_UNIFORM_ITEMS]++;
         if (m->uni_F == 2) hipLaunchKernelGGL(k_split_eq_uniform<2>, g, b, 0, st, ua, e_out, e_in, (int)m->e_in_bits, m->len / 2, part, (uint32_t)i, (uint32_t)it.slot, rd);
         else if (m->uni_F == 3) hipLaunchKernelGGL(k_split_eq_uniform<3>, g, b, 0, st, ua, e_out, e_in, (int)m->e_in_bits, m->len / 2, part, (uint32_t)i, (uint32_t)it.slot, rd);
         else hipLaunchKernelGGL(k_split_eq_uniform<4>, g, b, 0, st, ua, e_out, e_in, (int)m->e_in_bits, m->len / 2, part, (uint32_t)i, (uint32_t)it.slot, rd);
         JOLT_HIP_TRY(ctx, hipGetLastError());
     }
     for (TailLaunch& T : tails) {
+        ctx->round_paths[JOLT_ROUND_PATH_TAIL]++;
         hipLaunchKernelGGL(k_round_evals_tail, dim3(T.gx, (unsigned)T.count, T.gz), dim3(kBlock), 0, next_stream(ctx->fuse_tail), T.args, T.r, T.shifted, ctx->d_partials, rd);
         JOLT_HIP_TRY(ctx, hipGetLastError());
     }
     for (Launch& L : launches) {
         dim3 grid(L.grid, (unsigned)L.count);
         hipStream_t lst = next_stream(L.fused);
+        ctx->round_paths[L.small ? JOLT_ROUND_PATH_SMALL : JOLT_ROUND_PATH_GROUP + 4 * (L.order == JOLT_ORDER_HIGH_TO_LOW ? 1 : 0) + 2 * L.skip + L.fused]++;
         if (L.small) {
             if (L.skip) launch_round_small<true>(L.ne, grid, lst, L.args, L.sargs, ctx->d_partials, rd);
             else launch_round_small<false>(L.ne, grid, lst, L.args, L.sargs, ctx->d_partials, rd);
@@ -1776,6 +1792,7 @@ static int32_t group_enqueue(jolt_ctx* ctx, jolt_member* const* members, size_t 
         const Fr* e_out = m->e_out_cache[m->e_out_bits]->data();
         const Fr* e_in = m->e_in_cache[m->e_in_bits]->data();
         hipStream_t bst = next_stream();
+        if (m->lazy_width) ctx->round_paths[JOLT_ROUND_PATH_LAZY]++;
         if (m->lazy_width && it.bool_cols)
             hipLaunchKernelGGL(k_split_eq_booleanity_lds, dim3(it.grid), dim3(kBlock), (size_t)it.bool_cols * m->lazy_width * ((size_t)m->onehot->k + 1) * sizeof(Fr), bst, ba,
                                it.bool_cols, it.lds_blocks, e_out, e_in, (int)m->e_in_bits, m->len / 2, ctx->d_partials + it.part_off, (uint32_t)i, (uint32_t)it.slot, rd);
@@ -1796,6 +1813,7 @@ static int32_t group_enqueue(jolt_ctx* ctx, jolt_member* const* members, size_t 
         Fr r = it.fused ? it.r : Fr::zero();
         int shifted = fr_low_limbs_zero(r) ? 1 : 0;
         hipStream_t sst = next_stream(it.fused);
+        ctx->round_paths[JOLT_ROUND_PATH_SPLIT_EQ_PRODUCT + (it.fused ? 1 : 0)]++;
         if (it.fused)
             hipLaunchKernelGGL(k_split_eq_product<true>, dim3(it.grid), dim3(kBlock), 0, sst, it.in[0], it.in[1], it.out[0], it.out[1], r, shifted,
                                e_out, e_in, (int)m->e_in_bits, m->len / 2, ctx->d_partials + it.part_off, (uint32_t)i, (uint32_t)it.slot, rd);

@@ -82,6 +82,7 @@ struct jolt_ctx {
     size_t fuse_ratio = 2;        // an expression member's pending bind is fused into its round kernel when multiplies per pair <= ratio x tables (JOLT_FUSE_RATIO)
     size_t tail_pairs = 16384;    // rounds with at most this many pairs use the tail kernel (JOLT_TAIL_PAIRS; 4096..65536 measure within 2 %)
     bool fuse_tail = false;       // JOLT_FUSE_TAIL=1: pending binds of expr members are applied inside the tail kernel too
+    uint64_t round_paths[JOLT_ROUND_PATH_COUNT] = {};  // launches of group_enqueue per kernel path (jolt_ctx_round_path_stats): host bookkeeping only
     bool msm_lds_attr_set = false;
     bool msm_fx_attr_set = false;
     bool grid_hint_attr_set = false;  // k_grid_onehot_sum's dynamic-LDS limit raised on this device (pcs.hip: background class sums reserve LDS to stay at one wave per SIMD)

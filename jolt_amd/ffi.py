@@ -2113,6 +2113,20 @@ def _memory_stats(self):
     return out
 
 
+ROUND_PATH_COUNT = 17  # JOLT_ROUND_PATH_COUNT
+
+
+def _round_path_stats(self, reset=False):
+    """Launch counts of the batch rounds per kernel path since the last reset (jolt_ctx_round_path_stats): `group` is keyed by (order, skip_one, fused),
+    `split_eq_product` and `bind` are (unfused, fused) and (LowToHigh, HighToLow)."""
+    a = np.zeros(ROUND_PATH_COUNT, dtype=np.uint64)
+    _ck(lib().jolt_ctx_round_path_stats(self.h, _p(a), C.c_size_t(ROUND_PATH_COUNT), C.c_int32(1 if reset else 0)), "jolt_ctx_round_path_stats", self)
+    c = [int(x) for x in a]
+    return {"tail": c[0], "group": {(o, bool(s), bool(f)): c[1 + 4 * o + 2 * s + f] for o in (0, 1) for s in (0, 1) for f in (0, 1)}, "small": c[9],
+            "split_eq_product": (c[10], c[11]), "uniform_items": c[12], "uniform_rows": c[13], "lazy": c[14], "bind": (c[15], c[16])}
+
+
+Context.round_path_stats = _round_path_stats
 Context.table_from_ints = _table_from_ints
 Context.grid_commit_onehot = _grid_commit_onehot
 Context.grid_commit_onehot_classes = _grid_commit_onehot_classes

@@ -185,6 +185,15 @@ pub const JOLT_DORY_PHASE_FIRST: i32 = 1;
 pub const JOLT_DORY_PHASE_SECOND: i32 = 2;
 pub const JOLT_DORY_PHASE_GAMMA: i32 = 3;
 pub const JOLT_DORY_PHASE_FINAL: i32 = 4;
+pub const JOLT_ROUND_PATH_TAIL: usize = 0;
+pub const JOLT_ROUND_PATH_GROUP: usize = 1;
+pub const JOLT_ROUND_PATH_SMALL: usize = 9;
+pub const JOLT_ROUND_PATH_SPLIT_EQ_PRODUCT: usize = 10;
+pub const JOLT_ROUND_PATH_UNIFORM_ITEMS: usize = 12;
+pub const JOLT_ROUND_PATH_UNIFORM_ROWS: usize = 13;
+pub const JOLT_ROUND_PATH_LAZY: usize = 14;
+pub const JOLT_ROUND_PATH_BIND: usize = 15;
+pub const JOLT_ROUND_PATH_COUNT: usize = 17;
 pub const JOLT_MAX_MEMBER_TABLES: usize = 40;
 pub const JOLT_MAX_MEMBER_TERMS: usize = 16;
 pub const JOLT_MAX_MEMBER_FACTORS: usize = 64;
@@ -256,6 +265,7 @@ extern "C" {
     pub fn jolt_ctx_trim(ctx: *mut jolt_ctx) -> i32;
     pub fn jolt_ctx_memory_stats(ctx: *const jolt_ctx, live_bytes: *mut usize, cached_bytes: *mut usize, peak_bytes: *mut usize) -> i32;
     pub fn jolt_ctx_workspace_stats(ctx: *const jolt_ctx, msm_lane_bytes: *mut usize, msm_batch_bytes: *mut usize) -> i32;
+    pub fn jolt_ctx_round_path_stats(ctx: *mut jolt_ctx, counts: *mut u64, cap: usize, reset: i32) -> i32;
     pub fn jolt_timer_begin(ctx: *mut jolt_ctx) -> i32;
     pub fn jolt_timer_end(ctx: *mut jolt_ctx, elapsed_ms: *mut f32) -> i32;
     pub fn jolt_table_upload(ctx: *mut jolt_ctx, host: *const jolt_fr_t, len: usize, out: *mut *mut jolt_table) -> i32;

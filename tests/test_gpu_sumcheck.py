@@ -28,8 +28,9 @@ def one():
     return ONE
 
 
-def lockstep(dev, orc, n_vars, seed, shifted=True):
-    """run_lockstep: same claim and challenges into both members, coefficients compared every round."""
+def lockstep(dev, orc, n_vars, seed, shifted=True, challenge=None):
+    """run_lockstep: same claim and challenges into both members, coefficients compared every round.
+    challenge(rnd), when given, supplies the round's challenge instead of rand_challenge(seed + rnd, shifted)."""
     claim = orc.input_claim()
     assert np.array_equal(dev.input_claim(), claim)
     bind = None
@@ -48,7 +49,7 @@ def lockstep(dev, orc, n_vars, seed, shifted=True):
             assert np.array_equal(O.fr_add(evals[:1], evals[1:2])[0], claim), f"round {rnd}: s(0)+s(1) != claim"
             coeffs = ffi.host_univariate_from_evals(evals)
         assert np.array_equal(coeffs, want), f"round {rnd}"
-        bind = rand_challenge(seed + rnd, shifted)
+        bind = challenge(rnd) if challenge else rand_challenge(seed + rnd, shifted)
         claim = O.univariate_evaluate(want, bind)
     orc.finish_rounds(bind)
     dev.finish(bind)
@@ -253,12 +254,13 @@ def test_split_eq_uniform_product_member_lockstep(ctx, V, F, n_vars):
     assert np.array_equal(fv[:-1], ofv[1:]) and np.array_equal(fv[-1], ofv[0])  # bound tables, then the bound eq scalar
 
 
-@pytest.mark.parametrize("n_vars", [1, 5, 9, 14])
+@pytest.mark.parametrize("n_vars", [1, 5, 9, 14, 16])
 def test_eq_weighted_lc_member_matches_oracle(ctx, n_vars):
     """eq(w,j) * q(j) with the eq weight factored out (jolt_member_create_split_eq_lc): q = (f1*a + f2*b) + g*(f3*c) + const-factor
     group, inner degree 2 -> two sums per round, s = l*q on the host.  Lock-step against the oracle's flat Expr member over the
-    dense eq table; borrowed tables, both challenge shapes, tail and grouped kernels (n_vars 14 crosses the tail threshold), and
-    again inside prove_batch next to an ordinary member."""
+    dense eq table; borrowed tables, both challenge shapes, and again inside prove_batch next to an ordinary member.  Up to n_vars 14
+    (8192 pairs in round 0) every round is a tail round: the tail threshold is 16384 pairs.  Only n_vars 16 starts in the group kernel
+    (32768 pairs); tests/test_gpu_round_kernels.py asserts the path taken above the threshold from the context's launch counts."""
     N = 1 << n_vars
     w = rand_fr(n_vars, 5100)
     scale = rand_fr(1, 5101)[0]

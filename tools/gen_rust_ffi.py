@@ -139,6 +139,9 @@ def render(decls):
     out.append("pub const JOLT_DORY_UPDATE_BETA: i32 = 0;\npub const JOLT_DORY_UPDATE_ALPHA: i32 = 1;\n"
                "pub const JOLT_DORY_PHASE_VMV: i32 = 0;\npub const JOLT_DORY_PHASE_FIRST: i32 = 1;\npub const JOLT_DORY_PHASE_SECOND: i32 = 2;\n"
                "pub const JOLT_DORY_PHASE_GAMMA: i32 = 3;\npub const JOLT_DORY_PHASE_FINAL: i32 = 4;")
+    out.append("pub const JOLT_ROUND_PATH_TAIL: usize = 0;\npub const JOLT_ROUND_PATH_GROUP: usize = 1;\npub const JOLT_ROUND_PATH_SMALL: usize = 9;\n"
+               "pub const JOLT_ROUND_PATH_SPLIT_EQ_PRODUCT: usize = 10;\npub const JOLT_ROUND_PATH_UNIFORM_ITEMS: usize = 12;\npub const JOLT_ROUND_PATH_UNIFORM_ROWS: usize = 13;\n"
+               "pub const JOLT_ROUND_PATH_LAZY: usize = 14;\npub const JOLT_ROUND_PATH_BIND: usize = 15;\npub const JOLT_ROUND_PATH_COUNT: usize = 17;")
     out.append("pub const JOLT_MAX_MEMBER_TABLES: usize = 40;\npub const JOLT_MAX_MEMBER_TERMS: usize = 16;\npub const JOLT_MAX_MEMBER_FACTORS: usize = 64;\npub const JOLT_MAX_DEGREE: usize = 7;")
     out.append("")
     out.append("#[repr(C)]\npub struct jolt_member_desc {\n    pub n_tables: u32,\n    pub n_terms: u32,\n    pub degree: u32,\n    pub order: i32,\n"
