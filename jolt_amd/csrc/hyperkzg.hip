@@ -155,13 +155,20 @@ static __global__ __launch_bounds__(kBlock) void k_rlc(RlcArgs a, const Fr* __re
 }
 
 // log2 of the elements per thread of the blocked suffix scan: 64.  8 / 16 / 32 / 64 measure the same (141 ms of suffix + Horner kernel time over three
-// 2^26-coefficient openings each): the scans are not bound by their access pattern
+// 2^26-coefficient openings each)
 constexpr int kScanChunkLog = 6;
+// A thread of a scan walks a chunk of its own, 2 or 4 KiB from its neighbours'.  It reads the kLineFr coefficients of a 128-byte line together and then steps through
+// them, instead of coming back to the line four times with every other thread's line in between (chunks start on a line boundary).
+constexpr int kLineFr = 4;
+__device__ __forceinline__ void ld_line(const Fr* p, Fr (&x)[kLineFr]) {
+#pragma unroll
+    for (int i = 0; i < kLineFr; ++i) x[i] = ld_fr(p + i);
+}
 // LANES interleaved chains: s[k] = a[k] + mu s[k + LANES].  LANES = 1 is the suffix Horner of a witness polynomial (kzg.rs:39-44); LANES = 2 runs the even and the odd
 // coefficients as two chains, which divides by (X^2 - mu) in ONE pass -- the pair of witness polynomials at r and -r of an opening share that quotient
 // (hyperkzg_open_impl).  A chunk is kScanChunk positions of EVERY chain (kScanChunk * LANES consecutive coefficients); heads / S hold LANES values per chunk.
-// The scans are bound by their two field multiplications per coefficient (one per pass), not by the access pattern: a version through LDS tiles (coalesced loads and
-// stores, chains of 8) needed 3.1 multiplications per coefficient for its in-tile scan and measured no faster (profiles/r04_open_tiled_scan_ab.txt).
+// A version through LDS tiles (coalesced loads and stores, chains of 8) needed 3.1 multiplications per coefficient for its in-tile scan and measured no faster
+// (profiles/r04_open_tiled_scan_ab.txt).
 // heads[c * LANES + l] = Horner of chunk c of chain l with zero carry-in
 template <int LANES>
 static __global__ __launch_bounds__(kBlock) void k_suffix_heads(const Fr* __restrict__ a, size_t m /* positions per chain */, Fr mu, Fr* __restrict__ heads, size_t nchunks, size_t kScanChunk) {
@@ -171,9 +178,16 @@ static __global__ __launch_bounds__(kBlock) void k_suffix_heads(const Fr* __rest
     Fr acc[LANES];
 #pragma unroll
     for (int l = 0; l < LANES; ++l) acc[l] = Fr::zero();
-    for (size_t k = hi; k-- > lo;) {
+    size_t k = hi;
+    for (; k > lo && (k * LANES) % kLineFr; --k) {  // down to a line boundary (a short last chunk only)
 #pragma unroll
-        for (int l = 0; l < LANES; ++l) acc[l] = add(mul(acc[l], mu), ld_fr(a + k * LANES + l));
+        for (int l = 0; l < LANES; ++l) acc[l] = add(mul(acc[l], mu), ld_fr(a + (k - 1) * LANES + l));
+    }
+    for (; k > lo; k -= kLineFr / LANES) {  // a line at a time, as k_suffix_apply
+        Fr x[kLineFr];
+        ld_line(a + (k * LANES - kLineFr), x);
+#pragma unroll
+        for (int i = kLineFr - 1; i >= 0; --i) acc[i % LANES] = add(mul(acc[i % LANES], mu), x[i]);
     }
 #pragma unroll
     for (int l = 0; l < LANES; ++l) st_fr(heads + c * LANES + l, acc[l]);
@@ -189,19 +203,33 @@ static __global__ __launch_bounds__(kBlock) void k_suffix_apply(const Fr* __rest
     Fr acc[LANES];
 #pragma unroll
     for (int l = 0; l < LANES; ++l) acc[l] = (S != nullptr && c + 1 < nchunks) ? ld_fr(S + (c + 1) * LANES + l) : carry;
-    for (size_t k = hi; k-- > lo;) {
+    static_assert(kLineFr % LANES == 0, "a line holds whole positions");
+    size_t k = hi;
+    for (; k > lo && (k * LANES) % kLineFr; --k) {  // down to a line boundary (a short last chunk only: chunks start on one)
 #pragma unroll
         for (int l = LANES - 1; l >= 0; --l) {
-            acc[l] = add(mul(acc[l], mu), ld_fr(a + k * LANES + l));
-            const size_t g = k * LANES + l;
+            const size_t g = (k - 1) * LANES + l;
+            acc[l] = add(mul(acc[l], mu), ld_fr(a + g));
             if (g >= shift) st_fr(out + (g - shift), acc[l]);
+        }
+    }
+    for (; k > lo; k -= kLineFr / LANES) {  // (k - lo) * LANES is a multiple of kLineFr from here on
+        const size_t g0 = k * LANES - kLineFr;
+        Fr x[kLineFr];
+        ld_line(a + g0, x);
+#pragma unroll
+        for (int i = kLineFr - 1; i >= 0; --i) {
+            acc[i % LANES] = add(mul(acc[i % LANES], mu), x[i]);
+            if (g0 + i >= shift) st_fr(out + (g0 + i - shift), acc[i % LANES]);
         }
     }
 }
 
-// s[k] = a[k] + mu s[k + LANES] over the m coefficients of a (m a multiple of LANES), written to out[k - shift]
+// s[k] = a[k] + mu s[k + LANES] over the m coefficients of a (m a multiple of LANES), written to out[k - shift].  `given_heads`: the chunk heads of a where the caller
+// has them already (nchunks * LANES values in this function's chunk geometry; the opening gets them by linearity from the heads of its levels); nullptr: a heads pass
+// over the array computes them.
 template <int LANES>
-int32_t suffix_scan(jolt_ctx* ctx, const Fr* a, size_t m, const Fr& mu, Fr* out, size_t shift, const Fr& carry) {
+int32_t suffix_scan(jolt_ctx* ctx, const Fr* a, size_t m, const Fr& mu, Fr* out, size_t shift, const Fr& carry, const Fr* given_heads = nullptr) {
     if (m % LANES) return JOLT_ERR_UNSUPPORTED;
     if (LANES != 1 && !(carry == Fr::zero())) return JOLT_ERR_UNSUPPORTED;
     const size_t positions = m / LANES;  // per chain
@@ -218,23 +246,190 @@ int32_t suffix_scan(jolt_ctx* ctx, const Fr* a, size_t m, const Fr& mu, Fr* out,
         return JOLT_OK;
     }
     Fr *heads = nullptr, *S = nullptr;
-    JOLT_TRY(jolt_internal_dev_alloc(ctx, nchunks * LANES * sizeof(Fr), (void**)&heads));
-    if (jolt_internal_dev_alloc(ctx, nchunks * LANES * sizeof(Fr), (void**)&S) != JOLT_OK) { jolt_internal_dev_free(ctx, heads); return JOLT_ERR_OOM; }
-    hipLaunchKernelGGL(k_suffix_heads<LANES>, dim3(grid), dim3(kBlock), 0, ctx->stream, a, positions, mu, heads, nchunks, kScanChunk);
+    if (given_heads == nullptr) {
+        JOLT_TRY(jolt_internal_dev_alloc(ctx, nchunks * LANES * sizeof(Fr), (void**)&heads));
+        hipLaunchKernelGGL(k_suffix_heads<LANES>, dim3(grid), dim3(kBlock), 0, ctx->stream, a, positions, mu, heads, nchunks, kScanChunk);
+        given_heads = heads;
+    }
+    if (jolt_internal_dev_alloc(ctx, nchunks * LANES * sizeof(Fr), (void**)&S) != JOLT_OK) { if (heads) jolt_internal_dev_free(ctx, heads); return JOLT_ERR_OOM; }
     Fr mu_c = mu;
     for (int i = 0; i < chunk_log; ++i) mu_c = sqr(mu_c);  // mu^chunk
-    int32_t s = suffix_scan<LANES>(ctx, heads, nchunks * LANES, mu_c, S, 0, carry);  // the chunk values form LANES chains again; the carry enters at the same place
+    int32_t s = suffix_scan<LANES>(ctx, given_heads, nchunks * LANES, mu_c, S, 0, carry);  // the chunk values form LANES chains again; the carry enters at the same place
     if (s == JOLT_OK) {
         hipLaunchKernelGGL(k_suffix_apply<LANES>, dim3(grid), dim3(kBlock), 0, ctx->stream, a, positions, mu, (const Fr*)S, nchunks, out, shift, kScanChunk, carry);
         if (hipGetLastError() != hipSuccess) s = JOLT_ERR_HIP;
     }
-    jolt_internal_dev_free(ctx, heads);  // pool blocks: reused in stream order, no synchronisation
+    if (heads) jolt_internal_dev_free(ctx, heads);  // pool blocks: reused in stream order, no synchronisation
     jolt_internal_dev_free(ctx, S);
     return s;
 }
 // s = suffix Horner of a (length m) with multiplier mu, written to out[k - shift]
 int32_t suffix_horner(jolt_ctx* ctx, const Fr* a, size_t m, const Fr& mu, Fr* out, size_t shift, const Fr& carry = Fr::zero()) {
     return suffix_scan<1>(ctx, a, m, mu, out, shift, carry);
+}
+
+// ---- the opening's evaluations as the heads of its quotient scan (hyperkzg_open_impl, one GPU) ---------------------------------------------
+// With mu = r^2 the chunk heads of suffix_scan<2> over level P_j are Horner values of the chunk's even and odd coefficients, so their chunk-level Horner sums are
+// E_j(mu) and O_j(mu) for P_j(X) = E_j(X^2) + X O_j(X^2): P_j(r) = E_j + r O_j, P_j(-r) = E_j - r O_j, and, level j + 1 being the fold (1 - x) E_j + x O_j
+// coefficient by coefficient, P_(j+1)(mu) = (1 - x) E_j(mu) + x O_j(mu).  Heads are linear in the input and every level starts at index 0, so the heads of
+// B = sum_j q^j P_j are the same combination of the levels' heads (k_rlc over arrays 64 times shorter): ONE pass over the levels before q exists gives every
+// evaluation of the proof and the heads of the scan that divides B, at one multiplication per coefficient (two on level 0, whose value at mu needs a third chain).
+struct LevelHeadsArgs {
+    const Fr* level[40];
+    Fr* heads[40];             // 2 * nchunks_j values: (even, odd) per chunk of 2 * 64 coefficients
+    size_t len[40];
+    unsigned first_block[41];  // level j owns the workgroups [first_block[j], first_block[j + 1]): 256 chunks each
+    int ell;
+};
+// partials[block * 3 + t]: the block's chunk values weighed with lane_weights[t][tid] = w_t^tid (w_0 = w_1 = mu^64, a chunk of one chain; w_2 = mu^128: a chunk of
+// the plain Horner sum of level 0, zero on the other levels)
+static __global__ __launch_bounds__(kBlock) void k_level_heads(LevelHeadsArgs a, Fr mu, const Fr* __restrict__ lane_weights, Fr* __restrict__ partials) {
+    int j = 0;
+    while (j + 1 < a.ell && blockIdx.x >= a.first_block[j + 1]) ++j;
+    const Fr* __restrict__ p = a.level[j];
+    const size_t chunk = (size_t)1 << kScanChunkLog, positions = a.len[j] / 2, nchunks = (positions + chunk - 1) >> kScanChunkLog;
+    const size_t c = (size_t)(blockIdx.x - a.first_block[j]) * kBlock + threadIdx.x;
+    Fr acc[3] = {Fr::zero(), Fr::zero(), Fr::zero()};
+    if (c < nchunks) {
+        const size_t lo = c * chunk, hi = lo + chunk < positions ? lo + chunk : positions;
+        const bool plain = j == 0;  // (the same for the whole workgroup)
+        auto step = [&](const Fr& e, const Fr& o) {
+            acc[0] = add(mul(acc[0], mu), e);
+            acc[1] = add(mul(acc[1], mu), o);
+            if (plain) acc[2] = add(mul(add(mul(acc[2], mu), o), mu), e);
+        };
+        size_t k = hi;
+        if (k & 1) {  // (a level of two coefficients)
+            --k;
+            step(ld_fr(p + 2 * k), ld_fr(p + 2 * k + 1));
+        }
+        for (; k > lo; k -= 2) {  // two positions: one 128-byte line
+            Fr x[kLineFr];
+            ld_line(p + (2 * k - kLineFr), x);
+            step(x[2], x[3]);
+            step(x[0], x[1]);
+        }
+        Fr* __restrict__ h = a.heads[j];
+        st_fr(h + 2 * c, acc[0]);
+        st_fr(h + 2 * c + 1, acc[1]);
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+            if (t < 2 || j == 0) acc[t] = mul(acc[t], ld_fr(lane_weights + t * kBlock + threadIdx.x));
+    }
+    block_reduce_store<3>(acc, partials);
+}
+// results[3 j + t] = sum over level j's workgroups b of partials[b][t] (w_t^256)^b: workgroup = level; thread tid takes the workgroups tid, tid + 256, ... by Horner
+// in (w_t^256)^256 and weighs the sum with (w_t^256)^tid
+static __global__ __launch_bounds__(kBlock) void k_level_totals(LevelHeadsArgs a, const Fr* __restrict__ partials, Fr3 wb /* w_t^256 */, Fr3 wb256, Fr* __restrict__ results) {
+    const unsigned b0 = a.first_block[blockIdx.x], nb = a.first_block[blockIdx.x + 1] - b0;
+    Fr acc[3] = {Fr::zero(), Fr::zero(), Fr::zero()};
+    if (threadIdx.x < nb) {
+        for (unsigned b = threadIdx.x + (nb - 1 - threadIdx.x) / kBlock * kBlock;; b -= kBlock) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t) acc[t] = add(mul(acc[t], wb256.v[t]), ld_fr(partials + (size_t)(b0 + b) * 3 + t));
+            if (b < (unsigned)kBlock) break;
+        }
+#pragma unroll
+        for (int t = 0; t < 3; ++t) acc[t] = mul(acc[t], fr_pow_u64(wb.v[t], threadIdx.x));
+    }
+    block_reduce_store_at<3>(acc, results + 3 * (size_t)blockIdx.x);
+}
+
+struct OpenLevelHeads {
+    LevelHeadsArgs args;
+    Fr* heads = nullptr;  // one pool block behind args.heads[]
+};
+// The first pass of an opening behind r: the heads of every level and, from their sums, v[t][j] = P_j(u_t) for u = (r, -r, r^2), row-major as jolt_hyperkzg_eval3 returns them.
+// Level lengths are 2^(ell - j); x: the opening point (fold j uses x[ell - j], jolt_hyperkzg_fold).  One download, one synchronisation.
+int32_t open_level_heads(jolt_ctx* ctx, jolt_table* const* levels, size_t ell, const Fr& r, const jolt_fr_t* x, jolt_fr_t* v_out, OpenLevelHeads* out) {
+    LevelHeadsArgs& a = out->args;
+    const size_t chunk = (size_t)1 << kScanChunkLog;
+    size_t total = 0, off[40];
+    a.ell = (int)ell;
+    a.first_block[0] = 0;
+    for (size_t j = 0; j < 40; ++j) { a.level[j] = nullptr; a.heads[j] = nullptr; a.len[j] = 0; }
+    for (size_t j = 0; j < ell; ++j) {
+        if (!levels[j] || levels[j]->len < 2 || levels[j]->len % 2) return JOLT_ERR_INVALID_ARG;
+        const size_t nchunks = (levels[j]->len / 2 + chunk - 1) / chunk;
+        a.level[j] = levels[j]->data();
+        a.len[j] = levels[j]->len;
+        a.first_block[j + 1] = a.first_block[j] + (unsigned)((nchunks + kBlock - 1) / kBlock);
+        off[j] = total;
+        total += 2 * nchunks;
+    }
+    const unsigned nblocks = a.first_block[ell];
+    const Fr mu = mul(r, r);
+    Fr3 w, wb, wb256;
+    w.v[0] = mu;
+    for (int i = 0; i < kScanChunkLog; ++i) w.v[0] = sqr(w.v[0]);
+    w.v[1] = w.v[0];
+    w.v[2] = sqr(w.v[0]);
+    for (int t = 0; t < 3; ++t) {
+        wb.v[t] = w.v[t];
+        for (int i = 0; i < 8; ++i) wb.v[t] = sqr(wb.v[t]);  // kBlock = 2^8 chunks per workgroup
+        wb256.v[t] = wb.v[t];
+        for (int i = 0; i < 8; ++i) wb256.v[t] = sqr(wb256.v[t]);
+    }
+    static_assert(kBlock == 256, "the chunk weights of k_level_heads / k_level_totals are powers by eight squarings");
+    JOLT_TRY(jolt_internal_ensure_scratch(ctx, (size_t)nblocks * 3, 3 * ell + 8));
+    Fr* lane_weights = nullptr;
+    JOLT_TRY(jolt_internal_dev_alloc(ctx, 3 * kBlock * sizeof(Fr), (void**)&lane_weights));
+    if (jolt_internal_dev_alloc(ctx, total * sizeof(Fr), (void**)&out->heads) != JOLT_OK) { jolt_internal_dev_free(ctx, lane_weights); return JOLT_ERR_OOM; }
+    for (size_t j = 0; j < ell; ++j) a.heads[j] = out->heads + off[j];
+    hipLaunchKernelGGL(k_power_table3, dim3(1), dim3(kBlock), 0, ctx->stream, w, lane_weights);
+    hipLaunchKernelGGL(k_level_heads, dim3(nblocks), dim3(kBlock), 0, ctx->stream, a, mu, (const Fr*)lane_weights, ctx->d_partials);
+    hipLaunchKernelGGL(k_level_totals, dim3((unsigned)ell), dim3(kBlock), 0, ctx->stream, a, (const Fr*)ctx->d_partials, wb, wb256, ctx->d_results);
+    hipError_t e = hipGetLastError();
+    jolt_internal_dev_free(ctx, lane_weights);  // stream-ordered: safe right after the last launch
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_results, ctx->d_results, 3 * ell * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->last_error = std::string("hyperkzg open (level heads): ") + hipGetErrorString(e);
+        jolt_internal_dev_free(ctx, out->heads);
+        out->heads = nullptr;
+        return JOLT_ERR_HIP;
+    }
+    const Fr* tot = ctx->h_results;  // (E_j, O_j, P_0(mu) on level 0) at mu
+    for (size_t j = 0; j < ell; ++j) {
+        const Fr ro = mul(r, tot[3 * j + 1]);
+        Fr at_mu = tot[2];
+        if (j) {
+            const Fr xj = fr_from_abi(&x[ell - j]);
+            at_mu = add(tot[3 * (j - 1)], mul(xj, sub(tot[3 * (j - 1) + 1], tot[3 * (j - 1)])));
+        }
+        fr_to_abi(&v_out[j], add(tot[3 * j], ro));
+        fr_to_abi(&v_out[ell + j], sub(tot[3 * j], ro));
+        fr_to_abi(&v_out[2 * ell + j], at_mu);
+    }
+    return JOLT_OK;
+}
+// q = B div (X^2 - mu) for B = sum_j q^j P_j (length len_0, qp: len_0 - 2 coefficients): the heads of the scan are the same combination of the levels' heads,
+// over arrays 64 times shorter than the levels, and the heads pass over B is not run
+int32_t open_quotient(jolt_ctx* ctx, const OpenLevelHeads& lh, const Fr& q, const Fr& mu, const Fr* B, Fr* qp) {
+    const LevelHeadsArgs& a = lh.args;
+    const size_t ell = (size_t)a.ell, chunk = (size_t)1 << kScanChunkLog;
+    RlcArgs hd;
+    hd.ell = a.ell;
+    std::vector<Fr> qpow(ell);
+    Fr cur = Fr::one();
+    for (size_t j = 0; j < 40; ++j) {
+        hd.level[j] = a.heads[j];
+        hd.len[j] = j < ell ? 2 * ((a.len[j] / 2 + chunk - 1) / chunk) : 0;
+    }
+    for (size_t j = 0; j < ell; ++j) { qpow[j] = cur; cur = mul(cur, q); }  // challenge_powers (kzg.rs:213-221)
+    jolt_table* dq = nullptr;
+    JOLT_TRY(jolt_table_upload(ctx, reinterpret_cast<const jolt_fr_t*>(qpow.data()), ell, &dq));
+    Fr* heads_b = nullptr;
+    int32_t s = jolt_internal_dev_alloc(ctx, hd.len[0] * sizeof(Fr), (void**)&heads_b);
+    if (s == JOLT_OK) {
+        hipLaunchKernelGGL(k_rlc, dim3((unsigned)((hd.len[0] + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, hd, (const Fr*)dq->data(), heads_b, hd.len[0]);
+        if (hipGetLastError() != hipSuccess) s = JOLT_ERR_HIP;
+    }
+    if (s == JOLT_OK) s = suffix_scan<2>(ctx, B, a.len[0], mu, qp, 2, Fr::zero(), heads_b);
+    if (heads_b) jolt_internal_dev_free(ctx, heads_b);
+    jolt_table_free(ctx, dq);  // back to the pool; reused in stream order
+    return s;
 }
 
 }  // namespace
@@ -633,7 +828,13 @@ static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt
     Fr u[3] = {r, neg(r), mul(r, r)};
     jolt_fr_t u_abi[3];
     for (int t = 0; t < 3; ++t) fr_to_abi(&u_abi[t], u[t]);
-    s = jolt_hyperkzg_eval3(ctx, polys.data(), ell, u_abi, v);  // kzg.rs:84-85
+    // One GPU, at least two variables (an even length >= 4): the evaluations come out of the heads pass of the quotient scan below (open_level_heads), run on the
+    // levels before q exists.
+    const bool from_heads = world == 1 && ell >= 2;
+    OpenLevelHeads level_heads;
+    struct FreeHeads { jolt_ctx* c; OpenLevelHeads* h; ~FreeHeads() { if (h->heads) jolt_internal_dev_free(c, h->heads); } } free_heads{ctx, &level_heads};
+    if (from_heads) s = open_level_heads(ctx, polys.data(), ell, r, point, v, &level_heads);
+    else s = jolt_hyperkzg_eval3(ctx, polys.data(), ell, u_abi, v);  // kzg.rs:84-85
     if (s != JOLT_OK) { cleanup(); return s; }
     Fr q;  // kzg.rs:88-95: every v[t][j], row-major
     s = tr.after_values(1, v, 3 * ell, &q);
@@ -653,14 +854,15 @@ static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt
         // q in ONE pass over B when its length is even (every opening of >= 2 variables): q[k] = B[k + 2] + r^2 q[k + 2], two interleaved chains (suffix_scan<2>), and
         // alpha = B[1] + r^2 q[1] (the X^1 coefficient of B = q (X^2 - r^2) + alpha X + beta); otherwise two divisions, by (X - r) and then by (X + r), whose second
         // remainder h_r[0] + q[0] (-r) is alpha.  Q3[k] = q[k + 1] + r^2 Q3[k + 1] (len - 3 coefficients), a = q[0] + r^2 Q3[0].
+        // The scan's heads are there since the evaluations (open_level_heads, open_quotient).
         jolt_table *h0 = nullptr, *qp = nullptr, *q3 = nullptr;
         bool direct = false;
         const size_t q3_len = b_poly->len - 3;
         if (srs->n < 2 || q3_len > srs->n - 2) s = JOLT_ERR_SRS_TOO_SMALL;  // (what the three commitments of len - 1 coefficients need)
-        if (s == JOLT_OK && b_poly->len % 2 == 0) {
+        if (s == JOLT_OK && from_heads) {
             s = jolt_internal_table_new(ctx, b_poly->len - 2, &qp);
             if (s == JOLT_OK) {
-                const int32_t qs = suffix_scan<2>(ctx, b_poly->data(), b_poly->len, u[2], qp->data(), 2, Fr::zero());
+                const int32_t qs = open_quotient(ctx, level_heads, q, u[2], b_poly->data(), qp->data());
                 if (qs == JOLT_OK) direct = true;
                 else if (qs == JOLT_ERR_UNSUPPORTED) { jolt_table_free(ctx, qp); qp = nullptr; }
                 else s = qs;
