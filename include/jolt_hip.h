@@ -425,6 +425,14 @@ int32_t jolt_host_transcript_append_round_poly(jolt_host_transcript *t, const ch
 int32_t jolt_host_transcript_challenge(jolt_host_transcript *t, int32_t full_width, jolt_fr_t *out);    /* 0: 125-bit challenge shape */
 int32_t jolt_host_transcript_state(const jolt_host_transcript *t, uint8_t *out32);
 int32_t jolt_host_transcript_destroy(jolt_host_transcript *t);
+/* The framing of HomomorphicBatch::prove_batch (crates/jolt-openings/src/schemes.rs:487-524) around a scheme's own messages; scheme-agnostic, host only.
+ *   _statement_absorb: LabelWithCount(b"rlc_claims", n), then each evaluation as a field element (VerifierRlcClaims, crates/jolt-openings/src/claims.rs:79-88);
+ *     then challenge_scalar_powers(n) (crates/jolt-transcript/src/legacy.rs:82-91): powers_out = 1, gamma, gamma^2, ... from ONE challenge_scalar.  n == 0 is
+ *     JOLT_ERR_INVALID_ARG (the reference refuses an empty batch).
+ *   _claim_absorb: LabelWithCount(b"opening_point", n_vars), the coordinates in the order given, Label(b"opening_eval"), the value (EvaluationClaim, claims.rs:23-35).
+ * A value that is not canonical is JOLT_ERR_INVALID_ARG, with nothing absorbed. */
+int32_t jolt_host_opening_statement_absorb(jolt_host_transcript *t, const jolt_fr_t *evaluations, size_t n, jolt_fr_t *powers_out /* n */);
+int32_t jolt_host_opening_claim_absorb(jolt_host_transcript *t, const jolt_fr_t *point, size_t n_vars, const jolt_fr_t *value);
 /* the two hash primitives behind engines 1 and 2, for known-answer tests: BLAKE2b (RFC 7693, unkeyed, 1..64 digest bytes), Keccak-f[1600] on a 200-byte state */
 int32_t jolt_host_blake2b(const uint8_t *in, size_t n, size_t outlen, uint8_t *out);
 int32_t jolt_host_keccak_f1600(uint8_t *state200);
@@ -920,6 +928,29 @@ int32_t jolt_host_dory_open_with_transcript(jolt_ctx *ctx, const jolt_dory_setup
 int32_t jolt_host_dory_open(jolt_ctx *ctx, const jolt_dory_setup *setup, const jolt_dory_vec *const *hints, const size_t *hint_first, const size_t *hint_rows,
                             size_t n_hints, const jolt_fr_t *scalars, const jolt_table *v_table, const jolt_table *left, const jolt_table *right, uint32_t nu,
                             uint32_t sigma, jolt_host_transcript *t, jolt_gt_t *gts, jolt_g1_t *g1s, jolt_g2_t *g2s, jolt_fr_t *challenges_out);
+/* HomomorphicBatch::<DoryScheme>::prove_batch (crates/jolt-openings/src/schemes.rs:487-524) on resident inputs: cycle-major placement, transparent mode, under one of
+ * the library's engines.  n_claims resident G1 hint views with evaluations[i] as the statement holds them (already scaled, crates/jolt-prover/src/dory/stages/stage8.rs:
+ * 148-162); the joint polynomial's columns as jolt_dory_fold_rows_grid takes them (n_claims = the one-hot columns of all sources + n_dense); column_of_claim[i] = claim
+ * i's column in that entry's order (one-hot columns source by source, then dense), NULL = the identity -- the batch order (final_opening_polynomial_order) is the
+ * caller's; point: log_k + log2(T) coordinates, most significant first, as jolt_eq_evals indexes.  The call
+ *   1. absorbs the statement (jolt_host_opening_statement_absorb): scalars_out = 1, gamma, ..., gamma^(n_claims - 1);
+ *   2. joint_eval_out = sum_i scalars[i] * evaluations[i];
+ *   3. sigma = ceil(n / 2), nu = n - sigma for n = n_point (crates/jolt-dory/src/scheme.rs:242-243); L = eq(point[:nu]), R = eq(point[nu:]);
+ *   4. v = jolt_dory_fold_rows_grid under the scalars in column order;
+ *   5. checks <v, R> == joint_eval: JOLT_ERR_ROUND_CHECK otherwise, before any state vector is built (the reference's open trusts its eval argument; this entry does
+ *      not return a proof of a false statement).  The transcript has absorbed the statement by then and is the caller's to discard;
+ *   6. opens as jolt_host_dory_open, the hints weighted by the same scalars (outputs sized by jolt_host_dory_proof_counts(sigma));
+ *   7. absorbs the closing claim (jolt_host_opening_claim_absorb) with joint_eval.
+ * Contract of jolt_host_dory_open: everything -- this entry's checks, the row fold's, the opening's -- is checked before the transcript absorbs anything and before
+ * anything is enqueued; on every exit the streams are drained before pool blocks go back; the inputs stay the caller's; the context stays usable.
+ * JOLT_ERR_INVALID_ARG: the common contract, n_claims == 0 or != the number of columns, a column_of_claim that is not a permutation, a point of another length, a value
+ * that is not canonical, a hint longer than 2^nu, T not a power of two; JOLT_ERR_SIZE_MISMATCH: columns of different cycle counts; JOLT_ERR_SRS_TOO_SMALL: 2^sigma
+ * above the setup's size; JOLT_ERR_UNSUPPORTED: beyond jolt_dory_fold_rows_grid's limits. */
+int32_t jolt_host_dory_prove_batch(jolt_ctx *ctx, const jolt_dory_setup *setup, const jolt_dory_vec *const *hints, const size_t *hint_first, const size_t *hint_rows,
+                                   size_t n_claims, const jolt_fr_t *evaluations, const jolt_onehot *const *sources, size_t n_sources, jolt_table *const *dense,
+                                   size_t n_dense, uint32_t log_k, const size_t *column_of_claim, const jolt_fr_t *point, size_t n_point, jolt_host_transcript *t,
+                                   jolt_gt_t *gts, jolt_g1_t *g1s, jolt_g2_t *g2s, jolt_fr_t *challenges_out, jolt_fr_t *scalars_out /* n_claims */,
+                                   jolt_fr_t *joint_eval_out);
 /* sigma > 30 is JOLT_ERR_INVALID_ARG; any of the four pointers may be NULL */
 int32_t jolt_host_dory_proof_counts(uint32_t sigma, size_t *n_gt, size_t *n_g1, size_t *n_g2, size_t *n_challenges);
 /* ark-serialize's compressed forms on the host.  G2: x.c0 then x.c1, 32 little-endian bytes of the canonical value each; the top two bits of the last byte hold the
@@ -953,6 +984,16 @@ int32_t jolt_grid_commit_onehot(jolt_ctx *ctx, const jolt_srs *srs, const jolt_o
 int32_t jolt_grid_joint_polynomial(jolt_ctx *ctx, const jolt_onehot *const *sources, size_t n_sources, const jolt_fr_t *onehot_scalars,
                                    jolt_table *const *dense, size_t n_dense, const jolt_fr_t *dense_scalars, uint32_t log_k,
                                    jolt_table **out);
+/* The claims of a stage-8 statement from one pass over the witness: claims_out[c] = the multilinear evaluation of column c of that grid at `point`, for the
+ * columns jolt_dory_fold_rows_grid and jolt_grid_joint_polynomial take, in their order (one-hot columns source by source, then dense):
+ *   one-hot p:  sum over the hot cycles j of eq_a[hot_p(j)] * eq_c[j]        dense d:  eq_a[0] * sum_j eq_c[j] * dense[d][j]
+ * with eq_a = eq(point[:log_k]) and eq_c = eq(point[log_k:]); point has log_k + log2(T) coordinates, most significant first, as jolt_eq_evals indexes.  One launch over
+ * the columns and a small one that adds the workgroups' partial sums (no atomics: the claims do not depend on the grid); the claims are downloaded before the call
+ * returns.  Everything is checked before anything is enqueued: JOLT_ERR_INVALID_ARG for a null pointer, a source or table of another context, T not a power of two,
+ * n_point != log_k + log2(T), a coordinate that is not canonical, source->k > 2^log_k; JOLT_ERR_SIZE_MISMATCH for columns of different cycle counts;
+ * JOLT_ERR_UNSUPPORTED beyond the limits of jolt_grid_joint_polynomial (4 sources, 8 dense columns, log_k <= 8, at least one column). */
+int32_t jolt_grid_evaluate_columns(jolt_ctx *ctx, const jolt_onehot *const *sources, size_t n_sources, jolt_table *const *dense, size_t n_dense, uint32_t log_k,
+                                   const jolt_fr_t *point, size_t n_point, jolt_fr_t *claims_out /* one per column */);
 
 /* Instruction read+RAF checking (stage 5) -- SURVEY.md section 8(f) row 4.  Replaces the T-scale scans of
  * OptimizedInstructionReadRafKernel (crates/jolt-kernels/src/optimized/instruction_read_raf.rs): per prefix-suffix phase the

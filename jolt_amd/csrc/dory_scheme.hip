@@ -10,12 +10,15 @@
 // per-lane functions are naf_mul / scale_add_one and the field fold of dory_kernels.hip.h, so the vectors hold what the separate calls write.
 // The opening (open_impl) is host control flow over those entries: the protocol of jolt_amd/dory_open.py and dory_reduce.py, with the challenges drawn through a
 // callback after each message.  Every exit drains the streams before the state vectors go back to the pool (OpenState's destructor).
+// The batch opening of stage 8 (jolt_host_dory_prove_batch) is HomomorphicBatch::prove_batch around it: the statement's framing (host_mirror.hip), the eq tables of the
+// point, the lazy row fold under gamma's powers, the check <v, R> == joint_eval, open_impl with the hints weighted by the same powers, the closing claim.
 #include <vector>
 
 #include "ctx.hpp"
 #include "dory_host.hpp"
 #include "dory_kernels.hip.h"
 #include "dory_prepared.hip.h"
+#include "onehot.hpp"
 
 using namespace jolt;
 using namespace jolt::dory_host;
@@ -433,4 +436,101 @@ extern "C" int32_t jolt_host_dory_open(jolt_ctx* ctx, const jolt_dory_setup* set
                                        uint32_t sigma, jolt_host_transcript* t, jolt_gt_t* gts, jolt_g1_t* g1s, jolt_g2_t* g2s, jolt_fr_t* challenges_out) {
     if (!t) return JOLT_ERR_INVALID_ARG;
     return open_impl(ctx, setup, hints, hint_first, hint_rows, n_hints, scalars, v_table, left, right, nu, sigma, engine_fn, t, gts, g1s, g2s, challenges_out);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the batch opening of stage 8
+namespace {
+
+// the tables one batch opening makes (L, R, v).  As OpenState: the streams are drained before the blocks go back to the pool.
+struct BatchTables {
+    jolt_ctx* ctx;
+    jolt_table *left = nullptr, *right = nullptr, *v = nullptr;
+    explicit BatchTables(jolt_ctx* c) : ctx(c) {}
+    ~BatchTables() {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (hipStream_t st : ctx->side)
+            if (st) (void)hipStreamSynchronize(st);
+        for (jolt_table* x : {left, right, v})
+            if (x) (void)jolt_table_free(ctx, x);
+    }
+};
+
+// eq(r[0 .. n)) as a device table; n = 0 is the table (1)
+int32_t eq_table(jolt_ctx* ctx, const jolt_fr_t* r, size_t n, jolt_table** out) {
+    if (n) return jolt_eq_evals(ctx, r, n, nullptr, out);
+    jolt_fr_t one;
+    fr_to_abi(&one, Fr::one());
+    return jolt_table_upload(ctx, &one, 1, out);
+}
+
+}  // namespace
+
+extern "C" int32_t jolt_host_dory_prove_batch(jolt_ctx* ctx, const jolt_dory_setup* setup, const jolt_dory_vec* const* hints, const size_t* hint_first, const size_t* hint_rows,
+                                              size_t n_claims, const jolt_fr_t* evaluations, const jolt_onehot* const* sources, size_t n_sources, jolt_table* const* dense,
+                                              size_t n_dense, uint32_t log_k, const size_t* column_of_claim, const jolt_fr_t* point, size_t n_point, jolt_host_transcript* t,
+                                              jolt_gt_t* gts, jolt_g1_t* g1s, jolt_g2_t* g2s, jolt_fr_t* challenges_out, jolt_fr_t* scalars_out, jolt_fr_t* joint_eval_out) {
+    if (!ctx || !setup || !hints || !hint_first || !hint_rows || !evaluations || !point || !t || !gts || !g1s || !g2s || !challenges_out || !scalars_out || !joint_eval_out ||
+        (n_sources && !sources) || (n_dense && !dense))
+        return JOLT_ERR_INVALID_ARG;
+    // ---- every check of this entry, of the row fold and of the opening, before the transcript absorbs anything and before anything is enqueued ----
+    JOLT_REQUIRE(ctx, setup->ctx == ctx, "the setup belongs to another context");
+    JOLT_REQUIRE(ctx, n_claims != 0, "an empty batch");  // HomomorphicBatchStatement::new refuses it
+    if (n_sources > 4 || n_dense > 8 || log_k > 8 || n_claims > (size_t)0x00FFFFFFu) return JOLT_ERR_UNSUPPORTED;  // the limits of jolt_dory_fold_rows_grid and of the hint combination
+    for (size_t s = 0; s < n_sources; ++s) JOLT_REQUIRE(ctx, sources[s] && sources[s]->ctx == ctx, "a source is null or of another context");
+    for (size_t d = 0; d < n_dense; ++d) JOLT_REQUIRE(ctx, dense[d] && dense[d]->ctx == ctx && dense[d]->data(), "a dense column is null or of another context");
+    JOLT_REQUIRE(ctx, n_sources + n_dense != 0, "a batch has at least one column");
+    const size_t T = n_sources ? sources[0]->cycles : dense[0]->len;
+    JOLT_REQUIRE(ctx, T != 0 && (T & (T - 1)) == 0, "the cycle count must be a power of two");
+    size_t log_t = 0, n_onehot = 0;
+    while (((size_t)1 << log_t) < T) ++log_t;
+    for (size_t s = 0; s < n_sources; ++s) {
+        if (sources[s]->cycles != T) return JOLT_ERR_SIZE_MISMATCH;
+        JOLT_REQUIRE(ctx, sources[s]->k <= (1u << log_k), "a hot address outside the grid");
+        n_onehot += sources[s]->n_polys;
+    }
+    for (size_t d = 0; d < n_dense; ++d)
+        if (dense[d]->len != T) return JOLT_ERR_SIZE_MISMATCH;
+    JOLT_REQUIRE(ctx, n_claims == n_onehot + n_dense, "one claim per column of the joint polynomial");
+    JOLT_REQUIRE(ctx, n_point == (size_t)log_k + log_t, "the point has log_k + log_t coordinates");
+    const uint32_t sigma = (uint32_t)((n_point + 1) / 2), nu = (uint32_t)n_point - sigma;  // crates/jolt-dory/src/scheme.rs:242-243
+    JOLT_REQUIRE(ctx, sigma <= kMaxSigma, "sigma <= 30");
+    const size_t rows = (size_t)1 << nu, n = (size_t)1 << sigma;
+    if (n > setup->n) {
+        ctx->last_error = "the setup holds fewer than 2^sigma bases";
+        return JOLT_ERR_SRS_TOO_SMALL;
+    }
+    for (size_t i = 0; i < n_claims; ++i)
+        JOLT_REQUIRE(ctx, view_ok(ctx, hints[i], JOLT_DORY_KIND_G1, hint_first[i], hint_rows[i]) && hint_rows[i] <= rows, "a hint is a G1 view of this context of at most 2^nu rows");
+    JOLT_REQUIRE(ctx, all_canonical(evaluations, n_claims) && all_canonical(point, n_point), "an evaluation or a coordinate is not a canonical Fr");
+    std::vector<size_t> column(n_claims);
+    {
+        std::vector<uint8_t> seen(n_claims, 0);
+        for (size_t i = 0; i < n_claims; ++i) {
+            const size_t c = column_of_claim ? column_of_claim[i] : i;
+            JOLT_REQUIRE(ctx, c < n_claims && !seen[c], "column_of_claim is not a permutation of the columns");
+            seen[c] = 1;
+            column[i] = c;
+        }
+    }
+    // ---- the statement: rlc_claims, the evaluations, gamma's powers; joint_eval = sum_i gamma^i y_i ----
+    JOLT_TRY(jolt_host_opening_statement_absorb(t, evaluations, n_claims, scalars_out));
+    Fr joint = Fr::zero();
+    for (size_t i = 0; i < n_claims; ++i) joint = add(joint, mul(fr_from_abi(&scalars_out[i]), fr_from_abi(&evaluations[i])));
+    fr_to_abi(joint_eval_out, joint);
+    std::vector<jolt_fr_t> by_column(n_claims);  // the row fold takes its scalars in column order
+    for (size_t i = 0; i < n_claims; ++i) by_column[column[i]] = scalars_out[i];
+    // ---- L = eq(point[:nu]), R = eq(point[nu:]), v = L^T M by the lazy row fold ----
+    BatchTables tb(ctx);
+    JOLT_TRY(eq_table(ctx, point, nu, &tb.left));
+    JOLT_TRY(eq_table(ctx, point + nu, sigma, &tb.right));
+    JOLT_TRY(jolt_dory_fold_rows_grid(ctx, sources, n_sources, by_column.data(), dense, n_dense, by_column.data() + n_onehot, log_k, sigma, tb.left, &tb.v));
+    // ---- <v, R> is the joint polynomial's evaluation at the point: a statement that does not hold is refused here, before any state vector is built ----
+    jolt_fr_t y;
+    JOLT_TRY(jolt_table_dot(ctx, tb.v, tb.right, 0, &y));
+    if (!(fr_from_abi(&y) == joint)) {
+        ctx->last_error = "the claimed evaluations do not combine to the joint polynomial's evaluation at the point";
+        return JOLT_ERR_ROUND_CHECK;
+    }
+    JOLT_TRY(open_impl(ctx, setup, hints, hint_first, hint_rows, n_claims, scalars_out, tb.v, tb.left, tb.right, nu, sigma, engine_fn, t, gts, g1s, g2s, challenges_out));
+    return jolt_host_opening_claim_absorb(t, point, n_point, joint_eval_out);
 }

@@ -1175,6 +1175,35 @@ extern "C" int32_t jolt_host_transcript_destroy(jolt_host_transcript* t) {
     return JOLT_OK;
 }
 
+// ---- the framing of a homomorphic batch opening (HomomorphicBatch::prove_batch, crates/jolt-openings/src/schemes.rs:487-524), the same for every scheme:
+// the statement before the scheme's own messages, the closing claim after them.  Both validate everything before the first append, so a refused call leaves
+// the transcript where it was.
+extern "C" int32_t jolt_host_opening_statement_absorb(jolt_host_transcript* t, const jolt_fr_t* evaluations, size_t n, jolt_fr_t* powers_out) {
+    if (!t || !evaluations || !powers_out || n == 0) return JOLT_ERR_INVALID_ARG;  // an empty batch: HomomorphicBatchStatement::new refuses it
+    for (size_t i = 0; i < n; ++i)
+        if (!fr_is_canonical(fr_from_abi(&evaluations[i]))) return JOLT_ERR_INVALID_ARG;
+    t->t.append_label_with_count("rlc_claims", n);  // VerifierRlcClaims (claims.rs:79-88)
+    for (size_t i = 0; i < n; ++i) t->t.append_fr(fr_from_abi(&evaluations[i]));
+    const Fr gamma = t->t.challenge_scalar();  // challenge_scalar_powers (legacy.rs:82-91): ONE challenge, then its powers
+    Fr power = Fr::one();
+    for (size_t i = 0; i < n; ++i) {
+        fr_to_abi(&powers_out[i], power);
+        power = mul(power, gamma);
+    }
+    return JOLT_OK;
+}
+extern "C" int32_t jolt_host_opening_claim_absorb(jolt_host_transcript* t, const jolt_fr_t* point, size_t n_vars, const jolt_fr_t* value) {
+    if (!t || (!point && n_vars) || !value) return JOLT_ERR_INVALID_ARG;
+    for (size_t i = 0; i < n_vars; ++i)
+        if (!fr_is_canonical(fr_from_abi(&point[i]))) return JOLT_ERR_INVALID_ARG;
+    if (!fr_is_canonical(fr_from_abi(value))) return JOLT_ERR_INVALID_ARG;
+    t->t.append_label_with_count("opening_point", n_vars);  // EvaluationClaim (claims.rs:23-35)
+    for (size_t i = 0; i < n_vars; ++i) t->t.append_fr(fr_from_abi(&point[i]));
+    t->t.append_label("opening_eval");
+    t->t.append_fr(fr_from_abi(value));
+    return JOLT_OK;
+}
+
 extern "C" int32_t jolt_host_gruen_poly_from_q(const jolt_fr_t* current_scalar, const jolt_fr_t* point_i, const jolt_fr_t* q_evals, size_t dq,
                                                const jolt_fr_t* s0_plus_s1, jolt_fr_t* coeffs_out) {
     if (!current_scalar || !point_i || !q_evals || !s0_plus_s1 || !coeffs_out || dq < 1 || dq > 8) return JOLT_ERR_INVALID_ARG;

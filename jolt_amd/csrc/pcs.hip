@@ -238,6 +238,73 @@ __global__ __launch_bounds__(kBlock) void k_promote_ints(const void* __restrict_
     }
 }
 
+// ---- the statement's claims: every committed column's evaluation at the opening point, from ONE pass over the witness ----
+// A column of the cycle-major grid evaluates to  sum_j eq_a[hot(j)] * eq_c[j]  (one-hot, over its hot cycles)  or  eq_a[0] * sum_j eq_c[j] * dense[j]  (dense, at
+// address 0), with eq_a / eq_c the eq tables of the address / cycle part of the point.  blockIdx.y names a GROUP of at most kEvalCols columns of one source (or of
+// the dense columns): a lane loads eq_c[j] once and serves the group's columns from it, eq_a sits in LDS.  kEvalCols is the register budget, not the source's width:
+// an accumulator is eight words, four of them beside eq_c[j] and a product in flight stay clear of the 128-VGPR step at which a workgroup's waves per SIMD halve; the
+// 32 columns of an instruction source are eight groups.  No atomics: a workgroup's kEvalCols sums go to partials[(group * gridDim.x + block) * kEvalCols + slot] and
+// k_grid_eval_sum adds them, so the claims are the same field elements for every grid.
+constexpr int kEvalCols = 4;
+struct EvalGroup {
+    int source;             // < 0: dense columns
+    uint32_t first, count;  // columns [first, first + count) of the source (of the dense list)
+};
+__device__ __forceinline__ EvalGroup eval_group(const JointArgs& a, uint32_t g) {
+    for (int s = 0; s < a.n_sources; ++s) {
+        const uint32_t groups = (a.n_polys[s] + kEvalCols - 1) / kEvalCols;
+        if (g < groups) return EvalGroup{s, g * kEvalCols, min((uint32_t)kEvalCols, a.n_polys[s] - g * kEvalCols)};
+        g -= groups;
+    }
+    return EvalGroup{-1, g * kEvalCols, min((uint32_t)kEvalCols, (uint32_t)a.n_dense - g * kEvalCols)};
+}
+__global__ __launch_bounds__(kBlock) void k_grid_eval_columns(JointArgs a, const Fr* __restrict__ eq_a, const Fr* __restrict__ eq_c, size_t cycles, uint32_t K,
+                                                              Fr* __restrict__ partials) {
+    __shared__ Fr s_eq_a[256];  // K <= 2^8
+    const EvalGroup g = eval_group(a, blockIdx.y);  // uniform over the workgroup
+    Fr acc[kEvalCols];
+#pragma unroll
+    for (int c = 0; c < kEvalCols; ++c) acc[c] = Fr::zero();
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    if (g.source >= 0) {
+        for (uint32_t k = threadIdx.x; k < K; k += kBlock) s_eq_a[k] = ld_fr(eq_a + k);
+        __syncthreads();
+        const uint8_t* idx = a.idx[g.source];
+        const uint32_t wide = a.wide[g.source];
+        for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < cycles; j += stride) {
+            const Fr e = ld_fr(eq_c + j);
+#pragma unroll
+            for (int c = 0; c < kEvalCols; ++c) {
+                if ((uint32_t)c < g.count) {
+                    const uint32_t h = hot_load(idx, (size_t)(g.first + c) * cycles + j, wide);
+                    if (h < K) acc[c] = add(acc[c], mul(s_eq_a[h], e));  // a cold cycle (kColdIdx) adds nothing
+                }
+            }
+        }
+    } else {
+        for (size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x; j < cycles; j += stride) {
+            const Fr e = ld_fr(eq_c + j);
+#pragma unroll
+            for (int c = 0; c < kEvalCols; ++c)
+                if ((uint32_t)c < g.count) acc[c] = add(acc[c], mul(ld_fr(a.dense[g.first + c] + j), e));
+        }
+        const Fr a0 = ld_fr(eq_a);  // dense columns live at address 0
+#pragma unroll
+        for (int c = 0; c < kEvalCols; ++c) acc[c] = mul(acc[c], a0);
+    }
+    block_reduce_store_at<kEvalCols>(acc, partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kEvalCols);
+}
+// one workgroup per (group, slot): out[column] = the sum of that slot over the group's n_blocks workgroups; columns in jolt_dory_fold_rows_grid's order
+__global__ __launch_bounds__(kBlock) void k_grid_eval_sum(JointArgs a, const Fr* __restrict__ partials, uint32_t n_blocks, uint32_t n_onehot, Fr* __restrict__ out) {
+    const uint32_t group = blockIdx.x / kEvalCols, c = blockIdx.x % kEvalCols;
+    const EvalGroup g = eval_group(a, group);
+    if (c >= g.count) return;  // uniform over the workgroup
+    Fr acc[1] = {Fr::zero()};
+    for (uint32_t b = threadIdx.x; b < n_blocks; b += kBlock) acc[0] = add(acc[0], ld_fr(partials + ((size_t)group * n_blocks + b) * kEvalCols + c));
+    const uint32_t column = g.source >= 0 ? a.first[g.source] + g.first + c : n_onehot + g.first + c;
+    block_reduce_store_at<1>(acc, out + column);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -565,4 +632,71 @@ static int32_t grid_joint_impl(jolt_ctx* ctx, const jolt_onehot* const* sources,
     if (e != hipSuccess) { jolt_table_free(ctx, r); ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
     *out = r;
     return JOLT_OK;
+}
+
+// The claims of a stage-8 statement (crates/jolt-prover/src/dory/stages/stage8.rs:148-162 before scaling): claims_out[column] = the multilinear evaluation of that
+// column of the cycle-major grid at `point`, columns in jolt_dory_fold_rows_grid's order.  Two launches (k_grid_eval_columns, k_grid_eval_sum) and one download.
+extern "C" int32_t jolt_grid_evaluate_columns(jolt_ctx* ctx, const jolt_onehot* const* sources, size_t n_sources, jolt_table* const* dense, size_t n_dense, uint32_t log_k,
+                                              const jolt_fr_t* point, size_t n_point, jolt_fr_t* claims_out) {
+    if (!ctx || !point || !claims_out || (n_sources && !sources) || (n_dense && !dense)) return JOLT_ERR_INVALID_ARG;
+    if (n_sources > (size_t)kJointMaxSources || n_dense > (size_t)kJointMaxDense || log_k > 8 || n_sources + n_dense == 0) return JOLT_ERR_UNSUPPORTED;
+    // ---- every check before anything is enqueued ----
+    const uint32_t K = 1u << log_k;
+    JointArgs a;
+    std::memset(&a, 0, sizeof(a));
+    for (size_t s = 0; s < n_sources; ++s) if (!sources[s] || sources[s]->ctx != ctx) return JOLT_ERR_INVALID_ARG;
+    for (size_t d = 0; d < n_dense; ++d) if (!dense[d] || dense[d]->ctx != ctx || !dense[d]->data()) return JOLT_ERR_INVALID_ARG;
+    const size_t T = n_sources ? sources[0]->cycles : dense[0]->len;
+    JOLT_REQUIRE(ctx, T != 0 && (T & (T - 1)) == 0, "evaluate_columns: the cycle count must be a power of two");
+    size_t log_t = 0;
+    while (((size_t)1 << log_t) < T) ++log_t;
+    JOLT_REQUIRE(ctx, n_point == (size_t)log_k + log_t, "evaluate_columns: the point has log_k + log_t coordinates");
+    for (size_t i = 0; i < n_point; ++i) JOLT_REQUIRE(ctx, fr_is_canonical(fr_from_abi(&point[i])), "evaluate_columns: a coordinate is not a canonical Fr");
+    size_t total = 0, groups = 0;
+    for (size_t s = 0; s < n_sources; ++s) {
+        if (sources[s]->cycles != T) return JOLT_ERR_SIZE_MISMATCH;
+        JOLT_REQUIRE(ctx, sources[s]->k <= K, "evaluate_columns: a hot address outside the grid");
+        a.idx[s] = sources[s]->idx;
+        a.wide[s] = sources[s]->wide;
+        a.n_polys[s] = (uint32_t)sources[s]->n_polys;
+        a.first[s] = (uint32_t)total;
+        total += sources[s]->n_polys;
+        groups += (sources[s]->n_polys + kEvalCols - 1) / kEvalCols;
+    }
+    a.n_sources = (int)n_sources;
+    for (size_t d = 0; d < n_dense; ++d) {
+        if (dense[d]->len != T) return JOLT_ERR_SIZE_MISMATCH;
+        a.dense[d] = dense[d]->data();
+    }
+    a.n_dense = (int)n_dense;
+    groups += (n_dense + kEvalCols - 1) / kEvalCols;
+    const size_t columns = total + n_dense;
+    if (groups == 0 || groups > 4096 || total > 0x00FFFFFFu) return JOLT_ERR_UNSUPPORTED;  // (a source without columns gives no group)
+    // a workgroup per 256 cycles, capped so that the launch stays near 2048 workgroups; a lane strides over the rest
+    const size_t n_blocks = std::max<size_t>(1, std::min<size_t>((T + kBlock - 1) / kBlock, std::max<size_t>(1, 2048 / groups)));
+
+    jolt_table *eq_a = nullptr, *eq_c = nullptr, *out = nullptr;
+    Fr* partials = nullptr;
+    const jolt_fr_t one = [] { jolt_fr_t o; fr_to_abi(&o, Fr::one()); return o; }();
+    int32_t st = log_k ? jolt_eq_evals(ctx, point, log_k, nullptr, &eq_a) : jolt_table_upload(ctx, &one, 1, &eq_a);
+    if (st == JOLT_OK) st = log_t ? jolt_eq_evals(ctx, point + log_k, log_t, nullptr, &eq_c) : jolt_table_upload(ctx, &one, 1, &eq_c);
+    if (st == JOLT_OK) st = jolt_internal_table_new(ctx, columns, &out);
+    if (st == JOLT_OK) st = jolt_internal_dev_alloc(ctx, groups * n_blocks * kEvalCols * sizeof(Fr), (void**)&partials);
+    if (st == JOLT_OK) {
+        hipLaunchKernelGGL(k_grid_eval_columns, dim3((unsigned)n_blocks, (unsigned)groups), dim3(kBlock), 0, ctx->stream, a, (const Fr*)eq_a->data(), (const Fr*)eq_c->data(), T, K,
+                           partials);
+        hipLaunchKernelGGL(k_grid_eval_sum, dim3((unsigned)(groups * kEvalCols)), dim3(kBlock), 0, ctx->stream, a, (const Fr*)partials, (uint32_t)n_blocks, (uint32_t)total,
+                           out->data());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("evaluate_columns: ") + hipGetErrorString(e);
+            st = JOLT_ERR_HIP;
+        } else {
+            st = jolt_table_download(ctx, out, 0, columns, claims_out);  // synchronises the stream
+        }
+    }
+    if (partials) jolt_internal_dev_free(ctx, partials);  // back to the pool: reuse is stream-ordered
+    for (jolt_table* t : {eq_a, eq_c, out})
+        if (t) jolt_table_free(ctx, t);
+    return st;
 }

@@ -1809,9 +1809,65 @@ def host_dory_transcript_append(transcript, element):
         raise ValueError("a GT element has 48 words, a G1 point 12, a G2 point 24")
 
 
+def host_opening_statement_absorb(transcript, evaluations):
+    """the statement of HomomorphicBatch::prove_batch into `transcript` (jolt_host_opening_statement_absorb): LabelWithCount(b"rlc_claims", n) and the n evaluations;
+    -> (n, 4) the RLC scalars 1, gamma, ..., gamma^(n - 1) of the ONE challenge_scalar that follows"""
+    v = fr(evaluations).reshape(-1, 4)
+    out = fr_array(max(v.shape[0], 1))
+    _ck(lib().jolt_host_opening_statement_absorb(transcript.h, _p(v), C.c_size_t(v.shape[0]), _p(out)), "jolt_host_opening_statement_absorb")
+    return out[:v.shape[0]]
+
+
+def host_opening_claim_absorb(transcript, point, value):
+    """the closing claim (jolt_host_opening_claim_absorb): LabelWithCount(b"opening_point", len(point)), the coordinates in order, Label(b"opening_eval"), the value"""
+    p = fr(point).reshape(-1, 4)
+    _ck(lib().jolt_host_opening_claim_absorb(transcript.h, _p(p) if p.shape[0] else None, C.c_size_t(p.shape[0]), _p(fr(value).reshape(4))), "jolt_host_opening_claim_absorb")
+
+
+def _dory_prove_batch(self, setup, hints, evaluations, sources, dense, log_k, point, transcript, column_of_claim=None):
+    """HomomorphicBatch::<DoryScheme>::prove_batch as one call (jolt_host_dory_prove_batch): setup a DoryLibSetup; hints one resident G1 view per claim; evaluations
+    (n, 4) as the statement holds them; sources / dense / log_k the joint polynomial's columns as dory_fold_rows_grid takes them; column_of_claim[i] = claim i's column
+    in that order (None: the identity); point: log_k + log T coordinates, most significant first; transcript a HostTranscript.
+    -> dict(gts, g1s, g2s, challenges, scalars, joint_eval, nu, sigma): the proof in protocol order, the RLC scalars 1, gamma, ... and sum_i scalars[i] evaluations[i]."""
+    views = [_dory_view(h) for h in hints]
+    hs, firsts, rows = _dory_view_arrays(views)
+    ev = fr(evaluations).reshape(-1, 4)
+    if ev.shape[0] != len(views):
+        raise ValueError("one evaluation per hint")
+    pt = fr(point).reshape(-1, 4)
+    sigma = (pt.shape[0] + 1) // 2
+    n_gt, n_g1, n_g2, n_ch = host_dory_proof_counts(sigma)
+    gts, g1s, g2s, ch = np.zeros((n_gt, 48), dtype=np.uint64), np.zeros((n_g1, 12), dtype=np.uint64), np.zeros((n_g2, 24), dtype=np.uint64), fr_array(n_ch)
+    scalars, joint = fr_array(max(len(views), 1)), fr_array(1)
+    ss = (C.c_void_p * max(len(sources), 1))(*[s.h for s in sources])
+    ds = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
+    order = None if column_of_claim is None else (C.c_size_t * max(len(column_of_claim), 1))(*[int(c) for c in column_of_claim])
+    if order is not None and len(column_of_claim) != len(views):
+        raise ValueError("one column per claim")
+    _ck(lib().jolt_host_dory_prove_batch(self.h, setup.h, hs, firsts, rows, C.c_size_t(len(views)), _p(ev), ss if sources else None, C.c_size_t(len(sources)),
+                                         ds if dense else None, C.c_size_t(len(dense)), C.c_uint32(log_k), order, _p(pt), C.c_size_t(pt.shape[0]), transcript.h,
+                                         _p(gts), _p(g1s), _p(g2s), _p(ch), _p(scalars), _p(joint)), "jolt_host_dory_prove_batch", self)
+    return dict(gts=gts, g1s=g1s, g2s=g2s, challenges=ch, scalars=scalars[:len(views)], joint_eval=joint[0], nu=pt.shape[0] - sigma, sigma=sigma)
+
+
+def _grid_evaluate_columns(self, sources, dense, log_k, point):
+    """the statement's claims from one pass over the witness (jolt_grid_evaluate_columns): (columns, 4), the multilinear evaluation at `point` of every column of the
+    cycle-major grid, in dory_fold_rows_grid's column order (one-hot columns source by source, then dense)"""
+    pt = fr(point).reshape(-1, 4)
+    n = sum(s.n_polys for s in sources) + len(dense)
+    out = fr_array(max(n, 1))
+    ss = (C.c_void_p * max(len(sources), 1))(*[s.h for s in sources])
+    ds = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
+    _ck(lib().jolt_grid_evaluate_columns(self.h, ss if sources else None, C.c_size_t(len(sources)), ds if dense else None, C.c_size_t(len(dense)), C.c_uint32(log_k),
+                                         _p(pt), C.c_size_t(pt.shape[0]), _p(out)), "jolt_grid_evaluate_columns", self)
+    return out[:n]
+
+
 Context.dory_setup_create = lambda self, gamma1, gamma2, h1, h2: DoryLibSetup(self, gamma1, gamma2, h1, h2)
 Context.dory_round_update = _dory_round_update
 Context.dory_open = _dory_open
+Context.dory_prove_batch = _dory_prove_batch
+Context.grid_evaluate_columns = _grid_evaluate_columns
 
 
 # ---- the witness commitment in front of an opening (dory.hip, dory_hints.hip.h): row commitments written on the device, normalised, in hint order

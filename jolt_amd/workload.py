@@ -237,10 +237,16 @@ class DeviceWorkload:
 
     pcs: None (sumcheck only: BASELINE configs[1]) or "grid" (configs[2]: every committed polynomial lives on the 2^(log_k + n_vars)
     commitment grid of crates/jolt-kernels/src/commitment.rs:86-130 -- the two dense increment columns at address 0, the one-hot
-    RA columns as 0/1 coefficients -- committed with HyperKZG and opened jointly at one point)."""
+    RA columns as 0/1 coefficients -- committed with HyperKZG and opened jointly at one point) or "dory" (the same columns over the same
+    grid under the reference's production scheme: commit() is a dory_commit.DoryWitnessCommitment -- resident tier-1 hints, tier 2 as one
+    product batch -- and open() is HomomorphicBatch::prove_batch as one library call, jolt_host_dory_prove_batch, over the statement's claims
+    `opening_claims`, which one launch over the witness columns computes at construction; dory_bases= plants the setup's bases, otherwise
+    jolt_amd/dory_setup.py generates 2^sigma per group from the seed)."""
 
     def __init__(self, ctx, n_vars, seed=2026, pcs=None, srs=None, fixed_base=True, extended=False, witness_upload=False, ram_addresses="uniform", **kw):
         from . import ffi
+        if pcs == "dory" and n_vars < 4:  # sigma = ceil((4 + n_vars) / 2) > n_vars: a matrix row wider than one address's cycles (refused before anything is uploaded)
+            raise ValueError("pcs='dory' needs n_vars >= 4")
         self.ctx, self.n_vars, self.ffi, self.pcs, self._seed = ctx, n_vars, ffi, pcs, seed
         # witness_upload: every step STARTS from the packed per-cycle rows in host memory (RowSource::rows() + WitnessBundle::from_row windows,
         # crates/jolt-witness/src/consumer.rs:129-143, crates/jolt-kernels/src/optimized/rows.rs:22-72): one H2D copy of the rows, the typed columns and hot
@@ -271,6 +277,7 @@ class DeviceWorkload:
             self.ext = DeviceExtended(self.ext_ctx or ctx, n_vars, seed, ram_addresses=ram_addresses)  # "hotset": a btreemap-like skewed RAM / register address stream
             for pool, slot_ctx in self._stage_slots:
                 pool.submit(lambda c=slot_ctx: (c.bind_thread(), self.ext.bind_context(c))).result()
+        dory_bases = kw.pop("dory_bases", None)  # pcs="dory": dict(gamma1, gamma2, h1, h2) of host arrays (jolt_amd/dory_setup.py); None: generated from the seed
         self.tables_spec, self.members_spec, gammas = build(n_vars, seed, **kw)
         one = ffi.host_fr_from_u64(1)
         zero = np.zeros(4, dtype=np.uint64)
@@ -336,6 +343,31 @@ class DeviceWorkload:
             self.rlc_onehot = rand_fr(n_oh, prng)
             self.rlc_dense = rand_fr(len(self.committed_dense), prng)
             self.open_point = rand_fr(self.grid_vars, prng)
+        elif pcs == "dory":
+            # The same committed columns over the same cycle-major grid, under the reference's production scheme: the grid is a 2^nu x 2^sigma matrix
+            # (crates/jolt-dory/src/scheme.rs:242-243) and the setup is 2^sigma bases per group -- built here, once, untimed, like the SRS of pcs="grid".
+            from . import dory_setup
+            from .dory_proof import DoryProofSetup
+            self.log_k = 4
+            assert all(len(self.tables_spec[t].point) == self.log_k for ms in self.members_spec if self._lazy(ms) for t in ms.tables[1:])
+            self.grid_vars = self.log_k + n_vars
+            self.committed_dense = ["s6.ram_inc", "s6.rd_inc"]
+            self.dory_sigma = (self.grid_vars + 1) // 2
+            self.dory_nu = self.grid_vars - self.dory_sigma
+            width = 1 << self.dory_sigma
+            bases = dory_setup.check(dory_bases) if dory_bases is not None else dory_setup.generate(ctx, width, seed + 2)
+            if bases["gamma1"].shape[0] < width:
+                raise ValueError("dory_bases holds fewer than 2^sigma bases per group")
+            # ONE setup object over the bases (jolt_dory_setup): the commitment's tier 2 goes through its prepared Gamma2 (DoryLibSetup.tier2) and the opening through
+            # the same handle, so the bases are uploaded here and never again.  The SRS handle is what the tier-1 hint kernels read Gamma1 through.
+            self.dory_bases = bases  # the host arrays: what a verifier of this workload's proofs is set up with
+            self.dory_setup = DoryProofSetup(ctx, bases["gamma1"], bases["gamma2"], bases["h1"], bases["h2"])
+            self.srs = ctx.srs_upload(bases["gamma1"][:width])
+            self.own_srs = True
+            self.dory_commitment = None
+            prng = np.random.default_rng(seed + 3)
+            self.open_point = rand_fr(self.grid_vars, prng)
+            self.column_of_claim = None  # the batch order is the caller's (final_opening_polynomial_order); None: the column order
         elif pcs is not None:
             raise ValueError(pcs)
         self.tables, self.members, self.prepared, self.hint = {}, [], False, None
@@ -343,6 +375,9 @@ class DeviceWorkload:
         ctx.synchronize()
         # input claims: in the real prover these are the previous stage's output claims; here computed once, untimed
         self.claims = [m.input_claim() for m in self.members]
+        if pcs == "dory":
+            # the statement of stage 8: every committed column's evaluation at the unified opening point, from one launch over the witness columns
+            self.opening_claims = self.evaluate_columns()
 
     # ---- per-proof tables -------------------------------------------------------------------------------------------
     def _scale_table(self, spec):
@@ -515,6 +550,9 @@ class DeviceWorkload:
         return int(self._packed.shape[1])
 
     def release(self):
+        if getattr(self, "dory_commitment", None) is not None:  # pcs="dory": this proof's hints go with its tables
+            self.dory_commitment.close()
+            self.dory_commitment = None
         for m in self.members:
             m.destroy()
         self.members = []
@@ -668,7 +706,9 @@ class DeviceWorkload:
 
     def commit(self):
         """Stage 0 over the commitment grid: dense increment columns = T-term MSMs of 64-bit scalars against the SRS prefix (address 0),
-        one-hot columns = sums of selected bases."""
+        one-hot columns = sums of selected bases.  pcs="dory": dory_commit."""
+        if self.pcs == "dory":
+            return self.dory_commit()
         ctx, T = self.ctx, 1 << self.n_vars
         # the dense columns' MSMs go in flight on the side lanes (short: bound by the latency of their sort and reduction chains) and are collected after the one-hot
         # sums of bases have run on the main stream (bound by multiplications); a context that cannot hold them in flight: one after the other
@@ -704,7 +744,9 @@ class DeviceWorkload:
 
     def open(self, label=0):
         """Stage 8: joint polynomial of the homomorphic batch, one HyperKZG opening at the unified point; the first level commitments by linearity from the opening hint
-        the commit leg left in flight (jolt_host_hyperkzg_open_grid) -- begun here if this proof has none"""
+        the commit leg left in flight (jolt_host_hyperkzg_open_grid) -- begun here if this proof has none.  pcs="dory": dory_open."""
+        if self.pcs == "dory":
+            return self.dory_open(label)
         joint = self.joint_polynomial()
         levels = self.linear_levels()
         if levels and self.hint is None:
@@ -718,6 +760,72 @@ class DeviceWorkload:
             self.hint.free()
             self.hint = None
         joint.free()
+        return out
+
+    # ---- pcs="dory": the same columns under the reference's production scheme ------------------------------------------------------------------------------
+    def _dory_columns(self):
+        """(sources, dense field tables): the joint polynomial's columns in jolt_dory_fold_rows_grid's order"""
+        return [self.sources[i] for i in sorted(self.sources)], [self.tables[name] for name in self.committed_dense]
+
+    def evaluate_columns(self):
+        """(columns, 4): every committed column's evaluation at open_point, ONE launch over the witness columns (jolt_grid_evaluate_columns)"""
+        if not self.prepared:
+            self.prepare()
+        sources, dense = self._dory_columns()
+        return self.ctx.grid_evaluate_columns(sources, dense, self.log_k, self.open_point)
+
+    def evaluate_columns_pushforward(self):
+        """the same claims by the route that preceded that entry, kept as the second implementation the tests hold it against: per source one
+        jolt_onehot_pushforward of the cycles' eq table, its K-entry masses downloaded and dotted with the addresses' eq table on the host; a dense column is
+        eq_a[0] * <eq_c, column>"""
+        if not self.prepared:
+            self.prepare()
+        ffi, ctx = self.ffi, self.ctx
+        sources, dense = self._dory_columns()
+        eq_a = ffi.host_eq_evals(self.open_point[:self.log_k])
+        eq_c = ctx.eq_evals(self.open_point[self.log_k:])
+        out = []
+        try:
+            for s in sources:
+                masses = s.pushforward(eq_c)
+                g = masses.download().reshape(s.n_polys, s.k, 4)
+                masses.free()
+                out += [ffi.host_fr_wide_dot(g[p], eq_a[:s.k]) for p in range(s.n_polys)]
+            for t in dense:
+                out.append(ffi.host_fr_mul(ctx.table_dot(t, eq_c), eq_a[0]))
+        finally:
+            eq_c.free()
+        return np.stack(out)
+
+    def dory_commit(self):
+        """Stage 0 under Dory: tier 1 into resident hints (one jolt_dory_hints_onehot per source, one jolt_dory_hints_rows per integer column), tier 2 as ONE product
+        batch against the setup's prepared Gamma2.  The commitment object stays as this proof's opening hint.  -> dict(tier2=(columns, 48))"""
+        from .dory_commit import DoryWitnessCommitment
+        if self.dory_commitment is not None:  # a hint nobody released
+            self.dory_commitment.close()
+            self.dory_commitment = None
+        sources = [self.sources[i] for i in sorted(self.sources)]
+        self.dory_commitment = DoryWitnessCommitment(self.dory_setup, self.srs, sources, [self.ints[name] for name in self.committed_dense], self.dory_sigma)
+        return dict(tier2=np.stack(self.dory_setup.tier2(self.dory_commitment.hints)))
+
+    def dory_open(self, label=0, evaluations=None, column_of_claim=None):
+        """Stage 8 under Dory: HomomorphicBatch::prove_batch as ONE call of the library (jolt_host_dory_prove_batch) under a transcript of the label's engine -- the
+        statement, gamma's powers, the row fold, the check <v, R> == joint_eval, the evaluation proof, the closing claim.  evaluations / column_of_claim: the
+        statement's claims and their batch order (default: opening_claims in self.column_of_claim's order; claim i is column column_of_claim[i]).
+        -> what Context.dory_prove_batch returns + transcript_state (32 bytes, after the closing claim)"""
+        if self.dory_commitment is None:
+            self.dory_commit()
+        order = self.column_of_claim if column_of_claim is None else column_of_claim
+        hints = self.dory_commitment.hints if order is None else [self.dory_commitment.hints[c] for c in order]
+        if evaluations is None:
+            evaluations = self.opening_claims if order is None else self.opening_claims[list(order)]
+        sources, dense = self._dory_columns()
+        transcript = self.ffi.HostTranscript(label)
+        try:
+            out = self.ctx.dory_prove_batch(self.dory_setup, hints, evaluations, sources, dense, self.log_k, self.open_point, transcript, column_of_claim=order)
+            out["transcript_state"] = transcript.state()
+        finally:
+            transcript.close()
         return out
 
     def step(self, label=0):
@@ -772,6 +880,9 @@ class DeviceWorkload:
         if self.own_srs and self.srs is not None:
             self.srs.free()
             self.srs = None
+        if getattr(self, "dory_setup", None) is not None:
+            self.dory_setup.close()
+            self.dory_setup = None
 
 
 # BN254 G1 generator (1, 2) as Montgomery Jacobian limbs (ark_bn254::G1Projective layout): R mod q, 2R mod q, R mod q

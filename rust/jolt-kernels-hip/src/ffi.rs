@@ -362,6 +362,8 @@ extern "C" {
     pub fn jolt_host_transcript_challenge(t: *mut jolt_host_transcript, full_width: i32, out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_transcript_state(t: *const jolt_host_transcript, out32: *mut u8) -> i32;
     pub fn jolt_host_transcript_destroy(t: *mut jolt_host_transcript) -> i32;
+    pub fn jolt_host_opening_statement_absorb(t: *mut jolt_host_transcript, evaluations: *const jolt_fr_t, n: usize, powers_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_opening_claim_absorb(t: *mut jolt_host_transcript, point: *const jolt_fr_t, n_vars: usize, value: *const jolt_fr_t) -> i32;
     pub fn jolt_host_blake2b(r#in: *const u8, n: usize, outlen: usize, out: *mut u8) -> i32;
     pub fn jolt_host_keccak_f1600(state200: *mut u8) -> i32;
     pub fn jolt_host_g1_add(p: *const jolt_g1_t, q: *const jolt_g1_t, out: *mut jolt_g1_t) -> i32;
@@ -484,6 +486,7 @@ extern "C" {
     pub fn jolt_dory_round_update(ctx: *mut jolt_ctx, mode: i32, v1: *mut jolt_dory_vec, v1_first: usize, v2: *mut jolt_dory_vec, v2_first: usize, a: *mut jolt_dory_vec, a_first: usize, b: *mut jolt_dory_vec, b_first: usize, n: usize, scalar: *const jolt_fr_t, scalar_inv: *const jolt_fr_t) -> i32;
     pub fn jolt_host_dory_open_with_transcript(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, v_table: *const jolt_table, left: *const jolt_table, right: *const jolt_table, nu: u32, sigma: u32, r#fn: jolt_dory_transcript_fn, user: *mut c_void, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_dory_open(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, v_table: *const jolt_table, left: *const jolt_table, right: *const jolt_table, nu: u32, sigma: u32, t: *mut jolt_host_transcript, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_dory_prove_batch(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_claims: usize, evaluations: *const jolt_fr_t, sources: *const *const jolt_onehot, n_sources: usize, dense: *const *mut jolt_table, n_dense: usize, log_k: u32, column_of_claim: *const usize, point: *const jolt_fr_t, n_point: usize, t: *mut jolt_host_transcript, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t, scalars_out: *mut jolt_fr_t, joint_eval_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_dory_proof_counts(sigma: u32, n_gt: *mut usize, n_g1: *mut usize, n_g2: *mut usize, n_challenges: *mut usize) -> i32;
     pub fn jolt_host_g2_serialize_compressed(p: *const jolt_g2_t, out: *mut u8) -> i32;
     pub fn jolt_host_gt_serialize(f: *const jolt_gt_t, out: *mut u8) -> i32;
@@ -493,6 +496,7 @@ extern "C" {
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_grid_evaluate_columns(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, dense: *const *mut jolt_table, n_dense: usize, log_k: u32, point: *const jolt_fr_t, n_point: usize, claims_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_read_raf_create(ctx: *mut jolt_ctx, lookup_index: *const u64, table_index: *const u8, raf_flag: *const u8, cycles: usize, n_tables: u32, out: *mut *mut jolt_read_raf) -> i32;
     pub fn jolt_read_raf_destroy(ctx: *mut jolt_ctx, rr: *mut jolt_read_raf) -> i32;
     pub fn jolt_read_raf_cycles(rr: *const jolt_read_raf, cycles: *mut usize, n_tables: *mut u32) -> i32;
