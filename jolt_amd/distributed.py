@@ -23,13 +23,13 @@ import os
 
 import numpy as np
 
-from . import ffi
+from . import abi, ffi
 from . import workload as W
 
 KIND_EXPR, KIND_EXPR_SKIP, KIND_SPLIT_EQ, KIND_SPLIT_EQ_UNIFORM = 0, 1, 2, 3
 
-LOCAL_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t)
-GATHER_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+LOCAL_FN = abi.CALLBACK_TYPES["jolt_local_round_fn"]
+GATHER_FN = abi.CALLBACK_TYPES["jolt_gather_fn"]
 
 
 def _p(a):
@@ -45,7 +45,7 @@ class ShmExchange:
     def __init__(self, name, rank, world, max_bytes=MAX_BYTES, nonce=0):
         self.rank, self.world = rank, world
         h = C.c_void_p()
-        st = ffi.lib().jolt_shm_create_nonce(name.encode(), C.c_uint64(nonce), C.c_int32(rank), C.c_int32(world), C.c_size_t(max_bytes), C.byref(h))
+        st = ffi.lib().jolt_shm_create_nonce(name.encode(), nonce, rank, world, max_bytes, C.byref(h))
         if st:
             raise ffi.JoltError(st, "jolt_shm_create_nonce")
         self.h = h
@@ -53,7 +53,7 @@ class ShmExchange:
     def all_gather_u64(self, arr):
         flat = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1)
         out = np.empty(self.world * flat.size, dtype=np.uint64)
-        st = ffi.lib().jolt_shm_all_gather(self.h, _p(flat), C.c_size_t(flat.nbytes), _p(out))
+        st = ffi.lib().jolt_shm_all_gather(self.h, _p(flat), flat.nbytes, _p(out))
         if st:
             raise ffi.JoltError(st, "jolt_shm_all_gather")
         return out.reshape(self.world, -1)
@@ -170,7 +170,7 @@ class NativeCollective:
         saved = os.dup(1)
         os.dup2(2, 1)
         try:
-            st = lib.jolt_comm_create(ctx.h, self._path, uid, C.c_int32(rank), C.c_int32(world), C.byref(h))
+            st = lib.jolt_comm_create(ctx.h, self._path, uid, rank, world, C.byref(h))
         finally:
             libc.fflush(None)
             os.dup2(saved, 1)
@@ -182,13 +182,13 @@ class NativeCollective:
     def all_gather_u64(self, arr):
         flat = np.ascontiguousarray(arr, dtype=np.uint64).reshape(-1)
         out = np.empty(self.world * flat.size, dtype=np.uint64)
-        st = ffi.lib().jolt_comm_all_gather_host(self.h, _p(flat), C.c_size_t(flat.nbytes), _p(out))
+        st = ffi.lib().jolt_comm_all_gather_host(self.h, _p(flat), flat.nbytes, _p(out))
         if st:
             ffi._ck(st, "jolt_comm_all_gather_host", self.ctx)
         return out.reshape(self.world, -1)
 
     def all_gather_table(self, local, n, gathered):
-        st = ffi.lib().jolt_comm_all_gather_table(self.h, local.h, C.c_size_t(n), gathered.h)
+        st = ffi.lib().jolt_comm_all_gather_table(self.h, local.h, n, gathered.h)
         if st:
             ffi._ck(st, "jolt_comm_all_gather_table", self.ctx)
 
@@ -256,8 +256,8 @@ def prove_batch_sharded(ctx_handle, infos, claims, coeffs, n_total, n_local, max
     one = ffi.host_fr_from_u64(1)
     scales = np.ascontiguousarray(np.stack([one if i.scale is None else np.asarray(i.scale, dtype=np.uint64) for i in infos]))
     batch = C.c_void_p()
-    st = lib.jolt_host_batch_begin(ctx_handle, C.c_size_t(n), _p(ic), _p(co), rounds, offsets, kinds, degs, w_ptrs, _p(scales),
-                                   C.c_size_t(n_total), C.c_size_t(max_degree), C.c_uint64(label), C.c_int32(challenge_mode), C.byref(batch))
+    st = lib.jolt_host_batch_begin(ctx_handle, n, _p(ic), _p(co), rounds, offsets, kinds, degs, w_ptrs, _p(scales),
+                                   n_total, max_degree, label, challenge_mode, C.byref(batch))
     if st:
         raise ffi.JoltError(st, "jolt_host_batch_begin")
     state = {"backend": shard, "err": None}
@@ -302,7 +302,7 @@ def prove_batch_sharded(ctx_handle, infos, claims, coeffs, n_total, n_local, max
         gather, user = (None, None)
         if w > 1 or (force_gather and exchange):  # force_gather: run the exchange even with a single rank
             gather, user = (native_gather, native_user) if native_gather is not None else (gcb, None)
-        st = lib.jolt_host_batch_run(batch, handles, C.c_size_t(n_rounds), C.c_int32(w), gather, None if handles is not None else lcb, user)
+        st = lib.jolt_host_batch_run(batch, handles, n_rounds, w, gather, None if handles is not None else lcb, user)
         if st:
             if state["err"] is not None:
                 raise state["err"]
@@ -334,7 +334,7 @@ def prove_batch_sharded(ctx_handle, infos, claims, coeffs, n_total, n_local, max
         for i, info in enumerate(infos):
             if info.kind in (KIND_SPLIT_EQ, KIND_SPLIT_EQ_UNIFORM):
                 o = ffi.fr_array(1)
-                lib.jolt_host_batch_split_eq_scalar(batch, C.c_size_t(i), _p(o))
+                lib.jolt_host_batch_split_eq_scalar(batch, i, _p(o))
                 scalars.append(o[0])
             else:
                 scalars.append(None)
@@ -381,7 +381,7 @@ class DeviceShard:
         hs = (C.c_void_p * len(ms))(*[m.h for m in ms])
         store = [ffi.fr(b) for b in bs]
         bp = (C.c_void_p * len(ms))(*[b.ctypes.data for b in store])
-        st = ffi.lib().jolt_round_group_finish(self.ctx.h, hs, C.c_size_t(len(ms)), bp)
+        st = ffi.lib().jolt_round_group_finish(self.ctx.h, hs, len(ms), bp)
         if st:
             raise ffi.JoltError(st, "jolt_round_group_finish")
 
@@ -445,7 +445,7 @@ class _TailShard(DeviceShard):
         self.tail_members, self.keep = None, []
 
     def make_tail(self, coll, scalars):
-        ctx, world, lib = self.ctx, self.world, ffi.lib()
+        ctx, world = self.ctx, self.world
         log_g = world.bit_length() - 1
         E = 1 << self.tail_log
         n_tab = sum(m.n_tables for m in self.members)
@@ -453,19 +453,19 @@ class _TailShard(DeviceShard):
         pack, gath, arena = ctx.alloc(n_tab * E), ctx.alloc(world * n_tab * E), ctx.alloc(world * n_tab * E)
         self.keep += [pack, gath, arena]
         hs = (C.c_void_p * len(self.members))(*[m.h for m in self.members])
-        ffi._ck(lib.jolt_round_group_pack_tables(ctx.h, hs, C.c_size_t(len(self.members)), C.c_size_t(E), pack.h), "jolt_round_group_pack_tables", ctx)
+        ffi._call("jolt_round_group_pack_tables", ctx, ctx.h, hs, len(self.members), E, pack.h)
         if isinstance(coll, NativeCollective):
             coll.all_gather_table(pack, n_tab * E, gath)
         else:  # torch.distributed: through the host
             g = coll.all_gather_u64(pack.download())
-            ffi._ck(lib.jolt_table_write(ctx.h, gath.h, C.c_size_t(0), _p(np.ascontiguousarray(g.reshape(-1, 4))), C.c_size_t(world * n_tab * E)), "jolt_table_write", ctx)
-        ffi._ck(lib.jolt_tail_interleave(ctx.h, gath.h, C.c_size_t(world), C.c_size_t(n_tab), C.c_size_t(E), arena.h), "jolt_tail_interleave", ctx)
+            ffi._call("jolt_table_write", ctx, ctx.h, gath.h, 0, _p(np.ascontiguousarray(g.reshape(-1, 4))), world * n_tab * E)
+        ffi._call("jolt_tail_interleave", ctx, ctx.h, gath.h, world, n_tab, E, arena.h)
         tails, pos = [], 0
         for k, m in enumerate(self.members):
             tabs = []
             for _ in range(m.n_tables):
                 h = C.c_void_p()
-                ffi._ck(lib.jolt_table_slice(ctx.h, arena.h, C.c_size_t(pos * world * E), C.c_size_t(world * E), C.byref(h)), "jolt_table_slice", ctx)
+                ffi._call("jolt_table_slice", ctx, ctx.h, arena.h, pos * world * E, world * E, C.byref(h))
                 tabs.append(ffi.Table(ctx, h))
                 pos += 1
             self.keep += tabs
@@ -717,7 +717,7 @@ class ShardedWorkload:
                     shard_scale = ffi.host_fr_mul(shard_scale, w[j] if bit else ffi.host_fr_sub(one, w[j]))
                 h = C.c_void_p()
                 wl = np.ascontiguousarray(w[log_g:])
-                st = ffi.lib().jolt_member_create_split_eq_product_sharded(ctx.h, tabs[a].h, tabs[b].h, _p(wl), C.c_size_t(n_local), None,
+                st = ffi.lib().jolt_member_create_split_eq_product_sharded(ctx.h, tabs[a].h, tabs[b].h, _p(wl), n_local, None,
                                                                         _p(ffi.fr(shard_scale)), C.byref(h))
                 if st:
                     raise ffi.JoltError(st, "jolt_member_create_split_eq_product_sharded")
@@ -787,17 +787,17 @@ class ShardedWorkload:
                                   "slices": None, "members": None}
         T = self._tails[stage]
         hs = (C.c_void_p * len(idxs))(*[self.members[i].h for i in idxs])
-        st = lib.jolt_round_group_pack_tables(ctx.h, hs, C.c_size_t(len(idxs)), C.c_size_t(E), T["pack"].h)
+        st = lib.jolt_round_group_pack_tables(ctx.h, hs, len(idxs), E, T["pack"].h)
         if st:
             ffi._ck(st, "jolt_round_group_pack_tables", ctx)
         if isinstance(coll, NativeCollective):
             coll.all_gather_table(T["pack"], n_tab * E, T["gath"])
         else:  # torch.distributed fallback: through the host
             g = coll.all_gather_u64(T["pack"].download())
-            st = lib.jolt_table_write(ctx.h, T["gath"].h, C.c_size_t(0), _p(np.ascontiguousarray(g.reshape(-1, 4))), C.c_size_t(world * n_tab * E))
+            st = lib.jolt_table_write(ctx.h, T["gath"].h, 0, _p(np.ascontiguousarray(g.reshape(-1, 4))), world * n_tab * E)
             if st:
                 ffi._ck(st, "jolt_table_write", ctx)
-        st = lib.jolt_tail_interleave(ctx.h, T["gath"].h, C.c_size_t(world), C.c_size_t(n_tab), C.c_size_t(E), T["arena"].h)
+        st = lib.jolt_tail_interleave(ctx.h, T["gath"].h, world, n_tab, E, T["arena"].h)
         if st:
             ffi._ck(st, "jolt_tail_interleave", ctx)
 
@@ -818,7 +818,7 @@ class ShardedWorkload:
                 tabs = []
                 for _ in range(m.n_tables):
                     h = C.c_void_p()
-                    st = lib.jolt_table_slice(ctx.h, T["arena"].h, C.c_size_t(pos * world * E), C.c_size_t(world * E), C.byref(h))
+                    st = lib.jolt_table_slice(ctx.h, T["arena"].h, pos * world * E, world * E, C.byref(h))
                     if st:
                         ffi._ck(st, "jolt_table_slice", ctx)
                     tabs.append(ffi.Table(ctx, h))
@@ -925,19 +925,17 @@ class ShardedPcs:
         base_lo = 0 if self.block else lo  # compact SRS: the rank's cycles of address row 0 are its first T_local bases
         for t in self.dense_tables:
             out = ffi.g1_array(1)
-            ffi._ck(ffi.lib().jolt_msm_g1_table_range(ctx.h, self.srs.h, C.c_size_t(base_lo), t.h, C.c_size_t(lo), C.c_size_t(self.T_local), ffi._p(out)),
-                    "jolt_msm_g1_table_range", ctx)
+            ffi._call("jolt_msm_g1_table_range", ctx, ctx.h, self.srs.h, base_lo, t.h, lo, self.T_local, ffi._p(out))
             parts.append(out)
         if self.block:
             for s in self.local_sources:  # the single-GPU commitment of the rank's own cycles over its compact SRS
                 out = ffi.g1_array(s.n_polys)
-                ffi._ck(ffi.lib().jolt_grid_commit_onehot(ctx.h, self.srs.h, s.h, ffi._p(out)), "jolt_grid_commit_onehot", ctx)
+                ffi._call("jolt_grid_commit_onehot", ctx, ctx.h, self.srs.h, s.h, ffi._p(out))
                 parts.append(out)
         else:
             for s in self.sources:
                 out = ffi.g1_array(s.n_polys)
-                ffi._ck(ffi.lib().jolt_grid_commit_onehot_range(ctx.h, self.srs.h, s.h, C.c_size_t(lo), C.c_size_t(lo + self.T_local), ffi._p(out)),
-                        "jolt_grid_commit_onehot_range", ctx)
+                ffi._call("jolt_grid_commit_onehot_range", ctx, ctx.h, self.srs.h, s.h, lo, lo + self.T_local, ffi._p(out))
                 parts.append(out)
         local = np.concatenate(parts)
         allp = self.gather_points(local)  # (world, count, 12)
@@ -964,13 +962,11 @@ class ShardedPcs:
         ell = p.shape[0]
         com, w, v, ch = ffi.g1_array(max(ell - 1, 1)), ffi.g1_array(3), ffi.fr_array(3 * ell), ffi.fr_array(3)
         if self.block:
-            ffi._ck(ffi.lib().jolt_host_hyperkzg_open_sharded_blocks(ctx.h, self.srs.h, joint.h, ffi._p(p), C.c_size_t(ell), C.c_uint64(label), C.c_int32(self.rank),
-                                                                      C.c_int32(self.world), C.c_size_t(self.block), self.gather_fn, self.gather_user, ffi._p(com),
-                                                                      ffi._p(w), ffi._p(v), ffi._p(ch)), "jolt_host_hyperkzg_open_sharded_blocks", ctx)
+            ffi._call("jolt_host_hyperkzg_open_sharded_blocks", ctx, ctx.h, self.srs.h, joint.h, ffi._p(p), ell, label, self.rank, self.world, self.block, self.gather_fn,
+                      self.gather_user, ffi._p(com), ffi._p(w), ffi._p(v), ffi._p(ch))
         else:
-            ffi._ck(ffi.lib().jolt_host_hyperkzg_open_sharded(ctx.h, self.srs.h, joint.h, ffi._p(p), C.c_size_t(ell), C.c_uint64(label), C.c_int32(self.rank),
-                                                               C.c_int32(self.world), self.gather_fn, self.gather_user, ffi._p(com), ffi._p(w), ffi._p(v), ffi._p(ch)),
-                    "jolt_host_hyperkzg_open_sharded", ctx)
+            ffi._call("jolt_host_hyperkzg_open_sharded", ctx, ctx.h, self.srs.h, joint.h, ffi._p(p), ell, label, self.rank, self.world, self.gather_fn, self.gather_user,
+                      ffi._p(com), ffi._p(w), ffi._p(v), ffi._p(ch))
         joint.free()
         for t in self.dense_tables:
             t.free()

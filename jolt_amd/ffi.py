@@ -9,14 +9,18 @@ import os
 
 import numpy as np
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libjolt_hip.so")
 
-STATUS = {0: "ok", 1: "invalid argument", 2: "no device", 3: "oom", 4: "hip error", 5: "size mismatch", 6: "unsupported",
-          7: "not fully bound", 8: "round check failed", 9: "srs too small", 10: "empty point", 11: "not invertible"}
-ORDER_LOW_TO_HIGH, ORDER_HIGH_TO_LOW = 0, 1
-MEMBER_FLAG_SKIP_ONE = 1
-MEMBER_FLAG_BORROW_TABLES = 2
+STATUS = {abi.CONSTANTS[name]: text for name, text in {
+    "JOLT_OK": "ok", "JOLT_ERR_INVALID_ARG": "invalid argument", "JOLT_ERR_NO_DEVICE": "no device", "JOLT_ERR_OOM": "oom", "JOLT_ERR_HIP": "hip error",
+    "JOLT_ERR_SIZE_MISMATCH": "size mismatch", "JOLT_ERR_UNSUPPORTED": "unsupported", "JOLT_ERR_NOT_FULLY_BOUND": "not fully bound", "JOLT_ERR_ROUND_CHECK": "round check failed",
+    "JOLT_ERR_SRS_TOO_SMALL": "srs too small", "JOLT_ERR_EMPTY_POINT": "empty point", "JOLT_ERR_NOT_INVERTIBLE": "not invertible"}.items()}
+# every constant of the header under its name without the JOLT_ prefix: ORDER_LOW_TO_HIGH, MEMBER_FLAG_SKIP_ONE, PAIRING_LINES, DORY_KIND_G1, ...
+# (but the transcript kinds: TRANSCRIPT_* below are the kinds shifted into a label's top bits)
+globals().update({name[len("JOLT_"):]: value for name, value in abi.CONSTANTS.items() if not name.startswith("JOLT_TRANSCRIPT_")})
 
 
 class JoltError(RuntimeError):
@@ -47,9 +51,9 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: run `python -m jolt_amd.build` (there is no CPU fallback)")
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # (capi.hip sets the same default when the library is loaded; here for processes whose HIP runtime starts before it)
-        _lib = C.CDLL(LIB_PATH)
-        _lib.jolt_status_string.restype = C.c_char_p
-        _lib.jolt_last_error.restype = C.c_char_p
+        loaded = C.CDLL(LIB_PATH)
+        abi.declare(loaded)  # every entry point gets the header's prototype: call sites pass plain ints, a mistyped argument is a ctypes.ArgumentError
+        _lib = loaded
     return _lib
 
 
@@ -77,11 +81,16 @@ def _ck(status, where, ctx=None):
         raise JoltError(status, where, detail)
 
 
+def _call(name, ctx, *args):
+    """call entry point `name` and raise JoltError (with ctx's last error text) unless it returns JOLT_OK"""
+    _ck(getattr(lib(), name)(*args), name, ctx)
+
+
 class Context:
     def __init__(self, device_id=0, stream=None):
         self.h = C.c_void_p()
         self.device_id = device_id
-        st = lib().jolt_ctx_create(C.c_int32(device_id), C.c_void_p(stream) if stream else None, C.byref(self.h))
+        st = lib().jolt_ctx_create(device_id, C.c_void_p(stream) if stream else None, C.byref(self.h))
         if st != 0:
             self.h = C.c_void_p()
             raise JoltError(st, "jolt_ctx_create")
@@ -93,92 +102,89 @@ class Context:
 
     def bind_thread(self):
         """select this context's device on the calling thread (a worker thread starts on device 0)"""
-        _ck(lib().jolt_ctx_bind_thread(self.h), "jolt_ctx_bind_thread", self)
+        _call("jolt_ctx_bind_thread", self, self.h)
 
     def synchronize_foreground(self):
         """every stream but the background one (the opening hint's class sums)"""
-        _ck(lib().jolt_ctx_synchronize_foreground(self.h), "jolt_ctx_synchronize_foreground", self)
+        _call("jolt_ctx_synchronize_foreground", self, self.h)
 
     def synchronize(self):
-        _ck(lib().jolt_ctx_synchronize(self.h), "jolt_ctx_synchronize", self)
+        _call("jolt_ctx_synchronize", self, self.h)
 
     def timer_begin(self):
-        _ck(lib().jolt_timer_begin(self.h), "jolt_timer_begin", self)
+        _call("jolt_timer_begin", self, self.h)
 
     def timer_end(self):
         ms = C.c_float()
-        _ck(lib().jolt_timer_end(self.h, C.byref(ms)), "jolt_timer_end", self)
+        _call("jolt_timer_end", self, self.h, C.byref(ms))
         return ms.value
 
     # ---- tables
     def upload(self, arr):
         a = fr(arr).reshape(-1, 4)
         h = C.c_void_p()
-        _ck(lib().jolt_table_upload(self.h, _p(a), C.c_size_t(a.shape[0]), C.byref(h)), "jolt_table_upload", self)
+        _call("jolt_table_upload", self, self.h, _p(a), a.shape[0], C.byref(h))
         return Table(self, h)
 
     def from_device(self, ptr, length):
         h = C.c_void_p()
-        _ck(lib().jolt_table_from_device(self.h, C.c_void_p(ptr), C.c_size_t(length), C.byref(h)), "jolt_table_from_device", self)
+        _call("jolt_table_from_device", self, self.h, C.c_void_p(ptr), length, C.byref(h))
         return Table(self, h)
 
     def alloc(self, length):
         h = C.c_void_p()
-        _ck(lib().jolt_table_alloc(self.h, C.c_size_t(length), C.byref(h)), "jolt_table_alloc", self)
+        _call("jolt_table_alloc", self, self.h, length, C.byref(h))
         return Table(self, h)
 
     def from_u64(self, vals):
         v = np.ascontiguousarray(vals, dtype=np.uint64)
         h = C.c_void_p()
-        _ck(lib().jolt_table_from_u64(self.h, _p(v), C.c_size_t(v.shape[0]), C.byref(h)), "jolt_table_from_u64", self)
+        _call("jolt_table_from_u64", self, self.h, _p(v), v.shape[0], C.byref(h))
         return Table(self, h)
 
     def from_i64(self, vals):
         v = np.ascontiguousarray(vals, dtype=np.int64)
         h = C.c_void_p()
-        _ck(lib().jolt_table_from_i64(self.h, _p(v), C.c_size_t(v.shape[0]), C.byref(h)), "jolt_table_from_i64", self)
+        _call("jolt_table_from_i64", self, self.h, _p(v), v.shape[0], C.byref(h))
         return Table(self, h)
 
     def bind(self, tables, r, order=ORDER_LOW_TO_HIGH):
         hs = (C.c_void_p * len(tables))(*[t.h for t in tables])
-        _ck(lib().jolt_bind(self.h, hs, C.c_size_t(len(tables)), _p(fr(r)), C.c_int32(order)), "jolt_bind", self)
+        _call("jolt_bind", self, self.h, hs, len(tables), _p(fr(r)), order)
 
     def eq_evals(self, r, scale=None):
         r = fr(r).reshape(-1, 4)
         h = C.c_void_p()
-        _ck(lib().jolt_eq_evals(self.h, _p(r), C.c_size_t(r.shape[0]), _p(fr(scale)) if scale is not None else None, C.byref(h)),
-            "jolt_eq_evals", self)
+        _call("jolt_eq_evals", self, self.h, _p(r), r.shape[0], _p(fr(scale)) if scale is not None else None, C.byref(h))
         return Table(self, h)
 
     def eq_evals_aligned_block(self, r, start, block):
         r = fr(r).reshape(-1, 4)
         h = C.c_void_p()
-        _ck(lib().jolt_eq_evals_aligned_block(self.h, _p(r), C.c_size_t(r.shape[0]), C.c_size_t(start), C.c_size_t(block), C.byref(h)),
-            "jolt_eq_evals_aligned_block", self)
+        _call("jolt_eq_evals_aligned_block", self, self.h, _p(r), r.shape[0], start, block, C.byref(h))
         return Table(self, h)
 
     def lt_evals(self, r):
         r = fr(r).reshape(-1, 4)
         h = C.c_void_p()
-        _ck(lib().jolt_lt_evals(self.h, _p(r), C.c_size_t(r.shape[0]), C.byref(h)), "jolt_lt_evals", self)
+        _call("jolt_lt_evals", self, self.h, _p(r), r.shape[0], C.byref(h))
         return Table(self, h)
 
     def eq_plus_one_evals(self, r, scale=None):
         r = fr(r).reshape(-1, 4)
         h1, h2 = C.c_void_p(), C.c_void_p()
-        _ck(lib().jolt_eq_plus_one_evals(self.h, _p(r), C.c_size_t(r.shape[0]), _p(fr(scale)) if scale is not None else None,
-                                         C.byref(h1), C.byref(h2)), "jolt_eq_plus_one_evals", self)
+        _call("jolt_eq_plus_one_evals", self, self.h, _p(r), r.shape[0], _p(fr(scale)) if scale is not None else None, C.byref(h1), C.byref(h2))
         return Table(self, h1), Table(self, h2)
 
     def evaluate(self, table, point):
         p = fr(point).reshape(-1, 4)
         o = fr_array(1)
-        _ck(lib().jolt_table_evaluate(self.h, table.h, _p(p), C.c_size_t(p.shape[0]), _p(o)), "jolt_table_evaluate", self)
+        _call("jolt_table_evaluate", self, self.h, table.h, _p(p), p.shape[0], _p(o))
         return o[0]
 
     def table_sum(self, table):
         o = fr_array(1)
-        _ck(lib().jolt_table_sum(self.h, table.h, _p(o)), "jolt_table_sum", self)
+        _call("jolt_table_sum", self, self.h, table.h, _p(o))
         return o[0]
 
     # ---- members
@@ -194,7 +200,7 @@ class Context:
         d = MemberDesc(len(tables), len(terms), degree, order, offs.ctypes.data, facs_a.ctypes.data, coeffs.ctypes.data)
         hs = (C.c_void_p * len(tables))(*[t.h for t in tables])
         h = C.c_void_p()
-        _ck(lib().jolt_member_create_expr(self.h, hs, C.byref(d), C.byref(h)), "jolt_member_create_expr", self)
+        _call("jolt_member_create_expr", self, self.h, hs, C.byref(d), C.byref(h))
         for t in tables:
             t.h = None  # ownership moved into the member
         return Member(self, h, degree, len(tables), False, False)
@@ -230,9 +236,8 @@ class Context:
             assert borrow and order == ORDER_LOW_TO_HIGH, "integer-backed slots: borrowed tables, LowToHigh"
             ih = (C.c_void_p * len(tables))(*[t.h if isinstance(t, Ints) else None for t in tables])
             w = fr(eq_point).reshape(-1, 4) if eq_point is not None else None
-            _ck(lib().jolt_member_create_lc_small(self.h, hs, ih, C.byref(d), _p(w) if w is not None else None, C.c_size_t(0 if w is None else w.shape[0]),
-                                                  _p(fr(eq_scale)) if eq_scale is not None else None, _p(fr(shard_scale)) if shard_scale is not None else None,
-                                                  C.byref(h)), "jolt_member_create_lc_small", self)
+            _call("jolt_member_create_lc_small", self, self.h, hs, ih, C.byref(d), _p(w) if w is not None else None, 0 if w is None else w.shape[0],
+                  _p(fr(eq_scale)) if eq_scale is not None else None, _p(fr(shard_scale)) if shard_scale is not None else None, C.byref(h))
             if eq_point is not None:
                 m = Member(self, h, degree + 1, len(tables), True, True)
                 m.n_evals = degree
@@ -242,14 +247,14 @@ class Context:
                 m = Member(self, h, degree, len(tables), False, skip_one)
         elif eq_point is not None:
             w = fr(eq_point).reshape(-1, 4)
-            _ck(lib().jolt_member_create_split_eq_lc(self.h, hs, C.byref(d), _p(w), C.c_size_t(w.shape[0]), _p(fr(eq_scale)) if eq_scale is not None else None,
-                                                     _p(fr(shard_scale)) if shard_scale is not None else None, C.byref(h)), "jolt_member_create_split_eq_lc", self)
+            _call("jolt_member_create_split_eq_lc", self, self.h, hs, C.byref(d), _p(w), w.shape[0], _p(fr(eq_scale)) if eq_scale is not None else None,
+                  _p(fr(shard_scale)) if shard_scale is not None else None, C.byref(h))
             m = Member(self, h, degree + 1, len(tables), True, True)
             m.n_evals = degree
             m.uniform = True  # same host-side shape as the uniform member: dq sums, gruen_poly_from_q
             m.eq_weighted = True
         else:
-            _ck(lib().jolt_member_create_lc(self.h, hs, C.byref(d), C.byref(h)), "jolt_member_create_lc", self)
+            _call("jolt_member_create_lc", self, self.h, hs, C.byref(d), C.byref(h))
             m = Member(self, h, degree, len(tables), False, skip_one)
         if borrow:
             m._keepalive = list(tables)
@@ -262,7 +267,7 @@ class Context:
         w = fr(w).reshape(-1, 4)
         h = C.c_void_p()
         fn = lib().jolt_member_create_split_eq_product_borrowed if borrow else lib().jolt_member_create_split_eq_product
-        _ck(fn(self.h, a.h, b.h, _p(w), C.c_size_t(w.shape[0]), _p(fr(scale)) if scale is not None else None, C.byref(h)),
+        _ck(fn(self.h, a.h, b.h, _p(w), w.shape[0], _p(fr(scale)) if scale is not None else None, C.byref(h)),
             "jolt_member_create_split_eq_product", self)
         m = Member(self, h, 3, 2, True, False)
         if borrow:
@@ -277,9 +282,8 @@ class Context:
         low log2(rows) coordinates of the point, shard_scale = eq(w_hi, rank)"""
         w = fr(w_local).reshape(-1, 4)
         h = C.c_void_p()
-        _ck(lib().jolt_member_create_split_eq_product_sharded(self.h, a.h, b.h, _p(w), C.c_size_t(w.shape[0]), _p(fr(scale)) if scale is not None else None,
-                                                              _p(fr(shard_scale)) if shard_scale is not None else None, C.byref(h)),
-            "jolt_member_create_split_eq_product_sharded", self)
+        _call("jolt_member_create_split_eq_product_sharded", self, self.h, a.h, b.h, _p(w), w.shape[0], _p(fr(scale)) if scale is not None else None,
+              _p(fr(shard_scale)) if shard_scale is not None else None, C.byref(h))
         m = Member(self, h, 3, 2, True, False)
         m._keepalive = [a, b]
         return m
@@ -290,11 +294,8 @@ class Context:
         co = np.ascontiguousarray(np.stack([fr(c) for c in coeffs])).reshape(-1, 4)
         hs = (C.c_void_p * len(tables))(*[t.h for t in tables])
         h = C.c_void_p()
-        _ck(lib().jolt_member_create_split_eq_uniform(self.h, hs, C.c_uint32(V), C.c_uint32(F), _p(co), _p(w), C.c_size_t(w.shape[0]),
-                                                      _p(fr(scale)) if scale is not None else None,
-                                                      _p(fr(shard_scale)) if shard_scale is not None else None,
-                                                      C.c_uint32(MEMBER_FLAG_BORROW_TABLES if borrow else 0), C.byref(h)),
-            "jolt_member_create_split_eq_uniform", self)
+        _call("jolt_member_create_split_eq_uniform", self, self.h, hs, V, F, _p(co), _p(w), w.shape[0], _p(fr(scale)) if scale is not None else None,
+              _p(fr(shard_scale)) if shard_scale is not None else None, MEMBER_FLAG_BORROW_TABLES if borrow else 0, C.byref(h))
         m = Member(self, h, F + 1, len(tables), True, False)
         m.n_evals = F
         m.uniform = True
@@ -311,7 +312,7 @@ class Context:
         bp = (C.c_void_p * len(members))(*[None if b is None else b.ctypes.data for b in bstore])
         total = sum(m.n_evals for m in members)
         out = fr_array(total)
-        _ck(lib().jolt_round_group_prove(self.h, hs, C.c_size_t(len(members)), bp, _p(out), C.c_size_t(total)), "jolt_round_group_prove", self)
+        _call("jolt_round_group_prove", self, self.h, hs, len(members), bp, _p(out), total)
         res, off = [], 0
         for m in members:
             res.append(out[off:off + m.n_evals].copy())
@@ -327,9 +328,8 @@ class Context:
         offs = (C.c_size_t * n)(*offsets)
         polys, chal = fr_array(max_num_vars * (max_degree + 1)), fr_array(max_num_vars)
         mclaims, final = fr_array(n), fr_array(1)
-        _ck(lib().jolt_host_prove_batch(self.h, hs, C.c_size_t(n), _p(ic), _p(co), offs, C.c_size_t(max_num_vars), C.c_size_t(max_degree),
-                                        C.c_uint64(label), C.c_int32(challenge_mode), C.c_int32(1 if use_round_group else 0),
-                                        _p(polys), _p(chal), _p(mclaims), _p(final)), "jolt_host_prove_batch", self)
+        _call("jolt_host_prove_batch", self, self.h, hs, n, _p(ic), _p(co), offs, max_num_vars, max_degree, label, challenge_mode, 1 if use_round_group else 0, _p(polys),
+              _p(chal), _p(mclaims), _p(final))
         return dict(polys=polys.reshape(max_num_vars, max_degree + 1, 4), challenges=chal, member_claims=mclaims, final_claim=final[0])
 
     def __enter__(self):
@@ -351,23 +351,23 @@ class Table:
 
     def __len__(self):
         n = C.c_size_t()
-        _ck(lib().jolt_table_len(self.h, C.byref(n)), "jolt_table_len", self.ctx)
+        _call("jolt_table_len", self.ctx, self.h, C.byref(n))
         return n.value
 
     def download(self, offset=0, length=None):
         n = len(self) - offset if length is None else length
         out = fr_array(n)
-        _ck(lib().jolt_table_download(self.ctx.h, self.h, C.c_size_t(offset), C.c_size_t(n), _p(out)), "jolt_table_download", self.ctx)
+        _call("jolt_table_download", self.ctx, self.ctx.h, self.h, offset, n, _p(out))
         return out
 
     def clone(self):
         h = C.c_void_p()
-        _ck(lib().jolt_table_clone(self.ctx.h, self.h, C.byref(h)), "jolt_table_clone", self.ctx)
+        _call("jolt_table_clone", self.ctx, self.ctx.h, self.h, C.byref(h))
         return Table(self.ctx, h)
 
     def device_ptr(self):
         p = C.c_void_p()
-        _ck(lib().jolt_table_device_ptr(self.h, C.byref(p)), "jolt_table_device_ptr", self.ctx)
+        _call("jolt_table_device_ptr", self.ctx, self.h, C.byref(p))
         return p.value
 
     def free(self):
@@ -391,35 +391,34 @@ class Member:
         self.uniform = False
 
     def set_scale(self, scale):
-        _ck(lib().jolt_member_set_scale(self.h, _p(fr(scale))), "jolt_member_set_scale", self.ctx)
+        _call("jolt_member_set_scale", self.ctx, self.h, _p(fr(scale)))
 
     def num_rounds(self):
         n = C.c_size_t()
-        _ck(lib().jolt_member_num_rounds(self.h, C.byref(n)), "jolt_member_num_rounds", self.ctx)
+        _call("jolt_member_num_rounds", self.ctx, self.h, C.byref(n))
         return n.value
 
     def prove_round(self, bind=None, want_aux=False):
         out, aux = fr_array(self.n_evals), fr_array(3)
-        _ck(lib().jolt_member_prove_round(self.h, _p(fr(bind)) if bind is not None else None, _p(out), C.c_size_t(self.n_evals), _p(aux)),
-            "jolt_member_prove_round", self.ctx)
+        _call("jolt_member_prove_round", self.ctx, self.h, _p(fr(bind)) if bind is not None else None, _p(out), self.n_evals, _p(aux))
         return (out, aux) if want_aux else out
 
     def finish(self, bind):
-        _ck(lib().jolt_member_finish(self.h, _p(fr(bind))), "jolt_member_finish", self.ctx)
+        _call("jolt_member_finish", self.ctx, self.h, _p(fr(bind)))
 
     def final_values(self):
         k = self.n_tables + (1 if self.split_eq else 0)
         out = fr_array(k)
-        _ck(lib().jolt_member_final_values(self.h, _p(out), C.c_size_t(k)), "jolt_member_final_values", self.ctx)
+        _call("jolt_member_final_values", self.ctx, self.h, _p(out), k)
         return out
 
     def input_claim(self):
         out = fr_array(1)
-        _ck(lib().jolt_member_input_claim(self.h, _p(out)), "jolt_member_input_claim", self.ctx)
+        _call("jolt_member_input_claim", self.ctx, self.h, _p(out))
         return out[0]
 
     def reset(self):
-        _ck(lib().jolt_member_reset(self.h), "jolt_member_reset", self.ctx)
+        _call("jolt_member_reset", self.ctx, self.h)
 
     def destroy(self):
         if self.h and self.ctx.h:
@@ -436,7 +435,7 @@ class Member:
 # ---- host-side helpers (no GPU needed) ------------------------------------------------------------------------------
 def host_fr_binop(name, a, b):
     o = fr_array(1)
-    _ck(getattr(lib(), name)(_p(fr(a)), _p(fr(b)), _p(o)), name)
+    _call(name, None, _p(fr(a)), _p(fr(b)), _p(o))
     return o[0]
 
 
@@ -446,7 +445,7 @@ def host_fr_mul(a, b): return host_fr_binop("jolt_host_fr_mul", a, b)
 def host_mul_limbs29(field, a, b):
     """the device multiplication algorithm (29-bit limbs) built for the host; field 0 = Fr, 1 = Fq"""
     o = fr_array(1)
-    _ck(lib().jolt_host_mul_limbs29(C.c_int32(field), _p(fr(a)), _p(fr(b)), _p(o)), "jolt_host_mul_limbs29")
+    _call("jolt_host_mul_limbs29", None, field, _p(fr(a)), _p(fr(b)), _p(o))
     return o[0]
 
 
@@ -455,7 +454,7 @@ def host_fr_wide_dot(a, b):
     a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
     b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
     o = fr_array(1)
-    _ck(lib().jolt_host_fr_wide_dot(_p(a), _p(b), C.c_size_t(a.shape[0]), _p(o)), "jolt_host_fr_wide_dot")
+    _call("jolt_host_fr_wide_dot", None, _p(a), _p(b), a.shape[0], _p(o))
     return o[0]
 
 def host_fr_add(a, b): return host_fr_binop("jolt_host_fr_add", a, b)
@@ -465,20 +464,20 @@ def host_fr_mul_shifted(a, c): return host_fr_binop("jolt_host_fr_mul_shifted", 
 
 def host_fr_inv(a):
     o = fr_array(1)
-    _ck(lib().jolt_host_fr_inv(_p(fr(a)), _p(o)), "jolt_host_fr_inv")
+    _call("jolt_host_fr_inv", None, _p(fr(a)), _p(o))
     return o[0]
 
 
 def host_fr_from_u64(v):
     o = fr_array(1)
-    _ck(lib().jolt_host_fr_from_u64(C.c_uint64(v), _p(o)), "jolt_host_fr_from_u64")
+    _call("jolt_host_fr_from_u64", None, v, _p(o))
     return o[0]
 
 
 def host_eq_evals(r, scale=None):
     p = fr(r).reshape(-1, 4)
     out = fr_array(1 << p.shape[0])
-    st = lib().jolt_host_eq_evals(_p(p), C.c_size_t(p.shape[0]), _p(fr(scale)) if scale is not None else None, _p(out))
+    st = lib().jolt_host_eq_evals(_p(p), p.shape[0], _p(fr(scale)) if scale is not None else None, _p(out))
     if st != 0:
         raise JoltError(st, "jolt_host_eq_evals")
     return out
@@ -487,22 +486,21 @@ def host_eq_evals(r, scale=None):
 def host_univariate_from_evals(evals):
     e = fr(evals).reshape(-1, 4)
     o = fr_array(e.shape[0])
-    _ck(lib().jolt_host_univariate_from_evals(_p(e), C.c_size_t(e.shape[0]), _p(o)), "jolt_host_univariate_from_evals")
+    _call("jolt_host_univariate_from_evals", None, _p(e), e.shape[0], _p(o))
     return o
 
 
 def host_univariate_evaluate(coeffs, x):
     c = fr(coeffs).reshape(-1, 4)
     o = fr_array(1)
-    _ck(lib().jolt_host_univariate_evaluate(_p(c), C.c_size_t(c.shape[0]), _p(fr(x)), _p(o)), "jolt_host_univariate_evaluate")
+    _call("jolt_host_univariate_evaluate", None, _p(c), c.shape[0], _p(fr(x)), _p(o))
     return o[0]
 
 
 def host_gruen_poly_from_q(scalar, point_i, q_evals, claim):
     q = fr(q_evals).reshape(-1, 4)
     o = fr_array(q.shape[0] + 2)
-    _ck(lib().jolt_host_gruen_poly_from_q(_p(fr(scalar)), _p(fr(point_i)), _p(q), C.c_size_t(q.shape[0]), _p(fr(claim)), _p(o)),
-        "jolt_host_gruen_poly_from_q")
+    _call("jolt_host_gruen_poly_from_q", None, _p(fr(scalar)), _p(fr(point_i)), _p(q), q.shape[0], _p(fr(claim)), _p(o))
     return o
 
 
@@ -524,13 +522,11 @@ class HostBooleanityAddress:
 
     def round(self):
         o = fr_array(4)
-        _ck(lib().jolt_host_booleanity_address_round(_p(self.linear), _p(self.squared), C.c_size_t(self.n_polys), C.c_size_t(self.k), C.c_size_t(self.len), _p(self.weights), _p(self.eq),
-                                                     _p(o)), "jolt_host_booleanity_address_round")
+        _call("jolt_host_booleanity_address_round", None, _p(self.linear), _p(self.squared), self.n_polys, self.k, self.len, _p(self.weights), _p(self.eq), _p(o))
         return o
 
     def bind(self, r):
-        _ck(lib().jolt_host_booleanity_address_bind(_p(self.linear), _p(self.squared), C.c_size_t(self.n_polys), C.c_size_t(self.k), C.c_size_t(self.len), _p(self.eq), _p(fr(r))),
-            "jolt_host_booleanity_address_bind")
+        _call("jolt_host_booleanity_address_bind", None, _p(self.linear), _p(self.squared), self.n_polys, self.k, self.len, _p(self.eq), _p(fr(r)))
         self.len //= 2
 
     def intermediate(self):
@@ -553,15 +549,15 @@ class HostHammingWeight:
         vp = np.ascontiguousarray(virtualization_points, dtype=np.uint64).reshape(-1, 4)
         assert ra.shape[0] == log_k and vp.shape[0] == self.n_polys * log_k
         self.w = fr_array(self.n_polys * self.k).reshape(self.n_polys, self.k, 4)
-        _ck(lib().jolt_host_hamming_weights(_p(fr(gamma)), _p(ra), _p(vp), C.c_size_t(self.n_polys), C.c_size_t(log_k), _p(self.w)), "jolt_host_hamming_weights")
+        _call("jolt_host_hamming_weights", None, _p(fr(gamma)), _p(ra), _p(vp), self.n_polys, log_k, _p(self.w))
 
     def round(self):
         o = fr_array(3)
-        _ck(lib().jolt_host_pair_tables_round(_p(self.g), _p(self.w), C.c_size_t(self.n_polys), C.c_size_t(self.k), C.c_size_t(self.len), _p(o)), "jolt_host_pair_tables_round")
+        _call("jolt_host_pair_tables_round", None, _p(self.g), _p(self.w), self.n_polys, self.k, self.len, _p(o))
         return o
 
     def bind(self, r):
-        _ck(lib().jolt_host_pair_tables_bind(_p(self.g), _p(self.w), C.c_size_t(self.n_polys), C.c_size_t(self.k), C.c_size_t(self.len), _p(fr(r))), "jolt_host_pair_tables_bind")
+        _call("jolt_host_pair_tables_bind", None, _p(self.g), _p(self.w), self.n_polys, self.k, self.len, _p(fr(r)))
         self.len //= 2
 
     def output_claims(self):
@@ -569,7 +565,7 @@ class HostHammingWeight:
         return self.g[:, 0].copy()
 
 
-TRANSCRIPT_TEST, TRANSCRIPT_BLAKE2B, TRANSCRIPT_KECCAK, TRANSCRIPT_BLAKE2B_SPONGE = 0, 1 << 62, 2 << 62, 3 << 62  # OR into any `label` / `transcript_label`: the engine behind it (include/jolt_hip.h)
+TRANSCRIPT_TEST, TRANSCRIPT_BLAKE2B, TRANSCRIPT_KECCAK, TRANSCRIPT_BLAKE2B_SPONGE = (abi.CONSTANTS["JOLT_TRANSCRIPT_" + k] << 62 for k in ("TEST", "BLAKE2B_LEGACY", "KECCAK_SPONGE", "BLAKE2B_SPONGE"))  # OR into any `label` / `transcript_label`: the engine behind it (include/jolt_hip.h)
 
 
 class HostTranscript:
@@ -581,36 +577,36 @@ class HostTranscript:
         self.h = C.c_void_p()
         if isinstance(label, (bytes, bytearray)):
             buf = (C.c_uint8 * max(1, len(label))).from_buffer_copy(bytes(label) if len(label) else b"\0")
-            _ck(lib().jolt_host_transcript_create_labelled(C.c_int32(kind), buf, C.c_size_t(len(label)), C.byref(self.h)), "jolt_host_transcript_create_labelled")
+            _call("jolt_host_transcript_create_labelled", None, kind, buf, len(label), C.byref(self.h))
         else:
-            _ck(lib().jolt_host_transcript_create(C.c_uint64(label), C.byref(self.h)), "jolt_host_transcript_create")
+            _call("jolt_host_transcript_create", None, label, C.byref(self.h))
 
     def append(self, values):
         v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
-        _ck(lib().jolt_host_transcript_append_fr(self.h, _p(v), C.c_size_t(v.shape[0])), "jolt_host_transcript_append_fr")
+        _call("jolt_host_transcript_append_fr", None, self.h, _p(v), v.shape[0])
 
     def append_bytes(self, data):
         buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(bytes(data) if len(data) else b"\0")
-        _ck(lib().jolt_host_transcript_append_bytes(self.h, buf, C.c_size_t(len(data))), "jolt_host_transcript_append_bytes")
+        _call("jolt_host_transcript_append_bytes", None, self.h, buf, len(data))
 
     def append_label(self, label, count=None):
-        _ck(lib().jolt_host_transcript_append_label(self.h, C.c_char_p(label), C.c_int32(0 if count is None else 1), C.c_uint64(count or 0)), "jolt_host_transcript_append_label")
+        _call("jolt_host_transcript_append_label", None, self.h, C.c_char_p(label), 0 if count is None else 1, count or 0)
 
     def append_u64_word(self, value):
-        _ck(lib().jolt_host_transcript_append_u64_word(self.h, C.c_uint64(value)), "jolt_host_transcript_append_u64_word")
+        _call("jolt_host_transcript_append_u64_word", None, self.h, value)
 
     def append_round_poly(self, coefficients, label=b"sumcheck_poly"):
         v = np.ascontiguousarray(coefficients, dtype=np.uint64).reshape(-1, 4)
-        _ck(lib().jolt_host_transcript_append_round_poly(self.h, C.c_char_p(label), _p(v), C.c_size_t(v.shape[0])), "jolt_host_transcript_append_round_poly")
+        _call("jolt_host_transcript_append_round_poly", None, self.h, C.c_char_p(label), _p(v), v.shape[0])
 
     def state(self):
         out = (C.c_uint8 * 32)()
-        _ck(lib().jolt_host_transcript_state(self.h, out), "jolt_host_transcript_state")
+        _call("jolt_host_transcript_state", None, self.h, out)
         return bytes(out)
 
     def challenge(self, full_width=False):
         o = fr_array(1)
-        _ck(lib().jolt_host_transcript_challenge(self.h, C.c_int32(1 if full_width else 0), _p(o)), "jolt_host_transcript_challenge")
+        _call("jolt_host_transcript_challenge", None, self.h, 1 if full_width else 0, _p(o))
         return o[0]
 
     def close(self):
@@ -622,13 +618,13 @@ class HostTranscript:
 def host_blake2b(data, outlen=32):
     out = (C.c_uint8 * outlen)()
     buf = (C.c_uint8 * max(1, len(data))).from_buffer_copy(bytes(data) if len(data) else b"\0")
-    _ck(lib().jolt_host_blake2b(buf, C.c_size_t(len(data)), C.c_size_t(outlen), out), "jolt_host_blake2b")
+    _call("jolt_host_blake2b", None, buf, len(data), outlen, out)
     return bytes(out)
 
 
 def host_keccak_f1600(state):
     buf = (C.c_uint8 * 200).from_buffer_copy(bytes(state))
-    _ck(lib().jolt_host_keccak_f1600(buf), "jolt_host_keccak_f1600")
+    _call("jolt_host_keccak_f1600", None, buf)
     return bytes(buf)
 
     def __del__(self):
@@ -640,8 +636,7 @@ def host_keccak_f1600(state):
 
 def host_gruen_poly_deg_3(scalar, point_i, q0, qinf, claim):
     o = fr_array(4)
-    _ck(lib().jolt_host_gruen_poly_deg_3(_p(fr(scalar)), _p(fr(point_i)), _p(fr(q0)), _p(fr(qinf)), _p(fr(claim)), _p(o)),
-        "jolt_host_gruen_poly_deg_3")
+    _call("jolt_host_gruen_poly_deg_3", None, _p(fr(scalar)), _p(fr(point_i)), _p(fr(q0)), _p(fr(qinf)), _p(fr(claim)), _p(o))
     return o
 
 
@@ -654,13 +649,13 @@ class Srs:
 
     def __len__(self):
         n = C.c_size_t()
-        _ck(lib().jolt_srs_len(self.h, C.byref(n)), "jolt_srs_len", self.ctx)
+        _call("jolt_srs_len", self.ctx, self.h, C.byref(n))
         return n.value
 
     def download(self, offset=0, n=None):
         n = len(self) - offset if n is None else n
         out = g1_array(n)
-        _ck(lib().jolt_srs_download(self.ctx.h, self.h, C.c_size_t(offset), C.c_size_t(n), _p(out)), "jolt_srs_download", self.ctx)
+        _call("jolt_srs_download", self.ctx, self.ctx.h, self.h, offset, n, _p(out))
         return out
 
     def free(self):
@@ -678,50 +673,48 @@ class Srs:
 def _srs_upload(self, bases):
     b = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 12)
     h = C.c_void_p()
-    _ck(lib().jolt_srs_upload_g1(self.h, _p(b), C.c_size_t(b.shape[0]), C.byref(h)), "jolt_srs_upload_g1", self)
+    _call("jolt_srs_upload_g1", self, self.h, _p(b), b.shape[0], C.byref(h))
     return Srs(self, h)
 
 
 def _srs_setup_from_secret(self, beta, count, g1):
     h = C.c_void_p()
-    _ck(lib().jolt_srs_setup_from_secret(self.h, _p(fr(beta)), C.c_size_t(count), _p(np.ascontiguousarray(g1, dtype=np.uint64)), C.byref(h)),
-        "jolt_srs_setup_from_secret", self)
+    _call("jolt_srs_setup_from_secret", self, self.h, _p(fr(beta)), count, _p(np.ascontiguousarray(g1, dtype=np.uint64)), C.byref(h))
     return Srs(self, h)
 
 
 def host_owned_terms(n, block, rank, world):
     """Terms of the prefix [0, n) that `rank` owns under the block-cyclic assignment (host only)."""
     out = C.c_size_t()
-    _ck(lib().jolt_host_owned_terms(C.c_size_t(n), C.c_size_t(block), C.c_int32(rank), C.c_int32(world), C.byref(out)), "jolt_host_owned_terms")
+    _call("jolt_host_owned_terms", None, n, block, rank, world, C.byref(out))
     return out.value
 
 
 def host_subtree_owned_terms(n, rank, world):
     """Terms of the prefix [0, n) that `rank` owns under the subtree assignment (host only)."""
     out = C.c_size_t()
-    _ck(lib().jolt_host_subtree_owned_terms(C.c_size_t(n), C.c_int32(rank), C.c_int32(world), C.byref(out)), "jolt_host_subtree_owned_terms")
+    _call("jolt_host_subtree_owned_terms", None, n, rank, world, C.byref(out))
     return out.value
 
 
 def host_subtree_term_index(slot, rank, world):
     """Index of the rank's compact slot under the subtree assignment (host only)."""
     out = C.c_size_t()
-    _ck(lib().jolt_host_subtree_term_index(C.c_size_t(slot), C.c_int32(rank), C.c_int32(world), C.byref(out)), "jolt_host_subtree_term_index")
+    _call("jolt_host_subtree_term_index", None, slot, rank, world, C.byref(out))
     return out.value
 
 
 def _srs_setup_from_secret_subtree(self, beta, count_global, g1, rank, world):
     """One rank's compact share of the powers under the subtree assignment."""
     h = C.c_void_p()
-    _ck(lib().jolt_srs_setup_from_secret_subtree(self.h, _p(fr(beta)), C.c_size_t(count_global), _p(np.ascontiguousarray(g1, dtype=np.uint64)), C.c_int32(rank),
-                                                 C.c_int32(world), C.byref(h)), "jolt_srs_setup_from_secret_subtree", self)
+    _call("jolt_srs_setup_from_secret_subtree", self, self.h, _p(fr(beta)), count_global, _p(np.ascontiguousarray(g1, dtype=np.uint64)), rank, world, C.byref(h))
     return Srs(self, h)
 
 
 def _msm_subtree(self, srs, table, n, rank, world):
     """The rank's share of sum_{i<n} table[i] * SRS[i] under the subtree assignment (srs = the rank's compact SRS)."""
     out = g1_array(1)
-    _ck(lib().jolt_msm_g1_table_subtree(self.h, srs.h, table.h, C.c_size_t(n), C.c_int32(rank), C.c_int32(world), _p(out)), "jolt_msm_g1_table_subtree", self)
+    _call("jolt_msm_g1_table_subtree", self, self.h, srs.h, table.h, n, rank, world, _p(out))
     return out[0]
 
 
@@ -730,24 +723,21 @@ def _hyperkzg_open_subtree(self, srs, evals_compact, point, label, rank, world, 
     p = fr(point).reshape(-1, 4)
     ell = p.shape[0]
     com, w, v, ch = g1_array(max(ell - 1, 1)), g1_array(3), fr_array(3 * ell), fr_array(3)
-    _ck(lib().jolt_host_hyperkzg_open_subtree(self.h, srs.h, evals_compact.h, _p(p), C.c_size_t(ell), C.c_uint64(label), C.c_int32(rank), C.c_int32(world),
-                                              gather_fn, gather_user, _p(com), _p(w), _p(v), _p(ch)), "jolt_host_hyperkzg_open_subtree", self)
+    _call("jolt_host_hyperkzg_open_subtree", self, self.h, srs.h, evals_compact.h, _p(p), ell, label, rank, world, gather_fn, gather_user, _p(com), _p(w), _p(v), _p(ch))
     return dict(com=com[: ell - 1], w=w, v=v.reshape(3, ell, 4), challenges=ch)
 
 
 def _srs_setup_from_secret_blocks(self, beta, count_global, g1, block, rank, world):
     """One rank's compact share of the powers under the block-cyclic term assignment (term i belongs to rank (i / block) % world)."""
     h = C.c_void_p()
-    _ck(lib().jolt_srs_setup_from_secret_blocks(self.h, _p(fr(beta)), C.c_size_t(count_global), _p(np.ascontiguousarray(g1, dtype=np.uint64)), C.c_size_t(block),
-                                                C.c_int32(rank), C.c_int32(world), C.byref(h)), "jolt_srs_setup_from_secret_blocks", self)
+    _call("jolt_srs_setup_from_secret_blocks", self, self.h, _p(fr(beta)), count_global, _p(np.ascontiguousarray(g1, dtype=np.uint64)), block, rank, world, C.byref(h))
     return Srs(self, h)
 
 
 def _msm_blocks(self, srs, table, n, block, rank, world):
     """The rank's share of sum_{i<n} table[i] * SRS[i] under the block-cyclic assignment (srs = the rank's compact SRS)."""
     out = g1_array(1)
-    _ck(lib().jolt_msm_g1_table_blocks(self.h, srs.h, table.h, C.c_size_t(n), C.c_size_t(block), C.c_int32(rank), C.c_int32(world), _p(out)),
-        "jolt_msm_g1_table_blocks", self)
+    _call("jolt_msm_g1_table_blocks", self, self.h, srs.h, table.h, n, block, rank, world, _p(out))
     return out[0]
 
 
@@ -758,13 +748,13 @@ class PendingMsms:
         hs = (C.c_void_p * len(tables))(*[t.h for t in tables])
         nn = (C.c_size_t * len(tables))(*[int(x) for x in ns])
         h = C.c_void_p()
-        _ck(lib().jolt_msm_g1_tables_begin(ctx.h, srs.h, hs, nn, C.c_size_t(len(tables)), C.byref(h)), "jolt_msm_g1_tables_begin", ctx)
+        _call("jolt_msm_g1_tables_begin", ctx, ctx.h, srs.h, hs, nn, len(tables), C.byref(h))
         self.ctx, self.h, self.count = ctx, h, len(tables)
 
     def finish(self):
         out = g1_array(self.count)
         h, self.h = self.h, None
-        _ck(lib().jolt_msm_g1_tables_finish(self.ctx.h, h, _p(out)), "jolt_msm_g1_tables_finish", self.ctx)
+        _call("jolt_msm_g1_tables_finish", self.ctx, self.ctx.h, h, _p(out))
         return out
 
 
@@ -779,30 +769,30 @@ def _msm(self, srs, scalars, n=None, full_width=False):
     if isinstance(scalars, Table):
         n = len(scalars) if n is None else n
         fn = "jolt_msm_g1_table_full_width" if full_width else "jolt_msm_g1_table"
-        _ck(getattr(lib(), fn)(self.h, srs.h, scalars.h, C.c_size_t(n), _p(out)), fn, self)
+        _call(fn, self, self.h, srs.h, scalars.h, n, _p(out))
     else:
         s = fr(scalars).reshape(-1, 4)
         n = s.shape[0] if n is None else n
-        _ck(lib().jolt_msm_g1(self.h, srs.h, _p(s), C.c_size_t(n), _p(out)), "jolt_msm_g1", self)
+        _call("jolt_msm_g1", self, self.h, srs.h, _p(s), n, _p(out))
     return out[0]
 
 
 def _msm_profile_buckets(self, enable=True):
     """HIP events around the bucket-sum kernel of every later fixed-base MSM (jolt_msm_profile_buckets)"""
-    _ck(lib().jolt_msm_profile_buckets(self.h, C.c_int32(1 if enable else 0)), "jolt_msm_profile_buckets", self)
+    _call("jolt_msm_profile_buckets", self, self.h, 1 if enable else 0)
 
 
 def _msm_profile_buckets_last(self):
     """(milliseconds, mixed additions) of the last profiled bucket-sum launch"""
     ms, adds = C.c_float(), C.c_uint64()
-    _ck(lib().jolt_msm_profile_buckets_last(self.h, C.byref(ms), C.byref(adds)), "jolt_msm_profile_buckets_last", self)
+    _call("jolt_msm_profile_buckets_last", self, self.h, C.byref(ms), C.byref(adds))
     return float(ms.value), int(adds.value)
 
 
 def _measure_mad_peak(self, target_ms=50.0):
     """jolt_ctx_measure_mad_peak: (v_mad_u64_u32 lane-operations per second chip-wide, kernel milliseconds timed, launches)"""
     rate, ms, n = C.c_double(), C.c_float(), C.c_uint32()
-    _ck(lib().jolt_ctx_measure_mad_peak(self.h, C.c_float(target_ms), C.byref(rate), C.byref(ms), C.byref(n)), "jolt_ctx_measure_mad_peak", self)
+    _call("jolt_ctx_measure_mad_peak", self, self.h, target_ms, C.byref(rate), C.byref(ms), C.byref(n))
     return float(rate.value), float(ms.value), int(n.value)
 
 
@@ -815,8 +805,7 @@ def _msm_window(self, srs, base_offset, values, kind=None, acc=None):
     code = {"u64": 0, "i64": 1, "i128": 2, "fr": 3}[kind]
     out = g1_array(1)
     a = None if acc is None else np.ascontiguousarray(acc, dtype=np.uint64).reshape(-1)
-    _ck(lib().jolt_msm_g1_window(self.h, srs.h, C.c_size_t(base_offset), C.c_int32(code), v.ctypes.data_as(C.c_void_p), C.c_size_t(v.shape[0]),
-                                 None if a is None else _p(a), _p(out)), "jolt_msm_g1_window", self)
+    _call("jolt_msm_g1_window", self, self.h, srs.h, base_offset, code, v.ctypes.data_as(C.c_void_p), v.shape[0], None if a is None else _p(a), _p(out))
     return out[0]
 
 
@@ -824,7 +813,7 @@ def _hyperkzg_fold(self, evals, point):
     p = fr(point).reshape(-1, 4)
     ell = p.shape[0]
     hs = (C.c_void_p * max(ell, 1))()
-    _ck(lib().jolt_hyperkzg_fold(self.h, evals.h, _p(p), C.c_size_t(ell), hs), "jolt_hyperkzg_fold", self)
+    _call("jolt_hyperkzg_fold", self, self.h, evals.h, _p(p), ell, hs)
     return [Table(self, C.c_void_p(hs[i])) for i in range(ell)]
 
 
@@ -832,26 +821,26 @@ def _hyperkzg_eval3(self, levels, u):
     hs = (C.c_void_p * len(levels))(*[t.h for t in levels])
     uu = fr(u).reshape(3, 4)
     out = fr_array(3 * len(levels))
-    _ck(lib().jolt_hyperkzg_eval3(self.h, hs, C.c_size_t(len(levels)), _p(uu), _p(out)), "jolt_hyperkzg_eval3", self)
+    _call("jolt_hyperkzg_eval3", self, self.h, hs, len(levels), _p(uu), _p(out))
     return out.reshape(3, len(levels), 4)
 
 
 def _hyperkzg_rlc(self, levels, q):
     hs = (C.c_void_p * len(levels))(*[t.h for t in levels])
     h = C.c_void_p()
-    _ck(lib().jolt_hyperkzg_rlc(self.h, hs, C.c_size_t(len(levels)), _p(fr(q)), C.byref(h)), "jolt_hyperkzg_rlc", self)
+    _call("jolt_hyperkzg_rlc", self, self.h, hs, len(levels), _p(fr(q)), C.byref(h))
     return Table(self, h)
 
 
 def _hyperkzg_witness_poly(self, f, u):
     h = C.c_void_p()
-    _ck(lib().jolt_hyperkzg_witness_poly(self.h, f.h, _p(fr(u)), C.byref(h)), "jolt_hyperkzg_witness_poly", self)
+    _call("jolt_hyperkzg_witness_poly", self, self.h, f.h, _p(fr(u)), C.byref(h))
     return Table(self, h)
 
 
 def _hyperkzg_commit(self, srs, evals):
     out = g1_array(1)
-    _ck(lib().jolt_host_hyperkzg_commit(self.h, srs.h, evals.h, _p(out)), "jolt_host_hyperkzg_commit", self)
+    _call("jolt_host_hyperkzg_commit", self, self.h, srs.h, evals.h, _p(out))
     return out[0]
 
 
@@ -862,11 +851,9 @@ def _hyperkzg_open(self, srs, evals, point, label=0, known_levels=None):
     com, w, v, ch = g1_array(max(ell - 1, 1)), g1_array(3), fr_array(3 * max(ell, 1)), fr_array(3)
     if known_levels is not None and len(known_levels):
         kl = np.ascontiguousarray(known_levels, dtype=np.uint64).reshape(-1, 12)
-        _ck(lib().jolt_host_hyperkzg_open_with_levels(self.h, srs.h, evals.h, _p(p), C.c_size_t(ell), C.c_uint64(label), None, None, _p(kl), C.c_size_t(kl.shape[0]),
-                                                      _p(com), _p(w), _p(v), _p(ch)), "jolt_host_hyperkzg_open_with_levels", self)
+        _call("jolt_host_hyperkzg_open_with_levels", self, self.h, srs.h, evals.h, _p(p), ell, label, None, None, _p(kl), kl.shape[0], _p(com), _p(w), _p(v), _p(ch))
         return dict(com=com[: ell - 1], w=w, v=v.reshape(3, ell, 4), challenges=ch)
-    _ck(lib().jolt_host_hyperkzg_open(self.h, srs.h, evals.h, _p(p), C.c_size_t(ell), C.c_uint64(label), _p(com), _p(w), _p(v), _p(ch)),
-        "jolt_host_hyperkzg_open", self)
+    _call("jolt_host_hyperkzg_open", self, self.h, srs.h, evals.h, _p(p), ell, label, _p(com), _p(w), _p(v), _p(ch))
     return dict(com=com[: ell - 1], w=w, v=v.reshape(3, ell, 4), challenges=ch)
 
 
@@ -877,15 +864,15 @@ class GridHint:
     def __init__(self, ctx, srs, sources, levels, background=True):
         hs = (C.c_void_p * len(sources))(*[s_.h for s_ in sources])
         h = C.c_void_p()
-        _ck(lib().jolt_grid_hint_begin(ctx.h, srs.h, hs, C.c_size_t(len(sources)), C.c_uint32(levels), C.c_int32(1 if background else 0), C.byref(h)), "jolt_grid_hint_begin", ctx)
+        _call("jolt_grid_hint_begin", ctx, ctx.h, srs.h, hs, len(sources), levels, 1 if background else 0, C.byref(h))
         self.ctx, self.h, self.levels, self.n_cols, self._keep = ctx, h, levels, sum(s_.n_polys for s_ in sources), list(sources)
 
     def wait(self):
-        _ck(lib().jolt_grid_hint_wait(self.ctx.h, self.h), "jolt_grid_hint_wait", self.ctx)
+        _call("jolt_grid_hint_wait", self.ctx, self.ctx.h, self.h)
 
     def download(self, level):
         out = g1_array(self.n_cols << level)
-        _ck(lib().jolt_grid_hint_download(self.ctx.h, self.h, C.c_uint32(level), _p(out)), "jolt_grid_hint_download", self.ctx)
+        _call("jolt_grid_hint_download", self.ctx, self.ctx.h, self.h, level, _p(out))
         return out.reshape(1 << level, self.n_cols, 12)
 
     def free(self):
@@ -909,14 +896,14 @@ def _hyperkzg_open_grid(self, srs, evals, point, hint, levels, onehot_scalars, d
     osc = np.ascontiguousarray(onehot_scalars, dtype=np.uint64).reshape(-1, 4)
     dsc = np.ascontiguousarray(dense_scalars, dtype=np.uint64).reshape(-1, 4) if len(dense) else None
     hs = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
-    _ck(lib().jolt_host_hyperkzg_open_grid(self.h, srs.h, evals.h, _p(p), C.c_size_t(ell), C.c_uint64(label), None, None, hint.h, C.c_uint32(levels), _p(osc), hs,
-                                           C.c_size_t(len(dense)), _p(dsc) if dsc is not None else None, _p(com), _p(w), _p(v), _p(ch)), "jolt_host_hyperkzg_open_grid", self)
+    _call("jolt_host_hyperkzg_open_grid", self, self.h, srs.h, evals.h, _p(p), ell, label, None, None, hint.h, levels, _p(osc), hs, len(dense),
+          _p(dsc) if dsc is not None else None, _p(com), _p(w), _p(v), _p(ch))
     return dict(com=com[: ell - 1], w=w, v=v.reshape(3, ell, 4), challenges=ch)
 
 
 def _srs_precompute_windows(self, srs, window_bits=0, min_terms=0):
     """Fixed-base tables 2^(c*w) * srs[i] (one bucket set for all windows of an MSM): ceil(255/c) copies of the bases in HBM."""
-    _ck(lib().jolt_srs_precompute_windows(self.h, srs.h, C.c_uint32(window_bits), C.c_size_t(min_terms)), "jolt_srs_precompute_windows", self)
+    _call("jolt_srs_precompute_windows", self, self.h, srs.h, window_bits, min_terms)
 
 
 Context.srs_precompute_windows = _srs_precompute_windows
@@ -942,7 +929,7 @@ Context.hyperkzg_open = _hyperkzg_open
 Context.hyperkzg_open_grid = _hyperkzg_open_grid
 Context.grid_hint = lambda self, srs, sources, levels, background=True: GridHint(self, srs, sources, levels, background)
 
-OPEN_TRANSCRIPT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p)
+OPEN_TRANSCRIPT_FN = abi.CALLBACK_TYPES["jolt_open_transcript_fn"]
 
 
 def _hyperkzg_open_with_transcript(self, srs, evals, point, absorb_points, absorb_values, challenge):
@@ -967,7 +954,7 @@ def _hyperkzg_open_with_transcript(self, srs, evals, point, absorb_points, absor
             return 4
 
     fn = OPEN_TRANSCRIPT_FN(cb)
-    st = lib().jolt_host_hyperkzg_open_with_transcript(self.h, srs.h, evals.h, _p(p), C.c_size_t(ell), fn, None, _p(com), _p(w), _p(v), _p(ch))
+    st = lib().jolt_host_hyperkzg_open_with_transcript(self.h, srs.h, evals.h, _p(p), ell, fn, None, _p(com), _p(w), _p(v), _p(ch))
     if err:
         raise err[0]
     _ck(st, "jolt_host_hyperkzg_open_with_transcript", self)
@@ -979,25 +966,25 @@ Context.hyperkzg_open_with_transcript = _hyperkzg_open_with_transcript
 
 def host_g1_add(p, q):
     o = g1_array(1)
-    _ck(lib().jolt_host_g1_add(_p(np.ascontiguousarray(p, dtype=np.uint64)), _p(np.ascontiguousarray(q, dtype=np.uint64)), _p(o)), "jolt_host_g1_add")
+    _call("jolt_host_g1_add", None, _p(np.ascontiguousarray(p, dtype=np.uint64)), _p(np.ascontiguousarray(q, dtype=np.uint64)), _p(o))
     return o[0]
 
 
 def host_g1_is_on_curve(p):
     e = C.c_int32()
-    _ck(lib().jolt_host_g1_is_on_curve(_p(np.ascontiguousarray(p, dtype=np.uint64)), C.byref(e)), "jolt_host_g1_is_on_curve")
+    _call("jolt_host_g1_is_on_curve", None, _p(np.ascontiguousarray(p, dtype=np.uint64)), C.byref(e))
     return bool(e.value)
 
 
 def host_g1_eq(p, q):
     e = C.c_int32()
-    _ck(lib().jolt_host_g1_eq(_p(np.ascontiguousarray(p, dtype=np.uint64)), _p(np.ascontiguousarray(q, dtype=np.uint64)), C.byref(e)), "jolt_host_g1_eq")
+    _call("jolt_host_g1_eq", None, _p(np.ascontiguousarray(p, dtype=np.uint64)), _p(np.ascontiguousarray(q, dtype=np.uint64)), C.byref(e))
     return bool(e.value)
 
 
 def host_g1_serialize_compressed(p):
     out = (C.c_uint8 * 32)()
-    _ck(lib().jolt_host_g1_serialize_compressed(_p(np.ascontiguousarray(p, dtype=np.uint64)), out), "jolt_host_g1_serialize_compressed")
+    _call("jolt_host_g1_serialize_compressed", None, _p(np.ascontiguousarray(p, dtype=np.uint64)), out)
     return bytes(out)
 
 
@@ -1008,14 +995,14 @@ class PinnedBuffer:
         shape = tuple(int(x) for x in (shape if isinstance(shape, (tuple, list)) else (shape,)))
         n = int(np.prod(shape))
         p = C.c_void_p()
-        _ck(lib().jolt_host_pinned_alloc(ctx.h, C.c_size_t(n), C.byref(p)), "jolt_host_pinned_alloc", ctx)
+        _call("jolt_host_pinned_alloc", ctx, ctx.h, n, C.byref(p))
         self.ctx, self.p = ctx, p
         self.array = np.ctypeslib.as_array((C.c_uint8 * n).from_address(p.value)).reshape(shape)
 
     def free(self):
         if self.p:
             self.array = None
-            _ck(lib().jolt_host_pinned_free(self.ctx.h, self.p), "jolt_host_pinned_free", self.ctx)
+            _call("jolt_host_pinned_free", self.ctx, self.ctx.h, self.p)
             self.p = None
 
 
@@ -1026,7 +1013,7 @@ class Rows:
         raw = np.ascontiguousarray(rows)
         self.n_rows, self.row_bytes = raw.shape[0], raw.dtype.itemsize if raw.ndim == 1 else raw.shape[1]
         h = C.c_void_p()
-        _ck(lib().jolt_rows_upload(ctx.h, raw.ctypes.data_as(C.c_void_p), C.c_size_t(self.n_rows), C.c_size_t(self.row_bytes), C.byref(h)), "jolt_rows_upload", ctx)
+        _call("jolt_rows_upload", ctx, ctx.h, raw.ctypes.data_as(C.c_void_p), self.n_rows, self.row_bytes, C.byref(h))
         self.ctx, self.h = ctx, h
 
     @classmethod
@@ -1038,23 +1025,22 @@ class Rows:
         self = cls.__new__(cls)
         self.n_rows, self.row_bytes = raw.shape[0], raw.shape[1]
         h = C.c_void_p()
-        _ck(lib().jolt_rows_upload_begin(ctx.h, raw.ctypes.data_as(C.c_void_p), C.c_size_t(self.n_rows), C.c_size_t(self.row_bytes), C.byref(h)), "jolt_rows_upload_begin", ctx)
+        _call("jolt_rows_upload_begin", ctx, ctx.h, raw.ctypes.data_as(C.c_void_p), self.n_rows, self.row_bytes, C.byref(h))
         self.ctx, self.h = ctx, h
         return self
 
     def wait(self):
-        _ck(lib().jolt_rows_upload_wait(self.ctx.h, self.h), "jolt_rows_upload_wait", self.ctx)
+        _call("jolt_rows_upload_wait", self.ctx, self.ctx.h, self.h)
 
     def table(self, offset, width, signed=False):
         h = C.c_void_p()
-        _ck(lib().jolt_table_from_rows(self.ctx.h, self.h, C.c_size_t(offset), C.c_uint32(width), C.c_int32(1 if signed else 0), C.byref(h)), "jolt_table_from_rows",
-            self.ctx)
+        _call("jolt_table_from_rows", self.ctx, self.ctx.h, self.h, offset, width, 1 if signed else 0, C.byref(h))
         return Table(self.ctx, h)
 
     def ints(self, offset, width, signed=False):
         """the field as a resident integer column (jolt_ints_from_rows): compact scalars, no promotion"""
         h = C.c_void_p()
-        _ck(lib().jolt_ints_from_rows(self.ctx.h, self.h, C.c_size_t(offset), C.c_uint32(width), C.c_int32(1 if signed else 0), C.byref(h)), "jolt_ints_from_rows", self.ctx)
+        _call("jolt_ints_from_rows", self.ctx, self.ctx.h, self.h, offset, width, 1 if signed else 0, C.byref(h))
         v = Ints.__new__(Ints)
         v.ctx, v.kind, v.count, v.h = self.ctx, "i64" if signed else "u64", self.n_rows, h
         return v
@@ -1066,7 +1052,7 @@ class Rows:
         widths = (C.c_uint32 * n)(*[f[1] for f in fields])
         signed = (C.c_int32 * n)(*[1 if f[2] else 0 for f in fields])
         hs = (C.c_void_p * n)()
-        _ck(lib().jolt_ints_from_rows_many(self.ctx.h, self.h, offs, widths, signed, C.c_size_t(n), hs), "jolt_ints_from_rows_many", self.ctx)
+        _call("jolt_ints_from_rows_many", self.ctx, self.ctx.h, self.h, offs, widths, signed, n, hs)
         out = []
         for k, f in enumerate(fields):
             v = Ints.__new__(Ints)
@@ -1077,9 +1063,8 @@ class Rows:
     def onehot(self, offset, width, shifts, log_k, valid_offset=None):
         sh = (C.c_uint32 * len(shifts))(*shifts)
         h = C.c_void_p()
-        vo = C.c_size_t(valid_offset if valid_offset is not None else 2**64 - 1)
-        _ck(lib().jolt_onehot_from_rows(self.ctx.h, self.h, C.c_size_t(offset), C.c_uint32(width), sh, C.c_size_t(len(shifts)), C.c_uint32(log_k), vo, C.byref(h)),
-            "jolt_onehot_from_rows", self.ctx)
+        vo = valid_offset if valid_offset is not None else 2**64 - 1
+        _call("jolt_onehot_from_rows", self.ctx, self.ctx.h, self.h, offset, width, sh, len(shifts), log_k, vo, C.byref(h))
         src = OneHot.__new__(OneHot)
         src.ctx, src.n_polys, src.cycles, src.k, src.h, src.wide = self.ctx, len(shifts), self.n_rows, 1 << log_k, h, log_k > 7
         return src
@@ -1096,26 +1081,25 @@ class SplitLt:
     def __init__(self, ctx, r_cycle, constant=None):
         r = fr(r_cycle).reshape(-1, 4)
         h = C.c_void_p()
-        _ck(lib().jolt_split_lt_create(ctx.h, _p(r) if r.shape[0] else None, C.c_size_t(r.shape[0]), _p(fr(constant)) if constant is not None else None,
-                                       C.byref(h)), "jolt_split_lt_create", ctx)
+        _call("jolt_split_lt_create", ctx, ctx.h, _p(r) if r.shape[0] else None, r.shape[0], _p(fr(constant)) if constant is not None else None, C.byref(h))
         self.ctx, self.h = ctx, h
 
     def __len__(self):
         n = C.c_size_t()
-        _ck(lib().jolt_split_lt_len(self.h, C.byref(n)), "jolt_split_lt_len", self.ctx)
+        _call("jolt_split_lt_len", self.ctx, self.h, C.byref(n))
         return n.value
 
     def bind(self, r):
-        _ck(lib().jolt_split_lt_bind(self.ctx.h, self.h, _p(fr(r))), "jolt_split_lt_bind", self.ctx)
+        _call("jolt_split_lt_bind", self.ctx, self.ctx.h, self.h, _p(fr(r)))
 
     def to_dense(self):
         h = C.c_void_p()
-        _ck(lib().jolt_split_lt_to_dense(self.ctx.h, self.h, C.byref(h)), "jolt_split_lt_to_dense", self.ctx)
+        _call("jolt_split_lt_to_dense", self.ctx, self.ctx.h, self.h, C.byref(h))
         return Table(self.ctx, h)
 
     def final_value(self):
         o = fr_array(1)
-        _ck(lib().jolt_split_lt_final_value(self.ctx.h, self.h, _p(o)), "jolt_split_lt_final_value", self.ctx)
+        _call("jolt_split_lt_final_value", self.ctx, self.ctx.h, self.h, _p(o))
         return o[0]
 
     def free(self):
@@ -1134,25 +1118,23 @@ class OneHot:
         assert idx.ndim == 2
         self.ctx, self.n_polys, self.cycles, self.k, self.wide = ctx, idx.shape[0], idx.shape[1], k, wide
         h = C.c_void_p()
-        fn = lib().jolt_onehot_upload16 if wide else lib().jolt_onehot_upload
-        _ck(fn(ctx.h, idx.ctypes.data_as(C.c_void_p), C.c_size_t(idx.shape[0]), C.c_size_t(idx.shape[1]), C.c_uint32(k), C.byref(h)), "jolt_onehot_upload", ctx)
+        _call("jolt_onehot_upload16" if wide else "jolt_onehot_upload", ctx, ctx.h, idx.ctypes.data_as(C.c_void_p), idx.shape[0], idx.shape[1], k, C.byref(h))
         self.h = h
 
     def download(self):
         wide = self.wide
         out = np.empty((self.n_polys, self.cycles), dtype=np.uint16 if wide else np.uint8)
-        fn = lib().jolt_onehot_download16 if wide else lib().jolt_onehot_download
-        _ck(fn(self.ctx.h, self.h, out.ctypes.data_as(C.c_void_p)), "jolt_onehot_download", self.ctx)
+        _call("jolt_onehot_download16" if wide else "jolt_onehot_download", self.ctx, self.ctx.h, self.h, out.ctypes.data_as(C.c_void_p))
         return out
 
     def materialize(self, poly, scale_table):
         h = C.c_void_p()
-        _ck(lib().jolt_onehot_materialize(self.ctx.h, self.h, C.c_size_t(poly), scale_table.h, C.byref(h)), "jolt_onehot_materialize", self.ctx)
+        _call("jolt_onehot_materialize", self.ctx, self.ctx.h, self.h, poly, scale_table.h, C.byref(h))
         return Table(self.ctx, h)
 
     def pushforward(self, weights):
         h = C.c_void_p()
-        _ck(lib().jolt_onehot_pushforward(self.ctx.h, self.h, weights.h, C.byref(h)), "jolt_onehot_pushforward", self.ctx)
+        _call("jolt_onehot_pushforward", self.ctx, self.ctx.h, self.h, weights.h, C.byref(h))
         return Table(self.ctx, h)
 
     def free(self):
@@ -1164,7 +1146,7 @@ class OneHot:
 class Ints:
     """Small machine integers resident on the device for the Dory tier-1 row commitments: uint64 / int64 numpy arrays, or
     i128 as an (n, 2) uint64 array (low, high; two's complement) / a list of Python ints with kind="i128"."""
-    KINDS = {"u64": 0, "i64": 1, "i128": 2}
+    KINDS = {"u64": INT_U64, "i64": INT_I64, "i128": INT_I128}
 
     def __init__(self, ctx, values, kind=None):
         if kind == "i128" and not isinstance(values, np.ndarray):
@@ -1175,7 +1157,7 @@ class Ints:
         self.ctx, self.kind = ctx, kind
         self.count = v.shape[0]
         h = C.c_void_p()
-        _ck(lib().jolt_ints_upload(ctx.h, v.ctypes.data_as(C.c_void_p), C.c_int32(self.KINDS[kind]), C.c_size_t(self.count), C.byref(h)), "jolt_ints_upload", ctx)
+        _call("jolt_ints_upload", ctx, ctx.h, v.ctypes.data_as(C.c_void_p), self.KINDS[kind], self.count, C.byref(h))
         self.h = h
 
     def free(self):
@@ -1188,7 +1170,7 @@ def _dory_commit_rows(self, srs, values, row_width):
     """DoryScheme::feed_u64 / feed_i128 over every row_width window of `values` (an Ints): one G1 point per row."""
     rows = values.count // row_width if row_width else 0
     out = g1_array(max(rows, 1))
-    _ck(lib().jolt_dory_commit_rows(self.h, srs.h, values.h, C.c_size_t(row_width), _p(out)), "jolt_dory_commit_rows", self)
+    _call("jolt_dory_commit_rows", self, self.h, srs.h, values.h, row_width, _p(out))
     return out[:rows]
 
 
@@ -1196,7 +1178,7 @@ def _dory_commit_onehot(self, srs, source, poly, chunk_width):
     """DoryScheme::process_one_hot_chunks_with for hot-index column `poly`: (chunks, k) G1 points."""
     chunks = source.cycles // chunk_width if chunk_width else 0
     out = g1_array(max(chunks * source.k, 1))
-    _ck(lib().jolt_dory_commit_onehot(self.h, srs.h, source.h, C.c_size_t(poly), C.c_size_t(chunk_width), _p(out)), "jolt_dory_commit_onehot", self)
+    _call("jolt_dory_commit_onehot", self, self.h, srs.h, source.h, poly, chunk_width, _p(out))
     return out[:chunks * source.k].reshape(chunks, source.k, -1)
 
 
@@ -1207,12 +1189,10 @@ def _member_lazy_ra_uniform(self, source, scale_tables, V, F, coeffs, w, scale=N
     st = np.ascontiguousarray(scale_tables, dtype=np.uint64).reshape(-1, 4)
     h = C.c_void_p()
     if shard_scale is not None:
-        _ck(lib().jolt_member_create_lazy_ra_uniform_sharded(self.h, source.h, _p(st), C.c_uint32(V), C.c_uint32(F), _p(co), _p(w), C.c_size_t(w.shape[0]),
-                                                             _p(fr(scale)) if scale is not None else None, _p(fr(shard_scale)), C.byref(h)),
-            "jolt_member_create_lazy_ra_uniform_sharded", self)
+        _call("jolt_member_create_lazy_ra_uniform_sharded", self, self.h, source.h, _p(st), V, F, _p(co), _p(w), w.shape[0], _p(fr(scale)) if scale is not None else None,
+              _p(fr(shard_scale)), C.byref(h))
     else:
-        _ck(lib().jolt_member_create_lazy_ra_uniform(self.h, source.h, _p(st), C.c_uint32(V), C.c_uint32(F), _p(co), _p(w), C.c_size_t(w.shape[0]),
-                                                     _p(fr(scale)) if scale is not None else None, C.byref(h)), "jolt_member_create_lazy_ra_uniform", self)
+        _call("jolt_member_create_lazy_ra_uniform", self, self.h, source.h, _p(st), V, F, _p(co), _p(w), w.shape[0], _p(fr(scale)) if scale is not None else None, C.byref(h))
     m = Member(self, h, F + 1, V * F, True, False)
     m.n_evals = F
     m.uniform = True
@@ -1226,8 +1206,7 @@ def _member_lazy_booleanity(self, source, scale_tables, rho, w, scale=None):
     st = np.ascontiguousarray(scale_tables, dtype=np.uint64).reshape(-1, 4)
     rh = np.ascontiguousarray(np.stack([fr(c) for c in rho])).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_member_create_lazy_booleanity(self.h, source.h, _p(st), _p(rh), _p(w), C.c_size_t(w.shape[0]),
-                                                 _p(fr(scale)) if scale is not None else None, C.byref(h)), "jolt_member_create_lazy_booleanity", self)
+    _call("jolt_member_create_lazy_booleanity", self, self.h, source.h, _p(st), _p(rh), _p(w), w.shape[0], _p(fr(scale)) if scale is not None else None, C.byref(h))
     m = Member(self, h, 3, rh.shape[0], True, False)
     m.n_evals = 2
     m._keepalive = [source]
@@ -1267,8 +1246,8 @@ def _dory_fold_rows_grid(self, sources, onehot_scalars, dense, dense_scalars, lo
     osc = fr(np.stack([fr(c) for c in onehot_scalars])).reshape(-1, 4) if len(onehot_scalars) else None
     dsc = fr(np.stack([fr(c) for c in dense_scalars])).reshape(-1, 4) if len(dense_scalars) else None
     h = C.c_void_p()
-    _ck(lib().jolt_dory_fold_rows_grid(self.h, hs if sources else None, C.c_size_t(len(sources)), _p(osc), ds if dense else None, C.c_size_t(len(dense)),
-                                       _p(dsc), C.c_uint32(log_k), C.c_uint32(sigma), left.h, C.byref(h)), "jolt_dory_fold_rows_grid", self)
+    _call("jolt_dory_fold_rows_grid", self, self.h, hs if sources else None, len(sources), _p(osc), ds if dense else None, len(dense), _p(dsc), log_k, sigma, left.h,
+          C.byref(h))
     return Table(self, h)
 
 
@@ -1281,7 +1260,7 @@ def _dory_combine_hints(self, hints, scalars):
     sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if n else fr_array(1)
     width = max([h.shape[0] for h in hs], default=0)
     out = g1_array(max(width, 1))
-    _ck(lib().jolt_dory_combine_hints(self.h, ptrs, rows, C.c_size_t(n), _p(sc), _p(out)), "jolt_dory_combine_hints", self)
+    _call("jolt_dory_combine_hints", self, self.h, ptrs, rows, n, _p(sc), _p(out))
     return out[:width]
 
 
@@ -1290,7 +1269,7 @@ def host_dory_combine_row(points, scalars):
     pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
     sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if pts.shape[0] else fr_array(1)
     out = g1_array(1)
-    _ck(lib().jolt_host_dory_combine_row(_p(pts), _p(sc), C.c_size_t(pts.shape[0]), _p(out)), "jolt_host_dory_combine_row")
+    _call("jolt_host_dory_combine_row", None, _p(pts), _p(sc), pts.shape[0], _p(out))
     return out[0]
 
 
@@ -1315,7 +1294,7 @@ def _dory_msm(self, group, bases, scalars):
         raise ValueError("msm: bases and scalars differ in length")
     out = np.zeros(_DORY_GROUPS[group], dtype=np.uint64)
     name = f"jolt_dory_{group}_msm"
-    _ck(getattr(lib(), name)(self.h, _p(b) if b.shape[0] else None, _p(sc) if b.shape[0] else None, C.c_size_t(b.shape[0]), _p(out)), name, self)
+    _call(name, self, self.h, _p(b) if b.shape[0] else None, _p(sc) if b.shape[0] else None, b.shape[0], _p(out))
     return out
 
 
@@ -1326,7 +1305,7 @@ def _dory_fixed_base_mul(self, group, base, scalars):
     n = sc.shape[0]
     out = np.zeros((max(n, 1), _DORY_GROUPS[group]), dtype=np.uint64)
     name = f"jolt_dory_{group}_fixed_base_mul"
-    _ck(getattr(lib(), name)(self.h, _p(b), _p(sc) if n else None, C.c_size_t(n), _p(out) if n else None), name, self)
+    _call(name, self, self.h, _p(b), _p(sc) if n else None, n, _p(out) if n else None)
     return out[:n]
 
 
@@ -1337,7 +1316,7 @@ def _dory_scale_bases_add(self, group, bases, vs, scalar):
         raise ValueError("lengths must match")
     n = v.shape[0]
     name = f"jolt_dory_{group}_scale_bases_add"
-    _ck(getattr(lib(), name)(self.h, _p(b) if n else None, _p(v) if n else None, C.c_size_t(n), _p(fr(scalar))), name, self)
+    _call(name, self, self.h, _p(b) if n else None, _p(v) if n else None, n, _p(fr(scalar)))
     return v
 
 
@@ -1348,7 +1327,7 @@ def _dory_scale_vs_add(self, group, vs, addends, scalar):
         raise ValueError("lengths must match")
     n = v.shape[0]
     name = f"jolt_dory_{group}_scale_vs_add"
-    _ck(getattr(lib(), name)(self.h, _p(v) if n else None, _p(a) if n else None, C.c_size_t(n), _p(fr(scalar))), name, self)
+    _call(name, self, self.h, _p(v) if n else None, _p(a) if n else None, n, _p(fr(scalar)))
     return v
 
 
@@ -1358,14 +1337,14 @@ def _dory_fold_field_vectors(self, left, right, scalar):
     if l.shape[0] != r.shape[0]:
         raise ValueError("lengths must match")
     n = l.shape[0]
-    _ck(lib().jolt_dory_fold_field_vectors(self.h, _p(l) if n else None, _p(r) if n else None, C.c_size_t(n), _p(fr(scalar))), "jolt_dory_fold_field_vectors", self)
+    _call("jolt_dory_fold_field_vectors", self, self.h, _p(l) if n else None, _p(r) if n else None, n, _p(fr(scalar)))
     return l
 
 
 def _dory_routines_timing(self, enable):
     """(checks, host -> device, kernels, device -> host) wall ms of the last routine call made while timing was on; then switches timing on / off"""
     ms = (C.c_double * 4)()
-    _ck(lib().jolt_dory_routines_timing(self.h, C.c_int32(1 if enable else 0), ms), "jolt_dory_routines_timing", self)
+    _call("jolt_dory_routines_timing", self, self.h, 1 if enable else 0, ms)
     return tuple(ms)
 
 
@@ -1380,7 +1359,6 @@ Context.dory_g2_scale_vs_add = lambda self, vs, addends, scalar: _dory_scale_vs_
 Context.dory_fold_field_vectors = _dory_fold_field_vectors
 Context.dory_routines_timing = _dory_routines_timing
 
-FQ2_ADD, FQ2_SUB, FQ2_MUL, FQ2_SQR, FQ2_NEG = 0, 1, 2, 3, 4
 
 
 def host_fq2_op(op, a, b=None):
@@ -1388,14 +1366,14 @@ def host_fq2_op(op, a, b=None):
     a = np.ascontiguousarray(a, dtype=np.uint64).reshape(8)
     b = np.ascontiguousarray(b, dtype=np.uint64).reshape(8) if b is not None else None
     out = np.zeros(8, dtype=np.uint64)
-    _ck(lib().jolt_host_fq2_op(C.c_int32(op), _p(a), _p(b), _p(out)), "jolt_host_fq2_op")
+    _call("jolt_host_fq2_op", None, op, _p(a), _p(b), _p(out))
     return out
 
 
 def _host_g2(name, *pts):
     out = np.zeros(24, dtype=np.uint64)
     args = [_p(np.ascontiguousarray(p, dtype=np.uint64)) for p in pts]
-    _ck(getattr(lib(), name)(*args, _p(out)), name)
+    _call(name, None, *args, _p(out))
     return out
 
 
@@ -1407,19 +1385,19 @@ def host_g2_scalar_mul(p, s): return _host_g2("jolt_host_g2_scalar_mul", p, s)
 
 def host_g2_eq(p, q):
     e = C.c_int32()
-    _ck(lib().jolt_host_g2_eq(_p(np.ascontiguousarray(p, dtype=np.uint64)), _p(np.ascontiguousarray(q, dtype=np.uint64)), C.byref(e)), "jolt_host_g2_eq")
+    _call("jolt_host_g2_eq", None, _p(np.ascontiguousarray(p, dtype=np.uint64)), _p(np.ascontiguousarray(q, dtype=np.uint64)), C.byref(e))
     return bool(e.value)
 
 
 def host_g2_is_on_curve(p):
     e = C.c_int32()
-    _ck(lib().jolt_host_g2_is_on_curve(_p(np.ascontiguousarray(p, dtype=np.uint64)), C.byref(e)), "jolt_host_g2_is_on_curve")
+    _call("jolt_host_g2_is_on_curve", None, _p(np.ascontiguousarray(p, dtype=np.uint64)), C.byref(e))
     return bool(e.value)
 
 
 def _host_dory_one(name, group, *args):
     out = np.zeros(_DORY_GROUPS[group], dtype=np.uint64)
-    _ck(getattr(lib(), name)(*[_p(np.ascontiguousarray(a, dtype=np.uint64)) for a in args], _p(out)), name)
+    _call(name, None, *[_p(np.ascontiguousarray(a, dtype=np.uint64)) for a in args], _p(out))
     return out
 
 
@@ -1439,8 +1417,6 @@ def host_dory_msm_term(group, base, scalar):
 
 
 # ---- Dory's multi-pairings (dory_pairing.hip): the tier-2 commitment and the multi-pairings of the reduce-and-fold rounds
-PAIRING_LINES = 88  # JOLT_PAIRING_LINES
-FQ12_MUL, FQ12_SQR, FQ12_INV, FQ12_CONJ, FQ12_FROBENIUS1, FQ12_FROBENIUS2, FQ12_FROBENIUS3, FQ12_MUL_SPARSE = range(8)
 
 
 def gt_array():
@@ -1459,7 +1435,7 @@ def _dory_multi_pair(self, g1s, g2s, final_exponentiation=True):
         raise ValueError("multi_pair: the two sides differ in length")
     n, out = a.shape[0], gt_array()
     name = "jolt_dory_multi_pair" if final_exponentiation else "jolt_dory_multi_miller"
-    _ck(getattr(lib(), name)(self.h, _p(a) if n else None, _p(b) if n else None, C.c_size_t(n), _p(out)), name, self)
+    _call(name, self, self.h, _p(a) if n else None, _p(b) if n else None, n, _p(out))
     return out
 
 
@@ -1471,14 +1447,14 @@ class G2Prepared:
 
     def free(self):
         if self.h:
-            _ck(lib().jolt_g2_prepared_free(self.ctx.h, self.h), "jolt_g2_prepared_free", self.ctx)
+            _call("jolt_g2_prepared_free", self.ctx, self.ctx.h, self.h)
             self.h = None
 
 
 def _dory_g2_prepare(self, g2s):
     b = _dory_pts("g2", g2s)
     h = C.c_void_p()
-    _ck(lib().jolt_dory_g2_prepare(self.h, _p(b) if b.shape[0] else None, C.c_size_t(b.shape[0]), C.byref(h)), "jolt_dory_g2_prepare", self)
+    _call("jolt_dory_g2_prepare", self, self.h, _p(b) if b.shape[0] else None, b.shape[0], C.byref(h))
     return G2Prepared(self, h, b.shape[0])
 
 
@@ -1487,14 +1463,14 @@ def _dory_multi_pair_g2_setup(self, g1s, prepared, n=None):
     a = _pair_g1(g1s)
     n = a.shape[0] if n is None else n
     out = gt_array()
-    _ck(lib().jolt_dory_multi_pair_g2_setup(self.h, _p(a) if a.shape[0] else None, prepared.h, C.c_size_t(n), _p(out)), "jolt_dory_multi_pair_g2_setup", self)
+    _call("jolt_dory_multi_pair_g2_setup", self, self.h, _p(a) if a.shape[0] else None, prepared.h, n, _p(out))
     return out
 
 
 def _dory_pairing_timing(self, enable):
     """(checks, host -> device, prepare, Miller, product, device -> host, final exponentiation) wall ms of the last pairing call made while timing was on"""
     ms = (C.c_double * 7)()
-    _ck(lib().jolt_dory_pairing_timing(self.h, C.c_int32(1 if enable else 0), ms), "jolt_dory_pairing_timing", self)
+    _call("jolt_dory_pairing_timing", self, self.h, 1 if enable else 0, ms)
     return tuple(ms)
 
 
@@ -1505,8 +1481,6 @@ Context.dory_pairing_timing = _dory_pairing_timing
 
 
 # ---- Dory's rounds on resident vectors (dory_resident.hip): vectors that stay in HBM, in-place routines on views, product batches
-DORY_KIND_G1, DORY_KIND_G2, DORY_KIND_FR = range(3)
-DORY_PAIR, DORY_MSM_G1, DORY_MSM_G2 = range(3)
 _DORY_KIND_WIDTH = {DORY_KIND_G1: 12, DORY_KIND_G2: 24, DORY_KIND_FR: 4}
 _DORY_RESULT_WIDTH = {DORY_PAIR: 48, DORY_MSM_G1: 12, DORY_MSM_G2: 24}
 
@@ -1525,7 +1499,7 @@ class DoryVec:
 
     def __len__(self):
         n = C.c_size_t()
-        _ck(lib().jolt_dory_vec_len(self.h, C.byref(n)), "jolt_dory_vec_len", self.ctx)
+        _call("jolt_dory_vec_len", self.ctx, self.h, C.byref(n))
         return n.value
 
     def view(self, first=0, n=None):
@@ -1534,21 +1508,21 @@ class DoryVec:
     def device_kind(self):
         """the kind the library holds for the handle"""
         k = C.c_int32()
-        _ck(lib().jolt_dory_vec_kind(self.h, C.byref(k)), "jolt_dory_vec_kind", self.ctx)
+        _call("jolt_dory_vec_kind", self.ctx, self.h, C.byref(k))
         return k.value
 
     def download(self, first=0, n=None):
         n = len(self) - first if n is None else n
         out = np.zeros((n, _DORY_KIND_WIDTH[self.kind]), dtype=np.uint64)
-        _ck(lib().jolt_dory_vec_download(self.ctx.h, self.h, C.c_size_t(first), C.c_size_t(n), _p(out) if n else None), "jolt_dory_vec_download", self.ctx)
+        _call("jolt_dory_vec_download", self.ctx, self.ctx.h, self.h, first, n, _p(out) if n else None)
         return out
 
     def truncate(self, n):
-        _ck(lib().jolt_dory_vec_truncate(self.h, C.c_size_t(n)), "jolt_dory_vec_truncate", self.ctx)
+        _call("jolt_dory_vec_truncate", self.ctx, self.h, n)
 
     def free(self):
         if self.h:
-            _ck(lib().jolt_dory_vec_free(self.ctx.h, self.h), "jolt_dory_vec_free", self.ctx)
+            _call("jolt_dory_vec_free", self.ctx, self.ctx.h, self.h)
             self.h = None
 
 
@@ -1560,7 +1534,7 @@ def _dory_view(v):
 def _dory_vec_upload(self, kind, host):
     a = np.ascontiguousarray(host, dtype=np.uint64).reshape(-1, _DORY_KIND_WIDTH[kind])
     h = C.c_void_p()
-    _ck(lib().jolt_dory_vec_upload(self.h, C.c_int32(kind), _p(a) if a.shape[0] else None, C.c_size_t(a.shape[0]), C.byref(h)), "jolt_dory_vec_upload", self)
+    _call("jolt_dory_vec_upload", self, self.h, kind, _p(a) if a.shape[0] else None, a.shape[0], C.byref(h))
     return DoryVec(self, h, kind)
 
 
@@ -1568,7 +1542,7 @@ def _dory_g2_prepare_vec(self, view):
     """the line table of a resident G2 view, built on the device (jolt_dory_g2_prepare_vec)"""
     v, first, n = _dory_view(view)
     h = C.c_void_p()
-    _ck(lib().jolt_dory_g2_prepare_vec(self.h, v.h, C.c_size_t(first), C.c_size_t(n), C.byref(h)), "jolt_dory_g2_prepare_vec", self)
+    _call("jolt_dory_g2_prepare_vec", self, self.h, v.h, first, n, C.byref(h))
     return G2Prepared(self, h, n)
 
 
@@ -1582,32 +1556,32 @@ def _dory_two_views(x, y):
 def _dory_vec_scale_bases_add(self, bases, vs, scalar):
     """vs[i] += scalar * bases[i] in place on views (fixed_scalar_mul_bases_then_add); enqueued, not awaited"""
     bv, bf, vv, vf, n = _dory_two_views(bases, vs)
-    _ck(lib().jolt_dory_vec_scale_bases_add(self.h, bv.h, C.c_size_t(bf), vv.h, C.c_size_t(vf), C.c_size_t(n), _p(fr(scalar))), "jolt_dory_vec_scale_bases_add", self)
+    _call("jolt_dory_vec_scale_bases_add", self, self.h, bv.h, bf, vv.h, vf, n, _p(fr(scalar)))
 
 
 def _dory_vec_scale_vs_add(self, vs, addends, scalar):
     """vs[i] = scalar * vs[i] + addends[i] in place on views (fixed_scalar_mul_vs_then_add); enqueued, not awaited"""
     vv, vf, av, af, n = _dory_two_views(vs, addends)
-    _ck(lib().jolt_dory_vec_scale_vs_add(self.h, vv.h, C.c_size_t(vf), av.h, C.c_size_t(af), C.c_size_t(n), _p(fr(scalar))), "jolt_dory_vec_scale_vs_add", self)
+    _call("jolt_dory_vec_scale_vs_add", self, self.h, vv.h, vf, av.h, af, n, _p(fr(scalar)))
 
 
 def _dory_vec_fold_field(self, left, right, scalar):
     """left[i] = left[i] * scalar + right[i] in place on Fr views (fold_field_vectors); enqueued, not awaited"""
     lv, lf, rv, rf, n = _dory_two_views(left, right)
-    _ck(lib().jolt_dory_vec_fold_field(self.h, lv.h, C.c_size_t(lf), rv.h, C.c_size_t(rf), C.c_size_t(n), _p(fr(scalar))), "jolt_dory_vec_fold_field", self)
+    _call("jolt_dory_vec_fold_field", self, self.h, lv.h, lf, rv.h, rf, n, _p(fr(scalar)))
 
 
 def _dory_state_alloc(self, kind, n):
     """n neutral elements on the device (jolt_dory_state_alloc): identities (1, 1, 0), or zeros for DORY_KIND_FR; enqueued, not awaited"""
     h = C.c_void_p()
-    _ck(lib().jolt_dory_state_alloc(self.h, C.c_int32(kind), C.c_size_t(n), C.byref(h)), "jolt_dory_state_alloc", self)
+    _call("jolt_dory_state_alloc", self, self.h, kind, n, C.byref(h))
     return DoryVec(self, h, kind)
 
 
 def _dory_state_from_table(self, table, dst, table_first=0):
     """dst[i] = table[table_first + i] over the Fr view dst = DoryVec or (DoryVec, first, n): a device copy (jolt_dory_state_from_table); enqueued, not awaited"""
     dv, df, n = _dory_view(dst)
-    _ck(lib().jolt_dory_state_from_table(self.h, table.h, C.c_size_t(table_first), dv.h, C.c_size_t(df), C.c_size_t(n)), "jolt_dory_state_from_table", self)
+    _call("jolt_dory_state_from_table", self, self.h, table.h, table_first, dv.h, df, n)
 
 
 def _dory_state_combine_hints(self, hints, scalars, out, out_first=0):
@@ -1621,7 +1595,7 @@ def _dory_state_combine_hints(self, hints, scalars, out, out_first=0):
     sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if n else fr_array(1)
     if sc.shape[0] != max(n, 1):
         raise ValueError("one scalar per hint")
-    _ck(lib().jolt_dory_state_combine_hints(self.h, hs, firsts, rows, C.c_size_t(n), _p(sc), out.h, C.c_size_t(out_first)), "jolt_dory_state_combine_hints", self)
+    _call("jolt_dory_state_combine_hints", self, self.h, hs, firsts, rows, n, _p(sc), out.h, out_first)
     return max([r for _, _, r in views], default=0)
 
 
@@ -1629,7 +1603,7 @@ def _dory_state_fixed_base_mul(self, kind, base, scalars, out):
     """out[i] = scalars[i] * base on views (fixed_base_vector_scalar_mul): kind = DORY_KIND_G1 / _G2, base one host point, scalars an Fr view, out a view of `kind`"""
     b = np.ascontiguousarray(base, dtype=np.uint64).reshape(_DORY_KIND_WIDTH[kind])
     sv, sf, ov, of, n = _dory_two_views(scalars, out)
-    _ck(lib().jolt_dory_state_fixed_base_mul(self.h, C.c_int32(kind), _p(b), sv.h, C.c_size_t(sf), ov.h, C.c_size_t(of), C.c_size_t(n)), "jolt_dory_state_fixed_base_mul", self)
+    _call("jolt_dory_state_fixed_base_mul", self, self.h, kind, _p(b), sv.h, sf, ov.h, of, n)
 
 
 def dory_item(op, a, b, prepared_first=0):
@@ -1648,7 +1622,7 @@ def _dory_products(self, items):
     n = len(items)
     arr = (DoryItem * max(n, 1))(*items)
     outs = np.zeros((max(n, 1), 48), dtype=np.uint64)
-    _ck(lib().jolt_dory_products(self.h, arr if n else None, C.c_size_t(n), _p(outs) if n else None), "jolt_dory_products", self)
+    _call("jolt_dory_products", self, self.h, arr if n else None, n, _p(outs) if n else None)
     return [outs[k, :_DORY_RESULT_WIDTH[items[k].op]].copy() for k in range(n)]
 
 
@@ -1658,10 +1632,10 @@ def host_dory_batch_plan(lens):
     a = (C.c_size_t * max(n, 1))(*lens)
     base = (C.c_size_t * max(n, 1))()
     n_wgs, levels = C.c_size_t(), C.c_uint32()
-    _ck(lib().jolt_host_dory_batch_plan(a, C.c_size_t(n), C.c_size_t(0), None, None, base, C.byref(n_wgs), C.byref(levels)), "jolt_host_dory_batch_plan")
+    _call("jolt_host_dory_batch_plan", None, a, n, 0, None, None, base, C.byref(n_wgs), C.byref(levels))
     w = n_wgs.value
     wg_item, wg_first = np.zeros(max(w, 1), dtype=np.uint32), np.zeros(max(w, 1), dtype=np.uint32)
-    _ck(lib().jolt_host_dory_batch_plan(a, C.c_size_t(n), C.c_size_t(max(w, 1)), _p(wg_item), _p(wg_first), base, C.byref(n_wgs), C.byref(levels)), "jolt_host_dory_batch_plan")
+    _call("jolt_host_dory_batch_plan", None, a, n, max(w, 1), _p(wg_item), _p(wg_first), base, C.byref(n_wgs), C.byref(levels))
     return wg_item[:w], wg_first[:w], [int(b) for b in base[:n]], levels.value
 
 
@@ -1678,9 +1652,7 @@ Context.dory_state_fixed_base_mul = _dory_state_fixed_base_mul
 
 
 # ---- Dory evaluation proofs as one call (dory_scheme.hip): the setup object, a round's update as one call, the opening under Fiat-Shamir, the byte forms
-DORY_UPDATE_BETA, DORY_UPDATE_ALPHA = range(2)
-DORY_PHASE_VMV, DORY_PHASE_FIRST, DORY_PHASE_SECOND, DORY_PHASE_GAMMA, DORY_PHASE_FINAL = range(5)
-DORY_TRANSCRIPT_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p)
+DORY_TRANSCRIPT_FN = abi.CALLBACK_TYPES["jolt_dory_transcript_fn"]
 
 
 def _dory_view_arrays(views):
@@ -1702,9 +1674,9 @@ class DoryLibSetup:
         self.ctx, self.h = ctx, C.c_void_p()
         self.h1 = np.ascontiguousarray(h1, dtype=np.uint64).reshape(12).copy()
         self.h2 = np.ascontiguousarray(h2, dtype=np.uint64).reshape(24).copy()
-        _ck(lib().jolt_dory_setup_create(ctx.h, _p(g1), _p(g2), C.c_size_t(g1.shape[0]), _p(self.h1), _p(self.h2), C.byref(self.h)), "jolt_dory_setup_create", ctx)
+        _call("jolt_dory_setup_create", ctx, ctx.h, _p(g1), _p(g2), g1.shape[0], _p(self.h1), _p(self.h2), C.byref(self.h))
         n = C.c_size_t()
-        _ck(lib().jolt_dory_setup_size(self.h, C.byref(n)), "jolt_dory_setup_size", ctx)
+        _call("jolt_dory_setup_size", ctx, self.h, C.byref(n))
         self.n = n.value
 
     def tier2(self, hints):
@@ -1712,12 +1684,12 @@ class DoryLibSetup:
         views = [_dory_view(h) for h in hints]
         hs, firsts, rows = _dory_view_arrays(views)
         outs = np.zeros((max(len(views), 1), 48), dtype=np.uint64)
-        _ck(lib().jolt_dory_setup_tier2(self.ctx.h, self.h, hs, firsts, rows, C.c_size_t(len(views)), _p(outs)), "jolt_dory_setup_tier2", self.ctx)
+        _call("jolt_dory_setup_tier2", self.ctx, self.ctx.h, self.h, hs, firsts, rows, len(views), _p(outs))
         return [outs[k].copy() for k in range(len(views))]
 
     def close(self):
         if self.h:
-            _ck(lib().jolt_dory_setup_free(self.ctx.h, self.h), "jolt_dory_setup_free", self.ctx)
+            _call("jolt_dory_setup_free", self.ctx, self.ctx.h, self.h)
             self.h = None
 
     free = close
@@ -1731,14 +1703,13 @@ def _dory_round_update(self, mode, v1, v2, a, b, scalar, scalar_inv):
     if len({n for _, _, n in views}) != 1:
         raise ValueError("the four views of a round update have one length")
     (v1v, v1f, n), (v2v, v2f, _), (av, af, _), (bv, bf, _) = views
-    _ck(lib().jolt_dory_round_update(self.h, C.c_int32(mode), v1v.h, C.c_size_t(v1f), v2v.h, C.c_size_t(v2f), av.h, C.c_size_t(af), bv.h, C.c_size_t(bf), C.c_size_t(n),
-                                     _p(fr(scalar)), _p(fr(scalar_inv))), "jolt_dory_round_update", self)
+    _call("jolt_dory_round_update", self, self.h, mode, v1v.h, v1f, v2v.h, v2f, av.h, af, bv.h, bf, n, _p(fr(scalar)), _p(fr(scalar_inv)))
 
 
 def host_dory_proof_counts(sigma):
     """(GT elements, G1 points, G2 points, challenges) of an opening of 2^sigma columns (jolt_host_dory_proof_counts)"""
     c = [C.c_size_t() for _ in range(4)]
-    _ck(lib().jolt_host_dory_proof_counts(C.c_uint32(sigma), *[C.byref(x) for x in c]), "jolt_host_dory_proof_counts")
+    _call("jolt_host_dory_proof_counts", None, sigma, *[C.byref(x) for x in c])
     return tuple(x.value for x in c)
 
 
@@ -1755,10 +1726,10 @@ def _dory_open(self, setup, hints, scalars, v_table, left, right, nu, sigma, tra
         raise ValueError("one scalar per hint")
     n_gt, n_g1, n_g2, n_ch = host_dory_proof_counts(sigma)
     gts, g1s, g2s, ch = np.zeros((n_gt, 48), dtype=np.uint64), np.zeros((n_g1, 12), dtype=np.uint64), np.zeros((n_g2, 24), dtype=np.uint64), fr_array(n_ch)
-    head = (self.h, setup.h, hs, firsts, rows, C.c_size_t(len(views)), _p(sc), v_table.h, left.h, right.h, C.c_uint32(nu), C.c_uint32(sigma))
+    head = (self.h, setup.h, hs, firsts, rows, len(views), _p(sc), v_table.h, left.h, right.h, nu, sigma)
     tail = (_p(gts), _p(g1s), _p(g2s), _p(ch))
     if transcript is not None:
-        _ck(lib().jolt_host_dory_open(*head, transcript.h, *tail), "jolt_host_dory_open", self)
+        _call("jolt_host_dory_open", self, *head, transcript.h, *tail)
     else:
         err = []
 
@@ -1786,13 +1757,13 @@ def _dory_open(self, setup, hints, scalars, v_table, left, right, nu, sigma, tra
 
 def host_g2_serialize_compressed(p):
     out = (C.c_uint8 * 64)()
-    _ck(lib().jolt_host_g2_serialize_compressed(_p(np.ascontiguousarray(p, dtype=np.uint64)), out), "jolt_host_g2_serialize_compressed")
+    _call("jolt_host_g2_serialize_compressed", None, _p(np.ascontiguousarray(p, dtype=np.uint64)), out)
     return bytes(out)
 
 
 def host_gt_serialize(f):
     out = (C.c_uint8 * 384)()
-    _ck(lib().jolt_host_gt_serialize(_p(np.ascontiguousarray(f, dtype=np.uint64)), out), "jolt_host_gt_serialize")
+    _call("jolt_host_gt_serialize", None, _p(np.ascontiguousarray(f, dtype=np.uint64)), out)
     return bytes(out)
 
 
@@ -1800,11 +1771,11 @@ def host_dory_transcript_append(transcript, element):
     """one group element as JoltToDoryTranscript::append_group absorbs it; the kind by the element's width: (48,) GT, (12,) G1, (24,) G2"""
     e = np.ascontiguousarray(element, dtype=np.uint64).reshape(-1)
     if e.size == 48:
-        _ck(lib().jolt_host_dory_transcript_append_gt(transcript.h, _p(e)), "jolt_host_dory_transcript_append_gt")
+        _call("jolt_host_dory_transcript_append_gt", None, transcript.h, _p(e))
     elif e.size == 12:
-        _ck(lib().jolt_host_dory_transcript_append_g1(transcript.h, _p(e)), "jolt_host_dory_transcript_append_g1")
+        _call("jolt_host_dory_transcript_append_g1", None, transcript.h, _p(e))
     elif e.size == 24:
-        _ck(lib().jolt_host_dory_transcript_append_g2(transcript.h, _p(e)), "jolt_host_dory_transcript_append_g2")
+        _call("jolt_host_dory_transcript_append_g2", None, transcript.h, _p(e))
     else:
         raise ValueError("a GT element has 48 words, a G1 point 12, a G2 point 24")
 
@@ -1814,14 +1785,14 @@ def host_opening_statement_absorb(transcript, evaluations):
     -> (n, 4) the RLC scalars 1, gamma, ..., gamma^(n - 1) of the ONE challenge_scalar that follows"""
     v = fr(evaluations).reshape(-1, 4)
     out = fr_array(max(v.shape[0], 1))
-    _ck(lib().jolt_host_opening_statement_absorb(transcript.h, _p(v), C.c_size_t(v.shape[0]), _p(out)), "jolt_host_opening_statement_absorb")
+    _call("jolt_host_opening_statement_absorb", None, transcript.h, _p(v), v.shape[0], _p(out))
     return out[:v.shape[0]]
 
 
 def host_opening_claim_absorb(transcript, point, value):
     """the closing claim (jolt_host_opening_claim_absorb): LabelWithCount(b"opening_point", len(point)), the coordinates in order, Label(b"opening_eval"), the value"""
     p = fr(point).reshape(-1, 4)
-    _ck(lib().jolt_host_opening_claim_absorb(transcript.h, _p(p) if p.shape[0] else None, C.c_size_t(p.shape[0]), _p(fr(value).reshape(4))), "jolt_host_opening_claim_absorb")
+    _call("jolt_host_opening_claim_absorb", None, transcript.h, _p(p) if p.shape[0] else None, p.shape[0], _p(fr(value).reshape(4)))
 
 
 def _dory_prove_batch(self, setup, hints, evaluations, sources, dense, log_k, point, transcript, column_of_claim=None):
@@ -1844,9 +1815,8 @@ def _dory_prove_batch(self, setup, hints, evaluations, sources, dense, log_k, po
     order = None if column_of_claim is None else (C.c_size_t * max(len(column_of_claim), 1))(*[int(c) for c in column_of_claim])
     if order is not None and len(column_of_claim) != len(views):
         raise ValueError("one column per claim")
-    _ck(lib().jolt_host_dory_prove_batch(self.h, setup.h, hs, firsts, rows, C.c_size_t(len(views)), _p(ev), ss if sources else None, C.c_size_t(len(sources)),
-                                         ds if dense else None, C.c_size_t(len(dense)), C.c_uint32(log_k), order, _p(pt), C.c_size_t(pt.shape[0]), transcript.h,
-                                         _p(gts), _p(g1s), _p(g2s), _p(ch), _p(scalars), _p(joint)), "jolt_host_dory_prove_batch", self)
+    _call("jolt_host_dory_prove_batch", self, self.h, setup.h, hs, firsts, rows, len(views), _p(ev), ss if sources else None, len(sources), ds if dense else None, len(dense),
+          log_k, order, _p(pt), pt.shape[0], transcript.h, _p(gts), _p(g1s), _p(g2s), _p(ch), _p(scalars), _p(joint))
     return dict(gts=gts, g1s=g1s, g2s=g2s, challenges=ch, scalars=scalars[:len(views)], joint_eval=joint[0], nu=pt.shape[0] - sigma, sigma=sigma)
 
 
@@ -1858,8 +1828,7 @@ def _grid_evaluate_columns(self, sources, dense, log_k, point):
     out = fr_array(max(n, 1))
     ss = (C.c_void_p * max(len(sources), 1))(*[s.h for s in sources])
     ds = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
-    _ck(lib().jolt_grid_evaluate_columns(self.h, ss if sources else None, C.c_size_t(len(sources)), ds if dense else None, C.c_size_t(len(dense)), C.c_uint32(log_k),
-                                         _p(pt), C.c_size_t(pt.shape[0]), _p(out)), "jolt_grid_evaluate_columns", self)
+    _call("jolt_grid_evaluate_columns", self, self.h, ss if sources else None, len(sources), ds if dense else None, len(dense), log_k, _p(pt), pt.shape[0], _p(out))
     return out[:n]
 
 
@@ -1875,14 +1844,13 @@ def _dory_hints_onehot(self, srs, source, out, chunk_width, first_poly=0, n_poly
     """the hints of columns [first_poly, first_poly + n_polys) of a OneHot into the G1 vector `out` from element out_first on (jolt_dory_hints_onehot):
     out[out_first + p * k * chunks + row * chunks + chunk]; enqueued, not awaited.  The number of elements written."""
     n_polys = source.n_polys - first_poly if n_polys is None else n_polys
-    _ck(lib().jolt_dory_hints_onehot(self.h, srs.h, source.h, C.c_size_t(first_poly), C.c_size_t(n_polys), C.c_size_t(chunk_width), out.h, C.c_size_t(out_first),
-                                     C.c_size_t(batch_points)), "jolt_dory_hints_onehot", self)
+    _call("jolt_dory_hints_onehot", self, self.h, srs.h, source.h, first_poly, n_polys, chunk_width, out.h, out_first, batch_points)
     return n_polys * source.k * (source.cycles // chunk_width)
 
 
 def _dory_hints_rows(self, srs, values, row_width, out, out_first=0):
     """the row commitments of dory_commit_rows into the G1 vector `out` from element out_first on, normalised (jolt_dory_hints_rows).  The number of rows."""
-    _ck(lib().jolt_dory_hints_rows(self.h, srs.h, values.h, C.c_size_t(row_width), out.h, C.c_size_t(out_first)), "jolt_dory_hints_rows", self)
+    _call("jolt_dory_hints_rows", self, self.h, srs.h, values.h, row_width, out.h, out_first)
     return values.count // row_width
 
 
@@ -1890,14 +1858,14 @@ def host_dory_g1_normalise(points, run):
     """the per-lane routine of the hint kernel on the host: every point as (x / z^2, y / z^3, 1), the identity as (1, 1, 0), one inversion per `run` points"""
     pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
     out = g1_array(max(pts.shape[0], 1))
-    _ck(lib().jolt_host_dory_g1_normalise(_p(pts) if pts.shape[0] else None, C.c_size_t(pts.shape[0]), C.c_size_t(run), _p(out)), "jolt_host_dory_g1_normalise")
+    _call("jolt_host_dory_g1_normalise", None, _p(pts) if pts.shape[0] else None, pts.shape[0], run, _p(out))
     return out[:pts.shape[0]]
 
 
 def host_dory_hint_map(k, chunks, window0, e):
     """the hint kernel's index map for one-hot columns: (workspace bucket, hint element) of element e of a launch set that starts at window0"""
     src, dst = C.c_size_t(), C.c_size_t()
-    _ck(lib().jolt_host_dory_hint_map(C.c_uint32(k), C.c_size_t(chunks), C.c_size_t(window0), C.c_size_t(e), C.byref(src), C.byref(dst)), "jolt_host_dory_hint_map")
+    _call("jolt_host_dory_hint_map", None, k, chunks, window0, e, C.byref(src), C.byref(dst))
     return src.value, dst.value
 
 
@@ -1910,14 +1878,13 @@ def _dory_hints_onehot_am(self, srs, source, out, sigma, log_block, log_stride=0
     """the address-major hints of columns [first_poly, first_poly + n_polys) of a OneHot into the G1 vector `out` (jolt_dory_hints_onehot_am):
     out[out_first + p * rows + r], rows = cycles >> (sigma - log_block); enqueued, not awaited.  The number of elements written."""
     n_polys = source.n_polys - first_poly if n_polys is None else n_polys
-    _ck(lib().jolt_dory_hints_onehot_am(self.h, srs.h, source.h, C.c_size_t(first_poly), C.c_size_t(n_polys), C.c_uint32(sigma), C.c_uint32(log_block),
-                                        C.c_uint32(log_stride), out.h, C.c_size_t(out_first)), "jolt_dory_hints_onehot_am", self)
+    _call("jolt_dory_hints_onehot_am", self, self.h, srs.h, source.h, first_poly, n_polys, sigma, log_block, log_stride, out.h, out_first)
     return n_polys * (source.cycles >> (sigma - log_block))
 
 
 def _dory_hints_rows_am(self, srs, values, sigma, log_block, out, out_first=0):
     """the address-major row commitments of a dense column, out[out_first + r] = sum_j values[r C + j] * srs[j << log_block], normalised (jolt_dory_hints_rows_am)"""
-    _ck(lib().jolt_dory_hints_rows_am(self.h, srs.h, values.h, C.c_uint32(sigma), C.c_uint32(log_block), out.h, C.c_size_t(out_first)), "jolt_dory_hints_rows_am", self)
+    _call("jolt_dory_hints_rows_am", self, self.h, srs.h, values.h, sigma, log_block, out.h, out_first)
     return values.count >> (sigma - log_block)
 
 
@@ -1928,16 +1895,15 @@ def _dory_fold_rows_grid_am(self, sources, onehot_scalars, dense, dense_scalars,
     osc = fr(np.stack([fr(c) for c in onehot_scalars])).reshape(-1, 4) if len(onehot_scalars) else None
     dsc = fr(np.stack([fr(c) for c in dense_scalars])).reshape(-1, 4) if len(dense_scalars) else None
     h = C.c_void_p()
-    _ck(lib().jolt_dory_fold_rows_grid_am(self.h, hs if sources else None, C.c_size_t(len(sources)), _p(osc), ds if dense else None, C.c_size_t(len(dense)),
-                                          _p(dsc), C.c_uint32(log_block), C.c_uint32(log_stride), C.c_uint32(sigma), left.h, C.byref(h)), "jolt_dory_fold_rows_grid_am", self)
+    _call("jolt_dory_fold_rows_grid_am", self, self.h, hs if sources else None, len(sources), _p(osc), ds if dense else None, len(dense), _p(dsc), log_block, log_stride,
+          sigma, left.h, C.byref(h))
     return Table(self, h)
 
 
 def host_dory_am_place(log_block, log_stride, sigma, cycle, address):
     """(row, column) of the coefficient of (cycle, address) in the address-major matrix of 2^sigma columns"""
     row, col = C.c_size_t(), C.c_size_t()
-    _ck(lib().jolt_host_dory_am_place(C.c_uint32(log_block), C.c_uint32(log_stride), C.c_uint32(sigma), C.c_size_t(cycle), C.c_size_t(address), C.byref(row), C.byref(col)),
-        "jolt_host_dory_am_place")
+    _call("jolt_host_dory_am_place", None, log_block, log_stride, sigma, cycle, address, C.byref(row), C.byref(col))
     return row.value, col.value
 
 
@@ -1947,8 +1913,7 @@ def host_dory_am_row(bases, hot, k, log_block, log_stride=0):
     pts = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, 12)
     idx = np.ascontiguousarray(hot, dtype=np.uint16)
     out = g1_array(1)
-    _ck(lib().jolt_host_dory_am_row(_p(pts), C.c_size_t(pts.shape[0]), idx.ctypes.data_as(C.c_void_p) if idx.size else None, C.c_size_t(idx.size), C.c_uint32(k),
-                                    C.c_uint32(log_block), C.c_uint32(log_stride), _p(out)), "jolt_host_dory_am_row")
+    _call("jolt_host_dory_am_row", None, _p(pts), pts.shape[0], idx.ctypes.data_as(C.c_void_p) if idx.size else None, idx.size, k, log_block, log_stride, _p(out))
     return out[0]
 
 
@@ -1966,15 +1931,14 @@ def _dory_commit_rows_fr(self, srs, table, row_width, first=0, count=None):
     count = len(table) - first if count is None else count
     rows = count // row_width if row_width else 0
     out = g1_array(max(rows, 1))
-    _ck(lib().jolt_dory_commit_rows_fr(self.h, srs.h, table.h, C.c_size_t(first), C.c_size_t(count), C.c_size_t(row_width), _p(out)), "jolt_dory_commit_rows_fr", self)
+    _call("jolt_dory_commit_rows_fr", self, self.h, srs.h, table.h, first, count, row_width, _p(out))
     return out[:rows]
 
 
 def _dory_hints_rows_fr(self, srs, table, row_width, out, out_first=0, first=0, count=None):
     """the same rows, normalised, into the G1 vector `out` from element out_first on (jolt_dory_hints_rows_fr).  The number of rows."""
     count = len(table) - first if count is None else count
-    _ck(lib().jolt_dory_hints_rows_fr(self.h, srs.h, table.h, C.c_size_t(first), C.c_size_t(count), C.c_size_t(row_width), out.h, C.c_size_t(out_first)),
-        "jolt_dory_hints_rows_fr", self)
+    _call("jolt_dory_hints_rows_fr", self, self.h, srs.h, table.h, first, count, row_width, out.h, out_first)
     return count // row_width
 
 
@@ -1988,8 +1952,7 @@ def _dory_fold_rows_blocks(self, tables, sigma_tables, scalars, sigma, left, bas
     sg = (C.c_uint32 * max(n, 1))(*sigma_tables)
     sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if n else fr_array(1)
     h = C.c_void_p()
-    _ck(lib().jolt_dory_fold_rows_blocks(self.h, hs, sg, C.c_size_t(n), _p(sc), C.c_uint32(sigma), left.h, base.h if base is not None else None, C.byref(h)),
-        "jolt_dory_fold_rows_blocks", self)
+    _call("jolt_dory_fold_rows_blocks", self, self.h, hs, sg, n, _p(sc), sigma, left.h, base.h if base is not None else None, C.byref(h))
     return Table(self, h)
 
 
@@ -1997,21 +1960,21 @@ def host_dory_fr_digits(scalar, c, W):
     """the signed c-bit digits the field-row kernels give one scalar: ([digit_w for w < W], negative) with sum_w digit_w 2^(c w) = min(s, r - s) and
     negative = whether r - s was taken"""
     digits, neg = np.zeros(max(W, 1), dtype=np.uint32), C.c_uint32()
-    _ck(lib().jolt_host_dory_fr_digits(_p(fr(scalar)), C.c_int32(c), C.c_int32(W), _p(digits), C.byref(neg)), "jolt_host_dory_fr_digits")
+    _call("jolt_host_dory_fr_digits", None, _p(fr(scalar)), c, W, _p(digits), C.byref(neg))
     return [-(int(d) & 0x7FFFFFFF) if int(d) >> 31 else int(d) for d in digits[:W]], bool(neg.value)
 
 
 def host_dory_rows_fr_plan(bit_length, row_width):
     """(c, W) of the field rows for magnitudes of bit_length bits in rows of row_width values"""
     c, W = C.c_int32(), C.c_int32()
-    _ck(lib().jolt_host_dory_rows_fr_plan(C.c_uint32(bit_length), C.c_size_t(row_width), C.byref(c), C.byref(W)), "jolt_host_dory_rows_fr_plan")
+    _call("jolt_host_dory_rows_fr_plan", None, bit_length, row_width, C.byref(c), C.byref(W))
     return c.value, W.value
 
 
 def host_dory_block_index(sigma_table, sigma_grid, i):
     """grid index of coefficient i of a block of 2^sigma_table columns embedded top-left in a grid of 2^sigma_grid columns"""
     out = C.c_size_t()
-    _ck(lib().jolt_host_dory_block_index(C.c_uint32(sigma_table), C.c_uint32(sigma_grid), C.c_size_t(i), C.byref(out)), "jolt_host_dory_block_index")
+    _call("jolt_host_dory_block_index", None, sigma_table, sigma_grid, i, C.byref(out))
     return out.value
 
 
@@ -2027,14 +1990,14 @@ def _gt(a):
 def host_fq12_op(op, a, b=None):
     """Fq12 on the host as the kernels compute it; raises JoltError(1) for an operand that is not canonical, JoltError(11) for the inverse of zero"""
     out = gt_array()
-    _ck(lib().jolt_host_fq12_op(C.c_int32(op), _p(_gt(a)), _p(_gt(b)) if b is not None else None, _p(out)), "jolt_host_fq12_op")
+    _call("jolt_host_fq12_op", None, op, _p(_gt(a)), _p(_gt(b)) if b is not None else None, _p(out))
     return out
 
 
 def host_g2_prepare_one(g2):
     """-> ((PAIRING_LINES, 3, 8) uint64 line coefficients (a, b, c), skip)"""
     lines, skip = np.zeros((PAIRING_LINES, 3, 8), dtype=np.uint64), C.c_int32()
-    _ck(lib().jolt_host_g2_prepare_one(_p(np.ascontiguousarray(g2, dtype=np.uint64).reshape(24)), _p(lines), C.byref(skip)), "jolt_host_g2_prepare_one")
+    _call("jolt_host_g2_prepare_one", None, _p(np.ascontiguousarray(g2, dtype=np.uint64).reshape(24)), _p(lines), C.byref(skip))
     return lines, bool(skip.value)
 
 
@@ -2044,19 +2007,19 @@ def host_miller_loop(g1s, g2s):
     if a.shape[0] != b.shape[0]:
         raise ValueError("miller_loop: the two sides differ in length")
     n, out = a.shape[0], gt_array()
-    _ck(lib().jolt_host_miller_loop(_p(a) if n else None, _p(b) if n else None, C.c_size_t(n), _p(out)), "jolt_host_miller_loop")
+    _call("jolt_host_miller_loop", None, _p(a) if n else None, _p(b) if n else None, n, _p(out))
     return out
 
 
 def host_final_exponentiation(f):
     out = gt_array()
-    _ck(lib().jolt_host_final_exponentiation(_p(_gt(f)), _p(out)), "jolt_host_final_exponentiation")
+    _call("jolt_host_final_exponentiation", None, _p(_gt(f)), _p(out))
     return out
 
 
 def host_gt_pow(gt, scalar):
     out = gt_array()
-    _ck(lib().jolt_host_gt_pow(_p(_gt(gt)), _p(fr(scalar)), _p(out)), "jolt_host_gt_pow")
+    _call("jolt_host_gt_pow", None, _p(_gt(gt)), _p(fr(scalar)), _p(out))
     return out
 
 
@@ -2065,7 +2028,7 @@ def host_hyperkzg_witness_triple(c, g0, g1, r, a, alpha):
     cs = np.ascontiguousarray(c, dtype=np.uint64).reshape(3, 12)
     p0, p1 = (np.ascontiguousarray(p, dtype=np.uint64).reshape(12) for p in (g0, g1))
     out = g1_array(3)
-    _ck(lib().jolt_host_hyperkzg_witness_triple(_p(cs), _p(p0), _p(p1), _p(fr(r)), _p(fr(a)), _p(fr(alpha)), _p(out)), "jolt_host_hyperkzg_witness_triple")
+    _call("jolt_host_hyperkzg_witness_triple", None, _p(cs), _p(p0), _p(p1), _p(fr(r)), _p(fr(a)), _p(fr(alpha)), _p(out))
     return out
 
 
@@ -2076,20 +2039,20 @@ Context.dory_combine_hints = _dory_combine_hints
 def _table_op2(name):
     def f(self, a, b):
         h = C.c_void_p()
-        _ck(getattr(lib(), name)(self.h, a.h, b.h, C.byref(h)), name, self)
+        _call(name, self, self.h, a.h, b.h, C.byref(h))
         return Table(self, h)
     return f
 
 
 def _tile(self, base, copies):
     h = C.c_void_p()
-    _ck(lib().jolt_tile(self.h, base.h, C.c_size_t(copies), C.byref(h)), "jolt_tile", self)
+    _call("jolt_tile", self, self.h, base.h, copies, C.byref(h))
     return Table(self, h)
 
 
 def _replicate_stream_lsb(self, base):
     h = C.c_void_p()
-    _ck(lib().jolt_replicate_stream_lsb(self.h, base.h, C.byref(h)), "jolt_replicate_stream_lsb", self)
+    _call("jolt_replicate_stream_lsb", self, self.h, base.h, C.byref(h))
     return Table(self, h)
 
 
@@ -2097,7 +2060,7 @@ def _rlc(self, tables, scalars):
     hs = (C.c_void_p * len(tables))(*[t.h for t in tables])
     sc = fr(scalars).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_rlc(self.h, hs, C.c_size_t(len(tables)), _p(sc), C.byref(h)), "jolt_rlc", self)
+    _call("jolt_rlc", self, self.h, hs, len(tables), _p(sc), C.byref(h))
     return Table(self, h)
 
 
@@ -2113,21 +2076,21 @@ def _table_from_ints(self, values, offset=0, length=None):
     """Ring::from_u64 / from_i64 / from_i128 of entries [offset, offset+length) of an Ints (already in HBM) as a field table."""
     length = values.count - offset if length is None else length
     h = C.c_void_p()
-    _ck(lib().jolt_table_from_ints(self.h, values.h, C.c_size_t(offset), C.c_size_t(length), C.byref(h)), "jolt_table_from_ints", self)
+    _call("jolt_table_from_ints", self, self.h, values.h, offset, length, C.byref(h))
     return Table(self, h)
 
 
 def _grid_commit_onehot(self, srs, source):
     """KZG commitments of the one-hot columns of `source` over the K x T commitment grid (index k*T + j): (n_polys, 12)."""
     out = g1_array(source.n_polys)
-    _ck(lib().jolt_grid_commit_onehot(self.h, srs.h, source.h, _p(out)), "jolt_grid_commit_onehot", self)
+    _call("jolt_grid_commit_onehot", self, self.h, srs.h, source.h, _p(out))
     return out
 
 
 def _grid_commit_onehot_classes(self, srs, source, shift):
     """(2^shift, n_polys, 12): per residue class c of the cycle mod 2^shift the sums of the bases at (hot * T + j) >> shift (jolt_grid_commit_onehot_classes)"""
     out = g1_array(source.n_polys << shift)
-    _ck(lib().jolt_grid_commit_onehot_classes(self.h, srs.h, source.h, C.c_uint32(shift), _p(out)), "jolt_grid_commit_onehot_classes", self)
+    _call("jolt_grid_commit_onehot_classes", self, self.h, srs.h, source.h, shift, _p(out))
     return out.reshape(1 << shift, source.n_polys, 12)
 
 
@@ -2138,8 +2101,7 @@ def _grid_joint_polynomial(self, sources, onehot_scalars, dense, dense_scalars, 
     osc = fr(np.stack([fr(c) for c in onehot_scalars])).reshape(-1, 4) if len(onehot_scalars) else None
     dsc = fr(np.stack([fr(c) for c in dense_scalars])).reshape(-1, 4) if len(dense_scalars) else None
     h = C.c_void_p()
-    _ck(lib().jolt_grid_joint_polynomial(self.h, hs if sources else None, C.c_size_t(len(sources)), _p(osc), ds if dense else None, C.c_size_t(len(dense)),
-                                         _p(dsc), C.c_uint32(log_k), C.byref(h)), "jolt_grid_joint_polynomial", self)
+    _call("jolt_grid_joint_polynomial", self, self.h, hs if sources else None, len(sources), _p(osc), ds if dense else None, len(dense), _p(dsc), log_k, C.byref(h))
     return Table(self, h)
 
 
@@ -2150,33 +2112,32 @@ def _grid_joint_polynomial_subtree(self, sources, onehot_scalars, dense, dense_s
     osc = fr(np.stack([fr(c) for c in onehot_scalars])).reshape(-1, 4) if len(onehot_scalars) else None
     dsc = fr(np.stack([fr(c) for c in dense_scalars])).reshape(-1, 4) if len(dense_scalars) else None
     h = C.c_void_p()
-    _ck(lib().jolt_grid_joint_polynomial_subtree(self.h, hs if sources else None, C.c_size_t(len(sources)), _p(osc), ds if dense else None, C.c_size_t(len(dense)),
-                                                 _p(dsc), C.c_uint32(log_k), C.c_int32(rank), C.c_int32(world), C.byref(h)), "jolt_grid_joint_polynomial_subtree", self)
+    _call("jolt_grid_joint_polynomial_subtree", self, self.h, hs if sources else None, len(sources), _p(osc), ds if dense else None, len(dense), _p(dsc), log_k, rank, world,
+          C.byref(h))
     return Table(self, h)
 
 
 def _trim(self):
-    _ck(lib().jolt_ctx_trim(self.h), "jolt_ctx_trim", self)
+    _call("jolt_ctx_trim", self, self.h)
 
 
 def _memory_stats(self):
     a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
-    _ck(lib().jolt_ctx_memory_stats(self.h, C.byref(a), C.byref(b), C.byref(c)), "jolt_ctx_memory_stats", self)
+    _call("jolt_ctx_memory_stats", self, self.h, C.byref(a), C.byref(b), C.byref(c))
     out = {"live_bytes": a.value, "cached_bytes": b.value, "peak_bytes": c.value}
     la, ba = C.c_size_t(), C.c_size_t()
-    _ck(lib().jolt_ctx_workspace_stats(self.h, C.byref(la), C.byref(ba)), "jolt_ctx_workspace_stats", self)
+    _call("jolt_ctx_workspace_stats", self, self.h, C.byref(la), C.byref(ba))
     out["msm_lanes_bytes"], out["msm_batch_bytes"] = la.value, ba.value  # outside the pool: grow-only MSM workspaces
     return out
 
 
-ROUND_PATH_COUNT = 17  # JOLT_ROUND_PATH_COUNT
 
 
 def _round_path_stats(self, reset=False):
     """Launch counts of the batch rounds per kernel path since the last reset (jolt_ctx_round_path_stats): `group` is keyed by (order, skip_one, fused),
     `split_eq_product` and `bind` are (unfused, fused) and (LowToHigh, HighToLow)."""
     a = np.zeros(ROUND_PATH_COUNT, dtype=np.uint64)
-    _ck(lib().jolt_ctx_round_path_stats(self.h, _p(a), C.c_size_t(ROUND_PATH_COUNT), C.c_int32(1 if reset else 0)), "jolt_ctx_round_path_stats", self)
+    _call("jolt_ctx_round_path_stats", self, self.h, _p(a), ROUND_PATH_COUNT, 1 if reset else 0)
     c = [int(x) for x in a]
     return {"tail": c[0], "group": {(o, bool(s), bool(f)): c[1 + 4 * o + 2 * s + f] for o in (0, 1) for s in (0, 1) for f in (0, 1)}, "small": c[9],
             "split_eq_product": (c[10], c[11]), "uniform_items": c[12], "uniform_rows": c[13], "lazy": c[14], "bind": (c[15], c[16])}
@@ -2202,37 +2163,35 @@ class RwMatrix:
         self.ctx = ctx
         h = C.c_void_p()
         if isinstance(addresses, Ints):
-            _ck(lib().jolt_rw_matrix_create_resident(ctx.h, addresses.h, pre.h, post.h, inc.h, val_init.h, _p(tau), _p(fr(gamma)), C.byref(h)),
-                "jolt_rw_matrix_create_resident", ctx)
+            _call("jolt_rw_matrix_create_resident", ctx, ctx.h, addresses.h, pre.h, post.h, inc.h, val_init.h, _p(tau), _p(fr(gamma)), C.byref(h))
         else:
             a, p, q = (np.ascontiguousarray(x, dtype=np.uint64) for x in (addresses, pre, post))
-            _ck(lib().jolt_rw_matrix_create(ctx.h, _p(a), _p(p), _p(q), C.c_size_t(a.shape[0]), inc.h, val_init.h, _p(tau), _p(fr(gamma)), C.byref(h)),
-                "jolt_rw_matrix_create", ctx)
+            _call("jolt_rw_matrix_create", ctx, ctx.h, _p(a), _p(p), _p(q), a.shape[0], inc.h, val_init.h, _p(tau), _p(fr(gamma)), C.byref(h))
         self.h = h
 
     def __len__(self):
         n = C.c_size_t()
-        _ck(lib().jolt_rw_matrix_len(self.h, C.byref(n)), "jolt_rw_matrix_len", self.ctx)
+        _call("jolt_rw_matrix_len", self.ctx, self.h, C.byref(n))
         return n.value
 
     def prove_round(self, bind=None):
         evals, aux = fr_array(2), fr_array(3)
-        _ck(lib().jolt_rw_matrix_prove_round(self.h, _p(fr(bind)) if bind is not None else None, _p(evals), _p(aux)), "jolt_rw_matrix_prove_round", self.ctx)
+        _call("jolt_rw_matrix_prove_round", self.ctx, self.h, _p(fr(bind)) if bind is not None else None, _p(evals), _p(aux))
         return evals, aux
 
     def finish(self, bind):
-        _ck(lib().jolt_rw_matrix_finish(self.h, _p(fr(bind))), "jolt_rw_matrix_finish", self.ctx)
+        _call("jolt_rw_matrix_finish", self.ctx, self.h, _p(fr(bind)))
 
     def final_values(self):
         out = fr_array(4)
-        _ck(lib().jolt_rw_matrix_final_values(self.h, _p(out)), "jolt_rw_matrix_final_values", self.ctx)
+        _call("jolt_rw_matrix_final_values", self.ctx, self.h, _p(out))
         return out
 
     def download(self):
         n = len(self)
         rows, cols = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
         val, ra, prev, nxt = fr_array(max(n, 1)), fr_array(max(n, 1)), fr_array(max(n, 1)), fr_array(max(n, 1))
-        _ck(lib().jolt_rw_matrix_download(self.h, _p(rows), _p(cols), _p(val), _p(ra), _p(prev), _p(nxt)), "jolt_rw_matrix_download", self.ctx)
+        _call("jolt_rw_matrix_download", self.ctx, self.h, _p(rows), _p(cols), _p(val), _p(ra), _p(prev), _p(nxt))
         return dict(rows=rows[:n], cols=cols[:n], val=val[:n], ra=ra[:n], prev=prev[:n], next=nxt[:n])
 
     def free(self):
@@ -2252,11 +2211,11 @@ Context.rw_matrix = lambda self, *a, **k: RwMatrix(self, *a, **k)
 
 # ---- the sharded form of both sparse matrices (jolt_rw_matrix_hold_row / _bind / _export_row / _create_merged): shared by RwMatrix and RegistersRw handles
 def rw_hold_row(m):
-    _ck(lib().jolt_rw_matrix_hold_row(m.h), "jolt_rw_matrix_hold_row", m.ctx)
+    _call("jolt_rw_matrix_hold_row", m.ctx, m.h)
 
 
 def rw_bind(m, bind):
-    _ck(lib().jolt_rw_matrix_bind(m.h, _p(fr(bind))), "jolt_rw_matrix_bind", m.ctx)
+    _call("jolt_rw_matrix_bind", m.ctx, m.h, _p(fr(bind)))
 
 
 def rw_export_row(m, registers):
@@ -2267,8 +2226,7 @@ def rw_export_row(m, registers):
     val, ra, wa = fr_array(cap), fr_array(cap), fr_array(cap)
     inc, scalar = fr_array(1), fr_array(1)
     got = C.c_size_t()
-    _ck(lib().jolt_rw_matrix_export_row(m.h, C.c_size_t(cap), _p(cols), _p(prev), _p(nxt), _p(val), _p(ra), _p(wa) if registers else None, _p(inc), _p(scalar), C.byref(got)),
-        "jolt_rw_matrix_export_row", m.ctx)
+    _call("jolt_rw_matrix_export_row", m.ctx, m.h, cap, _p(cols), _p(prev), _p(nxt), _p(val), _p(ra), _p(wa) if registers else None, _p(inc), _p(scalar), C.byref(got))
     n = got.value
     out = dict(cols=cols[:n], prev=prev[:n], next=nxt[:n], val=val[:n], ra=ra[:n], inc=inc[0], scalar=scalar[0])
     if registers:
@@ -2290,14 +2248,13 @@ class MergedRw:
         inc = u(inc).reshape(-1, 4)
         assert inc.shape[0] == 1 << log_rows
         h = C.c_void_p()
-        _ck(lib().jolt_rw_matrix_create_merged(ctx.h, C.c_int32(1 if registers else 0), C.c_size_t(log_rows), C.c_size_t(log_k), C.c_size_t(n), _p(rows), _p(cols), _p(prev), _p(nxt),
-                                               _p(val), _p(ra), _p(wa) if registers else None, _p(inc), val_init.h if val_init is not None else None,
-                                               _p(fr(w).reshape(-1, 4)), _p(fr(scalar)), _p(fr(gamma)), C.byref(h)), "jolt_rw_matrix_create_merged", ctx)
+        _call("jolt_rw_matrix_create_merged", ctx, ctx.h, 1 if registers else 0, log_rows, log_k, n, _p(rows), _p(cols), _p(prev), _p(nxt), _p(val), _p(ra),
+              _p(wa) if registers else None, _p(inc), val_init.h if val_init is not None else None, _p(fr(w).reshape(-1, 4)), _p(fr(scalar)), _p(fr(gamma)), C.byref(h))
         self.h = h
 
     def __len__(self):
         n = C.c_size_t()
-        _ck(lib().jolt_rw_matrix_len(self.h, C.byref(n)), "jolt_rw_matrix_len", self.ctx)
+        _call("jolt_rw_matrix_len", self.ctx, self.h, C.byref(n))
         return n.value
 
     def prove_round(self, bind=None):
@@ -2307,7 +2264,7 @@ class MergedRw:
         return evals, aux
 
     def finish(self, bind):
-        _ck(lib().jolt_rw_matrix_finish(self.h, _p(fr(bind))), "jolt_rw_matrix_finish", self.ctx)
+        _call("jolt_rw_matrix_finish", self.ctx, self.h, _p(fr(bind)))
 
     def final_values(self):
         out = fr_array(5 if self.registers else 4)
@@ -2334,12 +2291,12 @@ class KeyIndex:
     def __init__(self, ctx, keys, k):
         self.ctx, self.k = ctx, int(k)
         h = C.c_void_p()
-        _ck(lib().jolt_key_index_create(ctx.h, keys.h, C.c_uint64(self.k), C.byref(h)), "jolt_key_index_create", ctx)
+        _call("jolt_key_index_create", ctx, ctx.h, keys.h, self.k, C.byref(h))
         self.h = h
 
     def size(self):
         cycles, k, items = C.c_size_t(), C.c_uint64(), C.c_uint32()
-        _ck(lib().jolt_key_index_size(self.h, C.byref(cycles), C.byref(k), C.byref(items)), "jolt_key_index_size", self.ctx)
+        _call("jolt_key_index_size", self.ctx, self.h, C.byref(cycles), C.byref(k), C.byref(items))
         return cycles.value, k.value, items.value
 
     def pushforward(self, weights):
@@ -2347,13 +2304,13 @@ class KeyIndex:
         n = len(weights)
         hs = (C.c_void_p * n)(*[w.h for w in weights])
         out = (C.c_void_p * n)()
-        _ck(lib().jolt_key_index_pushforward(self.ctx.h, self.h, hs, C.c_size_t(n), out), "jolt_key_index_pushforward", self.ctx)
+        _call("jolt_key_index_pushforward", self.ctx, self.ctx.h, self.h, hs, n, out)
         return [Table(self.ctx, C.c_void_p(out[i])) for i in range(n)]
 
     def last_value(self, values, init):
         """values: u64 Ints over the cycles; init: Table of k entries -> Table: the value at the latest cycle of every key, init where a key never occurs"""
         h = C.c_void_p()
-        _ck(lib().jolt_key_index_last_value(self.ctx.h, self.h, values.h, init.h, C.byref(h)), "jolt_key_index_last_value", self.ctx)
+        _call("jolt_key_index_last_value", self.ctx, self.ctx.h, self.h, values.h, init.h, C.byref(h))
         return Table(self.ctx, h)
 
     def free(self):
@@ -2378,33 +2335,32 @@ class RegistersRw:
     def __init__(self, ctx, regs, rs1_val, rs2_val, rd_pre, rd_post, inc, r_cycle, gamma):
         self.ctx, self.regs = ctx, regs
         h = C.c_void_p()
-        _ck(lib().jolt_registers_rw_create(ctx.h, regs.h, rs1_val.h, rs2_val.h, rd_pre.h, rd_post.h, inc.h, _p(fr(r_cycle).reshape(-1, 4)), _p(fr(gamma)), C.byref(h)),
-            "jolt_registers_rw_create", ctx)
+        _call("jolt_registers_rw_create", ctx, ctx.h, regs.h, rs1_val.h, rs2_val.h, rd_pre.h, rd_post.h, inc.h, _p(fr(r_cycle).reshape(-1, 4)), _p(fr(gamma)), C.byref(h))
         self.h = h
 
     def __len__(self):
         n = C.c_size_t()
-        _ck(lib().jolt_rw_matrix_len(self.h, C.byref(n)), "jolt_rw_matrix_len", self.ctx)
+        _call("jolt_rw_matrix_len", self.ctx, self.h, C.byref(n))
         return n.value
 
     def prove_round(self, bind=None):
         evals, aux = fr_array(4), fr_array(3)
-        _ck(lib().jolt_registers_rw_prove_round(self.h, _p(fr(bind)) if bind is not None else None, _p(evals), _p(aux)), "jolt_registers_rw_prove_round", self.ctx)
+        _call("jolt_registers_rw_prove_round", self.ctx, self.h, _p(fr(bind)) if bind is not None else None, _p(evals), _p(aux))
         return evals, aux
 
     def finish(self, bind):
-        _ck(lib().jolt_rw_matrix_finish(self.h, _p(fr(bind))), "jolt_rw_matrix_finish", self.ctx)
+        _call("jolt_rw_matrix_finish", self.ctx, self.h, _p(fr(bind)))
 
     def final_values(self):
         out = fr_array(5)
-        _ck(lib().jolt_registers_rw_final_values(self.h, _p(out)), "jolt_registers_rw_final_values", self.ctx)
+        _call("jolt_registers_rw_final_values", self.ctx, self.h, _p(out))
         return out
 
     def download(self):
         n = len(self)
         rows, cols, prev, nxt = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(4))
         val, ra, wa = fr_array(max(n, 1)), fr_array(max(n, 1)), fr_array(max(n, 1))
-        _ck(lib().jolt_registers_rw_download(self.h, _p(rows), _p(cols), _p(val), _p(ra), _p(wa), _p(prev), _p(nxt)), "jolt_registers_rw_download", self.ctx)
+        _call("jolt_registers_rw_download", self.ctx, self.h, _p(rows), _p(cols), _p(val), _p(ra), _p(wa), _p(prev), _p(nxt))
         return dict(rows=rows[:n], cols=cols[:n], val=val[:n], ra=ra[:n], wa=wa[:n], prev=prev[:n], next=nxt[:n])
 
     def free(self):
@@ -2424,7 +2380,7 @@ Context.registers_rw = lambda self, *a, **k: RegistersRw(self, *a, **k)
 
 def _table_dot(self, a, b, deferred=False):
     out = fr_array(1)
-    _ck(lib().jolt_table_dot(self.h, a.h, b.h, C.c_int32(1 if deferred else 0), _p(out)), "jolt_table_dot", self)
+    _call("jolt_table_dot", self, self.h, a.h, b.h, 1 if deferred else 0, _p(out))
     return out[0]
 
 
@@ -2440,21 +2396,21 @@ def _r1cs_uniskip_sums(self, inputs, eq, a_weights, b_weights):
     wa = fr(a_weights).reshape(-1, 2, 1 + len(inputs), 4)
     wb = fr(b_weights).reshape(-1, 2, 1 + len(inputs), 4)
     out = fr_array(wa.shape[0])
-    _ck(lib().jolt_r1cs_uniskip_sums(self.h, _handles(inputs), C.c_size_t(len(inputs)), eq.h, _p(wa), _p(wb), C.c_size_t(wa.shape[0]), _p(out)), "jolt_r1cs_uniskip_sums", self)
+    _call("jolt_r1cs_uniskip_sums", self, self.h, _handles(inputs), len(inputs), eq.h, _p(wa), _p(wb), wa.shape[0], _p(out))
     return out
 
 
 def _r1cs_materialize(self, inputs, a_weights, b_weights):
     wa, wb = fr(a_weights).reshape(2, 1 + len(inputs), 4), fr(b_weights).reshape(2, 1 + len(inputs), 4)
     az, bz = C.c_void_p(), C.c_void_p()
-    _ck(lib().jolt_r1cs_materialize(self.h, _handles(inputs), C.c_size_t(len(inputs)), _p(wa), _p(wb), C.byref(az), C.byref(bz)), "jolt_r1cs_materialize", self)
+    _call("jolt_r1cs_materialize", self, self.h, _handles(inputs), len(inputs), _p(wa), _p(wb), C.byref(az), C.byref(bz))
     return Table(self, az), Table(self, bz)
 
 
 def _tables_evaluate(self, tables, point):
     p = fr(point).reshape(-1, 4)
     out = fr_array(len(tables))
-    _ck(lib().jolt_tables_evaluate(self.h, _handles(tables), C.c_size_t(len(tables)), _p(p), C.c_size_t(p.shape[0]), _p(out)), "jolt_tables_evaluate", self)
+    _call("jolt_tables_evaluate", self, self.h, _handles(tables), len(tables), _p(p), p.shape[0], _p(out))
     return out
 
 
@@ -2464,23 +2420,22 @@ def _r1cs_uniskip_sums_small(self, inputs, eq, a_weights, b_weights, streams=2):
     wa = np.ascontiguousarray(a_weights, dtype=np.int64).reshape(-1, streams, 1 + len(inputs))
     wb = np.ascontiguousarray(b_weights, dtype=np.int64).reshape(-1, streams, 1 + len(inputs))
     out = fr_array(wa.shape[0])
-    _ck(lib().jolt_r1cs_uniskip_sums_small(self.h, _handles(inputs), C.c_size_t(len(inputs)), eq.h, C.c_uint32(streams), wa.ctypes.data_as(C.c_void_p),
-                                           wb.ctypes.data_as(C.c_void_p), C.c_size_t(wa.shape[0]), _p(out)), "jolt_r1cs_uniskip_sums_small", self)
+    _call("jolt_r1cs_uniskip_sums_small", self, self.h, _handles(inputs), len(inputs), eq.h, streams, wa.ctypes.data_as(C.c_void_p), wb.ctypes.data_as(C.c_void_p),
+          wa.shape[0], _p(out))
     return out
 
 
 def _r1cs_materialize_small(self, inputs, a_weights, b_weights, streams=2):
     wa, wb = fr(a_weights).reshape(streams, 1 + len(inputs), 4), fr(b_weights).reshape(streams, 1 + len(inputs), 4)
     az, bz = C.c_void_p(), C.c_void_p()
-    _ck(lib().jolt_r1cs_materialize_small(self.h, _handles(inputs), C.c_size_t(len(inputs)), C.c_uint32(streams), _p(wa), _p(wb), C.byref(az), C.byref(bz)),
-        "jolt_r1cs_materialize_small", self)
+    _call("jolt_r1cs_materialize_small", self, self.h, _handles(inputs), len(inputs), streams, _p(wa), _p(wb), C.byref(az), C.byref(bz))
     return Table(self, az), Table(self, bz)
 
 
 def _ints_evaluate(self, columns, point):
     p = fr(point).reshape(-1, 4)
     out = fr_array(len(columns))
-    _ck(lib().jolt_ints_evaluate(self.h, _handles(columns), C.c_size_t(len(columns)), _p(p), C.c_size_t(p.shape[0]), _p(out)), "jolt_ints_evaluate", self)
+    _call("jolt_ints_evaluate", self, self.h, _handles(columns), len(columns), _p(p), p.shape[0], _p(out))
     return out
 
 
@@ -2496,8 +2451,7 @@ def _rows_window_table(self, offset, width, signed=False, lookahead=0, cycles=No
     """RandomAccessRows::window: field of row j (or j + 1) for every cycle of the padded domain, padding / None rows as given."""
     cycles = self.n_rows if cycles is None else cycles
     h = C.c_void_p()
-    _ck(lib().jolt_table_from_rows_window(self.ctx.h, self.h, C.c_size_t(offset), C.c_uint32(width), C.c_int32(1 if signed else 0), C.c_int32(lookahead),
-                                          C.c_size_t(cycles), C.c_int64(padding_value), C.c_int64(none_value), C.byref(h)), "jolt_table_from_rows_window", self.ctx)
+    _call("jolt_table_from_rows_window", self.ctx, self.ctx.h, self.h, offset, width, 1 if signed else 0, lookahead, cycles, padding_value, none_value, C.byref(h))
     return Table(self.ctx, h)
 
 
@@ -2506,8 +2460,7 @@ def _rows_onehot_sentinel(self, offset, width, shifts, log_k, cycles=None):
     cycles = self.n_rows if cycles is None else cycles
     sh = (C.c_uint32 * len(shifts))(*shifts)
     h = C.c_void_p()
-    _ck(lib().jolt_onehot_from_rows_sentinel(self.ctx.h, self.h, C.c_size_t(offset), C.c_uint32(width), sh, C.c_size_t(len(shifts)), C.c_uint32(log_k),
-                                             C.c_size_t(cycles), C.byref(h)), "jolt_onehot_from_rows_sentinel", self.ctx)
+    _call("jolt_onehot_from_rows_sentinel", self.ctx, self.ctx.h, self.h, offset, width, sh, len(shifts), log_k, cycles, C.byref(h))
     src = OneHot.__new__(OneHot)
     src.ctx, src.n_polys, src.cycles, src.k, src.h, src.wide = self.ctx, len(shifts), cycles, 1 << log_k, h, log_k > 7
     return src
@@ -2528,8 +2481,8 @@ class ReadRaf:
         assert idx.shape[0] == tab.shape[0] == raf.shape[0]
         self.ctx, self.cycles, self.n_tables = ctx, idx.shape[0], n_tables
         h = C.c_void_p()
-        _ck(lib().jolt_read_raf_create(ctx.h, idx.ctypes.data_as(C.c_void_p), tab.ctypes.data_as(C.c_void_p), raf.ctypes.data_as(C.c_void_p), C.c_size_t(self.cycles),
-                                       C.c_uint32(n_tables), C.byref(h)), "jolt_read_raf_create", ctx)
+        _call("jolt_read_raf_create", ctx, ctx.h, idx.ctypes.data_as(C.c_void_p), tab.ctypes.data_as(C.c_void_p), raf.ctypes.data_as(C.c_void_p), self.cycles, n_tables,
+              C.byref(h))
         self.h = h
 
     def phase_scan(self, u, suffix_len, address_bits, suffix_lists, canonical=False):
@@ -2539,22 +2492,21 @@ class ReadRaf:
         kinds = np.array([k for l in suffix_lists for k in l], dtype=np.uint8)
         raf = fr_array(6 * 256)
         suf = fr_array(max(int(offs[-1]) * 256, 1))
-        _ck(lib().jolt_read_raf_phase_scan(self.ctx.h, self.h, u.h, C.c_uint32(suffix_len), C.c_uint32(address_bits), C.c_int32(1 if canonical else 0),
-                                           offs.ctypes.data_as(C.c_void_p), kinds.ctypes.data_as(C.c_void_p) if kinds.size else None, _p(raf), _p(suf)),
-            "jolt_read_raf_phase_scan", self.ctx)
+        _call("jolt_read_raf_phase_scan", self.ctx, self.ctx.h, self.h, u.h, suffix_len, address_bits, 1 if canonical else 0, offs.ctypes.data_as(C.c_void_p),
+              kinds.ctypes.data_as(C.c_void_p) if kinds.size else None, _p(raf), _p(suf))
         return raf.reshape(6, 256, 4), suf[: int(offs[-1]) * 256].reshape(-1, 256, 4)
 
     def condense(self, u, v_table, shift):
         v = fr(v_table).reshape(256, 4)
-        _ck(lib().jolt_read_raf_condense(self.ctx.h, self.h, u.h, _p(v), C.c_uint32(shift)), "jolt_read_raf_condense", self.ctx)
+        _call("jolt_read_raf_condense", self.ctx, self.ctx.h, self.h, u.h, _p(v), shift)
 
     def cycle_tables(self, table_values, raf_interleaved, raf_identity, v_tables, address_bits, ra_count):
         tv = fr(table_values).reshape(self.n_tables, 4)
         vt = fr(v_tables).reshape(-1, 256, 4)
         combined = C.c_void_p()
         ra = (C.c_void_p * ra_count)()
-        _ck(lib().jolt_read_raf_cycle_tables(self.ctx.h, self.h, _p(tv), _p(fr(raf_interleaved).reshape(4)), _p(fr(raf_identity).reshape(4)), _p(vt), C.c_uint32(vt.shape[0]),
-                                             C.c_uint32(address_bits), C.c_uint32(ra_count), C.byref(combined), ra), "jolt_read_raf_cycle_tables", self.ctx)
+        _call("jolt_read_raf_cycle_tables", self.ctx, self.ctx.h, self.h, _p(tv), _p(fr(raf_interleaved).reshape(4)), _p(fr(raf_identity).reshape(4)), _p(vt), vt.shape[0],
+              address_bits, ra_count, C.byref(combined), ra)
         return Table(self.ctx, combined), [Table(self.ctx, C.c_void_p(p)) for p in ra]
 
     def free(self):
@@ -2570,7 +2522,7 @@ def host_fq_limb_op(op, a, b=None, c=None, d=None):
     """fq_limb.hip.h on the host: op 0 a*b, 1 a^2, 2 a*b + c*d, 3 (a - b)*c, 4 (a - b - 2c)*d over canonical Fq (standard Montgomery limbs)"""
     o = fr_array(1)
     arg = lambda x: _p(fr(x)) if x is not None else None
-    _ck(lib().jolt_host_fq_limb_op(C.c_int32(op), arg(a), arg(b), arg(c), arg(d), _p(o)), "jolt_host_fq_limb_op")
+    _call("jolt_host_fq_limb_op", None, op, arg(a), arg(b), arg(c), arg(d), _p(o))
     return o[0]
 
 
@@ -2579,7 +2531,7 @@ def host_g1_sum_limb_form(points, negate=None):
     pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
     neg = np.ascontiguousarray(negate if negate is not None else np.zeros(pts.shape[0]), dtype=np.uint8)
     out = g1_array(1)
-    _ck(lib().jolt_host_g1_sum_limb_form(pts.ctypes.data_as(C.c_void_p), neg.ctypes.data_as(C.c_void_p), C.c_size_t(pts.shape[0]), _p(out)), "jolt_host_g1_sum_limb_form")
+    _call("jolt_host_g1_sum_limb_form", None, pts.ctypes.data_as(C.c_void_p), neg.ctypes.data_as(C.c_void_p), pts.shape[0], _p(out))
     return out[0]
 
 
@@ -2592,7 +2544,7 @@ def host_g1xl_add_paths(acc, q, negate=False):
     canon = np.zeros((2, 4, 8), dtype=np.uint32)
     sus = C.c_int32()
     vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    _ck(lib().jolt_host_g1xl_add_paths(vp(a), vp(b), C.c_int32(1 if negate else 0), vp(common), vp(full), vp(step), C.byref(sus), vp(canon)), "jolt_host_g1xl_add_paths")
+    _call("jolt_host_g1xl_add_paths", None, vp(a), vp(b), 1 if negate else 0, vp(common), vp(full), vp(step), C.byref(sus), vp(canon))
     return {"common": common, "full": full, "step": step, "suspect": bool(sus.value), "canon_common": canon[0], "canon_full": canon[1]}
 
 
@@ -2600,20 +2552,20 @@ def host_fx_digits(scalar, window_bits):
     """(signed digits as Python ints, bucket count) of the fixed-base MSM's recoding of one Montgomery-form scalar"""
     keys = np.zeros(64, dtype=np.uint32)
     nw, nb = C.c_uint32(), C.c_uint32()
-    _ck(lib().jolt_host_fx_digits(_p(fr(scalar)), C.c_uint32(window_bits), keys.ctypes.data_as(C.c_void_p), C.byref(nw), C.byref(nb)), "jolt_host_fx_digits")
+    _call("jolt_host_fx_digits", None, _p(fr(scalar)), window_bits, keys.ctypes.data_as(C.c_void_p), C.byref(nw), C.byref(nb))
     return [(-1 if int(k) >> 31 else 1) * (int(k) & 0x7FFFFFFF) for k in keys[: nw.value]], nb.value
 
 
 def host_fx_segment_capacity(n, window_bits, segment):
     """the region (in entries) the capacity sort of an n-term fixed-base MSM gives segment `segment` of 256 buckets (jolt_host_fx_segment_capacity)"""
     cap = C.c_uint32()
-    _ck(lib().jolt_host_fx_segment_capacity(C.c_uint64(n), C.c_uint32(window_bits), C.c_uint32(segment), C.byref(cap)), "jolt_host_fx_segment_capacity")
+    _call("jolt_host_fx_segment_capacity", None, n, window_bits, segment, C.byref(cap))
     return int(cap.value)
 
 
 def host_suffix_mle(kind, bits, length):
     out = C.c_uint64()
-    _ck(lib().jolt_host_suffix_mle(C.c_uint32(kind), C.c_uint64(bits & (2**64 - 1)), C.c_uint64((bits >> 64) & (2**64 - 1)), C.c_uint32(length), C.byref(out)), "jolt_host_suffix_mle")
+    _call("jolt_host_suffix_mle", None, kind, bits & (2**64 - 1), (bits >> 64) & (2**64 - 1), length, C.byref(out))
     return out.value
 
 
@@ -2622,7 +2574,7 @@ def host_small_scalar_dot(values, scalars):
     v = fr(values).reshape(-1, 4)
     sc = np.array([[int(x) & (2**64 - 1), (int(x) >> 64) & (2**64 - 1)] for x in scalars], dtype=np.uint64).reshape(-1, 2)
     o = fr_array(1)
-    _ck(lib().jolt_host_small_scalar_dot(_p(v), sc.ctypes.data_as(C.c_void_p), C.c_size_t(v.shape[0]), _p(o)), "jolt_host_small_scalar_dot")
+    _call("jolt_host_small_scalar_dot", None, _p(v), sc.ctypes.data_as(C.c_void_p), v.shape[0], _p(o))
     return o[0]
 
 
@@ -2632,49 +2584,46 @@ NUM_LOOKUP_TABLES, NUM_LOOKUP_PREFIXES = 42, 49
 
 def lookup_table_suffixes(kind):
     out, n = np.zeros(8, dtype=np.uint8), C.c_uint32()
-    _ck(lib().jolt_lookup_table_suffixes(C.c_uint32(kind), _p(out), C.byref(n)), "jolt_lookup_table_suffixes")
+    _call("jolt_lookup_table_suffixes", None, kind, _p(out), C.byref(n))
     return [int(k) for k in out[: n.value]]
 
 
 def lookup_table_prefixes(kind):
     out, n = np.zeros(8, dtype=np.uint8), C.c_uint32()
-    _ck(lib().jolt_lookup_table_prefixes(C.c_uint32(kind), _p(out), C.byref(n)), "jolt_lookup_table_prefixes")
+    _call("jolt_lookup_table_prefixes", None, kind, _p(out), C.byref(n))
     return [int(k) for k in out[: n.value]]
 
 
 def lookup_suffix_lists():
     """LookupTableKind::suffixes() of the 42 tables: the suffix_lists argument of ReadRaf.phase_scan for real tables"""
     offs = np.zeros(NUM_LOOKUP_TABLES + 1, dtype=np.uint32)
-    _ck(lib().jolt_lookup_suffix_layout(_p(offs), None), "jolt_lookup_suffix_layout")
+    _call("jolt_lookup_suffix_layout", None, _p(offs), None)
     kinds = np.zeros(int(offs[-1]), dtype=np.uint8)
-    _ck(lib().jolt_lookup_suffix_layout(_p(offs), _p(kinds)), "jolt_lookup_suffix_layout")
+    _call("jolt_lookup_suffix_layout", None, _p(offs), _p(kinds))
     return [[int(k) for k in kinds[offs[t]: offs[t + 1]]] for t in range(NUM_LOOKUP_TABLES)]
 
 
 def host_lookup_prefix_default_checkpoints():
     out = fr_array(NUM_LOOKUP_PREFIXES)
-    _ck(lib().jolt_host_lookup_prefix_default_checkpoints(_p(out)), "jolt_host_lookup_prefix_default_checkpoints")
+    _call("jolt_host_lookup_prefix_default_checkpoints", None, _p(out))
     return out
 
 
 def host_lookup_prefix_evaluate(prefix, checkpoints, b, b_len, suffix_len):
     out = fr_array(1)
-    _ck(lib().jolt_host_lookup_prefix_evaluate(C.c_uint32(prefix), _p(fr(checkpoints).reshape(NUM_LOOKUP_PREFIXES, 4)), C.c_uint32(b), C.c_uint32(b_len), C.c_uint32(suffix_len),
-                                               _p(out)), "jolt_host_lookup_prefix_evaluate")
+    _call("jolt_host_lookup_prefix_evaluate", None, prefix, _p(fr(checkpoints).reshape(NUM_LOOKUP_PREFIXES, 4)), b, b_len, suffix_len, _p(out))
     return out[0]
 
 
 def host_lookup_prefix_table(prefix, checkpoints, b_len, suffix_len):
     out = fr_array(1 << b_len)
-    _ck(lib().jolt_host_lookup_prefix_table(C.c_uint32(prefix), _p(fr(checkpoints).reshape(NUM_LOOKUP_PREFIXES, 4)), C.c_uint32(b_len), C.c_uint32(suffix_len), _p(out)),
-        "jolt_host_lookup_prefix_table")
+    _call("jolt_host_lookup_prefix_table", None, prefix, _p(fr(checkpoints).reshape(NUM_LOOKUP_PREFIXES, 4)), b_len, suffix_len, _p(out))
     return out
 
 
 def host_lookup_table_combine(kind, prefixes, suffixes):
     out = fr_array(1)
-    _ck(lib().jolt_host_lookup_table_combine(C.c_uint32(kind), _p(fr(prefixes).reshape(NUM_LOOKUP_PREFIXES, 4)), _p(fr(suffixes).reshape(-1, 4)), _p(out)),
-        "jolt_host_lookup_table_combine")
+    _call("jolt_host_lookup_table_combine", None, kind, _p(fr(prefixes).reshape(NUM_LOOKUP_PREFIXES, 4)), _p(fr(suffixes).reshape(-1, 4)), _p(out))
     return out[0]
 
 
@@ -2685,39 +2634,38 @@ class HostReadRafAddress:
         present = np.zeros(NUM_LOOKUP_TABLES, dtype=np.uint8)
         present[: len(table_present)] = np.asarray(table_present, dtype=np.uint8)
         h = C.c_void_p()
-        _ck(lib().jolt_host_read_raf_address_create(_p(fr(gamma).reshape(4)), _p(present), C.c_int32(1 if canonical else 0), C.byref(h)), "jolt_host_read_raf_address_create")
+        _call("jolt_host_read_raf_address_create", None, _p(fr(gamma).reshape(4)), _p(present), 1 if canonical else 0, C.byref(h))
         self.h = h
 
     def init_phase(self, phase, raf_sums, suffix_sums):
-        _ck(lib().jolt_host_read_raf_address_init_phase(self.h, C.c_uint32(phase), _p(fr(raf_sums).reshape(6 * 256, 4)), _p(fr(suffix_sums).reshape(-1, 4))),
-            "jolt_host_read_raf_address_init_phase")
+        _call("jolt_host_read_raf_address_init_phase", None, self.h, phase, _p(fr(raf_sums).reshape(6 * 256, 4)), _p(fr(suffix_sums).reshape(-1, 4)))
 
     def message(self, previous_claim=None):
         """s(0), s(1), s(2); without a running claim s(1) is summed from the tables (round 0: s(0) + s(1) = the input claim)"""
         o = fr_array(3)
-        _ck(lib().jolt_host_read_raf_address_message(self.h, _p(fr(previous_claim).reshape(4)) if previous_claim is not None else None, _p(o)), "jolt_host_read_raf_address_message")
+        _call("jolt_host_read_raf_address_message", None, self.h, _p(fr(previous_claim).reshape(4)) if previous_claim is not None else None, _p(o))
         return o
 
     def bind(self, r):
         done = C.c_int32()
-        _ck(lib().jolt_host_read_raf_address_bind(self.h, _p(fr(r).reshape(4)), C.byref(done)), "jolt_host_read_raf_address_bind")
+        _call("jolt_host_read_raf_address_bind", None, self.h, _p(fr(r).reshape(4)), C.byref(done))
         return bool(done.value)
 
     def prove_phase(self, claim, transcript):
         """the 8 rounds of the open phase against a HostTranscript: -> (claim after the phase, coefficients (8, 3, 4), challenges (8, 4))"""
         c = fr(claim).reshape(4).copy()
         coeffs, challenges = fr_array(24), fr_array(8)
-        _ck(lib().jolt_host_read_raf_address_prove_phase(self.h, _p(c), None, None, transcript.h, _p(coeffs), _p(challenges)), "jolt_host_read_raf_address_prove_phase")
+        _call("jolt_host_read_raf_address_prove_phase", None, self.h, _p(c), None, None, transcript.h, _p(coeffs), _p(challenges))
         return c, coeffs.reshape(8, 3, 4), challenges
 
     def v_table(self, phase):
         o = fr_array(256)
-        _ck(lib().jolt_host_read_raf_address_v_table(self.h, C.c_uint32(phase), _p(o)), "jolt_host_read_raf_address_v_table")
+        _call("jolt_host_read_raf_address_v_table", None, self.h, phase, _p(o))
         return o
 
     def finish(self):
         tv, a, b = fr_array(NUM_LOOKUP_TABLES), fr_array(1), fr_array(1)
-        _ck(lib().jolt_host_read_raf_address_finish(self.h, _p(tv), _p(a), _p(b)), "jolt_host_read_raf_address_finish")
+        _call("jolt_host_read_raf_address_finish", None, self.h, _p(tv), _p(a), _p(b))
         return tv, a[0], b[0]
 
     def close(self):
@@ -2749,7 +2697,7 @@ def host_small_round_pair(n_tables, groups, is_int, int_pairs, fr_pairs, n_evals
     ip = np.ascontiguousarray(int_pairs, dtype=np.uint64).reshape(n_tables, 2)
     fp = np.ascontiguousarray(fr_pairs, dtype=np.uint64).reshape(n_tables, 2, 4)
     out = fr_array(n_evals)
-    _ck(lib().jolt_host_small_round_pair(C.byref(d), _p(mask), _p(ip), _p(fp), C.c_uint32(n_evals), C.c_int32(1 if skip_one else 0), _p(out)), "jolt_host_small_round_pair")
+    _call("jolt_host_small_round_pair", None, C.byref(d), _p(mask), _p(ip), _p(fp), n_evals, 1 if skip_one else 0, _p(out))
     return out
 
 
@@ -2763,47 +2711,46 @@ class StageOp:
     @property
     def rounds(self):
         n = C.c_size_t()
-        _ck(lib().jolt_stage_op_num_rounds(self.h, C.byref(n)), "jolt_stage_op_num_rounds", self.ctx)
+        _call("jolt_stage_op_num_rounds", self.ctx, self.h, C.byref(n))
         return n.value
 
     @property
     def degree(self):
         n = C.c_size_t()
-        _ck(lib().jolt_stage_op_degree(self.h, C.byref(n)), "jolt_stage_op_degree", self.ctx)
+        _call("jolt_stage_op_degree", self.ctx, self.h, C.byref(n))
         return n.value
 
     def input_claim(self):
         o = fr_array(1)
-        _ck(lib().jolt_stage_op_input_claim(self.h, _p(o)), "jolt_stage_op_input_claim", self.ctx)
+        _call("jolt_stage_op_input_claim", self.ctx, self.h, _p(o))
         return o[0]
 
     def prove_round(self, bind, rnd, previous_claim):
         """ProveRounds::prove_round: the round message as coefficients (n, 4)"""
         cap = self.degree + 1
         out, n = fr_array(cap), C.c_size_t()
-        _ck(lib().jolt_stage_op_prove_round(self.h, _p(fr(bind)) if bind is not None else None, C.c_size_t(rnd), _p(fr(previous_claim)), _p(out), C.c_size_t(cap), C.byref(n)),
-            "jolt_stage_op_prove_round", self.ctx)
+        _call("jolt_stage_op_prove_round", self.ctx, self.h, _p(fr(bind)) if bind is not None else None, rnd, _p(fr(previous_claim)), _p(out), cap, C.byref(n))
         return out[: n.value].copy()
 
     def finish_rounds(self, bind):
-        _ck(lib().jolt_stage_op_finish_rounds(self.h, _p(fr(bind))), "jolt_stage_op_finish_rounds", self.ctx)
+        _call("jolt_stage_op_finish_rounds", self.ctx, self.h, _p(fr(bind)))
 
     def output_claims(self):
         n = C.c_size_t()
         out = fr_array(320)  # (a precommitted reduction answers with up to 1 + 256 claims)
-        _ck(lib().jolt_stage_op_output_claims(self.h, _p(out), C.c_size_t(320), C.byref(n)), "jolt_stage_op_output_claims", self.ctx)
+        _call("jolt_stage_op_output_claims", self.ctx, self.h, _p(out), 320, C.byref(n))
         return out[: n.value].copy()
 
     def kept(self, key):
         n = C.c_size_t()
-        _ck(lib().jolt_stage_op_kept(self.h, key.encode(), None, C.c_size_t(0), C.byref(n)), "jolt_stage_op_kept", self.ctx)
+        _call("jolt_stage_op_kept", self.ctx, self.h, key.encode(), None, 0, C.byref(n))
         out = fr_array(max(n.value, 1))
-        _ck(lib().jolt_stage_op_kept(self.h, key.encode(), _p(out), C.c_size_t(n.value), C.byref(n)), "jolt_stage_op_kept", self.ctx)
+        _call("jolt_stage_op_kept", self.ctx, self.h, key.encode(), _p(out), n.value, C.byref(n))
         return out[: n.value]
 
     def window(self, first, n):
         h = C.c_void_p()
-        _ck(lib().jolt_stage_op_window(self.h, C.c_size_t(first), C.c_size_t(n), C.byref(h)), "jolt_stage_op_window", self.ctx)
+        _call("jolt_stage_op_window", self.ctx, self.h, first, n, C.byref(h))
         return StageOp(self.ctx, h, keep=[self])
 
     def prove_alone(self, transcript, claim):
@@ -2811,8 +2758,7 @@ class StageOp:
         rounds, stride = self.rounds, self.degree + 1
         c = fr(claim).reshape(4).copy()
         coeffs, counts, chal = fr_array(max(rounds * stride, 1)), np.zeros(max(rounds, 1), dtype=np.uint32), fr_array(max(rounds, 1))
-        _ck(lib().jolt_host_stage_op_prove_alone(self.h, transcript.h, _p(c), _p(coeffs), C.c_size_t(stride), counts.ctypes.data_as(C.c_void_p), _p(chal)),
-            "jolt_host_stage_op_prove_alone", self.ctx)
+        _call("jolt_host_stage_op_prove_alone", self.ctx, self.h, transcript.h, _p(c), _p(coeffs), stride, counts.ctypes.data_as(C.c_void_p), _p(chal))
         coeffs = coeffs.reshape(-1, stride, 4)
         return dict(polys=[coeffs[r, : counts[r]].copy() for r in range(rounds)], challenges=chal[:rounds].copy() if rounds else np.zeros((0, 4), dtype=np.uint64), final_claim=c)
 
@@ -2842,7 +2788,7 @@ def stage_host_expr(tables, terms, degree):
     d = MemberDesc(len(tabs), len(terms), degree, ORDER_LOW_TO_HIGH, offs.ctypes.data, facs_a.ctypes.data, coeffs.ctypes.data)
     ptrs = (C.c_void_p * len(tabs))(*[t.ctypes.data for t in tabs])
     h = C.c_void_p()
-    _ck(lib().jolt_stage_host_expr_create(ptrs, C.c_size_t(tabs[0].shape[0]), C.byref(d), C.byref(h)), "jolt_stage_host_expr_create")
+    _call("jolt_stage_host_expr_create", None, ptrs, tabs[0].shape[0], C.byref(d), C.byref(h))
     return StageOp(None, h)
 
 
@@ -2867,8 +2813,8 @@ def _prove_batch_ops(self, ops, input_claims, coefficients, offsets, max_num_var
     polys, chal = fr_array(max(max_num_vars * (max_degree + 1), 1)), fr_array(max(max_num_vars, 1))
     mclaims, final = fr_array(n), fr_array(1)
     name = "jolt_host_prove_batch_ops_grouped" if grouped else "jolt_host_prove_batch_ops"
-    _ck(getattr(lib(), name)(self.h if self is not None else None, hs, C.c_size_t(n), _p(ic), _p(co), offs, C.c_size_t(max_num_vars), C.c_size_t(max_degree), C.c_uint64(label),
-                             C.c_int32(challenge_mode), _p(polys), _p(chal), _p(mclaims), _p(final)), name, self)
+    _call(name, self, self.h if self is not None else None, hs, n, _p(ic), _p(co), offs, max_num_vars, max_degree, label, challenge_mode, _p(polys), _p(chal), _p(mclaims),
+          _p(final))
     return dict(polys=polys[: max_num_vars * (max_degree + 1)].reshape(max_num_vars, max_degree + 1, 4), challenges=chal[:max_num_vars], member_claims=mclaims, final_claim=final[0])
 
 
@@ -2877,8 +2823,8 @@ def _stage_spartan_uniskip_sums(self, cols, tau, a_weights, b_weights, streams):
     wb = np.ascontiguousarray(b_weights, dtype=np.int64).reshape(-1, streams, 1 + len(cols))
     t = fr(tau).reshape(-1, 4)
     out = fr_array(wa.shape[0])
-    _ck(lib().jolt_stage_spartan_uniskip_sums(self.h, _handles(cols), C.c_size_t(len(cols)), C.c_uint32(streams), _p(t), C.c_size_t(t.shape[0]), wa.ctypes.data_as(C.c_void_p),
-                                              wb.ctypes.data_as(C.c_void_p), C.c_size_t(wa.shape[0]), _p(out)), "jolt_stage_spartan_uniskip_sums", self)
+    _call("jolt_stage_spartan_uniskip_sums", self, self.h, _handles(cols), len(cols), streams, _p(t), t.shape[0], wa.ctypes.data_as(C.c_void_p), wb.ctypes.data_as(C.c_void_p),
+          wa.shape[0], _p(out))
     return out
 
 
@@ -2886,47 +2832,44 @@ def _stage_spartan_remainder(self, cols, fa, fb, tau, scale, streams):
     wa, wb = fr(fa).reshape(streams, 1 + len(cols), 4), fr(fb).reshape(streams, 1 + len(cols), 4)
     t = fr(tau).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_spartan_remainder_create(self.h, _handles(cols), C.c_size_t(len(cols)), C.c_uint32(streams), _p(wa), _p(wb), _p(t), C.c_size_t(t.shape[0]),
-                                                  _p(fr(scale)) if scale is not None else None, C.byref(h)), "jolt_stage_spartan_remainder_create", self)
+    _call("jolt_stage_spartan_remainder_create", self, self.h, _handles(cols), len(cols), streams, _p(wa), _p(wb), _p(t), t.shape[0],
+          _p(fr(scale)) if scale is not None else None, C.byref(h))
     return StageOp(self, h, keep=cols)
 
 
 def _stage_ram_read_write(self, addresses, pre, post, inc, val_init, tau_low, gamma):
     h = C.c_void_p()
-    _ck(lib().jolt_stage_ram_read_write_create(self.h, addresses.h, pre.h, post.h, inc.h, val_init.h, _p(fr(tau_low).reshape(-1, 4)), _p(fr(gamma)), C.byref(h)),
-        "jolt_stage_ram_read_write_create", self)
+    _call("jolt_stage_ram_read_write_create", self, self.h, addresses.h, pre.h, post.h, inc.h, val_init.h, _p(fr(tau_low).reshape(-1, 4)), _p(fr(gamma)), C.byref(h))
     return StageOp(self, h, keep=[addresses, pre, post, inc, val_init])
 
 
 def _stage_registers_read_write(self, regs, rs1_val, rs2_val, rd_pre, rd_post, inc, r_cycle, gamma):
     h = C.c_void_p()
-    _ck(lib().jolt_stage_registers_read_write_create(self.h, regs.h, rs1_val.h, rs2_val.h, rd_pre.h, rd_post.h, inc.h, _p(fr(r_cycle).reshape(-1, 4)), _p(fr(gamma)), C.byref(h)),
-        "jolt_stage_registers_read_write_create", self)
+    _call("jolt_stage_registers_read_write_create", self, self.h, regs.h, rs1_val.h, rs2_val.h, rd_pre.h, rd_post.h, inc.h, _p(fr(r_cycle).reshape(-1, 4)), _p(fr(gamma)),
+          C.byref(h))
     return StageOp(self, h, keep=[regs, rs1_val, rs2_val, rd_pre, rd_post, inc])
 
 
 def _stage_booleanity_address(self, cols, reference_cycle, reference_address, gamma):
     rc = fr(reference_cycle).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_booleanity_address_create(self.h, cols.h, _p(rc), C.c_size_t(rc.shape[0]), _p(fr(reference_address).reshape(-1, 4)), _p(fr(gamma)), C.byref(h)),
-        "jolt_stage_booleanity_address_create", self)
+    _call("jolt_stage_booleanity_address_create", self, self.h, cols.h, _p(rc), rc.shape[0], _p(fr(reference_address).reshape(-1, 4)), _p(fr(gamma)), C.byref(h))
     return StageOp(self, h, keep=[cols])
 
 
 def _stage_booleanity_cycle(self, cols, r_address, reference_address, reference_cycle, gamma):
     rc = fr(reference_cycle).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_booleanity_cycle_create(self.h, cols.h, _p(fr(r_address).reshape(-1, 4)), _p(fr(reference_address).reshape(-1, 4)), _p(rc), C.c_size_t(rc.shape[0]),
-                                                 _p(fr(gamma)), C.byref(h)), "jolt_stage_booleanity_cycle_create", self)
+    _call("jolt_stage_booleanity_cycle_create", self, self.h, cols.h, _p(fr(r_address).reshape(-1, 4)), _p(fr(reference_address).reshape(-1, 4)), _p(rc), rc.shape[0],
+          _p(fr(gamma)), C.byref(h))
     return StageOp(self, h, keep=[cols])
 
 
 def _stage_hamming_weight(self, cols, r_cycle, r_address, virtualization_points, gamma):
     rc = fr(r_cycle).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_hamming_weight_create(self.h, cols.h, _p(rc), C.c_size_t(rc.shape[0]), _p(fr(r_address).reshape(-1, 4)),
-                                               _p(np.ascontiguousarray(virtualization_points, dtype=np.uint64).reshape(-1, 4)), _p(fr(gamma)), C.byref(h)),
-        "jolt_stage_hamming_weight_create", self)
+    _call("jolt_stage_hamming_weight_create", self, self.h, cols.h, _p(rc), rc.shape[0], _p(fr(r_address).reshape(-1, 4)),
+          _p(np.ascontiguousarray(virtualization_points, dtype=np.uint64).reshape(-1, 4)), _p(fr(gamma)), C.byref(h))
     return StageOp(self, h, keep=[cols])
 
 
@@ -2935,8 +2878,7 @@ def _stage_instruction_read_raf(self, rows, claim_columns, r_reduction, gamma, t
     present = np.zeros(NUM_LOOKUP_TABLES, dtype=np.uint8)
     present[: len(table_present)] = np.asarray(table_present, dtype=np.uint8)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_instruction_read_raf_create(self.h, rows.h, claim_columns.h, _p(rr), C.c_size_t(rr.shape[0]), _p(fr(gamma)), _p(present), C.c_uint32(ra_count), C.byref(h)),
-        "jolt_stage_instruction_read_raf_create", self)
+    _call("jolt_stage_instruction_read_raf_create", self, self.h, rows.h, claim_columns.h, _p(rr), rr.shape[0], _p(fr(gamma)), _p(present), ra_count, C.byref(h))
     return StageOp(self, h, keep=[rows, claim_columns])
 
 
@@ -2944,41 +2886,38 @@ def _stage_bytecode_read_raf_address(self, pc_index, stage_points, stage_values,
     sp = np.ascontiguousarray(stage_points, dtype=np.uint64).reshape(5, -1, 4)
     sv = np.ascontiguousarray(stage_values, dtype=np.uint64).reshape(5, -1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_bytecode_read_raf_address_create(self.h, pc_index.h, _p(sp), C.c_size_t(sp.shape[1]), _p(sv), _p(fr(gamma)), C.c_uint64(int(first_pc)),
-                                                          C.c_uint64(int(entry_index)), C.byref(h)), "jolt_stage_bytecode_read_raf_address_create", self)
+    _call("jolt_stage_bytecode_read_raf_address_create", self, self.h, pc_index.h, _p(sp), sp.shape[1], _p(sv), _p(fr(gamma)), int(first_pc), int(entry_index), C.byref(h))
     return StageOp(self, h, keep=[pc_index])
 
 
 def _stage_bytecode_read_raf_cycle(self, address_op, pc_chunks, chunk_bits):
     h = C.c_void_p()
-    _ck(lib().jolt_stage_bytecode_read_raf_cycle_create(self.h, address_op.h, pc_chunks.h, C.c_uint32(chunk_bits), C.byref(h)), "jolt_stage_bytecode_read_raf_cycle_create", self)
+    _call("jolt_stage_bytecode_read_raf_cycle_create", self, self.h, address_op.h, pc_chunks.h, chunk_bits, C.byref(h))
     return StageOp(self, h, keep=[pc_chunks])
 
 
 def _stage_ram_raf_evaluation(self, ram_index, tau_low, lowest_address):
     t = fr(tau_low).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_ram_raf_evaluation_create(self.h, ram_index.h, _p(t), C.c_size_t(t.shape[0]), C.c_uint64(int(lowest_address)), C.byref(h)),
-        "jolt_stage_ram_raf_evaluation_create", self)
+    _call("jolt_stage_ram_raf_evaluation_create", self, self.h, ram_index.h, _p(t), t.shape[0], int(lowest_address), C.byref(h))
     return StageOp(self, h, keep=[ram_index])
 
 
 def _stage_ram_output_check(self, ram_index, post_values, val_init, val_io, io_lo, io_len, r_address):
     vi, vo = np.ascontiguousarray(val_init, dtype=np.uint64), np.ascontiguousarray(val_io, dtype=np.uint64)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_ram_output_check_create(self.h, ram_index.h, post_values.h, _p(vi), _p(vo), C.c_uint64(int(io_lo)), C.c_uint64(int(io_len)), _p(fr(r_address).reshape(-1, 4)),
-                                                 C.byref(h)), "jolt_stage_ram_output_check_create", self)
+    _call("jolt_stage_ram_output_check_create", self, self.h, ram_index.h, post_values.h, _p(vi), _p(vo), int(io_lo), int(io_len), _p(fr(r_address).reshape(-1, 4)),
+          C.byref(h))
     return StageOp(self, h, keep=[ram_index, post_values])
 
 
-STAGE_MEMBER_OWN = 1  # JOLT_STAGE_MEMBER_OWN
 
 
 def _stage_member(self, member, own=False):
     """jolt_stage_member_create: a device Member as a stage operator.  It borrows `member` (which stays the caller's: reset() after the operator is destroyed makes it
     provable again) unless own=True, in which case destroying the operator destroys the member and the Member handle is emptied here."""
     h = C.c_void_p()
-    _ck(lib().jolt_stage_member_create(self.h, member.h if member is not None else None, C.c_uint32(STAGE_MEMBER_OWN if own else 0), C.byref(h)), "jolt_stage_member_create", self)
+    _call("jolt_stage_member_create", self, self.h, member.h if member is not None else None, STAGE_MEMBER_OWN if own else 0, C.byref(h))
     if own:
         member.h = None
     return StageOp(self, h, keep=[member])
@@ -3023,8 +2962,8 @@ class R1csRows:
         per = np.array([len(st) for st in streams] + [0], dtype=np.uint32)
         self.h = C.c_void_p()
         self.n_streams, self.domain_size, self.n_inputs, self.zero_on_domain = len(streams), domain_size, n_inputs, bool(zero_on_domain)
-        _ck(lib().jolt_r1cs_rows_create(C.c_uint32(len(streams)), C.c_uint32(domain_size), _p(per), C.c_uint32(n_inputs), _p(ao), _p(ac), _p(af), _p(a0), _p(bo), _p(bc), _p(bf),
-                                        _p(b0), C.c_int32(1 if zero_on_domain else 0), C.byref(self.h)), "jolt_r1cs_rows_create")
+        _call("jolt_r1cs_rows_create", None, len(streams), domain_size, _p(per), n_inputs, _p(ao), _p(ac), _p(af), _p(a0), _p(bo), _p(bc), _p(bf), _p(b0),
+              1 if zero_on_domain else 0, C.byref(self.h))
 
     @property
     def n_nodes(self):
@@ -3033,16 +2972,16 @@ class R1csRows:
     def extension(self):
         """L_i(node): (2D - 1, D) int64"""
         out = np.zeros((self.n_nodes, self.domain_size), dtype=np.int64)
-        _ck(lib().jolt_r1cs_rows_extension(self.h, _p(out)), "jolt_r1cs_rows_extension")
+        _call("jolt_r1cs_rows_extension", None, self.h, _p(out))
         return out
 
     def fold_small(self):
         """the column form of the evaluated nodes: (wa, wb) int64 [node][stream][1 + n_inputs] (JoltError `unsupported` where a folded weight has no int64)"""
         n = C.c_size_t()
-        _ck(lib().jolt_r1cs_rows_fold_small(self.h, None, None, C.byref(n)), "jolt_r1cs_rows_fold_small")
+        _call("jolt_r1cs_rows_fold_small", None, self.h, None, None, C.byref(n))
         wa = np.zeros((n.value, self.n_streams, 1 + self.n_inputs), dtype=np.int64)
         wb = np.zeros_like(wa)
-        _ck(lib().jolt_r1cs_rows_fold_small(self.h, _p(wa), _p(wb), C.byref(n)), "jolt_r1cs_rows_fold_small")
+        _call("jolt_r1cs_rows_fold_small", None, self.h, _p(wa), _p(wb), C.byref(n))
         return wa, wb
 
     def host_cycle(self, values, kinds, stream, node):
@@ -3050,7 +2989,7 @@ class R1csRows:
         v = np.array([[int(x) & (2**64 - 1), (int(x) >> 64) & (2**64 - 1)] for x in values], dtype=np.uint64)
         k = np.array([Ints.KINDS[q] for q in kinds], dtype=np.int32)
         az, bz, pr, ng = np.zeros(2, dtype=np.uint64), np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_int32()
-        _ck(lib().jolt_host_r1cs_rows_cycle(self.h, _p(v), _p(k), C.c_uint32(stream), C.c_uint32(node), _p(az), _p(bz), _p(pr), C.byref(ng)), "jolt_host_r1cs_rows_cycle")
+        _call("jolt_host_r1cs_rows_cycle", None, self.h, _p(v), _p(k), stream, node, _p(az), _p(bz), _p(pr), C.byref(ng))
         def signed(words, bits):
             x = sum(int(w) << (64 * i) for i, w in enumerate(words))
             return x - (1 << bits) if x >> (bits - 1) else x
@@ -3060,7 +2999,7 @@ class R1csRows:
     def remainder_weights(self, r0, tau_high):
         """jolt_host_r1cs_rows_remainder_weights -> (fa, fb) [stream][1 + n_inputs], scale"""
         fa, fb, k = fr_array(self.n_streams * (1 + self.n_inputs)), fr_array(self.n_streams * (1 + self.n_inputs)), fr_array(1)
-        _ck(lib().jolt_host_r1cs_rows_remainder_weights(self.h, _p(fr(r0)), _p(fr(tau_high)), _p(fa), _p(fb), _p(k)), "jolt_host_r1cs_rows_remainder_weights")
+        _call("jolt_host_r1cs_rows_remainder_weights", None, self.h, _p(fr(r0)), _p(fr(tau_high)), _p(fa), _p(fb), _p(k))
         shape = (self.n_streams, 1 + self.n_inputs, 4)
         return fa.reshape(shape), fb.reshape(shape), k[0]
 
@@ -3078,20 +3017,20 @@ class R1csRows:
 
 def host_centered_lagrange_evals(domain_size, r):
     out = fr_array(domain_size)
-    _ck(lib().jolt_host_centered_lagrange_evals(C.c_size_t(domain_size), _p(fr(r)), _p(out)), "jolt_host_centered_lagrange_evals")
+    _call("jolt_host_centered_lagrange_evals", None, domain_size, _p(fr(r)), _p(out))
     return out
 
 
 def host_centered_lagrange_kernel(domain_size, x, y):
     out = fr_array(1)
-    _ck(lib().jolt_host_centered_lagrange_kernel(C.c_size_t(domain_size), _p(fr(x)), _p(fr(y)), _p(out)), "jolt_host_centered_lagrange_kernel")
+    _call("jolt_host_centered_lagrange_kernel", None, domain_size, _p(fr(x)), _p(fr(y)), _p(out))
     return out[0]
 
 
 def host_interpolate_to_coeffs(domain_start, values):
     v = fr(values).reshape(-1, 4)
     out = fr_array(v.shape[0])
-    _ck(lib().jolt_host_interpolate_to_coeffs(C.c_int64(domain_start), _p(v), C.c_size_t(v.shape[0]), _p(out)), "jolt_host_interpolate_to_coeffs")
+    _call("jolt_host_interpolate_to_coeffs", None, domain_start, _p(v), v.shape[0], _p(out))
     return out
 
 
@@ -3099,7 +3038,7 @@ def host_uniskip_first_round_poly(domain_size, tau_high, t1):
     v = fr(t1).reshape(-1, 4)
     assert v.shape[0] == 2 * domain_size - 1
     out = fr_array(3 * domain_size - 2)
-    _ck(lib().jolt_host_uniskip_first_round_poly(C.c_size_t(domain_size), _p(fr(tau_high)), _p(v), _p(out)), "jolt_host_uniskip_first_round_poly")
+    _call("jolt_host_uniskip_first_round_poly", None, domain_size, _p(fr(tau_high)), _p(v), _p(out))
     return out
 
 
@@ -3107,7 +3046,7 @@ def host_prove_uniskip(transcript, coeffs, domain_size, input_claim):
     """jolt_host_prove_uniskip -> (r0, output claim)"""
     c = fr(coeffs).reshape(-1, 4)
     r0, claim = fr_array(1), fr_array(1)
-    _ck(lib().jolt_host_prove_uniskip(transcript.h, _p(c), C.c_size_t(c.shape[0]), C.c_size_t(domain_size), _p(fr(input_claim)), _p(r0), _p(claim)), "jolt_host_prove_uniskip")
+    _call("jolt_host_prove_uniskip", None, transcript.h, _p(c), c.shape[0], domain_size, _p(fr(input_claim)), _p(r0), _p(claim))
     return r0[0], claim[0]
 
 
@@ -3120,23 +3059,22 @@ def prove_batch_ops_on(ops, input_claims, coefficients, offsets, max_num_vars, m
     offs = (C.c_size_t * n)(*offsets)
     polys, chal = fr_array(max(max_num_vars * (max_degree + 1), 1)), fr_array(max(max_num_vars, 1))
     mclaims, final = fr_array(n), fr_array(1)
-    _ck(lib().jolt_host_prove_batch_ops_on(ctx.h if ctx is not None else None, hs, C.c_size_t(n), _p(ic), _p(co), offs, C.c_size_t(max_num_vars), C.c_size_t(max_degree), transcript.h,
-                                           C.c_int32(challenge_mode), _p(polys), _p(chal), _p(mclaims), _p(final)), "jolt_host_prove_batch_ops_on", ctx)
+    _call("jolt_host_prove_batch_ops_on", ctx, ctx.h if ctx is not None else None, hs, n, _p(ic), _p(co), offs, max_num_vars, max_degree, transcript.h, challenge_mode,
+          _p(polys), _p(chal), _p(mclaims), _p(final))
     return dict(polys=polys[: max_num_vars * (max_degree + 1)].reshape(max_num_vars, max_degree + 1, 4), challenges=chal[:max_num_vars], member_claims=mclaims, final_claim=final[0])
 
 
 def _r1cs_uniskip_sums_rows(self, rows, cols, eq):
     """jolt_r1cs_uniskip_sums_rows: t1 at the 2D - 1 extended nodes (nodes the system marks as vanishing: 0)"""
     out = fr_array(rows.n_nodes)
-    _ck(lib().jolt_r1cs_uniskip_sums_rows(self.h, rows.h, _handles(cols), C.c_size_t(len(cols)), eq.h, _p(out)), "jolt_r1cs_uniskip_sums_rows", self)
+    _call("jolt_r1cs_uniskip_sums_rows", self, self.h, rows.h, _handles(cols), len(cols), eq.h, _p(out))
     return out
 
 
 def _stage_spartan_remainder_rows(self, rows, cols, tau, tau_high, r0):
     t = fr(tau).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_spartan_remainder_rows_create(self.h, rows.h, _handles(cols), C.c_size_t(len(cols)), _p(t), C.c_size_t(t.shape[0]), _p(fr(tau_high)), _p(fr(r0)), C.byref(h)),
-        "jolt_stage_spartan_remainder_rows_create", self)
+    _call("jolt_stage_spartan_remainder_rows_create", self, self.h, rows.h, _handles(cols), len(cols), _p(t), t.shape[0], _p(fr(tau_high)), _p(fr(r0)), C.byref(h))
     return StageOp(self, h, keep=list(cols) + [rows])
 
 
@@ -3147,8 +3085,8 @@ def _prove_spartan_stage(self, rows, cols, tau, input_claim, coefficient, transc
     D = rows.domain_size
     uc, r0, claim = fr_array(3 * D - 2), fr_array(1), fr_array(1)
     polys, chal, final, values = fr_array(max(n * 4, 1)), fr_array(max(n, 1)), fr_array(1), fr_array(len(cols))
-    _ck(lib().jolt_host_prove_spartan_stage(self.h, rows.h, _handles(cols), C.c_size_t(len(cols)), _p(t), C.c_size_t(t.shape[0]), _p(fr(input_claim)), _p(fr(coefficient)), transcript.h,
-                                            _p(uc), _p(r0), _p(claim), _p(polys), _p(chal), _p(final), _p(values)), "jolt_host_prove_spartan_stage", self)
+    _call("jolt_host_prove_spartan_stage", self, self.h, rows.h, _handles(cols), len(cols), _p(t), t.shape[0], _p(fr(input_claim)), _p(fr(coefficient)), transcript.h, _p(uc),
+          _p(r0), _p(claim), _p(polys), _p(chal), _p(final), _p(values))
     return dict(uniskip_coeffs=uc, r0=r0[0], uniskip_claim=claim[0], polys=polys[: n * 4].reshape(n, 4, 4), challenges=chal[:n], final_claim=final[0], values=values)
 
 
@@ -3158,7 +3096,6 @@ Context.prove_spartan_stage = _prove_spartan_stage
 
 
 # ---- precommitted claim reductions (precommitted.hip): the operator pair, its host twin, the table builders ----------------------------------------------------
-TRACE_CYCLE_MAJOR, TRACE_ADDRESS_MAJOR = 0, 1  # JOLT_TRACE_*
 
 
 def _size_array(values):
@@ -3171,15 +3108,14 @@ def _stage_precommitted_cycle(self, value, eq, aux, cycle_active, cycle_total, a
     ca, n_ca = _size_array(cycle_active)
     aa, n_aa = _size_array(address_active)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_precommitted_cycle_create(self.h, value.h, eq.h, _handles(aux), C.c_size_t(len(aux)), ca, C.c_size_t(n_ca), C.c_size_t(cycle_total), aa, C.c_size_t(n_aa),
-                                                   C.c_size_t(address_total), C.byref(h)), "jolt_stage_precommitted_cycle_create", self)
+    _call("jolt_stage_precommitted_cycle_create", self, self.h, value.h, eq.h, _handles(aux), len(aux), ca, n_ca, cycle_total, aa, n_aa, address_total, C.byref(h))
     return StageOp(self, h)
 
 
 def _stage_precommitted_address(self, cycle_op):
     """jolt_stage_precommitted_address_create: the stage-7 address phase from the carry of a FINISHED cycle operator"""
     h = C.c_void_p()
-    _ck(lib().jolt_stage_precommitted_address_create(self.h, cycle_op.h, C.byref(h)), "jolt_stage_precommitted_address_create", self)
+    _call("jolt_stage_precommitted_address_create", self, self.h, cycle_op.h, C.byref(h))
     return StageOp(self, h)
 
 
@@ -3190,15 +3126,14 @@ def stage_host_precommitted(value, eq, aux, cycle_active, cycle_total, address_a
     ca, n_ca = _size_array(cycle_active)
     aa, n_aa = _size_array(address_active)
     h = C.c_void_p()
-    _ck(lib().jolt_stage_host_precommitted_create(_p(tabs[0]), _p(tabs[1]), ptrs, C.c_size_t(len(tabs) - 2), C.c_size_t(tabs[0].shape[0] if length is None else length), ca,
-                                                  C.c_size_t(n_ca), C.c_size_t(cycle_total), aa, C.c_size_t(n_aa), C.c_size_t(address_total), C.byref(h)),
-        "jolt_stage_host_precommitted_create")
+    _call("jolt_stage_host_precommitted_create", None, _p(tabs[0]), _p(tabs[1]), ptrs, len(tabs) - 2, tabs[0].shape[0] if length is None else length, ca, n_ca, cycle_total,
+          aa, n_aa, address_total, C.byref(h))
     return StageOp(None, h)
 
 
 def stage_host_precommitted_address(cycle_op):
     h = C.c_void_p()
-    _ck(lib().jolt_stage_host_precommitted_address_create(cycle_op.h, C.byref(h)), "jolt_stage_host_precommitted_address_create")
+    _call("jolt_stage_host_precommitted_address_create", None, cycle_op.h, C.byref(h))
     return StageOp(None, h)
 
 
@@ -3206,7 +3141,7 @@ def host_precommitted_lsb_permutation(perm_be):
     """lsb_permutation -> (old_lsb_to_new_lsb as a list, is_identity)"""
     p, n = _size_array(perm_be)
     out, same = (C.c_size_t * max(n, 1))(), C.c_int32()
-    _ck(lib().jolt_host_precommitted_lsb_permutation(p, C.c_size_t(n), out, C.byref(same)), "jolt_host_precommitted_lsb_permutation")
+    _call("jolt_host_precommitted_lsb_permutation", None, p, n, out, C.byref(same))
     return [int(out[i]) for i in range(n)], bool(same.value)
 
 
@@ -3214,28 +3149,28 @@ def host_precommitted_permute_challenges(challenges_be, mapping):
     c = fr(challenges_be).reshape(-1, 4)
     m, n = _size_array(mapping)
     out = fr_array(max(n, 1))
-    _ck(lib().jolt_host_precommitted_permute_challenges(_p(c), C.c_size_t(c.shape[0]), m, _p(out)), "jolt_host_precommitted_permute_challenges")
+    _call("jolt_host_precommitted_permute_challenges", None, _p(c), c.shape[0], m, _p(out))
     return out[:n]
 
 
 def _table_permute_bits(self, table, old_lsb_to_new_lsb):
     m, n = _size_array(old_lsb_to_new_lsb)
     h = C.c_void_p()
-    _ck(lib().jolt_table_permute_bits(self.h, table.h, m, C.c_size_t(n), C.byref(h)), "jolt_table_permute_bits", self)
+    _call("jolt_table_permute_bits", self, self.h, table.h, m, n, C.byref(h))
     return Table(self, h)
 
 
 def _eq_evals_shifted(self, r, start_index, length):
     r = fr(r).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_eq_evals_shifted(self.h, _p(r), C.c_size_t(r.shape[0]), C.c_size_t(start_index), C.c_size_t(length), C.byref(h)), "jolt_eq_evals_shifted", self)
+    _call("jolt_eq_evals_shifted", self, self.h, _p(r), r.shape[0], start_index, length, C.byref(h))
     return Table(self, h)
 
 
 def _table_outer(self, lane_weights, cycle_table, order):
     w = fr(lane_weights).reshape(-1, 4)
     h = C.c_void_p()
-    _ck(lib().jolt_table_outer(self.h, _p(w), C.c_size_t(w.shape[0]), cycle_table.h, C.c_int32(order), C.byref(h)), "jolt_table_outer", self)
+    _call("jolt_table_outer", self, self.h, _p(w), w.shape[0], cycle_table.h, order, C.byref(h))
     return Table(self, h)
 
 

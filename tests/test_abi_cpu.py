@@ -531,3 +531,135 @@ def test_host_transcript_is_the_oracles_byte_for_byte():
             else:
                 assert np.array_equal(mine.challenge(full_width=True), theirs.challenge_scalar()), (label, step)
         mine.close()
+
+
+# ---- the header as the one statement of the ABI (jolt_amd/abi.py): prototypes, constants, callback types
+_WIDTHS = {"int32_t": (4, True), "uint32_t": (4, False), "int64_t": (8, True), "uint64_t": (8, False), "uint8_t": (1, False), "uint16_t": (2, False),
+           "size_t": (C.sizeof(C.c_void_p), False)}
+
+
+def _is_scalar_of(ctype, base):
+    """ctype is the ctypes integer of `base`'s width and signedness (or the float type of that name)"""
+    if base in ("float", "double"):
+        return ctype is {"float": C.c_float, "double": C.c_double}[base]
+    width, signed = _WIDTHS[base]
+    return C.sizeof(ctype) == width and (ctype(-1).value < 0) == signed and isinstance(ctype(1).value, int)
+
+
+def test_every_declared_entry_point_has_the_headers_prototype():
+    """ffi.lib() declares argtypes / restype for every entry point from the header: arity, exact width and signedness of every scalar, c_void_p for every pointer and
+    function pointer, c_char_p for the two `const char *` returns.  Widths and signedness are measured on the ctypes types, against a table of the C types kept here."""
+    from jolt_amd import abi
+    lib = ffi.lib()
+    decls = abi.parse_header()
+    assert sorted(d[0] for d in decls) == declared_symbols() and len(decls) > 300
+    returns = {}
+    for name, (rbase, rptr), params in decls:
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        for got, (pname, (base, ptr)) in zip(fn.argtypes, params):
+            if ptr or base in abi.CALLBACKS:
+                assert got is C.c_void_p, (name, pname)
+            else:
+                assert _is_scalar_of(got, base), (name, pname, got)
+        if rptr:
+            assert (rbase, rptr) == ("char", (True,)) and fn.restype is C.c_char_p, name
+        else:
+            assert _is_scalar_of(fn.restype, rbase), name
+        returns[rbase] = returns.get(rbase, 0) + 1
+    assert returns["char"] == 2 and returns["uint32_t"] == 2 and set(returns) == {"int32_t", "uint32_t", "char"}
+
+
+def test_sixty_four_bit_arguments_survive_and_mistyped_ones_never_reach_c():
+    """A bare Python int reaches a size_t parameter whole (without a prototype ctypes truncates it to a 32-bit int: the direct call below computed on n = 5), and a
+    float or a ctypes integer of another width is refused before the call.  Closed form of the owned-term count: full * block + clamp(rem - rank * block, 0, block),
+    full = n // (block * world), rem = n - full * block * world."""
+    n, block, rank, world = 2**33 + 5, 4, 1, 2
+    full = n // (block * world)
+    want = full * block + min(max(n - full * block * world - rank * block, 0), block)
+    assert want == 2**32 + 1
+    assert ffi.host_owned_terms(n, block, rank, world) == want
+    out = C.c_size_t()
+    assert ffi.lib().jolt_host_owned_terms(n, block, rank, world, C.byref(out)) == 0 and out.value == want
+    for bad in (1.5, C.c_uint32(8)):
+        with pytest.raises(C.ArgumentError):
+            ffi.lib().jolt_host_owned_terms(bad, block, rank, world, C.byref(out))
+        with pytest.raises(C.ArgumentError):
+            ffi.lib().jolt_host_owned_terms(n, bad, rank, world, C.byref(out))
+
+
+def test_constants_and_callback_types_come_from_the_header():
+    """abi.CONSTANTS has one entry per enum member and numeric #define of the header (counted here with a flat regex of its own), ffi's public constants are those
+    values, the CFUNCTYPE callback types have their typedef's arity and scalar widths, and the three struct mirrors have the size the C compiler gives the structs."""
+    import shutil
+    import subprocess
+    from jolt_amd import abi, distributed
+    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    flat = dict(re.findall(r"\b(JOLT_[A-Z0-9_]+)\s*=\s*(\d+)", text) + re.findall(r"#\s*define\s+(JOLT_[A-Z0-9_]+)[ \t]+(\d+)[uU]?[ \t]*(?:\n|$)", text))
+    assert {k: int(v) for k, v in flat.items()} == abi.CONSTANTS and len(flat) >= 68
+    shared = [k for k in abi.CONSTANTS if hasattr(ffi, k[len("JOLT_"):]) and not k.startswith("JOLT_TRANSCRIPT_")]
+    assert len(shared) >= 60
+    for k in shared:
+        assert getattr(ffi, k[len("JOLT_"):]) == abi.CONSTANTS[k], k
+    for name in ("ORDER_LOW_TO_HIGH", "ORDER_HIGH_TO_LOW", "MEMBER_FLAG_SKIP_ONE", "MEMBER_FLAG_BORROW_TABLES", "PAIRING_LINES", "ROUND_PATH_COUNT", "STAGE_MEMBER_OWN",
+                 "DORY_KIND_G1", "DORY_KIND_G2", "DORY_KIND_FR", "DORY_PAIR", "DORY_MSM_G1", "DORY_MSM_G2", "DORY_UPDATE_BETA", "DORY_UPDATE_ALPHA", "DORY_PHASE_VMV",
+                 "DORY_PHASE_FINAL", "TRACE_CYCLE_MAJOR", "TRACE_ADDRESS_MAJOR", "FQ2_NEG", "FQ12_MUL_SPARSE"):
+        assert "JOLT_" + name in shared, name
+    # the transcript kinds are exported shifted into a label's top two bits (JOLT_TRANSCRIPT_LABEL(kind, 0)); the status messages are keyed by the header's codes
+    for mine, kind in (("TEST", "TEST"), ("BLAKE2B", "BLAKE2B_LEGACY"), ("KECCAK", "KECCAK_SPONGE"), ("BLAKE2B_SPONGE", "BLAKE2B_SPONGE")):
+        assert getattr(ffi, "TRANSCRIPT_" + mine) == abi.CONSTANTS["JOLT_TRANSCRIPT_" + kind] << 62
+    assert sorted(ffi.STATUS) == sorted(v for k, v in abi.CONSTANTS.items() if k == "JOLT_OK" or k.startswith("JOLT_ERR_"))
+    assert ffi.STATUS[abi.CONSTANTS["JOLT_ERR_NO_DEVICE"]] == "no device" and ffi.Ints.KINDS == {"u64": 0, "i64": 1, "i128": 2}
+
+    typedefs = dict(re.findall(r"typedef\s+int32_t\s*\(\*(jolt_\w+_fn)\)\s*\(([^;]*?)\)\s*;", text, flags=re.S))
+    assert set(typedefs) == set(abi.CALLBACK_TYPES) and len(typedefs) == 5
+    assert ffi.OPEN_TRANSCRIPT_FN is abi.CALLBACK_TYPES["jolt_open_transcript_fn"] and ffi.DORY_TRANSCRIPT_FN is abi.CALLBACK_TYPES["jolt_dory_transcript_fn"]
+    assert distributed.LOCAL_FN is abi.CALLBACK_TYPES["jolt_local_round_fn"] and distributed.GATHER_FN is abi.CALLBACK_TYPES["jolt_gather_fn"]
+    for name, params in typedefs.items():
+        cb = abi.CALLBACK_TYPES[name]
+        params = [p.strip() for p in params.split(",")]
+        assert cb._restype_ is C.c_int32 and len(cb._argtypes_) == len(params), name
+        for got, p in zip(cb._argtypes_, params):
+            if "*" in p:
+                assert C.sizeof(got) == C.sizeof(C.c_void_p) and (got is C.c_void_p or issubclass(got, C._Pointer)), (name, p)
+            else:
+                assert _is_scalar_of(got, p.split()[0]), (name, p)
+
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("no gcc: the struct sizes cannot be compared with the C compiler's")
+    probe = ('#include <stdio.h>\n#include "jolt_hip.h"\n'
+             'int main(void) { printf("%zu %zu %zu\\n", sizeof(jolt_member_desc), sizeof(jolt_member_lc_desc), sizeof(jolt_dory_item)); return 0; }\n')
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        src, exe = os.path.join(tmp, "sizes.c"), os.path.join(tmp, "sizes")
+        open(src, "w").write(probe)
+        subprocess.run([gcc, "-I", os.path.dirname(HEADER), src, "-o", exe], check=True)
+        sizes = [int(x) for x in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    assert sizes == [C.sizeof(ffi.MemberDesc), C.sizeof(ffi.MemberLcDesc), C.sizeof(ffi.DoryItem)]
+
+
+def test_no_scalar_cast_stands_at_a_declared_entry_point_in_the_package():
+    """The prototypes are the one statement of the argument types: no `C.c_size_t(..)` / c_uint32 / c_int32 / c_uint64 / c_int64 call is a direct argument of a declared
+    entry point in jolt_amd/*.py, whether the call is written lib().jolt_x(..), getattr(lib(), name)(..) or _call("jolt_x", ctx, ..)."""
+    import ast
+    import glob
+    from jolt_amd import abi
+    declared = {d[0] for d in abi.parse_header()}
+    casts = {"c_size_t", "c_uint32", "c_int32", "c_uint64", "c_int64"}
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "jolt_amd")
+    sites, found = 0, []
+    for path in sorted(glob.glob(os.path.join(root, "*.py"))):
+        for node in ast.walk(ast.parse(open(path).read())):
+            if not isinstance(node, ast.Call):
+                continue
+            f = node.func
+            entry = (isinstance(f, ast.Attribute) and f.attr in declared) or (isinstance(f, ast.Call) and isinstance(f.func, ast.Name) and f.func.id == "getattr") \
+                or (isinstance(f, (ast.Name, ast.Attribute)) and ast.unparse(f).split(".")[-1] == "_call")
+            if not entry:
+                continue
+            sites += 1
+            for a in node.args:
+                if isinstance(a, ast.Call) and ast.unparse(a.func).split(".")[-1] in casts and a.args:
+                    found.append((os.path.basename(path), node.lineno, ast.unparse(a)))
+    assert sites > 350 and not found, found

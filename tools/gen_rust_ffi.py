@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate rust/jolt-kernels-hip/src/ffi.rs from include/jolt_hip.h (and parse either side for the agreement test).
+"""Generate rust/jolt-kernels-hip/src/ffi.rs from include/jolt_hip.h as jolt_amd/abi.py reads it (and parse either side for the agreement test).
 
 The image has no Rust toolchain, so the FFI crate cannot be compiled here; what CAN be guaranteed mechanically is that the Rust
 declarations name every entry point of the C header with the same arity and the same types.  tests/test_abi_cpu.py re-parses both
@@ -13,77 +13,27 @@ import re
 import sys
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-HEADER = os.path.join(ROOT, "include", "jolt_hip.h")
 FFI_RS = os.path.join(ROOT, "rust", "jolt-kernels-hip", "src", "ffi.rs")
+
+sys.path.insert(0, ROOT)
+from jolt_amd import abi  # noqa: E402  (the header's parser lives with the Python binding, which reads the same declarations)
 
 SCALARS = {"int32_t": "i32", "uint32_t": "u32", "uint64_t": "u64", "int64_t": "i64", "uint8_t": "u8", "uint16_t": "u16", "size_t": "usize", "float": "f32", "double": "f64",
            "void": "c_void", "char": "c_char"}
-def opaque_handles(path=None):
-    """every `typedef struct X X;` of the header, in declaration order: the handle types ffi.rs must define (a hand-kept list went stale in round 3)"""
-    return re.findall(r"typedef\s+struct\s+(jolt_\w+)\s+\1\s*;", open(path or HEADER).read())
-
-
-FNPTR = {"jolt_local_round_fn", "jolt_gather_fn", "jolt_round_transcript_fn", "jolt_open_transcript_fn", "jolt_dory_transcript_fn"}
-
-
-def strip_comments(src):
-    return re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
 
 
 def c_type_to_rust(ctype):
-    """'const jolt_fr_t *const *' -> '*const *const jolt_fr_t' (pointer levels read right to left)."""
-    t = ctype.strip()
-    toks = re.findall(r"\*|\w+", t)
-    base, i = None, 0
-    base_const = False
-    while i < len(toks) and toks[i] != "*":
-        if toks[i] == "const":
-            base_const = True
-        elif toks[i] != "struct":
-            base = toks[i]
-        i += 1
+    """('jolt_fr_t', (True, True)), i.e. 'const jolt_fr_t *const *' -> '*const *const jolt_fr_t' (pointer levels read right to left)."""
+    base, consts = ctype
     rust = SCALARS.get(base, base)
-    const_here = base_const
-    while i < len(toks):
-        assert toks[i] == "*", ctype
-        rust = ("*const " if const_here else "*mut ") + rust
-        i += 1
-        const_here = False
-        if i < len(toks) and toks[i] == "const":
-            const_here = True
-            i += 1
-    if base in FNPTR and not rust.startswith("*"):
-        return base
+    for const in consts:
+        rust = ("*const " if const else "*mut ") + rust
     return rust
 
 
-def parse_header(path=HEADER):
+def parse_header(path=abi.HEADER):
     """-> list of (name, ret_rust, [(param_name, rust_type)]) in declaration order"""
-    src = strip_comments(open(path).read())
-    src = re.sub(r"#.*", "", src)
-    src = re.sub(r'extern\s+"C"\s*\{', "", src)
-    decls = []
-    for m in re.finditer(r"(?:^|;|\})\s*((?:const\s+)?\w+\s*\**)\s*(jolt_\w+)\s*\(([^;{}]*?)\)\s*(?=;)", src, flags=re.S):
-        ret, name, params = m.group(1), m.group(2), m.group(3)
-        stmt_start = max(src.rfind(";", 0, m.start(2)), src.rfind("}", 0, m.start(2))) + 1
-        if "typedef" in src[stmt_start:m.start(2)]:
-            continue
-        plist = []
-        params = " ".join(params.split())
-        if params and params != "void":
-            for k, p in enumerate(params.split(",")):
-                p = p.strip()
-                arr = re.match(r"(.*?)(\w+)\s*\[\s*\d*\s*\]$", p)  # `uint8_t out[32]` / `const jolt_fr_t u[3]` decay to pointers
-                if arr:
-                    ctype, pname = arr.group(1).strip() + " *", arr.group(2)
-                else:
-                    mm = re.match(r"(.*?)(\w+)$", p)
-                    ctype, pname = mm.group(1).strip(), mm.group(2)
-                    if not ctype:  # unnamed parameter
-                        ctype, pname = p, f"arg{k}"
-                plist.append((pname, c_type_to_rust(ctype)))
-        decls.append((name, c_type_to_rust(ret), plist))
-    return decls
+    return [(name, c_type_to_rust(ret), [(p, c_type_to_rust(t)) for p, t in params]) for name, ret, params in abi.parse_header(path)]
 
 
 def parse_rust(path=FFI_RS):
@@ -120,7 +70,7 @@ def render(decls):
     out.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]\npub struct jolt_fq2_t {\n    pub c0: jolt_fq_t,\n    pub c1: jolt_fq_t,\n}")
     out.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]\npub struct jolt_g2_t {\n    pub x: jolt_fq2_t,\n    pub y: jolt_fq2_t,\n    pub z: jolt_fq2_t,\n}")
     out.append("#[repr(C)]\n#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]\npub struct jolt_gt_t {\n    pub c: [jolt_fq_t; 12],\n}")
-    for o in opaque_handles():
+    for o in abi.opaque_handles():
         out.append(f"#[repr(C)]\npub struct {o} {{\n    _private: [u8; 0],\n}}")
     out.append("")
     out.append("/// Status codes (`enum` of the header); see `crate::status` for the mapping onto the reference's error types.")
