@@ -1501,24 +1501,15 @@ extern "C" int32_t jolt_dory_combine_hints(jolt_ctx* ctx, const jolt_g1_t* const
     JOLT_REQUIRE(ctx, combine_plan(scalars, n_hints, &plan), "scalar is not a canonical Fr");
     if (rows == 0) return JOLT_OK;
     if (!out) return JOLT_ERR_INVALID_ARG;
-    hipStream_t st = ctx->stream;
+    dory_host::HostCall c(ctx);
     G1Jac *d_pts = nullptr, *d_out = nullptr;
-    int32_t rc = jolt_internal_dev_alloc(ctx, total * sizeof(G1Jac), (void**)&d_pts);
-    if (rc == JOLT_OK) rc = jolt_internal_dev_alloc(ctx, rows * sizeof(G1Jac), (void**)&d_out);
-    hipError_t e = hipSuccess;
-    if (rc == JOLT_OK) {
-        for (size_t i = 0; i < n_hints && e == hipSuccess; ++i)
-            if (hint_rows[i]) e = hipMemcpyAsync(d_pts + meta[i], hints[i], hint_rows[i] * sizeof(G1Jac), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) rc = dory_host::combine_enqueue(ctx, d_pts, meta, plan, rows, d_out);
-        if (e == hipSuccess && rc == JOLT_OK) e = hipMemcpyAsync(out, d_out, rows * sizeof(G1Jac), hipMemcpyDeviceToHost, st);
-        hipError_t e2 = hipStreamSynchronize(st);  // the plan and the caller's arrays are read until here
-        if (e == hipSuccess) e = e2;
-    }
-    jolt_internal_dev_free(ctx, d_pts);
-    jolt_internal_dev_free(ctx, d_out);
-    if (rc != JOLT_OK) return rc;
-    if (e != hipSuccess) return hip_fail(ctx, "dory combine", e);
-    return JOLT_OK;
+    c.take(total, &d_pts);
+    c.take(rows, &d_out);
+    for (size_t i = 0; i < n_hints; ++i)
+        if (hint_rows[i]) c.h2d(d_pts + meta[i], hints[i], hint_rows[i]);
+    if (c.ok()) c.rc = dory_host::combine_enqueue(ctx, d_pts, meta, plan, rows, d_out);
+    c.down(out, d_out, rows);
+    return c.finish("dory combine");  // the plan and the caller's arrays are read until here
 }
 
 // The per-row routine of k_dory_combine_windows / k_dory_combine_horner on the host: out = sum_i scalars[i] * points[i], through the same plan, window walk and Horner

@@ -1,6 +1,9 @@
-// jolt_amd/csrc/dory_host.hpp -- host-side helpers shared by the Dory entry points (dory.hip, dory_routines.hip, dory_pairing.hip, dory_resident.hip).
+// jolt_amd/csrc/dory_host.hpp -- host-side helpers shared by the Dory entry points (dory.hip, dory_routines.hip, dory_pairing.hip, dory_resident.hip,
+// dory_scheme.hip): the views of resident vectors, the argument checks' thread pool, and the two scopes every entry's body is written on -- HostCall (pool blocks,
+// copies, phase clock, running error, the synchronise before return) and Fork (side chains forked from and joined to the main stream).
 #pragma once
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -72,6 +75,95 @@ struct DevBufs {  // pool blocks of one call, returned on every path
         if (rc == JOLT_OK) blocks.push_back(p);
         *out = (T*)p;
         return rc;
+    }
+};
+
+// One call of an entry point that copies from or to the caller's host arrays: its pool blocks, its phase clock (`ms` and `timing` of jolt_dory_routines_timing or
+// jolt_dory_pairing_timing; none for an entry without a clock) and its running error.  After the first failure every member but finish() does nothing, so a body
+// reads straight down: up() per array, `if (c.ok()) c.e = enqueue_...`, down(), finish().  finish() synchronises the stream on EVERY path: host memory of the call
+// (the caller's arrays, tables on the entry's stack) is read and written until there.
+struct HostCall {
+    jolt_ctx* ctx;
+    hipStream_t st;
+    DevBufs bufs;
+    hipError_t e = hipSuccess;
+    int32_t rc = JOLT_OK;  // a pool allocation that failed; it outranks `e`
+    double* ms = nullptr;
+    bool timing = false;
+    std::chrono::steady_clock::time_point t0;
+    explicit HostCall(jolt_ctx* c) : ctx(c), st(c->stream), bufs(c) {}
+    template <size_t P>
+    HostCall(jolt_ctx* c, double (&phase_ms)[P], bool timing_on) : ctx(c), st(c->stream), bufs(c), ms(phase_ms), timing(timing_on), t0(std::chrono::steady_clock::now()) {
+        if (timing) std::fill(ms, ms + P, 0.0);
+    }
+    bool ok() const { return e == hipSuccess && rc == JOLT_OK; }
+    template <class T>
+    void take(size_t n, T** dev) {
+        if (ok()) rc = bufs.take(n, dev);
+    }
+    template <class T>
+    void h2d(T* dev, const void* host, size_t n) {
+        if (ok()) e = hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, st);
+    }
+    template <class T>
+    void up(const void* host, size_t n, T** dev) {
+        take(n, dev);
+        h2d(*dev, host, n);
+    }
+    template <class T>
+    void down(void* host, const T* dev, size_t n) {
+        if (ok()) e = hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, st);
+    }
+    // closes `phase`.  With timing on, the stream is drained first so that the phase gets its own wall time -- not for host-only phases (`drain` false); with
+    // timing off, neither the stream nor the array is touched
+    void mark(int phase, bool drain = true) {
+        if (!timing || !ok()) return;
+        if (drain) e = hipStreamSynchronize(st);
+        stamp(phase);
+    }
+    // the call's last phase ends with its synchronise
+    int32_t finish(const char* what, int last_phase = 0) {
+        const hipError_t e_sync = hipStreamSynchronize(st);
+        if (rc != JOLT_OK) return rc;
+        if (e == hipSuccess) e = e_sync;
+        if (timing) stamp(last_phase);
+        return e == hipSuccess ? JOLT_OK : hip_fail(ctx, what, e);
+    }
+
+private:
+    void stamp(int phase) {
+        const auto t1 = std::chrono::steady_clock::now();
+        ms[phase] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+    }
+};
+
+// Side chains beside the context's main stream: forked from it by ev_fork when made, joined by ev_join[c].  A chain runs on the main stream itself when the
+// context serialises its streams or has no side stream c.
+struct Fork {
+    jolt_ctx* ctx;
+    int chains;
+    hipStream_t st[3];
+    hipError_t e;  // of the fork
+    Fork(jolt_ctx* c, int n_chains) : ctx(c), chains(n_chains) {
+        for (int k = 0; k < chains; ++k) st[k] = (c->serial_streams || !c->side[k]) ? c->stream : c->side[k];
+        e = hipEventRecord(c->ev_fork, c->stream);
+        for (int k = 0; k < chains && e == hipSuccess; ++k)
+            if (st[k] != c->stream) e = hipStreamWaitEvent(st[k], c->ev_fork, 0);
+    }
+    // enqueued on every path: the main stream must not run ahead of a chain that was started.  A chain whose join cannot be enqueued is synchronised instead.
+    // Returns `err`, or the first error of the joins when `err` is none.
+    hipError_t join(hipError_t err) {
+        for (int k = 0; k < chains; ++k) {
+            if (st[k] == ctx->stream) continue;
+            hipError_t ej = hipEventRecord(ctx->ev_join[k], st[k]);
+            if (ej == hipSuccess) ej = hipStreamWaitEvent(ctx->stream, ctx->ev_join[k], 0);
+            if (ej != hipSuccess) {
+                (void)hipStreamSynchronize(st[k]);
+                if (err == hipSuccess) err = ej;
+            }
+        }
+        return err;
     }
 };
 

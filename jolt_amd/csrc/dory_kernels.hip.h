@@ -1,5 +1,6 @@
 // jolt_amd/csrc/dory_kernels.hip.h -- what the Dory round entry points share: the two groups behind one interface, the shared scalar's non-adjacent form and its
-// walk, the fixed-base table and its signed-nibble walk, one MSM term, and the kernels over them.  dory_routines.hip runs them on the caller's host arrays, dory_resident.hip on vectors that stay in HBM.
+// walk, the fixed-base table and its signed-nibble walk, one MSM term, the kernels over them and their launch layer (enqueue_*: one launch site per kernel).
+// dory_routines.hip runs them on the caller's host arrays, dory_resident.hip and dory_scheme.hip on vectors that stay in HBM.
 #pragma once
 #include <cstring>
 
@@ -138,6 +139,11 @@ void fixed_table(const typename O::Pt& base, typename O::Pt* table) {
     table[1] = base;
     for (int k = 2; k < kFixedTable; ++k) table[k] = (k & 1) ? O::add(table[k - 1], base) : O::dbl(table[k / 2]);
 }
+// from a base point of the ABI (checked by the caller).  The table stays in the caller's frame: its upload reads it until the caller's synchronise
+template <class O>
+void fixed_table_from_abi(const void* base, typename O::Pt (&table)[kFixedTable]) {
+    fixed_table<O>(dory_host::pt_from_abi<typename O::Pt>(base), table);
+}
 // scalar * base.  Signed digits without a carry chain: k' = k + 0x88..8 (8 in each of the 64 nibbles; k < 2^254, so k' < 2^256), digit w = nibble w of k' - 8 in [-8, 7],
 // since sum_w 8 * 16^w is exactly what was added.  The table entry is taken by index (digits differ from lane to lane), its sign by a select on y.
 template <class O>
@@ -183,17 +189,56 @@ __global__ __launch_bounds__(kLanes) void k_dory_fixed_base(const typename O::Pt
     if (i >= n) return;
     out[i] = fixed_mul_one<O>(table, scalars[i]);
 }
-// one level of the addition tree: terms[i] += terms[i + half] for i + half < m
+// one level of a halving tree: v[i] = v[i] (x) v[i + half] for i + half < m.  Op: AddPt<O> for the sums of an MSM, MulFq12 (dory_prepared.hip.h) for the product of
+// the Miller values; k_batch_tree_level of dory_resident.hip takes the same step inside every item's segment
 template <class O>
-__global__ __launch_bounds__(kLanes) void k_dory_tree_level(typename O::Pt* terms, size_t half, size_t m) {
+struct AddPt {
+    static JOLT_HD typename O::Pt combine(const typename O::Pt& a, const typename O::Pt& b) { return O::add(a, b); }
+};
+template <class T, class Op>
+__global__ __launch_bounds__(kLanes) void k_tree_level(T* v, size_t half, size_t m) {
     const size_t i = (size_t)blockIdx.x * kLanes + threadIdx.x;
     if (i >= half || i + half >= m) return;
-    terms[i] = O::add(terms[i], terms[i + half]);
+    v[i] = Op::combine(v[i], v[i + half]);
 }
 static __global__ __launch_bounds__(256) void k_dory_fold_field(Fr* __restrict__ left, const Fr* __restrict__ right, Fr s, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     st_fr(left + i, add(mul(ld_fr(left + i), s), ld_fr(right + i)));
+}
+
+// ---- the launch layer: THE launch site of each kernel above, over device pointers, n > 0.  These only enqueue on `st` and return hipGetLastError(); the host-pointer
+// entries (dory_routines.hip, dory_pairing.hip), the resident ones (dory_resident.hip) and a round's update (dory_scheme.hip) all go through them ----
+template <class O>
+hipError_t enqueue_scale_add(hipStream_t st, const NafPlan& plan, const typename O::Pt* scaled, const typename O::Pt* addend, typename O::Pt* out, size_t n) {
+    hipLaunchKernelGGL(k_dory_scale_add<O>, dim3(dory_host::lanes_grid(n)), dim3(kLanes), 0, st, plan, scaled, addend, out, n);
+    return hipGetLastError();
+}
+inline hipError_t enqueue_fold_field(hipStream_t st, Fr* left, const Fr* right, const Fr& s, size_t n) {
+    hipLaunchKernelGGL(k_dory_fold_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, left, right, s, n);
+    return hipGetLastError();
+}
+// d_table: fixed_table's kFixedTable points on the device
+template <class O>
+hipError_t enqueue_fixed_base(hipStream_t st, const typename O::Pt* d_table, const Fr* d_scalars, typename O::Pt* d_out, size_t n) {
+    hipLaunchKernelGGL(k_dory_fixed_base<O>, dim3(dory_host::lanes_grid(n)), dim3(kLanes), 0, st, d_table, d_scalars, d_out, n);
+    return hipGetLastError();
+}
+// the halving loop: the result in d_v[0], NOT normalised
+template <class T, class Op>
+hipError_t enqueue_tree(hipStream_t st, T* d_v, size_t n) {
+    for (size_t m = n; m > 1;) {
+        const size_t half = (m + 1) / 2;
+        hipLaunchKernelGGL((k_tree_level<T, Op>), dim3(dory_host::lanes_grid(half)), dim3(kLanes), 0, st, d_v, half, m);
+        m = half;
+    }
+    return hipGetLastError();
+}
+// sum_i scalars[i] * bases[i] into d_terms[0] (n terms of scratch): the term launch and the addition tree
+template <class O>
+hipError_t enqueue_msm(hipStream_t st, const typename O::Pt* d_bases, const Fr* d_scalars, typename O::Pt* d_terms, size_t n) {
+    hipLaunchKernelGGL(k_dory_msm_terms<O>, dim3(dory_host::lanes_grid(n)), dim3(kLanes), 0, st, d_bases, d_scalars, d_terms, n);
+    return enqueue_tree<typename O::Pt, AddPt<O>>(st, d_terms, n);
 }
 
 // ---- the argument checks of the entry points ----

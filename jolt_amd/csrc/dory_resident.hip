@@ -10,12 +10,13 @@
 //     k_batch_miller         one launch over all pairs of all PAIR items: miller_walk per lane against the scratch table or a range of a jolt_g2_prepared
 //     k_batch_msm_terms      one launch per group over all MSM items of that group: term_mul_one per lane
 //     k_batch_tree_level     one launch per LEVEL over all items of a chain: f[i] *= f[i + half] / terms[i] += terms[i + half] inside each item's segment, with that
-//                            segment's own m -- the step of k_pair_product_level and k_dory_tree_level
+//                            segment's own m -- the step of k_tree_level (dory_kernels.hip.h), under the same operations
 //     k_batch_gather         each item's element 0 (or the neutral element of an empty item) into one result block: one read-back for the batch
 //   jolt_dory_state_alloc / _from_table / _combine_hints / _fixed_base_mul   the state an opening's rounds start from, built where it is used: neutral vectors
 //                            (k_dory_fill), entries of an Fr table (a device copy), the combined hints (the plan and the two kernels of dory.hip's combine_hints, on
 //                            the hints gathered back to back by device copies), multiples of one base (k_dory_fixed_base of dory_kernels.hip.h)
-//   The three chains are independent: they run on the context's side streams, forked from the main stream by one event and joined before the read-back.
+//   The three chains are independent: they run on the context's side streams, forked from the main stream by one event and joined before the read-back (Fork of
+//   dory_host.hpp).  Single launches go through the launch layer of dory_kernels.hip.h / dory_prepared.hip.h; an entry that reads host memory is one HostCall.
 // Workgroups of one wavefront, one element per lane, integer VALU work, no MFMA, as the kernels these are made of; register figures in docs/kernels.md 3.5h.
 #include <algorithm>
 #include <thread>
@@ -122,14 +123,8 @@ __global__ __launch_bounds__(kLanes) void k_batch_msm_terms(const WgDev* __restr
     if (i >= it.len) return;
     terms[it.base + i] = term_mul_one<O>(it.pts[i], it.scalars[i]);
 }
-struct MulFq12 {
-    static JOLT_HD Fq12 combine(const Fq12& a, const Fq12& b) { return mul(a, b); }
-};
-template <class O>
-struct AddPt {
-    static JOLT_HD typename O::Pt combine(const typename O::Pt& a, const typename O::Pt& b) { return O::add(a, b); }
-};
-// level `level` of every item's tree at once: the segment holds m = len halved `level` times elements, v[i] = v[i] (x) v[i + half] for i + half < m
+// level `level` of every item's tree at once: the segment holds m = len halved `level` times elements, v[i] = v[i] (x) v[i + half] for i + half < m -- the step of
+// k_tree_level, under the same Op (MulFq12, AddPt<O>)
 template <class T, class Op>
 __global__ __launch_bounds__(kLanes) void k_batch_tree_level(const WgDev* __restrict__ wgs, const SegDev* __restrict__ segs, T* v, uint32_t level) {
     const WgDev w = wgs[blockIdx.x];
@@ -182,8 +177,7 @@ int32_t scale_add_views(jolt_ctx* ctx, jolt_dory_vec* vs, size_t vs_first, const
     if (n == 0) return JOLT_OK;
     Pt* d_vs = at<Pt>(vs, vs_first);
     const Pt* d_other = at<Pt>(other, other_first);
-    hipLaunchKernelGGL(k_dory_scale_add<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, ctx->stream, plan, scale_vs ? (const Pt*)d_vs : d_other, scale_vs ? d_other : (const Pt*)d_vs, d_vs, n);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = enqueue_scale_add<O>(ctx->stream, plan, scale_vs ? d_vs : d_other, scale_vs ? d_other : d_vs, d_vs, n);
     return e == hipSuccess ? JOLT_OK : hip_fail(ctx, what, e);
 }
 int32_t scale_add_entry(jolt_ctx* ctx, jolt_dory_vec* vs, size_t vs_first, const jolt_dory_vec* other, size_t other_first, size_t n, const jolt_fr_t* scalar, bool scale_vs, const char* what) {
@@ -218,13 +212,11 @@ extern "C" int32_t jolt_dory_vec_upload(jolt_ctx* ctx, int32_t kind, const void*
     }
     jolt_dory_vec* v = nullptr;
     JOLT_TRY(vec_new(ctx, kind, n, &v));
-    const size_t bytes = n * kind_size(kind);
     int32_t rc = JOLT_OK;
     if (n) {
-        hipError_t e = hipMemcpyAsync(v->data, host, bytes, hipMemcpyHostToDevice, ctx->stream);
-        const hipError_t e2 = hipStreamSynchronize(ctx->stream);  // the caller's array is read until here
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) rc = hip_fail(ctx, "dory vec upload", e);
+        HostCall c(ctx);
+        c.h2d((uint8_t*)v->data, host, n * kind_size(kind));
+        rc = c.finish("dory vec upload");
     }
     if (rc != JOLT_OK) {
         (void)jolt_dory_vec_free(ctx, v);
@@ -239,11 +231,9 @@ extern "C" int32_t jolt_dory_vec_download(jolt_ctx* ctx, const jolt_dory_vec* ve
     JOLT_REQUIRE(ctx, view_ok(ctx, vec, vec->kind, first, n), "the view is outside its vector, or the vector belongs to another context");
     if (n == 0) return JOLT_OK;
     const size_t sz = kind_size(vec->kind);
-    hipError_t e = hipMemcpyAsync(host, (const uint8_t*)vec->data + first * sz, n * sz, hipMemcpyDeviceToHost, ctx->stream);
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return hip_fail(ctx, "dory vec download", e);
-    return JOLT_OK;
+    HostCall c(ctx);
+    c.down(host, (const uint8_t*)vec->data + first * sz, n * sz);
+    return c.finish("dory vec download");
 }
 
 extern "C" int32_t jolt_dory_vec_len(const jolt_dory_vec* vec, size_t* len) {
@@ -307,8 +297,7 @@ extern "C" int32_t jolt_dory_vec_fold_field(jolt_ctx* ctx, jolt_dory_vec* left, 
     const Fr s = fr_from_abi(scalar);
     JOLT_REQUIRE(ctx, fr_is_canonical(s), "scalar is not a canonical Fr");
     if (n == 0) return JOLT_OK;
-    hipLaunchKernelGGL(k_dory_fold_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, at<Fr>(left, left_first), (const Fr*)at<Fr>(right, right_first), s, n);
-    const hipError_t e = hipGetLastError();
+    const hipError_t e = enqueue_fold_field(ctx->stream, at<Fr>(left, left_first), at<Fr>(right, right_first), s, n);
     return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory vec field fold", e);
 }
 
@@ -358,19 +347,13 @@ extern "C" int32_t jolt_dory_state_combine_hints(jolt_ctx* ctx, const jolt_dory_
     CombinePlan plan;
     JOLT_REQUIRE(ctx, combine_plan(scalars, n_hints, &plan), "scalar is not a canonical Fr");
     if (rows == 0) return JOLT_OK;
-    hipStream_t st = ctx->stream;
-    DevBufs bufs(ctx);
+    HostCall c(ctx);
     G1Jac* d_pts = nullptr;
-    JOLT_TRY(bufs.take(total, &d_pts));
-    hipError_t e = hipSuccess;
-    for (size_t i = 0; i < n_hints && e == hipSuccess; ++i)  // back to back, the layout k_dory_combine_windows indexes
-        if (hint_rows[i]) e = hipMemcpyAsync(d_pts + meta[i], at<G1Jac>(hints[i], hint_first[i]), hint_rows[i] * sizeof(G1Jac), hipMemcpyDeviceToDevice, st);
-    int32_t rc = JOLT_OK;
-    if (e == hipSuccess) rc = combine_enqueue(ctx, d_pts, meta, plan, rows, at<G1Jac>(out, out_first));
-    const hipError_t e2 = hipStreamSynchronize(st);  // the plan (host memory of this call) is read until here
-    if (e == hipSuccess) e = e2;
-    if (rc != JOLT_OK) return rc;
-    return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory state combine", e);
+    c.take(total, &d_pts);
+    for (size_t i = 0; i < n_hints && c.ok(); ++i)  // back to back, the layout k_dory_combine_windows indexes
+        if (hint_rows[i]) c.e = hipMemcpyAsync(d_pts + meta[i], at<G1Jac>(hints[i], hint_first[i]), hint_rows[i] * sizeof(G1Jac), hipMemcpyDeviceToDevice, c.st);
+    if (c.ok()) c.rc = combine_enqueue(ctx, d_pts, meta, plan, rows, at<G1Jac>(out, out_first));
+    return c.finish("dory state combine");  // the plan (host memory of this call) is read until here
 }
 
 namespace {
@@ -379,20 +362,13 @@ int32_t fixed_base_views(jolt_ctx* ctx, const void* base, const jolt_dory_vec* s
     using Pt = typename O::Pt;
     JOLT_REQUIRE(ctx, all_on_curve<O>((const typename O::Abi*)base, 1), "a point is not on its curve or not canonical");
     if (n == 0) return JOLT_OK;
-    Pt table[kFixedTable];
-    fixed_table<O>(pt_from_abi<Pt>(base), table);
-    hipStream_t st = ctx->stream;
-    DevBufs bufs(ctx);
+    Pt table[kFixedTable];  // read by its upload until finish()
+    fixed_table_from_abi<O>(base, table);
+    HostCall c(ctx);
     Pt* d_table = nullptr;
-    JOLT_TRY(bufs.take(kFixedTable, &d_table));
-    hipError_t e = hipMemcpyAsync(d_table, table, sizeof(table), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_dory_fixed_base<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, (const Pt*)d_table, (const Fr*)at<Fr>(scalars, scalars_first), at<Pt>(out, out_first), n);
-        e = hipGetLastError();
-    }
-    const hipError_t e2 = hipStreamSynchronize(st);  // `table` (on this stack) is read until here
-    if (e == hipSuccess) e = e2;
-    return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory state fixed base", e);
+    c.up(table, kFixedTable, &d_table);
+    if (c.ok()) c.e = enqueue_fixed_base<O>(c.st, d_table, at<Fr>(scalars, scalars_first), at<Pt>(out, out_first), n);
+    return c.finish("dory state fixed base");
 }
 }  // namespace
 
@@ -463,20 +439,20 @@ extern "C" int32_t jolt_dory_products(jolt_ctx* ctx, const jolt_dory_item* items
         !batch_plan(g1_lens.data(), g1_lens.size(), &g1_plan) || !batch_plan(g2_lens.data(), g2_lens.size(), &g2_plan))
         return JOLT_ERR_UNSUPPORTED;
 
-    DevBufs bufs(ctx);
+    HostCall c(ctx);
     PairLine* d_lines = nullptr;
     uint8_t *d_skip = nullptr, *d_blob = nullptr, *d_res = nullptr;
     Fq12* d_f = nullptr;
     G1Jac* d_t1 = nullptr;
     G2Jac* d_t2 = nullptr;
     const size_t stride = prep_plan.packed;
-    JOLT_TRY(bufs.take(stride * kPairingLines, &d_lines));
-    JOLT_TRY(bufs.take(stride, &d_skip));
-    JOLT_TRY(bufs.take(pair_plan.packed, &d_f));
-    JOLT_TRY(bufs.take(g1_plan.packed, &d_t1));
-    JOLT_TRY(bufs.take(g2_plan.packed, &d_t2));
+    JOLT_TRY(c.bufs.take(stride * kPairingLines, &d_lines));
+    JOLT_TRY(c.bufs.take(stride, &d_skip));
+    JOLT_TRY(c.bufs.take(pair_plan.packed, &d_f));
+    JOLT_TRY(c.bufs.take(g1_plan.packed, &d_t1));
+    JOLT_TRY(c.bufs.take(g2_plan.packed, &d_t2));
     const size_t res_gt = 0, res_g1 = res_gt + pair_ids.size() * sizeof(Fq12), res_g2 = res_g1 + g1_ids.size() * sizeof(G1Jac), res_bytes = res_g2 + g2_ids.size() * sizeof(G2Jac);
-    JOLT_TRY(bufs.take(res_bytes, &d_res));
+    JOLT_TRY(c.bufs.take(res_bytes, &d_res));
 
     // ---- the tables, one block ----
     std::vector<PrepDev> prep_items(ranges.size());
@@ -515,19 +491,15 @@ extern "C" int32_t jolt_dory_products(jolt_ctx* ctx, const jolt_dory_item* items
     const size_t o_prep_wg = blob.put(wg_table(prep_plan)), o_pair_wg = blob.put(wg_table(pair_plan)), o_g1_wg = blob.put(wg_table(g1_plan)), o_g2_wg = blob.put(wg_table(g2_plan));
     const size_t o_prep = blob.put(prep_items), o_pair = blob.put(pair_items), o_g1 = blob.put(g1_items), o_g2 = blob.put(g2_items);
     const size_t o_pair_seg = blob.put(pair_segs), o_g1_seg = blob.put(g1_segs), o_g2_seg = blob.put(g2_segs);
-    JOLT_TRY(bufs.take(blob.bytes.size(), &d_blob));
+    JOLT_TRY(c.bufs.take(blob.bytes.size(), &d_blob));
 
     // ---- enqueue: tables on the main stream, fork, the three chains, join, one read-back ----
-    hipStream_t main_st = ctx->stream;
-    hipStream_t chain[3];
-    for (int c = 0; c < 3; ++c) chain[c] = (ctx->serial_streams || !ctx->side[c]) ? main_st : ctx->side[c];
     std::vector<uint8_t> res(res_bytes);
-    hipError_t e = hipMemcpyAsync(d_blob, blob.bytes.data(), blob.bytes.size(), hipMemcpyHostToDevice, main_st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->ev_fork, main_st);
-    for (int c = 0; c < 3 && e == hipSuccess; ++c)
-        if (chain[c] != main_st) e = hipStreamWaitEvent(chain[c], ctx->ev_fork, 0);
+    c.h2d(d_blob, blob.bytes.data(), blob.bytes.size());
+    Fork fork(ctx, 3);
+    hipError_t e = c.ok() ? fork.e : c.e;
     if (e == hipSuccess && !pair_ids.empty()) {
-        hipStream_t st = chain[0];
+        hipStream_t st = fork.st[0];
         const WgDev* wgs = (const WgDev*)(d_blob + o_pair_wg);
         if (!prep_plan.wg_item.empty())
             hipLaunchKernelGGL(k_batch_prepare_g2, dim3((unsigned)prep_plan.wg_item.size()), dim3(kLanes), 0, st, (const WgDev*)(d_blob + o_prep_wg), (const PrepDev*)(d_blob + o_prep), d_lines, d_skip, stride);
@@ -536,33 +508,22 @@ extern "C" int32_t jolt_dory_products(jolt_ctx* ctx, const jolt_dory_item* items
         e = reduce_chain<Fq12, MulFq12>(st, pair_plan, wgs, (const SegDev*)(d_blob + o_pair_seg), d_f, (Fq12*)(d_res + res_gt), Fq12::one());
     }
     if (e == hipSuccess && !g1_ids.empty()) {
-        hipStream_t st = chain[1];
+        hipStream_t st = fork.st[1];
         const WgDev* wgs = (const WgDev*)(d_blob + o_g1_wg);
         if (!g1_plan.wg_item.empty())
             hipLaunchKernelGGL(k_batch_msm_terms<G1Ops>, dim3((unsigned)g1_plan.wg_item.size()), dim3(kLanes), 0, st, wgs, (const MsmDev<G1Jac>*)(d_blob + o_g1), d_t1);
         e = reduce_chain<G1Jac, AddPt<G1Ops>>(st, g1_plan, wgs, (const SegDev*)(d_blob + o_g1_seg), d_t1, (G1Jac*)(d_res + res_g1), G1Ops::identity());
     }
     if (e == hipSuccess && !g2_ids.empty()) {
-        hipStream_t st = chain[2];
+        hipStream_t st = fork.st[2];
         const WgDev* wgs = (const WgDev*)(d_blob + o_g2_wg);
         if (!g2_plan.wg_item.empty())
             hipLaunchKernelGGL(k_batch_msm_terms<G2Ops>, dim3((unsigned)g2_plan.wg_item.size()), dim3(kLanes), 0, st, wgs, (const MsmDev<G2Jac>*)(d_blob + o_g2), d_t2);
         e = reduce_chain<G2Jac, AddPt<G2Ops>>(st, g2_plan, wgs, (const SegDev*)(d_blob + o_g2_seg), d_t2, (G2Jac*)(d_res + res_g2), G2Ops::identity());
     }
-    // the join is enqueued on every path: the main stream must not run ahead of a chain that was started
-    for (int c = 0; c < 3; ++c) {
-        if (chain[c] == main_st) continue;
-        hipError_t ej = hipEventRecord(ctx->ev_join[c], chain[c]);
-        if (ej == hipSuccess) ej = hipStreamWaitEvent(main_st, ctx->ev_join[c], 0);
-        if (ej != hipSuccess) {
-            (void)hipStreamSynchronize(chain[c]);
-            if (e == hipSuccess) e = ej;
-        }
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_res, res_bytes, hipMemcpyDeviceToHost, main_st);
-    const hipError_t e2 = hipStreamSynchronize(main_st);  // the tables of this call are read until here
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return hip_fail(ctx, "dory products", e);
+    c.e = fork.join(e);
+    c.down(res.data(), d_res, res_bytes);
+    JOLT_TRY(c.finish("dory products"));  // the tables of this call are read until here
 
     // ---- one final exponentiation per PAIR item, beside each other on the host ----
     std::vector<Fq12> gt(pair_ids.size());

@@ -15,8 +15,8 @@
 // additions per element (85 on average), no table.  The per-element-scalar routines cannot share a sequence: the fixed-base one takes k * base
 // (k = 0..8, signed 4-bit windows) from one shared table by index, the MSM is one double-and-add per term followed by a tree of additions.
 // Integer VALU work, no MFMA; the chains are ~254 dependent doublings long, so these kernels are latency bound (docs/kernels.md).
+// The kernels and their launch sites (enqueue_*) are dory_kernels.hip.h; every entry here is one HostCall (dory_host.hpp): checks, up() per array, one enqueue_*, down(), finish().
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -32,134 +32,77 @@ using namespace jolt::dory_dev;
 
 namespace {
 
-// Phase clock of jolt_dory_routines_timing: when it is on, the stream is drained between the phases of a call so that each gets its own wall time.
-struct Phases {
-    jolt_ctx* ctx;
-    std::chrono::steady_clock::time_point t0;
-    explicit Phases(jolt_ctx* c) : ctx(c), t0(std::chrono::steady_clock::now()) {
-        if (c->dory_timing)
-            for (double& v : c->dory_ms) v = 0.0;
-    }
-    hipError_t mark(int phase) {  // closes `phase`: 0 checks, 1 host -> device, 2 kernels, 3 device -> host
-        if (!ctx->dory_timing) return hipSuccess;
-        const hipError_t e = phase ? hipStreamSynchronize(ctx->stream) : hipSuccess;
-        const auto t1 = std::chrono::steady_clock::now();
-        ctx->dory_ms[phase] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-        return e;
-    }
-};
+// The phases of jolt_dory_routines_timing, closed by HostCall::mark: checks, host -> device, kernels, device -> host
+enum { kChecks = 0, kUpload = 1, kKernels = 2, kDownload = 3 };
 
 // vs[i] = addend + s * scaled with (scaled, addend) = (other, vs) [bases_then_add] or (vs, other) [vs_then_add]
 template <class O>
 int32_t scale_add(jolt_ctx* ctx, typename O::Abi* vs, const typename O::Abi* other, size_t n, const jolt_fr_t* scalar, bool scale_vs, const char* what) {
     if (!ctx || !scalar || (n && (!vs || !other))) return JOLT_ERR_INVALID_ARG;
     if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
-    Phases ph(ctx);
+    HostCall c(ctx, ctx->dory_ms, ctx->dory_timing);
     NafPlan plan;
     JOLT_REQUIRE(ctx, naf_plan(scalar, &plan), "scalar is not a canonical Fr");
     JOLT_REQUIRE(ctx, all_on_curve<O>(vs, n) && all_on_curve<O>(other, n), "a point is not on its curve or not canonical");
     if (n == 0) return JOLT_OK;
-    (void)ph.mark(0);
-    using Pt = typename O::Pt;
-    hipStream_t st = ctx->stream;
-    DevBufs bufs(ctx);
-    Pt *d_vs = nullptr, *d_other = nullptr;
-    JOLT_TRY(bufs.take(n, &d_vs));
-    JOLT_TRY(bufs.take(n, &d_other));
-    hipError_t e = hipMemcpyAsync(d_vs, vs, n * sizeof(Pt), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_other, other, n * sizeof(Pt), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = ph.mark(1);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_dory_scale_add<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, plan, (const Pt*)(scale_vs ? d_vs : d_other), (const Pt*)(scale_vs ? d_other : d_vs), d_vs, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = ph.mark(2);
-    if (e == hipSuccess) e = hipMemcpyAsync(vs, d_vs, n * sizeof(Pt), hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);  // the caller's arrays are read and written until here
-    if (e == hipSuccess) e = e2;
-    (void)ph.mark(3);
-    if (e != hipSuccess) return hip_fail(ctx, what, e);
-    return JOLT_OK;
+    c.mark(kChecks, false);
+    typename O::Pt *d_vs = nullptr, *d_other = nullptr;
+    c.up(vs, n, &d_vs);
+    c.up(other, n, &d_other);
+    c.mark(kUpload);
+    if (c.ok()) c.e = enqueue_scale_add<O>(c.st, plan, scale_vs ? d_vs : d_other, scale_vs ? d_other : d_vs, d_vs, n);
+    c.mark(kKernels);
+    c.down(vs, d_vs, n);
+    return c.finish(what, kDownload);
 }
 
 template <class O>
 int32_t fixed_base(jolt_ctx* ctx, const typename O::Abi* base, const jolt_fr_t* scalars, size_t n, typename O::Abi* out, const char* what) {
     if (!ctx || !base || (n && (!scalars || !out))) return JOLT_ERR_INVALID_ARG;
     if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
-    Phases ph(ctx);
+    HostCall c(ctx, ctx->dory_ms, ctx->dory_timing);
     using Pt = typename O::Pt;
     JOLT_REQUIRE(ctx, all_on_curve<O>(base, 1), "a point is not on its curve or not canonical");
     JOLT_REQUIRE(ctx, all_canonical(scalars, n), "scalar is not a canonical Fr");
     if (n == 0) return JOLT_OK;  // an empty input gives an empty output (routines.rs:67-69)
-    Pt b, table[kFixedTable];
-    std::memcpy(&b, base, sizeof(b));
-    fixed_table<O>(b, table);
-    (void)ph.mark(0);
-    hipStream_t st = ctx->stream;
-    DevBufs bufs(ctx);
+    Pt table[kFixedTable];       // read by its upload until finish()
+    fixed_table_from_abi<O>(base, table);
+    c.mark(kChecks, false);
     Pt *d_table = nullptr, *d_out = nullptr;
     Fr* d_scalars = nullptr;
-    JOLT_TRY(bufs.take(kFixedTable, &d_table));
-    JOLT_TRY(bufs.take(n, &d_out));
-    JOLT_TRY(bufs.take(n, &d_scalars));
-    hipError_t e = hipMemcpyAsync(d_table, table, sizeof(table), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_scalars, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = ph.mark(1);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_dory_fixed_base<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, (const Pt*)d_table, (const Fr*)d_scalars, d_out, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = ph.mark(2);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * sizeof(Pt), hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);  // `table` (on this stack) and the caller's arrays are read until here
-    if (e == hipSuccess) e = e2;
-    (void)ph.mark(3);
-    if (e != hipSuccess) return hip_fail(ctx, what, e);
-    return JOLT_OK;
+    c.up(table, kFixedTable, &d_table);
+    c.up(scalars, n, &d_scalars);
+    c.take(n, &d_out);
+    c.mark(kUpload);
+    if (c.ok()) c.e = enqueue_fixed_base<O>(c.st, d_table, d_scalars, d_out, n);
+    c.mark(kKernels);
+    c.down(out, d_out, n);
+    return c.finish(what, kDownload);
 }
 
 template <class O>
 int32_t msm(jolt_ctx* ctx, const typename O::Abi* bases, const jolt_fr_t* scalars, size_t n, typename O::Abi* out, const char* what) {
     if (!ctx || !out || (n && (!bases || !scalars))) return JOLT_ERR_INVALID_ARG;
     if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
-    Phases ph(ctx);
+    HostCall c(ctx, ctx->dory_ms, ctx->dory_timing);
     using Pt = typename O::Pt;
     JOLT_REQUIRE(ctx, all_canonical(scalars, n), "scalar is not a canonical Fr");
     JOLT_REQUIRE(ctx, all_on_curve<O>(bases, n), "a point is not on its curve or not canonical");
-    if (n == 0) {  // the empty sum
-        const Pt id = O::identity();
-        std::memcpy(out, &id, sizeof(id));
-        return JOLT_OK;
+    Pt sum = O::identity();  // the empty sum
+    if (n) {
+        c.mark(kChecks, false);
+        Pt *d_bases = nullptr, *d_terms = nullptr;
+        Fr* d_scalars = nullptr;
+        c.up(bases, n, &d_bases);
+        c.up(scalars, n, &d_scalars);
+        c.take(n, &d_terms);
+        c.mark(kUpload);
+        if (c.ok()) c.e = enqueue_msm<O>(c.st, d_bases, d_scalars, d_terms, n);
+        c.mark(kKernels);
+        c.down(&sum, d_terms, 1);
+        JOLT_TRY(c.finish(what, kDownload));
+        sum = normalised<O>(sum);
     }
-    (void)ph.mark(0);
-    hipStream_t st = ctx->stream;
-    DevBufs bufs(ctx);
-    Pt *d_bases = nullptr, *d_terms = nullptr;
-    Fr* d_scalars = nullptr;
-    JOLT_TRY(bufs.take(n, &d_bases));
-    JOLT_TRY(bufs.take(n, &d_terms));
-    JOLT_TRY(bufs.take(n, &d_scalars));
-    hipError_t e = hipMemcpyAsync(d_bases, bases, n * sizeof(Pt), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_scalars, scalars, n * sizeof(Fr), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = ph.mark(1);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_dory_msm_terms<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, (const Pt*)d_bases, (const Fr*)d_scalars, d_terms, n);
-        for (size_t m = n; m > 1;) {
-            const size_t half = (m + 1) / 2;
-            hipLaunchKernelGGL(k_dory_tree_level<O>, dim3(lanes_grid(half)), dim3(kLanes), 0, st, d_terms, half, m);
-            m = half;
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = ph.mark(2);
-    Pt sum = O::identity();
-    if (e == hipSuccess) e = hipMemcpyAsync(&sum, d_terms, sizeof(Pt), hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    (void)ph.mark(3);
-    if (e != hipSuccess) return hip_fail(ctx, what, e);
-    sum = normalised<O>(sum);
     std::memcpy(out, &sum, sizeof(sum));
     return JOLT_OK;
 }
@@ -228,30 +171,19 @@ extern "C" int32_t jolt_dory_g2_scale_vs_add(jolt_ctx* ctx, jolt_g2_t* vs, const
 extern "C" int32_t jolt_dory_fold_field_vectors(jolt_ctx* ctx, jolt_fr_t* left, const jolt_fr_t* right, size_t n, const jolt_fr_t* scalar) {
     if (!ctx || !scalar || (n && (!left || !right))) return JOLT_ERR_INVALID_ARG;
     if (n > kMaxElements) return JOLT_ERR_UNSUPPORTED;
-    Phases ph(ctx);
+    HostCall c(ctx, ctx->dory_ms, ctx->dory_timing);
     const Fr s = fr_from_abi(scalar);
     JOLT_REQUIRE(ctx, fr_is_canonical(s) && all_canonical(left, n) && all_canonical(right, n), "scalar is not a canonical Fr");
     if (n == 0) return JOLT_OK;
-    (void)ph.mark(0);
-    hipStream_t st = ctx->stream;
-    DevBufs bufs(ctx);
+    c.mark(kChecks, false);
     Fr *d_left = nullptr, *d_right = nullptr;
-    JOLT_TRY(bufs.take(n, &d_left));
-    JOLT_TRY(bufs.take(n, &d_right));
-    hipError_t e = hipMemcpyAsync(d_left, left, n * sizeof(Fr), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_right, right, n * sizeof(Fr), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = ph.mark(1);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_dory_fold_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_left, (const Fr*)d_right, s, n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = ph.mark(2);
-    if (e == hipSuccess) e = hipMemcpyAsync(left, d_left, n * sizeof(Fr), hipMemcpyDeviceToHost, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    (void)ph.mark(3);
-    if (e != hipSuccess) return hip_fail(ctx, "dory field fold", e);
-    return JOLT_OK;
+    c.up(left, n, &d_left);
+    c.up(right, n, &d_right);
+    c.mark(kUpload);
+    if (c.ok()) c.e = enqueue_fold_field(c.st, d_left, d_right, s, n);
+    c.mark(kKernels);
+    c.down(left, d_left, n);
+    return c.finish("dory field fold", kDownload);
 }
 
 extern "C" int32_t jolt_dory_routines_timing(jolt_ctx* ctx, int32_t enable, double* out_ms) {

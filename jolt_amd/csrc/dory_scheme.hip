@@ -6,8 +6,8 @@
 //   beta    v1 += beta Gamma1 | v2 += (1/beta) Gamma2                       k_dory_scale_add<G1Ops> on the main stream, k_dory_scale_add<G2Ops> on side[0]
 //   alpha   v1 <- alpha v1_L + v1_R, s1 <- alpha s1_L + s1_R | the same under 1/alpha for v2, s2     each group's k_dory_scale_add and then its k_dory_fold_field
 // TWO launches, one per group, not one kernel holding both paths: a shared kernel would give the G1 blocks G2's register budget (docs/kernels.md 3.5m).  The chains are
-// forked by ctx->ev_fork and joined by ctx->ev_join[0], as jolt_dory_products forks its chains; no further stream, no captured graph, no host synchronisation.  The
-// per-lane functions are naf_mul / scale_add_one and the field fold of dory_kernels.hip.h, so the vectors hold what the separate calls write.
+// forked by ctx->ev_fork and joined by ctx->ev_join[0] (Fork of dory_host.hpp, as jolt_dory_products forks its chains); no further stream, no captured graph, no host
+// synchronisation.  The launches are enqueue_scale_add / enqueue_fold_field of dory_kernels.hip.h, the launch sites of the separate calls, so the vectors hold what those write.
 // The opening (open_impl) is host control flow over those entries: the protocol of jolt_amd/dory_open.py and dory_reduce.py, with the challenges drawn through a
 // callback after each message.  Every exit drains the streams before the state vectors go back to the pool (OpenState's destructor).
 // The batch opening of stage 8 (jolt_host_dory_prove_batch) is HomomorphicBatch::prove_batch around it: the statement's framing (host_mirror.hip), the eq tables of the
@@ -97,18 +97,6 @@ extern "C" int32_t jolt_dory_setup_tier2(jolt_ctx* ctx, const jolt_dory_setup* s
 }
 
 // ------------------------------------------------------------------------------------------------------------------ a round's update
-namespace {
-
-template <class O>
-void launch_scale_add(hipStream_t st, const NafPlan& plan, const typename O::Pt* scaled, const typename O::Pt* addend, typename O::Pt* out, size_t n) {
-    hipLaunchKernelGGL(k_dory_scale_add<O>, dim3(lanes_grid(n)), dim3(kLanes), 0, st, plan, scaled, addend, out, n);
-}
-void launch_fold(hipStream_t st, Fr* left, const Fr* right, const Fr& s, size_t n) {
-    hipLaunchKernelGGL(k_dory_fold_field, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, left, right, s, n);
-}
-
-}  // namespace
-
 extern "C" int32_t jolt_dory_round_update(jolt_ctx* ctx, int32_t mode, jolt_dory_vec* v1, size_t v1_first, jolt_dory_vec* v2, size_t v2_first, jolt_dory_vec* a, size_t a_first,
                                           jolt_dory_vec* b, size_t b_first, size_t n, const jolt_fr_t* scalar, const jolt_fr_t* scalar_inv) {
     if (!ctx || !v1 || !v2 || !a || !b || !scalar || !scalar_inv) return JOLT_ERR_INVALID_ARG;
@@ -129,38 +117,21 @@ extern "C" int32_t jolt_dory_round_update(jolt_ctx* ctx, int32_t mode, jolt_dory
     JOLT_REQUIRE(ctx, mul(s, s_inv) == Fr::one(), "the scalar times its inverse is not one");
     const size_t h = n / 2, m = alpha ? h : n;
     if (m != 0) {
-        hipStream_t main_st = ctx->stream;
-        hipStream_t g2_st = (ctx->serial_streams || !ctx->side[0]) ? main_st : ctx->side[0];
-        hipError_t e = hipSuccess;
-        const bool forked = g2_st != main_st;
-        if (forked) {
-            e = hipEventRecord(ctx->ev_fork, main_st);
-            if (e == hipSuccess) e = hipStreamWaitEvent(g2_st, ctx->ev_fork, 0);
-            if (e != hipSuccess) return hip_fail(ctx, "dory round update", e);  // nothing is enqueued yet
-        }
+        Fork fork(ctx, 1);  // the G2 work beside the G1 work
+        hipStream_t main_st = ctx->stream, g2_st = fork.st[0];
+        hipError_t e = fork.e;
         G1Jac* p1 = at<G1Jac>(v1, v1_first);
         G2Jac* p2 = at<G2Jac>(v2, v2_first);
         if (alpha) {
-            launch_scale_add<G1Ops>(main_st, plan, p1, p1 + h, p1, h);
-            launch_fold(main_st, at<Fr>(a, a_first), at<Fr>(a, a_first) + h, s, h);
-            e = hipGetLastError();
-            launch_scale_add<G2Ops>(g2_st, plan_inv, p2, p2 + h, p2, h);
-            launch_fold(g2_st, at<Fr>(b, b_first), at<Fr>(b, b_first) + h, s_inv, h);
+            if (e == hipSuccess) e = enqueue_scale_add<G1Ops>(main_st, plan, p1, p1 + h, p1, h);
+            if (e == hipSuccess) e = enqueue_fold_field(main_st, at<Fr>(a, a_first), at<Fr>(a, a_first) + h, s, h);
+            if (e == hipSuccess) e = enqueue_scale_add<G2Ops>(g2_st, plan_inv, p2, p2 + h, p2, h);
+            if (e == hipSuccess) e = enqueue_fold_field(g2_st, at<Fr>(b, b_first), at<Fr>(b, b_first) + h, s_inv, h);
         } else {
-            launch_scale_add<G1Ops>(main_st, plan, at<G1Jac>(a, a_first), p1, p1, n);
-            e = hipGetLastError();
-            launch_scale_add<G2Ops>(g2_st, plan_inv, at<G2Jac>(b, b_first), p2, p2, n);
+            if (e == hipSuccess) e = enqueue_scale_add<G1Ops>(main_st, plan, at<G1Jac>(a, a_first), p1, p1, n);
+            if (e == hipSuccess) e = enqueue_scale_add<G2Ops>(g2_st, plan_inv, at<G2Jac>(b, b_first), p2, p2, n);
         }
-        const hipError_t e2 = hipGetLastError();
-        if (e == hipSuccess) e = e2;
-        if (forked) {  // the join is enqueued on every path: the main stream must not run ahead of a chain that was started
-            hipError_t ej = hipEventRecord(ctx->ev_join[0], g2_st);
-            if (ej == hipSuccess) ej = hipStreamWaitEvent(main_st, ctx->ev_join[0], 0);
-            if (ej != hipSuccess) {
-                (void)hipStreamSynchronize(g2_st);
-                if (e == hipSuccess) e = ej;
-            }
-        }
+        e = fork.join(e);
         if (e != hipSuccess) return hip_fail(ctx, "dory round update", e);
     }
     if (alpha) {

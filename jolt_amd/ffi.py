@@ -1589,9 +1589,7 @@ def _dory_state_combine_hints(self, hints, scalars, out, out_first=0):
     (jolt_dory_state_combine_hints); the number of rows written, max_i rows_i"""
     views = [_dory_view(h) for h in hints]
     n = len(views)
-    hs = (C.c_void_p * max(n, 1))(*[v.h for v, _, _ in views])
-    firsts = (C.c_size_t * max(n, 1))(*[f for _, f, _ in views])
-    rows = (C.c_size_t * max(n, 1))(*[r for _, _, r in views])
+    hs, firsts, rows = _dory_view_arrays(views)
     sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if n else fr_array(1)
     if sc.shape[0] != max(n, 1):
         raise ValueError("one scalar per hint")
