@@ -869,7 +869,24 @@ int32_t jolt_host_dory_rows_fr_plan(uint32_t bit_length, size_t row_width, int32
  * JOLT_ERR_SIZE_MISMATCH; n_tables = 0 JOLT_ERR_INVALID_ARG, more than 8 JOLT_ERR_UNSUPPORTED.  Temporary device memory O(2^sigma * rows / 64). */
 int32_t jolt_dory_fold_rows_blocks(jolt_ctx *ctx, jolt_table *const *tables, const uint32_t *sigma_tables, size_t n_tables, const jolt_fr_t *scalars,
                                    uint32_t sigma, const jolt_table *left, const jolt_table *base /* may be NULL */, jolt_table **out /* 2^sigma */);
-/* *index = ((i >> sigma_table) << sigma_grid) | (i & (2^sigma_table - 1)); sigma_table > sigma_grid or an index past 64 bits is JOLT_ERR_INVALID_ARG */
+/* The same fold of up to 256 tables -- a committed program is up to 256 bytecode chunks and the image: a chain of launch sets of eight, each taking the running
+ * output as its base.  Field addition is exact, so the output is the one jolt_dory_fold_rows_blocks gives for n_tables <= 8 (that entry is a call of this one) and
+ * does not depend on the grouping.  Codes as there; more than 256 tables JOLT_ERR_UNSUPPORTED. */
+int32_t jolt_dory_fold_rows_blocks_many(jolt_ctx *ctx, jolt_table *const *tables, const uint32_t *sigma_tables, size_t n_tables, const jolt_fr_t *scalars,
+                                        uint32_t sigma, const jolt_table *left, const jolt_table *base /* may be NULL */, jolt_table **out /* 2^sigma */);
+/* The claims of block-embedded tables from one pass -- what a stage-8 statement holds for advice, bytecode chunks and the program image (opening_claim * entry.scale,
+ * crates/jolt-prover/src/dory/stages/stage8.rs:148-162; BlockOpeningPoly, crates/jolt-kernels/src/optimized/opening.rs:594-611):
+ *   claims_out[d] = sum_i tables[d][i] * eq(point, jolt_host_dory_block_index(sigma_tables[d], sigma, i))
+ *                 = sum_r L[r] * sum_c R[c] * tables[d][(r << sigma_d) + c],   L = eq(point[:nu]), R = eq(point[nu:]).
+ * point is the grid-order opening point, nu + sigma coordinates, most significant first, as jolt_eq_evals indexes; the Lagrange factors of the high row and column
+ * coordinates sit inside L[r] and R[c], so the claim is the scaled one.  One launch over all tables (descriptors in device memory) and a small one that adds the
+ * workgroups' partial sums (no atomics: the claims do not depend on the grid); the claims are downloaded before the call returns.  Everything is checked before
+ * anything is enqueued, codes of jolt_dory_fold_rows_blocks: JOLT_ERR_INVALID_ARG for a null pointer, a table of another context, a length that is not a power of
+ * two, sigma_d > m_d or > sigma, a coordinate that is not canonical, n_point != nu + sigma, n_tables = 0; JOLT_ERR_SIZE_MISMATCH for a table of more than 2^nu rows;
+ * JOLT_ERR_UNSUPPORTED for more than 256 tables. */
+int32_t jolt_dory_evaluate_blocks(jolt_ctx *ctx, jolt_table *const *tables, const uint32_t *sigma_tables, size_t n_tables, const jolt_fr_t *point, size_t n_point,
+                                  uint32_t nu, uint32_t sigma, jolt_fr_t *claims_out /* one per table */);
+/* *index =((i >> sigma_table) << sigma_grid) | (i & (2^sigma_table - 1)); sigma_table > sigma_grid or an index past 64 bits is JOLT_ERR_INVALID_ARG */
 int32_t jolt_host_dory_block_index(uint32_t sigma_table, uint32_t sigma_grid, size_t i, size_t *index);
 
 /* Dory evaluation proofs as one call (dory_scheme.hip): the setup object, a round's in-place update as one call, the prover's side of Eval-VMV-RE under Fiat-Shamir,
@@ -951,6 +968,29 @@ int32_t jolt_host_dory_prove_batch(jolt_ctx *ctx, const jolt_dory_setup *setup, 
                                    size_t n_dense, uint32_t log_k, const size_t *column_of_claim, const jolt_fr_t *point, size_t n_point, jolt_host_transcript *t,
                                    jolt_gt_t *gts, jolt_g1_t *g1s, jolt_g2_t *g2s, jolt_fr_t *challenges_out, jolt_fr_t *scalars_out /* n_claims */,
                                    jolt_fr_t *joint_eval_out);
+/* The same over everything prove_stage8 hands to prove_batch (crates/jolt-prover/src/dory/stages/stage8.rs:164-258): the trace columns AND the block-embedded
+ * polynomials (trusted and untrusted advice, bytecode chunks, the program image: BlockOpeningPoly, crates/jolt-kernels/src/optimized/opening.rs:594-611), in either
+ * trace placement.  Arguments of jolt_host_dory_prove_batch plus
+ *   blocks, sigma_blocks, n_blocks   tables of 2^m_d field elements, each 2^(m_d - sigma_d) rows of 2^sigma_d columns top-left in the grid, as
+ *                                    jolt_dory_fold_rows_blocks takes them; at most 256;
+ *   order                            JOLT_DORY_ORDER_CYCLE_MAJOR or JOLT_DORY_ORDER_ADDRESS_MAJOR (the trace as jolt_dory_fold_rows_grid_am places it, log_block =
+ *                                    log_k + log_extra, log_stride = log_extra; a block's embedding is the same in both);
+ *   log_extra                        the embedding extra of a widened address-major grid; 0 in the cycle-major placement.
+ * n_claims = one-hot columns + n_dense + n_blocks; the columns are the one-hot columns source by source, then the dense columns, then the blocks, and
+ * column_of_claim permutes over all of them.  A block's hint is a resident G1 view of its 2^(m_d - sigma_d) row commitments (hints shorter than 2^nu are padded as
+ * combine_hints pads them).  point is the GRID-ORDER point as final_opening_point produces it: log_k + log2(T) coordinates cycle-major, log2(T) + log_k + log_extra
+ * address-major.  The seven steps above with: step 4 the trace's fold in the chosen placement, then jolt_dory_fold_rows_blocks_many with that as base, gamma's powers
+ * taken in claim order and mapped through column_of_claim; step 5 over all claims; step 6 weighting every hint, the blocks' included.  The contract above word for
+ * word; beyond its codes JOLT_ERR_INVALID_ARG for an unknown order, log_extra != 0 cycle-major, a block of another context, a length that is not a power of two,
+ * sigma_d > m_d or > sigma, a block's hint of another row count than the block; JOLT_ERR_SIZE_MISMATCH for a block of more than 2^nu rows; JOLT_ERR_UNSUPPORTED for
+ * more than 256 blocks and for an address-major grid with sigma < log_k + log_extra.  jolt_host_dory_prove_batch is this entry with n_blocks = 0, cycle-major. */
+enum { JOLT_DORY_ORDER_CYCLE_MAJOR = 0, JOLT_DORY_ORDER_ADDRESS_MAJOR = 1 };
+int32_t jolt_host_dory_prove_batch_blocks(jolt_ctx *ctx, const jolt_dory_setup *setup, const jolt_dory_vec *const *hints, const size_t *hint_first, const size_t *hint_rows,
+                                          size_t n_claims, const jolt_fr_t *evaluations, const jolt_onehot *const *sources, size_t n_sources, jolt_table *const *dense,
+                                          size_t n_dense, jolt_table *const *blocks, const uint32_t *sigma_blocks, size_t n_blocks, uint32_t log_k, int32_t order,
+                                          uint32_t log_extra, const size_t *column_of_claim, const jolt_fr_t *point, size_t n_point, jolt_host_transcript *t,
+                                          jolt_gt_t *gts, jolt_g1_t *g1s, jolt_g2_t *g2s, jolt_fr_t *challenges_out, jolt_fr_t *scalars_out /* n_claims */,
+                                          jolt_fr_t *joint_eval_out);
 /* sigma > 30 is JOLT_ERR_INVALID_ARG; any of the four pointers may be NULL */
 int32_t jolt_host_dory_proof_counts(uint32_t sigma, size_t *n_gt, size_t *n_g1, size_t *n_g2, size_t *n_challenges);
 /* ark-serialize's compressed forms on the host.  G2: x.c0 then x.c1, 32 little-endian bytes of the canonical value each; the top two bits of the last byte hold the

@@ -1387,53 +1387,186 @@ __global__ __launch_bounds__(kBlock) void k_dory_fold_blocks_sum(const Fr* __res
     st_fr(out + c, acc);
 }
 
+// ---- the claims of block-embedded tables: claims[d] = sum_r L[r] * sum_c R[c] * table_d[(r << sigma_d) + c] ----
+// The statement's (already scaled) claim of a BlockOpeningPoly at the grid-order opening point, L = eq(point[:nu]), R = eq(point[nu:]).  ONE launch over all tables:
+// blockIdx.y names the table, its descriptor is read from device memory (256 of them do not fit kernel arguments).  A table is cut into UNITS of consecutive entries
+// that one wavefront serves, lane <-> entry, so a wavefront reads 64 consecutive field elements: at 2^sigma_d >= 64 columns a unit is min(2^sigma_d, 64 *
+// kEvalBlockRun) entries of ONE row -- a lane's products R[c] * entry go through the deferred-reduction accumulator (at most kEvalBlockRun <= kWideMaxProducts of
+// them) and are multiplied by L[r] once; below 64 columns a unit is 64 entries of 64 / 2^sigma_d rows, one product per lane and its own L[r].  Waves stride over the
+// units, so the launch may be capped.  No atomics: a workgroup's sum goes to partials[table * gridDim.x + block] and k_dory_eval_blocks_sum adds them, so the claims
+// are the same field elements for every grid.
+constexpr size_t kBlocksMax = 256;       // tables per call of jolt_dory_evaluate_blocks and jolt_dory_fold_rows_blocks_many
+constexpr uint32_t kEvalBlockLogRun = 3;
+constexpr uint32_t kEvalBlockRun = 1u << kEvalBlockLogRun;  // products per lane and unit
+static_assert(kEvalBlockRun <= (uint32_t)kWideMaxProducts, "a unit's products fit one deferred reduction");
+struct BlockDesc {
+    const Fr* table;
+    uint32_t sigma_d, log_len;
+};
+__host__ __device__ inline uint32_t eval_block_log_unit(uint32_t sigma_d) { return sigma_d < 6 ? 6 : (sigma_d < 6 + kEvalBlockLogRun ? sigma_d : 6 + kEvalBlockLogRun); }
+
+__global__ __launch_bounds__(kBlock) void k_dory_eval_blocks(const BlockDesc* __restrict__ descs, const Fr* __restrict__ left, const Fr* __restrict__ right,
+                                                             Fr* __restrict__ partials) {
+    const BlockDesc d = descs[blockIdx.y];  // uniform over the workgroup
+    const size_t len = (size_t)1 << d.log_len, mask = ((size_t)1 << d.sigma_d) - 1;
+    const uint32_t log_unit = eval_block_log_unit(d.sigma_d);
+    const size_t units = (len + (((size_t)1 << log_unit) - 1)) >> log_unit;
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t waves = (size_t)gridDim.x * (kBlock / 64);
+    Fr acc[1] = {Fr::zero()};
+    for (size_t u = (size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); u < units; u += waves) {
+        const size_t i0 = (u << log_unit) + lane;
+        const size_t end = ((u + 1) << log_unit) < len ? ((u + 1) << log_unit) : len;
+        if (i0 >= end) continue;  // a table of fewer than 64 entries
+        WideAcc<FrParams> w = wide_zero<FrParams>();
+        for (size_t i = i0; i < end; i += 64) wide_fmadd(w, ld_fr(right + (i & mask)), ld_fr(d.table + i));  // one row: 2^log_unit <= 2^sigma_d wherever a lane has two entries
+        acc[0] = add(acc[0], mul(wide_reduce(w), ld_fr(left + (i0 >> d.sigma_d))));
+    }
+    block_reduce_store_at<1>(acc, partials + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+}
+// one workgroup per table: out[d] = the sum of its n_blocks partial sums
+__global__ __launch_bounds__(kBlock) void k_dory_eval_blocks_sum(const Fr* __restrict__ partials, uint32_t n_blocks, Fr* __restrict__ out) {
+    Fr acc[1] = {Fr::zero()};
+    for (uint32_t b = threadIdx.x; b < n_blocks; b += kBlock) acc[0] = add(acc[0], ld_fr(partials + (size_t)blockIdx.x * n_blocks + b));
+    block_reduce_store_at<1>(acc, out + blockIdx.x);
+}
+
+size_t eval_blocks_cap() {  // workgroups per table at most: unset, the launch stays near 2048 workgroups; the suite sets it to make waves stride at small sizes
+    if (const char* e = std::getenv("JOLT_DORY_EVAL_BLOCKS_CAP"))
+        if (std::atoll(e) > 0) return (size_t)std::atoll(e);
+    return 0;
+}
+
 }  // namespace
 
-extern "C" int32_t jolt_dory_fold_rows_blocks(jolt_ctx* ctx, jolt_table* const* tables, const uint32_t* sigma_tables, size_t n_tables, const jolt_fr_t* scalars,
-                                              uint32_t sigma, const jolt_table* left, const jolt_table* base, jolt_table** out) {
+// One launch set of at most kFoldMaxDense tables: out[c] = (base ? base[c] : 0) + the tables' fold.  Everything was checked by the caller; enqueue only.
+static int32_t fold_blocks_enqueue(jolt_ctx* ctx, const BlockFoldArgs& a, size_t max_rows, uint32_t sigma, const Fr* left, const Fr* base, Fr* out) {
+    const size_t cols = (size_t)1 << sigma;
+    const size_t slices = (max_rows + kBlockFoldSlice - 1) / kBlockFoldSlice, groups = (cols + kBlock - 1) / kBlock;
+    Fr* partial = nullptr;
+    const bool direct = slices == 1 && !base;
+    if (!direct) JOLT_TRY(jolt_internal_dev_alloc(ctx, slices * cols * sizeof(Fr), (void**)&partial));
+    hipLaunchKernelGGL(k_dory_fold_blocks, dim3((unsigned)(slices * groups)), dim3(kBlock), 0, ctx->stream, a, left, sigma, (uint32_t)groups, direct ? out : partial);
+    if (!direct) hipLaunchKernelGGL(k_dory_fold_blocks_sum, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, (const Fr*)partial, base, cols, (uint32_t)slices, out);
+    const hipError_t e = hipGetLastError();
+    if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered
+    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
+    return JOLT_OK;
+}
+
+// The wide form: up to kBlocksMax tables as a CHAIN of launch sets of kFoldMaxDense, each taking the running output as its base (field addition is exact, so the
+// grouping does not show in the output; at most eight tables are one set, the launches jolt_dory_fold_rows_blocks always made).  Two result tables alternate, so that
+// no launch reads the table it writes.
+extern "C" int32_t jolt_dory_fold_rows_blocks_many(jolt_ctx* ctx, jolt_table* const* tables, const uint32_t* sigma_tables, size_t n_tables, const jolt_fr_t* scalars,
+                                                   uint32_t sigma, const jolt_table* left, const jolt_table* base, jolt_table** out) {
     if (!ctx || !out || !left || !tables || !sigma_tables || !scalars || n_tables == 0) return JOLT_ERR_INVALID_ARG;
-    if (n_tables > (size_t)kFoldMaxDense) return JOLT_ERR_UNSUPPORTED;
+    if (n_tables > kBlocksMax) return JOLT_ERR_UNSUPPORTED;
     JOLT_REQUIRE(ctx, sigma < 48 && left->data(), "fold_rows: sigma out of range");
-    BlockFoldArgs a;
-    std::memset(&a, 0, sizeof(a));
+    const size_t n_sets = (n_tables + kFoldMaxDense - 1) / kFoldMaxDense;
+    std::vector<BlockFoldArgs> sets(n_sets);
+    std::vector<size_t> set_rows(n_sets, 0);
+    std::memset(sets.data(), 0, n_sets * sizeof(BlockFoldArgs));
     size_t max_rows = 0;
     for (size_t d = 0; d < n_tables; ++d) {
         if (!tables[d] || !tables[d]->data()) return JOLT_ERR_INVALID_ARG;
         const int m = log2_exact(tables[d]->len);
         JOLT_REQUIRE(ctx, m >= 0, "fold_rows: a block's length must be a power of two");
         JOLT_REQUIRE(ctx, sigma_tables[d] <= (uint32_t)m && sigma_tables[d] <= sigma, "fold_rows: a block's columns exceed its variables or the grid's");
-        a.table[d] = tables[d]->data();
-        a.sigma_d[d] = sigma_tables[d];
-        a.log_rows[d] = (uint32_t)m - sigma_tables[d];
-        a.scalar[d] = fr_from_abi(&scalars[d]);
-        JOLT_REQUIRE(ctx, fr_is_canonical(a.scalar[d]), "scalar is not a canonical Fr");
-        max_rows = std::max(max_rows, (size_t)1 << a.log_rows[d]);
+        BlockFoldArgs& a = sets[d / kFoldMaxDense];
+        const size_t k = d % kFoldMaxDense;
+        a.table[k] = tables[d]->data();
+        a.sigma_d[k] = sigma_tables[d];
+        a.log_rows[k] = (uint32_t)m - sigma_tables[d];
+        a.scalar[k] = fr_from_abi(&scalars[d]);
+        JOLT_REQUIRE(ctx, fr_is_canonical(a.scalar[k]), "scalar is not a canonical Fr");
+        a.n = (int)k + 1;
+        set_rows[d / kFoldMaxDense] = std::max(set_rows[d / kFoldMaxDense], (size_t)1 << a.log_rows[k]);
+        max_rows = std::max(max_rows, (size_t)1 << a.log_rows[k]);
     }
-    a.n = (int)n_tables;
     if (max_rows > left->len) return JOLT_ERR_SIZE_MISMATCH;
     const size_t cols = (size_t)1 << sigma;
     if (base && (!base->data() || base->len != cols)) return JOLT_ERR_SIZE_MISMATCH;
-    const size_t slices = (max_rows + kBlockFoldSlice - 1) / kBlockFoldSlice, groups = (cols + kBlock - 1) / kBlock;
-    if (slices * groups > 0x7FFFFFFFull) return JOLT_ERR_UNSUPPORTED;
-    jolt_table* r = nullptr;
-    JOLT_TRY(jolt_internal_table_new(ctx, cols, &r));
-    Fr* partial = nullptr;
-    const bool direct = slices == 1 && !base;
-    int32_t st = direct ? JOLT_OK : jolt_internal_dev_alloc(ctx, slices * cols * sizeof(Fr), (void**)&partial);
-    hipError_t e = hipSuccess;
-    if (st == JOLT_OK) {
-        hipLaunchKernelGGL(k_dory_fold_blocks, dim3((unsigned)(slices * groups)), dim3(kBlock), 0, ctx->stream, a, (const Fr*)left->data(), sigma, (uint32_t)groups,
-                           direct ? r->data() : partial);
-        if (!direct)
-            hipLaunchKernelGGL(k_dory_fold_blocks_sum, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, (const Fr*)partial, base ? (const Fr*)base->data() : (const Fr*)nullptr,
-                               cols, (uint32_t)slices, r->data());
-        e = hipGetLastError();
+    if ((max_rows + kBlockFoldSlice - 1) / kBlockFoldSlice * ((cols + kBlock - 1) / kBlock) > 0x7FFFFFFFull) return JOLT_ERR_UNSUPPORTED;
+    jolt_table* r[2] = {nullptr, nullptr};
+    JOLT_TRY(jolt_internal_table_new(ctx, cols, &r[0]));
+    int32_t st = n_sets > 1 ? jolt_internal_table_new(ctx, cols, &r[1]) : JOLT_OK;
+    const Fr* running = base ? (const Fr*)base->data() : (const Fr*)nullptr;
+    size_t at = (n_sets - 1) & 1;  // the last set writes r[0]
+    for (size_t g = 0; g < n_sets && st == JOLT_OK; ++g, at ^= 1) {
+        st = fold_blocks_enqueue(ctx, sets[g], set_rows[g], sigma, (const Fr*)left->data(), running, r[at]->data());
+        running = r[at]->data();
     }
-    if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered
-    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
-    if (e != hipSuccess) { jolt_table_free(ctx, r); ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
-    *out = r;
+    if (r[1]) jolt_table_free(ctx, r[1]);  // back to the pool: reuse is stream-ordered
+    if (st != JOLT_OK) { jolt_table_free(ctx, r[0]); return st; }
+    *out = r[0];
     return JOLT_OK;
+}
+
+extern "C" int32_t jolt_dory_fold_rows_blocks(jolt_ctx* ctx, jolt_table* const* tables, const uint32_t* sigma_tables, size_t n_tables, const jolt_fr_t* scalars,
+                                              uint32_t sigma, const jolt_table* left, const jolt_table* base, jolt_table** out) {
+    if (!ctx || !out || !left || !tables || !sigma_tables || !scalars || n_tables == 0) return JOLT_ERR_INVALID_ARG;
+    if (n_tables > (size_t)kFoldMaxDense) return JOLT_ERR_UNSUPPORTED;  // this entry keeps its limit; the wide form is the entry above
+    return jolt_dory_fold_rows_blocks_many(ctx, tables, sigma_tables, n_tables, scalars, sigma, left, base, out);
+}
+
+// The claims a stage-8 statement holds for its block-embedded polynomials (crates/jolt-prover/src/dory/stages/stage8.rs:148-162, opening_claim * entry.scale: the
+// Lagrange factors of the grid's high row and column coordinates sit inside L[r] and R[c] for the small r and c a block reaches).  Two launches (k_dory_eval_blocks,
+// k_dory_eval_blocks_sum), one upload of the descriptors and one download, which synchronises the stream.
+extern "C" int32_t jolt_dory_evaluate_blocks(jolt_ctx* ctx, jolt_table* const* tables, const uint32_t* sigma_tables, size_t n_tables, const jolt_fr_t* point, size_t n_point,
+                                             uint32_t nu, uint32_t sigma, jolt_fr_t* claims_out) {
+    if (!ctx || !tables || !sigma_tables || !point || !claims_out || n_tables == 0) return JOLT_ERR_INVALID_ARG;
+    if (n_tables > kBlocksMax) return JOLT_ERR_UNSUPPORTED;
+    // ---- every check before anything is enqueued ----
+    JOLT_REQUIRE(ctx, sigma < 48 && nu < 48, "evaluate_blocks: sigma or nu out of range");
+    JOLT_REQUIRE(ctx, n_point == (size_t)nu + sigma, "evaluate_blocks: the point has nu + sigma coordinates");
+    std::vector<BlockDesc> descs(n_tables);
+    size_t max_rows = 0, max_units = 1;
+    for (size_t d = 0; d < n_tables; ++d) {
+        if (!tables[d] || tables[d]->ctx != ctx || !tables[d]->data()) return JOLT_ERR_INVALID_ARG;
+        const int m = log2_exact(tables[d]->len);
+        JOLT_REQUIRE(ctx, m >= 0, "evaluate_blocks: a block's length must be a power of two");
+        JOLT_REQUIRE(ctx, sigma_tables[d] <= (uint32_t)m && sigma_tables[d] <= sigma, "evaluate_blocks: a block's columns exceed its variables or the grid's");
+        descs[d] = BlockDesc{tables[d]->data(), sigma_tables[d], (uint32_t)m};
+        max_rows = std::max(max_rows, (size_t)1 << ((uint32_t)m - sigma_tables[d]));
+        const uint32_t log_unit = eval_block_log_unit(sigma_tables[d]);
+        max_units = std::max(max_units, (tables[d]->len + (((size_t)1 << log_unit) - 1)) >> log_unit);
+    }
+    if (max_rows > (size_t)1 << nu) return JOLT_ERR_SIZE_MISMATCH;
+    for (size_t i = 0; i < n_point; ++i) JOLT_REQUIRE(ctx, fr_is_canonical(fr_from_abi(&point[i])), "evaluate_blocks: a coordinate is not a canonical Fr");
+    // a workgroup per four units of the largest table, capped so that the launch stays near 2048 workgroups; the waves stride over the rest
+    const size_t forced = eval_blocks_cap(), cap = forced ? forced : std::max<size_t>(1, 2048 / n_tables);
+    const size_t n_blocks = std::max<size_t>(1, std::min<size_t>((max_units + kBlock / 64 - 1) / (kBlock / 64), std::min<size_t>(cap, 65535)));
+
+    jolt_table *left = nullptr, *right = nullptr, *out = nullptr;
+    Fr* partials = nullptr;
+    BlockDesc* d_descs = nullptr;
+    const jolt_fr_t one = [] { jolt_fr_t o; fr_to_abi(&o, Fr::one()); return o; }();
+    int32_t st = nu ? jolt_eq_evals(ctx, point, nu, nullptr, &left) : jolt_table_upload(ctx, &one, 1, &left);
+    if (st == JOLT_OK) st = sigma ? jolt_eq_evals(ctx, point + nu, sigma, nullptr, &right) : jolt_table_upload(ctx, &one, 1, &right);
+    if (st == JOLT_OK) st = jolt_internal_table_new(ctx, n_tables, &out);
+    if (st == JOLT_OK) st = jolt_internal_dev_alloc(ctx, n_tables * n_blocks * sizeof(Fr), (void**)&partials);
+    if (st == JOLT_OK) st = jolt_internal_dev_alloc(ctx, n_tables * sizeof(BlockDesc), (void**)&d_descs);
+    if (st == JOLT_OK) {
+        hipError_t e = hipMemcpyAsync(d_descs, descs.data(), n_tables * sizeof(BlockDesc), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_dory_eval_blocks, dim3((unsigned)n_blocks, (unsigned)n_tables), dim3(kBlock), 0, ctx->stream, (const BlockDesc*)d_descs, (const Fr*)left->data(),
+                               (const Fr*)right->data(), partials);
+            hipLaunchKernelGGL(k_dory_eval_blocks_sum, dim3((unsigned)n_tables), dim3(kBlock), 0, ctx->stream, (const Fr*)partials, (uint32_t)n_blocks, out->data());
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream);  // `descs` is read by the copy until here
+            ctx->last_error = std::string("evaluate_blocks: ") + hipGetErrorString(e);
+            st = JOLT_ERR_HIP;
+        } else {
+            st = jolt_table_download(ctx, out, 0, n_tables, claims_out);  // synchronises the stream
+        }
+    }
+    if (partials) jolt_internal_dev_free(ctx, partials);  // back to the pool: reuse is stream-ordered
+    if (d_descs) jolt_internal_dev_free(ctx, d_descs);
+    for (jolt_table* t : {left, right, out})
+        if (t) jolt_table_free(ctx, t);
+    return st;
 }
 
 // grid index of coefficient i of a block of 2^sigma_table columns embedded top-left in a grid of 2^sigma_grid columns

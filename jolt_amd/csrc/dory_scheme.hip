@@ -11,7 +11,7 @@
 // The opening (open_impl) is host control flow over those entries: the protocol of jolt_amd/dory_open.py and dory_reduce.py, with the challenges drawn through a
 // callback after each message.  Every exit drains the streams before the state vectors go back to the pool (OpenState's destructor).
 // The batch opening of stage 8 (jolt_host_dory_prove_batch) is HomomorphicBatch::prove_batch around it: the statement's framing (host_mirror.hip), the eq tables of the
-// point, the lazy row fold under gamma's powers, the check <v, R> == joint_eval, open_impl with the hints weighted by the same powers, the closing claim.
+// point, the lazy row fold under gamma's powers (the trace in either placement, then the block-embedded tables on top of it), the check <v, R> == joint_eval, open_impl with the hints weighted by the same powers, the closing claim.
 #include <vector>
 
 #include "ctx.hpp"
@@ -412,16 +412,16 @@ extern "C" int32_t jolt_host_dory_open(jolt_ctx* ctx, const jolt_dory_setup* set
 // ------------------------------------------------------------------------------------------------------------------ the batch opening of stage 8
 namespace {
 
-// the tables one batch opening makes (L, R, v).  As OpenState: the streams are drained before the blocks go back to the pool.
+// the tables one batch opening makes (L, R, the trace's fold under a batch with blocks, v).  As OpenState: the streams are drained before the blocks go back to the pool.
 struct BatchTables {
     jolt_ctx* ctx;
-    jolt_table *left = nullptr, *right = nullptr, *v = nullptr;
+    jolt_table *left = nullptr, *right = nullptr, *trace = nullptr, *v = nullptr;
     explicit BatchTables(jolt_ctx* c) : ctx(c) {}
     ~BatchTables() {
         (void)hipStreamSynchronize(ctx->stream);
         for (hipStream_t st : ctx->side)
             if (st) (void)hipStreamSynchronize(st);
-        for (jolt_table* x : {left, right, v})
+        for (jolt_table* x : {left, right, trace, v})
             if (x) (void)jolt_table_free(ctx, x);
     }
 };
@@ -436,19 +436,27 @@ int32_t eq_table(jolt_ctx* ctx, const jolt_fr_t* r, size_t n, jolt_table** out) 
 
 }  // namespace
 
-extern "C" int32_t jolt_host_dory_prove_batch(jolt_ctx* ctx, const jolt_dory_setup* setup, const jolt_dory_vec* const* hints, const size_t* hint_first, const size_t* hint_rows,
-                                              size_t n_claims, const jolt_fr_t* evaluations, const jolt_onehot* const* sources, size_t n_sources, jolt_table* const* dense,
-                                              size_t n_dense, uint32_t log_k, const size_t* column_of_claim, const jolt_fr_t* point, size_t n_point, jolt_host_transcript* t,
-                                              jolt_gt_t* gts, jolt_g1_t* g1s, jolt_g2_t* g2s, jolt_fr_t* challenges_out, jolt_fr_t* scalars_out, jolt_fr_t* joint_eval_out) {
+// The one body of both entries.  n_blocks = 0 in the cycle-major placement is jolt_host_dory_prove_batch as it always was: the same checks in the same order, the
+// same launches, the same bytes.
+static int32_t prove_batch_impl(jolt_ctx* ctx, const jolt_dory_setup* setup, const jolt_dory_vec* const* hints, const size_t* hint_first, const size_t* hint_rows, size_t n_claims,
+                                const jolt_fr_t* evaluations, const jolt_onehot* const* sources, size_t n_sources, jolt_table* const* dense, size_t n_dense,
+                                jolt_table* const* blocks, const uint32_t* sigma_blocks, size_t n_blocks, uint32_t log_k, int32_t order, uint32_t log_extra,
+                                const size_t* column_of_claim, const jolt_fr_t* point, size_t n_point, jolt_host_transcript* t, jolt_gt_t* gts, jolt_g1_t* g1s, jolt_g2_t* g2s,
+                                jolt_fr_t* challenges_out, jolt_fr_t* scalars_out, jolt_fr_t* joint_eval_out) {
     if (!ctx || !setup || !hints || !hint_first || !hint_rows || !evaluations || !point || !t || !gts || !g1s || !g2s || !challenges_out || !scalars_out || !joint_eval_out ||
-        (n_sources && !sources) || (n_dense && !dense))
+        (n_sources && !sources) || (n_dense && !dense) || (n_blocks && (!blocks || !sigma_blocks)))
         return JOLT_ERR_INVALID_ARG;
-    // ---- every check of this entry, of the row fold and of the opening, before the transcript absorbs anything and before anything is enqueued ----
+    // ---- every check of this entry, of the row folds and of the opening, before the transcript absorbs anything and before anything is enqueued ----
     JOLT_REQUIRE(ctx, setup->ctx == ctx, "the setup belongs to another context");
     JOLT_REQUIRE(ctx, n_claims != 0, "an empty batch");  // HomomorphicBatchStatement::new refuses it
-    if (n_sources > 4 || n_dense > 8 || log_k > 8 || n_claims > (size_t)0x00FFFFFFu) return JOLT_ERR_UNSUPPORTED;  // the limits of jolt_dory_fold_rows_grid and of the hint combination
+    // the limits of jolt_dory_fold_rows_grid, of jolt_dory_fold_rows_blocks_many and of the hint combination
+    if (n_sources > 4 || n_dense > 8 || n_blocks > 256 || log_k > 8 || n_claims > (size_t)0x00FFFFFFu) return JOLT_ERR_UNSUPPORTED;
+    const bool address_major = order == JOLT_DORY_ORDER_ADDRESS_MAJOR;
+    JOLT_REQUIRE(ctx, address_major || order == JOLT_DORY_ORDER_CYCLE_MAJOR, "the order is cycle-major or address-major");
+    JOLT_REQUIRE(ctx, address_major ? log_extra <= 32 : log_extra == 0, "log_extra widens the address-major grid only");
     for (size_t s = 0; s < n_sources; ++s) JOLT_REQUIRE(ctx, sources[s] && sources[s]->ctx == ctx, "a source is null or of another context");
     for (size_t d = 0; d < n_dense; ++d) JOLT_REQUIRE(ctx, dense[d] && dense[d]->ctx == ctx && dense[d]->data(), "a dense column is null or of another context");
+    for (size_t d = 0; d < n_blocks; ++d) JOLT_REQUIRE(ctx, blocks[d] && blocks[d]->ctx == ctx && blocks[d]->data(), "a block is null or of another context");
     JOLT_REQUIRE(ctx, n_sources + n_dense != 0, "a batch has at least one column");
     const size_t T = n_sources ? sources[0]->cycles : dense[0]->len;
     JOLT_REQUIRE(ctx, T != 0 && (T & (T - 1)) == 0, "the cycle count must be a power of two");
@@ -461,10 +469,12 @@ extern "C" int32_t jolt_host_dory_prove_batch(jolt_ctx* ctx, const jolt_dory_set
     }
     for (size_t d = 0; d < n_dense; ++d)
         if (dense[d]->len != T) return JOLT_ERR_SIZE_MISMATCH;
-    JOLT_REQUIRE(ctx, n_claims == n_onehot + n_dense, "one claim per column of the joint polynomial");
-    JOLT_REQUIRE(ctx, n_point == (size_t)log_k + log_t, "the point has log_k + log_t coordinates");
+    const size_t n_trace = n_onehot + n_dense;
+    JOLT_REQUIRE(ctx, n_claims == n_trace + n_blocks, "one claim per column of the joint polynomial");
+    JOLT_REQUIRE(ctx, n_point == (size_t)log_k + log_extra + log_t, "the point has one coordinate per variable of the grid");
     const uint32_t sigma = (uint32_t)((n_point + 1) / 2), nu = (uint32_t)n_point - sigma;  // crates/jolt-dory/src/scheme.rs:242-243
     JOLT_REQUIRE(ctx, sigma <= kMaxSigma, "sigma <= 30");
+    if (address_major && sigma < log_k + log_extra) return JOLT_ERR_UNSUPPORTED;  // a cycle's block wider than a matrix row (jolt_dory_fold_rows_grid_am)
     const size_t rows = (size_t)1 << nu, n = (size_t)1 << sigma;
     if (n > setup->n) {
         ctx->last_error = "the setup holds fewer than 2^sigma bases";
@@ -483,18 +493,37 @@ extern "C" int32_t jolt_host_dory_prove_batch(jolt_ctx* ctx, const jolt_dory_set
             column[i] = c;
         }
     }
+    {  // a block: 2^m_d entries as 2^(m_d - sigma_d) rows of 2^sigma_d columns inside the grid, its hint one row commitment per row (jolt_dory_fold_rows_blocks' codes)
+        std::vector<size_t> block_rows(n_blocks);
+        for (size_t d = 0; d < n_blocks; ++d) {
+            const size_t len = blocks[d]->len;
+            JOLT_REQUIRE(ctx, len != 0 && (len & (len - 1)) == 0, "a block's length must be a power of two");
+            uint32_t m = 0;
+            while (((size_t)1 << m) < len) ++m;
+            JOLT_REQUIRE(ctx, sigma_blocks[d] <= m && sigma_blocks[d] <= sigma, "a block's columns exceed its variables or the grid's");
+            block_rows[d] = (size_t)1 << (m - sigma_blocks[d]);
+            if (block_rows[d] > rows) return JOLT_ERR_SIZE_MISMATCH;
+        }
+        for (size_t i = 0; i < n_claims; ++i)
+            if (column[i] >= n_trace) JOLT_REQUIRE(ctx, hint_rows[i] == block_rows[column[i] - n_trace], "a block's hint has one row commitment per row of the block");
+    }
     // ---- the statement: rlc_claims, the evaluations, gamma's powers; joint_eval = sum_i gamma^i y_i ----
     JOLT_TRY(jolt_host_opening_statement_absorb(t, evaluations, n_claims, scalars_out));
     Fr joint = Fr::zero();
     for (size_t i = 0; i < n_claims; ++i) joint = add(joint, mul(fr_from_abi(&scalars_out[i]), fr_from_abi(&evaluations[i])));
     fr_to_abi(joint_eval_out, joint);
-    std::vector<jolt_fr_t> by_column(n_claims);  // the row fold takes its scalars in column order
+    std::vector<jolt_fr_t> by_column(n_claims);  // the row folds take their scalars in column order
     for (size_t i = 0; i < n_claims; ++i) by_column[column[i]] = scalars_out[i];
-    // ---- L = eq(point[:nu]), R = eq(point[nu:]), v = L^T M by the lazy row fold ----
+    // ---- L = eq(point[:nu]), R = eq(point[nu:]), v = L^T M by the lazy row fold of the trace, then the blocks on top of it ----
     BatchTables tb(ctx);
     JOLT_TRY(eq_table(ctx, point, nu, &tb.left));
     JOLT_TRY(eq_table(ctx, point + nu, sigma, &tb.right));
-    JOLT_TRY(jolt_dory_fold_rows_grid(ctx, sources, n_sources, by_column.data(), dense, n_dense, by_column.data() + n_onehot, log_k, sigma, tb.left, &tb.v));
+    jolt_table** trace_out = n_blocks ? &tb.trace : &tb.v;
+    if (address_major)
+        JOLT_TRY(jolt_dory_fold_rows_grid_am(ctx, sources, n_sources, by_column.data(), dense, n_dense, by_column.data() + n_onehot, log_k + log_extra, log_extra, sigma, tb.left, trace_out));
+    else
+        JOLT_TRY(jolt_dory_fold_rows_grid(ctx, sources, n_sources, by_column.data(), dense, n_dense, by_column.data() + n_onehot, log_k, sigma, tb.left, trace_out));
+    if (n_blocks) JOLT_TRY(jolt_dory_fold_rows_blocks_many(ctx, blocks, sigma_blocks, n_blocks, by_column.data() + n_trace, sigma, tb.left, tb.trace, &tb.v));
     // ---- <v, R> is the joint polynomial's evaluation at the point: a statement that does not hold is refused here, before any state vector is built ----
     jolt_fr_t y;
     JOLT_TRY(jolt_table_dot(ctx, tb.v, tb.right, 0, &y));
@@ -504,4 +533,22 @@ extern "C" int32_t jolt_host_dory_prove_batch(jolt_ctx* ctx, const jolt_dory_set
     }
     JOLT_TRY(open_impl(ctx, setup, hints, hint_first, hint_rows, n_claims, scalars_out, tb.v, tb.left, tb.right, nu, sigma, engine_fn, t, gts, g1s, g2s, challenges_out));
     return jolt_host_opening_claim_absorb(t, point, n_point, joint_eval_out);
+}
+
+extern "C" int32_t jolt_host_dory_prove_batch_blocks(jolt_ctx* ctx, const jolt_dory_setup* setup, const jolt_dory_vec* const* hints, const size_t* hint_first,
+                                                     const size_t* hint_rows, size_t n_claims, const jolt_fr_t* evaluations, const jolt_onehot* const* sources, size_t n_sources,
+                                                     jolt_table* const* dense, size_t n_dense, jolt_table* const* blocks, const uint32_t* sigma_blocks, size_t n_blocks,
+                                                     uint32_t log_k, int32_t order, uint32_t log_extra, const size_t* column_of_claim, const jolt_fr_t* point, size_t n_point,
+                                                     jolt_host_transcript* t, jolt_gt_t* gts, jolt_g1_t* g1s, jolt_g2_t* g2s, jolt_fr_t* challenges_out, jolt_fr_t* scalars_out,
+                                                     jolt_fr_t* joint_eval_out) {
+    return prove_batch_impl(ctx, setup, hints, hint_first, hint_rows, n_claims, evaluations, sources, n_sources, dense, n_dense, blocks, sigma_blocks, n_blocks, log_k, order,
+                            log_extra, column_of_claim, point, n_point, t, gts, g1s, g2s, challenges_out, scalars_out, joint_eval_out);
+}
+
+extern "C" int32_t jolt_host_dory_prove_batch(jolt_ctx* ctx, const jolt_dory_setup* setup, const jolt_dory_vec* const* hints, const size_t* hint_first, const size_t* hint_rows,
+                                              size_t n_claims, const jolt_fr_t* evaluations, const jolt_onehot* const* sources, size_t n_sources, jolt_table* const* dense,
+                                              size_t n_dense, uint32_t log_k, const size_t* column_of_claim, const jolt_fr_t* point, size_t n_point, jolt_host_transcript* t,
+                                              jolt_gt_t* gts, jolt_g1_t* g1s, jolt_g2_t* g2s, jolt_fr_t* challenges_out, jolt_fr_t* scalars_out, jolt_fr_t* joint_eval_out) {
+    return prove_batch_impl(ctx, setup, hints, hint_first, hint_rows, n_claims, evaluations, sources, n_sources, dense, n_dense, nullptr, nullptr, 0, log_k,
+                            JOLT_DORY_ORDER_CYCLE_MAJOR, 0, column_of_claim, point, n_point, t, gts, g1s, g2s, challenges_out, scalars_out, joint_eval_out);
 }

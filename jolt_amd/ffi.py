@@ -1793,10 +1793,17 @@ def host_opening_claim_absorb(transcript, point, value):
     _call("jolt_host_opening_claim_absorb", None, transcript.h, _p(p) if p.shape[0] else None, p.shape[0], _p(fr(value).reshape(4)))
 
 
-def _dory_prove_batch(self, setup, hints, evaluations, sources, dense, log_k, point, transcript, column_of_claim=None):
+DORY_ORDERS = {"cycle_major": 0, "address_major": 1}  # JOLT_DORY_ORDER_* of the header
+
+
+def _dory_prove_batch(self, setup, hints, evaluations, sources, dense, log_k, point, transcript, column_of_claim=None, blocks=(), block_sigmas=(), order="cycle_major",
+                      log_extra=0):
     """HomomorphicBatch::<DoryScheme>::prove_batch as one call (jolt_host_dory_prove_batch): setup a DoryLibSetup; hints one resident G1 view per claim; evaluations
     (n, 4) as the statement holds them; sources / dense / log_k the joint polynomial's columns as dory_fold_rows_grid takes them; column_of_claim[i] = claim i's column
     in that order (None: the identity); point: log_k + log T coordinates, most significant first; transcript a HostTranscript.
+    blocks / block_sigmas / order / log_extra (any of them given: jolt_host_dory_prove_batch_blocks): block-embedded Tables of 2^m field elements with their sigma_d, as
+    dory_fold_rows_blocks takes them -- the columns after the dense ones; order "cycle_major" or "address_major" (the trace as dory_fold_rows_grid_am places it, log_block
+    = log_k + log_extra, log_stride = log_extra; the point is then log T + log_k + log_extra coordinates in grid order).  Without them the call is the call it was.
     -> dict(gts, g1s, g2s, challenges, scalars, joint_eval, nu, sigma): the proof in protocol order, the RLC scalars 1, gamma, ... and sum_i scalars[i] evaluations[i]."""
     views = [_dory_view(h) for h in hints]
     hs, firsts, rows = _dory_view_arrays(views)
@@ -1810,11 +1817,22 @@ def _dory_prove_batch(self, setup, hints, evaluations, sources, dense, log_k, po
     scalars, joint = fr_array(max(len(views), 1)), fr_array(1)
     ss = (C.c_void_p * max(len(sources), 1))(*[s.h for s in sources])
     ds = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
-    order = None if column_of_claim is None else (C.c_size_t * max(len(column_of_claim), 1))(*[int(c) for c in column_of_claim])
-    if order is not None and len(column_of_claim) != len(views):
+    claim_order = None if column_of_claim is None else (C.c_size_t * max(len(column_of_claim), 1))(*[int(c) for c in column_of_claim])
+    if claim_order is not None and len(column_of_claim) != len(views):
         raise ValueError("one column per claim")
-    _call("jolt_host_dory_prove_batch", self, self.h, setup.h, hs, firsts, rows, len(views), _p(ev), ss if sources else None, len(sources), ds if dense else None, len(dense),
-          log_k, order, _p(pt), pt.shape[0], transcript.h, _p(gts), _p(g1s), _p(g2s), _p(ch), _p(scalars), _p(joint))
+    if order not in DORY_ORDERS:
+        raise ValueError("order is cycle_major or address_major")
+    if len(block_sigmas) != len(blocks):
+        raise ValueError("one sigma per block")
+    if not blocks and order == "cycle_major" and log_extra == 0:
+        _call("jolt_host_dory_prove_batch", self, self.h, setup.h, hs, firsts, rows, len(views), _p(ev), ss if sources else None, len(sources), ds if dense else None,
+              len(dense), log_k, claim_order, _p(pt), pt.shape[0], transcript.h, _p(gts), _p(g1s), _p(g2s), _p(ch), _p(scalars), _p(joint))
+    else:
+        bs = (C.c_void_p * max(len(blocks), 1))(*[t.h for t in blocks])
+        sg = (C.c_uint32 * max(len(blocks), 1))(*[int(x) for x in block_sigmas])
+        _call("jolt_host_dory_prove_batch_blocks", self, self.h, setup.h, hs, firsts, rows, len(views), _p(ev), ss if sources else None, len(sources),
+              ds if dense else None, len(dense), bs if blocks else None, sg if blocks else None, len(blocks), log_k, DORY_ORDERS[order], log_extra, claim_order, _p(pt),
+              pt.shape[0], transcript.h, _p(gts), _p(g1s), _p(g2s), _p(ch), _p(scalars), _p(joint))
     return dict(gts=gts, g1s=g1s, g2s=g2s, challenges=ch, scalars=scalars[:len(views)], joint_eval=joint[0], nu=pt.shape[0] - sigma, sigma=sigma)
 
 
@@ -1954,6 +1972,35 @@ def _dory_fold_rows_blocks(self, tables, sigma_tables, scalars, sigma, left, bas
     return Table(self, h)
 
 
+def _dory_fold_rows_blocks_many(self, tables, sigma_tables, scalars, sigma, left, base=None):
+    """dory_fold_rows_blocks over up to 256 tables (jolt_dory_fold_rows_blocks_many): a chain of launch sets of eight; the same field elements for any grouping"""
+    n = len(tables)
+    if len(sigma_tables) != n or len(scalars) != n:
+        raise ValueError("one sigma and one scalar per table")
+    hs = (C.c_void_p * max(n, 1))(*[t.h for t in tables])
+    sg = (C.c_uint32 * max(n, 1))(*sigma_tables)
+    sc = fr(np.stack([fr(c) for c in scalars])).reshape(-1, 4) if n else fr_array(1)
+    h = C.c_void_p()
+    _call("jolt_dory_fold_rows_blocks_many", self, self.h, hs, sg, n, _p(sc), sigma, left.h, base.h if base is not None else None, C.byref(h))
+    return Table(self, h)
+
+
+def _dory_evaluate_blocks(self, tables, sigma_tables, point, sigma):
+    """the statement's claims of block-embedded tables from one pass (jolt_dory_evaluate_blocks): (len(tables), 4),
+    claims[d] = sum_i tables[d][i] * eq(point, host_dory_block_index(sigma_tables[d], sigma, i)); point: the grid-order opening point of nu + sigma coordinates"""
+    n = len(tables)
+    if len(sigma_tables) != n:
+        raise ValueError("one sigma per table")
+    pt = fr(point).reshape(-1, 4)
+    if pt.shape[0] < sigma:
+        raise ValueError("the point has nu + sigma coordinates")
+    hs = (C.c_void_p * max(n, 1))(*[t.h for t in tables])
+    sg = (C.c_uint32 * max(n, 1))(*[int(x) for x in sigma_tables])
+    out = fr_array(max(n, 1))
+    _call("jolt_dory_evaluate_blocks", self, self.h, hs, sg, n, _p(pt) if pt.shape[0] else _p(fr_array(1)), pt.shape[0], pt.shape[0] - sigma, sigma, _p(out))
+    return out[:n]
+
+
 def host_dory_fr_digits(scalar, c, W):
     """the signed c-bit digits the field-row kernels give one scalar: ([digit_w for w < W], negative) with sum_w digit_w 2^(c w) = min(s, r - s) and
     negative = whether r - s was taken"""
@@ -1979,6 +2026,8 @@ def host_dory_block_index(sigma_table, sigma_grid, i):
 Context.dory_commit_rows_fr = _dory_commit_rows_fr
 Context.dory_hints_rows_fr = _dory_hints_rows_fr
 Context.dory_fold_rows_blocks = _dory_fold_rows_blocks
+Context.dory_fold_rows_blocks_many = _dory_fold_rows_blocks_many
+Context.dory_evaluate_blocks = _dory_evaluate_blocks
 
 
 def _gt(a):

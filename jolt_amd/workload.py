@@ -241,12 +241,22 @@ class DeviceWorkload:
     grid under the reference's production scheme: commit() is a dory_commit.DoryWitnessCommitment -- resident tier-1 hints, tier 2 as one
     product batch -- and open() is HomomorphicBatch::prove_batch as one library call, jolt_host_dory_prove_batch, over the statement's claims
     `opening_claims`, which one launch over the witness columns computes at construction; dory_bases= plants the setup's bases, otherwise
-    jolt_amd/dory_setup.py generates 2^sigma per group from the seed)."""
+    jolt_amd/dory_setup.py generates 2^sigma per group from the seed; dory_blocks= adds the polynomials of stage 8 that are field elements -- advice, bytecode
+    chunks, the program image -- as block-embedded columns after the trace's: host arrays (2^m, 4) or log2 sizes m to draw from the seed, committed by
+    jolt_dory_hints_rows_fr, their claims from jolt_dory_evaluate_blocks, opened with the trace by jolt_host_dory_prove_batch_blocks; dory_order="address_major"
+    (with dory_log_extra) commits and opens the trace in the other placement, open_point then in that grid's order)."""
 
     def __init__(self, ctx, n_vars, seed=2026, pcs=None, srs=None, fixed_base=True, extended=False, witness_upload=False, ram_addresses="uniform", **kw):
         from . import ffi
         if pcs == "dory" and n_vars < 4:  # sigma = ceil((4 + n_vars) / 2) > n_vars: a matrix row wider than one address's cycles (refused before anything is uploaded)
             raise ValueError("pcs='dory' needs n_vars >= 4")
+        # pcs="dory": the polynomials of stage 8 that are field elements and not trace columns (advice, bytecode chunks, the program image), embedded top-left in the
+        # grid: host arrays (2^m, 4) of canonical field elements, or m itself (generated from the seed); the trace placement; the widening of an address-major grid
+        dory_blocks, dory_order, dory_log_extra = list(kw.pop("dory_blocks", ())), kw.pop("dory_order", "cycle_major"), int(kw.pop("dory_log_extra", 0))
+        if pcs == "dory":  # refused before anything is uploaded
+            dory_blocks = self._check_dory_shape(n_vars, seed, dory_blocks, dory_order, dory_log_extra)
+        elif dory_blocks or dory_order != "cycle_major" or dory_log_extra:
+            raise ValueError("dory_blocks, dory_order and dory_log_extra belong to pcs='dory'")
         self.ctx, self.n_vars, self.ffi, self.pcs, self._seed = ctx, n_vars, ffi, pcs, seed
         # witness_upload: every step STARTS from the packed per-cycle rows in host memory (RowSource::rows() + WitnessBundle::from_row windows,
         # crates/jolt-witness/src/consumer.rs:129-143, crates/jolt-kernels/src/optimized/rows.rs:22-72): one H2D copy of the rows, the typed columns and hot
@@ -350,7 +360,8 @@ class DeviceWorkload:
             from .dory_proof import DoryProofSetup
             self.log_k = 4
             assert all(len(self.tables_spec[t].point) == self.log_k for ms in self.members_spec if self._lazy(ms) for t in ms.tables[1:])
-            self.grid_vars = self.log_k + n_vars
+            self.dory_order, self.dory_log_extra = dory_order, dory_log_extra
+            self.grid_vars = self.log_k + n_vars + dory_log_extra
             self.committed_dense = ["s6.ram_inc", "s6.rd_inc"]
             self.dory_sigma = (self.grid_vars + 1) // 2
             self.dory_nu = self.grid_vars - self.dory_sigma
@@ -368,6 +379,10 @@ class DeviceWorkload:
             prng = np.random.default_rng(seed + 3)
             self.open_point = rand_fr(self.grid_vars, prng)
             self.column_of_claim = None  # the batch order is the caller's (final_opening_polynomial_order); None: the column order
+            # the block-embedded polynomials are resident inputs like the witness columns: each its own balanced matrix (BlockOpeningPoly::new), columns after the dense ones
+            from .dory_commit import block_sigma
+            self.dory_blocks = [ctx.upload(b) for b in dory_blocks]
+            self.dory_block_sigmas = [block_sigma(len(b)) for b in dory_blocks]
         elif pcs is not None:
             raise ValueError(pcs)
         self.tables, self.members, self.prepared, self.hint = {}, [], False, None
@@ -763,16 +778,63 @@ class DeviceWorkload:
         return out
 
     # ---- pcs="dory": the same columns under the reference's production scheme ------------------------------------------------------------------------------
+    @staticmethod
+    def _check_dory_shape(n_vars, seed, blocks, order, log_extra, log_k=4):
+        """the refusals of pcs="dory" that need no device: the placement, and every block against the grid of 2^nu x 2^sigma.  -> the blocks as host arrays (an int m
+        becomes 2^m field elements drawn from the seed)"""
+        if order not in ("cycle_major", "address_major"):
+            raise ValueError("dory_order is cycle_major or address_major")
+        if log_extra < 0 or (log_extra and order != "address_major"):
+            raise ValueError("dory_log_extra widens the address-major grid only")
+        grid_vars = log_k + n_vars + log_extra
+        sigma = (grid_vars + 1) // 2
+        nu = grid_vars - sigma
+        if order == "address_major" and sigma < log_k + log_extra:
+            raise ValueError("address_major: sigma < log_k + log_extra, a cycle's block is wider than a matrix row")
+        if len(blocks) > 256:
+            raise ValueError("at most 256 blocks")
+        rng = np.random.default_rng(seed + 4)
+        out = []
+        for b in blocks:
+            if isinstance(b, (int, np.integer)):
+                if not 0 <= b <= grid_vars:
+                    raise ValueError("a block does not fit the grid")
+                b = rand_fr(1 << int(b), rng)
+            b = np.ascontiguousarray(b, dtype=np.uint64).reshape(-1, 4)
+            n = b.shape[0]
+            if n == 0 or n & (n - 1):
+                raise ValueError("a block holds a power of two of field elements")
+            sigma_p = (n.bit_length() - 1 + 1) // 2  # dory_commit.block_sigma
+            if sigma_p > sigma or n >> sigma_p > 1 << nu:
+                raise ValueError("a block does not fit the grid")
+            out.append(b)
+        return out
+
     def _dory_columns(self):
         """(sources, dense field tables): the joint polynomial's columns in jolt_dory_fold_rows_grid's order"""
         return [self.sources[i] for i in sorted(self.sources)], [self.tables[name] for name in self.committed_dense]
 
     def evaluate_columns(self):
-        """(columns, 4): every committed column's evaluation at open_point, ONE launch over the witness columns (jolt_grid_evaluate_columns)"""
+        """(columns, 4): every committed column's evaluation at open_point, ONE launch over the witness columns (jolt_grid_evaluate_columns), then the blocks' claims
+        from one launch over the blocks (jolt_dory_evaluate_blocks).  open_point is in grid order: address then cycle coordinates cycle-major; cycle, address, extra
+        coordinates address-major -- the same column at the permuted point, times the Lagrange factor prod (1 - e) of the extra coordinates at zero."""
         if not self.prepared:
             self.prepare()
         sources, dense = self._dory_columns()
-        return self.ctx.grid_evaluate_columns(sources, dense, self.log_k, self.open_point)
+        if getattr(self, "dory_order", "cycle_major") == "address_major":
+            ffi, n, k = self.ffi, self.n_vars, self.log_k
+            cycle, address, extra = self.open_point[:n], self.open_point[n:n + k], self.open_point[n + k:]
+            claims = self.ctx.grid_evaluate_columns(sources, dense, k, np.concatenate([address, cycle]))
+            if len(extra):
+                scale = self.one
+                for e in extra:
+                    scale = ffi.host_fr_mul(scale, ffi.host_fr_sub(self.one, e))
+                claims = np.stack([ffi.host_fr_mul(c, scale) for c in claims])
+        else:
+            claims = self.ctx.grid_evaluate_columns(sources, dense, self.log_k, self.open_point)
+        if getattr(self, "dory_blocks", None):
+            claims = np.concatenate([claims, self.ctx.dory_evaluate_blocks(self.dory_blocks, self.dory_block_sigmas, self.open_point, self.dory_sigma)])
+        return claims
 
     def evaluate_columns_pushforward(self):
         """the same claims by the route that preceded that entry, kept as the second implementation the tests hold it against: per source one
@@ -805,7 +867,8 @@ class DeviceWorkload:
             self.dory_commitment.close()
             self.dory_commitment = None
         sources = [self.sources[i] for i in sorted(self.sources)]
-        self.dory_commitment = DoryWitnessCommitment(self.dory_setup, self.srs, sources, [self.ints[name] for name in self.committed_dense], self.dory_sigma)
+        self.dory_commitment = DoryWitnessCommitment(self.dory_setup, self.srs, sources, [self.ints[name] for name in self.committed_dense], self.dory_sigma,
+                                                     order=self.dory_order, log_k=self.log_k, log_extra=self.dory_log_extra, blocks=self.dory_blocks)
         return dict(tier2=np.stack(self.dory_setup.tier2(self.dory_commitment.hints)))
 
     def dory_open(self, label=0, evaluations=None, column_of_claim=None):
@@ -822,7 +885,8 @@ class DeviceWorkload:
         sources, dense = self._dory_columns()
         transcript = self.ffi.HostTranscript(label)
         try:
-            out = self.ctx.dory_prove_batch(self.dory_setup, hints, evaluations, sources, dense, self.log_k, self.open_point, transcript, column_of_claim=order)
+            out = self.ctx.dory_prove_batch(self.dory_setup, hints, evaluations, sources, dense, self.log_k, self.open_point, transcript, column_of_claim=order,
+                                            blocks=self.dory_blocks, block_sigmas=self.dory_block_sigmas, order=self.dory_order, log_extra=self.dory_log_extra)
             out["transcript_state"] = transcript.state()
         finally:
             transcript.close()
@@ -870,6 +934,9 @@ class DeviceWorkload:
         for v in self.ints.values():
             v.free()
         self.sources, self.ints = {}, {}
+        for b in getattr(self, "dory_blocks", []):
+            b.free()
+        self.dory_blocks = []
         if getattr(self, "_rows_in_flight", None) is not None:
             self._rows_in_flight.free()
             self._rows_in_flight = None

@@ -478,6 +478,8 @@ extern "C" {
     pub fn jolt_host_dory_fr_digits(scalar: *const jolt_fr_t, c: i32, W: i32, digits_out: *mut u32, negative_out: *mut u32) -> i32;
     pub fn jolt_host_dory_rows_fr_plan(bit_length: u32, row_width: usize, c: *mut i32, W: *mut i32) -> i32;
     pub fn jolt_dory_fold_rows_blocks(ctx: *mut jolt_ctx, tables: *const *mut jolt_table, sigma_tables: *const u32, n_tables: usize, scalars: *const jolt_fr_t, sigma: u32, left: *const jolt_table, base: *const jolt_table, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_dory_fold_rows_blocks_many(ctx: *mut jolt_ctx, tables: *const *mut jolt_table, sigma_tables: *const u32, n_tables: usize, scalars: *const jolt_fr_t, sigma: u32, left: *const jolt_table, base: *const jolt_table, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_dory_evaluate_blocks(ctx: *mut jolt_ctx, tables: *const *mut jolt_table, sigma_tables: *const u32, n_tables: usize, point: *const jolt_fr_t, n_point: usize, nu: u32, sigma: u32, claims_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_dory_block_index(sigma_table: u32, sigma_grid: u32, i: usize, index: *mut usize) -> i32;
     pub fn jolt_dory_setup_create(ctx: *mut jolt_ctx, gamma1: *const jolt_g1_t, gamma2: *const jolt_g2_t, n: usize, h1: *const jolt_g1_t, h2: *const jolt_g2_t, out: *mut *mut jolt_dory_setup) -> i32;
     pub fn jolt_dory_setup_free(ctx: *mut jolt_ctx, setup: *mut jolt_dory_setup) -> i32;
@@ -487,6 +489,7 @@ extern "C" {
     pub fn jolt_host_dory_open_with_transcript(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, v_table: *const jolt_table, left: *const jolt_table, right: *const jolt_table, nu: u32, sigma: u32, r#fn: jolt_dory_transcript_fn, user: *mut c_void, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_dory_open(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_hints: usize, scalars: *const jolt_fr_t, v_table: *const jolt_table, left: *const jolt_table, right: *const jolt_table, nu: u32, sigma: u32, t: *mut jolt_host_transcript, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_dory_prove_batch(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_claims: usize, evaluations: *const jolt_fr_t, sources: *const *const jolt_onehot, n_sources: usize, dense: *const *mut jolt_table, n_dense: usize, log_k: u32, column_of_claim: *const usize, point: *const jolt_fr_t, n_point: usize, t: *mut jolt_host_transcript, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t, scalars_out: *mut jolt_fr_t, joint_eval_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_dory_prove_batch_blocks(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, hints: *const *const jolt_dory_vec, hint_first: *const usize, hint_rows: *const usize, n_claims: usize, evaluations: *const jolt_fr_t, sources: *const *const jolt_onehot, n_sources: usize, dense: *const *mut jolt_table, n_dense: usize, blocks: *const *mut jolt_table, sigma_blocks: *const u32, n_blocks: usize, log_k: u32, order: i32, log_extra: u32, column_of_claim: *const usize, point: *const jolt_fr_t, n_point: usize, t: *mut jolt_host_transcript, gts: *mut jolt_gt_t, g1s: *mut jolt_g1_t, g2s: *mut jolt_g2_t, challenges_out: *mut jolt_fr_t, scalars_out: *mut jolt_fr_t, joint_eval_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_host_dory_proof_counts(sigma: u32, n_gt: *mut usize, n_g1: *mut usize, n_g2: *mut usize, n_challenges: *mut usize) -> i32;
     pub fn jolt_host_g2_serialize_compressed(p: *const jolt_g2_t, out: *mut u8) -> i32;
     pub fn jolt_host_gt_serialize(f: *const jolt_gt_t, out: *mut u8) -> i32;
