@@ -88,6 +88,8 @@ int32_t jolt_ctx_trim(jolt_ctx *ctx);
 int32_t jolt_ctx_memory_stats(const jolt_ctx *ctx, size_t *live_bytes, size_t *cached_bytes, size_t *peak_bytes);
 /* ... and what the context holds outside the pool: the grow-only workspaces of its MSM lanes and of the batch of short MSMs (bytes). */
 int32_t jolt_ctx_workspace_stats(const jolt_ctx *ctx, size_t *msm_lane_bytes, size_t *msm_batch_bytes);
+/* ... and the pair tables of the commitment grid built on this context's SRSs (jolt_srs_precompute_grid_pairs), bytes. */
+int32_t jolt_ctx_grid_pairs_stats(const jolt_ctx *ctx, size_t *bytes);
 /* Which kernel path the batch rounds of this context took: host-side launch counts since the context was created or the counts were last zeroed (a test names the
  * kernel it means to reach with them; nothing on the device reads or writes them).  counts[k], k < min(cap, JOLT_ROUND_PATH_COUNT), is the count of the enum below;
  * reset != 0 zeroes all of them after the copy (counts may be NULL to zero only). */
@@ -303,6 +305,20 @@ int32_t jolt_srs_free(jolt_ctx *ctx, jolt_srs *srs);
  * window_bits = 0 picks c from the SRS length (23 from 2^24 points, else <= 24); MSMs over fewer than min_terms terms (0 = 2^(c-2)) keep
  * the per-window method.  Results are the same points. */
 int32_t jolt_srs_precompute_windows(jolt_ctx *ctx, jolt_srs *srs, uint32_t window_bits, size_t min_terms);
+/* Pair tables of the K x T commitment grid, for an SRS that has its window tables: on that grid a one-hot column adds, per cycle, one of only k
+ * bases, so two consecutive cycles add one of k^2 sums.  For every shift s set in shift_mask (s <= 4), with the domain length D = cycles >> s, keep
+ * PT_D[(m * k + a) * k + b] = srs[a * D + 2m] + srs[b * D + 2m + 1] (m < D / 2; a, b < k) resident as affine points in the bucket kernels' radix:
+ * jolt_grid_commit_onehot (s = 0), jolt_grid_commit_onehot_classes and jolt_grid_hint_begin (s = shift / level) then add one entry per pair of hot
+ * cycles instead of two bases.  The tables depend on the SRS, k and D alone.  32 k^2 D bytes per table (k = 16, D = 2^22: 32 GiB).  Needs
+ * k <= 16, cycles a power of two >= 2 << s and k * cycles <= the SRS; a table that cannot be built (shape, memory) is left out, the SRS stays as
+ * it was and the call still returns JOLT_OK -- the sums then run on the single bases.  Results are the same points either way.
+ * _bytes: the size of the table for (k, D), 0 when there is none. */
+int32_t jolt_srs_precompute_grid_pairs(jolt_ctx *ctx, jolt_srs *srs, uint32_t k, size_t cycles, uint32_t shift_mask);
+int32_t jolt_srs_grid_pairs_bytes(const jolt_srs *srs, uint32_t k, size_t domain, size_t *bytes);
+/* The entry arithmetic and the index map of those tables compiled for the host (csrc/grid_pairs.hip.h): out_words = the 8 words (x, y) stored for
+ * p + q -- (0, 0) for the point at infinity --, readable by jolt_host_g1_sum_limb_form. */
+int32_t jolt_host_grid_pair_entry(const jolt_g1_t *p, const jolt_g1_t *q, uint64_t *out_words);
+int32_t jolt_host_grid_pair_index(size_t m, uint32_t k, uint32_t a, uint32_t b, size_t *out);
 
 /* Measurement hook (no reference counterpart): HIP events around the dominant kernel of a fixed-base MSM (the bucket sums, k_fx_buckets_ordered) on the stream it is
  * launched on, and the number of mixed additions of that launch (the non-zero signed digits of its scalars).  bench.py's `roofline_msm` divides the two. */

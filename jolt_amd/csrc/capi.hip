@@ -262,6 +262,12 @@ extern "C" int32_t jolt_ctx_workspace_stats(const jolt_ctx* ctx, size_t* msm_lan
     if (msm_batch_bytes) *msm_batch_bytes = ctx->msm_batch_ws_cap;
     return JOLT_OK;
 }
+/* ... and the commitment grid's pair tables on the SRSs of this context (jolt_srs_precompute_grid_pairs). */
+extern "C" int32_t jolt_ctx_grid_pairs_stats(const jolt_ctx* ctx, size_t* bytes) {
+    if (!ctx || !bytes) return JOLT_ERR_INVALID_ARG;
+    *bytes = ctx->grid_pairs_bytes;
+    return JOLT_OK;
+}
 
 /* Launch counts of group_enqueue per kernel path (the JOLT_ROUND_PATH_* indices), optionally zeroed after the copy. */
 extern "C" int32_t jolt_ctx_round_path_stats(jolt_ctx* ctx, uint64_t* counts, size_t cap, int32_t reset) {

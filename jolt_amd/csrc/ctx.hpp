@@ -107,6 +107,7 @@ struct jolt_ctx {
     std::unordered_map<void*, size_t> pool_live;               // block -> size class (bytes)
     std::unordered_map<size_t, std::vector<void*>> pool_free;  // size class -> cached blocks
     size_t pool_cached_bytes = 0, pool_live_bytes = 0, pool_peak_bytes = 0;
+    size_t grid_pairs_bytes = 0;  // outside the pool: the pair tables built on this context's SRSs (grid_pairs.hip), until their SRS is freed
     // jolt_dory_routines_timing: per-phase wall time of the last Dory routine call (checks, host -> device, kernels, device -> host)
     bool dory_timing = false;
     double dory_ms[4] = {0.0, 0.0, 0.0, 0.0};

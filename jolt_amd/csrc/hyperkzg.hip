@@ -766,6 +766,9 @@ static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt
         std::vector<jolt_table*> dense_levels;
         jolt_table* dense_rlc = nullptr;
         auto lin_cleanup = [&]() {
+            // the combination runs on the hint's stream and the pool hands freed blocks to main-stream work at once: on every exit the buffers go back only after
+            // that stream has drained (a no-op after the download below, which has waited for it already)
+            if ((d_small || d_temp) && lin && lin->hint && lin->hint->stream != ctx->stream) (void)hipStreamSynchronize(lin->hint->stream);
             if (d_small) jolt_internal_dev_free(ctx, d_small);
             if (d_temp) jolt_internal_dev_free(ctx, d_temp);
             for (jolt_table* t : dense_levels) if (t) jolt_table_free(ctx, t);

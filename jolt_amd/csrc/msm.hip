@@ -198,6 +198,10 @@ extern "C" int32_t jolt_srs_free(jolt_ctx* ctx, jolt_srs* srs) {
         if (srs->mid_tables->pre) (void)hipFree(srs->mid_tables->pre);
         delete srs->mid_tables;
     }
+    for (int i = 0; i < srs->n_pairs; ++i) {
+        (void)hipFree(srs->pairs[i].table);
+        if (srs->ctx) srs->ctx->grid_pairs_bytes -= 32 * (size_t)srs->pairs[i].k * srs->pairs[i].k * srs->pairs[i].domain;
+    }
     delete srs;
     return JOLT_OK;
 }

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "grid_hint.hpp"
+#include "grid_pairs.hip.h"
 #include "ints.hpp"
 #include "msm_kernels.hip.h"
 #include "onehot.hpp"
@@ -93,6 +94,66 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(JOLT_BUC
             mine.y = fql_to_std(fql_mul(acc_l.y, fql_sqr(acc_l.zzz)), r256);
             mine.z = fql_to_std(acc_l.zzz, r256);
         }
+    }
+    const G1Jac total = wave_sum_g1(mine, 64);
+    if ((threadIdx.x & 63) == 0) partial[((cls * gridDim.y + p) * gridDim.x + blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6)] = total;
+}
+// The same sums over the L-form tables with the pair table of (k, folded_cycles) resident (grid_pairs.hip.h): a lane walks PAIRS of consecutive cycles of its class,
+// m = cycle pair (2m, 2m + 1) of the folded domain, and adds ONE point per pair -- pairs[(m k + a) k + b] when both cycles are hot, the single base of window 0
+// when one is, nothing when both are cold.  Everything else is k_grid_onehot_sum<true>: the first point starts the accumulator, the next indices and point are in
+// flight during the addition, g1xl_accumulate (infinity, which a table over a degenerate SRS can hold, behind its wave-uniform branch), the same partial sums out.
+// Narrow sources, whole columns.
+__device__ __forceinline__ bool grid_pair_pick(const uint8_t* __restrict__ col, size_t m, uint32_t shift, size_t cls, size_t folded_cycles, uint32_t k,
+                                               const G1Affine* __restrict__ bases, const G1Affine* __restrict__ pairs, const G1Affine*& src) {
+    const uint32_t a = hot_load(col, ((2 * m) << shift) + cls, 0u), b = hot_load(col, ((2 * m + 1) << shift) + cls, 0u);
+    if (a != kColdIdx && b != kColdIdx) src = pairs + grid_pair_index(m, k, a, b);
+    else if (a != kColdIdx) src = bases + (size_t)a * folded_cycles + 2 * m;
+    else if (b != kColdIdx) src = bases + (size_t)b * folded_cycles + 2 * m + 1;
+    else return false;
+    return true;
+}
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(JOLT_BUCKET_WAVES, JOLT_BUCKET_WAVES))) void k_grid_onehot_sum_pairs(
+    const uint8_t* __restrict__ idx, size_t grid_cycles, const G1Affine* __restrict__ bases, const G1Affine* __restrict__ pairs, uint32_t k, G1Jac* __restrict__ partial,
+    LformConsts lc, uint32_t shift) {
+    const size_t p = blockIdx.y, cls = blockIdx.z;
+    const uint8_t* col = hot_col(idx, p * grid_cycles, 0u);
+    const size_t stride = (size_t)gridDim.x * kBlock, folded_cycles = grid_cycles >> shift, n_pairs = folded_cycles >> 1;
+    G1XyzzL acc_l = g1xl_identity();
+    bool ident = true;
+    const FqL one = fql_from_words(lc.one_l);
+    size_t m = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    const G1Affine* src = nullptr;
+    for (; m < n_pairs; m += stride) {
+        if (!grid_pair_pick(col, m, shift, cls, folded_cycles, k, bases, pairs, src)) continue;
+        acc_l = g1xl_from_affine(ld_aff(src), 0u, one, ident);
+        m += stride;
+        break;
+    }
+    bool has = m < n_pairs && grid_pair_pick(col, m, shift, cls, folded_cycles, k, bases, pairs, src);
+    G1Affine pt;
+    pt.x = Fq::zero();
+    pt.y = Fq::zero();
+    if (has) pt = ld_aff(src);
+    while (m < n_pairs) {
+        const size_t mn = m + stride;
+        const G1Affine* srcn = nullptr;
+        const bool hasn = mn < n_pairs && grid_pair_pick(col, mn, shift, cls, folded_cycles, k, bases, pairs, srcn);
+        G1Affine pn;
+        pn.x = Fq::zero();
+        pn.y = Fq::zero();
+        if (hasn) pn = ld_aff(srcn);
+        if (has) g1xl_accumulate(acc_l, ident, pt, src, 0u, one);
+        pt = pn;
+        src = srcn;
+        has = hasn;
+        m = mn;
+    }
+    G1Jac mine = g1_identity();
+    if (!ident) {
+        const FqL r256 = fql_from_words(lc.r256);
+        mine.x = fql_to_std(fql_mul(acc_l.x, fql_sqr(acc_l.zz)), r256);
+        mine.y = fql_to_std(fql_mul(acc_l.y, fql_sqr(acc_l.zzz)), r256);
+        mine.z = fql_to_std(acc_l.zzz, r256);
     }
     const G1Jac total = wave_sum_g1(mine, 64);
     if ((threadIdx.x & 63) == 0) partial[((cls * gridDim.y + p) * gridDim.x + blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6)] = total;
@@ -331,16 +392,28 @@ extern "C" int32_t jolt_table_from_ints(jolt_ctx* ctx, const jolt_ints* values, 
     return JOLT_OK;
 }
 
+// `whole`: the launch covers whole columns and may take the SRS's pair table (range commits keep the single bases whatever their range)
+static int32_t grid_commit_onehot_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t cycle_lo, size_t cycle_hi, uint32_t shift, bool whole, jolt_g1_t* out);
 extern "C" int32_t jolt_grid_commit_onehot(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, jolt_g1_t* out) {
     if (!source) return JOLT_ERR_INVALID_ARG;
-    return jolt_grid_commit_onehot_range(ctx, srs, source, 0, source->cycles, out);
+    return grid_commit_onehot_impl(ctx, srs, source, 0, source->cycles, 0, true, out);
 }
 
 // the partial commitments over cycles [cycle_lo, cycle_hi): one rank's share of a commitment sharded over the cycles (the ranks'
 // partial points add up to jolt_grid_commit_onehot's)
-static int32_t grid_commit_onehot_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t cycle_lo, size_t cycle_hi, uint32_t shift, jolt_g1_t* out);
 extern "C" int32_t jolt_grid_commit_onehot_range(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t cycle_lo, size_t cycle_hi, jolt_g1_t* out) {
-    return grid_commit_onehot_impl(ctx, srs, source, cycle_lo, cycle_hi, 0, out);
+    return grid_commit_onehot_impl(ctx, srs, source, cycle_lo, cycle_hi, 0, false, out);
+}
+// The pair table a whole-column launch over the L-form tables adds from (k_grid_onehot_sum_pairs), or null: narrow sources only, and the table of exactly this
+// (k, T >> shift) -- its domain is a power of two >= 2, so T is one as well
+static const G1Affine* grid_pairs_for(const jolt_srs* srs, const jolt_onehot* source, uint32_t shift) {
+    if (!srs->pre || srs->pre_stride < (size_t)source->k * source->cycles || source->wide || (source->cycles >> shift) << shift != source->cycles) return nullptr;
+    return jolt_srs_grid_pairs(srs, source->k, source->cycles >> shift);
+}
+// workgroups per column of a sum over `span` additions per (column, class): see grid_commit_onehot_impl
+static unsigned grid_sum_blocks(const jolt_ctx* ctx, size_t span, size_t N, size_t cap) {
+    const size_t by_work = (span + (size_t)kBlock * 128 - 1) / ((size_t)kBlock * 128), fill = ((size_t)ctx->num_cus * 8 + N - 1) / std::max<size_t>(N, 1);
+    return (unsigned)std::max<size_t>(1, std::min<size_t>({(span + kBlock - 1) / kBlock, std::max(by_work, fill), cap}));
 }
 // out[c * n_polys + p] = sum over the cycles j = c mod 2^shift of srs[(hot_p(j) * T + j) >> shift]: the commitments of the 2^shift residue-class parts of every
 // column on the grid of a polynomial folded `shift` times low to high.  With them the first level commitments of an opening of the joint polynomial follow by
@@ -349,9 +422,9 @@ extern "C" int32_t jolt_grid_commit_onehot_range(jolt_ctx* ctx, const jolt_srs* 
 extern "C" int32_t jolt_grid_commit_onehot_classes(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, uint32_t shift, jolt_g1_t* out) {
     if (!source) return JOLT_ERR_INVALID_ARG;
     if (shift > 4 || (source->cycles & (source->cycles - 1)) != 0 || source->cycles < ((size_t)1 << shift)) return JOLT_ERR_UNSUPPORTED;  // a power-of-two grid
-    return grid_commit_onehot_impl(ctx, srs, source, 0, source->cycles, shift, out);
+    return grid_commit_onehot_impl(ctx, srs, source, 0, source->cycles, shift, true, out);
 }
-static int32_t grid_commit_onehot_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t cycle_lo, size_t cycle_hi, uint32_t shift, jolt_g1_t* out) {
+static int32_t grid_commit_onehot_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t cycle_lo, size_t cycle_hi, uint32_t shift, bool whole, jolt_g1_t* out) {
     if (!ctx || !srs || !source || !out) return JOLT_ERR_INVALID_ARG;
     const size_t T = source->cycles, classes = (size_t)1 << shift, N = source->n_polys;
     if (cycle_lo > cycle_hi || cycle_hi > T) return JOLT_ERR_SIZE_MISMATCH;
@@ -359,9 +432,10 @@ static int32_t grid_commit_onehot_impl(jolt_ctx* ctx, const jolt_srs* srs, const
     if (N > 65535) return JOLT_ERR_UNSUPPORTED;
     // lanes per column: every lane ends with an XYZZ -> Jacobian conversion and six shuffle rounds of full additions (~11 mixed additions' worth), so a lane should own
     // >= 128 cycles (32 cycles per lane at T = 2^22 made that a third of the kernel); enough workgroups over all columns to fill the chip all the same
+    // with a pair table a lane's additions are pairs of cycles: the same rule counts pairs, so that a lane still owns >= 128 additions
+    const G1Affine* pairs = whole && cycle_lo == 0 && cycle_hi == T ? grid_pairs_for(srs, source, shift) : nullptr;
     const size_t span = (cycle_hi - cycle_lo) >> shift;  // cycles per (column, class)
-    const size_t by_work = (span + (size_t)kBlock * 128 - 1) / ((size_t)kBlock * 128), fill = ((size_t)ctx->num_cus * 8 + N - 1) / std::max<size_t>(N, 1);
-    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>({(span + kBlock - 1) / kBlock, std::max(by_work, fill), (size_t)kGridSumBlocks}));
+    const unsigned blocks = grid_sum_blocks(ctx, pairs ? span / 2 : span, N, (size_t)kGridSumBlocks);
     const uint32_t per_col = blocks * (kBlock / 64);
     G1Jac *partial = nullptr, *sums = nullptr;
     JOLT_TRY(jolt_internal_dev_alloc(ctx, classes * N * per_col * sizeof(G1Jac), (void**)&partial));
@@ -375,7 +449,10 @@ static int32_t grid_commit_onehot_impl(jolt_ctx* ctx, const jolt_srs* srs, const
         lc.r256 = Fq::one();
     }
     // window 0 of the fixed-base tables IS the SRS in L-form (msm_fixed.hip): the sums then run on the limb-form accumulator
-    if (srs->pre && srs->pre_stride >= (size_t)source->k * T)
+    if (pairs)
+        hipLaunchKernelGGL(k_grid_onehot_sum_pairs, dim3(blocks, (unsigned)N, (unsigned)classes), dim3(kBlock), 0, ctx->stream, (const uint8_t*)source->idx, T, (const G1Affine*)srs->pre,
+                           pairs, source->k, partial, lc, shift);
+    else if (srs->pre && srs->pre_stride >= (size_t)source->k * T)
         hipLaunchKernelGGL(k_grid_onehot_sum<true>, dim3(blocks, (unsigned)N, (unsigned)classes), dim3(kBlock), 0, ctx->stream, (const uint8_t*)source->idx, source->wide, T, cycle_lo,
                            cycle_hi, (const G1Affine*)srs->pre, partial, lc, shift);
     else
@@ -460,6 +537,7 @@ extern "C" int32_t jolt_grid_hint_begin(jolt_ctx* ctx, const jolt_srs* srs, cons
         if (e == hipSuccess && lds && !ctx->grid_hint_attr_set) {
             e = hipFuncSetAttribute((const void*)k_grid_onehot_sum<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_grid_onehot_sum<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_grid_onehot_sum_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e == hipSuccess) ctx->grid_hint_attr_set = true;
         }
     }
@@ -476,10 +554,13 @@ extern "C" int32_t jolt_grid_hint_begin(jolt_ctx* ctx, const jolt_srs* srs, cons
         for (size_t q = 0; q < n_sources; ++q) {
             const jolt_onehot* src = sources[q];
             const size_t N = src->n_polys;
-            const size_t by_work = (span + (size_t)kBlock * 128 - 1) / ((size_t)kBlock * 128), fill = ((size_t)ctx->num_cus * 8 + N - 1) / std::max<size_t>(N, 1);
-            const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>({(span + kBlock - 1) / kBlock, std::max(by_work, fill), blocks_max}));
+            const G1Affine* pairs = grid_pairs_for(srs, src, s_);
+            const unsigned blocks = grid_sum_blocks(ctx, pairs ? span / 2 : span, N, blocks_max);
             const uint32_t per_col = blocks * (kBlock / 64);
-            if (srs->pre && srs->pre_stride >= (size_t)src->k * T)
+            if (pairs)
+                hipLaunchKernelGGL(k_grid_onehot_sum_pairs, dim3(blocks, (unsigned)N, (unsigned)classes), dim3(kBlock), lds, h->stream, (const uint8_t*)src->idx, T, (const G1Affine*)srs->pre,
+                                   pairs, src->k, h->partial, lc, s_);
+            else if (srs->pre && srs->pre_stride >= (size_t)src->k * T)
                 hipLaunchKernelGGL(k_grid_onehot_sum<true>, dim3(blocks, (unsigned)N, (unsigned)classes), dim3(kBlock), lds, h->stream, (const uint8_t*)src->idx, src->wide, T, (size_t)0, T,
                                    (const G1Affine*)srs->pre, h->partial, lc, s_);
             else

@@ -19,7 +19,22 @@ struct jolt_srs {
     // 6.3 M buckets costs 3.5 ms whatever the MSM's length -- more than half of a 2^21-term MSM -- so MSMs of 2^19 .. 2^23 terms (the level commitments of an opening below
     // 2^24, the commitments of the 64-bit witness columns) take 2^19 buckets and 13 windows instead of 6.3 M and 11.  Owned; range views with an offset do not see it.
     jolt_srs* mid_tables = nullptr;
+    // Pair tables of the commitment grid (jolt_srs_precompute_grid_pairs, grid_pairs.hip): pairs[i].table[(m * k + a) * k + b] = pts[a * D + 2m] + pts[b * D + 2m + 1]
+    // in L-form for the domain length D = pairs[i].domain, 32 k^2 D bytes each -- the one-hot sums of bases (pcs.hip) add one entry per pair of cycles.  Owned, found
+    // again by (k, D); range views with an offset do not see them.
+    static constexpr int kMaxGridPairs = 5;
+    struct GridPairs {
+        uint32_t k = 0;
+        size_t domain = 0;
+        jolt::G1Affine* table = nullptr;
+    } pairs[kMaxGridPairs];
+    int n_pairs = 0;
 };
+static inline const jolt::G1Affine* jolt_srs_grid_pairs(const jolt_srs* srs, uint32_t k, size_t domain) {
+    for (int i = 0; i < srs->n_pairs; ++i)
+        if (srs->pairs[i].k == k && srs->pairs[i].domain == domain) return srs->pairs[i].table;
+    return nullptr;
+}
 
 // bases [offset, n) of `parent` as an SRS of their own (no ownership): term-range MSMs of a sharded opening
 static inline jolt_srs jolt_srs_range_view(const jolt_srs& parent, size_t offset) {
@@ -28,5 +43,6 @@ static inline jolt_srs jolt_srs_range_view(const jolt_srs& parent, size_t offset
     v.n = parent.n - offset;
     if (parent.pre) v.pre = parent.pre + offset;
     if (offset) v.mid_tables = nullptr;  // the mid set covers the bases from 0
+    if (offset) v.n_pairs = 0;           // ... and so do the grid's pair tables
     return v;
 }

@@ -906,7 +906,34 @@ def _srs_precompute_windows(self, srs, window_bits=0, min_terms=0):
     _call("jolt_srs_precompute_windows", self, self.h, srs.h, window_bits, min_terms)
 
 
+def _srs_precompute_grid_pairs(self, srs, k, cycles, shifts=(0,)):
+    """Pair tables of the k x cycles commitment grid for the given shifts (jolt_srs_precompute_grid_pairs): the one-hot sums of bases over an SRS with window
+    tables then add one entry per pair of cycles.  A table that cannot be built is left out; returns the bytes the SRS holds for (k, cycles >> s), per shift."""
+    _call("jolt_srs_precompute_grid_pairs", self, self.h, srs.h, k, cycles, sum(1 << s for s in set(shifts)))
+    return {s: srs_grid_pairs_bytes(srs, k, cycles >> s) for s in sorted(set(shifts))}
+
+
+def srs_grid_pairs_bytes(srs, k, domain):
+    out = C.c_size_t()
+    _call("jolt_srs_grid_pairs_bytes", srs.ctx, srs.h, k, domain, C.byref(out))
+    return out.value
+
+
+def host_grid_pair_entry(p, q):
+    """(8,) words of the pair-table entry for p + q (L-form affine x, y; zeros = infinity), from the host twin of the builder's arithmetic"""
+    out = np.zeros(8, dtype=np.uint64)
+    _call("jolt_host_grid_pair_entry", None, _p(np.ascontiguousarray(p, dtype=np.uint64)), _p(np.ascontiguousarray(q, dtype=np.uint64)), _p(out))
+    return out
+
+
+def host_grid_pair_index(m, k, a, b):
+    out = C.c_size_t()
+    _call("jolt_host_grid_pair_index", None, m, k, a, b, C.byref(out))
+    return out.value
+
+
 Context.srs_precompute_windows = _srs_precompute_windows
+Context.srs_precompute_grid_pairs = _srs_precompute_grid_pairs
 Context.srs_upload = _srs_upload
 Context.srs_setup_from_secret = _srs_setup_from_secret
 Context.msm = _msm
@@ -2175,6 +2202,9 @@ def _memory_stats(self):
     la, ba = C.c_size_t(), C.c_size_t()
     _call("jolt_ctx_workspace_stats", self, self.h, C.byref(la), C.byref(ba))
     out["msm_lanes_bytes"], out["msm_batch_bytes"] = la.value, ba.value  # outside the pool: grow-only MSM workspaces
+    gp = C.c_size_t()
+    _call("jolt_ctx_grid_pairs_stats", self, self.h, C.byref(gp))
+    out["grid_pairs_bytes"] = gp.value  # outside the pool: the commitment grid's pair tables on this context's SRSs
     return out
 
 

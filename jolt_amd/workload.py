@@ -334,7 +334,7 @@ class DeviceWorkload:
         for i, ms in enumerate(self.members_spec):
             self.stages.setdefault(ms.stage, []).append(i)
         # ---- PCS side (pcs="grid")
-        self.srs, self.own_srs = srs, False
+        self.srs, self.own_srs, self.grid_pairs_bytes = srs, False, 0
         if pcs == "grid":
             self.log_k = 4
             assert all(len(self.tables_spec[t].point) == self.log_k for ms in self.members_spec if self._lazy(ms) for t in ms.tables[1:])
@@ -348,6 +348,13 @@ class DeviceWorkload:
                 ctx.synchronize()
                 if fixed_base and self.grid_vars >= 12:  # setup-time (like the SRS itself): window-precomputed bases for the big MSMs
                     ctx.srs_precompute_windows(self.srs)
+                    # ... and the grid's pair tables beside them (a function of the SRS, K and T alone): shift 0 serves the commitment's sums of bases, shifts
+                    # 1 .. linear_levels() the opening hint's; JOLT_GRID_PAIR_SHIFTS ("" or e.g. "0,1") overrides the set for A/B runs
+                    import os
+                    shifts = os.environ.get("JOLT_GRID_PAIR_SHIFTS")
+                    shifts = range(self.linear_levels() + 1) if shifts is None else [int(s) for s in shifts.split(",") if s.strip()]
+                    if len(shifts):
+                        self.grid_pairs_bytes = sum(ctx.srs_precompute_grid_pairs(self.srs, 1 << self.log_k, 1 << n_vars, shifts).values())
             prng = np.random.default_rng(seed + 3)
             n_oh = sum(self.sources[i].n_polys for i in sorted(self.sources))
             self.rlc_onehot = rand_fr(n_oh, prng)

@@ -265,6 +265,7 @@ extern "C" {
     pub fn jolt_ctx_trim(ctx: *mut jolt_ctx) -> i32;
     pub fn jolt_ctx_memory_stats(ctx: *const jolt_ctx, live_bytes: *mut usize, cached_bytes: *mut usize, peak_bytes: *mut usize) -> i32;
     pub fn jolt_ctx_workspace_stats(ctx: *const jolt_ctx, msm_lane_bytes: *mut usize, msm_batch_bytes: *mut usize) -> i32;
+    pub fn jolt_ctx_grid_pairs_stats(ctx: *const jolt_ctx, bytes: *mut usize) -> i32;
     pub fn jolt_ctx_round_path_stats(ctx: *mut jolt_ctx, counts: *mut u64, cap: usize, reset: i32) -> i32;
     pub fn jolt_timer_begin(ctx: *mut jolt_ctx) -> i32;
     pub fn jolt_timer_end(ctx: *mut jolt_ctx, elapsed_ms: *mut f32) -> i32;
@@ -318,6 +319,10 @@ extern "C" {
     pub fn jolt_srs_download(ctx: *mut jolt_ctx, srs: *const jolt_srs, offset: usize, n: usize, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_srs_free(ctx: *mut jolt_ctx, srs: *mut jolt_srs) -> i32;
     pub fn jolt_srs_precompute_windows(ctx: *mut jolt_ctx, srs: *mut jolt_srs, window_bits: u32, min_terms: usize) -> i32;
+    pub fn jolt_srs_precompute_grid_pairs(ctx: *mut jolt_ctx, srs: *mut jolt_srs, k: u32, cycles: usize, shift_mask: u32) -> i32;
+    pub fn jolt_srs_grid_pairs_bytes(srs: *const jolt_srs, k: u32, domain: usize, bytes: *mut usize) -> i32;
+    pub fn jolt_host_grid_pair_entry(p: *const jolt_g1_t, q: *const jolt_g1_t, out_words: *mut u64) -> i32;
+    pub fn jolt_host_grid_pair_index(m: usize, k: u32, a: u32, b: u32, out: *mut usize) -> i32;
     pub fn jolt_msm_profile_buckets(ctx: *mut jolt_ctx, enable: i32) -> i32;
     pub fn jolt_msm_profile_buckets_last(ctx: *mut jolt_ctx, ms: *mut f32, additions: *mut u64) -> i32;
     pub fn jolt_ctx_measure_mad_peak(ctx: *mut jolt_ctx, target_ms: f32, mads_per_s: *mut f64, timed_ms: *mut f32, launches: *mut u32) -> i32;
