@@ -17,10 +17,12 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "ctx.hpp"
 #include "dory_am.hip.h"
+#include "dory_batches.hip.h"
 #include "dory_hints.hip.h"
 #include "dory_host.hpp"
 #include "dory_rows_fr.hip.h"
@@ -30,6 +32,7 @@
 
 using namespace jolt;
 using namespace jolt::msmk;
+using namespace jolt::dory_batches;
 
 #include "ints.hpp"
 
@@ -281,92 +284,11 @@ __global__ __launch_bounds__(kBlock) void k_onehot_emit(const G1Jac* __restrict_
     out[t] = g1_is_identity(b) ? g1_identity() : b;
 }
 
-struct BucketPlan {
-    int L;
-    uint32_t heavy_threshold, heavy_cap;
-};
-// V bucket sets of B buckets over n points each
-BucketPlan plan_buckets(size_t V, uint32_t B, size_t n) {
-    BucketPlan p;
-    p.L = 1;
-    while (p.L < 64 && V * B * (size_t)(2 * p.L) <= 524288) p.L *= 2;  // enough lanes to fill the chip when there are few buckets
-    size_t avg = (n + B - 1) / B;
-    p.heavy_threshold = (uint32_t)std::min<size_t>((size_t)p.L * std::max<size_t>(kLaneCap, 2 * avg), 0x7FFFFFFFu);
-    size_t pts = V * n;
-    p.heavy_cap = (uint32_t)std::min<size_t>(pts / kHeavySeg + pts / p.heavy_threshold + 16, 0x7FFFFFFFu);
-    return p;  // callers keep V * (B + 1) < 2^32 (bucket slots are u32) by batching at 2^26 points
-}
-
-struct Workspace {
-    uint32_t *keys, *sorted, *hist, *offs, *cur, *heavy, *hcnt;
-    G1Jac *buckets, *seg, *out;
-    Fq* pool;
-};
-// Carve lane 0's grow-only MSM workspace for V windows of n points, B buckets each, `outs` result points and `pool` Fq cells (the running products of
-// k_dory_hints_normalise; none: the layout the host-pointer entries have always had).
-int32_t carve(jolt_ctx* ctx, size_t V, size_t n, uint32_t B, uint32_t heavy_cap, size_t outs, Workspace* w, size_t pool = 0) {
-    const size_t VB = V * (B + 1);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    size_t o_keys = take(V * n * 4), o_sorted = take(V * n * 4), o_hist = take(VB * 4), o_offs = take(VB * 4), o_cur = take(VB * 4),
-           o_heavy = take((size_t)heavy_cap * 8), o_hcnt = take(256), o_buckets = take(VB * sizeof(G1Jac)),
-           o_seg = take((size_t)heavy_cap * sizeof(G1Jac)), o_out = take(outs * sizeof(G1Jac)), o_pool = take(pool * sizeof(Fq));
-    if (off > ctx->msm_ws_cap[0]) {
-        if (ctx->msm_ws[0]) {
-            JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            JOLT_HIP_TRY(ctx, hipFree(ctx->msm_ws[0]));
-            ctx->msm_ws[0] = nullptr;
-            ctx->msm_ws_cap[0] = 0;
-        }
-        JOLT_HIP_TRY(ctx, hipMalloc(&ctx->msm_ws[0], off));
-        ctx->msm_ws_cap[0] = off;
-    }
-    char* ws = (char*)ctx->msm_ws[0];
-    w->keys = (uint32_t*)(ws + o_keys);
-    w->sorted = (uint32_t*)(ws + o_sorted);
-    w->hist = (uint32_t*)(ws + o_hist);
-    w->offs = (uint32_t*)(ws + o_offs);
-    w->cur = (uint32_t*)(ws + o_cur);
-    w->heavy = (uint32_t*)(ws + o_heavy);
-    w->hcnt = (uint32_t*)(ws + o_hcnt);
-    w->buckets = (G1Jac*)(ws + o_buckets);
-    w->seg = (G1Jac*)(ws + o_seg);
-    w->out = (G1Jac*)(ws + o_out);
-    w->pool = (Fq*)(ws + o_pool);
-    return JOLT_OK;
-}
-
-// scan -> scatter -> light / heavy bucket sums for V windows whose keys and histogram are in place (already_sorted: hist / offsets /
-// sorted / heavy list were produced by k_rows_sort_lds)
-void launch_bucket_sums(jolt_ctx* ctx, const Workspace& w, const G1Affine* bases, size_t V, size_t n, uint32_t B, const BucketPlan& p,
-                        bool already_sorted = false) {
-    hipStream_t st = ctx->stream;
-    const unsigned gn = (unsigned)((n + kBlock - 1) / kBlock);
-    const unsigned gy = (unsigned)std::min<size_t>(V, 32768), gz = (unsigned)((V + gy - 1) / gy);
-    const unsigned gh = std::min<uint32_t>((p.heavy_cap + 3) / 4, 4096);
-    if (!already_sorted) {
-        hipLaunchKernelGGL(k_msm_scan, dim3((unsigned)V), dim3(kBlock), 0, st, (const uint32_t*)w.hist, w.offs, w.cur, B, p.heavy_threshold, w.heavy, w.hcnt,
-                           p.heavy_cap);
-        hipLaunchKernelGGL(k_msm_scatter, dim3(gn, gy, gz), dim3(kBlock), 0, st, (const uint32_t*)w.keys, n, B, w.cur, w.sorted, V);
-    }
-    hipLaunchKernelGGL(k_msm_buckets_light<false>, dim3((unsigned)(((size_t)B * p.L + kBlock - 1) / kBlock), gy, gz), dim3(kBlock), 0, st, (const uint32_t*)w.hist,
-                       (const uint32_t*)w.offs, (const uint32_t*)w.sorted, bases, n, B, p.L, p.heavy_threshold, w.buckets, V);
-    hipLaunchKernelGGL(k_msm_buckets_heavy<false>, dim3(gh), dim3(kBlock), 0, st, (const uint32_t*)w.heavy, (const uint32_t*)w.hcnt, (const uint32_t*)w.hist,
-                       (const uint32_t*)w.offs, (const uint32_t*)w.sorted, bases, n, B, w.seg, LformConsts{});
-    hipLaunchKernelGGL(k_msm_heavy_combine, dim3(gh), dim3(kBlock), 0, st, (const uint32_t*)w.heavy, (const uint32_t*)w.hcnt, (const uint32_t*)w.hist,
-                       (const G1Jac*)w.seg, w.buckets);
-}
-
 int log2_exact(size_t v) {
     if (v == 0 || (v & (v - 1))) return -1;
     int l = 0;
     while (((size_t)1 << l) < v) ++l;
     return l;
-}
-
-int32_t hip_fail(jolt_ctx* ctx, const char* what, hipError_t e) {
-    ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
-    return e == hipErrorOutOfMemory ? JOLT_ERR_OOM : JOLT_ERR_HIP;
 }
 
 }  // namespace
@@ -401,11 +323,15 @@ extern "C" int32_t jolt_ints_free(jolt_ctx* ctx, jolt_ints* v) {
     return JOLT_OK;
 }
 
+// =====================================================================================================================
+// The sinks and sources of bucket_batches (dory_batches.hip.h), the one launch loop under every tier-1 entry below.
+// =====================================================================================================================
 namespace {
 
 // Where a batch of row commitments goes once the fold kernels have left it in the workspace: to the caller's host array, as jolt_dory_commit_rows always has ...
 struct RowsToHost {
     jolt_g1_t* out;
+    size_t outs(size_t nr) const { return nr; }
     size_t pool_cells(size_t) const { return 0; }
     hipError_t zeros(jolt_ctx*, size_t rows) const {  // all-zero batch: every row commitment is the identity (Bn254G1::default())
         G1Jac id = g1_identity();
@@ -422,6 +348,7 @@ struct RowsToHost {
 // ... or normalised into a resident G1 view (jolt_dory_hints_rows): enqueued only
 struct RowsToView {
     G1Jac* out;
+    size_t outs(size_t nr) const { return nr; }
     size_t pool_cells(size_t nr) const { return nr; }
     hipError_t zeros(jolt_ctx* ctx, size_t rows) const {
         hipLaunchKernelGGL(dory_hints::k_dory_hints_identity, dim3((unsigned)((rows + dory_hints::kLanes - 1) / dory_hints::kLanes)), dim3(dory_hints::kLanes), 0, ctx->stream, out, rows);
@@ -433,82 +360,123 @@ struct RowsToView {
         return e;
     }
 };
+// The one-hot chunks' two: the K bucket sums of every chunk, as they are, to the caller's host array (jolt_dory_commit_onehot) ...
+struct OneHotToHost {
+    jolt_g1_t* out;
+    uint32_t K;
+    size_t outs(size_t V) const { return V * K; }
+    size_t pool_cells(size_t) const { return 0; }
+    hipError_t emit(jolt_ctx* ctx, const Workspace& w, size_t c0, size_t V) const {
+        hipLaunchKernelGGL(k_onehot_emit, dim3((unsigned)((V * K + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, (const G1Jac*)w.buckets, K, V * K, w.out);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out + c0 * K, w.out, V * K * sizeof(G1Jac), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        return e;
+    }
+};
+// ... or normalised straight from the buckets to where OneHotMap places window v0 + i of the column range (jolt_dory_hints_onehot): enqueued only
+struct OneHotToView {
+    G1Jac* out;
+    uint32_t K;
+    size_t chunks;
+    size_t outs(size_t) const { return 0; }
+    size_t pool_cells(size_t V) const { return V * K; }
+    hipError_t emit(jolt_ctx* ctx, const Workspace& w, size_t v0, size_t V) const {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = dory_hints::launch_normalise(ctx->stream, (const G1Jac*)w.buckets, dory_hints::OneHotMap{K, chunks, v0}, V * K, w.pool, out);
+        return e;
+    }
+};
 
-// The row commitments of `values` (checked by the caller: wl = log2(row_width), rows > 0), batch by batch into `sink`
+// values->kind as a compile-time constant: f(std::integral_constant<int, KIND>)
+template <class F>
+void with_int_kind(int kind, F&& f) {
+    if (kind == JOLT_INT_U64) f(std::integral_constant<int, JOLT_INT_U64>{});
+    else if (kind == JOLT_INT_I64) f(std::integral_constant<int, JOLT_INT_I64>{});
+    else f(std::integral_constant<int, JOLT_INT_I128>{});
+}
+
+// The integer rows' magnitudes: read in place by the row kernels of the values' kind
+struct IntMagnitudes {
+    const jolt_ints* values;
+    static constexpr int kWords = 4;
+    size_t batch_slots() const { return ~(size_t)0; }  // a batch is bounded by its keys alone
+    int32_t reserve(size_t) { return JOLT_OK; }  // nothing of its own per batch
+    void enqueue_or(hipStream_t st, uint32_t* out) const {
+        const unsigned g = (unsigned)std::min<size_t>((values->count + kBlock - 1) / kBlock, 4096);
+        with_int_kind(values->kind, [&](auto kind) {
+            hipLaunchKernelGGL(k_ints_or<decltype(kind)::value>, dim3(g), dim3(kBlock), 0, st, (const void*)values->data, values->count, out);
+        });
+    }
+    // f(kind, data, first): the magnitudes of values [first, first + n) are data[first ...] for the row kernels of `kind`
+    template <class F>
+    void stage(hipStream_t, size_t first, size_t, F&& f) const {
+        with_int_kind(values->kind, [&](auto kind) { f(kind, (const void*)values->data, first); });
+    }
+};
+
+// Rows of 2^wl values over the first 2^wl bases: an item is a row, W windows of c bits (2^(c-1) buckets) each
+template <class Magnitudes>
+struct RowSource {
+    const Magnitudes& mags;
+    int wl, c, W;
+    BatchShape shape;
+    bool keys(jolt_ctx* ctx, size_t r0, size_t nr, const BucketPlan& p, const Workspace& w) const {
+        hipStream_t st = ctx->stream;
+        const size_t nvals = nr << wl;
+        const size_t sort_lds = ((size_t)shape.buckets + 1 + kBlock) * sizeof(uint32_t);
+        const bool lds_sort = ctx->msm_lds_sort && sort_lds <= 64 * 1024;
+        mags.stage(st, r0 << wl, nvals, [&](auto kind, const void* data, size_t first) {
+            constexpr int KIND = decltype(kind)::value;
+            if (lds_sort)  // one workgroup per row sorts its W windows in LDS
+                hipLaunchKernelGGL(k_rows_sort_lds<KIND>, dim3((unsigned)nr), dim3(kBlock), sort_lds, st, data, first, (uint32_t)wl, c, W, w.hist, w.offs, w.sorted,
+                                   p.heavy_threshold, w.heavy, w.hcnt, p.heavy_cap);
+            else
+                hipLaunchKernelGGL(k_rows_digits<KIND>, dim3((unsigned)((nvals + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, data, first, nvals, (uint32_t)wl, c, W, w.keys,
+                                   w.hist);
+        });
+        return lds_sort;
+    }
+    void reduce(jolt_ctx* ctx, const Workspace& w, size_t nr) const {
+        const uint32_t B = shape.buckets;
+        if (B <= 128)
+            hipLaunchKernelGGL(k_rows_fold_lanes, dim3((unsigned)nr), dim3(B <= 64 ? 64 : 128), 0, ctx->stream, (const G1Jac*)w.buckets, B, c, W, w.out);
+        else
+            hipLaunchKernelGGL(k_rows_fold, dim3((unsigned)nr), dim3(kBlock), 0, ctx->stream, (const G1Jac*)w.buckets, B, c, W, w.out);
+    }
+};
+
+// The row commitments of `rows` rows of 2^wl magnitudes (checked by the caller: rows > 0), batch by batch into `sink`: the OR of all magnitudes bounds the windows
+// worth processing, an all-zero column never reaches the pipeline.
 // (min_window: the narrow rows of the address-major entry ask for wider digits than the ~16 points per bucket rule gives them; 0: the rule alone)
-template <class Sink>
-int32_t commit_rows_into(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, int wl, size_t rows, const Sink& sink, int min_window = 0) {
+template <class Magnitudes, class Sink>
+int32_t commit_rows_into(jolt_ctx* ctx, const G1Affine* bases, const char* what, Magnitudes& mags, int wl, size_t rows, const Sink& sink, int min_window = 0) {
     hipStream_t st = ctx->stream;
-    const int kind = values->kind;
-
-    // ---- bit length of the largest magnitude (pinned scratch: the lane-0 MSM result buffer)
+    // ---- bit length of the largest magnitude (pinned scratch: the lane-0 MSM result buffer).  The probe's words are read back before the first batch carves:
+    // that may move the workspace.
     if (!ctx->msm_host[0]) JOLT_HIP_TRY(ctx, hipHostMalloc(&ctx->msm_host[0], 128 * sizeof(G1Jac), hipHostMallocDefault));
     Workspace probe;
     JOLT_TRY(carve(ctx, 1, 1, 1, 16, 1, &probe));
     JOLT_HIP_TRY(ctx, hipMemsetAsync(probe.hcnt, 0, 256, st));
-    {
-        unsigned g = (unsigned)std::min<size_t>((values->count + kBlock - 1) / kBlock, 4096);
-        if (kind == JOLT_INT_U64) hipLaunchKernelGGL(k_ints_or<JOLT_INT_U64>, dim3(g), dim3(kBlock), 0, st, (const void*)values->data, values->count, probe.hcnt);
-        else if (kind == JOLT_INT_I64) hipLaunchKernelGGL(k_ints_or<JOLT_INT_I64>, dim3(g), dim3(kBlock), 0, st, (const void*)values->data, values->count, probe.hcnt);
-        else hipLaunchKernelGGL(k_ints_or<JOLT_INT_I128>, dim3(g), dim3(kBlock), 0, st, (const void*)values->data, values->count, probe.hcnt);
-    }
+    mags.enqueue_or(st, probe.hcnt);
     uint32_t* h_or = (uint32_t*)ctx->msm_host[0];
-    JOLT_HIP_TRY(ctx, hipMemcpyAsync(h_or, probe.hcnt, 16, hipMemcpyDeviceToHost, st));
+    JOLT_HIP_TRY(ctx, hipMemcpyAsync(h_or, probe.hcnt, 4 * Magnitudes::kWords, hipMemcpyDeviceToHost, st));
     JOLT_HIP_TRY(ctx, hipStreamSynchronize(st));
     int bits = 0;
-    for (int k = 3; k >= 0 && !bits; --k)
+    for (int k = Magnitudes::kWords - 1; k >= 0 && !bits; --k)
         if (h_or[k]) bits = 32 * k + 32 - __builtin_clz(h_or[k]);
     if (bits == 0) {
         const hipError_t e = sink.zeros(ctx, rows);
-        return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory rows", e);
+        return e == hipSuccess ? JOLT_OK : hip_fail(ctx, what, e);
     }
-
-    // ---- plan: ~16 points per bucket; the top window keeps one spare bit for the signed-digit carry
-    const int c = std::max(std::max(3, std::min(13, wl - 4)), min_window);
-    const int W = (bits + 1 + c - 1) / c;
-    if (W > kMaxRowWindows) return JOLT_ERR_UNSUPPORTED;
-    const uint32_t B = 1u << (c - 1);
-    const size_t batch_rows = std::max<size_t>(1, std::min<size_t>(rows, ((size_t)1 << 26) / ((size_t)W * row_width)));
-    for (size_t r0 = 0; r0 < rows; r0 += batch_rows) {
-        const size_t nr = std::min(batch_rows, rows - r0), V = nr * (size_t)W, nvals = nr * row_width;
-        BucketPlan p = plan_buckets(V, B, row_width);
-        Workspace w;
-        JOLT_TRY(carve(ctx, V, row_width, B, p.heavy_cap, nr, &w, sink.pool_cells(nr)));
-        const size_t VB = V * (B + 1);
-        hipError_t e = hipMemsetAsync(w.hist, 0, VB * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(w.hcnt, 0, 256, st);
-        if (e == hipSuccess) e = hipMemsetAsync(w.buckets, 0, VB * sizeof(G1Jac), st);  // z = 0: identity
-        if (e != hipSuccess) return hip_fail(ctx, "dory rows", e);
-        const unsigned gv = (unsigned)((nvals + kBlock - 1) / kBlock);
-        const size_t first = r0 * row_width;
-        const size_t sort_lds = ((size_t)B + 1 + kBlock) * sizeof(uint32_t);
-        const bool lds_sort = ctx->msm_lds_sort && sort_lds <= 64 * 1024;
-        if (lds_sort) {  // one workgroup per row sorts its W windows in LDS
-            const void* vd = (const void*)values->data;
-            if (kind == JOLT_INT_U64)
-                hipLaunchKernelGGL(k_rows_sort_lds<JOLT_INT_U64>, dim3((unsigned)nr), dim3(kBlock), sort_lds, st, vd, first, (uint32_t)wl, c, W, w.hist, w.offs, w.sorted,
-                                   p.heavy_threshold, w.heavy, w.hcnt, p.heavy_cap);
-            else if (kind == JOLT_INT_I64)
-                hipLaunchKernelGGL(k_rows_sort_lds<JOLT_INT_I64>, dim3((unsigned)nr), dim3(kBlock), sort_lds, st, vd, first, (uint32_t)wl, c, W, w.hist, w.offs, w.sorted,
-                                   p.heavy_threshold, w.heavy, w.hcnt, p.heavy_cap);
-            else
-                hipLaunchKernelGGL(k_rows_sort_lds<JOLT_INT_I128>, dim3((unsigned)nr), dim3(kBlock), sort_lds, st, vd, first, (uint32_t)wl, c, W, w.hist, w.offs, w.sorted,
-                                   p.heavy_threshold, w.heavy, w.hcnt, p.heavy_cap);
-        } else if (kind == JOLT_INT_U64)
-            hipLaunchKernelGGL(k_rows_digits<JOLT_INT_U64>, dim3(gv), dim3(kBlock), 0, st, (const void*)values->data, first, nvals, (uint32_t)wl, c, W, w.keys, w.hist);
-        else if (kind == JOLT_INT_I64)
-            hipLaunchKernelGGL(k_rows_digits<JOLT_INT_I64>, dim3(gv), dim3(kBlock), 0, st, (const void*)values->data, first, nvals, (uint32_t)wl, c, W, w.keys, w.hist);
-        else
-            hipLaunchKernelGGL(k_rows_digits<JOLT_INT_I128>, dim3(gv), dim3(kBlock), 0, st, (const void*)values->data, first, nvals, (uint32_t)wl, c, W, w.keys, w.hist);
-        launch_bucket_sums(ctx, w, srs->pts, V, row_width, B, p, lds_sort);
-        if (B <= 128)
-            hipLaunchKernelGGL(k_rows_fold_lanes, dim3((unsigned)nr), dim3(B <= 64 ? 64 : 128), 0, st, (const G1Jac*)w.buckets, B, c, W, w.out);
-        else
-            hipLaunchKernelGGL(k_rows_fold, dim3((unsigned)nr), dim3(kBlock), 0, st, (const G1Jac*)w.buckets, B, c, W, w.out);
-        e = sink.emit(ctx, w, r0, nr);
-        if (e != hipSuccess) return hip_fail(ctx, "dory rows", e);
-    }
-    return JOLT_OK;
+    // ---- plan: ~16 points per bucket, the top window keeps one spare bit for the signed-digit carry, at most kMaxRowWindows windows (dory_fr::plan)
+    int c, W;
+    dory_fr::plan(bits, wl, min_window, &c, &W);
+    const size_t width = (size_t)1 << wl, B = (size_t)1 << (c - 1);
+    const size_t by_keys = kMaxBatchKeys / ((size_t)W * width), by_slots = mags.batch_slots() / ((size_t)W * (B + 1));
+    const size_t batch_rows = std::max<size_t>(1, std::min(rows, std::min(by_keys, by_slots)));
+    JOLT_TRY(mags.reserve(batch_rows * width));
+    return bucket_batches(ctx, bases, what, RowSource<Magnitudes>{mags, wl, c, W, {rows, batch_rows, (size_t)W, width, (uint32_t)B}}, sink);
 }
 
 // the argument checks the two row entries share, with the reference's codes; rows = 0: nothing to do
@@ -529,7 +497,8 @@ extern "C" int32_t jolt_dory_commit_rows(jolt_ctx* ctx, const jolt_srs* srs, con
     size_t rows;
     JOLT_TRY(rows_shape(ctx, srs, values, row_width, &wl, &rows));
     if (rows == 0) return JOLT_OK;
-    return commit_rows_into(ctx, srs, values, row_width, wl, rows, RowsToHost{out});
+    IntMagnitudes mags{values};
+    return commit_rows_into(ctx, srs->pts, "dory rows", mags, wl, rows, RowsToHost{out});
 }
 
 extern "C" int32_t jolt_dory_hints_rows(jolt_ctx* ctx, const jolt_srs* srs, const jolt_ints* values, size_t row_width, jolt_dory_vec* out, size_t out_first) {
@@ -540,7 +509,8 @@ extern "C" int32_t jolt_dory_hints_rows(jolt_ctx* ctx, const jolt_srs* srs, cons
     G1Jac* dst = (G1Jac*)dory_host::g1_view(ctx, out, out_first, rows);
     JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the row commitments");
     if (rows == 0) return JOLT_OK;
-    return commit_rows_into(ctx, srs, values, row_width, wl, rows, RowsToView{dst});
+    IntMagnitudes mags{values};
+    return commit_rows_into(ctx, srs->pts, "dory rows", mags, wl, rows, RowsToView{dst});
 }
 
 // =====================================================================================================================
@@ -575,66 +545,29 @@ __global__ __launch_bounds__(kBlock) void k_fr_magnitudes(const Fr* __restrict__
     dory_fr::pack(m, negf, packed + 2 * i);
 }
 
-// commit_rows_into for table[first, first + rows * row_width)
-template <class Sink>
-int32_t commit_rows_fr_into(jolt_ctx* ctx, const jolt_srs* srs, const Fr* values, size_t row_width, int wl, size_t rows, const Sink& sink) {
-    hipStream_t st = ctx->stream;
-    const size_t count = rows * row_width;
-    if (!ctx->msm_host[0]) JOLT_HIP_TRY(ctx, hipHostMalloc(&ctx->msm_host[0], 128 * sizeof(G1Jac), hipHostMallocDefault));
-    Workspace probe;
-    JOLT_TRY(carve(ctx, 1, 1, 1, 16, 1, &probe));
-    JOLT_HIP_TRY(ctx, hipMemsetAsync(probe.hcnt, 0, 256, st));
-    hipLaunchKernelGGL(k_fr_or, dim3((unsigned)std::min<size_t>((count + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st, values, count, probe.hcnt);
-    uint32_t* h_or = (uint32_t*)ctx->msm_host[0];
-    JOLT_HIP_TRY(ctx, hipMemcpyAsync(h_or, probe.hcnt, 4 * dory_fr::kWords, hipMemcpyDeviceToHost, st));
-    JOLT_HIP_TRY(ctx, hipStreamSynchronize(st));
-    int bits = 0;
-    for (int k = dory_fr::kWords - 1; k >= 0 && !bits; --k)
-        if (h_or[k]) bits = 32 * k + 32 - __builtin_clz(h_or[k]);
-    if (bits == 0) {
-        const hipError_t e = sink.zeros(ctx, rows);
-        return e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory field rows", e);
-    }
-    int c, W;
-    dory_fr::plan(bits, wl, 0, &c, &W);
-    const uint32_t B = 1u << (c - 1);
-    // a batch is bounded by its keys, as the integer rows', and by its bucket slots: the widened digits give narrow rows 33 slots per window where c = 3 gives 5
-    const size_t by_keys = ((size_t)1 << 26) / ((size_t)W * row_width), by_slots = dory_fr::kMaxBatchSlots / ((size_t)W * (B + 1));
-    const size_t batch_rows = std::max<size_t>(1, std::min(rows, std::min(by_keys, by_slots)));
+// The field rows' magnitudes of table[0, count): packed per batch into a pool buffer, which goes back to the pool (reuse is stream-ordered) whichever way the entry ends
+struct FrMagnitudes {
+    jolt_ctx* ctx;
+    const Fr* values;
+    size_t count;
     uint4* packed = nullptr;
-    JOLT_TRY(jolt_internal_dev_alloc(ctx, batch_rows * row_width * 2 * sizeof(uint4), (void**)&packed));
-    int32_t rc = JOLT_OK;
-    for (size_t r0 = 0; r0 < rows && rc == JOLT_OK; r0 += batch_rows) {
-        const size_t nr = std::min(batch_rows, rows - r0), V = nr * (size_t)W, nvals = nr * row_width;
-        BucketPlan p = plan_buckets(V, B, row_width);
-        Workspace w;
-        rc = carve(ctx, V, row_width, B, p.heavy_cap, nr, &w, sink.pool_cells(nr));
-        if (rc != JOLT_OK) break;
-        const size_t VB = V * (B + 1);
-        hipError_t e = hipMemsetAsync(w.hist, 0, VB * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(w.hcnt, 0, 256, st);
-        if (e == hipSuccess) e = hipMemsetAsync(w.buckets, 0, VB * sizeof(G1Jac), st);  // z = 0: identity
-        if (e != hipSuccess) { rc = hip_fail(ctx, "dory field rows", e); break; }
-        const unsigned gv = (unsigned)((nvals + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(k_fr_magnitudes, dim3(gv), dim3(kBlock), 0, st, values + r0 * row_width, nvals, packed);
-        const size_t sort_lds = ((size_t)B + 1 + kBlock) * sizeof(uint32_t);
-        const bool lds_sort = ctx->msm_lds_sort && sort_lds <= 64 * 1024;
-        if (lds_sort)
-            hipLaunchKernelGGL(k_rows_sort_lds<kKindFrMag>, dim3((unsigned)nr), dim3(kBlock), sort_lds, st, (const void*)packed, (size_t)0, (uint32_t)wl, c, W, w.hist, w.offs,
-                               w.sorted, p.heavy_threshold, w.heavy, w.hcnt, p.heavy_cap);
-        else
-            hipLaunchKernelGGL(k_rows_digits<kKindFrMag>, dim3(gv), dim3(kBlock), 0, st, (const void*)packed, (size_t)0, nvals, (uint32_t)wl, c, W, w.keys, w.hist);
-        launch_bucket_sums(ctx, w, srs->pts, V, row_width, B, p, lds_sort);
-        if (B <= 128)
-            hipLaunchKernelGGL(k_rows_fold_lanes, dim3((unsigned)nr), dim3(B <= 64 ? 64 : 128), 0, st, (const G1Jac*)w.buckets, B, c, W, w.out);
-        else
-            hipLaunchKernelGGL(k_rows_fold, dim3((unsigned)nr), dim3(kBlock), 0, st, (const G1Jac*)w.buckets, B, c, W, w.out);
-        e = sink.emit(ctx, w, r0, nr);
-        if (e != hipSuccess) rc = hip_fail(ctx, "dory field rows", e);
+    static constexpr int kWords = dory_fr::kWords;
+    FrMagnitudes(jolt_ctx* c, const Fr* v, size_t n) : ctx(c), values(v), count(n) {}
+    FrMagnitudes(const FrMagnitudes&) = delete;
+    ~FrMagnitudes() { if (packed) jolt_internal_dev_free(ctx, packed); }
+    // a batch is bounded by its bucket slots too: the widened digits give narrow rows 33 slots per window where c = 3 gives 5
+    size_t batch_slots() const { return dory_fr::kMaxBatchSlots; }
+    int32_t reserve(size_t batch_values) { return jolt_internal_dev_alloc(ctx, batch_values * 2 * sizeof(uint4), (void**)&packed); }
+    void enqueue_or(hipStream_t st, uint32_t* out) const {
+        hipLaunchKernelGGL(k_fr_or, dim3((unsigned)std::min<size_t>((count + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0, st, values, count, out);
     }
-    jolt_internal_dev_free(ctx, packed);  // back to the pool: reuse is stream-ordered
-    return rc;
-}
+    // the batch's values are packed first: the row kernels read them from the buffer's start
+    template <class F>
+    void stage(hipStream_t st, size_t first, size_t n, F&& f) const {
+        hipLaunchKernelGGL(k_fr_magnitudes, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, values + first, n, packed);
+        f(std::integral_constant<int, kKindFrMag>{}, (const void*)packed, (size_t)0);
+    }
+};
 
 // the argument checks the two field-row entries share: jolt_dory_commit_rows' codes, and the stretch inside the table
 int32_t rows_fr_shape(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* table, size_t first, size_t count, size_t row_width, int* wl, size_t* rows) {
@@ -655,7 +588,8 @@ extern "C" int32_t jolt_dory_commit_rows_fr(jolt_ctx* ctx, const jolt_srs* srs, 
     size_t rows;
     JOLT_TRY(rows_fr_shape(ctx, srs, table, first, count, row_width, &wl, &rows));
     if (rows == 0) return JOLT_OK;
-    return commit_rows_fr_into(ctx, srs, (const Fr*)table->data() + first, row_width, wl, rows, RowsToHost{out});
+    FrMagnitudes mags(ctx, (const Fr*)table->data() + first, count);
+    return commit_rows_into(ctx, srs->pts, "dory field rows", mags, wl, rows, RowsToHost{out});
 }
 
 extern "C" int32_t jolt_dory_hints_rows_fr(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* table, size_t first, size_t count, size_t row_width, jolt_dory_vec* out,
@@ -667,7 +601,8 @@ extern "C" int32_t jolt_dory_hints_rows_fr(jolt_ctx* ctx, const jolt_srs* srs, c
     G1Jac* dst = (G1Jac*)dory_host::g1_view(ctx, out, out_first, rows);
     JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the row commitments");
     if (rows == 0) return JOLT_OK;
-    return commit_rows_fr_into(ctx, srs, (const Fr*)table->data() + first, row_width, wl, rows, RowsToView{dst});
+    FrMagnitudes mags(ctx, (const Fr*)table->data() + first, count);
+    return commit_rows_into(ctx, srs->pts, "dory field rows", mags, wl, rows, RowsToView{dst});
 }
 
 // The digits the kKindFrMag kernels give one scalar, on the host through the same routines: digits_out[w] = magnitude | negative << 31 of the signed digit of window w
@@ -700,6 +635,29 @@ extern "C" int32_t jolt_host_dory_rows_fr_plan(uint32_t bit_length, size_t row_w
     return JOLT_OK;
 }
 
+namespace {
+
+// One-hot columns from `first_poly` on as one key stream (the index array is [poly][cycle] contiguous): items = chunks of 2^wl cycles, each ONE window of K buckets whose
+// sums are the result as they stand
+struct OneHotSource {
+    const jolt_onehot* source;
+    size_t first_poly;
+    int wl;
+    BatchShape shape;
+    OneHotSource(const jolt_onehot* s, size_t poly, int log_width, size_t windows, size_t batch)
+        : source(s), first_poly(poly), wl(log_width), shape{windows, batch, 1, (size_t)1 << log_width, s->k} {}
+    bool keys(jolt_ctx* ctx, size_t v0, size_t V, const BucketPlan&, const Workspace& w) const {
+        const size_t nvals = V << wl;
+        const uint8_t* idx = source->idx + ((first_poly * source->cycles + (v0 << wl)) << source->wide);
+        hipLaunchKernelGGL(k_onehot_keys, dim3((unsigned)((nvals + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, idx, source->wide, nvals, (uint32_t)wl, source->k, w.keys,
+                           w.hist);
+        return false;
+    }
+    void reduce(jolt_ctx*, const Workspace&, size_t) const {}
+};
+
+}  // namespace
+
 extern "C" int32_t jolt_dory_commit_onehot(jolt_ctx* ctx, const jolt_srs* srs, const jolt_onehot* source, size_t poly, size_t chunk_width, jolt_g1_t* out) {
     if (!ctx || !srs || !source || !out) return JOLT_ERR_INVALID_ARG;
     if (poly >= source->n_polys) return JOLT_ERR_INVALID_ARG;
@@ -709,29 +667,8 @@ extern "C" int32_t jolt_dory_commit_onehot(jolt_ctx* ctx, const jolt_srs* srs, c
     if (source->cycles % chunk_width) return JOLT_ERR_SIZE_MISMATCH;
     const size_t chunks = source->cycles / chunk_width;
     if (chunks == 0) return JOLT_OK;
-    const uint32_t K = source->k;
-    hipStream_t st = ctx->stream;
-    const size_t batch = std::max<size_t>(1, std::min<size_t>(chunks, ((size_t)1 << 26) / chunk_width));
-    for (size_t c0 = 0; c0 < chunks; c0 += batch) {
-        const size_t V = std::min(batch, chunks - c0), nvals = V * chunk_width;
-        BucketPlan p = plan_buckets(V, K, chunk_width);
-        Workspace w;
-        JOLT_TRY(carve(ctx, V, chunk_width, K, p.heavy_cap, V * K, &w));
-        const size_t VB = V * (K + 1);
-        hipError_t e = hipMemsetAsync(w.hist, 0, VB * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(w.hcnt, 0, 256, st);
-        if (e == hipSuccess) e = hipMemsetAsync(w.buckets, 0, VB * sizeof(G1Jac), st);
-        if (e != hipSuccess) return hip_fail(ctx, "dory one-hot", e);
-        const uint8_t* idx = source->idx + ((poly * source->cycles + c0 * chunk_width) << source->wide);
-        hipLaunchKernelGGL(k_onehot_keys, dim3((unsigned)((nvals + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, idx, source->wide, nvals, (uint32_t)wl, K, w.keys, w.hist);
-        launch_bucket_sums(ctx, w, srs->pts, V, chunk_width, K, p);
-        hipLaunchKernelGGL(k_onehot_emit, dim3((unsigned)((V * K + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, (const G1Jac*)w.buckets, K, V * K, w.out);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out + c0 * K, w.out, V * K * sizeof(G1Jac), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return hip_fail(ctx, "dory one-hot", e);
-    }
-    return JOLT_OK;
+    const size_t batch = std::max<size_t>(1, std::min(chunks, kMaxBatchKeys / chunk_width));
+    return bucket_batches(ctx, srs->pts, "dory one-hot", OneHotSource{source, poly, wl, chunks, batch}, OneHotToHost{out, source->k});
 }
 
 // The hints of columns [first_poly, first_poly + n_polys) at once.  The index array is [poly][cycle] contiguous and chunk_width divides the cycle count, so the range is
@@ -754,28 +691,10 @@ extern "C" int32_t jolt_dory_hints_onehot(jolt_ctx* ctx, const jolt_srs* srs, co
     G1Jac* dst = (G1Jac*)dory_host::g1_view(ctx, out, out_first, total);
     JOLT_REQUIRE(ctx, dst, "out is not a G1 view of this context that holds the hints");
     if (total == 0) return JOLT_OK;
-    hipStream_t st = ctx->stream;
-    size_t batch = batch_points ? batch_points / chunk_width : std::max<size_t>(1, ((size_t)1 << 26) / chunk_width);
+    size_t batch = batch_points ? batch_points / chunk_width : std::max<size_t>(1, kMaxBatchKeys / chunk_width);
     batch = std::min(std::min(batch, windows), (size_t)0xFFFFFFFFu / ((size_t)K + 1));  // bucket slots are u32
     if (batch == 0) return JOLT_ERR_UNSUPPORTED;
-    for (size_t v0 = 0; v0 < windows; v0 += batch) {
-        const size_t V = std::min(batch, windows - v0), nvals = V * chunk_width;
-        BucketPlan p = plan_buckets(V, K, chunk_width);
-        Workspace w;
-        JOLT_TRY(carve(ctx, V, chunk_width, K, p.heavy_cap, 0, &w, V * K));
-        const size_t VB = V * ((size_t)K + 1);
-        hipError_t e = hipMemsetAsync(w.hist, 0, VB * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(w.hcnt, 0, 256, st);
-        if (e == hipSuccess) e = hipMemsetAsync(w.buckets, 0, VB * sizeof(G1Jac), st);  // z = 0: identity
-        if (e != hipSuccess) return hip_fail(ctx, "dory one-hot hints", e);
-        const uint8_t* idx = source->idx + ((first_poly * source->cycles + v0 * chunk_width) << source->wide);
-        hipLaunchKernelGGL(k_onehot_keys, dim3((unsigned)((nvals + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, idx, source->wide, nvals, (uint32_t)wl, K, w.keys, w.hist);
-        launch_bucket_sums(ctx, w, srs->pts, V, chunk_width, K, p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = dory_hints::launch_normalise(st, (const G1Jac*)w.buckets, dory_hints::OneHotMap{K, chunks, v0}, V * K, w.pool, dst);
-        if (e != hipSuccess) return hip_fail(ctx, "dory one-hot hints", e);
-    }
-    return JOLT_OK;
+    return bucket_batches(ctx, srs->pts, "dory one-hot hints", OneHotSource{source, first_poly, wl, windows, batch}, OneHotToView{dst, K, chunks});
 }
 
 // k_dory_hints_normalise on the host, for the suite: lane r owns the points [r * run, (r + 1) * run) (on the device a lane's points are interleaved with its neighbours';
@@ -889,14 +808,11 @@ extern "C" int32_t jolt_dory_hints_rows_am(jolt_ctx* ctx, const jolt_srs* srs, c
     hipError_t e = hipGetLastError();
     int32_t rc = e == hipSuccess ? JOLT_OK : hip_fail(ctx, "dory address-major rows", e);
     if (rc == JOLT_OK) {
-        jolt_srs strided;
-        strided.ctx = ctx;
-        strided.pts = compact;
-        strided.n = C;
         // Rows of C = 2^8 or 2^9 values would get 8 or 16 buckets per window: one bucket per lane leaves most of a wavefront idle in the bucket sums and the row fold
         // (measured 25 ms per column at T = 2^20).  Digits of up to 7 bits fill the 64 lanes; rows shorter than 2^4 keep the rule.
         const int wl = (int)(sigma - log_block);
-        rc = commit_rows_into(ctx, &strided, values, C, wl, rows, RowsToView{dst}, std::min(7, wl - 1));
+        IntMagnitudes mags{values};
+        rc = commit_rows_into(ctx, compact, "dory address-major rows", mags, wl, rows, RowsToView{dst}, std::min(7, wl - 1));
     }
     jolt_internal_dev_free(ctx, compact);  // back to the pool: reuse is stream-ordered
     return rc;
@@ -1193,79 +1109,107 @@ __global__ __launch_bounds__(kBlock) void k_dory_combine_horner(const G1Jac* __r
 
 }  // namespace
 
+namespace {
+
+// What the two grid folds share ahead of their kernels.  The limits, the sources and the dense tables into `a` (*T cycles each, *total one-hot polynomials), the
+// canonical-scalar checks, in the order the refusal tests pin; shape(T, &left_len) is the entry's own derivation, run once T is known: it refuses what its placement
+// cannot take and states the length `left` has to have.  The grid has 2^log_k addresses per cycle.
+template <class Shape>
+int32_t fold_gather(jolt_ctx* ctx, const jolt_onehot* const* sources, size_t n_sources, const jolt_fr_t* onehot_scalars, jolt_table* const* dense, size_t n_dense,
+                    const jolt_fr_t* dense_scalars, uint32_t log_k, const jolt_table* left, Shape&& shape, FoldArgs* a, size_t* T, size_t* total) {
+    if (n_sources > (size_t)kFoldMaxSources || n_dense > (size_t)kFoldMaxDense || log_k > 8 || n_sources + n_dense == 0) return JOLT_ERR_UNSUPPORTED;
+    const uint32_t K = 1u << log_k;
+    std::memset(a, 0, sizeof(*a));
+    for (size_t s = 0; s < n_sources; ++s) if (!sources[s]) return JOLT_ERR_INVALID_ARG;
+    for (size_t d = 0; d < n_dense; ++d) if (!dense[d]) return JOLT_ERR_INVALID_ARG;
+    *T = n_sources ? sources[0]->cycles : dense[0]->len;
+    size_t left_len = 0;
+    JOLT_TRY(shape(*T, &left_len));
+    *total = 0;
+    for (size_t s = 0; s < n_sources; ++s) {
+        if (sources[s]->cycles != *T) return JOLT_ERR_SIZE_MISMATCH;
+        JOLT_REQUIRE(ctx, sources[s]->k <= K, "fold_rows: a hot address outside the grid");
+        a->idx[s] = sources[s]->idx;
+        a->wide[s] = sources[s]->wide;
+        a->n_polys[s] = (uint32_t)sources[s]->n_polys;
+        a->first[s] = (uint32_t)*total;
+        *total += sources[s]->n_polys;
+    }
+    a->n_sources = (int)n_sources;
+    for (size_t d = 0; d < n_dense; ++d) {
+        if (dense[d]->len != *T) return JOLT_ERR_SIZE_MISMATCH;
+        a->dense[d] = dense[d]->data();
+        a->dense_scalar[d] = fr_from_abi(&dense_scalars[d]);
+        JOLT_REQUIRE(ctx, fr_is_canonical(a->dense_scalar[d]), "scalar is not a canonical Fr");
+    }
+    a->n_dense = (int)n_dense;
+    if (left->len != left_len) return JOLT_ERR_SIZE_MISMATCH;
+    for (size_t p = 0; p < *total; ++p) JOLT_REQUIRE(ctx, fr_is_canonical(fr_from_abi(&onehot_scalars[p])), "scalar is not a canonical Fr");
+    return JOLT_OK;
+}
+
+// ... and behind them: the result table of 2^sigma columns, the one-hot scalars on the device, then launch(scalars, dst, groups) -- the entry's kernel over `groups`
+// column groups, writing `slices` partial tables into dst, which k_dory_fold_sum adds when there is more than one.  Everything is released in one place and *out is
+// written only on success.
+template <class Launch>
+int32_t fold_finish(jolt_ctx* ctx, const jolt_fr_t* onehot_scalars, size_t total, uint32_t sigma, size_t slices, Launch&& launch, jolt_table** out) {
+    const size_t cols = (size_t)1 << sigma, groups = (cols + kBlock - 1) / kBlock;
+    jolt_table *r = nullptr, *ds = nullptr;
+    Fr* partial = nullptr;
+    JOLT_TRY(jolt_internal_table_new(ctx, cols, &r));
+    int32_t st = total ? jolt_table_upload(ctx, onehot_scalars, total, &ds) : JOLT_OK;  // synchronises: the caller's array may be short-lived
+    if (st == JOLT_OK && slices * groups > 0x7FFFFFFFull) st = JOLT_ERR_UNSUPPORTED;
+    if (st == JOLT_OK && slices > 1) st = jolt_internal_dev_alloc(ctx, slices * cols * sizeof(Fr), (void**)&partial);
+    if (st == JOLT_OK) {
+        launch(ds ? (const Fr*)ds->data() : (const Fr*)nullptr, partial ? partial : r->data(), groups);
+        if (slices > 1) hipLaunchKernelGGL(k_dory_fold_sum, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, (const Fr*)partial, cols, (uint32_t)slices, r->data());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            ctx->last_error = hipGetErrorString(e);
+            st = JOLT_ERR_HIP;
+        }
+    }
+    if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered
+    if (ds) jolt_table_free(ctx, ds);
+    if (st != JOLT_OK) {
+        jolt_table_free(ctx, r);
+        return st;
+    }
+    *out = r;
+    return JOLT_OK;
+}
+
+}  // namespace
+
 extern "C" int32_t jolt_dory_fold_rows_grid(jolt_ctx* ctx, const jolt_onehot* const* sources, size_t n_sources, const jolt_fr_t* onehot_scalars,
                                             jolt_table* const* dense, size_t n_dense, const jolt_fr_t* dense_scalars, uint32_t log_k, uint32_t sigma,
                                             const jolt_table* left, jolt_table** out) {
     if (!ctx || !out || !left || (n_sources && (!sources || !onehot_scalars)) || (n_dense && (!dense || !dense_scalars))) return JOLT_ERR_INVALID_ARG;
-    if (n_sources > (size_t)kFoldMaxSources || n_dense > (size_t)kFoldMaxDense || log_k > 8 || n_sources + n_dense == 0) return JOLT_ERR_UNSUPPORTED;
-    const uint32_t K = 1u << log_k;
     FoldArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (size_t s = 0; s < n_sources; ++s) if (!sources[s]) return JOLT_ERR_INVALID_ARG;
-    for (size_t d = 0; d < n_dense; ++d) if (!dense[d]) return JOLT_ERR_INVALID_ARG;
-    const size_t T = n_sources ? sources[0]->cycles : dense[0]->len;
-    const int log_t = log2_exact(T);
-    JOLT_REQUIRE(ctx, log_t >= 0, "fold_rows: the cycle count must be a power of two");
-    JOLT_REQUIRE(ctx, sigma <= log_k + (uint32_t)log_t, "fold_rows: sigma exceeds the grid's variables");
-    size_t total = 0;
-    for (size_t s = 0; s < n_sources; ++s) {
-        if (sources[s]->cycles != T) return JOLT_ERR_SIZE_MISMATCH;
-        JOLT_REQUIRE(ctx, sources[s]->k <= K, "fold_rows: a hot address outside the grid");
-        a.idx[s] = sources[s]->idx;
-        a.wide[s] = sources[s]->wide;
-        a.n_polys[s] = (uint32_t)sources[s]->n_polys;
-        a.first[s] = (uint32_t)total;
-        total += sources[s]->n_polys;
-    }
-    a.n_sources = (int)n_sources;
-    for (size_t d = 0; d < n_dense; ++d) {
-        if (dense[d]->len != T) return JOLT_ERR_SIZE_MISMATCH;
-        a.dense[d] = dense[d]->data();
-        a.dense_scalar[d] = fr_from_abi(&dense_scalars[d]);
-        JOLT_REQUIRE(ctx, fr_is_canonical(a.dense_scalar[d]), "scalar is not a canonical Fr");
-    }
-    a.n_dense = (int)n_dense;
-    const uint32_t nu = log_k + (uint32_t)log_t - sigma;
-    if (left->len != (size_t)1 << nu) return JOLT_ERR_SIZE_MISMATCH;
-    for (size_t p = 0; p < total; ++p) JOLT_REQUIRE(ctx, fr_is_canonical(fr_from_abi(&onehot_scalars[p])), "scalar is not a canonical Fr");
-
-    const size_t cols = (size_t)1 << sigma;
-    jolt_table *r = nullptr, *ds = nullptr;
-    JOLT_TRY(jolt_internal_table_new(ctx, cols, &r));
-    int32_t st = JOLT_OK;
-    if (total) st = jolt_table_upload(ctx, onehot_scalars, total, &ds);  // synchronises: the caller's array may be short-lived
-    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
-    const Fr* d_scalars = ds ? (const Fr*)ds->data() : (const Fr*)nullptr;
-    Fr* partial = nullptr;
-    if (sigma <= (uint32_t)log_t) {
-        const size_t M = T >> sigma;
-        const uint32_t slice = (uint32_t)std::min<size_t>(M, kFoldSlice);
-        const size_t slices = M / slice, groups = (cols + kBlock - 1) / kBlock;
-        const size_t lds = (size_t)K * (slice + 1) * sizeof(Fr);
-        const uint32_t use_lds = lds <= 48 * 1024 ? 1u : 0u;
-        if (slices * groups > 0x7FFFFFFFull) { st = JOLT_ERR_UNSUPPORTED; }
-        Fr* dst = r->data();
-        if (st == JOLT_OK && slices > 1) {
-            st = jolt_internal_dev_alloc(ctx, slices * cols * sizeof(Fr), (void**)&partial);
-            dst = partial;
-        }
-        if (st == JOLT_OK) {
-            hipLaunchKernelGGL(k_dory_fold_cols, dim3((unsigned)(slices * groups)), dim3(kBlock), use_lds ? lds : 0, ctx->stream, a, d_scalars, (const Fr*)left->data(),
-                               (uint32_t)log_t, sigma, K, slice, (uint32_t)groups, use_lds, dst);
-            if (slices > 1)
-                hipLaunchKernelGGL(k_dory_fold_sum, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, (const Fr*)partial, cols, (uint32_t)slices, r->data());
-        }
-    } else {
-        hipLaunchKernelGGL(k_dory_fold_wide, dim3((unsigned)((cols + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, a, d_scalars, (const Fr*)left->data(),
-                           (uint32_t)log_t, sigma, K, r->data());
-    }
-    hipError_t e = st == JOLT_OK ? hipGetLastError() : hipSuccess;
-    if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered
-    if (ds) jolt_table_free(ctx, ds);
-    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
-    if (e != hipSuccess) { jolt_table_free(ctx, r); ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
-    *out = r;
-    return JOLT_OK;
+    size_t T, total;
+    int log_t = 0;
+    auto shape = [&](size_t cycles, size_t* left_len) -> int32_t {
+        log_t = log2_exact(cycles);
+        JOLT_REQUIRE(ctx, log_t >= 0, "fold_rows: the cycle count must be a power of two");
+        JOLT_REQUIRE(ctx, sigma <= log_k + (uint32_t)log_t, "fold_rows: sigma exceeds the grid's variables");
+        *left_len = (size_t)1 << (log_k + (uint32_t)log_t - sigma);  // 2^nu matrix rows
+        return JOLT_OK;
+    };
+    JOLT_TRY(fold_gather(ctx, sources, n_sources, onehot_scalars, dense, n_dense, dense_scalars, log_k, left, shape, &a, &T, &total));
+    const uint32_t K = 1u << log_k;
+    const Fr* lv = (const Fr*)left->data();
+    if (sigma > (uint32_t)log_t)
+        return fold_finish(ctx, onehot_scalars, total, sigma, 1, [&](const Fr* scalars, Fr* dst, size_t groups) {
+            hipLaunchKernelGGL(k_dory_fold_wide, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, a, scalars, lv, (uint32_t)log_t, sigma, K, dst);
+        }, out);
+    const size_t M = T >> sigma;
+    const uint32_t slice = (uint32_t)std::min<size_t>(M, kFoldSlice);
+    const size_t slices = M / slice, lds = (size_t)K * (slice + 1) * sizeof(Fr);
+    const uint32_t use_lds = lds <= 48 * 1024 ? 1u : 0u;
+    return fold_finish(ctx, onehot_scalars, total, sigma, slices, [&](const Fr* scalars, Fr* dst, size_t groups) {
+        hipLaunchKernelGGL(k_dory_fold_cols, dim3((unsigned)(slices * groups)), dim3(kBlock), use_lds ? lds : 0, ctx->stream, a, scalars, lv, (uint32_t)log_t, sigma, K, slice,
+                           (uint32_t)groups, use_lds, dst);
+    }, out);
 }
 
 extern "C" int32_t jolt_dory_fold_rows_grid_am(jolt_ctx* ctx, const jolt_onehot* const* sources, size_t n_sources, const jolt_fr_t* onehot_scalars,
@@ -1274,65 +1218,21 @@ extern "C" int32_t jolt_dory_fold_rows_grid_am(jolt_ctx* ctx, const jolt_onehot*
     if (!ctx || !out || !left || (n_sources && (!sources || !onehot_scalars)) || (n_dense && (!dense || !dense_scalars))) return JOLT_ERR_INVALID_ARG;
     size_t C;
     JOLT_TRY(am_shape(ctx, sigma, log_block, log_stride, &C));
-    if (n_sources > (size_t)kFoldMaxSources || n_dense > (size_t)kFoldMaxDense || log_block - log_stride > 8 || n_sources + n_dense == 0) return JOLT_ERR_UNSUPPORTED;
-    const uint32_t K = 1u << (log_block - log_stride);
     FoldArgs a;
-    std::memset(&a, 0, sizeof(a));
-    for (size_t s = 0; s < n_sources; ++s) if (!sources[s]) return JOLT_ERR_INVALID_ARG;
-    for (size_t d = 0; d < n_dense; ++d) if (!dense[d]) return JOLT_ERR_INVALID_ARG;
-    const size_t T = n_sources ? sources[0]->cycles : dense[0]->len;
-    JOLT_REQUIRE(ctx, T % C == 0, "address-major: the cycles per row do not divide the cycle count");
-    const size_t rows = T / C;
-    size_t total = 0;
-    for (size_t s = 0; s < n_sources; ++s) {
-        if (sources[s]->cycles != T) return JOLT_ERR_SIZE_MISMATCH;
-        JOLT_REQUIRE(ctx, sources[s]->k <= K, "fold_rows: a hot address outside the grid");
-        a.idx[s] = sources[s]->idx;
-        a.wide[s] = sources[s]->wide;
-        a.n_polys[s] = (uint32_t)sources[s]->n_polys;
-        a.first[s] = (uint32_t)total;
-        total += sources[s]->n_polys;
-    }
-    a.n_sources = (int)n_sources;
-    for (size_t d = 0; d < n_dense; ++d) {
-        if (dense[d]->len != T) return JOLT_ERR_SIZE_MISMATCH;
-        a.dense[d] = dense[d]->data();
-        a.dense_scalar[d] = fr_from_abi(&dense_scalars[d]);
-        JOLT_REQUIRE(ctx, fr_is_canonical(a.dense_scalar[d]), "scalar is not a canonical Fr");
-    }
-    a.n_dense = (int)n_dense;
-    if (left->len != rows) return JOLT_ERR_SIZE_MISMATCH;
-    for (size_t p = 0; p < total; ++p) JOLT_REQUIRE(ctx, fr_is_canonical(fr_from_abi(&onehot_scalars[p])), "scalar is not a canonical Fr");
-
-    const size_t cols = (size_t)1 << sigma;
-    jolt_table *r = nullptr, *ds = nullptr;
-    JOLT_TRY(jolt_internal_table_new(ctx, cols, &r));
-    int32_t st = JOLT_OK;
-    if (rows == 0) st = JOLT_ERR_SIZE_MISMATCH;
-    if (st == JOLT_OK && total) st = jolt_table_upload(ctx, onehot_scalars, total, &ds);  // synchronises: the caller's array may be short-lived
-    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
-    const Fr* d_scalars = ds ? (const Fr*)ds->data() : (const Fr*)nullptr;
-    Fr* partial = nullptr;
+    size_t T, total, rows = 0;
+    auto shape = [&](size_t cycles, size_t* left_len) -> int32_t {
+        JOLT_REQUIRE(ctx, cycles % C == 0, "address-major: the cycles per row do not divide the cycle count");
+        *left_len = rows = cycles / C;
+        return JOLT_OK;
+    };
+    JOLT_TRY(fold_gather(ctx, sources, n_sources, onehot_scalars, dense, n_dense, dense_scalars, log_block - log_stride, left, shape, &a, &T, &total));
+    if (rows == 0) return JOLT_ERR_SIZE_MISMATCH;
     const uint32_t slice = (uint32_t)std::min<size_t>(rows, kAmFoldSlice);
-    const size_t slices = (rows + slice - 1) / slice, groups = (cols + kBlock - 1) / kBlock;
-    if (slices * groups > 0x7FFFFFFFull) st = JOLT_ERR_UNSUPPORTED;
-    Fr* dst = r->data();
-    if (st == JOLT_OK && slices > 1) {
-        st = jolt_internal_dev_alloc(ctx, slices * cols * sizeof(Fr), (void**)&partial);
-        dst = partial;
-    }
-    if (st == JOLT_OK) {
-        hipLaunchKernelGGL(k_dory_am_fold, dim3((unsigned)(slices * groups)), dim3(kBlock), 0, ctx->stream, a, d_scalars, (const Fr*)left->data(), T, rows, log_block,
-                           log_stride, sigma, slice, (uint32_t)groups, dst);
-        if (slices > 1) hipLaunchKernelGGL(k_dory_fold_sum, dim3((unsigned)groups), dim3(kBlock), 0, ctx->stream, (const Fr*)partial, cols, (uint32_t)slices, r->data());
-    }
-    hipError_t e = st == JOLT_OK ? hipGetLastError() : hipSuccess;
-    if (partial) jolt_internal_dev_free(ctx, partial);  // back to the pool: reuse is stream-ordered
-    if (ds) jolt_table_free(ctx, ds);
-    if (st != JOLT_OK) { jolt_table_free(ctx, r); return st; }
-    if (e != hipSuccess) { jolt_table_free(ctx, r); ctx->last_error = hipGetErrorString(e); return JOLT_ERR_HIP; }
-    *out = r;
-    return JOLT_OK;
+    const size_t slices = (rows + slice - 1) / slice;
+    return fold_finish(ctx, onehot_scalars, total, sigma, slices, [&](const Fr* scalars, Fr* dst, size_t groups) {
+        hipLaunchKernelGGL(k_dory_am_fold, dim3((unsigned)(slices * groups)), dim3(kBlock), 0, ctx->stream, a, scalars, (const Fr*)left->data(), T, rows, log_block, log_stride,
+                           sigma, slice, (uint32_t)groups, dst);
+    }, out);
 }
 
 // ---- fold_rows of dense field tables, whole or block-embedded ----------------------------------------------------------------

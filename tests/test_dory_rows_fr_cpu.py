@@ -96,6 +96,17 @@ def test_plan_covers_the_bit_length_and_fits_the_row_fold(log_width):
     assert ffi.host_dory_rows_fr_plan(254, 1) == (6, 43)
 
 
+def test_plan_is_the_integer_rows_rule_for_integer_magnitudes():
+    """The integer rows (jolt_dory_commit_rows / _hints_rows) take their windows from this plan and keep no rule of their own: for every bit length an integer
+    magnitude has and every row width up to 2^14 it gives c = clamp(wl - 4, 3, 13), W = (bits + c) // c, and never more windows than the row fold holds."""
+    for wl in range(0, 15):
+        for bits in range(1, 129):
+            c = min(max(wl - 4, 3), 13)
+            W = (bits + c) // c
+            assert ffi.host_dory_rows_fr_plan(bits, 1 << wl) == (c, W), (bits, wl)
+            assert W <= MAX_WINDOWS
+
+
 def test_plan_refusals():
     lib = ffi.lib()
     c, W = C.c_int32(-1), C.c_int32(-1)

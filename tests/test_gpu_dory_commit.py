@@ -126,7 +126,9 @@ def test_onehot_hints_16_bit_indices(ctx, srs):
 
 
 def test_onehot_hints_in_forced_batches(ctx, srs):
-    """12 windows in launch sets of 3: the cuts fall inside a column and a launch set spans two columns"""
+    """12 windows in launch sets of 3: the cuts fall inside a column and a launch set spans two columns.  The loop these cuts drive (bucket_batches,
+    jolt_amd/csrc/dory_batches.hip.h) is also the one under jolt_dory_commit_onehot, whose own cut -- 2^26 / chunk_width chunks, no parameter moves it -- no test of
+    a sensible size can reach: what changes there beside the batch length is the sink, which every host-entry comparison of this file runs."""
     beta, dev_srs = srs
     k, cycles, width, cols, empty_row = 16, 128, 32, 3, 3
     chunks = cycles // width
@@ -182,6 +184,36 @@ def test_rows_hints_all_kinds(ctx, srs):
     assert all(np.array_equal(e, IDENT) for e in out.download())
     out.free()
     zeros.free()
+
+
+def test_rows_hints_across_the_key_cut(ctx):
+    """Integer rows into a resident view in more than one batch: 1024 rows x 4096 i128 values (the shape of tests/test_gpu_dory.py::test_rows_multiple_batches) with
+    one value of magnitude 2^127, so the magnitudes take 128 bits, c = 8 gives 17 windows and a batch holds 2^26 // (17 * 4096) = 963 rows: the cut falls at row 963.
+    Every row of the view equals the row jolt_dory_commit_rows gives for the same values; rows 0, 962, 963 and 1023 -- both sides of the cut -- equal p_row(beta) G."""
+    beta = rand_fr(1, 1406)[0]
+    width, rows = 1 << 12, 1 << 10
+    dev_srs = ctx.srs_setup_from_secret(beta, width, O.g1_generator())
+    rng = np.random.default_rng(1407)
+    packed = np.stack([rng.integers(0, 2**64, size=rows * width, dtype=np.uint64) for _ in range(2)], axis=1)
+    packed[5 * width + 9] = (0, 2**63)  # i128::MIN
+    assert (2**26) // (17 * width) == 963 < rows
+    ints = ctx.ints(packed, "i128")
+    out = ctx.dory_state_alloc(ffi.DORY_KIND_G1, rows)
+    assert ctx.dory_hints_rows(dev_srs, ints, width, out) == rows
+    got = out.download()
+    ref = ctx.dory_commit_rows(dev_srs, ints, width)
+    assert ref.shape[0] == rows
+    for r in range(rows):
+        assert np.array_equal(got[r, 8:12], ONE) and O.g1_eq(got[r], ref[r]), r
+
+    def as_int(r, j):
+        v = int(packed[r * width + j, 0]) | (int(packed[r * width + j, 1]) << 64)
+        return v - (1 << 128) if v >> 127 else v
+    for r in (0, 962, 963, 1023):
+        assert_hint_element(got[r], eval_point(beta, [as_int(r, j) for j in range(width)]), r)
+    out.free()
+    ints.free()
+    dev_srs.free()
 
 
 # ------------------------------------------------------------------------------------------------------ refusals
