@@ -615,7 +615,7 @@ int32_t jolt_dory_commit_onehot(jolt_ctx *ctx, const jolt_srs *srs, const jolt_o
 /* The G1 and Fr work of a Dory opening ahead of the pairing rounds.  Cycle-major placement (TracePolynomialOrder::CycleMajor): grid
  * index k*T + j, dense columns at k = 0, as for the jolt_grid_* entry points below (the address-major twins are jolt_dory_*_am further down).  The tier-2 multi-pairing and the multi-pairings of the reduce-and-fold rounds of
  * dory::prove are jolt_dory_multi_pair / jolt_dory_multi_pair_g2_setup below, the rounds' group routines jolt_dory_g1_* / jolt_dory_g2_*; what stays on the host is
- * GT scalings, the transcript, the control flow and commit_blind.
+ * the transcript, the control flow and commit_blind (the verifier's GT scalings are jolt_dory_gt_multi_exp, further down).
  *
  * RlcSource::fold_rows over TraceOpeningPoly (optimized/opening.rs:491-510, multilinear.rs:452-462), cycle-major -- the
  * vector_matrix_product of dory::prove (crates/jolt-dory/src/scheme.rs:612-618), answered from the per-cycle columns without the K x T grid:
@@ -640,8 +640,8 @@ int32_t jolt_host_dory_combine_row(const jolt_g1_t *points, const jolt_fr_t *sca
 /* The group and field routines of dory::prove's reduce-and-fold rounds: dory's DoryRoutines seam as the reference implements it for both groups,
  * JoltG1Routines (crates/jolt-dory/src/routines.rs:60-97) and JoltG2Routines (:101-147).  Host pointers in and out, like jolt_dory_combine_hints: the trait works
  * on host slices and the pairings need the vectors on the host every round.  `vs` / `left` are updated in place.  Results are the reference's group elements; the
- * Jacobian representative is free, the identity comes back as (1, 1, 0).  The rounds' multi-pairings are jolt_dory_multi_pair below; GT scalings and the control flow of
- * dory::prove stay with the caller.
+ * Jacobian representative is free, the identity comes back as (1, 1, 0).  The rounds' multi-pairings are jolt_dory_multi_pair below; the control flow of
+ * dory::prove stays with the caller (GT scalings, which only a verifier needs, are jolt_dory_gt_multi_exp).
  * Every entry refuses with JOLT_ERR_INVALID_ARG: a null pointer with n > 0, a scalar that is not canonical, a point whose coordinates are not canonical or that
  * is not on its curve.  For G2 that is the twist equation ONLY -- there is NO subgroup check (the twist has cofactor 2q - r); the routines are group-law
  * identities on the whole twist, so a point outside the order-r subgroup gets the answer the same formulas give on the CPU.  A refused call enqueues nothing,
@@ -719,7 +719,7 @@ int32_t jolt_host_g2_prepare_one(const jolt_g2_t *g2, jolt_fq2_t *lines /* 3 * J
 int32_t jolt_host_miller_loop(const jolt_g1_t *g1s, const jolt_g2_t *g2s, size_t n, jolt_gt_t *out);
 /* f^((p^12 - 1) / r * 2 z (6 z^2 + 3 z + 1)); zero is JOLT_ERR_NOT_INVERTIBLE */
 int32_t jolt_host_final_exponentiation(const jolt_gt_t *f, jolt_gt_t *out);
-/* gt^scalar by square-and-multiply over the canonical scalar: the GT scaling that stays with the caller */
+/* gt^scalar by square-and-multiply over the canonical scalar: the host form of jolt_dory_gt_pow_many's powers (any canonical Fq12 is a valid base) */
 int32_t jolt_host_gt_pow(const jolt_gt_t *gt, const jolt_fr_t *scalar, jolt_gt_t *out);
 
 /* Dory's reduce-and-fold rounds on vectors that stay on the device.  A jolt_dory_vec is a device array of G1 points, G2 points or Fr elements from the context's
@@ -948,7 +948,8 @@ int32_t jolt_dory_round_update(jolt_ctx *ctx, int32_t mode, jolt_dory_vec *v1, s
  * challenges_out (beta_k, alpha_k) per round and then gamma.  GT values are the canonical values of jolt_dory_products, points as its MSM results and the in-place
  * routines leave them (the identity as (1, 1, 0)).  On every exit, an abort included, the streams are drained before the state vectors go back to the pool, and
  * the context stays usable; the inputs stay the caller's. */
-enum { JOLT_DORY_PHASE_VMV = 0, JOLT_DORY_PHASE_FIRST = 1, JOLT_DORY_PHASE_SECOND = 2, JOLT_DORY_PHASE_GAMMA = 3, JOLT_DORY_PHASE_FINAL = 4 };
+enum { JOLT_DORY_PHASE_VMV = 0, JOLT_DORY_PHASE_FIRST = 1, JOLT_DORY_PHASE_SECOND = 2, JOLT_DORY_PHASE_GAMMA = 3, JOLT_DORY_PHASE_FINAL = 4,
+       JOLT_DORY_PHASE_D = 5 /* the verifier's last challenge (jolt_host_dory_verify_with_transcript): no elements; the prover's side never sends it */ };
 typedef int32_t (*jolt_dory_transcript_fn)(void *user, int32_t phase, size_t round, const jolt_gt_t *gts, size_t n_gt, const jolt_g1_t *g1s, size_t n_g1,
                                            const jolt_g2_t *g2s, size_t n_g2, jolt_fr_t *challenge_out);
 int32_t jolt_host_dory_open_with_transcript(jolt_ctx *ctx, const jolt_dory_setup *setup, const jolt_dory_vec *const *hints, const size_t *hint_first,
@@ -1019,6 +1020,79 @@ int32_t jolt_host_gt_serialize(const jolt_gt_t *f, uint8_t out[384]);
 int32_t jolt_host_dory_transcript_append_gt(jolt_host_transcript *t, const jolt_gt_t *element);
 int32_t jolt_host_dory_transcript_append_g1(jolt_host_transcript *t, const jolt_g1_t *element);
 int32_t jolt_host_dory_transcript_append_g2(jolt_host_transcript *t, const jolt_g2_t *element);
+
+/* Dory verification (dory_verify.hip): GT multi-exponentiation on the device, the verifier's precomputed GT values, DoryScheme::verify
+ * (crates/jolt-dory/src/scheme.rs:277-308) and HomomorphicBatch::verify_batch (crates/jolt-openings/src/schemes.rs:526-551) as one call each.  The protocol is the
+ * transparent Eval-VMV-RE of the entries above; its verifier is the one tests/dory_open_model.py states in log space. */
+/* outs[i] = gts[i]^scalars[i]: n independent powers in one launch (k_gt_pow: one lane per element, 254 uniform steps of the GENERAL Fq12 squaring and
+ * multiplication, so any canonical Fq12 is a valid base -- no cyclotomic shortcut).  Host pointers in and out.  Refusals as jolt_dory_multi_pair:
+ * JOLT_ERR_INVALID_ARG for a null pointer with n > 0, a coordinate or a scalar that is not canonical; JOLT_ERR_UNSUPPORTED for n > 2^20; a refused call enqueues
+ * nothing and writes nothing.  Values are canonical Montgomery words: bit for bit jolt_host_gt_pow's. */
+int32_t jolt_dory_gt_pow_many(jolt_ctx *ctx, const jolt_gt_t *gts, const jolt_fr_t *scalars, size_t n, jolt_gt_t *outs);
+/* DoryScheme::combine (scheme.rs:313-323): out = prod_i gts[i]^scalars[i], the powers as above and their product by the halving tree of the multi-pairings
+ * (k_tree_level<Fq12, MulFq12>); n = 0 gives one.  Bit for bit the product of jolt_host_gt_pow's values under jolt_host_fq12_op(MUL). */
+int32_t jolt_dory_gt_multi_exp(jolt_ctx *ctx, const jolt_gt_t *gts, const jolt_fr_t *scalars, size_t n, jolt_gt_t *out);
+/* The GT values a verifier holds for a setup of n = 2^s bases (DoryVerifierSetup, crates/jolt-dory/src/types.rs), 3 s + 4 of them in this order:
+ *   chi_k    = e(Gamma1[:n_k], Gamma2[:n_k]),  n_k = n / 2^k,  k = 0 ... s
+ *   Delta1R_k = e(Gamma1[h:n_k], Gamma2[:h]),  h = n_k / 2,    k < s
+ *   Delta2R_k = e(Gamma1[:h], Gamma2[h:n_k]),                  k < s
+ *   HT = e(H1, H2),  e(H1, Gamma2[0]),  e(Gamma1[0], H2)
+ * (Delta1L_k = Delta2L_k = chi_{k+1}).  All from ONE jolt_dory_products batch of PAIR items over the setup's resident vectors.  A proof with sigma < s uses levels
+ * s - sigma ... s: the tables are prefixes.  The object belongs to the context of its setup and is freed on it. */
+typedef struct jolt_dory_verifier_setup jolt_dory_verifier_setup;
+int32_t jolt_dory_verifier_setup_create(jolt_ctx *ctx, const jolt_dory_setup *setup, jolt_dory_verifier_setup **out);
+int32_t jolt_dory_verifier_setup_free(jolt_ctx *ctx, jolt_dory_verifier_setup *vs);
+int32_t jolt_dory_verifier_setup_values(const jolt_dory_verifier_setup *vs, jolt_gt_t *out /* 3 log2(n) + 4 */);
+/* Measurement aid of tools/bench_dory_verify.py, as jolt_dory_pairing_timing: the wall milliseconds of the phases of the last verification made with `vs` while timing
+ * was on -- checks, replay, the folds of s1 / s2 and the exponents (host); the group folds (one batch of MSM items); the pairings with their final exponentiations
+ * (one batch of PAIR items); the multi-exponentiation.  jolt_dory_gt_pow_many and jolt_dory_gt_multi_exp report into jolt_dory_pairing_timing's clock: checks,
+ * host -> device, -, the power kernel (in the Miller kernel's place), the product tree, device -> host, -. */
+int32_t jolt_dory_verifier_setup_timing(const jolt_dory_verifier_setup *vs, int32_t enable, double *out_ms /* 4 */);
+/* an independent copy of a transcript in its current state (the verifier draws d from one) */
+int32_t jolt_host_transcript_clone(const jolt_host_transcript *t, jolt_host_transcript **out);
+/* Every exponent of the verifier's final equation, in Fr on the host.  challenges: (beta_k, alpha_k) per round, then gamma; s1, s2: the folded scalars (single
+ * elements).  With d1_0 = the commitment, d2_0 = the VMV message's D2 and the recurrences
+ *   c_{k+1} = c_k chi_k d2_k^beta d1_k^(1/beta) C+^alpha C-^(1/alpha),  d1_{k+1} = (D1L chi_{k+1}^beta)^alpha D1R Delta1R_k^beta,
+ *   d2_{k+1} = (D2L chi_{k+1}^(1/beta))^(1/alpha) D2R Delta2R_k^(1/beta)
+ * the right-hand side  chi_sigma c_sigma HT^(s1 s2) (d2_sigma e(Gamma1[0], H2)^(s2 / gamma))^d (d1_sigma e(H1, Gamma2[0])^(gamma s1))^(1/d)  is one product of powers:
+ *   exp_proof_gt    2 + 6 sigma, the proof's GT elements in proof order (C, D2, then per round D1L, D1R, D2L, D2R, C+, C-)
+ *   exp_commitment  one
+ *   exp_setup       3 sigma + 4, in the order of jolt_dory_verifier_setup_values for a setup of 2^sigma bases
+ * and the folds of the group elements are E1' = sum coef_g1 * (E1, then E1beta, E1+, E1- per round), E2' = coef_h2 * H2 + sum coef_g2 * (E2beta, E2+, E2- per round).
+ * JOLT_ERR_INVALID_ARG: a null pointer, sigma > 30, a value that is not canonical; JOLT_ERR_NOT_INVERTIBLE: a zero challenge or d. */
+int32_t jolt_host_dory_verify_exponents(uint32_t sigma, const jolt_fr_t *challenges, const jolt_fr_t *d, const jolt_fr_t *s1, const jolt_fr_t *s2, const jolt_fr_t *y,
+                                        jolt_fr_t *exp_proof_gt, jolt_fr_t *exp_commitment, jolt_fr_t *exp_setup, jolt_fr_t *coef_g1, jolt_fr_t *coef_g2,
+                                        jolt_fr_t *coef_h2);
+/* DoryScheme::verify as one call.  commitment: the tier-2 commitment; y: the claimed evaluation L^T M R; left (2^nu) and right (2^sigma) host arrays; gts, g1s, g2s as
+ * jolt_host_dory_open wrote them.  The call
+ *   1. replays the transcript: `fn` is called phase by phase with the proof's elements in jolt_host_dory_open's order and returns beta_k, alpha_k, gamma; then once more
+ *      with JOLT_DORY_PHASE_D (no elements) for d.  The prover's side never sends PHASE_D.  A zero challenge is JOLT_ERR_NOT_INVERTIBLE;
+ *   2. folds s1 from `right` under alpha and s2 from `left` (padded with zeros) under 1 / alpha, on the host;
+ *   3. computes every exponent (jolt_host_dory_verify_exponents);
+ *   4. folds the group elements: E1', E2', w1 + d Gamma1[0], w2 + Gamma2[0] / d, -gamma H1, -E1' / gamma, as one jolt_dory_products batch of MSM items;
+ *   5. checks (VMV) e(E1, H2) = D2 and (final) e(w1 + d Gamma1[0], w2 + Gamma2[0] / d) e(-gamma H1, E2') e(-E1' / gamma, H2) = ONE jolt_dory_gt_multi_exp over the
+ *      proof's GT elements, the commitment and the setup values; both left-hand sides are PAIR items of one product batch.
+ * *accepted = 1 only if both checks hold; a rejected proof is JOLT_OK with *accepted = 0 and *failed_check = 1 (VMV) or 2 (final), 0 when accepted.  Status codes are
+ * for malformed input -- JOLT_ERR_INVALID_ARG for a null pointer, a value that is not canonical, a point off its curve, nu > sigma, sigma > 30, a setup of another
+ * context or a verifier setup of another setup's size -- and JOLT_ERR_SRS_TOO_SMALL; everything is checked before the transcript absorbs anything. */
+int32_t jolt_host_dory_verify_with_transcript(jolt_ctx *ctx, const jolt_dory_verifier_setup *vs, const jolt_dory_setup *setup, const jolt_gt_t *commitment,
+                                              const jolt_fr_t *y, const jolt_fr_t *left, const jolt_fr_t *right, uint32_t nu, uint32_t sigma, const jolt_gt_t *gts,
+                                              const jolt_g1_t *g1s, const jolt_g2_t *g2s, jolt_dory_transcript_fn fn, void *user, int32_t *accepted,
+                                              int32_t *failed_check);
+/* The same under one of the library's engines: elements absorbed as jolt_host_dory_open absorbs them; d is drawn from a COPY of the transcript taken after the final
+ * message, so the caller's transcript ends in exactly the state jolt_host_dory_open leaves the prover's in (the prover draws no d). */
+int32_t jolt_host_dory_verify(jolt_ctx *ctx, const jolt_dory_verifier_setup *vs, const jolt_dory_setup *setup, const jolt_gt_t *commitment, const jolt_fr_t *y,
+                              const jolt_fr_t *left, const jolt_fr_t *right, uint32_t nu, uint32_t sigma, const jolt_gt_t *gts, const jolt_g1_t *g1s,
+                              const jolt_g2_t *g2s, jolt_host_transcript *t, int32_t *accepted, int32_t *failed_check);
+/* HomomorphicBatch::<DoryScheme>::verify_batch (schemes.rs:526-551): the statement (jolt_host_opening_statement_absorb) gives gamma's powers and the joint
+ * evaluation; sigma = ceil(n_point / 2), nu = n_point - sigma, L = eq(point[:nu]), R = eq(point[nu:]) as jolt_host_dory_prove_batch splits the point; `combine` is
+ * not a separate pass -- commitment i enters the one multi-exponentiation with exponent gamma^i * exp_commitment; then the closing claim
+ * (jolt_host_opening_claim_absorb) on both outcomes.  The transcript ends in the state jolt_host_dory_prove_batch_blocks leaves.  The placement and the blocks do
+ * not appear: a verifier sees commitments, evaluations and the grid-order point.  n_claims = 0 is JOLT_ERR_INVALID_ARG; otherwise the codes of jolt_host_dory_verify. */
+int32_t jolt_host_dory_verify_batch(jolt_ctx *ctx, const jolt_dory_verifier_setup *vs, const jolt_dory_setup *setup, const jolt_gt_t *commitments,
+                                    const jolt_fr_t *evaluations, size_t n_claims, const jolt_fr_t *point, size_t n_point, const jolt_gt_t *gts,
+                                    const jolt_g1_t *g1s, const jolt_g2_t *g2s, jolt_host_transcript *t, int32_t *accepted, int32_t *failed_check,
+                                    jolt_fr_t *joint_eval_out);
 
 /* Promotion of device-resident integers (entries [offset, offset+len) of `values`) to a field table: Ring::from_u64 / from_i64 /
  * from_i128 per entry (crates/jolt-field/src/bn254/mod.rs:265-328), the From<T> of Polynomial<T>::bind_to_field (dense.rs:129-142)

@@ -19,6 +19,16 @@ struct jolt_dory_vec {
     void* data = nullptr;  // device, from the context's pool
 };
 
+// the object behind jolt_dory_setup (dory_scheme.hip makes and frees them; dory_verify.hip reads them too)
+struct jolt_dory_setup {
+    jolt_ctx* ctx = nullptr;
+    size_t n = 0;
+    jolt_dory_vec *gamma1 = nullptr, *gamma2 = nullptr, *h1_vec = nullptr, *h2_vec = nullptr;
+    jolt_g2_prepared* prepared = nullptr;
+    jolt_g1_t h1;
+    jolt_g2_t h2;
+};
+
 namespace jolt {
 namespace dory_host {
 
@@ -186,6 +196,9 @@ int32_t combine_enqueue(jolt_ctx* ctx, const void* d_points, const std::vector<u
 // elements [first, first + n) of a resident G1 vector of this context (dory_resident.hip, where jolt_dory_vec is defined): the device address (G1Jac), or null when the
 // vector is of another kind or context or the view leaves it -- for the entries of dory.hip that write their results into resident vectors
 void* g1_view(const jolt_ctx* ctx, const jolt_dory_vec* vec, size_t first, size_t n);
+
+// the transcript callback of the library's engines (dory_scheme.hip): `user` is a jolt_host_transcript
+int32_t engine_fn(void* user, int32_t phase, size_t round, const jolt_gt_t* gts, size_t n_gt, const jolt_g1_t* g1s, size_t n_g1, const jolt_g2_t* g2s, size_t n_g2, jolt_fr_t* challenge_out);
 
 }  // namespace dory_host
 }  // namespace jolt

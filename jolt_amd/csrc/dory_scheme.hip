@@ -24,15 +24,6 @@ using namespace jolt;
 using namespace jolt::dory_host;
 using namespace jolt::dory_dev;
 
-struct jolt_dory_setup {
-    jolt_ctx* ctx = nullptr;
-    size_t n = 0;
-    jolt_dory_vec *gamma1 = nullptr, *gamma2 = nullptr, *h1_vec = nullptr, *h2_vec = nullptr;
-    jolt_g2_prepared* prepared = nullptr;
-    jolt_g1_t h1;
-    jolt_g2_t h2;
-};
-
 namespace {
 
 template <class T>
@@ -383,17 +374,25 @@ int32_t open_impl(jolt_ctx* ctx, const jolt_dory_setup* setup, const jolt_dory_v
     return fn(user, JOLT_DORY_PHASE_FINAL, sigma, gts + n_gt, 0, g1s + n_g1, 1, g2s + n_g2, 1, &ignored);
 }
 
-// the library's engines behind the callback: every element as JoltToDoryTranscript::append_group, every challenge Transcript::challenge_scalar
-int32_t engine_fn(void* user, int32_t phase, size_t, const jolt_gt_t* gts, size_t n_gt, const jolt_g1_t* g1s, size_t n_g1, const jolt_g2_t* g2s, size_t n_g2, jolt_fr_t* challenge_out) {
+}  // namespace
+
+// the library's engines behind the callback: every element as JoltToDoryTranscript::append_group, every challenge Transcript::challenge_scalar.  The verifier's d
+// (JOLT_DORY_PHASE_D) comes from a COPY of the transcript: the caller's stays where the prover's is after the final message
+int32_t jolt::dory_host::engine_fn(void* user, int32_t phase, size_t, const jolt_gt_t* gts, size_t n_gt, const jolt_g1_t* g1s, size_t n_g1, const jolt_g2_t* g2s, size_t n_g2, jolt_fr_t* challenge_out) {
     jolt_host_transcript* t = (jolt_host_transcript*)user;
     for (size_t i = 0; i < n_gt; ++i) JOLT_TRY(jolt_host_dory_transcript_append_gt(t, &gts[i]));
     for (size_t i = 0; i < n_g1; ++i) JOLT_TRY(jolt_host_dory_transcript_append_g1(t, &g1s[i]));
     for (size_t i = 0; i < n_g2; ++i) JOLT_TRY(jolt_host_dory_transcript_append_g2(t, &g2s[i]));
     if (phase == JOLT_DORY_PHASE_FIRST || phase == JOLT_DORY_PHASE_SECOND || phase == JOLT_DORY_PHASE_GAMMA) return jolt_host_transcript_challenge(t, 1, challenge_out);
+    if (phase == JOLT_DORY_PHASE_D) {
+        jolt_host_transcript* copy = nullptr;
+        JOLT_TRY(jolt_host_transcript_clone(t, &copy));
+        const int32_t rc = jolt_host_transcript_challenge(copy, 1, challenge_out);
+        (void)jolt_host_transcript_destroy(copy);
+        return rc;
+    }
     return JOLT_OK;
 }
-
-}  // namespace
 
 extern "C" int32_t jolt_host_dory_open_with_transcript(jolt_ctx* ctx, const jolt_dory_setup* setup, const jolt_dory_vec* const* hints, const size_t* hint_first,
                                                        const size_t* hint_rows, size_t n_hints, const jolt_fr_t* scalars, const jolt_table* v_table, const jolt_table* left,

@@ -488,6 +488,11 @@ void Blake2bSpongeTranscript::state(uint8_t out[32]) const {
     Bridge copy = *bridge;
     copy.squeeze(out, 32);
 }
+Transcript* Blake2bSpongeTranscript::clone() const {
+    Blake2bSpongeTranscript* c = new Blake2bSpongeTranscript(*this);
+    c->bridge = std::make_shared<Bridge>(*bridge);
+    return c;
+}
 
 LabelledTranscript::LabelledTranscript(int kind, const uint8_t* label, size_t n) {
     if (n > 32) return;
@@ -1169,6 +1174,11 @@ extern "C" int32_t jolt_host_transcript_challenge(jolt_host_transcript* t, int32
     if (!t || !out) return JOLT_ERR_INVALID_ARG;
     fr_to_abi(out, full_width ? t->t.challenge_scalar() : t->t.challenge());
     return JOLT_OK;
+}
+extern "C" int32_t jolt_host_transcript_clone(const jolt_host_transcript* t, jolt_host_transcript** out) {
+    if (!t || !out) return JOLT_ERR_INVALID_ARG;
+    *out = new (std::nothrow) jolt_host_transcript(*t);
+    return *out ? JOLT_OK : JOLT_ERR_OOM;
 }
 extern "C" int32_t jolt_host_transcript_destroy(jolt_host_transcript* t) {
     delete t;

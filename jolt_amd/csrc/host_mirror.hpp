@@ -45,6 +45,7 @@ struct Transcript {
     virtual void append_bytes(const uint8_t* b, size_t n) = 0;
     virtual void draw16(uint8_t out[16]) = 0;  // the 16 squeezed bytes behind either challenge shape
     virtual void state(uint8_t out[32]) const = 0;  // Transcript::state
+    virtual Transcript* clone() const = 0;          // an independent copy in the same state (the Dory verifier draws its last challenge from one)
     Fr challenge();         // Transcript::challenge: 16 bytes -> from_challenge_bytes (125-bit shape)
     Fr challenge_scalar();  // Transcript::challenge_scalar: 16 bytes -> from_scalar_challenge_bytes
     void append_fr(const Fr& v);
@@ -63,6 +64,7 @@ struct MockTranscript final : Transcript {
     void append_bytes(const uint8_t* b, size_t n) override;
     void draw16(uint8_t out[16]) override;
     void state(uint8_t out[32]) const override;
+    Transcript* clone() const override { return new MockTranscript(*this); }
 
    private:
     void absorb_word(uint64_t w);
@@ -77,6 +79,7 @@ struct LegacyBlake2bTranscript final : Transcript {
     void append_bytes(const uint8_t* b, size_t n) override;
     void draw16(uint8_t out[16]) override;
     void state(uint8_t out[32]) const override;
+    Transcript* clone() const override { return new LegacyBlake2bTranscript(*this); }
 
    private:
     void step(const uint8_t* payload, size_t n);
@@ -91,6 +94,7 @@ struct KeccakSpongeTranscript final : Transcript {
     void append_bytes(const uint8_t* b, size_t n) override;
     void draw16(uint8_t out[16]) override;
     void state(uint8_t out[32]) const override;
+    Transcript* clone() const override { return new KeccakSpongeTranscript(*this); }
 
    private:
     void absorb(const uint8_t* b, size_t n);
@@ -107,6 +111,7 @@ struct Blake2bSpongeTranscript final : Transcript {
     void append_bytes(const uint8_t* b, size_t n) override;
     void draw16(uint8_t out[16]) override;
     void state(uint8_t out[32]) const override;
+    Transcript* clone() const override;
 };
 
 // What a 64-bit transcript label of the C ABI selects: the two top bits name the engine (0 the test transcript, 1 LegacyBlake2b, 2 Keccak sponge, 3 Blake2b512 sponge; for 1 - 3 the session
@@ -118,6 +123,14 @@ struct LabelledTranscript final : Transcript {
     void append_bytes(const uint8_t* b, size_t n) override { inner->append_bytes(b, n); }
     void draw16(uint8_t out[16]) override { inner->draw16(out); }
     void state(uint8_t out[32]) const override { inner->state(out); }
+    Transcript* clone() const override {
+        LabelledTranscript* c = new LabelledTranscript();
+        if (inner) c->inner.reset(inner->clone());
+        return c;
+    }
+
+   private:
+    LabelledTranscript() = default;
 };
 void blake2b_digest(const uint8_t* in, size_t n, size_t outlen, uint8_t* out);  // RFC 7693, unkeyed
 void keccak_f1600(uint8_t lanes[200]);                                             // FIPS 202
@@ -230,4 +243,5 @@ struct jolt_host_transcript {
     jolt_host::LabelledTranscript t;
     explicit jolt_host_transcript(uint64_t label) : t(label) {}
     jolt_host_transcript(int kind, const uint8_t* label, size_t n) : t(kind, label, n) {}
+    jolt_host_transcript(const jolt_host_transcript& other) : t(0) { t.inner.reset(other.t.inner ? other.t.inner->clone() : nullptr); }
 };

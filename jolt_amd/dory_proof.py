@@ -17,7 +17,7 @@ import numpy as np
 
 from . import ffi
 
-DoryProofSetup = ffi.DoryLibSetup  # jolt_dory_setup: DoryProofSetup(ctx, gamma1, gamma2, h1, h2), .n, .tier2(hints), .close()
+DoryProofSetup = ffi.DoryLibSetup  # jolt_dory_setup: DoryProofSetup(ctx, gamma1, gamma2, h1, h2), .n, .tier2(hints), .verifier(), .combine(commitments, scalars), .close()
 
 
 class DoryProof:
@@ -50,6 +50,13 @@ def prove(setup, hints, scalars, v_table, left, right, nu, sigma, transcript=Non
     v = L^T M (2^sigma entries), L (2^nu) and R (2^sigma).  The library checks everything before it enqueues anything and refuses with a JoltError."""
     out = setup.ctx.dory_open(setup, hints, scalars, v_table, left, right, nu, sigma, transcript=transcript, callback=callback)
     return DoryProof(sigma, out["gts"], out["g1s"], out["g2s"], out["challenges"])
+
+
+def verify(setup, commitment, y, left, right, nu, sigma, proof, transcript=None, callback=None):
+    """DoryScheme::verify as one call over a DoryProofSetup: proof a DoryProof (or a dict(gts, g1s, g2s)), left / right host arrays of 2^nu / 2^sigma field elements.
+    The callback form is prove()'s, asked once more for d with DORY_PHASE_D.  -> (accepted, failed_check)"""
+    p = proof if isinstance(proof, dict) else dict(gts=proof.gts, g1s=proof.g1s, g2s=proof.g2s)
+    return setup.ctx.dory_verify(setup.verifier(), commitment, y, left, right, nu, sigma, p, transcript=transcript, callback=callback)
 
 
 def absorb(transcript, elements):

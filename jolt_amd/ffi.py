@@ -609,6 +609,13 @@ class HostTranscript:
         _call("jolt_host_transcript_challenge", None, self.h, 1 if full_width else 0, _p(o))
         return o[0]
 
+    def clone(self):
+        """an independent copy in the current state (jolt_host_transcript_clone)"""
+        c = HostTranscript.__new__(HostTranscript)
+        c.h = C.c_void_p()
+        _call("jolt_host_transcript_clone", None, self.h, C.byref(c.h))
+        return c
+
     def close(self):
         if self.h:
             lib().jolt_host_transcript_destroy(self.h)
@@ -1712,7 +1719,22 @@ class DoryLibSetup:
         _call("jolt_dory_setup_tier2", self.ctx, self.ctx.h, self.h, hs, firsts, rows, len(views), _p(outs))
         return [outs[k].copy() for k in range(len(views))]
 
+    _verifier = None
+
+    def verifier(self):
+        """the verifier's precomputed GT values (DoryVerifierSetup), built once -- one product batch over the resident bases -- and closed with the setup"""
+        if self._verifier is None:
+            self._verifier = DoryVerifierSetup(self)
+        return self._verifier
+
+    def combine(self, commitments, scalars):
+        """DoryScheme::combine: prod_i commitments[i]^scalars[i] in GT, one multi-exponentiation on the device (jolt_dory_gt_multi_exp)"""
+        return self.ctx.dory_gt_multi_exp(commitments, scalars)
+
     def close(self):
+        if self._verifier is not None:
+            self._verifier.close()
+            self._verifier = None
         if self.h:
             _call("jolt_dory_setup_free", self.ctx, self.ctx.h, self.h)
             self.h = None
@@ -1880,6 +1902,137 @@ Context.dory_round_update = _dory_round_update
 Context.dory_open = _dory_open
 Context.dory_prove_batch = _dory_prove_batch
 Context.grid_evaluate_columns = _grid_evaluate_columns
+
+
+# ---- Dory verification (dory_verify.hip): GT multi-exponentiation, the verifier's precomputed GT values, the verifier as one call
+def _gt_rows(gts):
+    return np.ascontiguousarray(gts, dtype=np.uint64).reshape(-1, 48)
+
+
+def _gt_powers_in(gts, scalars):
+    g, s = _gt_rows(gts), fr(scalars).reshape(-1, 4)
+    if g.shape[0] != s.shape[0]:
+        raise ValueError("one scalar per GT element")
+    return g, s, g.shape[0]
+
+
+def _dory_gt_pow_many(self, gts, scalars):
+    """(n, 48): gts[i]^scalars[i], n independent powers in one launch (jolt_dory_gt_pow_many); any canonical Fq12 is a valid base"""
+    g, s, n = _gt_powers_in(gts, scalars)
+    out = np.zeros((n, 48), dtype=np.uint64)
+    _call("jolt_dory_gt_pow_many", self, self.h, _p(g) if n else None, _p(s) if n else None, n, _p(out) if n else None)
+    return out
+
+
+def _dory_gt_multi_exp(self, gts, scalars):
+    """(48,): prod_i gts[i]^scalars[i] (DoryScheme::combine, jolt_dory_gt_multi_exp); one for no terms"""
+    g, s, n = _gt_powers_in(gts, scalars)
+    out = gt_array()
+    _call("jolt_dory_gt_multi_exp", self, self.h, _p(g) if n else None, _p(s) if n else None, n, _p(out))
+    return out
+
+
+class DoryVerifierSetup:
+    """jolt_dory_verifier_setup: the 3 log2(n) + 4 GT values a verifier holds for a DoryLibSetup of n bases, from one product batch"""
+
+    def __init__(self, setup):
+        self.ctx, self.setup, self.h = setup.ctx, setup, C.c_void_p()
+        _call("jolt_dory_verifier_setup_create", self.ctx, self.ctx.h, setup.h, C.byref(self.h))
+
+    def values(self):
+        """(3 s + 4, 48): chi_0 .. chi_s, Delta1R_0 .. Delta1R_{s-1}, Delta2R_0 .. Delta2R_{s-1}, HT, e(H1, Gamma2[0]), e(Gamma1[0], H2)"""
+        out = np.zeros((3 * (self.setup.n.bit_length() - 1) + 4, 48), dtype=np.uint64)
+        _call("jolt_dory_verifier_setup_values", self.ctx, self.h, _p(out))
+        return out
+
+    def timing(self, enable):
+        """(host replay + exponents, group folds, pairings + final exponentiations, multi-exponentiation) wall ms of the last verification made while timing was on"""
+        ms = (C.c_double * 4)()
+        _call("jolt_dory_verifier_setup_timing", self.ctx, self.h, 1 if enable else 0, ms)
+        return tuple(ms)
+
+    def close(self):
+        if self.h:
+            _call("jolt_dory_verifier_setup_free", self.ctx, self.ctx.h, self.h)
+            self.h = None
+
+    free = close
+
+
+def host_dory_verify_exponents(sigma, challenges, d, s1, s2, y):
+    """jolt_host_dory_verify_exponents: dict(proof_gt (2 + 6 sigma, 4), commitment (4,), setup (3 sigma + 4, 4), g1 (1 + 3 sigma, 4), g2 (3 sigma, 4), h2 (4,))"""
+    ch = fr(challenges).reshape(-1, 4)
+    if ch.shape[0] != 2 * sigma + 1:
+        raise ValueError("beta_k, alpha_k per round and gamma: 2 sigma + 1 challenges")
+    outs = [fr_array(2 + 6 * sigma), fr_array(1), fr_array(3 * sigma + 4), fr_array(1 + 3 * sigma), fr_array(max(3 * sigma, 1)), fr_array(1)]
+    _call("jolt_host_dory_verify_exponents", None, sigma, _p(ch), *[_p(fr(x).reshape(4)) for x in (d, s1, s2, y)], *[_p(o) for o in outs])
+    return dict(proof_gt=outs[0], commitment=outs[1][0], setup=outs[2], g1=outs[3], g2=outs[4][:3 * sigma], h2=outs[5][0])
+
+
+def _dory_verify(self, verifier, commitment, y, left, right, nu, sigma, proof, transcript=None, callback=None):
+    """DoryScheme::verify as one call (jolt_host_dory_verify under a HostTranscript, jolt_host_dory_verify_with_transcript under a callback of dory_open's shape, which
+    is also asked for d with DORY_PHASE_D).  verifier a DoryVerifierSetup; left (2^nu, 4), right (2^sigma, 4) host arrays; proof a dict(gts, g1s, g2s) as dory_open
+    returns.  -> (accepted, failed_check): failed_check 0 none, 1 the VMV check, 2 the final check.  A rejected proof raises nothing."""
+    if (transcript is None) == (callback is None):
+        raise ValueError("a verification runs under a transcript or under a callback")
+    lt, rt = fr(left).reshape(-1, 4), fr(right).reshape(-1, 4)
+    if nu > 62 or sigma > 62 or lt.shape[0] != 1 << nu or rt.shape[0] != 1 << sigma:
+        raise ValueError("left has 2^nu entries, right has 2^sigma")
+    n_gt, n_g1, n_g2, _ = host_dory_proof_counts(sigma)
+    gts, g1s, g2s = _gt_rows(proof["gts"]), _pair_g1(proof["g1s"]), _dory_pts("g2", proof["g2s"])
+    if (gts.shape[0], g1s.shape[0], g2s.shape[0]) != (n_gt, n_g1, n_g2):
+        raise ValueError("the proof does not have the element counts of an opening of 2^sigma columns")
+    accepted, failed = C.c_int32(-1), C.c_int32(-1)
+    head = (self.h, verifier.h, verifier.setup.h, _p(_gt_rows(commitment).reshape(48)), _p(fr(y).reshape(4)), _p(lt), _p(rt), nu, sigma, _p(gts), _p(g1s), _p(g2s))
+    if transcript is not None:
+        _call("jolt_host_dory_verify", self, *head, transcript.h, C.byref(accepted), C.byref(failed))
+    else:
+        err = []
+
+        def cb(user, phase, rnd, p_gt, k_gt, p_g1, k_g1, p_g2, k_g2, out):
+            try:
+                take = lambda p, k, w: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(k, w)).copy() if k else np.zeros((0, w), dtype=np.uint64)  # noqa: E731
+                c = callback(phase, rnd, take(p_gt, k_gt, 48), take(p_g1, k_g1, 12), take(p_g2, k_g2, 24))
+                if isinstance(c, (int, np.integer)) and not isinstance(c, bool):
+                    return int(c)
+                if c is not None:
+                    c = np.ascontiguousarray(c, dtype=np.uint64).reshape(4)
+                    C.memmove(out, c.ctypes.data, 32)
+                return 0
+            except Exception as e:  # never unwind through the C frame
+                err.append(e)
+                return 4
+
+        fn = DORY_TRANSCRIPT_FN(cb)
+        st = lib().jolt_host_dory_verify_with_transcript(*head, fn, None, C.byref(accepted), C.byref(failed))
+        if err:
+            raise err[0]
+        _ck(st, "jolt_host_dory_verify_with_transcript", self)
+    return bool(accepted.value), failed.value
+
+
+def _dory_verify_batch(self, verifier, commitments, evaluations, point, proof, transcript):
+    """HomomorphicBatch::<DoryScheme>::verify_batch as one call (jolt_host_dory_verify_batch): commitments (n, 48) the tier-2 commitments in claim order, evaluations
+    (n, 4) as the statement holds them, point the grid-order point, proof a dict(gts, g1s, g2s) as dory_prove_batch returns, transcript a HostTranscript.
+    -> dict(accepted, failed_check, joint_eval)"""
+    cm, ev, pt = _gt_rows(commitments), fr(evaluations).reshape(-1, 4), fr(point).reshape(-1, 4)
+    if cm.shape[0] != ev.shape[0]:
+        raise ValueError("one evaluation per commitment")
+    sigma = (pt.shape[0] + 1) // 2
+    n_gt, n_g1, n_g2, _ = host_dory_proof_counts(sigma)
+    gts, g1s, g2s = _gt_rows(proof["gts"]), _pair_g1(proof["g1s"]), _dory_pts("g2", proof["g2s"])
+    if (gts.shape[0], g1s.shape[0], g2s.shape[0]) != (n_gt, n_g1, n_g2):
+        raise ValueError("the proof does not have the element counts of an opening of 2^sigma columns")
+    accepted, failed, joint = C.c_int32(-1), C.c_int32(-1), fr_array(1)
+    _call("jolt_host_dory_verify_batch", self, self.h, verifier.h, verifier.setup.h, _p(cm) if cm.shape[0] else None, _p(ev) if ev.shape[0] else None, cm.shape[0],
+          _p(pt), pt.shape[0], _p(gts), _p(g1s), _p(g2s), transcript.h, C.byref(accepted), C.byref(failed), _p(joint))
+    return dict(accepted=bool(accepted.value), failed_check=failed.value, joint_eval=joint[0])
+
+
+Context.dory_gt_pow_many = _dory_gt_pow_many
+Context.dory_gt_multi_exp = _dory_gt_multi_exp
+Context.dory_verify = _dory_verify
+Context.dory_verify_batch = _dory_verify_batch
 
 
 # ---- the witness commitment in front of an opening (dory.hip, dory_hints.hip.h): row commitments written on the device, normalised, in hint order

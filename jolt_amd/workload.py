@@ -899,6 +899,25 @@ class DeviceWorkload:
             transcript.close()
         return out
 
+    def dory_verify(self, commit_out, open_out, label=0, evaluations=None):
+        """The verifier of stage 8 under Dory: HomomorphicBatch::verify_batch as ONE call of the library (jolt_host_dory_verify_batch) under a fresh transcript of the
+        label's engine.  commit_out: what dory_commit returned (its tier2 array, in column order); open_out: what dory_open returned; the statement is opening_claims
+        (or `evaluations`, in batch order) at open_point.  A verifier sees neither the placement nor the blocks.  -> bool; the details of the last call -- accepted,
+        failed_check, joint_eval, transcript_state (equal to dory_open's after an accepted proof) -- stay in self.dory_verify_result."""
+        order = self.column_of_claim
+        tier2 = np.asarray(commit_out["tier2"], dtype=np.uint64).reshape(-1, 48)
+        commitments = tier2 if order is None else tier2[list(order)]
+        if evaluations is None:
+            evaluations = self.opening_claims if order is None else self.opening_claims[list(order)]
+        transcript = self.ffi.HostTranscript(label)
+        try:
+            out = self.ctx.dory_verify_batch(self.dory_setup.verifier(), commitments, evaluations, self.open_point, open_out, transcript)
+            out["transcript_state"] = transcript.state()
+        finally:
+            transcript.close()
+        self.dory_verify_result = out
+        return out["accepted"]
+
     def step(self, label=0):
         """One proof's worth of hot-path work (bench.py's timed step)."""
         if self.witness_upload:

@@ -99,6 +99,10 @@ pub struct jolt_dory_setup {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct jolt_dory_verifier_setup {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct jolt_read_raf {
     _private: [u8; 0],
 }
@@ -501,6 +505,17 @@ extern "C" {
     pub fn jolt_host_dory_transcript_append_gt(t: *mut jolt_host_transcript, element: *const jolt_gt_t) -> i32;
     pub fn jolt_host_dory_transcript_append_g1(t: *mut jolt_host_transcript, element: *const jolt_g1_t) -> i32;
     pub fn jolt_host_dory_transcript_append_g2(t: *mut jolt_host_transcript, element: *const jolt_g2_t) -> i32;
+    pub fn jolt_dory_gt_pow_many(ctx: *mut jolt_ctx, gts: *const jolt_gt_t, scalars: *const jolt_fr_t, n: usize, outs: *mut jolt_gt_t) -> i32;
+    pub fn jolt_dory_gt_multi_exp(ctx: *mut jolt_ctx, gts: *const jolt_gt_t, scalars: *const jolt_fr_t, n: usize, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_dory_verifier_setup_create(ctx: *mut jolt_ctx, setup: *const jolt_dory_setup, out: *mut *mut jolt_dory_verifier_setup) -> i32;
+    pub fn jolt_dory_verifier_setup_free(ctx: *mut jolt_ctx, vs: *mut jolt_dory_verifier_setup) -> i32;
+    pub fn jolt_dory_verifier_setup_values(vs: *const jolt_dory_verifier_setup, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_dory_verifier_setup_timing(vs: *const jolt_dory_verifier_setup, enable: i32, out_ms: *mut f64) -> i32;
+    pub fn jolt_host_transcript_clone(t: *const jolt_host_transcript, out: *mut *mut jolt_host_transcript) -> i32;
+    pub fn jolt_host_dory_verify_exponents(sigma: u32, challenges: *const jolt_fr_t, d: *const jolt_fr_t, s1: *const jolt_fr_t, s2: *const jolt_fr_t, y: *const jolt_fr_t, exp_proof_gt: *mut jolt_fr_t, exp_commitment: *mut jolt_fr_t, exp_setup: *mut jolt_fr_t, coef_g1: *mut jolt_fr_t, coef_g2: *mut jolt_fr_t, coef_h2: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_dory_verify_with_transcript(ctx: *mut jolt_ctx, vs: *const jolt_dory_verifier_setup, setup: *const jolt_dory_setup, commitment: *const jolt_gt_t, y: *const jolt_fr_t, left: *const jolt_fr_t, right: *const jolt_fr_t, nu: u32, sigma: u32, gts: *const jolt_gt_t, g1s: *const jolt_g1_t, g2s: *const jolt_g2_t, r#fn: jolt_dory_transcript_fn, user: *mut c_void, accepted: *mut i32, failed_check: *mut i32) -> i32;
+    pub fn jolt_host_dory_verify(ctx: *mut jolt_ctx, vs: *const jolt_dory_verifier_setup, setup: *const jolt_dory_setup, commitment: *const jolt_gt_t, y: *const jolt_fr_t, left: *const jolt_fr_t, right: *const jolt_fr_t, nu: u32, sigma: u32, gts: *const jolt_gt_t, g1s: *const jolt_g1_t, g2s: *const jolt_g2_t, t: *mut jolt_host_transcript, accepted: *mut i32, failed_check: *mut i32) -> i32;
+    pub fn jolt_host_dory_verify_batch(ctx: *mut jolt_ctx, vs: *const jolt_dory_verifier_setup, setup: *const jolt_dory_setup, commitments: *const jolt_gt_t, evaluations: *const jolt_fr_t, n_claims: usize, point: *const jolt_fr_t, n_point: usize, gts: *const jolt_gt_t, g1s: *const jolt_g1_t, g2s: *const jolt_g2_t, t: *mut jolt_host_transcript, accepted: *mut i32, failed_check: *mut i32, joint_eval_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_table_from_ints(ctx: *mut jolt_ctx, values: *const jolt_ints, offset: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_grid_commit_onehot(ctx: *mut jolt_ctx, srs: *const jolt_srs, source: *const jolt_onehot, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_joint_polynomial(ctx: *mut jolt_ctx, sources: *const *const jolt_onehot, n_sources: usize, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, log_k: u32, out: *mut *mut jolt_table) -> i32;
