@@ -1702,6 +1702,39 @@ int32_t jolt_table_permute_bits(jolt_ctx *ctx, const jolt_table *table, const si
 int32_t jolt_eq_evals_shifted(jolt_ctx *ctx, const jolt_fr_t *r, size_t n, size_t start_index, size_t len, jolt_table **out);
 int32_t jolt_table_outer(jolt_ctx *ctx, const jolt_fr_t *lane_weights, size_t n_lanes, const jolt_table *cycle_table, int32_t order, jolt_table **out);
 
+/* ---- TESTS ONLY: device twins of the host forms above (csrc/device_probe.hip).  A jolt_host_* form compiles a function the kernels call for the CPU so that the
+ * CPU suite can hold it to an independent reference at corner operands; the jolt_probe_* entry of the same name runs that function on the device, one lane per
+ * operand tuple: host arrays of n tuples in, one launch, n results out.  Nothing on the product path calls these.  Every entry refuses n > 2^20
+ * (JOLT_ERR_UNSUPPORTED), a null array with n > 0, an unknown op, and the operands its host form refuses, with the host form's status; a refused call launches
+ * nothing and writes nothing; n = 0 is JOLT_OK.
+ * jolt_probe_field_op: field 0 = Fr, 1 = Fq as in jolt_host_mul_limbs29; unary ops ignore b; MUL_SHIFTED is Fr only and refuses a b whose four low u32 limbs are
+ *   not zero, as jolt_host_fr_mul_shifted does.  jolt_host_field_op is the same ops over the same arrays on the host, with the device's multiplication algorithm
+ *   (mul_limbs29) wherever the device multiplies.
+ * jolt_probe_fq_limb_op / jolt_probe_g1xl_add_paths: jolt_host_fq_limb_op / jolt_host_g1xl_add_paths per tuple (acc n x 36 limbs, q n x 18, negate n; common, full,
+ *   step n x 36 each, suspect n, canon n x 64 words).
+ * jolt_probe_fq2_op: JOLT_FQ2_*.  jolt_probe_fq12_op: JOLT_FQ12_MUL, _SQR, _CONJ, _MUL_SPARSE; _INV and the Frobenius maps exist for the host only (the final
+ *   exponentiation runs there): JOLT_ERR_UNSUPPORTED.  jolt_probe_g2_op: JOLT_PROBE_G2_ADD and _DOUBLE write n points to out, JOLT_PROBE_G2_EQ n flags to equal.
+ * jolt_probe_suffix_mle: jolt_host_suffix_mle per tuple.  jolt_probe_dory_fr_digits: jolt_host_dory_fr_digits per scalar, digits_out n rows of W words.
+ * jolt_probe_small_scalar_dots / jolt_host_small_scalar_dots: n dot products over slices of one column of n_terms machine integers of `kind` (JOLT_INT_*; 8 bytes a term,
+ *   16 for JOLT_INT_I128) against n_terms field elements through the small-scalar accumulator: out[i] = sum of values[k] * ints[k] over offsets[i] <= k < offsets[i + 1];
+ *   offsets holds n + 1 ascending entries, the last at most n_terms <= 2^20 (anything else is JOLT_ERR_INVALID_ARG).  One slice of kind I128 is
+ *   jolt_host_small_scalar_dot. */
+enum { JOLT_PROBE_MUL = 0, JOLT_PROBE_SQR = 1, JOLT_PROBE_ADD = 2, JOLT_PROBE_SUB = 3, JOLT_PROBE_NEG = 4, JOLT_PROBE_DBL = 5, JOLT_PROBE_FROM_MONT = 6,
+       JOLT_PROBE_TO_MONT = 7, JOLT_PROBE_MUL_SHIFTED = 8 };
+enum { JOLT_PROBE_G2_ADD = 0, JOLT_PROBE_G2_DOUBLE = 1, JOLT_PROBE_G2_EQ = 2 };
+int32_t jolt_host_field_op(int32_t field, int32_t op, const jolt_fr_t *a, const jolt_fr_t *b, size_t n, jolt_fr_t *out);
+int32_t jolt_probe_field_op(jolt_ctx *ctx, int32_t field, int32_t op, const jolt_fr_t *a, const jolt_fr_t *b, size_t n, jolt_fr_t *out);
+int32_t jolt_probe_fq_limb_op(jolt_ctx *ctx, int32_t op, const jolt_fr_t *a, const jolt_fr_t *b, const jolt_fr_t *c, const jolt_fr_t *d, size_t n, jolt_fr_t *out);
+int32_t jolt_probe_g1xl_add_paths(jolt_ctx *ctx, const uint32_t *acc, const uint32_t *q, const int32_t *negate, size_t n, uint32_t *common, uint32_t *full, uint32_t *step,
+                                  int32_t *suspect, uint32_t *canon);
+int32_t jolt_probe_fq2_op(jolt_ctx *ctx, int32_t op, const jolt_fq2_t *a, const jolt_fq2_t *b, size_t n, jolt_fq2_t *out);
+int32_t jolt_probe_g2_op(jolt_ctx *ctx, int32_t op, const jolt_g2_t *p, const jolt_g2_t *q, size_t n, jolt_g2_t *out, int32_t *equal);
+int32_t jolt_probe_fq12_op(jolt_ctx *ctx, int32_t op, const jolt_gt_t *a, const jolt_gt_t *b, size_t n, jolt_gt_t *out);
+int32_t jolt_probe_suffix_mle(jolt_ctx *ctx, const uint32_t *kind, const uint64_t *lo, const uint64_t *hi, const uint32_t *len, size_t n, uint64_t *out);
+int32_t jolt_probe_dory_fr_digits(jolt_ctx *ctx, const jolt_fr_t *scalars, size_t n, int32_t c, int32_t W, uint32_t *digits_out, uint32_t *negative_out);
+int32_t jolt_host_small_scalar_dots(const jolt_fr_t *values, const void *ints, int32_t kind, const uint64_t *offsets, size_t n_terms, size_t n, jolt_fr_t *out);
+int32_t jolt_probe_small_scalar_dots(jolt_ctx *ctx, const jolt_fr_t *values, const void *ints, int32_t kind, const uint64_t *offsets, size_t n_terms, size_t n, jolt_fr_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -825,30 +825,25 @@ extern "C" int32_t jolt_host_mul_limbs29(int32_t field, const jolt_fr_t* a, cons
 // Operands are canonical Fq in STANDARD Montgomery form; they are taken to L-form (x * 2^261: a product with the Montgomery form of 32),
 // combined there, and the result is brought back.  op 0: a * b   1: a^2   2: a * b + c * d (one reduction)   3: (a - b) * c through the lazily
 // reduced difference a + 8p - b   4: (a - b - 2c) * d through a + 6p - b - 2c.
-#include "g1.hip.h"
-#include "fq_limb.hip.h"
+#include "device_probe.hip.h"
 extern "C" int32_t jolt_host_fq_limb_op(int32_t op, const jolt_fr_t* a, const jolt_fr_t* b, const jolt_fr_t* c, const jolt_fr_t* d, jolt_fr_t* out) {
     if (!a || !out || (op != 1 && !b) || (op >= 2 && !c) || ((op == 2 || op == 4) && !d)) return JOLT_ERR_INVALID_ARG;
     using namespace jolt;
-    Fq thirty_two = Fq::zero();
-    thirty_two.l[0] = 32;
-    const Fq m32 = to_mont(thirty_two);
-    auto load = [&](const jolt_fr_t* p) {
+    auto load = [&](const jolt_fr_t* p) {  // an operand the op does not take: a
         Fq x;
-        std::memcpy(&x, p, sizeof(x));
-        return fql_from_words(mul(x, m32));
+        std::memcpy(&x, p ? p : a, sizeof(x));
+        return x;
     };
-    const FqL r256 = fql_from_words(Fq::one());
-    FqL r;
-    switch (op) {
-        case 0: r = fql_mul(load(a), load(b)); break;
-        case 1: r = fql_sqr(load(a)); break;
-        case 2: r = fql_mul2(load(a), load(b), load(c), load(d)); break;
-        case 3: r = fql_mul(fql_diff<8, false>(load(a), load(b), load(a)), load(c)); break;
-        case 4: r = fql_mul(fql_diff<6, true>(load(a), load(b), load(c)), load(d)); break;
+    const Fq x = load(a), y = load(b), z = load(c), w = load(d);
+    Fq res;
+    switch (op) {  // the bodies are device_probe.hip.h's: jolt_probe_fq_limb_op runs the same ones on the device
+        case 0: res = probe::fq_limb_op<0>(x, y, z, w); break;
+        case 1: res = probe::fq_limb_op<1>(x, y, z, w); break;
+        case 2: res = probe::fq_limb_op<2>(x, y, z, w); break;
+        case 3: res = probe::fq_limb_op<3>(x, y, z, w); break;
+        case 4: res = probe::fq_limb_op<4>(x, y, z, w); break;
         default: return JOLT_ERR_INVALID_ARG;
     }
-    const Fq res = fql_to_std(r, r256);
     std::memcpy(out, &res, sizeof(res));
     return JOLT_OK;
 }
@@ -891,32 +886,18 @@ extern "C" int32_t jolt_host_g1xl_add_paths(const uint32_t* acc, const uint32_t*
                                             uint32_t* canon) {
     if (!acc || !q || !common || !full || !step || !suspect || !canon) return JOLT_ERR_INVALID_ARG;
     using namespace jolt;
-    Fq thirty_two = Fq::zero();
-    thirty_two.l[0] = 32;
-    const FqL one = fql_from_words(to_mont(thirty_two)), r256 = fql_from_words(Fq::one());
     G1XyzzL p;
     FqL qx, qy;
     std::memcpy(&p, acc, sizeof(p));
     std::memcpy(&qx, q, sizeof(qx));
     std::memcpy(&qy, q + 9, sizeof(qy));
-    const uint32_t neg_mask = negate ? ~0u : 0u;
-    bool sus = false;
-    const G1XyzzL c = g1xl_add_mixed_common(p, qx, qy, neg_mask, sus);
-    const G1XyzzL f = g1xl_add_mixed(p, qx, fql_signed_y(qy, neg_mask), one);
-    bool ident = g1xl_is_identity(p);  // the bit a loop carries beside its accumulator
-    const G1XyzzL s = sus ? g1xl_add_mixed_rare(c, ident, qx, qy, neg_mask, one) : c;
-    std::memcpy(common, &c, sizeof(c));
-    std::memcpy(full, &f, sizeof(f));
-    std::memcpy(step, &s, sizeof(s));
-    *suspect = sus ? 1 : 0;
-    const G1XyzzL* both[2] = {&c, &f};
-    for (int k = 0; k < 2; ++k) {
-        const FqL* co[4] = {&both[k]->x, &both[k]->y, &both[k]->zz, &both[k]->zzz};
-        for (int j = 0; j < 4; ++j) {
-            const Fq v = fql_to_std(*co[j], r256);
-            std::memcpy(canon + (k * 4 + j) * 8, &v, sizeof(v));
-        }
-    }
+    probe::AddPaths r;  // the body is device_probe.hip.h's: jolt_probe_g1xl_add_paths runs the same one on the device
+    probe::g1xl_add_paths(p, qx, qy, negate != 0, r);
+    std::memcpy(common, &r.common, sizeof(r.common));
+    std::memcpy(full, &r.full, sizeof(r.full));
+    std::memcpy(step, &r.step, sizeof(r.step));
+    *suspect = r.suspect;
+    std::memcpy(canon, r.canon, sizeof(r.canon));
     return JOLT_OK;
 }
 extern "C" int32_t jolt_host_fr_add(const jolt_fr_t* a, const jolt_fr_t* b, jolt_fr_t* out) {

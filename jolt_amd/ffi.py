@@ -3409,3 +3409,119 @@ Context.stage_precommitted_address = _stage_precommitted_address
 Context.table_permute_bits = _table_permute_bits
 Context.eq_evals_shifted = _eq_evals_shifted
 Context.table_outer = _table_outer
+
+
+# ---- TESTS ONLY: the device twins of the host forms (device_probe.hip) ---------------------------------------------------------------------------------------
+# One call = one launch over n operand tuples.  Arrays may be None and `n` / `out` may be given, so that the suite can make the calls the entries refuse; a refused
+# call raises JoltError and leaves `out` as it was.
+def _rows(a, width, dtype=np.uint64):
+    return np.ascontiguousarray(a, dtype=dtype).reshape(-1, width) if a is not None else None
+
+
+def _probe_n(n, *arrays):
+    return n if n is not None else next(a.shape[0] for a in arrays if a is not None)
+
+
+def host_field_op(field, op, a, b=None):
+    """PROBE_* over (n, 4) operand arrays on the host, with the device's multiplication algorithm wherever the device multiplies; field 0 = Fr, 1 = Fq"""
+    a, b = _rows(a, 4), _rows(b, 4)
+    out = fr_array(a.shape[0])
+    _call("jolt_host_field_op", None, field, op, _p(a), _p(b), a.shape[0], _p(out))
+    return out
+
+
+def probe_field_op(ctx, field, op, a, b=None, n=None, out=None):
+    a, b = _rows(a, 4), _rows(b, 4)
+    n = _probe_n(n, a, b)
+    out = fr_array(n) if out is None else out
+    _call("jolt_probe_field_op", ctx, ctx.h if ctx else None, field, op, _p(a), _p(b), n, _p(out))
+    return out
+
+
+def probe_fq_limb_op(ctx, op, a, b=None, c=None, d=None, n=None, out=None):
+    a, b, c, d = (_rows(x, 4) for x in (a, b, c, d))
+    n = _probe_n(n, a, b, c, d)
+    out = fr_array(n) if out is None else out
+    _call("jolt_probe_fq_limb_op", ctx, ctx.h if ctx else None, op, _p(a), _p(b), _p(c), _p(d), n, _p(out))
+    return out
+
+
+def probe_g1xl_add_paths(ctx, acc, q, negate):
+    """host_g1xl_add_paths over n tuples: acc (n, 36), q (n, 18) uint32 limbs, negate (n,); the same dict with a leading axis of n"""
+    acc, q = _rows(acc, 36, np.uint32), _rows(q, 18, np.uint32)
+    neg = np.ascontiguousarray(negate, dtype=np.int32).reshape(-1)
+    n = acc.shape[0]
+    common, full, step = (np.zeros((n, 4, 9), dtype=np.uint32) for _ in range(3))
+    canon, sus = np.zeros((n, 2, 4, 8), dtype=np.uint32), np.zeros(n, dtype=np.int32)
+    _call("jolt_probe_g1xl_add_paths", ctx, ctx.h, _p(acc), _p(q), _p(neg), n, _p(common), _p(full), _p(step), _p(sus), _p(canon))
+    return {"common": common, "full": full, "step": step, "suspect": sus != 0, "canon_common": canon[:, 0], "canon_full": canon[:, 1]}
+
+
+def probe_fq2_op(ctx, op, a, b=None, n=None, out=None):
+    a, b = _rows(a, 8), _rows(b, 8)
+    n = _probe_n(n, a, b)
+    out = np.zeros((n, 8), dtype=np.uint64) if out is None else out
+    _call("jolt_probe_fq2_op", ctx, ctx.h if ctx else None, op, _p(a), _p(b), n, _p(out))
+    return out
+
+
+def probe_g2_op(ctx, op, p, q=None):
+    """PROBE_G2_ADD / _DOUBLE -> (n, 24) points, PROBE_G2_EQ -> (n,) bool"""
+    p, q = _rows(p, 24), _rows(q, 24)
+    n = p.shape[0]
+    out, equal = np.zeros((n, 24), dtype=np.uint64), np.zeros(n, dtype=np.int32)
+    _call("jolt_probe_g2_op", ctx, ctx.h, op, _p(p), _p(q), n, _p(out), _p(equal))
+    return equal != 0 if op == PROBE_G2_EQ else out  # noqa: F821 (the header's constant)
+
+
+def probe_fq12_op(ctx, op, a, b=None, n=None, out=None):
+    a, b = _rows(a, 48), _rows(b, 48)
+    n = _probe_n(n, a, b)
+    out = np.zeros((n, 48), dtype=np.uint64) if out is None else out
+    _call("jolt_probe_fq12_op", ctx, ctx.h if ctx else None, op, _p(a), _p(b), n, _p(out))
+    return out
+
+
+def probe_suffix_mle(ctx, kinds, bits, lengths, n=None, out=None):
+    """host_suffix_mle over n tuples; bits are Python ints of up to 128 bits"""
+    kind = np.ascontiguousarray(kinds, dtype=np.uint32)
+    lo = np.array([int(b) & (2**64 - 1) for b in bits], dtype=np.uint64)
+    hi = np.array([(int(b) >> 64) & (2**64 - 1) for b in bits], dtype=np.uint64)
+    length = np.ascontiguousarray(lengths, dtype=np.uint32)
+    n = kind.shape[0] if n is None else n
+    out = np.zeros(n, dtype=np.uint64) if out is None else out
+    _call("jolt_probe_suffix_mle", ctx, ctx.h if ctx else None, _p(kind), _p(lo), _p(hi), _p(length), n, _p(out))
+    return out
+
+
+def probe_dory_fr_digits(ctx, scalars, c, W, n=None, out=None):
+    """host_dory_fr_digits over n scalars: ((n, W) signed digits as int64, (n,) bool negative)"""
+    s = _rows(scalars, 4)
+    n = _probe_n(n, s)
+    digits = np.zeros((n, max(W, 1)), dtype=np.uint32) if out is None else out
+    neg = np.zeros(digits.shape[0], dtype=np.uint32)
+    _call("jolt_probe_dory_fr_digits", ctx, ctx.h, _p(s), n, c, W, _p(digits), _p(neg))
+    mag = (digits & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    return np.where(digits >> np.uint32(31) != 0, -mag, mag), neg != 0
+
+
+def _small_column(ints, kind):
+    """Python ints -> the column's words: one uint64 per term, (lo, hi) two's complement for INT_I128"""
+    if kind == INT_I128:  # noqa: F821
+        return np.array([[int(x) & (2**64 - 1), (int(x) >> 64) & (2**64 - 1)] for x in ints], dtype=np.uint64).reshape(-1, 2)
+    return np.array([int(x) & (2**64 - 1) for x in ints], dtype=np.uint64)
+
+
+def host_small_scalar_dots(values, ints, kind, offsets):
+    """out[i] = sum of values[k] * ints[k] over offsets[i] <= k < offsets[i + 1] through the device's small-scalar accumulator, on the host; kind = INT_U64 / _I64 / _I128"""
+    v, z, off = _rows(values, 4), _small_column(ints, kind), np.ascontiguousarray(offsets, dtype=np.uint64)
+    out = fr_array(off.shape[0] - 1)
+    _call("jolt_host_small_scalar_dots", None, _p(v), _p(z), kind, _p(off), v.shape[0], off.shape[0] - 1, _p(out))
+    return out
+
+
+def probe_small_scalar_dots(ctx, values, ints, kind, offsets, n_terms=None, out=None):
+    v, z, off = _rows(values, 4), _small_column(ints, kind), np.ascontiguousarray(offsets, dtype=np.uint64)
+    out = fr_array(off.shape[0] - 1) if out is None else out
+    _call("jolt_probe_small_scalar_dots", ctx, ctx.h if ctx else None, _p(v), _p(z), kind, _p(off), v.shape[0] if n_terms is None else n_terms, off.shape[0] - 1, _p(out))
+    return out

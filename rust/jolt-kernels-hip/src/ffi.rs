@@ -664,4 +664,15 @@ extern "C" {
     pub fn jolt_table_permute_bits(ctx: *mut jolt_ctx, table: *const jolt_table, old_lsb_to_new_lsb: *const usize, n: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_eq_evals_shifted(ctx: *mut jolt_ctx, r: *const jolt_fr_t, n: usize, start_index: usize, len: usize, out: *mut *mut jolt_table) -> i32;
     pub fn jolt_table_outer(ctx: *mut jolt_ctx, lane_weights: *const jolt_fr_t, n_lanes: usize, cycle_table: *const jolt_table, order: i32, out: *mut *mut jolt_table) -> i32;
+    pub fn jolt_host_field_op(field: i32, op: i32, a: *const jolt_fr_t, b: *const jolt_fr_t, n: usize, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_probe_field_op(ctx: *mut jolt_ctx, field: i32, op: i32, a: *const jolt_fr_t, b: *const jolt_fr_t, n: usize, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_probe_fq_limb_op(ctx: *mut jolt_ctx, op: i32, a: *const jolt_fr_t, b: *const jolt_fr_t, c: *const jolt_fr_t, d: *const jolt_fr_t, n: usize, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_probe_g1xl_add_paths(ctx: *mut jolt_ctx, acc: *const u32, q: *const u32, negate: *const i32, n: usize, common: *mut u32, full: *mut u32, step: *mut u32, suspect: *mut i32, canon: *mut u32) -> i32;
+    pub fn jolt_probe_fq2_op(ctx: *mut jolt_ctx, op: i32, a: *const jolt_fq2_t, b: *const jolt_fq2_t, n: usize, out: *mut jolt_fq2_t) -> i32;
+    pub fn jolt_probe_g2_op(ctx: *mut jolt_ctx, op: i32, p: *const jolt_g2_t, q: *const jolt_g2_t, n: usize, out: *mut jolt_g2_t, equal: *mut i32) -> i32;
+    pub fn jolt_probe_fq12_op(ctx: *mut jolt_ctx, op: i32, a: *const jolt_gt_t, b: *const jolt_gt_t, n: usize, out: *mut jolt_gt_t) -> i32;
+    pub fn jolt_probe_suffix_mle(ctx: *mut jolt_ctx, kind: *const u32, lo: *const u64, hi: *const u64, len: *const u32, n: usize, out: *mut u64) -> i32;
+    pub fn jolt_probe_dory_fr_digits(ctx: *mut jolt_ctx, scalars: *const jolt_fr_t, n: usize, c: i32, W: i32, digits_out: *mut u32, negative_out: *mut u32) -> i32;
+    pub fn jolt_host_small_scalar_dots(values: *const jolt_fr_t, ints: *const c_void, kind: i32, offsets: *const u64, n_terms: usize, n: usize, out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_probe_small_scalar_dots(ctx: *mut jolt_ctx, values: *const jolt_fr_t, ints: *const c_void, kind: i32, offsets: *const u64, n_terms: usize, n: usize, out: *mut jolt_fr_t) -> i32;
 }

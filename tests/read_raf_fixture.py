@@ -5,6 +5,8 @@ that is the most literal reading -- so that the C oracle (oracle/read_raf.c) and
 machine words, are checked against something that shares none of their bit tricks."""
 import numpy as np
 
+from corner_grids import interesting_bits  # noqa: F401 (the suffix corner grid lives with the other grids)
+
 XLEN = 64
 KINDS = ["One", "And", "AndNot", "Xor", "Or", "RightOperand", "RightOperandW", "ChangeDivisor", "ChangeDivisorW", "UpperWord", "LowerWord", "LowerHalfWord", "LessThan",
          "GreaterThan", "Eq", "LeftOperandIsZero", "RightOperandIsZero", "Lsb", "DivByZero", "Pow2", "Pow2W", "Rev8W", "RightShiftPadding", "RightShift", "RightShiftHelper",
@@ -110,20 +112,6 @@ def suffix_model(kind, bits, length):
     if name == "WindowSign": return sign
     if name == "WindowSignPow2": return u64(sign << bin(y).count("1"))
     raise KeyError(name)
-
-
-def interesting_bits(rng, length):
-    """lookup-index suffixes that exercise the corner branches: zero, all ones, one operand zero / all ones, single bits, random"""
-    full = (1 << length) - 1 if length else 0
-    odd = sum(1 << k for k in range(1, 128, 2)) & full    # x all ones, y zero
-    even = sum(1 << k for k in range(0, 128, 2)) & full   # y all ones, x zero
-    out = [0, full, odd, even, 1 & full, 2 & full, 3 & full, 4 & full, (1 << 62) & full, (1 << 63) & full, (1 << 31) & full, full >> 1, full ^ 1]
-    for _ in range(40):
-        v = int.from_bytes(rng.bytes(16), "little") & full
-        out += [v, v & even, v & odd, v | even, v | odd]
-        hi_ones = int(rng.integers(0, 64))
-        out.append((v | (even ^ (even >> (2 * hi_ones)))) & full)  # y with a run of leading ones
-    return out
 
 
 def make_rows(T, n_tables, seed, raf_fraction=0.3, none_fraction=0.1):

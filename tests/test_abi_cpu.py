@@ -42,8 +42,9 @@ def test_no_cpu_fallback_without_device():
 
 
 def test_host_field_ops_match_oracle():
-    # field.hip.h compiled for the host: the 64-bit-limb host product (host_mul64) and the shared add/sub/inv code;
-    # the kernels' 32-bit mont_rows<8> is covered by the GPU tests, mont_rows<4> below
+    # field.hip.h compiled for the host: the 64-bit-limb host product (host_mul64) and the shared add/sub/inv code.  The kernels multiply with mul_limbs29
+    # (test_device_multiplication_algorithm_matches_oracle_on_host, and on the device build tests/test_gpu_device_probe.py); no device code calls the row-wise
+    # mont_rows<8> any more, its four-row form mont_rows<4> is below
     a, b = rand_fr(200, 1), rand_fr(200, 2)
     edge = O.to_mont([0, 1, O.R_MOD - 1, 2, O.R_MOD - 2])
     a[:5], b[:5] = edge, edge[::-1]
@@ -131,16 +132,17 @@ def test_deferred_reduction_accumulator_equals_plain_field_sum():
 def test_device_multiplication_algorithm_matches_oracle_on_host():
     """mul_limbs29 (what `mul` is on the device: nine 29-bit limbs, product scanning, b << 5 to square away the 2^261 radix) built
     for the host: Fr and Fq products against the oracle, including 0, 1, p-1, p-2 and operands with all-ones limb patterns that
-    maximise every column sum."""
-    rng = np.random.default_rng(29)
+    maximise every column sum (tests/corner_grids.py: 480 pairs per field, then the saturated operands' 44; tests/test_gpu_device_probe.py
+    runs the same pairs on the device build)."""
+    from corner_grids import field_grid
     for field, mod, omul in ((0, O.R_MOD, O.fr_mul), (1, O.Q_MOD, O.fq_mul)):
-        ints = [0, 1, 2, mod - 1, mod - 2, (1 << 253) - 1, (1 << 254) - 1 if (1 << 254) - 1 < mod else mod - 3, 0x1FFFFFFF, (1 << 29), ((1 << 232) - 1)]
-        ints += [int.from_bytes(rng.bytes(32), "little") % mod for _ in range(150)]
-        vals = np.array([[(v >> (64 * k)) & (2**64 - 1) for k in range(4)] for v in ints], dtype=np.uint64)  # raw limbs = Montgomery residues
-        for i in range(len(ints)):
-            for j in (i, (i * 7 + 3) % len(ints), len(ints) - 1 - i):
-                want = omul(vals[i:i + 1], vals[j:j + 1])[0]
-                assert np.array_equal(ffi.host_mul_limbs29(field, vals[i], vals[j]), want), (field, i, j)
+        ints, vals, pairs = field_grid(field)
+        assert len(ints) == 162 and len(pairs) == 480 + 44 and all(v < mod for v in ints)
+        for i, j in pairs:
+            want = omul(vals[i:i + 1], vals[j:j + 1])[0]
+            assert np.array_equal(ffi.host_mul_limbs29(field, vals[i], vals[j]), want), (field, i, j)
+        a, b = vals[[i for i, _ in pairs]], vals[[j for _, j in pairs]]
+        assert np.array_equal(ffi.host_field_op(field, ffi.PROBE_MUL, a, b), omul(a, b))  # the array form the device twin is compared with
 
 
 def test_rust_ffi_crate_agrees_with_the_header():
@@ -364,16 +366,14 @@ def test_limb_form_field_arithmetic_matches_oracle_on_host():
     """fq_limb.hip.h (2^261 Montgomery radix, lazy reduction, dedicated squaring, two-product reduction, lazily reduced differences) built
     for the host: every operation against the oracle's Fq arithmetic on corner values (0, 1, p - 1, all-ones limb patterns) and random
     operands -- the differences with the subtrahend LARGER than the minuend included, which is what the added multiples of p are for."""
-    rng = np.random.default_rng(61)
-    mod = O.Q_MOD
-    ints = [0, 1, 2, mod - 1, mod - 2, (1 << 253) - 1, mod - 3, 0x1FFFFFFF, 1 << 29, (1 << 232) - 1] + [int.from_bytes(rng.bytes(32), "little") % mod for _ in range(60)]
-    vals = np.array([[(v >> (64 * k)) & (2**64 - 1) for k in range(4)] for v in ints], dtype=np.uint64)
-    n = len(ints)
+    from corner_grids import limb_form_grid
+    vals, tuples = limb_form_grid()
+    assert len(tuples) == 70
     mul = lambda x, y: O.fq_mul(x.reshape(1, 4), y.reshape(1, 4))[0]
     sub = lambda x, y: O.fq_sub(x.reshape(1, 4), y.reshape(1, 4))[0]
     add = lambda x, y: O.fq_add(x.reshape(1, 4), y.reshape(1, 4))[0]
-    for i in range(n):
-        a, b, c, d = vals[i], vals[(7 * i + 3) % n], vals[n - 1 - i], vals[(5 * i + 11) % n]
+    for i, (ia, ib, ic, id_) in enumerate(tuples):
+        a, b, c, d = vals[ia], vals[ib], vals[ic], vals[id_]
         assert np.array_equal(ffi.host_fq_limb_op(0, a, b), mul(a, b)), i
         assert np.array_equal(ffi.host_fq_limb_op(1, a), mul(a, a)), i
         assert np.array_equal(ffi.host_fq_limb_op(2, a, b, c, d), add(mul(a, b), mul(c, d))), i
@@ -436,19 +436,29 @@ def test_small_scalar_accumulator_built_for_the_host():
     """small_scalar.hip.h (field x machine-integer products summed unreduced in 13 limbs, one REDC) on the host: equal to the plain sum of
     reduced products for i128 scalars incl. the corners, to the oracle's restatement of FrSmallScalarAccumulator where that one's five limbs
     suffice, and still exact for 5000 full-range 128-bit terms (headroom 2^34 terms)"""
-    rng = np.random.default_rng(90)
+    from corner_grids import small_scalar_cases
     R = O.R_MOD
-    for n in (0, 1, 4, 300, 5000):
-        values = rand_fr(max(n, 1), 91 + n)[:n]
-        scalars = [int(rng.integers(-2**62, 2**62)) * int(rng.integers(0, 2**63)) for _ in range(n)]
-        scalars[: min(n, 4)] = [0, -(2**127), 2**127 - 1, -1][: min(n, 4)]
+    cases = list(small_scalar_cases())
+    assert [n for n, _, _ in cases] == [0, 1, 4, 300, 5000, 200]
+    for n, values, scalars in cases[:-1]:
         v_int = O.from_mont(values) if n else []
         want = sum(v * s for v, s in zip(v_int, scalars)) % R
         got = ffi.host_small_scalar_dot(values if n else np.zeros((0, 4), dtype=np.uint64), scalars)
         assert O.from_mont(got.reshape(1, 4))[0] == want, n
-    values = rand_fr(200, 95)
-    small = rng.integers(-2**48, 2**48, size=200, dtype=np.int64)
+    _, values, small = cases[-1]
     assert np.array_equal(ffi.host_small_scalar_dot(values, [int(x) for x in small]), O.small_scalar_accumulate(values, small))
+    # the sliced form over a column of each integer kind (small_fmadd<2> for the 64-bit kinds): what tests/test_gpu_device_probe.py runs on the device build
+    from corner_grids import small_scalar_columns
+    for name, kind in (("i128", ffi.INT_I128), ("i64", ffi.INT_I64), ("u64", ffi.INT_U64)):
+        values, ints, offsets = small_scalar_columns()[name]
+        v_int = O.from_mont(values)
+        want = O.to_mont([sum(v * s for v, s in zip(v_int[lo:hi], ints[lo:hi])) % R for lo, hi in zip(offsets, offsets[1:])])
+        got = ffi.host_small_scalar_dots(values, ints, kind, offsets)
+        assert len(offsets) > 130 and np.array_equal(got, want), name
+        if name == "i128":
+            for i in (1, 2, 3, 4):  # one slice of this kind is the older entry
+                lo, hi = offsets[i], offsets[i + 1]
+                assert np.array_equal(ffi.host_small_scalar_dot(values[lo:hi], ints[lo:hi]), got[i])
 
 
 def test_block_cyclic_ownership_partitions_every_prefix():

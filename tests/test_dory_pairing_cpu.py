@@ -37,11 +37,9 @@ def test_generated_constants_are_current():
 
 
 def test_host_fq12_matches_the_model_at_the_corners():
-    rng = np.random.default_rng(6)
-    rand = [[int.from_bytes(rng.bytes(40), "little") % Q for _ in range(12)] for _ in range(3)]
-    sparse = PM.f12_add(PM.f12_from_fq2((rand[0][0], rand[0][1]), 0), PM.f12_add(PM.f12_from_fq2((rand[0][2], rand[0][3]), 1), PM.f12_from_fq2((rand[0][4], rand[0][5]), 3)))
-    all_top = PM.gt_from_abi(PM.gt_to_abi([0] * 12) + np.tile(np.array(O.int_to_limbs((Q - 1) * O.MONT_R % Q), dtype=np.uint64), 12))  # q - 1 in every coefficient
-    operands = rand + [PM.ZERO, PM.ONE, all_top, sparse]
+    from corner_grids import fq12_grid
+    operands, sparse = fq12_grid()
+    assert len(operands) == 7 and operands[-1] == sparse
     abi = [PM.gt_to_abi(x) for x in operands]
     for x, X in zip(operands, abi):
         for y, Y in zip(operands, abi):

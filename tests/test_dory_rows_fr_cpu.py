@@ -35,9 +35,7 @@ def test_entries_are_declared_exported_and_bound():
 
 
 # ------------------------------------------------------------------------------------------------------ digits
-def scalars():
-    rng = np.random.default_rng(2000)
-    return [0, 1, R - 1, (R - 1) // 2, (R + 1) // 2, 2**64 - 1, 2**128] + [int.from_bytes(rng.bytes(40), "little") % R for _ in range(200)]
+from corner_grids import dory_fr_scalars as scalars  # noqa: E402
 
 
 @pytest.mark.parametrize("c", range(3, 14))

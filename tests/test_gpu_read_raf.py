@@ -1,6 +1,8 @@
 """Instruction read+RAF checking (stage 5) scans on the device through the C ABI: every phase's condensation, RAF
 sums and per-table suffix accumulators (all 48 suffix kinds), the cycle-phase columns, and the cycle rounds through the split-eq
 uniform member -- against oracle/read_raf.c (tests/test_oracle_read_raf.py pins that restatement to a big-integer model)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -178,4 +180,96 @@ def test_address_rounds_with_device_scans_match_the_definition(ctx, log_t, seed,
     combined.free()
     u.free()
     state.close()
+    rr.free()
+
+
+FIXED_CORNERS = 13  # the head of interesting_bits: zero, all ones, one operand zero / all ones, single bits, all but the top / the lowest bit
+
+
+@functools.lru_cache(maxsize=None)
+def corner_rows(n_tables, seed):
+    """rows built from the suffix corner grid instead of make_rows: for each of the 16 phases the grid at that phase's suffix length (tests/corner_grids.py:
+    zero, all ones, one operand zero / all ones, single high bits, runs of leading ones) with the phase's own 8-bit chunk above it -- 0x00, 0xFF, 0x80, 0x01 and random
+    ones -- and zeros, ones or random bits above the chunk.  A row is accumulated under the suffix kinds of ITS table only, so the thirteen fixed corners of every
+    grid stand once in EVERY table; the grid's other 240 suffixes draw a table (or none) and every row a RAF flag as in make_rows.  16 x (13 n_tables + 240) rows,
+    padded to the next power of two with rows that have no table.  Returns idx, table, raf and, per row, (phase, suffix bits)."""
+    from corner_grids import interesting_bits
+    rng = np.random.default_rng(seed)
+    rows, tables, meta = [], [], []
+    for phase in range(PHASES):
+        suffix_len = ADDRESS_BITS - 8 * (phase + 1)
+        for i, bits in enumerate(interesting_bits(rng, suffix_len)):
+            bits %= 1 << suffix_len  # (the grid's `full ^ 1` is 1 at length 0; the evaluators mask, a row must not spill into its chunk)
+            for t in (range(n_tables) if i < FIXED_CORNERS else [0xFF if rng.random() < 0.1 else int(rng.integers(0, n_tables))]):
+                j = len(rows)
+                chunk = (0x00, 0xFF, 0x80, 0x01)[j % 8] if j % 8 < 4 else int(rng.integers(0, 256))
+                above = (0, (1 << 128) - 1, int.from_bytes(rng.bytes(16), "little"))[j % 3]
+                rows.append((((above >> (suffix_len + 8)) << 8 | chunk) << suffix_len | bits) & ((1 << 128) - 1))
+                tables.append(t)
+                meta.append((phase, bits))
+    n = len(rows)
+    T = 1 << n.bit_length()
+    idx = np.zeros((T, 2), dtype=np.uint64)
+    idx[:n, 0] = [r & (2**64 - 1) for r in rows]
+    idx[:n, 1] = [r >> 64 for r in rows]
+    table = np.full(T, 0xFF, dtype=np.uint8)
+    table[:n] = tables
+    raf = (rng.random(T) < 0.3).astype(np.uint8)
+    return idx, table, raf, meta
+
+
+def corner_rows_hold_their_classes(idx, table, meta, lists):
+    """on the model alone: at every phase whose suffix has 8 bits or more, every 0/1-valued suffix kind takes BOTH values among the phase's own rows whose table lists
+    that kind -- the rows under which the scan accumulates it -- but the kinds that are constant by definition (One; OverflowBitsZero while the suffix has no bit
+    above 64); the four fixed chunk values stand above every phase's suffixes; and operands that are zero, all ones and a single bit reach every table"""
+    from read_raf_fixture import ZERO_ONE, suffix_model, uninterleave
+    for phase in range(PHASES):
+        suffix_len = ADDRESS_BITS - 8 * (phase + 1)
+        own = [(j, bits) for j, (p, bits) in enumerate(meta) if p == phase]
+        chunks = {((int(idx[j, 0]) | int(idx[j, 1]) << 64) >> suffix_len) & 255 for j, _ in own}
+        assert chunks >= {0x00, 0xFF, 0x80, 0x01}, phase
+        assert all(((int(idx[j, 0]) | int(idx[j, 1]) << 64) % (1 << suffix_len)) == bits for j, bits in own), phase
+        if suffix_len < 8:
+            continue
+        for t, kinds in enumerate(lists):
+            mine = [bits for j, bits in own if table[j] == t]
+            ops = [uninterleave(bits, suffix_len) for bits in mine]
+            assert any(y == 0 and x != 0 for x, _, y, _ in ops) and any(x == 0 and y == (1 << yl) - 1 for x, _, y, yl in ops), (phase, t)  # y = 0 with x != 0; y all ones, x = 0
+            assert any(y and y & (y - 1) == 0 for _, _, y, _ in ops), (phase, t)
+            for kind in kinds:
+                if KINDS[kind] not in ZERO_ONE or KINDS[kind] == "One" or (KINDS[kind] == "OverflowBitsZero" and suffix_len <= 64):
+                    continue
+                assert {suffix_model(kind, bits, suffix_len) for bits in mine} == {0, 1}, (phase, t, KINDS[kind])
+
+
+@pytest.mark.parametrize("canonical", [False, True])
+def test_all_sixteen_phases_match_oracle_on_the_suffix_corner_grid(ctx, canonical):
+    """test_all_sixteen_phases_match_oracle over corner_rows: the scan kernels' own chunk_of / mask_low at the 64-bit boundaries (a chunk that straddles bit 64, a suffix
+    of exactly 64 bits, of none) and the bit-count intrinsics inside suffix_mle meet zero, all-ones and single-bit operands, which random indices give them only
+    where the suffix is a few bits long.  Condensation, the RAF sums and every (table, suffix) accumulator after every phase against the oracle."""
+    n_tables = 3  # sixteen suffix kinds per table
+    idx, table, raf, meta = corner_rows(n_tables, 130)  # one row set for both cases (built and checked once)
+    T = idx.shape[0]
+    assert len(meta) == 16 * (FIXED_CORNERS * n_tables + 240) and T == 8192 and (table[len(meta):] == 0xFF).all()
+    lists = suffix_lists(n_tables, 131)
+    assert sorted({k for l in lists for k in l}) == list(range(len(KINDS)))  # every suffix kind is listed
+    if not canonical:
+        corner_rows_hold_their_classes(idx, table, meta, lists)
+    rr = ctx.read_raf(idx, table, raf, n_tables)
+    u_host = rand_fr(T, 132)
+    u = ctx.upload(u_host)
+    for phase in range(PHASES):
+        suffix_len = ADDRESS_BITS - 8 * (phase + 1)
+        if phase:
+            v = rand_fr(256, 140 + phase)
+            rr.condense(u, v, suffix_len + 8)
+            u_host = O.read_raf_condense(idx, u_host, v, suffix_len + 8)
+            assert np.array_equal(u.download(), u_host), phase
+        got_raf, got_suf = rr.phase_scan(u, suffix_len, ADDRESS_BITS, lists, canonical=canonical)
+        want_raf, want_suf = O.read_raf_phase_scan(idx, table, raf, n_tables, u_host, suffix_len, ADDRESS_BITS, lists, canonical=canonical)
+        assert np.array_equal(got_raf, want_raf), phase
+        for t in range(n_tables):
+            base = sum(len(l) for l in lists[:t])
+            for s, kind in enumerate(lists[t]):
+                assert np.array_equal(got_suf[base + s], want_suf[base + s]), (phase, t, KINDS[kind])
     rr.free()

@@ -10,48 +10,7 @@ import numpy as np
 import oracle_lib as O
 from jolt_amd import ffi
 
-Q = O.Q_MOD
-W = 261
-RL = (1 << W) % Q                 # the L-form of 1
-NP = (-pow(Q, -1, 1 << W)) % (1 << W)
-MASK = (1 << 29) - 1
-P0 = Q & MASK                     # fql::P(0)
-
-
-def limbs(v):
-    assert 0 <= v < 1 << (W + 3)
-    return [(v >> (29 * k)) & MASK for k in range(8)] + [v >> 232]
-
-
-def value(l):
-    return sum(int(x) << (29 * k) for k, x in enumerate(l))
-
-
-def mont(a, b, c=0, d=0):         # fql_mul / fql_sqr / fql_mul2 as integers
-    t = a * b + c * d
-    assert t < 169 * Q * Q
-    return (t + (t * NP % (1 << W)) * Q) >> W
-
-
-def model_common(X, Y, ZZ, ZZZ, qx, qy, negate):
-    """the integers g1xl_add_mixed_common must produce, with the documented range of every difference asserted on the way"""
-    U2, S2 = mont(qx, ZZ), mont(qy, ZZZ)
-    P = U2 + 8 * Q - X
-    R = 7 * Q - S2 - Y if negate else S2 + 4 * Q - Y
-    assert 0.4 * Q < P < 9.6 * Q and ((1.8 * Q < R < 7 * Q) if negate else (0.4 * Q < R < 5.6 * Q))
-    PP = mont(P, P)
-    PPP, Qv, ZZ3 = mont(P, PP), mont(X, PP), mont(ZZ, PP)
-    X3 = mont(R, R) + 6 * Q - PPP - 2 * Qv
-    assert 1.2 * Q < X3 < 7.6 * Q
-    Y3 = mont(R, Qv + 8 * Q - X3, 4 * Q - Y, PPP)
-    assert Y3 < 1.44 * Q and ZZ3 < 1.6 * Q
-    return [X3, Y3, ZZ3, mont(ZZZ, PPP)]
-
-
-def oracle_inv(v):
-    r = O.from_mont(O.fq_inv(O.to_mont([v], Q)), Q)[0]
-    assert r * v % Q == 1
-    return r
+from corner_grids import MASK, P0, Q, RL, add_paths_false_positive_cases, add_paths_random_cases, add_paths_special_cases, curve_points, limbs, model_common, oracle_inv, value
 
 
 def run(acc, q, negate):
@@ -59,14 +18,6 @@ def run(acc, q, negate):
     for k in ("common", "full", "step"):
         assert (out[k][:, :8] <= MASK).all(), k  # every output limb normalised
     return out
-
-
-def rand_below(rng, bound):
-    return int.from_bytes(rng.bytes(40), "little") % int(bound)
-
-
-def rand_acc(rng):                # any representative inside the documented entry ranges
-    return [rand_below(rng, 7.6 * Q), rand_below(rng, 3.6 * Q), rand_below(rng, 1.6 * Q), rand_below(rng, 1.6 * Q)]
 
 
 def check_common(out, acc, q, negate, want_suspect):
@@ -83,94 +34,59 @@ def check_common(out, acc, q, negate, want_suspect):
 
 
 def test_common_path_equals_full_function_on_random_inputs():
-    rng = np.random.default_rng(71)
-    edge = [int(7.6 * Q) - 1, int(3.6 * Q) - 1, int(1.6 * Q) - 1, int(1.6 * Q) - 1]
-    cases = [rand_acc(rng) for _ in range(200)] + [edge, [1, 1, 1, 1], [edge[0], 0, 1, edge[3]]]
-    for i, acc in enumerate(cases):
-        q = [rand_below(rng, Q), rand_below(rng, Q)] if i % 7 else [Q - 1, Q - 1]
-        for negate in (False, True):
-            out = run(acc, q, negate)
-            hit = value(out["common"][2]) & MASK in (0, P0)  # ~2^-28 per case; the seed is fixed
-            check_common(out, acc, q, negate, hit)
-            assert not hit
-
-
-def curve_points(n, seed):
-    rng = np.random.default_rng(seed)
-    g = O.g1_generator()
-    jac = [O.g1_scalar_mul(g, np.array([int(rng.integers(1, 2**62)), 0, 0, 0], dtype=np.uint64)) for _ in range(n)]
-    return jac, O.g1_to_affine(np.stack(jac))
-
-
-def aff_ints(a):                  # (x, y) of an affine point of the oracle (standard Montgomery words) as integers
-    return O.from_mont(a[:4], Q)[0], O.from_mont(a[4:], Q)[0]
+    cases = list(add_paths_random_cases())
+    assert len(cases) == 406
+    for acc, q, negate in cases:
+        out = run(acc, q, negate)
+        hit = value(out["common"][2]) & MASK in (0, P0)  # ~2^-28 per case; the seed is fixed
+        check_common(out, acc, q, negate, hit)
+        assert not hit
 
 
 def test_every_true_special_case_raises_suspect():
-    rng = np.random.default_rng(72)
-    _, aff = curve_points(6, 73)
-    seen_rep = set()
-    for a in aff:
-        x, y = aff_ints(a)
-        q = [x * RL % Q, y * RL % Q]
-        one = RL
-        for negate in (False, True):
-            ys = (Q - q[1]) if negate else q[1]
+    seen_rep, count = set(), 0
+    for kind, acc, q, negate, info in add_paths_special_cases():
+        count += 1
+        out = run(acc, q, negate)
+        if kind == "identity":
             # identity accumulator, both representatives of ZZ = 0; the other coordinates are whatever the last addition left there
-            for zz in (0, Q):
-                acc = rand_acc(rng)
-                acc[2] = zz
-                out = run(acc, q, negate)
-                assert out["suspect"]
-                assert np.array_equal(out["step"], out["full"])
-                assert [value(r) for r in out["step"]] == [q[0], ys, one, one]
-                seen_rep.add(value(out["common"][2]))
+            ys = (Q - q[1]) if negate else q[1]
+            assert out["suspect"]
+            assert np.array_equal(out["step"], out["full"])
+            assert [value(r) for r in out["step"]] == [q[0], ys, RL, RL]
+            seen_rep.add(value(out["common"][2]))
+        elif kind in ("double", "cancel"):
             # the accumulator holds +-(the point added), as (x zz, y zzz, zz, zzz) with zz = z^2, zzz = z^3 and any representatives
-            for sign in (1, -1):
-                z = rand_below(rng, Q - 1) + 1
-                zz, zzz = z * z % Q, z * z * z % Q
-                for k in range(3):
-                    X = (x * zz * RL) % Q + k * Q
-                    Y = (sign * y * zzz * RL) % Q + (k % 2) * Q
-                    acc = [X, Y, zz * RL % Q, zzz * RL % Q]
-                    out = run(acc, q, negate)
-                    assert out["suspect"], (sign, negate, k)
-                    assert value(out["common"][2]) in (0, Q)
-                    seen_rep.add(value(out["common"][2]))
-                    assert np.array_equal(out["step"], out["full"])
-                    same = (sign == 1) != negate  # the same point again: doubling; otherwise its negative: the identity
-                    if same:
-                        xs, yv, zv = [value(r) % Q for r in out["step"][:3]]
-                        lam = 3 * x * x * oracle_inv(2 * y % Q) % Q
-                        x2 = (lam * lam - 2 * x) % Q
-                        assert zv != 0 and xs * oracle_inv(zv) % Q == x2  # X / ZZ (the L-form factors cancel)
-                    else:
-                        assert not out["step"].any()
-        # P = 0 as an integer (X = U2 + 8p, above the documented entry range but inside what the products accept): the representative 0 of the zero product
-        zz = rand_below(rng, Q - 1) + 1
-        acc = [mont(q[0], zz) + 8 * Q, rand_below(rng, 3.6 * Q), zz, rand_below(rng, 1.6 * Q)]
-        out = run(acc, q, False)
-        assert out["suspect"] and value(out["common"][2]) == 0 and np.array_equal(out["step"], out["full"])
+            x, y = info["x"], info["y"]
+            assert out["suspect"], (info["sign"], negate, info["k"])
+            assert value(out["common"][2]) in (0, Q)
+            seen_rep.add(value(out["common"][2]))
+            assert np.array_equal(out["step"], out["full"])
+            if kind == "double":  # the same point again: doubling; otherwise its negative: the identity
+                xs, yv, zv = [value(r) % Q for r in out["step"][:3]]
+                lam = 3 * x * x * oracle_inv(2 * y % Q) % Q
+                x2 = (lam * lam - 2 * x) % Q
+                assert zv != 0 and xs * oracle_inv(zv) % Q == x2  # X / ZZ (the L-form factors cancel)
+            else:
+                assert not out["step"].any()
+        else:
+            # P = 0 as an integer (X = U2 + 8p, above the documented entry range but inside what the products accept): the representative 0 of the zero product
+            assert kind == "p_zero" and not negate
+            assert out["suspect"] and value(out["common"][2]) == 0 and np.array_equal(out["step"], out["full"])
+    assert count == 6 * (2 * (2 + 6) + 1)
     assert seen_rep == {0, Q}  # both representatives of a zero ZZ3 went through the filter
 
 
 def test_false_positives_keep_the_common_path():
     """limb 0 of ZZ3 is 0 or P(0) although ZZ3 != 0 mod p, built without search: choose the difference P and a target t, set ZZ = t P^-2 (L-form: ZZ3 = ZZ P^2 2^-522)
     and X = qx ZZ - P; the lazily reduced ZZ3 is then t or t + p."""
-    rng = np.random.default_rng(74)
     found = {(lo, rep): 0 for lo in (0, P0) for rep in ("t", "t+p")}
-    for i in range(80):
-        lo = (0, P0)[i % 2]
-        small = i % 8 >= 6  # a tiny t: the product comes out as t + p whenever t < ZZ PP / 2^261 (limb 0 = lo + P(0): still in the filter only for lo = 0)
-        t = (rand_below(rng, (Q // 4000 if small else Q) >> 29) << 29) | lo
-        assert 0 < t < Q
-        Pres = rand_below(rng, Q - 1) + 1
-        zz = t * RL * RL * oracle_inv(Pres * Pres % Q) % Q
-        q = [rand_below(rng, Q), rand_below(rng, Q)]
-        X = (mont(q[0], zz) - Pres) % Q + (i % 7) * Q
-        acc = [X, rand_below(rng, 3.6 * Q), zz, rand_below(rng, 1.6 * Q)]
-        for negate in (False, True):
-            out = run(acc, q, negate)
+    count = 0
+    for kind, acc, q, negate, info in add_paths_false_positive_cases():
+        count += 1
+        out = run(acc, q, negate)
+        if kind == "planted":
+            t, lo = info["t"], info["lo"]
             zz3 = value(out["common"][2])
             assert zz3 in (t, t + Q) and zz3 % Q != 0
             hit = zz3 & MASK in (0, P0)
@@ -178,15 +94,12 @@ def test_false_positives_keep_the_common_path():
             check_common(out, acc, q, negate, hit)
             if hit and not negate:
                 found[(zz3 & MASK, "t" if zz3 == t else "t+p")] += 1
-    assert found[(0, "t")] >= 16 and found[(P0, "t")] >= 16 and found[(P0, "t+p")] >= 1, found
-    # limb 0 of the INCOMING ZZ is 0 or P(0), value non-zero: not a special case either (the filter looks at ZZ3 alone, which covers ZZ = 0)
-    for i in range(16):
-        acc = rand_acc(rng)
-        acc[2] = ((rand_below(rng, Q >> 29) << 29) | (0, P0)[i % 2]) or (1 << 29)
-        q = [rand_below(rng, Q), rand_below(rng, Q)]
-        for negate in (False, True):
-            out = run(acc, q, negate)
+        else:
+            # limb 0 of the INCOMING ZZ is 0 or P(0), value non-zero: not a special case either (the filter looks at ZZ3 alone, which covers ZZ = 0)
+            assert kind == "incoming"
             check_common(out, acc, q, negate, value(out["common"][2]) & MASK in (0, P0))
+    assert count == 2 * 80 + 2 * 16
+    assert found[(0, "t")] >= 16 and found[(P0, "t")] >= 16 and found[(P0, "t+p")] >= 1, found
 
 
 def test_lists_through_the_loop_match_the_group_law():
