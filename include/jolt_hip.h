@@ -324,6 +324,31 @@ int32_t jolt_host_grid_pair_index(size_t m, uint32_t k, uint32_t a, uint32_t b, 
  * launched on, and the number of mixed additions of that launch (the non-zero signed digits of its scalars).  bench.py's `roofline_msm` divides the two. */
 int32_t jolt_msm_profile_buckets(jolt_ctx *ctx, int32_t enable);
 int32_t jolt_msm_profile_buckets_last(jolt_ctx *ctx, float *ms, uint64_t *additions);
+/* Test hook (no reference counterpart): the plan of the context's last fixed-base MSM -- which sort kernels ran is a function of the window bits, the term count and
+ * the caller's full-width mark, and a test that means one path must fail when the call took another.  words[cap >= JOLT_FX_PLAN_WORDS]: what the enqueue decided on
+ * the host, then three words the sort left on the device (read after the MSM's stream has drained; JOLT_FX_PLAN_STALE once a later per-window MSM or Dory batch
+ * has reused the workspace they live in).  An MSM the fixed-base method refused (JOLT_ERR_UNSUPPORTED inside, the per-window method ran) leaves the plan before it.
+ * JOLT_ERR_INVALID_ARG while the context has run no fixed-base MSM. */
+enum {
+    JOLT_FX_PLAN_C = 0,               /* window bits of the table set                                                                      */
+    JOLT_FX_PLAN_W = 1,               /* windows: ceil(253 / c)                                                                            */
+    JOLT_FX_PLAN_LO_BITS = 2,         /* log2 of the buckets per segment: 8, or 11 above 24-bit windows                                    */
+    JOLT_FX_PLAN_SOA = 3,             /* the scalar-fed sort with split entries (no key array)                                             */
+    JOLT_FX_PLAN_WIDE = 4,            /* W = 13: the second instantiation of the scalar-fed passes                                         */
+    JOLT_FX_PLAN_CAPACITY = 5,        /* capacity regions in place of the histogram pass                                                   */
+    JOLT_FX_PLAN_TWO_PASS = 6,        /* the two partition passes are available (0: the one-pass k_fx_scatter on the key-array path)       */
+    JOLT_FX_PLAN_GRID_REDUCE = 7,     /* reduction by rows and columns (0: running sums)                                                   */
+    JOLT_FX_PLAN_HEAVY_THRESHOLD = 8, /* a bucket with more entries is summed in segments of 128                                           */
+    JOLT_FX_PLAN_STAGE_CAP = 9,       /* entries of LDS stage handed to k_fx_segment_sort_staged (0: 11-bit segments, k_fx_segment_sort)   */
+    JOLT_FX_PLAN_NB1 = 10,            /* segments                                                                                          */
+    JOLT_FX_PLAN_MAX_LDS = 11,        /* the device's LDS bytes per workgroup the plan was made with                                       */
+    JOLT_FX_PLAN_OVERFLOW = 12,       /* device: a capacity region overflowed and the exact passes redid the sort (0 without CAPACITY)     */
+    JOLT_FX_PLAN_LARGEST_SEGMENT = 13, /* device: entries of the largest segment (the largest region after a capacity sort that held)      */
+    JOLT_FX_PLAN_HEAVY_SEGMENTS = 14, /* device: 128-entry segments of over-full buckets                                                   */
+    JOLT_FX_PLAN_WORDS = 15
+};
+#define JOLT_FX_PLAN_STALE 4294967295u
+int32_t jolt_msm_fixed_last_plan(jolt_ctx *ctx, uint32_t *words, size_t cap);
 /* Measurement hook (no reference counterpart; SURVEY.md section 8d: "the run must print the peak it divides by"): the chip-wide issue rate of v_mad_u64_u32 -- the
  * instruction the bucket sums are bound by -- measured now, on this context's device: a register-only loop of independent 64-bit multiply-adds launched until
  * >= target_ms of kernel time have been timed with HIP events on the context's stream; *mads_per_s = the best launch's lane-operations per second.

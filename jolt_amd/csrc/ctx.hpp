@@ -74,6 +74,14 @@ struct jolt_ctx {
     hipEvent_t ev_fx[2] = {nullptr, nullptr};
     const uint32_t* fx_profile_info = nullptr;  // device: info[1] = non-zero digits of the profiled launch
     bool fx_profile_valid = false;
+    // jolt_msm_fixed_last_plan (tests only): what the last fixed-base enqueue decided on the host, and where its sort left the device words -- the lane's workspace
+    // at these offsets, readable while no later job has laid that workspace out again (msm_ws_gen[lane] counts the layouts: host bookkeeping only)
+    uint32_t fx_plan[12] = {};
+    bool fx_plan_valid = false;
+    int fx_plan_lane = 0;
+    uint64_t fx_plan_gen = 0;
+    size_t fx_plan_info_off = 0, fx_plan_hcnt_off = 0;
+    uint64_t msm_ws_gen[4] = {0, 0, 0, 0};
     // uniform split-eq members switch from (product, pair) work items to one item per pair at this many pairs
     // (JOLT_UNIFORM_ROWS_PAIRS overrides; tests lower it to run the row-major kernels at small sizes)
     size_t uniform_rows_pairs = (size_t)1 << 16;

@@ -52,6 +52,7 @@ inline int32_t carve(jolt_ctx* ctx, size_t V, size_t n, uint32_t B, uint32_t hea
     size_t o_keys = take(V * n * 4), o_sorted = take(V * n * 4), o_hist = take(VB * 4), o_offs = take(VB * 4), o_cur = take(VB * 4),
            o_heavy = take((size_t)heavy_cap * 8), o_hcnt = take(256), o_buckets = take(VB * sizeof(G1Jac)),
            o_seg = take((size_t)heavy_cap * sizeof(G1Jac)), o_out = take(outs * sizeof(G1Jac)), o_pool = take(pool * sizeof(Fq));
+    ctx->msm_ws_gen[0]++;
     if (off > ctx->msm_ws_cap[0]) {
         if (ctx->msm_ws[0]) {
             JOLT_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -239,6 +239,7 @@ int32_t jolt_internal_msm_enqueue(jolt_ctx* ctx, const jolt_srs* srs, const Fr* 
            o_cur = take(WB * 4), o_heavy = take((size_t)heavy_cap * 8), o_hcnt = take(256), o_buckets = take(WB * sizeof(G1Jac)),
            o_part = take((size_t)p.W * p.nb * sizeof(G1Jac)), o_seg = take((size_t)heavy_cap * sizeof(G1Jac)), o_wsum = take((size_t)p.W * sizeof(G1Jac));
     hipStream_t st = lane == 0 ? ctx->stream : ctx->side[lane - 1];
+    ctx->msm_ws_gen[lane]++;
     if (off > ctx->msm_ws_cap[lane]) {  // grow-only (hipMalloc / hipFree per MSM cost more than a small MSM itself)
         if (ctx->msm_ws[lane]) {
             JOLT_HIP_TRY(ctx, hipStreamSynchronize(st));

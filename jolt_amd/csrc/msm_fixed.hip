@@ -1132,6 +1132,7 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
     hipStream_t st = lane == 0 ? ctx->stream : ctx->side[lane - 1];
     // phases: sort (HBM bound) -> bucket sums (multiply-add bound) -> reduction (latency bound), all on the lane's stream (confining the sort and the bucket sums
     // to disjoint sets of compute units measured 1.6-2.1x slower: profiles/r03_cu_split_ab.txt)
+    ctx->msm_ws_gen[lane]++;
     if (off > ctx->msm_ws_cap[lane]) {
         if (ctx->msm_ws[lane]) {
             JOLT_HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -1268,11 +1269,13 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
     } else {
         hipLaunchKernelGGL(k_fx_scatter<11>, dim3(slices), dim3(kSortBlock), lds_bytes, st, (const uint32_t*)keys, total, n, srs->pre_stride, nb1, cur1, entries);
     }
+    uint32_t plan_stage_cap = 0;  // jolt_msm_fixed_last_plan
     if (lo_bits == 8) {
         // LDS for the staged segment: twice the average segment (uniform digits spread by ~1 %), at most what a CU has
         const size_t lds_max = ctx->max_lds_per_block > 12288 ? ctx->max_lds_per_block - 12288 : 0;  // cnt / cur / cls / wave sums live next to it
         const size_t want = (2 * (total / nb1) + 2048) * 4;
         const size_t stage_bytes = std::min(lds_max, want);
+        plan_stage_cap = (uint32_t)(stage_bytes / 4);
         if (soa)
             hipLaunchKernelGGL((k_fx_segment_sort_staged<8, true>), dim3(nb1), dim3(kSegThreads), stage_bytes, st, (const uint32_t*)hist1, (const uint32_t*)offs1, (const uint64_t*)nullptr,
                                (const uint32_t*)s_val, (const uint8_t*)s_low, keys, hist, offs, heavy_threshold, heavy, hcnt, heavy_cap, class_hist, (uint32_t)(stage_bytes / 4));
@@ -1376,6 +1379,16 @@ int32_t jolt_internal_msm_fixed_enqueue(jolt_ctx* ctx, const jolt_srs* srs, cons
             }
         }
     }
+    {   // what this enqueue decided, for jolt_msm_fixed_last_plan (host bookkeeping only)
+        const uint32_t plan[12] = {(uint32_t)c, (uint32_t)W, (uint32_t)lo_bits, soa, wide, capacity, two_pass, grid_reduce, heavy_threshold, plan_stage_cap, nb1,
+                                   (uint32_t)std::min<size_t>(ctx->max_lds_per_block, 0xFFFFFFFFu)};
+        std::copy(plan, plan + 12, ctx->fx_plan);
+        ctx->fx_plan_lane = lane;
+        ctx->fx_plan_gen = ctx->msm_ws_gen[lane];
+        ctx->fx_plan_info_off = o_info;
+        ctx->fx_plan_hcnt_off = o_hcnt;
+        ctx->fx_plan_valid = true;
+    }
     job->n = n;
     job->lane = lane;
     job->c = grid_reduce ? kRedS : 0;  // the collect step's Horner: 2^S * (row-weighted sum) + (column-weighted sum); or a single "window"
@@ -1425,6 +1438,26 @@ extern "C" int32_t jolt_msm_profile_buckets_last(jolt_ctx* ctx, float* ms, uint6
     uint32_t info[4] = {0, 0, 0, 0};
     JOLT_HIP_TRY(ctx, hipMemcpy(info, ctx->fx_profile_info, sizeof(info), hipMemcpyDeviceToHost));
     *additions = info[3] ? info[3] : info[1];  // a capacity sort counts its entries in info[3]; the exact scan leaves the total in info[1]
+    return JOLT_OK;
+}
+
+// ---- the plan of the last fixed-base MSM (tests only: a test names the sort path it means to run and fails when the call took another) -------------------------------
+// The host words are what jolt_internal_msm_fixed_enqueue recorded; the device words are read from the lane's workspace after its stream has drained, and come out as
+// JOLT_FX_PLAN_STALE once a later job (a per-window MSM, a Dory batch) has laid that workspace out again.
+extern "C" int32_t jolt_msm_fixed_last_plan(jolt_ctx* ctx, uint32_t* words, size_t cap) {
+    if (!ctx || !words || cap < JOLT_FX_PLAN_WORDS) return JOLT_ERR_INVALID_ARG;
+    if (!ctx->fx_plan_valid) { ctx->last_error = "no fixed-base MSM since the context was created"; return JOLT_ERR_INVALID_ARG; }
+    std::copy(ctx->fx_plan, ctx->fx_plan + 12, words);
+    const int lane = ctx->fx_plan_lane;
+    words[JOLT_FX_PLAN_OVERFLOW] = words[JOLT_FX_PLAN_LARGEST_SEGMENT] = words[JOLT_FX_PLAN_HEAVY_SEGMENTS] = JOLT_FX_PLAN_STALE;
+    if (ctx->fx_plan_gen != ctx->msm_ws_gen[lane] || !ctx->msm_ws[lane]) return JOLT_OK;
+    JOLT_HIP_TRY(ctx, hipStreamSynchronize(lane == 0 ? ctx->stream : ctx->side[lane - 1]));
+    uint32_t info[4] = {0, 0, 0, 0}, hcnt = 0;
+    JOLT_HIP_TRY(ctx, hipMemcpy(info, (const char*)ctx->msm_ws[lane] + ctx->fx_plan_info_off, sizeof(info), hipMemcpyDeviceToHost));
+    JOLT_HIP_TRY(ctx, hipMemcpy(&hcnt, (const char*)ctx->msm_ws[lane] + ctx->fx_plan_hcnt_off, sizeof(hcnt), hipMemcpyDeviceToHost));
+    words[JOLT_FX_PLAN_OVERFLOW] = words[JOLT_FX_PLAN_CAPACITY] ? info[2] : 0u;  // only a capacity sort clears and raises the flag
+    words[JOLT_FX_PLAN_LARGEST_SEGMENT] = info[0];
+    words[JOLT_FX_PLAN_HEAVY_SEGMENTS] = hcnt;
     return JOLT_OK;
 }
 

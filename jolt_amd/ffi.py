@@ -796,6 +796,25 @@ def _msm_profile_buckets_last(self):
     return float(ms.value), int(adds.value)
 
 
+FX_PLAN_FIELDS = ("c", "W", "lo_bits", "soa", "wide", "capacity", "two_pass", "grid_reduce", "heavy_threshold", "stage_cap", "nb1", "max_lds_per_block",
+                  "overflow", "largest_segment", "heavy_segments")
+
+
+def _msm_fixed_last_plan(self):
+    """The plan of the context's last fixed-base MSM (jolt_msm_fixed_last_plan) as a dict over FX_PLAN_FIELDS: the host's decisions (flags as bools), then the three
+    words the sort left on the device -- None once a later job has reused the workspace they live in.  Raises JoltError (invalid argument) before the first
+    fixed-base MSM of the context."""
+    a = np.zeros(FX_PLAN_WORDS, dtype=np.uint32)
+    _call("jolt_msm_fixed_last_plan", self, self.h, _p(a), FX_PLAN_WORDS)
+    out = {name: int(a[k]) for k, name in enumerate(FX_PLAN_FIELDS)}
+    for name in ("soa", "wide", "capacity", "two_pass", "grid_reduce"):
+        out[name] = bool(out[name])
+    for name in ("overflow", "largest_segment", "heavy_segments"):
+        if out[name] == FX_PLAN_STALE:
+            out[name] = None
+    return out
+
+
 def _measure_mad_peak(self, target_ms=50.0):
     """jolt_ctx_measure_mad_peak: (v_mad_u64_u32 lane-operations per second chip-wide, kernel milliseconds timed, launches)"""
     rate, ms, n = C.c_double(), C.c_float(), C.c_uint32()
@@ -947,6 +966,7 @@ Context.msm = _msm
 Context.msm_window = _msm_window
 Context.msm_profile_buckets = _msm_profile_buckets
 Context.msm_profile_buckets_last = _msm_profile_buckets_last
+Context.msm_fixed_last_plan = _msm_fixed_last_plan
 Context.measure_mad_peak = _measure_mad_peak
 Context.srs_setup_from_secret_blocks = _srs_setup_from_secret_blocks
 Context.msm_blocks = _msm_blocks

@@ -198,6 +198,23 @@ pub const JOLT_ROUND_PATH_UNIFORM_ROWS: usize = 13;
 pub const JOLT_ROUND_PATH_LAZY: usize = 14;
 pub const JOLT_ROUND_PATH_BIND: usize = 15;
 pub const JOLT_ROUND_PATH_COUNT: usize = 17;
+pub const JOLT_FX_PLAN_C: usize = 0;
+pub const JOLT_FX_PLAN_W: usize = 1;
+pub const JOLT_FX_PLAN_LO_BITS: usize = 2;
+pub const JOLT_FX_PLAN_SOA: usize = 3;
+pub const JOLT_FX_PLAN_WIDE: usize = 4;
+pub const JOLT_FX_PLAN_CAPACITY: usize = 5;
+pub const JOLT_FX_PLAN_TWO_PASS: usize = 6;
+pub const JOLT_FX_PLAN_GRID_REDUCE: usize = 7;
+pub const JOLT_FX_PLAN_HEAVY_THRESHOLD: usize = 8;
+pub const JOLT_FX_PLAN_STAGE_CAP: usize = 9;
+pub const JOLT_FX_PLAN_NB1: usize = 10;
+pub const JOLT_FX_PLAN_MAX_LDS: usize = 11;
+pub const JOLT_FX_PLAN_OVERFLOW: usize = 12;
+pub const JOLT_FX_PLAN_LARGEST_SEGMENT: usize = 13;
+pub const JOLT_FX_PLAN_HEAVY_SEGMENTS: usize = 14;
+pub const JOLT_FX_PLAN_WORDS: usize = 15;
+pub const JOLT_FX_PLAN_STALE: u32 = u32::MAX;
 pub const JOLT_MAX_MEMBER_TABLES: usize = 40;
 pub const JOLT_MAX_MEMBER_TERMS: usize = 16;
 pub const JOLT_MAX_MEMBER_FACTORS: usize = 64;
@@ -329,6 +346,7 @@ extern "C" {
     pub fn jolt_host_grid_pair_index(m: usize, k: u32, a: u32, b: u32, out: *mut usize) -> i32;
     pub fn jolt_msm_profile_buckets(ctx: *mut jolt_ctx, enable: i32) -> i32;
     pub fn jolt_msm_profile_buckets_last(ctx: *mut jolt_ctx, ms: *mut f32, additions: *mut u64) -> i32;
+    pub fn jolt_msm_fixed_last_plan(ctx: *mut jolt_ctx, words: *mut u32, cap: usize) -> i32;
     pub fn jolt_ctx_measure_mad_peak(ctx: *mut jolt_ctx, target_ms: f32, mads_per_s: *mut f64, timed_ms: *mut f32, launches: *mut u32) -> i32;
     pub fn jolt_msm_g1(ctx: *mut jolt_ctx, srs: *const jolt_srs, scalars: *const jolt_fr_t, n: usize, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_msm_g1_table(ctx: *mut jolt_ctx, srs: *const jolt_srs, scalars: *const jolt_table, n: usize, out: *mut jolt_g1_t) -> i32;

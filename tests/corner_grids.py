@@ -201,6 +201,43 @@ def add_paths_false_positive_cases():
             yield "incoming", acc, q, negate, {}
 
 
+# ---------------------------------------------------------------------------------------------------- the fixed-base MSM's digit recoding
+def fx_digit_corners(c):
+    """canonical scalars at which the recoding of c-bit windows (msm_fixed.hip fx_digits_of) has its worst cases: r - 1, (r - 1) / 2 and its neighbours (the negation
+    threshold), digits of exactly 2^(c-1) and one beyond, all-ones windows whose carry runs through every window to the top"""
+    return [0, 1, 2, R - 1, R - 2, (R - 1) // 2, (R - 1) // 2 + 1, (R + 1) // 2 + 1, (1 << 253) - 1, (1 << 252), (1 << (c - 1)), (1 << (c - 1)) + 1, (1 << c) - 1,
+            sum(((1 << c) - 1) << (c * w) for w in range(253 // c)) % R, sum((1 << (c - 1)) << (c * w) for w in range(253 // c)) % R]
+
+
+def fx_corner_grid(c):
+    """the corners above, then the same digit corners one window at a time (2^(c-1), 2^(c-1) + 1 and the all-ones digit alone in every window, each also negated:
+    r - s), as canonical integers: the scalars the sort paths of the device are fed in tests/test_gpu_msm_fixed_paths.py"""
+    out = fx_digit_corners(c)
+    for w in range(-(-253 // c)):
+        for d in (1 << (c - 1), (1 << (c - 1)) + 1, (1 << c) - 1):
+            s = (d << (c * w)) % R
+            out += [s, R - s]
+    return out
+
+
+def fx_uniform_scalars(n, seed):
+    """n uniform canonical scalars as Python integers"""
+    rng = np.random.default_rng(seed)
+    raw = rng.bytes(40 * n)
+    return [int.from_bytes(raw[40 * i:40 * i + 40], "little") % R for i in range(n)]
+
+
+def fx_planted_scalars(c, n, planted, seed):
+    """n uniform canonical scalars with `planted` of them, spread evenly, replaced by scalars whose every c-bit digit is drawn from [1, 255]: all their entries land
+    in segment 0 of the sort (buckets 1 .. 255), none carries, none is negated"""
+    out = fx_uniform_scalars(n, seed)
+    rng = np.random.default_rng(seed + 1)
+    W = -(-253 // c)
+    for k in range(planted):
+        out[(k * n) // planted] = sum(int(d) << (c * w) for w, d in enumerate(rng.integers(1, 256, size=W)))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- the small-scalar accumulator
 def small_scalar_cases():
     """(n, values, scalars): n field elements against i128 scalars with the corners 0, -2^127, 2^127 - 1, -1 first"""

@@ -417,10 +417,10 @@ def test_fixed_base_digit_recoding_reconstructs_the_scalar(c):
     """k_fx_digits' recoding on the host: sum_w digit_w 2^(c w) = s mod r (scalars above r / 2 come out negated), every signed digit is
     within +-2^(c-1), every magnitude addresses a bucket below the table set's bucket count, and the worst cases (r - 1, (r - 1) / 2 and
     its neighbours, all-ones windows that carry through every window) are among the samples."""
+    from corner_grids import fx_digit_corners
     R = O.R_MOD
     rng = np.random.default_rng(70 + c)
-    samples = [0, 1, 2, R - 1, R - 2, (R - 1) // 2, (R - 1) // 2 + 1, (R + 1) // 2 + 1, (1 << 253) - 1, (1 << 252), (1 << (c - 1)), (1 << (c - 1)) + 1, (1 << c) - 1,
-               sum(((1 << c) - 1) << (c * w) for w in range(253 // c)) % R, sum((1 << (c - 1)) << (c * w) for w in range(253 // c)) % R]
+    samples = fx_digit_corners(c)
     samples += [int.from_bytes(rng.bytes(32), "little") % R for _ in range(300)]
     for s in samples:
         digits, buckets = ffi.host_fx_digits(O.to_mont([s])[0], c)

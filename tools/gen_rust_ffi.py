@@ -92,6 +92,9 @@ def render(decls):
     out.append("pub const JOLT_ROUND_PATH_TAIL: usize = 0;\npub const JOLT_ROUND_PATH_GROUP: usize = 1;\npub const JOLT_ROUND_PATH_SMALL: usize = 9;\n"
                "pub const JOLT_ROUND_PATH_SPLIT_EQ_PRODUCT: usize = 10;\npub const JOLT_ROUND_PATH_UNIFORM_ITEMS: usize = 12;\npub const JOLT_ROUND_PATH_UNIFORM_ROWS: usize = 13;\n"
                "pub const JOLT_ROUND_PATH_LAZY: usize = 14;\npub const JOLT_ROUND_PATH_BIND: usize = 15;\npub const JOLT_ROUND_PATH_COUNT: usize = 17;")
+    out.append("".join(f"pub const JOLT_FX_PLAN_{name}: usize = {k};\n" for k, name in enumerate(
+        ["C", "W", "LO_BITS", "SOA", "WIDE", "CAPACITY", "TWO_PASS", "GRID_REDUCE", "HEAVY_THRESHOLD", "STAGE_CAP", "NB1", "MAX_LDS", "OVERFLOW", "LARGEST_SEGMENT",
+         "HEAVY_SEGMENTS", "WORDS"])) + "pub const JOLT_FX_PLAN_STALE: u32 = u32::MAX;")
     out.append("pub const JOLT_MAX_MEMBER_TABLES: usize = 40;\npub const JOLT_MAX_MEMBER_TERMS: usize = 16;\npub const JOLT_MAX_MEMBER_FACTORS: usize = 64;\npub const JOLT_MAX_DEGREE: usize = 7;")
     out.append("")
     out.append("#[repr(C)]\npub struct jolt_member_desc {\n    pub n_tables: u32,\n    pub n_terms: u32,\n    pub degree: u32,\n    pub order: i32,\n"
