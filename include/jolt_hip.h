@@ -1544,6 +1544,79 @@ int32_t jolt_host_hyperkzg_open_grid(jolt_ctx *ctx, const jolt_srs *srs, const j
                                      jolt_table *const *dense, size_t n_dense, const jolt_fr_t *dense_scalars, jolt_g1_t *com, jolt_g1_t *w, jolt_fr_t *v,
                                      jolt_fr_t *challenges_out);
 
+/* HyperKZG VERIFICATION (hyperkzg_verify.hip).  No kernel of its own: a verification is two jolt_dory_products batches -- L and -R as two MSM_G1 items, then
+ * e(L, g2) e(-R, beta g2) as one PAIR item against a line table prepared once -- and the host final exponentiation.  Proofs are the opening entries' above:
+ * com (ell - 1 points), w (3 points), v (3 * ell values, v[t][j] row-major).
+ *
+ * HyperKZGVerifierSetup (crates/jolt-hyperkzg/src/types.rs:112-146): g1, g2 and beta * g2.  _create checks canonical coordinates and the curve / twist equation (NO
+ * subgroup check, as the Dory entries make none), refuses the identity for any of the three (JOLT_ERR_INVALID_ARG), uploads (g2, beta g2) as one resident G2 vector
+ * and prepares their line table once (jolt_dory_g2_prepare_vec).  _from_secret is the G2 side of setup_from_secret (scheme.rs:54-73): beta * g2 by
+ * jolt_host_g2_scalar_mul -- the twin of jolt_srs_setup_from_secret for test setups.  The G2 generator is the caller's: which point of the twist a deployment's
+ * setup names is a convention no reference vector pins (docs/parity.md).  The object belongs to its context; _free(ctx, NULL) is JOLT_OK. */
+typedef struct jolt_hyperkzg_verifier_setup jolt_hyperkzg_verifier_setup;
+int32_t jolt_hyperkzg_verifier_setup_create(jolt_ctx *ctx, const jolt_g1_t *g1, const jolt_g2_t *g2, const jolt_g2_t *beta_g2, jolt_hyperkzg_verifier_setup **out);
+int32_t jolt_hyperkzg_verifier_setup_from_secret(jolt_ctx *ctx, const jolt_fr_t *beta, const jolt_g1_t *g1, const jolt_g2_t *g2, jolt_hyperkzg_verifier_setup **out);
+int32_t jolt_hyperkzg_verifier_setup_points(const jolt_hyperkzg_verifier_setup *vs, jolt_g1_t *g1, jolt_g2_t *g2, jolt_g2_t *beta_g2);
+int32_t jolt_hyperkzg_verifier_setup_free(jolt_ctx *ctx, jolt_hyperkzg_verifier_setup *vs);
+/* The verifier's scalars in Fr on the host, no GPU.  point: ell coordinates; eval: the claimed evaluation; v: 3 * ell; r, q, d0: the three challenges.
+ *   *folding_ok, *failed_level  the folding check of scheme.rs:203-234: 2 r y_next = r (1 - x) (y_pos + y_neg) + x (y_pos - y_neg) per level, y_next = v[2][level + 1]
+ *                               and the claimed evaluation at the last level, x = point[ell - 1 - level]; the FIRST failing level (0 when none fails)
+ *   l_scalars                   the ell + 4 scalars of L in the order of kzg.rs:182-200: q^j (1 + d_0 + d_1) for the ell commitments (C_0 first), then r, -r d_0,
+ *                               r^2 d_1 for the witness points, then -(B(r) + d_0 B(-r) + d_1 B(r^2)) for g1, B(u_t) = sum_j q^j v[t][j]
+ *   d_out                       d_0 and d_1 = d_0^2, the scalars of R = w_0 + d_0 w_1 + d_1 w_2 (kzg.rs:204-205)
+ * The scalars are written whether or not the folding check holds.  JOLT_ERR_INVALID_ARG: a null pointer, ell = 0 (HyperKZGError::EmptyPoint) or ell > 40, a value
+ * that is not canonical; JOLT_ERR_NOT_INVERTIBLE: r = 0 (HyperKZGError::DegenerateChallenge, scheme.rs:194-196). */
+int32_t jolt_host_hyperkzg_verify_scalars(size_t ell, const jolt_fr_t *point, const jolt_fr_t *eval, const jolt_fr_t *v /* 3 * ell */, const jolt_fr_t *r,
+                                          const jolt_fr_t *q, const jolt_fr_t *d0, int32_t *folding_ok, size_t *failed_level, jolt_fr_t *l_scalars /* ell + 4 */,
+                                          jolt_fr_t *d_out /* 2 */);
+/* HyperKZGScheme::verify (scheme.rs:162-242) with kzg_verify_batch (kzg.rs:132-210) as one call.  n_commitments = 1 with scalar one is `verify`; n_commitments > 1 is
+ * verify after AdditivelyHomomorphic::combine (scheme.rs:346-352) -- C_0 = sum_i s_i commitments[i] is never built: commitment i enters L's MSM with scalar
+ * s_i (1 + d_0 + d_1).  In order:
+ *   1. every check of the input: canonical values, points on the curve (the identity allowed), ell >= 1 (JOLT_ERR_EMPTY_POINT; ell > 40 or n_commitments > 2^20
+ *      JOLT_ERR_UNSUPPORTED: inside these limits the MSM batch below cannot refuse for its size), n_commitments >= 1, a setup of this context.  A refused call absorbs nothing, enqueues nothing and writes nothing;
+ *   2. `fn` phase 0 over com gives r -- the same three phases, in the same order, with the same elements as jolt_host_hyperkzg_open_with_transcript calls it, so a
+ *      caller's prover callback serves the verifier unchanged; at ell = 1 phase 0 is called with no point, as the opening calls it.  r = 0 is
+ *      JOLT_ERR_NOT_INVERTIBLE (DegenerateChallenge);
+ *   3. the folding check on the host.  On failure *accepted = 0, *failed_check = 1, *failed_level = the level, and phases 1 and 2 are NOT run (scheme.rs:231-233);
+ *   4. phase 1 over v gives q, phase 2 over w gives d_0;
+ *   5. ONE jolt_dory_products batch of two MSM_G1 items: L (n_commitments + ell - 1 + 4 terms) and -R (w under -1, -d_0, -d_1);
+ *   6. ONE batch of one PAIR item: (L, -R) against the prepared (g2, beta g2);
+ *   7. *accepted = 1 only if that product is one after the final exponentiation, otherwise *failed_check = 2.
+ * Two synchronisations.  A rejected proof is JOLT_OK; status codes are for malformed input only. */
+int32_t jolt_host_hyperkzg_verify_with_transcript(jolt_ctx *ctx, const jolt_hyperkzg_verifier_setup *vs, const jolt_g1_t *commitments,
+                                                  const jolt_fr_t *commitment_scalars, size_t n_commitments, const jolt_fr_t *point, size_t ell, const jolt_fr_t *eval,
+                                                  const jolt_g1_t *com, const jolt_g1_t *w, const jolt_fr_t *v, jolt_open_transcript_fn fn, void *user,
+                                                  int32_t *accepted, int32_t *failed_check, size_t *failed_level);
+/* The same under one of the library's engines.  The opening's own transcript is a jolt_host_transcript's engine and both sides absorb through one routine
+ * (hyperkzg_transcript.hpp): a fresh jolt_host_transcript_create(label) draws the challenges jolt_host_hyperkzg_open(..., label) reports in challenges_out. */
+int32_t jolt_host_hyperkzg_verify(jolt_ctx *ctx, const jolt_hyperkzg_verifier_setup *vs, const jolt_g1_t *commitments, const jolt_fr_t *commitment_scalars,
+                                  size_t n_commitments, const jolt_fr_t *point, size_t ell, const jolt_fr_t *eval, const jolt_g1_t *com, const jolt_g1_t *w,
+                                  const jolt_fr_t *v, jolt_host_transcript *t, int32_t *accepted, int32_t *failed_check, size_t *failed_level);
+/* HomomorphicBatch::<HyperKZGScheme>::prove_batch (crates/jolt-openings/src/schemes.rs:487-524) over the commitment grid's columns:
+ *   1. absorbs the statement (jolt_host_opening_statement_absorb): gamma's powers; claim i is column i in jolt_grid_evaluate_columns' order (one-hot columns source
+ *      by source, then dense); *joint_eval_out = sum_i gamma^i evaluations[i];
+ *   2. deals the powers to onehot_scalars and dense_scalars and builds the joint polynomial (jolt_grid_joint_polynomial);
+ *   3. runs the body of jolt_host_hyperkzg_open_grid under t.  The commit-time hint is a function of the columns alone and serves any scalars; hint = NULL or
+ *      levels = 0: every level commitment by MSM.  After the folds the last level (two entries, one small read-back) gives the joint polynomial's value at the point:
+ *      a statement that does not hold is JOLT_ERR_ROUND_CHECK before the transcript absorbs a level commitment (as jolt_host_dory_prove_batch refuses one);
+ *   4. absorbs the closing claim (jolt_host_opening_claim_absorb).
+ * Checked before the transcript absorbs anything: the arguments as jolt_grid_joint_polynomial and jolt_grid_evaluate_columns check them (contexts, limits, one cycle
+ * count), n_claims = the number of columns, n_point = log_k + log2(T) >= 1, canonical values, an SRS of at least 2^n_point bases (JOLT_ERR_SRS_TOO_SMALL), and a hint
+ * that is read (levels > 0, one-hot columns) made on this grid: its k = 2^log_k, its cycle count and its column count.  What the opening itself can still refuse comes
+ * AFTER the statement has been absorbed: a device error, an allocation that fails, a failure of the hint's background sums.  A hint made over other sources of the same
+ * shape is not detected: it yields a proof the verifier rejects.  challenges_out ({r, q, d_0}) may be NULL. */
+int32_t jolt_host_hyperkzg_prove_batch(jolt_ctx *ctx, const jolt_srs *srs, const jolt_onehot *const *sources, size_t n_sources, jolt_table *const *dense,
+                                       size_t n_dense, uint32_t log_k, const jolt_fr_t *evaluations, size_t n_claims, const jolt_fr_t *point, size_t n_point,
+                                       const jolt_grid_hint *hint, uint32_t levels, jolt_host_transcript *t, jolt_g1_t *com, jolt_g1_t *w, jolt_fr_t *v,
+                                       jolt_fr_t *challenges_out, jolt_fr_t *joint_eval_out);
+/* HomomorphicBatch::<HyperKZGScheme>::verify_batch (schemes.rs:526-551): after jolt_host_hyperkzg_verify's checks the statement is absorbed (gamma's powers), the
+ * joint evaluation formed, and the verifier above runs with the powers as commitment scalars.  The closing claim is absorbed ONLY AFTER AN ACCEPTED PROOF: the
+ * reference returns early through `?` (schemes.rs:541-549).  jolt_host_dory_verify_batch absorbs it on both outcomes; the two entries differ there.  After an accepted
+ * proof the transcript ends in the state jolt_host_hyperkzg_prove_batch leaves.  n_claims = 0 is JOLT_ERR_INVALID_ARG. */
+int32_t jolt_host_hyperkzg_verify_batch(jolt_ctx *ctx, const jolt_hyperkzg_verifier_setup *vs, const jolt_g1_t *commitments, const jolt_fr_t *evaluations,
+                                        size_t n_claims, const jolt_fr_t *point, size_t n_point, const jolt_g1_t *com, const jolt_g1_t *w, const jolt_fr_t *v,
+                                        jolt_host_transcript *t, int32_t *accepted, int32_t *failed_check, size_t *failed_level, jolt_fr_t *joint_eval_out);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Stage operators as ProveRounds objects -- one per backend slot (crates/jolt-kernels/src/backend.rs:126-171).
  *

@@ -16,6 +16,7 @@
 #include "g1.hip.h"
 #include "grid_hint.hpp"
 #include "host_mirror.hpp"
+#include "hyperkzg_transcript.hpp"
 #include "poly_kernels.hip.h"
 #include "srs.hpp"
 #include "term_map.hip.h"
@@ -552,13 +553,7 @@ extern "C" int32_t jolt_hyperkzg_witness_poly(jolt_ctx* ctx, const jolt_table* f
 // ------------------------------------------------------------------------------------------------------------------
 using namespace jolt_host;
 
-static void append_g1(Transcript& tr, const G1Jac& p) {
-    uint8_t b[32];
-    jolt_g1_t abi;
-    std::memcpy(&abi, &p, sizeof(abi));
-    jolt_host_g1_serialize_compressed(&abi, b);
-    tr.append_bytes(b, 32);
-}
+using namespace jolt::hyperkzg_host;  // append_g1, OpenTranscript: shared with the verifier (hyperkzg_transcript.hpp)
 
 // CommitmentScheme::commit -> kzg_commit (scheme.rs:302-312, kzg.rs:15-27)
 extern "C" int32_t jolt_host_hyperkzg_commit(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* evals, jolt_g1_t* out) {
@@ -681,40 +676,6 @@ extern "C" int32_t jolt_host_hyperkzg_witness_triple(const jolt_g1_t* c, const j
     return JOLT_OK;
 }
 
-// The opening's Fiat-Shamir: the library's test transcript, or the CALLER's (jolt_open_transcript_fn: the reference's Blake2b / Keccak transcript stays in Rust).
-// Three absorb-then-challenge steps: the level commitments -> r (scheme.rs:148-152), the 3 ell evaluations -> q (kzg.rs:88-95), the three witness
-// commitments -> d_0 (kzg.rs:118-124).
-namespace {
-struct OpenTranscript {
-    LabelledTranscript mock;
-    jolt_open_transcript_fn fn;
-    void* user;
-    int32_t after_points(int32_t phase, const G1Jac* pts, size_t n, Fr* out) {
-        if (!fn) {
-            for (size_t i = 0; i < n; ++i) append_g1(mock, pts[i]);
-            *out = mock.challenge();
-            return JOLT_OK;
-        }
-        static_assert(sizeof(G1Jac) == sizeof(jolt_g1_t), "a Jacobian point crosses the ABI as it lies in memory");
-        jolt_fr_t ch;
-        JOLT_TRY(fn(user, phase, reinterpret_cast<const jolt_g1_t*>(pts), n, nullptr, 0, &ch));
-        *out = fr_from_abi(&ch);
-        return fr_is_canonical(*out) ? JOLT_OK : JOLT_ERR_INVALID_ARG;
-    }
-    int32_t after_values(int32_t phase, const jolt_fr_t* vals, size_t n, Fr* out) {
-        if (!fn) {
-            for (size_t i = 0; i < n; ++i) mock.append_fr(fr_from_abi(&vals[i]));
-            *out = mock.challenge();
-            return JOLT_OK;
-        }
-        jolt_fr_t ch;
-        JOLT_TRY(fn(user, phase, nullptr, 0, vals, n, &ch));
-        *out = fr_from_abi(&ch);
-        return fr_is_canonical(*out) ? JOLT_OK : JOLT_ERR_INVALID_ARG;
-    }
-};
-}  // namespace
-
 // The first level commitments of an opening of the commitment grid's joint polynomial by LINEARITY (docs/kernels.md section 3.7b): the one-hot part from the hint's
 // class sums (grid_hint.hpp; the combination runs on the hint's stream beside the level MSMs), the dense part as MSMs over the dense columns' folds (T >> s terms, in
 // the same pipeline as the other levels' MSMs) -- no host round trip, nothing allocated outside the pool.
@@ -733,7 +694,7 @@ struct GridLinear {
 static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* evals, const jolt_fr_t* point, size_t ell, uint64_t transcript_label,
                                   int rank, int world, size_t block, jolt_gather_fn gather, void* user, jolt_g1_t* com, jolt_g1_t* w, jolt_fr_t* v, jolt_fr_t* challenges_out,
                                   jolt_open_transcript_fn transcript_fn = nullptr, void* transcript_user = nullptr, const jolt_g1_t* known_levels = nullptr, size_t n_known = 0,
-                                  const GridLinear* lin = nullptr) {
+                                  const GridLinear* lin = nullptr, const Fr* expected_eval = nullptr) {
     if (!ctx || !srs || !evals || !point || !w || !v || (ell > 1 && !com)) return JOLT_ERR_INVALID_ARG;
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && !gather)) return JOLT_ERR_INVALID_ARG;
     if (ell == 0) return JOLT_ERR_EMPTY_POINT;
@@ -747,6 +708,21 @@ static int32_t hyperkzg_open_impl(jolt_ctx* ctx, const jolt_srs* srs, const jolt
     };
     int32_t s = jolt_hyperkzg_fold(ctx, evals, point, ell, polys.data());  // phase 1
     if (s != JOLT_OK) { cleanup(); return s; }
+    if (expected_eval) {
+        // a batch's statement (jolt_host_hyperkzg_prove_batch): the last level's two entries give the polynomial's value at the point, p[0] + point[0] (p[1] - p[0]).
+        // A statement that does not hold is refused here, before a level is committed and before the transcript absorbs one.
+        Fr last[2];
+        hipError_t e = hipMemcpyAsync(last, polys[ell - 1]->data(), sizeof(last), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) { (void)hipGetLastError(); ctx->last_error = std::string("hyperkzg open (statement check): ") + hipGetErrorString(e); cleanup(); return JOLT_ERR_HIP; }
+        const Fr x0 = fr_from_abi(&point[0]);
+        if (!fr_is_canonical(x0)) { ctx->last_error = "point coordinate is not a canonical Fr"; cleanup(); return JOLT_ERR_INVALID_ARG; }
+        if (!(add(last[0], mul(x0, sub(last[1], last[0]))) == *expected_eval)) {
+            ctx->last_error = "the claimed evaluations do not combine to the joint polynomial's evaluation at the point";
+            cleanup();
+            return JOLT_ERR_ROUND_CHECK;
+        }
+    }
     std::vector<G1Jac> coms(ell > 1 ? ell - 1 : 0);
     {  // scheme.rs:141-145: the ell-1 level commitments are independent MSMs -> pipelined over the MSM lanes
         // the first n_known level commitments come from the caller (computed by linearity from the structure of the polynomial: jolt_grid_commit_onehot_classes)
@@ -1236,6 +1212,18 @@ extern "C" int32_t jolt_host_hyperkzg_open_grid(jolt_ctx* ctx, const jolt_srs* s
     if (!hint || !onehot_scalars || hint->ctx != ctx) return JOLT_ERR_INVALID_ARG;
     const GridLinear lin{hint, onehot_scalars, dense, n_dense, dense_scalars, levels};
     return hyperkzg_open_impl(ctx, srs, evals, point, ell, transcript_label, 0, 1, 0, nullptr, nullptr, com, w, v, challenges_out, fn, user, nullptr, 0, &lin);
+}
+
+// jolt_host_hyperkzg_open_grid for the batch framing (hyperkzg_verify.hip): always under a callback, the hint optional, the statement's check inside.
+int32_t jolt_internal_hyperkzg_open_grid_checked(jolt_ctx* ctx, const jolt_srs* srs, const jolt_table* evals, const jolt_fr_t* point, size_t ell, jolt_open_transcript_fn fn,
+                                                 void* user, const jolt_grid_hint* hint, uint32_t levels, const jolt_fr_t* onehot_scalars, jolt_table* const* dense,
+                                                 size_t n_dense, const jolt_fr_t* dense_scalars, const Fr* expected_eval, jolt_g1_t* com, jolt_g1_t* w, jolt_fr_t* v,
+                                                 jolt_fr_t* challenges_out) {
+    if (!fn || (hint && hint->ctx != ctx)) return JOLT_ERR_INVALID_ARG;
+    if (!hint || levels == 0) return hyperkzg_open_impl(ctx, srs, evals, point, ell, 0, 0, 1, 0, nullptr, nullptr, com, w, v, challenges_out, fn, user, nullptr, 0, nullptr, expected_eval);
+    if (!onehot_scalars) return JOLT_ERR_INVALID_ARG;
+    const GridLinear lin{hint, onehot_scalars, dense, n_dense, dense_scalars, levels};
+    return hyperkzg_open_impl(ctx, srs, evals, point, ell, 0, 0, 1, 0, nullptr, nullptr, com, w, v, challenges_out, fn, user, nullptr, 0, &lin, expected_eval);
 }
 
 // The same opening with its MSMs sharded over `world` ranks by term range (every rank holds the polynomial and the SRS; `gather` is a

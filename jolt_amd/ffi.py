@@ -914,16 +914,21 @@ class GridHint:
             pass
 
 
-def _hyperkzg_open_grid(self, srs, evals, point, hint, levels, onehot_scalars, dense, dense_scalars, label=0):
-    """jolt_host_hyperkzg_open_grid: the opening of the grid's joint polynomial with its first `levels` level commitments by linearity from the commit-time hint"""
+def _hyperkzg_open_grid(self, srs, evals, point, hint, levels, onehot_scalars, dense, dense_scalars, label=0, callback=None):
+    """jolt_host_hyperkzg_open_grid: the opening of the grid's joint polynomial with its first `levels` level commitments by linearity from the commit-time hint.
+    callback (phase, points (n, 12), values (n, 4)) -> challenge (4,): the caller's transcript in place of the library's under `label`"""
     p = fr(point).reshape(-1, 4)
     ell = p.shape[0]
     com, w, v, ch = g1_array(max(ell - 1, 1)), g1_array(3), fr_array(3 * max(ell, 1)), fr_array(3)
     osc = np.ascontiguousarray(onehot_scalars, dtype=np.uint64).reshape(-1, 4)
     dsc = np.ascontiguousarray(dense_scalars, dtype=np.uint64).reshape(-1, 4) if len(dense) else None
     hs = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
-    _call("jolt_host_hyperkzg_open_grid", self, self.h, srs.h, evals.h, _p(p), ell, label, None, None, hint.h, levels, _p(osc), hs, len(dense),
-          _p(dsc) if dsc is not None else None, _p(com), _p(w), _p(v), _p(ch))
+    fn, err = open_transcript_callback(callback) if callback is not None else (None, [])
+    st = lib().jolt_host_hyperkzg_open_grid(self.h, srs.h, evals.h, _p(p), ell, label, fn, None, hint.h, levels, _p(osc), hs, len(dense),
+                                            _p(dsc) if dsc is not None else None, _p(com), _p(w), _p(v), _p(ch))
+    if err:
+        raise err[0]
+    _ck(st, "jolt_host_hyperkzg_open_grid", self)
     return dict(com=com[: ell - 1], w=w, v=v.reshape(3, ell, 4), challenges=ch)
 
 
@@ -984,6 +989,27 @@ Context.hyperkzg_open_grid = _hyperkzg_open_grid
 Context.grid_hint = lambda self, srs, sources, levels, background=True: GridHint(self, srs, sources, levels, background)
 
 OPEN_TRANSCRIPT_FN = abi.CALLBACK_TYPES["jolt_open_transcript_fn"]
+
+
+def open_transcript_callback(callback):
+    """a jolt_open_transcript_fn around callback(phase, points (n, 12), values (n, 4)) -> challenge (4,) or a non-zero status; -> (fn, err): an exception of the
+    callback never unwinds through the C frame, it ends the call with status 4 and waits in err"""
+    err = []
+
+    def cb(user, phase, points, n_points, values, n_values, out):
+        try:
+            take = lambda p, k, wd: np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(k, wd)).copy() if k else np.zeros((0, wd), dtype=np.uint64)  # noqa: E731
+            c = callback(phase, take(points, n_points, 12), take(values, n_values, 4))
+            if isinstance(c, (int, np.integer)) and not isinstance(c, bool):
+                return int(c)
+            c = np.ascontiguousarray(c, dtype=np.uint64).reshape(4)
+            C.memmove(out, c.ctypes.data, 32)
+            return 0
+        except Exception as e:
+            err.append(e)
+            return 4
+
+    return OPEN_TRANSCRIPT_FN(cb), err
 
 
 def _hyperkzg_open_with_transcript(self, srs, evals, point, absorb_points, absorb_values, challenge):
@@ -2053,6 +2079,119 @@ Context.dory_gt_pow_many = _dory_gt_pow_many
 Context.dory_gt_multi_exp = _dory_gt_multi_exp
 Context.dory_verify = _dory_verify
 Context.dory_verify_batch = _dory_verify_batch
+
+
+# ---- HyperKZG verification (hyperkzg_verify.hip): the verifier's setup, its scalars, the verifier as one call, stage 8's batch framing
+class HyperKzgVerifierSetup:
+    """jolt_hyperkzg_verifier_setup: g1, g2, beta g2 with the line table of (g2, beta g2) resident.  Given `beta` (4 words) the G2 side of setup_from_secret,
+    given `beta_g2` (24 words) the three points as a deployment's setup holds them."""
+
+    def __init__(self, ctx, g1, g2, beta=None, beta_g2=None):
+        if (beta is None) == (beta_g2 is None):
+            raise ValueError("a verifier setup is made from beta or from beta g2")
+        self.ctx, self.h = ctx, C.c_void_p()
+        p1, p2 = _pair_g1(g1).reshape(12), _dory_pts("g2", g2).reshape(24)
+        if beta is not None:
+            _call("jolt_hyperkzg_verifier_setup_from_secret", ctx, ctx.h, _p(fr(beta).reshape(4)), _p(p1), _p(p2), C.byref(self.h))
+        else:
+            _call("jolt_hyperkzg_verifier_setup_create", ctx, ctx.h, _p(p1), _p(p2), _p(_dory_pts("g2", beta_g2).reshape(24)), C.byref(self.h))
+
+    def points(self):
+        """(g1 (12,), g2 (24,), beta_g2 (24,)) as the object holds them"""
+        g1, g2, bg2 = g1_array(1), g2_array(1), g2_array(1)
+        _call("jolt_hyperkzg_verifier_setup_points", self.ctx, self.h, _p(g1), _p(g2), _p(bg2))
+        return g1[0], g2[0], bg2[0]
+
+    def close(self):
+        if self.h:
+            _call("jolt_hyperkzg_verifier_setup_free", self.ctx, self.ctx.h, self.h)
+            self.h = None
+
+    free = close
+
+
+def host_hyperkzg_verify_scalars(point, eval_, v, r, q, d0):
+    """jolt_host_hyperkzg_verify_scalars: dict(folding_ok, failed_level, l_scalars (ell + 4, 4), d (2, 4)); v is (3, ell, 4) or (3 ell, 4)"""
+    pt, vv = fr(point).reshape(-1, 4), fr(v).reshape(-1, 4)
+    ell = pt.shape[0]
+    if vv.shape[0] != 3 * ell:
+        raise ValueError("v holds 3 ell values")
+    ok, level, ls, d = C.c_int32(-1), C.c_size_t(0), fr_array(ell + 4), fr_array(2)
+    _call("jolt_host_hyperkzg_verify_scalars", None, ell, _p(pt) if ell else None, _p(fr(eval_).reshape(4)), _p(vv) if ell else None,
+          *[_p(fr(x).reshape(4)) for x in (r, q, d0)], C.byref(ok), C.byref(level), _p(ls), _p(d))
+    return dict(folding_ok=bool(ok.value), failed_level=level.value, l_scalars=ls, d=d)
+
+
+def _hyperkzg_proof_in(ell, proof):
+    com = np.ascontiguousarray(proof["com"], dtype=np.uint64).reshape(-1, 12)
+    w, v = np.ascontiguousarray(proof["w"], dtype=np.uint64).reshape(-1, 12), fr(proof["v"]).reshape(-1, 4)
+    if (com.shape[0], w.shape[0], v.shape[0]) != (max(ell, 1) - 1, 3, 3 * ell):
+        raise ValueError("the proof does not have the element counts of an opening of ell variables")
+    return com, w, v
+
+
+def _hyperkzg_verify(self, verifier, commitments, point, eval_, proof, transcript=None, callback=None, commitment_scalars=None):
+    """HyperKZGScheme::verify as one call (jolt_host_hyperkzg_verify under a HostTranscript, jolt_host_hyperkzg_verify_with_transcript under a callback
+    (phase, points (n, 12), values (n, 4)) -> challenge (4,) or a non-zero status).  verifier a HyperKzgVerifierSetup; commitments (12,) or (n, 12) with
+    commitment_scalars (n, 4) (None: one commitment under scalar one); proof a dict(com, w, v) as hyperkzg_open returns.
+    -> dict(accepted, failed_check, failed_level): failed_check 0 none, 1 the folding check (failed_level names the level), 2 the pairing check.
+    A rejected proof raises nothing."""
+    if (transcript is None) == (callback is None):
+        raise ValueError("a verification runs under a transcript or under a callback")
+    cm, pt = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 12), fr(point).reshape(-1, 4)
+    sc = host_fr_from_u64(1).reshape(1, 4) if commitment_scalars is None else fr(commitment_scalars).reshape(-1, 4)
+    if cm.shape[0] != sc.shape[0]:
+        raise ValueError("one scalar per commitment")
+    ell = pt.shape[0]
+    com, w, v = _hyperkzg_proof_in(ell, proof)
+    accepted, failed, level = C.c_int32(-1), C.c_int32(-1), C.c_size_t(0)
+    head = (self.h, verifier.h, _p(cm), _p(sc), cm.shape[0], _p(pt) if ell else None, ell, _p(fr(eval_).reshape(4)), _p(com) if com.shape[0] else None, _p(w),
+            _p(v) if ell else None)
+    if transcript is not None:
+        _call("jolt_host_hyperkzg_verify", self, *head, transcript.h, C.byref(accepted), C.byref(failed), C.byref(level))
+    else:
+        fn, err = open_transcript_callback(callback)
+        st = lib().jolt_host_hyperkzg_verify_with_transcript(*head, fn, None, C.byref(accepted), C.byref(failed), C.byref(level))
+        if err:
+            raise err[0]
+        _ck(st, "jolt_host_hyperkzg_verify_with_transcript", self)
+    return dict(accepted=bool(accepted.value), failed_check=failed.value, failed_level=level.value)
+
+
+def _hyperkzg_prove_batch(self, srs, sources, dense, log_k, evaluations, point, transcript, hint=None, levels=0):
+    """HomomorphicBatch::<HyperKZGScheme>::prove_batch as one call (jolt_host_hyperkzg_prove_batch): evaluations (n, 4), one per column in grid_evaluate_columns' order;
+    point: log_k + log T coordinates; hint a GridHint over the same sources (None with levels = 0: every level by MSM); transcript a HostTranscript.
+    -> dict(com, w, v, challenges, joint_eval)"""
+    ev, pt = fr(evaluations).reshape(-1, 4), fr(point).reshape(-1, 4)
+    ell = pt.shape[0]
+    com, w, v, ch, joint = g1_array(max(ell - 1, 1)), g1_array(3), fr_array(3 * max(ell, 1)), fr_array(3), fr_array(1)
+    ss = (C.c_void_p * max(len(sources), 1))(*[s.h for s in sources])
+    ds = (C.c_void_p * max(len(dense), 1))(*[t.h for t in dense])
+    _call("jolt_host_hyperkzg_prove_batch", self, self.h, srs.h, ss if sources else None, len(sources), ds if dense else None, len(dense), log_k,
+          _p(ev) if ev.shape[0] else None, ev.shape[0], _p(pt) if ell else None, ell, hint.h if hint is not None else None, levels, transcript.h, _p(com), _p(w), _p(v), _p(ch),
+          _p(joint))
+    return dict(com=com[: ell - 1], w=w, v=v.reshape(3, ell, 4), challenges=ch, joint_eval=joint[0])
+
+
+def _hyperkzg_verify_batch(self, verifier, commitments, evaluations, point, proof, transcript):
+    """HomomorphicBatch::<HyperKZGScheme>::verify_batch as one call (jolt_host_hyperkzg_verify_batch): commitments (n, 12) in claim order, evaluations (n, 4).  The
+    closing claim is absorbed only after an accepted proof.  -> dict(accepted, failed_check, failed_level, joint_eval)"""
+    cm, ev, pt = np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 12), fr(evaluations).reshape(-1, 4), fr(point).reshape(-1, 4)
+    if cm.shape[0] != ev.shape[0]:
+        raise ValueError("one evaluation per commitment")
+    ell = pt.shape[0]
+    com, w, v = _hyperkzg_proof_in(ell, proof)
+    accepted, failed, level, joint = C.c_int32(-1), C.c_int32(-1), C.c_size_t(0), fr_array(1)
+    _call("jolt_host_hyperkzg_verify_batch", self, self.h, verifier.h, _p(cm) if cm.shape[0] else None, _p(ev) if ev.shape[0] else None, cm.shape[0],
+          _p(pt) if ell else None, ell, _p(com) if com.shape[0] else None, _p(w), _p(v) if ell else None, transcript.h, C.byref(accepted), C.byref(failed), C.byref(level),
+          _p(joint))
+    return dict(accepted=bool(accepted.value), failed_check=failed.value, failed_level=level.value, joint_eval=joint[0])
+
+
+Context.hyperkzg_verifier_setup = lambda self, g1, g2, beta=None, beta_g2=None: HyperKzgVerifierSetup(self, g1, g2, beta=beta, beta_g2=beta_g2)
+Context.hyperkzg_verify = _hyperkzg_verify
+Context.hyperkzg_prove_batch = _hyperkzg_prove_batch
+Context.hyperkzg_verify_batch = _hyperkzg_verify_batch
 
 
 # ---- the witness commitment in front of an opening (dory.hip, dory_hints.hip.h): row commitments written on the device, normalised, in hint order

@@ -918,6 +918,41 @@ class DeviceWorkload:
         self.dory_verify_result = out
         return out["accepted"]
 
+    def verify(self, commit_out, open_out, label=0, evaluations=None):
+        """The verifier of stage 8 under HyperKZG (pcs="grid"), the counterpart of dory_verify: the step's own opening as the step frames it, ONE call of the library
+        (jolt_host_hyperkzg_verify) under a fresh transcript of the label's engine.  commit_out: what commit() returned; its commitments enter in the joint
+        polynomial's column order (one-hot source by source, then dense) under rlc_onehot / rlc_dense -- verify after combine, C_0 never built; open_out: what open()
+        returned; the joint evaluation is formed from evaluate_columns() (or `evaluations`, in that column order) and the same scalars, at open_point.  The verifier
+        setup comes from the workload's own test secret on first use and is kept.  -> bool; the details of the last call -- accepted, failed_check, failed_level,
+        joint_eval, transcript_state -- stay in self.verify_result.  step() does not call it."""
+        if self.pcs != "grid":
+            raise ValueError('verify is the verifier of pcs="grid"; pcs="dory" has dory_verify')
+        ffi = self.ffi
+        if getattr(self, "verifier_setup", None) is None:
+            if getattr(self, "beta", None) is None:
+                raise ValueError("a workload over a caller's SRS does not know its secret: build a HyperKzgVerifierSetup from the setup's G2 points")
+            from .dory_setup import g2_generator
+            self.verifier_setup = self.ctx.hyperkzg_verifier_setup(G1_GENERATOR, g2_generator(), beta=self.beta)
+        commitments = np.concatenate([np.asarray(commit_out["onehot"], dtype=np.uint64).reshape(-1, 12), np.asarray(commit_out["dense"], dtype=np.uint64).reshape(-1, 12)])
+        scalars = np.concatenate([self.rlc_onehot.reshape(-1, 4), self.rlc_dense.reshape(-1, 4)])
+        if evaluations is None:
+            evaluations = self.evaluate_columns()
+        evaluations = np.asarray(evaluations, dtype=np.uint64).reshape(-1, 4)
+        if evaluations.shape[0] != scalars.shape[0] or commitments.shape[0] != scalars.shape[0]:
+            raise ValueError("one commitment and one evaluation per column")
+        joint = np.zeros(4, dtype=np.uint64)
+        for s, y in zip(scalars, evaluations):
+            joint = ffi.host_fr_add(joint, ffi.host_fr_mul(s, y))
+        transcript = ffi.HostTranscript(label)
+        try:
+            out = self.ctx.hyperkzg_verify(self.verifier_setup, commitments, self.open_point, joint, open_out, transcript=transcript, commitment_scalars=scalars)
+            out["transcript_state"] = transcript.state()
+        finally:
+            transcript.close()
+        out["joint_eval"] = joint
+        self.verify_result = out
+        return out["accepted"]
+
     def step(self, label=0):
         """One proof's worth of hot-path work (bench.py's timed step)."""
         if self.witness_upload:
@@ -976,6 +1011,9 @@ class DeviceWorkload:
         if getattr(self, "dory_setup", None) is not None:
             self.dory_setup.close()
             self.dory_setup = None
+        if getattr(self, "verifier_setup", None) is not None:
+            self.verifier_setup.close()
+            self.verifier_setup = None
 
 
 # BN254 G1 generator (1, 2) as Montgomery Jacobian limbs (ark_bn254::G1Projective layout): R mod q, 2R mod q, R mod q

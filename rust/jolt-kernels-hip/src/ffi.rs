@@ -135,6 +135,10 @@ pub struct jolt_grid_hint {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct jolt_hyperkzg_verifier_setup {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct jolt_stage_op {
     _private: [u8; 0],
 }
@@ -644,6 +648,15 @@ extern "C" {
     pub fn jolt_grid_hint_download(ctx: *mut jolt_ctx, hint: *mut jolt_grid_hint, level: u32, out: *mut jolt_g1_t) -> i32;
     pub fn jolt_grid_hint_free(ctx: *mut jolt_ctx, hint: *mut jolt_grid_hint) -> i32;
     pub fn jolt_host_hyperkzg_open_grid(ctx: *mut jolt_ctx, srs: *const jolt_srs, evals: *const jolt_table, point: *const jolt_fr_t, ell: usize, transcript_label: u64, r#fn: jolt_open_transcript_fn, user: *mut c_void, hint: *const jolt_grid_hint, levels: u32, onehot_scalars: *const jolt_fr_t, dense: *const *mut jolt_table, n_dense: usize, dense_scalars: *const jolt_fr_t, com: *mut jolt_g1_t, w: *mut jolt_g1_t, v: *mut jolt_fr_t, challenges_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_hyperkzg_verifier_setup_create(ctx: *mut jolt_ctx, g1: *const jolt_g1_t, g2: *const jolt_g2_t, beta_g2: *const jolt_g2_t, out: *mut *mut jolt_hyperkzg_verifier_setup) -> i32;
+    pub fn jolt_hyperkzg_verifier_setup_from_secret(ctx: *mut jolt_ctx, beta: *const jolt_fr_t, g1: *const jolt_g1_t, g2: *const jolt_g2_t, out: *mut *mut jolt_hyperkzg_verifier_setup) -> i32;
+    pub fn jolt_hyperkzg_verifier_setup_points(vs: *const jolt_hyperkzg_verifier_setup, g1: *mut jolt_g1_t, g2: *mut jolt_g2_t, beta_g2: *mut jolt_g2_t) -> i32;
+    pub fn jolt_hyperkzg_verifier_setup_free(ctx: *mut jolt_ctx, vs: *mut jolt_hyperkzg_verifier_setup) -> i32;
+    pub fn jolt_host_hyperkzg_verify_scalars(ell: usize, point: *const jolt_fr_t, eval: *const jolt_fr_t, v: *const jolt_fr_t, r: *const jolt_fr_t, q: *const jolt_fr_t, d0: *const jolt_fr_t, folding_ok: *mut i32, failed_level: *mut usize, l_scalars: *mut jolt_fr_t, d_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_hyperkzg_verify_with_transcript(ctx: *mut jolt_ctx, vs: *const jolt_hyperkzg_verifier_setup, commitments: *const jolt_g1_t, commitment_scalars: *const jolt_fr_t, n_commitments: usize, point: *const jolt_fr_t, ell: usize, eval: *const jolt_fr_t, com: *const jolt_g1_t, w: *const jolt_g1_t, v: *const jolt_fr_t, r#fn: jolt_open_transcript_fn, user: *mut c_void, accepted: *mut i32, failed_check: *mut i32, failed_level: *mut usize) -> i32;
+    pub fn jolt_host_hyperkzg_verify(ctx: *mut jolt_ctx, vs: *const jolt_hyperkzg_verifier_setup, commitments: *const jolt_g1_t, commitment_scalars: *const jolt_fr_t, n_commitments: usize, point: *const jolt_fr_t, ell: usize, eval: *const jolt_fr_t, com: *const jolt_g1_t, w: *const jolt_g1_t, v: *const jolt_fr_t, t: *mut jolt_host_transcript, accepted: *mut i32, failed_check: *mut i32, failed_level: *mut usize) -> i32;
+    pub fn jolt_host_hyperkzg_prove_batch(ctx: *mut jolt_ctx, srs: *const jolt_srs, sources: *const *const jolt_onehot, n_sources: usize, dense: *const *mut jolt_table, n_dense: usize, log_k: u32, evaluations: *const jolt_fr_t, n_claims: usize, point: *const jolt_fr_t, n_point: usize, hint: *const jolt_grid_hint, levels: u32, t: *mut jolt_host_transcript, com: *mut jolt_g1_t, w: *mut jolt_g1_t, v: *mut jolt_fr_t, challenges_out: *mut jolt_fr_t, joint_eval_out: *mut jolt_fr_t) -> i32;
+    pub fn jolt_host_hyperkzg_verify_batch(ctx: *mut jolt_ctx, vs: *const jolt_hyperkzg_verifier_setup, commitments: *const jolt_g1_t, evaluations: *const jolt_fr_t, n_claims: usize, point: *const jolt_fr_t, n_point: usize, com: *const jolt_g1_t, w: *const jolt_g1_t, v: *const jolt_fr_t, t: *mut jolt_host_transcript, accepted: *mut i32, failed_check: *mut i32, failed_level: *mut usize, joint_eval_out: *mut jolt_fr_t) -> i32;
     pub fn jolt_stage_op_num_rounds(op: *const jolt_stage_op, rounds: *mut usize) -> i32;
     pub fn jolt_stage_op_degree(op: *const jolt_stage_op, degree: *mut usize) -> i32;
     pub fn jolt_stage_op_input_claim(op: *mut jolt_stage_op, claim: *mut jolt_fr_t) -> i32;
